@@ -7,6 +7,7 @@ PCM written to HBM (4 B/sample, 11.8 GB per step per GPU).  A "step" is one rend
 C ABI (dusp_render_device): parameters and output stay resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config voices60|cfg4|cfg5] [--mode pcm|mixdown] [--gather]
+                  [--full] [--dump-outputs DIR]
 
   --config voices60  (default) weak scaling: --voices voices per GPU x --seconds
   --config cfg4      BASELINE configs[3]: 8192 feedback loops Osc -> Sum -> Delay(480) -> Filter(2000) -> Multiply(0.5) -> Sum x 10 s, sharded over the N GPUs
@@ -15,6 +16,13 @@ C ABI (dusp_render_device): parameters and output stay resident in HBM.
   --mode mixdown     the voices of a rank go through the reference's left-deep Sum.many chain (Sum.js:18-29) into one
                      channel; ranks' partial mixes are reduced onto rank 0 (voice-samples/s; not HBM-bound by construction)
   --gather           also time render + RCCL gather of the PCM onto rank 0, tile-pipelined (reported, never `value`)
+  --full             also measure what the headline figure does not need: the CPU-oracle baseline (`cpu_baseline`, --cpu-seconds
+                     per leg) and the box's write ceiling (a fill kernel over the same buffer: `roofline.write_ceiling_measured`).
+                     A plain run sets up, warms up, times the steps, writes its outputs if asked and prints the line.
+  --dump-outputs DIR after the timed steps, write the PCM of the last one as DIR/pcm.npy (f32, [instances, channels, samples]) or, above
+                     DUMP_MAX_VALUES samples, DIR/pcm_sample.npy: the samples at fixed seeded flat positions (same arguments, same
+                     inputs, same positions: two builds compare output for output).  On N > 1 GPUs rank r > 0 of a per-voice
+                     run writes its own voices as pcm_rank<r>[_sample].npy (the budget split over the ranks); a mix-down, rank 0 alone.
 
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks are already there (RANK / WORLD_SIZE in the
 environment); a bare `python bench.py --gpus N` starts them itself as child processes BEFORE this process touches the
@@ -53,11 +61,16 @@ def parse_args(argv=None):
     ap.add_argument("--seconds", type=float, default=None, help="rendered duration per voice (default: 60 / cfg5: 1)")
     ap.add_argument("--voices", type=int, default=None, help="voices per GPU (voices60, default 1024) / in total (cfg5, default 65536)")
     ap.add_argument("--sample-rate", type=int, default=48000)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-oracle baseline budget in seconds per leg (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: CPU-oracle baseline budget in seconds per leg (0 = skip)")
     ap.add_argument("--gather", action="store_true", help="also time render + gather of the PCM onto rank 0 (reported separately)")
     ap.add_argument("--gather-tile", type=int, default=0, help="voices per gather tile (0: shard / 8)")
     ap.add_argument("--engine", default="auto", choices=["auto", "chunk", "fused", "wave"])
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run the CPU-oracle baseline and the fill-kernel write ceiling (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's PCM (or a fixed seeded sample of it) as .npy files into DIR")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def visible_gpus():
@@ -135,6 +148,26 @@ def mixdown_program(cfg, sample_rate, first_voice, n_voices):
     freq = (lambda k: 10.0 * (k + 1)) if cfg == "voices60" else (lambda k: 20.0 + k / 8.0)
     mix = d.Sum.many([d.Osc(freq(k)) for k in range(first_voice, first_voice + n_voices)])
     return descriptor.extract(mix).words, None
+
+
+DUMP_MAX_VALUES = 8 << 20  # f32 samples --dump-outputs writes in all (32 MB): a larger output is sampled
+
+
+def dump_outputs(directory, pcm, name, max_values=DUMP_MAX_VALUES):
+    """Write the device tensor `pcm` (f32) as <directory>/<name>.npy when it holds at most `max_values` samples; else
+    <directory>/<name>_sample.npy, the samples at `max_values` flat positions drawn from a generator of fixed seed (duplicates
+    dropped, ascending): the positions depend on the output's size alone, so two runs with the same arguments write the same ones."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    flat = pcm.reshape(-1)
+    if flat.numel() <= max_values:
+        out, path = pcm.float().cpu().numpy(), os.path.join(directory, name + ".npy")
+    else:
+        pos = np.unique(np.random.default_rng(0).integers(0, flat.numel(), size=max_values, dtype=np.int64))
+        out, path = flat[torch.from_numpy(pos).to(flat.device)].float().cpu().numpy(), os.path.join(directory, name + "_sample.npy")
+    np.save(path, out)
+    return path
 
 
 def cpu_baseline(words, params, n_samples, budget_s):
@@ -302,6 +335,12 @@ def main():
     if not np.isfinite(head).all() or float(np.abs(head).max()) == 0.0:
         raise SystemExit("bench: rendered buffer is empty or non-finite")
 
+    if args.dump_outputs:  # (before anything below writes into d_out again)
+        if not mixdown:
+            dump_outputs(args.dump_outputs, d_out, "pcm" if rank == 0 else "pcm_rank%d" % rank, DUMP_MAX_VALUES // world)
+        elif rank == 0:
+            dump_outputs(args.dump_outputs, mix_root if chained else d_out, "pcm")
+
     gather_info = None
     if args.gather and not mixdown:
         # the north star's "trivial RCCL gather of rendered PCM over xGMI": render + gather, tile-pipelined (tile k+1 renders
@@ -342,7 +381,7 @@ def main():
     # buffer, after the timed region.  The roofline fraction is against the 8 TB/s paper peak; HBM3E sustains less
     # for a pure write stream, and how much varies from box to box.
     fill_ms = []
-    if rank == 0 and not mixdown:
+    if args.full and rank == 0 and not mixdown:
         for _ in range(4):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
@@ -403,7 +442,7 @@ def main():
             ceiling = algo_bytes / (min(fill_ms[1:]) * 1e-3) / 1e9
             line["roofline"]["write_ceiling_measured"] = {"GBps": round(ceiling, 1), "frac_of_it": round(achieved / ceiling, 4),
                                                           "what": "dusp_fill_device over the same buffer on this box, best of 3"}
-        if world == 1 and args.cpu_seconds > 0 and not mixdown:
+        if args.full and world == 1 and args.cpu_seconds > 0 and not mixdown:
             line["cpu_baseline"] = cpu_baseline(words, params, n_samples, args.cpu_seconds)
         # (fixed schema: the gather's fields are always there; null where --gather was not asked for)
         line["gather"] = gather_info or {"render_plus_gather_ms": None, "render_only_ms": None, "inbound_GBps": None, "per_link_GBps": None,

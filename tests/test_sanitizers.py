@@ -33,7 +33,9 @@ def test_oracle_under_asan_and_ubsan():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "asan"])
     libasan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"]).decode().strip()
     assert os.path.isabs(libasan) and os.path.exists(libasan), libasan
-    env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
+    # (the sanitizer run time must come first; whatever the environment already preloads stays behind it)
+    preload = " ".join([libasan] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else []))
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
                DUSP_ORACLE_LIB=os.path.join(ROOT, "oracle", "libdusp_oracle_asan.so"))
     p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_oracle_golden.py"), "-x", "-q", "-p", "no:cacheprovider"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, cwd=ROOT, timeout=1500)

@@ -169,15 +169,58 @@ def test_bench_gather_runs_at_one_rank():
 
 @pytest.mark.gpu
 def test_bench_renders_the_feedback_loops_of_configs_3():
-    """`bench.py --config cfg4` (BASELINE configs[3], a reduced set): the line names the workload, carries roofline and cpu_baseline."""
+    """`bench.py --config cfg4 --full` (BASELINE configs[3], a reduced set): the line names the workload, carries roofline and cpu_baseline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "cfg4", "--voices", "512", "--seconds", "0.5",
-                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, env=env)
+                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["config"]["workload"].startswith("configs[3] per-voice: 512 loops") and line["config"]["engine"] == "wave"
     assert "compiled kernel" in line["config"]["shape"] and line["scaling"] == "strong" and line["value"] > 0
     assert line["roofline"]["algorithmic_bytes_per_launch"] == 4.0 * 512 * 24000 and line["cpu_baseline"]["value"] > 0
+    assert line["roofline"]["write_ceiling_measured"]["GBps"] > 0
+
+
+def test_bench_dump_writes_a_whole_output_or_a_fixed_seeded_sample(tmp_path):
+    """bench.dump_outputs: an output within the budget is written whole; a larger one as the samples at seeded flat positions,
+    the same positions in every run (two builds compare output for output), within the budget."""
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(2 * 3 * 5, dtype=torch.float32).reshape(2, 3, 5)
+    path = bench.dump_outputs(str(tmp_path / "a"), small, "pcm", max_values=64)
+    assert path.endswith("pcm.npy") and np.array_equal(np.load(path), small.numpy())
+    big = torch.arange(1 << 20, dtype=torch.float32).reshape(4, 1, -1)  # (value = flat position, exact in f32)
+    one = np.load(bench.dump_outputs(str(tmp_path / "a"), big, "pcm", max_values=4096))
+    two = np.load(bench.dump_outputs(str(tmp_path / "b"), big, "pcm", max_values=4096))
+    assert one.dtype == np.float32 and 4000 < one.size <= 4096 and np.array_equal(one, two)
+    assert np.all(np.diff(one) > 0) and one[0] >= 0 and one[-1] < big.numel()
+    assert sorted(os.listdir(tmp_path / "a")) == ["pcm.npy", "pcm_sample.npy"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_what_it_rendered(tmp_path, oracle):
+    """A plain `bench.py` run (no --full) runs no CPU baseline and no fill kernel; `--steps` is the number of timed steps; `--dump-outputs`
+    writes a seeded sample of the last step's PCM, which equals the oracle's render of the same voices."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    n_voices, n_samples = 4096, 12000
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "cfg5", "--voices", str(n_voices), "--seconds", "0.25",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "cpu_baseline" not in line and "write_ceiling_measured" not in line["roofline"]
+    assert os.listdir(tmp_path) == ["pcm_sample.npy"]
+    got = np.load(tmp_path / "pcm_sample.npy")
+    sys.path.insert(0, ROOT)
+    import bench
+    assert got.dtype == np.float32 and got.nbytes <= 4 * bench.DUMP_MAX_VALUES
+    pos = np.unique(np.random.default_rng(0).integers(0, n_voices * n_samples, size=bench.DUMP_MAX_VALUES, dtype=np.int64))
+    assert got.shape == pos.shape and np.isfinite(got).all()
+    words, params = bench.voice_program("cfg5", 48000, n_samples, 0, n_voices)
+    for v in (0, 1, 2047, n_voices - 1):
+        want = oracle.render(words, n_samples, params=params, n_instances=n_voices, instance=v)[0]
+        mine = (pos >= v * n_samples) & (pos < (v + 1) * n_samples)
+        assert mine.sum() > 1000 and np.array_equal(got[mine], want[pos[mine] - v * n_samples]), "voice %d" % v
 
 
 # ---- one Sum.many chain over several ranks, bit for bit (shard.chain_mixdown / dusp_render_chain_window)
