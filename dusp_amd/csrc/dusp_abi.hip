@@ -421,7 +421,13 @@ static int finish_build(dusp_program *prog) {
         prog->wave = dusp::WavePlan();
         prog->wave.ramp_checked = std::move(checked);
     }
-    const bool fusable = dusp::plan_fused(prog->P, prog->fused);
+    bool fusable = dusp::plan_fused(prog->P, prog->fused);
+    // The fused sum chain keeps its phases in 32.32 fixed point: no nonzero entry of its table may lie below 2^-20.  At an odd rate the
+    // sine table's middle entry is sin(pi) ~ 1.2e-16 — there AUTO goes on to the next engine instead of building a program that cannot render.
+    if (fusable && prog->fused.kind == dusp::FUSED_SUMCHAIN && ctx->table_set[prog->fused.table_id] && !ctx->table_fx32_ok[prog->fused.table_id]) {
+        fusable = false;
+        prog->fused.why = "the sum chain's wave table has entries below 2^-20";
+    }
     const bool wavable = dusp::plan_wave(prog->P, prog->wave, prog->resumable);
     for (size_t k = 0; k < prog->wave.osc_level.size() && k < prog->P.ops.size(); k++)  // FM depth, for time-split rendering
         if (prog->wave.osc_level[k] >= 0) prog->P.ops[k].d[0] = (double)prog->wave.osc_level[k];
@@ -889,14 +895,14 @@ static int render_jit(dusp_program *prog, uint32_t n_inst, size_t n_samples, uin
     opt.filter_fma = ctx->knobs.filter_fma != 0;
     opt.nt_stores = ctx->knobs.jit_nt == 1 || (ctx->knobs.jit_nt == 2 && P.ring_samples != 0);
     for (int k = 0; k < dusp::kNumTables; k++) opt.table_form[k] = ctx->table_form[k], opt.table_delta[k] = ctx->knobs.jit_lean ? ctx->table_delta[k] : 0, opt.table_bound[k] = ctx->table_bound[k];
-    // the LDS image goes to the first oscillator table that needs one (saw / square / triangle are evaluated, not looked up)
-    for (const dusp::DevOp &op : P.ops)
-        if ((op.op == dusp::OP_OSC || op.op == dusp::OP_MULTI_OSC) && opt.lds_table < 0 && ctx->knobs.jit_lds_table != 0 && ctx->table_antisym[op.attr] && P.g.sample_rate % 2 == 0 &&
-            !(ctx->table_form[op.attr] >= dusp::TABLE_FORM_SAW && ctx->table_form[op.attr] <= dusp::TABLE_FORM_TRIANGLE)) {
-            opt.lds_table = ctx->table_form[op.attr] == dusp::TABLE_FORM_8BIT && ctx->table_antisym[0] ? 0 : op.attr;  // (the sine image serves 8bit too)
-            opt.table_bytes = dusp::half_table_lds_bytes((uint32_t)P.g.sample_rate);
-        }
     opt.scratch_floats = dusp::jit_scratch_floats(P);
+    // the LDS image goes to the first oscillator table that needs one (saw / square / triangle are evaluated, not looked up), where it fits
+    int image = -1;
+    for (const dusp::DevOp &op : P.ops)
+        if ((op.op == dusp::OP_OSC || op.op == dusp::OP_MULTI_OSC) && image < 0 && ctx->knobs.jit_lds_table != 0 && ctx->table_antisym[op.attr] && P.g.sample_rate % 2 == 0 &&
+            !(ctx->table_form[op.attr] >= dusp::TABLE_FORM_SAW && ctx->table_form[op.attr] <= dusp::TABLE_FORM_TRIANGLE))
+            image = ctx->table_form[op.attr] == dusp::TABLE_FORM_8BIT && ctx->table_antisym[0] ? 0 : op.attr;  // (the sine image serves 8bit too)
+    dusp::jit_place_table(opt, image, (uint32_t)P.g.sample_rate);
     // Filters whose cutoff is a constant of the circuit, high enough for the bound of jit_filter_scan_ok: a scan over the chunk, the circuit
     // an ordinary one (no Filter stage).  Not for programs that are continued (the stage's y1 / y2 are what the other engines hand over).
     opt.filter_scan = ctx->knobs.filter_scan != 0 && !persistent && !a.warm && dusp::jit_filter_scan_ok(P, ctx->table_bound, ctx->knobs.filter_scan == 2 ? 2 : 1);
@@ -920,10 +926,9 @@ static int render_jit(dusp_program *prog, uint32_t n_inst, size_t n_samples, uin
     int most = 16;
     if (ctx->knobs.wave_max_waves > 0) most = std::max(1, std::min(most, ctx->knobs.wave_max_waves));
     // the sequential-stage units' per-wave scratch comes out of the same 160 KiB: as many wavefronts as fit next to the table image
-    // (a power of two; the table image goes only when not even one wave's scratch fits beside it)
+    // (a power of two; jit_place_table has left the table image out where not even one wave's scratch fits beside it)
     if (opt.scratch_floats) {
         const size_t scratch = opt.scratch_floats * 4;
-        if (opt.table_bytes + scratch > 160 * 1024) opt.lds_table = -1, opt.table_bytes = 0;
         while (most > 1 && opt.table_bytes + (size_t)most * scratch > 160 * 1024) most /= 2;
     }
     const size_t budget = 160 * 1024 - (size_t)most * opt.scratch_floats * 4;

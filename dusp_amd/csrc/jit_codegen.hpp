@@ -71,6 +71,17 @@ struct JitOptions {
                              // inside the Filter stage's serial part and leaves the sums in JitArgs::debug
 };
 
+// The oscillators' half-table image in LDS, for the table `table_id` (-1: none wanted): only where one wavefront's scratch
+// (opt.scratch_floats) still fits beside it in the workgroup's 160 KiB.  Elsewhere — every circuit from 88.2 kHz on, where the image
+// alone takes 182 KB or more — the lookups gather from global memory (lds_table = -1).  The render path (dusp_abi.hip) and the
+// host-only option logic (jit_source_from_descriptor) both place the image through this one test.
+inline void jit_place_table(JitOptions &opt, int table_id, uint32_t sample_rate) {
+    const size_t bytes = (size_t)half_table_image_bytes(sample_rate);
+    const bool fits = table_id >= 0 && bytes + opt.scratch_floats * 4 <= 160 * 1024;
+    opt.lds_table = fits ? table_id : -1;
+    opt.table_bytes = fits ? bytes : 0;
+}
+
 // Where an oscillator's table comes from in a generated kernel (jit_prelude.hpp jit_pair): 1 the LDS half image, 2 a closed form
 // of the index, 3 8bit derived from the sine image, 0 a gather from L2.
 inline int jit_table_source(const JitOptions &opt, int table_id) {
@@ -2057,11 +2068,9 @@ inline int jit_source_from_descriptor(const double *desc, size_t n_words, const 
         opt.table_form[4] = 4;  // TABLE_FORM_8BIT
         for (int k = 0; k < 5; k++) opt.table_bound[k] = 1;  // (the oscillators' tables stay within [-1, 1])
         opt.table_delta[0] = rq.lean ? 1 : 0;  // (the sine table: differences of neighbours exact in f64 at any sample rate, in f32 at some — 44.1 kHz, not 48)
-        for (const DevOp &op : P.ops)
-            if ((op.op == OP_OSC || op.op == OP_MULTI_OSC) && opt.lds_table < 0 && (op.attr == 0 || op.attr == 4)) {
-                opt.lds_table = 0;
-                opt.table_bytes = (size_t)half_table_image_bytes((uint32_t)P.g.sample_rate);
-            }
+        bool wants_image = false;
+        for (const DevOp &op : P.ops) wants_image = wants_image || ((op.op == OP_OSC || op.op == OP_MULTI_OSC) && (op.attr == 0 || op.attr == 4));
+        jit_place_table(opt, wants_image ? 0 : -1, (uint32_t)P.g.sample_rate);
     }
     opt.filter_scan = !continued && rq.scan_knob != 0 && jit_filter_scan_ok(P, opt.table_bound, rq.scan_knob == 2 ? 2 : 1);
     opt.filter_stages = opt.filter_scan ? 0 : jit_filter_stages(P);
@@ -2072,8 +2081,12 @@ inline int jit_source_from_descriptor(const double *desc, size_t n_words, const 
         if (lines && opt.table_bytes + 16 * (opt.scratch_floats + lines) * 4 <= 160 * 1024) opt.line_floats = lines, opt.scratch_floats += lines;
     }
     if (plan.has_filter && !opt.filter_scan) {
-        const size_t used = opt.table_bytes + (size_t)rq.waves * opt.scratch_floats * 4;
-        opt.filter_sub = used < 160 * 1024 ? jit_filter_sub(rq.waves, rq.per_wave, opt.filter_stages, 160 * 1024 - used, opt.filter_mod) : 0;
+        for (;;) {
+            const size_t used = opt.table_bytes + (size_t)rq.waves * opt.scratch_floats * 4;
+            opt.filter_sub = used < 160 * 1024 ? jit_filter_sub(rq.waves, rq.per_wave, opt.filter_stages, 160 * 1024 - used, opt.filter_mod) : 0;
+            if (opt.filter_sub || opt.lds_table < 0) break;
+            opt.lds_table = -1, opt.table_bytes = 0;  // (as a render does: the rows keep their geometry, the table image goes)
+        }
         if (!opt.filter_sub) {
             err = "waves x per_wave Filter rows do not fit LDS";
             return 1;

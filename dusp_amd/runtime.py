@@ -183,10 +183,7 @@ class Context:
         """Compute (or take) the wave tables (ids 0-4) and Shape tables (ids 5-8) for this sample rate and hand
         them to the device."""
         for tid in range(N_TABLES):
-            try:
-                t = tables[tid] if tables is not None else make_table(tid, sample_rate)
-            except ValueError:
-                continue  # e.g. no triangle table at a sample rate not divisible by 4
+            t = tables[tid] if tables is not None else make_table(tid, sample_rate)  # (every table is defined at every rate, as in the reference)
             t = np.ascontiguousarray(t, dtype=np.float32)
             self._check(self._L.dusp_table_upload(self._h, tid, t.ctypes.data, t.size))
         self.sample_rate = sample_rate

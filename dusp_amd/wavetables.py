@@ -1,9 +1,10 @@
 """Oscillator wave tables, computed on the host exactly as the reference does
 (src/components/Osc/waveTables.js:5-40) and uploaded to the device as data.
 
-`math.sin` (libm) reproduces V8's Math.sin on every entry of the 44.1 k and
-48 k tables after the f32 store — tests/test_wavetables.py checks the sha256
-of all five tables against hashes captured from the reference.
+`math.sin` (libm) reproduces V8's Math.sin on every entry of the tables at
+every sample rate the goldens cover after the f32 store — tests/test_host_graph.py
+and tests/test_sample_rates.py check the sha256 of all nine tables against
+hashes captured from the reference (tests/golden/wavetables*.json).
 """
 import math
 
@@ -30,20 +31,21 @@ def make_table(table_id, sample_rate):
             out[:] = [_js_round(float(v) * 128.0) / 128.0 for v in out]
     elif table_id == 1:     # saw; the loop stops at sr so the last entry stays 0
         out[:sample_rate] = [-1 + t * 2 / n for t in range(sample_rate)]
-    elif table_id == 2:     # square
-        if sample_rate % 2:
-            raise ValueError("square table needs an even sample rate")
+    elif table_id == 2:     # square; TypedArray fill truncates its bounds: at an odd rate the +1 half ends at floor(sr / 2)
         out[: sample_rate // 2] = 1
         out[sample_rate // 2:] = -1
     elif table_id == 3:     # triangle; later quarters re-read the f32-rounded first quarter
-        if sample_rate % 4:
-            raise ValueError("triangle table needs a sample rate divisible by 4")
-        q = sample_rate // 4
+        # The quarter is sr / 4, a fraction unless 4 | sr: t runs while t < sr / 4, and a store to a fractional index of a typed
+        # array is dropped, so only the quarters at whole offsets k * sr / 4 are written; the rest of the table stays 0.
+        q = (sample_rate + 3) // 4  # entries of the first quarter: t = 0 .. ceil(sr / 4) - 1
         first = np.array([t / sample_rate * 4 for t in range(q)], dtype=np.float32)
         out[:q] = first
-        out[q:2 * q] = (1 - first.astype(np.float64)).astype(np.float32)
-        out[2 * q:3 * q] = -first
-        out[3 * q:4 * q] = (-1 + first.astype(np.float64)).astype(np.float32)
+        if sample_rate % 4 == 0:
+            out[q:2 * q] = (1 - first.astype(np.float64)).astype(np.float32)
+            out[3 * q:4 * q] = (-1 + first.astype(np.float64)).astype(np.float32)
+        if sample_rate % 2 == 0:
+            h = sample_rate // 2
+            out[h:h + q] = -first
         out[sample_rate] = 0
     elif 5 <= table_id <= 8:  # Shape tables: func(x / sampleRate), x = 0..sampleRate (Shape/shapeTables.js:3-38)
         func = {5: lambda x: 1 - x, 6: lambda x: x, 7: lambda x: math.sin(math.pi * x), 8: lambda x: (1 - x) * (1 - x)}[table_id]

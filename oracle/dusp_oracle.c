@@ -179,19 +179,18 @@ int dusp_oracle_wavetable(int id, int sr, float *out) {
         for (int t = 0; t < sr; t++) out[t] = (float)(-1 + t * 2.0 / n);
         out[sr] = 0;
         return 0;
-    case 2: /* square :24-26 */
-        if (sr % 2) return -1;
+    case 2: /* square :24-26 — TypedArray fill truncates its bounds: at an odd rate the +1 half ends at floor(sr / 2) */
         for (int t = 0; t < n; t++) out[t] = t < sr / 2 ? 1.f : -1.f;
         return 0;
-    case 3: { /* triangle :14-22 — later quarters read the f32-rounded first quarter back */
-        if (sr % 4) return -1;
-        const int q = sr / 4;
+    case 3: { /* triangle :14-22 — later quarters read the f32-rounded first quarter back.  The quarter is sr / 4, a fraction
+               * unless 4 | sr: t runs while t < sr / 4, and a store to a fractional index of a typed array is dropped, so only
+               * the quarters at whole offsets (k * sr / 4, k = 0..3) are written; the rest of the table stays 0 */
         memset(out, 0, (size_t)n * sizeof(float));
-        for (int t = 0; t < q; t++) {
+        for (int t = 0; 4 * t < sr; t++) {
             out[t] = (float)((double)t / sr * 4);
-            out[t + q] = (float)(1 - (double)out[t]);
-            out[t + 2 * q] = (float)(-(double)out[t]);
-            out[t + 3 * q] = (float)(-1 + (double)out[t]);
+            if (sr % 4 == 0) out[t + sr / 4] = (float)(1 - (double)out[t]);
+            if (sr % 2 == 0) out[t + sr / 2] = (float)(-(double)out[t]);
+            if (sr % 4 == 0) out[t + 3 * (sr / 4)] = (float)(-1 + (double)out[t]);
         }
         out[sr] = 0;
         return 0;
