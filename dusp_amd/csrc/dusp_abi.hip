@@ -22,6 +22,7 @@
 #include "fused_plan.hpp"
 #include "jit_codegen.hpp"
 #include "jit_engine.hpp"
+#include "jit_plan.hpp"
 #include "program.hpp"
 #include "ring_windows.hpp"
 #include "table_checks.hpp"
@@ -147,7 +148,7 @@ struct dusp_program {
     // WAVE programs the circuit compiler takes (jit_codegen.hpp): generated text per workgroup geometry, constants on the device
     bool jit_ok = false;
     std::string jit_why;
-    std::map<std::pair<int, int>, dusp::JitSource> jit_src;  // (wavefronts per workgroup, 8 x instances per wavefront + Filter block) -> kernel text (+ constants, scan list)
+    std::map<std::pair<int, int>, dusp::JitSource> jit_src;  // jit_plan.hpp jit_source_key -> kernel text (+ constants, scan list)
     bool jit_consts_uploaded = false;
     int voice_loop = -1;  // the circuit's voices run in a loop on its compiled kernel (jit_codegen.hpp VoicePlan): -1 not looked at yet
     // dusp_render_chain_window: the window the next render of this (sum chain) program is (set for the duration of that call)
@@ -746,317 +747,189 @@ static hipError_t zero_rings(dusp_program *prog, uint32_t n_pad, uint32_t n_chun
     return hipSuccess;
 }
 
-// handoff_chunks > 0: this launch continues a render whose first handoff_chunks chunks the chunk engine has just rendered (Program::warm_ops):
-// start state in d_handoff_init, rings and outlets' last chunk already in this kernel's layout.
-// probe: only find out whether the kernel is at hand (DUSP_OK) or being compiled in the background (kJitLater); nothing is launched.
-static int render_jit(dusp_program *prog, uint32_t n_inst, size_t n_samples, uint32_t n_chunks, const float *d_params, const float *d_inputs, float *d_out,
-                      hipStream_t stream, uint32_t handoff_chunks = 0, bool probe = false) {
-    dusp_ctx *ctx = prog->ctx;
-    const dusp::Program &P = prog->P;
-    const uint32_t n_pad = (n_inst + 63u) & ~63u;
-    const size_t n_slots = P.init_state.size();
-    const bool persistent = (prog->resumable && prog->persistent) || handoff_chunks > 0;
-    const bool resume = prog->keep_memory || handoff_chunks > 0;
-    if (resume && !handoff_chunks && n_inst != prog->last_n_inst) CTX_FAIL(ctx, DUSP_ERR_STATE, "render: the instance count cannot change while a program is being continued");
-    // Per-instance (parameter) delays: the kernel a Delay gets depends on where its instances' values lie — all of at least a chunk
-    // (write-once ring), all below a chunk (no ring), or neither (ordered slot operations) — so the column is looked at first
-    // (one small launch + a few bytes back; only programs with such a unit pay it).  The verdict lives in the operand's spare word.
-    // Per-instance CUTOFFS of Filters likewise: whether the Filter may run as a scan (jit_filter_scan_ok) depends on the range of the
-    // column — its smallest and largest value travel back with the Delays' verdicts, behind the same synchronisation.
-    {
-        std::vector<int64_t> entries;
-        std::vector<size_t> which, filters;
-        std::vector<int> slots;
-        for (size_t k = 0; k < prog->P.ops.size(); k++) {
-            const dusp::DevOp &op = prog->P.ops[k];
-            if ((op.op == dusp::OP_DELAY || op.op == dusp::OP_MONO_DELAY) && op.in[1].kind == dusp::SRC_PARAM) {
-                entries.insert(entries.end(), {(int64_t)op.in[1].idx, op.ring_len, (int64_t)(op.op == dusp::OP_MONO_DELAY)});
-                which.push_back(k);
-            }
-            if (op.op == dusp::OP_FILTER && op.in[1].kind == dusp::SRC_PARAM && ctx->knobs.filter_scan != 0 && !persistent) {
-                slots.push_back(op.in[1].idx);
-                filters.push_back(k);
-            }
-        }
-        if (!which.empty() || !filters.empty()) {
-            const size_t n = which.size(), nf = filters.size();
-            HIP_TRY(ctx, prog->d_jit_regime.ensure(4 * n + 2 * nf + 2));  // [3 n] entries as int64, n verdicts (one int64 slot each), then nf slots (int) and 3 nf range words (unsigned)
-            int64_t *d_entries = prog->d_jit_regime.p;
-            int *d_bits = (int *)(prog->d_jit_regime.p + 3 * n);
-            int *d_slots = (int *)(prog->d_jit_regime.p + 4 * n);
-            unsigned *d_range = (unsigned *)(d_slots + nf);
-            std::vector<int> bits(n, 0);
-            std::vector<unsigned> range(3 * nf, 0u);
-            if (n) {
-                HIP_TRY(ctx, hipMemcpyAsync(d_entries, entries.data(), 3 * n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-                HIP_TRY(ctx, hipMemsetAsync(d_bits, 0, n * sizeof(int64_t), stream));
-                HIP_TRY(ctx, dusp::jit_launch_classify_delays(d_params, n_inst, d_entries, (int)n, d_bits, stream));
-                HIP_TRY(ctx, hipMemcpyAsync(bits.data(), d_bits, n * sizeof(int), hipMemcpyDeviceToHost, stream));
-            }
-            if (nf) {
-                HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), nf * sizeof(int), hipMemcpyHostToDevice, stream));
-                HIP_TRY(ctx, hipMemsetAsync(d_range, 0, 3 * nf * sizeof(unsigned), stream));
-                HIP_TRY(ctx, dusp::jit_launch_column_range(d_params, n_inst, d_slots, (int)nf, d_range, stream));
-                HIP_TRY(ctx, hipMemcpyAsync(range.data(), d_range, 3 * nf * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-            }
-            HIP_TRY(ctx, hipStreamSynchronize(stream));
-            bool changed = false;
-            for (size_t i = 0; i < n; i++) {
-                const int regime = bits[i] == dusp::DELAY_REGIME_LONG || bits[i] == dusp::DELAY_REGIME_SHORT ? bits[i] : dusp::DELAY_REGIME_OTHER;
-                int32_t &pad = prog->P.ops[which[i]].in[1].pad;
-                changed = changed || pad != regime;
-                pad = regime;
-            }
-            for (size_t i = 0; i < nf; i++) {  // (the range itself is no part of the text: only whether the circuit's Filters scan — the key of jit_src — is)
-                dusp::DevOp &op = prog->P.ops[filters[i]];
-                const bool known = range[3 * i + 2] == 0u && range[3 * i] != 0u && range[3 * i + 1] != 0u;
-                op.in[1].pad = known ? dusp::kFilterColumnKnown : 0;
-                if (known) {
-                    float lo, hi;
-                    const unsigned lo_bits = 0x7fffffffu - range[3 * i], hi_bits = range[3 * i + 1];
-                    std::memcpy(&lo, &lo_bits, 4);
-                    std::memcpy(&hi, &hi_bits, 4);
-                    op.d[0] = (double)lo;
-                    op.d[1] = (double)hi;
-                }
-            }
-            if (changed) {  // (another kernel text: the generated units differ)
-                prog->jit_src.clear();
-                prog->jit_consts_uploaded = false;
-            }
-        }
-    }
-    if (prog->jit_table_generation != ctx->table_generation) {  // a table was uploaded since: forms / the LDS image may have changed
-        prog->jit_src.clear();
-        prog->jit_consts_uploaded = false;
-        prog->jit_table_generation = ctx->table_generation;
-    }
-
+// What the steps of render_jit hand on to each other
+struct JitRender {
     dusp::JitArgs a{};
-    a.params = d_params;
-    a.tables = ctx->d_tables;
-    a.inputs = d_inputs;
-    a.out = d_out;
-    a.state = prog->d_state.p;
-    a.init_state = handoff_chunks ? prog->d_handoff_init.p : prog->d_init.p;
-    a.n_samples = n_samples;
-    a.ring_samples = (uint64_t)P.ring_samples;
-    a.clock0 = (uint64_t)P.g.clock0 + (uint64_t)handoff_chunks * dusp::kChunk;
-    a.n_inst = n_inst;
-    a.n_pad = n_pad;
-    a.n_groups = n_chunks;
-    a.sample_rate = (uint32_t)P.g.sample_rate;
-    a.table_stride = ctx->table_stride;
-    a.vec4_ok = (n_samples % 4 == 0) && (((uintptr_t)d_out & 15) == 0);
-    a.n_out = (uint32_t)P.out_bufs.size();
-    // Few instances, long render: cut time into segments so that the whole chip works on it
-    a.n_seg = 1;
-    a.seg_groups = n_chunks;
-    if (prog->voice_loop < 0) {
-        dusp::VoicePlan voices;
-        prog->voice_loop = !persistent && P.ops.size() > dusp::jit_loop_voices_from() && dusp::jit_find_voices(P, prog->wave, voices) ? 1 : 0;
-    }
-    if (prog->wave.splittable && !ctx->knobs.jit_force_waves) {
-        const uint64_t target = (uint64_t)ctx->n_cus * 8;  // wavefronts that fill the chip
-        uint64_t n_seg = n_inst >= target ? 1 : std::min<uint64_t>(target / n_inst, n_chunks / 8);
-        if (ctx->knobs.wave_segments >= 0) n_seg = (uint64_t)ctx->knobs.wave_segments;
-        n_seg = std::max<uint64_t>(1, std::min<uint64_t>(n_seg, n_chunks));
-        if (n_seg > 1) {
-            a.seg_groups = (uint32_t)((n_chunks + n_seg - 1) / n_seg);
-            a.n_seg = (uint32_t)((n_chunks + a.seg_groups - 1) / a.seg_groups);  // no empty segments
-        }
-    }
-    // A few circuits with Filters, long: segments that warm up (jit_codegen.hpp jit_warm_chunks) — every segment starts a segment early, from rest,
-    // its Filters merge with the sequential trajectory on the way (checked below, after the launch), and only its own chunks are stored
-    // (a Filter stage's serving wave runs 32 recurrences side by side at the price of one: the chip is full at 32 rows a CU, so up to a quarter of that many
-    // instances are still worth cutting)
-    if ((uint64_t)n_inst * 4 <= (uint64_t)ctx->n_cus * 32 && !persistent && !resume && !handoff_chunks && !d_inputs && !ctx->knobs.jit_force_waves && ctx->knobs.filter_warm != 0 && ctx->knobs.wave_segments != 0 &&
-        ctx->knobs.wave_segments != 1) {
-        const uint32_t warm_chunks = dusp::jit_warm_chunks(P, prog->wave);
-        if (warm_chunks) {
-            // (DUSP_FILTER_WARM=n > 1, tests: segments of n chunks whatever the Filters need — too short a warm-up shows in the check, and the render is finished sequentially)
-            const uint64_t target = (uint64_t)ctx->n_cus * 32, per = ctx->knobs.filter_warm > 1 ? (uint64_t)ctx->knobs.filter_warm : std::max<uint64_t>(8, warm_chunks);
-            uint64_t n_seg = std::min<uint64_t>(target / n_inst, n_chunks / per);
-            if (ctx->knobs.wave_segments > 1) n_seg = std::min<uint64_t>((uint64_t)ctx->knobs.wave_segments, n_chunks / per);
-            if (n_seg >= (ctx->knobs.filter_warm > 1 ? 2u : 4u)) {  // (below that the warm-up costs what the split gains)
-                a.seg_groups = (uint32_t)((n_chunks + n_seg - 1) / n_seg);
-                a.n_seg = (uint32_t)((n_chunks + a.seg_groups - 1) / a.seg_groups);
-                a.warm = 1u;
-            }
-        }
-    }
-    // Voices in a loop (jit_codegen.hpp VoicePlan): where the circuit is a sum of isomorphic voices above jit_loop_voices_from() units
-    const bool voice_loop = prog->voice_loop != 0;
-    // workgroup geometry: as many wavefronts as LDS holds next to the table image, no more than gives every CU a workgroup
-    dusp::JitOptions opt;
-    opt.persistent = persistent;
-    opt.voice_loop = voice_loop;
-    opt.profile = ctx->knobs.jit_profile != 0;
-    opt.filter_fma = ctx->knobs.filter_fma != 0;
-    opt.nt_stores = ctx->knobs.jit_nt == 1 || (ctx->knobs.jit_nt == 2 && P.ring_samples != 0);
-    for (int k = 0; k < dusp::kNumTables; k++) opt.table_form[k] = ctx->table_form[k], opt.table_delta[k] = ctx->knobs.jit_lean ? ctx->table_delta[k] : 0, opt.table_bound[k] = ctx->table_bound[k];
-    opt.scratch_floats = dusp::jit_scratch_floats(P);
-    // the LDS image goes to the first oscillator table that needs one (saw / square / triangle are evaluated, not looked up), where it fits
-    int image = -1;
-    for (const dusp::DevOp &op : P.ops)
-        if ((op.op == dusp::OP_OSC || op.op == dusp::OP_MULTI_OSC) && image < 0 && ctx->knobs.jit_lds_table != 0 && ctx->table_antisym[op.attr] && P.g.sample_rate % 2 == 0 &&
-            !(ctx->table_form[op.attr] >= dusp::TABLE_FORM_SAW && ctx->table_form[op.attr] <= dusp::TABLE_FORM_TRIANGLE))
-            image = ctx->table_form[op.attr] == dusp::TABLE_FORM_8BIT && ctx->table_antisym[0] ? 0 : op.attr;  // (the sine image serves 8bit too)
-    dusp::jit_place_table(opt, image, (uint32_t)P.g.sample_rate);
-    // Filters whose cutoff is a constant of the circuit, high enough for the bound of jit_filter_scan_ok: a scan over the chunk, the circuit
-    // an ordinary one (no Filter stage).  Not for programs that are continued (the stage's y1 / y2 are what the other engines hand over).
-    opt.filter_scan = ctx->knobs.filter_scan != 0 && !persistent && !a.warm && dusp::jit_filter_scan_ok(P, ctx->table_bound, ctx->knobs.filter_scan == 2 ? 2 : 1);
-    if (!ctx->knobs.jit_rotate) opt.rotate = false;
-    if (a.warm) opt.warm = true, opt.rotate = false;  // (what a stage holds at the top of a chunk must be the chunk before's: nothing of the next one computed ahead)
-    opt.filter_stages = opt.filter_scan ? 0 : dusp::jit_filter_stages(P);
-    opt.filter_mod = !opt.filter_scan && dusp::jit_filter_mod(P);
-    // Constant delays of a chunk at least as lines of input samples in LDS (JitDelayLine) instead of rings in memory: where the circuit
-    // has no Filter stage (whose overlap splits a Delay's tick), the render is not continued, and all the lines fit at 16 wavefronts next
-    // to the table image and the shared scratch — one instance per wavefront.
-    if (ctx->knobs.delay_line != 0 && !persistent && opt.filter_stages == 0 && a.n_seg == 1 && !opt.voice_loop && !(ctx->knobs.jit_force_waves && ctx->knobs.jit_force_per_wave > 1)) {
-        opt.line_whole_only = ctx->knobs.delay_line == 2;
-        const size_t lines = dusp::jit_delay_lines(P, opt.line_whole_only);
-        if (lines && opt.table_bytes + 16 * (opt.scratch_floats + lines) * 4 <= 160 * 1024) {
-            opt.line_floats = lines;
-            opt.scratch_floats += lines;
-        }
-    }
-    const uint64_t n_virtual = (uint64_t)n_inst * a.n_seg;
-    const unsigned want = (unsigned)((n_virtual + 255) / 256);
-    int most = 16;
-    if (ctx->knobs.wave_max_waves > 0) most = std::max(1, std::min(most, ctx->knobs.wave_max_waves));
-    // the sequential-stage units' per-wave scratch comes out of the same 160 KiB: as many wavefronts as fit next to the table image
-    // (a power of two; jit_place_table has left the table image out where not even one wave's scratch fits beside it)
-    if (opt.scratch_floats) {
-        const size_t scratch = opt.scratch_floats * 4;
-        while (most > 1 && opt.table_bytes + (size_t)most * scratch > 160 * 1024) most /= 2;
-    }
-    const size_t budget = 160 * 1024 - (size_t)most * opt.scratch_floats * 4;
-    int waves = 1, per_wave = 1;
-    // (the lines are per wavefront; a wavefront walks ONE segment's chunks: the chunk loop has one counter)
-    const int per_wave_cap = opt.line_floats || a.n_seg > 1 ? 1 : ctx->knobs.wave_per_wave >= 1 ? std::min(4, ctx->knobs.wave_per_wave) : 4;
-    const bool filter_stage = opt.filter_stages > 0;
-    if (filter_stage) {
-        // The Filter stage runs one recurrence per lane of ONE wave: a workgroup wants as many instances (rows) as that wave has
-        // lanes, and every CU the same number of rounds — rows = instances per CU / rounds, spread over up to 16 wavefronts.
-        const uint64_t per_cu = (n_virtual + (uint64_t)ctx->n_cus - 1) / (uint64_t)ctx->n_cus;  // (instances, or the segments of one)
-        const uint64_t rounds = (per_cu + 63) / 64;
-        const int rows = (int)std::max<uint64_t>(1, (per_cu + rounds - 1) / rounds);
-        waves = std::min(most, rows);
-        per_wave = std::min(per_wave_cap, (rows + waves - 1) / waves);
-        // (16 wavefronts of FOUR instances — 128 registers a lane — spill 170-470 bytes in every Filter circuit measured, filter(osc) included, and end at 16 x 2 two
-        // compiles later: start there.  A first render of such a structure: 2.1-3.3 s -> one compile)
-        if (waves == 16 && per_wave == 4 && ctx->knobs.wave_per_wave < 4) per_wave = 2;
-        opt.filter_sub = dusp::jit_filter_sub(waves, per_wave, opt.filter_stages, budget - opt.table_bytes, opt.filter_mod);
-        // (a connected cutoff parks three values per sample in two sets of rows: fewer rows per workgroup before the table image goes)
-        while (opt.filter_mod && !opt.filter_sub && (per_wave > 1 || waves > 1)) {
-            if (per_wave > 1) per_wave /= 2;
-            else waves /= 2;
-            opt.filter_sub = dusp::jit_filter_sub(waves, per_wave, opt.filter_stages, budget - opt.table_bytes, opt.filter_mod);
-        }
-        if (!opt.filter_sub) {  // (cannot happen with a 99 KB image: 64 rows of 64 samples take 33 KB)
-            opt.lds_table = -1, opt.table_bytes = 0;
-            opt.filter_sub = dusp::jit_filter_sub(waves, per_wave, opt.filter_stages, budget, opt.filter_mod);
-        }
-    } else {
-        while (waves < most && (unsigned)waves < want) waves *= 2;
-        // instances per wavefront (unsplit renders of light circuits, jit_light): 4 or 2 while that leaves every CU a workgroup —
-        // their independent unit blocks fill each other's latencies
-        // (not next to the table image: since the oscillators' delta form — 17 instructions a sample instead of 26 — one instance per wave is
-        // the faster: osc(k) 0.66 / 0.70 / 0.69 ms at 1 / 2 / 4, mul(osc, k) 0.68 / 0.66 / 0.70; ramp and timer graphs 0.79 / 0.66 / 0.63)
-        if (a.n_seg == 1 && ((dusp::jit_light(P) && opt.lds_table < 0) || ctx->knobs.wave_per_wave > 1))
-            for (int r : {4, 2})
-                if (r <= per_wave_cap && (uint64_t)ctx->n_cus * waves * r <= n_inst) {
-                    per_wave = r;
-                    break;
-                }
-    }
-
-    if (ctx->knobs.jit_force_waves) {  // tests: this geometry, whatever the batch
-        waves = std::min(most, ctx->knobs.jit_force_waves);
-        per_wave = ctx->knobs.jit_force_per_wave;
-        if (filter_stage) {
-            opt.filter_sub = dusp::jit_filter_sub(waves, per_wave, opt.filter_stages, budget - opt.table_bytes, opt.filter_mod);
-            if (!opt.filter_sub) CTX_FAIL(ctx, DUSP_ERR_ARG, "render: DUSP_JIT_FORCE: the Filter stage's rows do not fit LDS at this geometry");
-        }
-    }
-
+    dusp::JitPlan plan;
     hipFunction_t render = nullptr;
     dusp::JitSource *src = nullptr;
-    int jit_scratch = 0;
-    for (;;) {  // a kernel that spills (128 registers per lane at 16 wavefronts) is rebuilt for fewer instances per wave, then fewer waves
-        opt.waves = waves;
-        opt.per_wave = per_wave;
-        auto it = prog->jit_src.find({waves, per_wave * 8 + opt.filter_block % 8 + (opt.voice_loop ? 64 : 0) + (opt.filter_scan ? 128 : 0) + (opt.rotate ? 0 : 256)});
+    int scratch = 0;    // bytes of scratch per lane of the kernel at hand
+    unsigned grid = 0;  // workgroups of the render launch
+    DevBuf<unsigned long long> d_debug;  // diagnostic build: what wave 0 of every workgroup measured
+};
+
+// Per-instance (parameter) delays: the kernel a Delay gets depends on where its instances' values lie — all of at least a chunk
+// (write-once ring), all below a chunk (no ring), or neither (ordered slot operations) — so the column is looked at first
+// (one small launch + a few bytes back; only programs with such a unit pay it).  The verdict lives in the operand's spare word.
+// Per-instance CUTOFFS of Filters likewise: whether the Filter may run as a scan (jit_filter_scan_ok) depends on the range of the
+// column — its smallest and largest value travel back with the Delays' verdicts, behind the same synchronisation.
+static int jit_classify_columns(dusp_program *prog, uint32_t n_inst, const float *d_params, bool persistent, hipStream_t stream) {
+    dusp_ctx *ctx = prog->ctx;
+    std::vector<int64_t> entries;
+    std::vector<size_t> which, filters;
+    std::vector<int> slots;
+    for (size_t k = 0; k < prog->P.ops.size(); k++) {
+        const dusp::DevOp &op = prog->P.ops[k];
+        if ((op.op == dusp::OP_DELAY || op.op == dusp::OP_MONO_DELAY) && op.in[1].kind == dusp::SRC_PARAM) {
+            entries.insert(entries.end(), {(int64_t)op.in[1].idx, op.ring_len, (int64_t)(op.op == dusp::OP_MONO_DELAY)});
+            which.push_back(k);
+        }
+        if (op.op == dusp::OP_FILTER && op.in[1].kind == dusp::SRC_PARAM && ctx->knobs.filter_scan != 0 && !persistent) {
+            slots.push_back(op.in[1].idx);
+            filters.push_back(k);
+        }
+    }
+    if (which.empty() && filters.empty()) return DUSP_OK;
+    const size_t n = which.size(), nf = filters.size();
+    HIP_TRY(ctx, prog->d_jit_regime.ensure(4 * n + 2 * nf + 2));  // [3 n] entries as int64, n verdicts (one int64 slot each), then nf slots (int) and 3 nf range words (unsigned)
+    int64_t *d_entries = prog->d_jit_regime.p;
+    int *d_bits = (int *)(prog->d_jit_regime.p + 3 * n);
+    int *d_slots = (int *)(prog->d_jit_regime.p + 4 * n);
+    unsigned *d_range = (unsigned *)(d_slots + nf);
+    std::vector<int> bits(n, 0);
+    std::vector<unsigned> range(3 * nf, 0u);
+    if (n) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_entries, entries.data(), 3 * n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_bits, 0, n * sizeof(int64_t), stream));
+        HIP_TRY(ctx, dusp::jit_launch_classify_delays(d_params, n_inst, d_entries, (int)n, d_bits, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(bits.data(), d_bits, n * sizeof(int), hipMemcpyDeviceToHost, stream));
+    }
+    if (nf) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), nf * sizeof(int), hipMemcpyHostToDevice, stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_range, 0, 3 * nf * sizeof(unsigned), stream));
+        HIP_TRY(ctx, dusp::jit_launch_column_range(d_params, n_inst, d_slots, (int)nf, d_range, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(range.data(), d_range, 3 * nf * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    bool changed = false;
+    for (size_t i = 0; i < n; i++) {
+        const int regime = bits[i] == dusp::DELAY_REGIME_LONG || bits[i] == dusp::DELAY_REGIME_SHORT ? bits[i] : dusp::DELAY_REGIME_OTHER;
+        int32_t &pad = prog->P.ops[which[i]].in[1].pad;
+        changed = changed || pad != regime;
+        pad = regime;
+    }
+    for (size_t i = 0; i < nf; i++) {  // (the range itself is no part of the text: only whether the circuit's Filters scan — the key of jit_src — is)
+        dusp::DevOp &op = prog->P.ops[filters[i]];
+        const bool known = range[3 * i + 2] == 0u && range[3 * i] != 0u && range[3 * i + 1] != 0u;
+        op.in[1].pad = known ? dusp::kFilterColumnKnown : 0;
+        if (known) {
+            float lo, hi;
+            const unsigned lo_bits = 0x7fffffffu - range[3 * i], hi_bits = range[3 * i + 1];
+            std::memcpy(&lo, &lo_bits, 4);
+            std::memcpy(&hi, &hi_bits, 4);
+            op.d[0] = (double)lo;
+            op.d[1] = (double)hi;
+        }
+    }
+    if (changed) {  // (another kernel text: the generated units differ)
+        prog->jit_src.clear();
+        prog->jit_consts_uploaded = false;
+    }
+    return DUSP_OK;
+}
+
+// Everything a render decides before it touches the device (jit_plan.hpp), for this context and this batch
+static int jit_plan_render(dusp_program *prog, JitRender &R, uint32_t n_inst, uint32_t n_chunks, bool persistent, bool resume, bool handoff, bool inputs) {
+    dusp_ctx *ctx = prog->ctx;
+    if (prog->voice_loop < 0) {
+        dusp::VoicePlan voices;
+        prog->voice_loop = !persistent && prog->P.ops.size() > dusp::jit_loop_voices_from() && dusp::jit_find_voices(prog->P, prog->wave, voices) ? 1 : 0;
+    }
+    dusp::JitSite site;
+    site.n_cus = ctx->n_cus;
+    site.knobs = ctx->knobs;
+    for (int k = 0; k < dusp::kNumTables; k++)
+        site.table_form[k] = ctx->table_form[k], site.table_delta[k] = ctx->table_delta[k], site.table_bound[k] = ctx->table_bound[k], site.table_antisym[k] = ctx->table_antisym[k];
+    dusp::JitBatch batch;
+    batch.n_inst = n_inst;
+    batch.n_chunks = n_chunks;
+    batch.persistent = persistent;
+    batch.resume = resume;
+    batch.handoff = handoff;
+    batch.inputs = inputs;
+    batch.voice_loop = prog->voice_loop != 0;
+    R.plan = dusp::jit_plan(site, batch, prog->P, prog->wave);
+    if (R.plan.error) CTX_FAIL(ctx, DUSP_ERR_ARG, R.plan.error);
+    R.a.n_seg = R.plan.n_seg;
+    R.a.seg_groups = R.plan.seg_groups;
+    R.a.warm = R.plan.warm ? 1u : 0u;
+    return DUSP_OK;
+}
+
+// The kernel for the plan's geometry: its text generated or found by jit_source_key, compiled (or, wait == false, left to a background
+// thread: kJitLater), and — where it spills — the next geometry of the ladder (jit_plan.hpp jit_spill_step) until one does not.
+static int jit_obtain_kernel(dusp_program *prog, JitRender &R, uint32_t n_inst, uint32_t n_chunks, bool wait) {
+    dusp_ctx *ctx = prog->ctx;
+    const dusp::Program &P = prog->P;
+    dusp::JitPlan &plan = R.plan;
+    dusp::JitOptions &opt = plan.opt;
+    auto text_of = [&](const dusp::JitOptions &o, std::string *why) -> dusp::JitSource * {  // found, or generated now (nullptr: the compiler refuses, *why says why)
+        auto it = prog->jit_src.find(dusp::jit_source_key(o));
         if (it == prog->jit_src.end()) {
             dusp::JitSource gen;
-            if (!dusp::jit_generate(P, prog->wave, opt, gen)) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "render: circuit compiler: " + gen.why);
-            it = prog->jit_src.emplace(std::make_pair(waves, per_wave * 8 + opt.filter_block % 8 + (opt.voice_loop ? 64 : 0) + (opt.filter_scan ? 128 : 0) + (opt.rotate ? 0 : 256)), std::move(gen)).first;
+            if (!dusp::jit_generate(P, prog->wave, o, gen)) {
+                if (why) *why = gen.why;
+                return nullptr;
+            }
+            it = prog->jit_src.emplace(dusp::jit_source_key(o), std::move(gen)).first;
         }
-        src = &it->second;
+        return &it->second;
+    };
+    for (;;) {  // a kernel that spills (128 registers per lane at 16 wavefronts) is rebuilt for fewer instances per wave, then fewer waves
+        std::string why;
+        R.src = text_of(opt, &why);
+        if (!R.src) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "render: circuit compiler: " + why);
         // A structure seen for the first time costs a compile of 0.3-0.8 s.  A render the interpreter kernel finishes sooner
         // than that does not wait for it: the compile starts in a background thread, THIS render runs on the interpreter (same
         // PCM, same state), and the next render of the structure — in this process, or in any with DUSP_JIT_CACHE set — finds
         // its kernel.  DUSP_WAVE_JIT=2 always waits (tests, benchmarks).
-        if (ctx->knobs.wave_jit == 1 && (!handoff_chunks || probe) && !dusp::jit_code_ready(src->text)) {
+        if (ctx->knobs.wave_jit == 1 && !wait && !dusp::jit_code_ready(R.src->text)) {
             // interpreter: ~0.7 ns per unit and chunk with the chip full, ~1 us per unit and chunk along one wavefront's serial path
             const double units = (double)P.ops.size();
-            const double est_ms = std::max(units * (double)n_inst * n_chunks * 0.7e-6, units * (double)a.seg_groups * 1.0e-3);
+            const double est_ms = std::max(units * (double)n_inst * n_chunks * 0.7e-6, units * (double)plan.seg_groups * 1.0e-3);
             if (est_ms < 400.0) {
-                dusp::jit_compile_in_background(src->text);
-                if (filter_stage && opt.filter_block == 8) {
+                dusp::jit_compile_in_background(R.src->text);
+                if (plan.filter_stage && opt.filter_block == 8) {
                     // (a Filter stage's kernel at 16 wavefronts usually ends on the recurrence loop's narrower form: that text joins the
                     // queue now, so the geometry search does not cost a further render on the interpreter per step)
                     dusp::JitOptions narrow = opt;
                     narrow.filter_block = 4;
-                    const auto key = std::make_pair(waves, per_wave * 8 + narrow.filter_block % 8 + (narrow.voice_loop ? 64 : 0) + (narrow.filter_scan ? 128 : 0) + (narrow.rotate ? 0 : 256));
-                    auto alt = prog->jit_src.find(key);
-                    if (alt == prog->jit_src.end()) {
-                        dusp::JitSource gen;
-                        if (dusp::jit_generate(P, prog->wave, narrow, gen)) alt = prog->jit_src.emplace(key, std::move(gen)).first;
-                    }
-                    if (alt != prog->jit_src.end() && !dusp::jit_code_ready(alt->second.text)) dusp::jit_compile_in_background(alt->second.text);
+                    const dusp::JitSource *alt = text_of(narrow, nullptr);
+                    if (alt && !dusp::jit_code_ready(alt->text)) dusp::jit_compile_in_background(alt->text);
                 }
                 return kJitLater;
             }
         }
         std::string err;
         int scratch = 0;
-        if (!dusp::jit_get_kernel(ctx->device, src->text, "dusp_jit_render", &render, &scratch, err))
+        if (!dusp::jit_get_kernel(ctx->device, R.src->text, "dusp_jit_render", &R.render, &scratch, err))
             CTX_FAIL(ctx, DUSP_ERR_HIP, "render: circuit compiler: " + err);
-        jit_scratch = scratch;
-        if (ctx->knobs.jit_log) fprintf(stderr, "[dusp jit] %d waves x %d instances, filter block %d: %d bytes of scratch per lane\n", waves, per_wave, opt.filter_block, scratch);
+        R.scratch = scratch;
+        if (ctx->knobs.jit_log) fprintf(stderr, "[dusp jit] %d waves x %d instances, filter block %d: %d bytes of scratch per lane\n", plan.waves, plan.per_wave, opt.filter_block, scratch);
         if (scratch <= ctx->knobs.jit_spill_bytes || ctx->knobs.jit_force_waves) break;  // (a few registers spilled outside the hot path is cheaper than halving the instances in flight)
-        // The kernel spills at this geometry (16 wavefronts: 128 registers per lane).  A Filter circuit keeps its rows if it can —
-        // half the wavefronts with twice the instances each have twice the registers — else instances per wave, then waves, go down.
-        if (filter_stage && opt.filter_block == 8) {
-            opt.filter_block = 4;  // (first: the recurrence loop with half the P values in flight, 16 registers less)
-            continue;
-        }
-        opt.filter_block = 8;
-        if (filter_stage && waves > 4 && waves % 2 == 0 && per_wave * 2 <= per_wave_cap) {
-            waves /= 2;
-            per_wave *= 2;
-        } else if (filter_stage && per_wave > 1) per_wave /= 2;  // (rows stay a power of two: whole rounds on every CU)
-        else if (per_wave > 1) per_wave /= 2;  // (4, 2, 1: an odd count leaves the last round of workgroups a third full at the usual batch sizes)
-        else if (waves > 4) waves /= 2;
-        else break;
-        if (filter_stage) opt.filter_sub = dusp::jit_filter_sub(waves, per_wave, opt.filter_stages, budget - opt.table_bytes, opt.filter_mod);
+        if (!dusp::jit_spill_step(plan)) break;
     }
-    if (probe) return DUSP_OK;
-    // (from here on the render happens on the compiled kernel: workspaces)
-    HIP_TRY(ctx, prog->d_state.ensure(std::max<size_t>(1, n_slots) * n_pad));
+    return DUSP_OK;
+}
+
+// (from here on the render happens on the compiled kernel) State, rings, parked outlets; the text's constants on the device
+static int jit_workspaces(dusp_program *prog, JitRender &R, uint32_t n_chunks, bool persistent, bool resume, hipStream_t stream) {
+    dusp_ctx *ctx = prog->ctx;
+    const dusp::Program &P = prog->P;
+    dusp::JitArgs &a = R.a;
+    const dusp::JitSource *src = R.src;
+    HIP_TRY(ctx, prog->d_state.ensure(std::max<size_t>(1, P.init_state.size()) * a.n_pad));
     a.state = prog->d_state.p;
     if (P.ring_samples && !resume) {  // Delay rings start as zeros (Delay.js:14); layout [instance][slot]
-        HIP_TRY(ctx, prog->d_rings.ensure((size_t)P.ring_samples * n_pad));
-        HIP_TRY(ctx, zero_rings(prog, n_pad, n_chunks, true, stream));
+        HIP_TRY(ctx, prog->d_rings.ensure((size_t)P.ring_samples * a.n_pad));
+        HIP_TRY(ctx, zero_rings(prog, a.n_pad, n_chunks, true, stream));
     }
     a.rings = prog->d_rings.p;
     a.resume = resume ? 1u : 0u;
     a.save_bufs = persistent ? 1u : 0u;
     a.n_bufs = (uint32_t)std::max(1, P.n_bufs);
     if (persistent) {  // every outlet's last chunk, parked between launches (the interpreter kernel's layout: either may continue the other)
-        HIP_TRY(ctx, prog->d_saved_bufs.ensure((size_t)a.n_bufs * dusp::kChunk * n_inst));
+        HIP_TRY(ctx, prog->d_saved_bufs.ensure((size_t)a.n_bufs * dusp::kChunk * a.n_inst));
         a.saved_bufs = prog->d_saved_bufs.p;
     }
     prog->keep_memory = false;
@@ -1077,123 +950,236 @@ static int render_jit(dusp_program *prog, uint32_t n_inst, size_t n_samples, uin
     }
     a.fk = prog->d_jit_fk.p;
     a.dk = prog->d_jit_dk.p;
-    const unsigned per_block = (unsigned)(waves * per_wave);
-    const unsigned grid = (unsigned)((n_virtual + per_block - 1) / per_block);
-    if (!handoff_chunks) HIP_TRY(ctx, hipEventRecord(prog->ev0, stream));  // (a hand-off's clock started in front of the chunk engine's part)
-    if (a.n_seg > 1 && !src->scans.empty()) {  // one accumulate pass + prefix per FM level that has scanned oscillators, then the render pass
-        const size_t per = src->scans.size() * (size_t)n_inst * a.n_seg;
-        HIP_TRY(ctx, prog->d_seg.ensure(2 * per));
-        a.seg_sum = prog->d_seg.p;
-        a.seg_start = prog->d_seg.p + per;
-        for (int level : src->pass_levels) {
-            hipFunction_t pass = nullptr;
-            std::string err;
-            if (!dusp::jit_get_kernel(ctx->device, src->text, "dusp_jit_pass" + std::to_string(level), &pass, nullptr, err))
-                CTX_FAIL(ctx, DUSP_ERR_HIP, "render: circuit compiler: " + err);
-            dusp::JitArgs own = a;
-            own.warm = 0u;  // (a pass totals every segment's OWN chunks, whatever the render kernel does in front of them)
-            HIP_TRY(ctx, dusp::jit_launch(pass, own, grid, (unsigned)waves * 64, stream));
-            HIP_TRY(ctx, dusp::jit_launch_prefix(a.seg_sum, a.seg_start, prog->d_init.p, prog->d_jit_scan.p, prog->d_jit_scan.p + src->scans.size(),
-                                                 (int)src->scans.size(), level, n_inst, a.n_seg, a.sample_rate, stream));
-        }
+    return DUSP_OK;
+}
+
+// Time segments of a circuit with scanned oscillators: one accumulate pass + prefix per FM level that has them, in front of the render pass
+static int jit_accumulate_passes(dusp_program *prog, JitRender &R, hipStream_t stream) {
+    dusp_ctx *ctx = prog->ctx;
+    dusp::JitArgs &a = R.a;
+    const dusp::JitSource *src = R.src;
+    if (!(a.n_seg > 1 && !src->scans.empty())) return DUSP_OK;
+    const size_t per = src->scans.size() * (size_t)a.n_inst * a.n_seg;
+    HIP_TRY(ctx, prog->d_seg.ensure(2 * per));
+    a.seg_sum = prog->d_seg.p;
+    a.seg_start = prog->d_seg.p + per;
+    for (int level : src->pass_levels) {
+        hipFunction_t pass = nullptr;
+        std::string err;
+        if (!dusp::jit_get_kernel(ctx->device, src->text, "dusp_jit_pass" + std::to_string(level), &pass, nullptr, err))
+            CTX_FAIL(ctx, DUSP_ERR_HIP, "render: circuit compiler: " + err);
+        dusp::JitArgs own = a;
+        own.warm = 0u;  // (a pass totals every segment's OWN chunks, whatever the render kernel does in front of them)
+        HIP_TRY(ctx, dusp::jit_launch(pass, own, R.grid, (unsigned)R.plan.waves * 64, stream));
+        HIP_TRY(ctx, dusp::jit_launch_prefix(a.seg_sum, a.seg_start, prog->d_init.p, prog->d_jit_scan.p, prog->d_jit_scan.p + src->scans.size(),
+                                             (int)src->scans.size(), level, a.n_inst, a.n_seg, a.sample_rate, stream));
     }
-    DevBuf<unsigned long long> d_debug;
-    if (opt.profile) {
-        HIP_TRY(ctx, d_debug.ensure((size_t)grid * 16));
-        HIP_TRY(ctx, hipMemsetAsync(d_debug.p, 0, (size_t)grid * 16 * sizeof(unsigned long long), stream));
-        a.debug = d_debug.p;
+    return DUSP_OK;
+}
+
+static int jit_launch_render(dusp_program *prog, JitRender &R, hipStream_t stream) {
+    dusp_ctx *ctx = prog->ctx;
+    dusp::JitArgs &a = R.a;
+    if (R.plan.opt.profile) {
+        HIP_TRY(ctx, R.d_debug.ensure((size_t)R.grid * 16));
+        HIP_TRY(ctx, hipMemsetAsync(R.d_debug.p, 0, (size_t)R.grid * 16 * sizeof(unsigned long long), stream));
+        a.debug = R.d_debug.p;
     }
     if (a.warm) {
-        HIP_TRY(ctx, prog->d_warm_records.ensure((size_t)std::max(1, opt.filter_stages) * n_virtual * 8));
+        HIP_TRY(ctx, prog->d_warm_records.ensure((size_t)std::max(1, R.plan.opt.filter_stages) * R.plan.n_virtual * 8));
         a.warm_records = prog->d_warm_records.p;
     }
-    HIP_TRY(ctx, dusp::jit_launch(render, a, grid, (unsigned)waves * 64, stream));
-    if (a.warm) {
-        // Segments that warmed up: does every Filter stage hold, where a segment's own chunks begin, what the segment before ended with?  Then —
-        // by induction from the first segment, which started from the render's true state — every stored sample is the sequential render's.
-        // Otherwise the render is finished sequentially from the last segment that is known to be right: one wavefront from that
-        // segment's first chunk on, its Filters started from the state recorded there (x1 x2 y1 y2 of every stage into a copy of the start state).
-        const size_t n_rec = (size_t)opt.filter_stages * n_virtual * 8;
-        std::vector<double> rec(n_rec);
-        HIP_TRY(ctx, hipMemcpyAsync(rec.data(), prog->d_warm_records.p, n_rec * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipStreamSynchronize(stream));
-        uint32_t bad = 0;  // first segment (of any instance) whose start differs from its predecessor's end (0: none)
-        for (uint32_t i = 0; i < n_inst; i++)
-            for (uint32_t s = 1; s < a.n_seg && (!bad || s < bad); s++)
-                for (int st = 0; st < opt.filter_stages; st++) {
-                    const double *now = rec.data() + ((size_t)st * n_virtual + (size_t)i * a.n_seg + s) * 8, *before = now - 8;
-                    if (!(now[0] == before[2] && now[1] == before[3])) bad = s;  // (a NaN never equals: such a render is finished as written)
-                }
-        prog->warm_redo_from = bad;
-        if (bad && (n_inst > 1 || !src->scans.empty())) {
-            // several instances (each with a state of its own by then), or scanned oscillators (their phases are the passes' business): the whole
-            // render once more, every instance as one chain from its first chunk
-            dusp::JitArgs whole = a;
-            whole.warm = 0u;
-            whole.n_seg = 1u;
-            whole.seg_groups = n_chunks;
-            const unsigned blocks = (unsigned)((n_inst + per_block - 1) / per_block);
-            HIP_TRY(ctx, dusp::jit_launch(render, whole, blocks, (unsigned)waves * 64, stream));
-            prog->warm_redo_from = 1;
-        } else if (bad) {
-            std::vector<double> init(P.init_state);
-            int st = 0;
-            for (int k : prog->wave.order) {  // (stage ordinals are dealt in the plan's execution order: jit_codegen.hpp filter_ordinal)
-                const dusp::DevOp &op = P.ops[(size_t)k];
-                if (op.op == dusp::OP_FILTER) {
-                    const double *before = rec.data() + ((size_t)st * n_virtual + (bad - 1)) * 8;
-                    const size_t at = (size_t)op.state_slot;
-                    if (at + 11 <= init.size()) init[at + 7] = before[4], init[at + 8] = before[5], init[at + 9] = before[2], init[at + 10] = before[3];
-                    st++;
-                }
+    HIP_TRY(ctx, dusp::jit_launch(R.render, a, R.grid, (unsigned)R.plan.waves * 64, stream));
+    return DUSP_OK;
+}
+
+// Segments that warmed up: does every Filter stage hold, where a segment's own chunks begin, what the segment before ended with?  Then —
+// by induction from the first segment, which started from the render's true state — every stored sample is the sequential render's.
+// Otherwise the render is finished sequentially from the last segment that is known to be right: one wavefront from that
+// segment's first chunk on, its Filters started from the state recorded there (x1 x2 y1 y2 of every stage into a copy of the start state).
+static int jit_check_warm(dusp_program *prog, JitRender &R, uint32_t n_chunks, hipStream_t stream) {
+    dusp_ctx *ctx = prog->ctx;
+    const dusp::Program &P = prog->P;
+    const dusp::JitArgs &a = R.a;
+    const dusp::JitOptions &opt = R.plan.opt;
+    const uint32_t n_inst = a.n_inst;
+    const uint64_t n_virtual = R.plan.n_virtual;
+    const unsigned per_block = (unsigned)(R.plan.waves * R.plan.per_wave);
+    const size_t n_rec = (size_t)opt.filter_stages * n_virtual * 8;
+    std::vector<double> rec(n_rec);
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), prog->d_warm_records.p, n_rec * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    uint32_t bad = 0;  // first segment (of any instance) whose start differs from its predecessor's end (0: none)
+    for (uint32_t i = 0; i < n_inst; i++)
+        for (uint32_t s = 1; s < a.n_seg && (!bad || s < bad); s++)
+            for (int st = 0; st < opt.filter_stages; st++) {
+                const double *now = rec.data() + ((size_t)st * n_virtual + (size_t)i * a.n_seg + s) * 8, *before = now - 8;
+                if (!(now[0] == before[2] && now[1] == before[3])) bad = s;  // (a NaN never equals: such a render is finished as written)
             }
-            HIP_TRY(ctx, prog->d_warm_init.ensure(init.size()));
-            HIP_TRY(ctx, hipMemcpyAsync(prog->d_warm_init.p, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-            dusp::JitArgs rest = a;
-            rest.warm = 0u;
-            rest.n_seg = 1u;
-            rest.g_first = bad * a.seg_groups;
-            rest.seg_groups = n_chunks;
-            rest.init_state = prog->d_warm_init.p;
-            HIP_TRY(ctx, dusp::jit_launch(render, rest, 1u, (unsigned)waves * 64, stream));
-            HIP_TRY(ctx, hipStreamSynchronize(stream));  // (`init` is a temporary)
+    prog->warm_redo_from = bad;
+    if (bad && (n_inst > 1 || !R.src->scans.empty())) {
+        // several instances (each with a state of its own by then), or scanned oscillators (their phases are the passes' business): the whole
+        // render once more, every instance as one chain from its first chunk
+        dusp::JitArgs whole = a;
+        whole.warm = 0u;
+        whole.n_seg = 1u;
+        whole.seg_groups = n_chunks;
+        const unsigned blocks = (unsigned)((n_inst + per_block - 1) / per_block);
+        HIP_TRY(ctx, dusp::jit_launch(R.render, whole, blocks, (unsigned)R.plan.waves * 64, stream));
+        prog->warm_redo_from = 1;
+    } else if (bad) {
+        std::vector<double> init(P.init_state);
+        int st = 0;
+        for (int k : prog->wave.order) {  // (stage ordinals are dealt in the plan's execution order: jit_codegen.hpp filter_ordinal)
+            const dusp::DevOp &op = P.ops[(size_t)k];
+            if (op.op == dusp::OP_FILTER) {
+                const double *before = rec.data() + ((size_t)st * n_virtual + (bad - 1)) * 8;
+                const size_t at = (size_t)op.state_slot;
+                if (at + 11 <= init.size()) init[at + 7] = before[4], init[at + 8] = before[5], init[at + 9] = before[2], init[at + 10] = before[3];
+                st++;
+            }
         }
+        HIP_TRY(ctx, prog->d_warm_init.ensure(init.size()));
+        HIP_TRY(ctx, hipMemcpyAsync(prog->d_warm_init.p, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        dusp::JitArgs rest = a;
+        rest.warm = 0u;
+        rest.n_seg = 1u;
+        rest.g_first = bad * a.seg_groups;
+        rest.seg_groups = n_chunks;
+        rest.init_state = prog->d_warm_init.p;
+        HIP_TRY(ctx, dusp::jit_launch(R.render, rest, 1u, (unsigned)R.plan.waves * 64, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));  // (`init` is a temporary)
     }
-    HIP_TRY(ctx, hipEventRecord(prog->ev1, stream));
-    if (opt.profile) {  // diagnostic build: what wave 0 of the workgroups measured (mean over workgroups), to stderr
-        std::vector<unsigned long long> h((size_t)grid * 16);
-        HIP_TRY(ctx, hipStreamSynchronize(stream));
-        HIP_TRY(ctx, hipMemcpy(h.data(), d_debug.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double loop = 0, serial = 0, chunks = 0;
-        double ph[12] = {0};
-        for (unsigned b = 0; b < grid; b++) {
-            loop += (double)h[b * 16], serial += (double)h[b * 16 + 1] + (double)h[b * 16 + 3], chunks += (double)h[b * 16 + 2];
-            for (int i = 0; i < 12; i++) ph[i] += (double)h[b * 16 + 4 + i];
-        }
-        std::fprintf(stderr, "[dusp jit profile] %ux%d waves x instances (%d B of scratch per lane), %u workgroups: chunk loop %.0f cycles per chunk, of which Filter recurrences %.0f (%.1f per sample-step)\n",
-                     (unsigned)waves, per_wave, jit_scratch, grid, loop / std::max(1.0, chunks), serial / std::max(1.0, chunks), serial / std::max(1.0, chunks) / 256.0);
-        std::fprintf(stderr, "[dusp jit profile]   barrier to barrier, as wave 0 sees them:");
-        for (int i = 0; i < 12; i++)
-            if (ph[i] > 0) std::fprintf(stderr, " %s%.0f", i == 11 ? "| tail " : "", ph[i] / std::max(1.0, chunks));
-        std::fprintf(stderr, "\n");
-        d_debug.release();
+    return DUSP_OK;
+}
+
+// diagnostic build: what wave 0 of the workgroups measured (mean over workgroups), to stderr
+static int jit_profile_report(dusp_program *prog, JitRender &R, hipStream_t stream) {
+    dusp_ctx *ctx = prog->ctx;
+    const unsigned grid = R.grid;
+    std::vector<unsigned long long> h((size_t)grid * 16);
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    HIP_TRY(ctx, hipMemcpy(h.data(), R.d_debug.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double loop = 0, serial = 0, chunks = 0;
+    double ph[12] = {0};
+    for (unsigned b = 0; b < grid; b++) {
+        loop += (double)h[b * 16], serial += (double)h[b * 16 + 1] + (double)h[b * 16 + 3], chunks += (double)h[b * 16 + 2];
+        for (int i = 0; i < 12; i++) ph[i] += (double)h[b * 16 + 4 + i];
     }
-    prog->jit_waves = waves;
-    prog->jit_per_wave = per_wave;
-    prog->jit_segments = a.n_seg;
-    prog->jit_voices = src->voice_loop;
-    prog->jit_scan = opt.filter_scan;
-    if (!a.warm) prog->warm_redo_from = 0;
+    std::fprintf(stderr, "[dusp jit profile] %ux%d waves x instances (%d B of scratch per lane), %u workgroups: chunk loop %.0f cycles per chunk, of which Filter recurrences %.0f (%.1f per sample-step)\n",
+                 (unsigned)R.plan.waves, R.plan.per_wave, R.scratch, grid, loop / std::max(1.0, chunks), serial / std::max(1.0, chunks), serial / std::max(1.0, chunks) / 256.0);
+    std::fprintf(stderr, "[dusp jit profile]   barrier to barrier, as wave 0 sees them:");
+    for (int i = 0; i < 12; i++)
+        if (ph[i] > 0) std::fprintf(stderr, " %s%.0f", i == 11 ? "| tail " : "", ph[i] / std::max(1.0, chunks));
+    std::fprintf(stderr, "\n");
+    R.d_debug.release();
+    return DUSP_OK;
+}
+
+// The bookkeeping every render ends with: what a state download, a continuation and the next render need to know about this one
+static void finish_render(dusp_program *prog, uint32_t n_inst, uint32_t n_pad, uint64_t n_chunks_total) {
     prog->last_n_inst = n_inst;
     prog->last_n_pad = n_pad;
     prog->rendered = true;
     prog->h_state_valid = false;
-    prog->next_clock = P.g.clock0 + (int64_t)(n_chunks + handoff_chunks) * dusp::kChunk;
+    prog->next_clock = prog->P.g.clock0 + (int64_t)n_chunks_total * dusp::kChunk;
+}
+
+// handoff_chunks > 0: this launch continues a render whose first handoff_chunks chunks the chunk engine has just rendered (Program::warm_ops):
+// start state in d_handoff_init, rings and outlets' last chunk already in this kernel's layout.
+// probe: only find out whether the kernel is at hand (DUSP_OK) or being compiled in the background (kJitLater); nothing is launched.
+static int render_jit(dusp_program *prog, uint32_t n_inst, size_t n_samples, uint32_t n_chunks, const float *d_params, const float *d_inputs, float *d_out,
+                      hipStream_t stream, uint32_t handoff_chunks = 0, bool probe = false) {
+    dusp_ctx *ctx = prog->ctx;
+    const dusp::Program &P = prog->P;
+    const uint32_t n_pad = (n_inst + 63u) & ~63u;
+    const bool persistent = (prog->resumable && prog->persistent) || handoff_chunks > 0;
+    const bool resume = prog->keep_memory || handoff_chunks > 0;
+    if (resume && !handoff_chunks && n_inst != prog->last_n_inst) CTX_FAIL(ctx, DUSP_ERR_STATE, "render: the instance count cannot change while a program is being continued");
+    if (int rc = jit_classify_columns(prog, n_inst, d_params, persistent, stream)) return rc;
+    if (prog->jit_table_generation != ctx->table_generation) {  // a table was uploaded since: forms / the LDS image may have changed
+        prog->jit_src.clear();
+        prog->jit_consts_uploaded = false;
+        prog->jit_table_generation = ctx->table_generation;
+    }
+
+    JitRender R;
+    dusp::JitArgs &a = R.a;
+    a.params = d_params;
+    a.tables = ctx->d_tables;
+    a.inputs = d_inputs;
+    a.out = d_out;
+    a.state = prog->d_state.p;
+    a.init_state = handoff_chunks ? prog->d_handoff_init.p : prog->d_init.p;
+    a.n_samples = n_samples;
+    a.ring_samples = (uint64_t)P.ring_samples;
+    a.clock0 = (uint64_t)P.g.clock0 + (uint64_t)handoff_chunks * dusp::kChunk;
+    a.n_inst = n_inst;
+    a.n_pad = n_pad;
+    a.n_groups = n_chunks;
+    a.sample_rate = (uint32_t)P.g.sample_rate;
+    a.table_stride = ctx->table_stride;
+    a.vec4_ok = (n_samples % 4 == 0) && (((uintptr_t)d_out & 15) == 0);
+    a.n_out = (uint32_t)P.out_bufs.size();
+    if (int rc = jit_plan_render(prog, R, n_inst, n_chunks, persistent, resume, handoff_chunks > 0, d_inputs != nullptr)) return rc;
+    if (int rc = jit_obtain_kernel(prog, R, n_inst, n_chunks, /*wait=*/handoff_chunks && !probe)) return rc;  // (kJitLater included)
+    if (probe) return DUSP_OK;
+    if (int rc = jit_workspaces(prog, R, n_chunks, persistent, resume, stream)) return rc;
+    const unsigned per_block = (unsigned)(R.plan.waves * R.plan.per_wave);
+    R.grid = (unsigned)((R.plan.n_virtual + per_block - 1) / per_block);
+    if (!handoff_chunks) HIP_TRY(ctx, hipEventRecord(prog->ev0, stream));  // (a hand-off's clock started in front of the chunk engine's part)
+    if (int rc = jit_accumulate_passes(prog, R, stream)) return rc;
+    if (int rc = jit_launch_render(prog, R, stream)) return rc;
+    if (a.warm)
+        if (int rc = jit_check_warm(prog, R, n_chunks, stream)) return rc;
+    HIP_TRY(ctx, hipEventRecord(prog->ev1, stream));
+    if (R.plan.opt.profile)
+        if (int rc = jit_profile_report(prog, R, stream)) return rc;
+    prog->jit_waves = R.plan.waves;
+    prog->jit_per_wave = R.plan.per_wave;
+    prog->jit_segments = a.n_seg;
+    prog->jit_voices = R.src->voice_loop;
+    prog->jit_scan = R.plan.opt.filter_scan;
+    if (!a.warm) prog->warm_redo_from = 0;
+    finish_render(prog, n_inst, n_pad, (uint64_t)n_chunks + handoff_chunks);
     return DUSP_OK;
 }
 
 static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_t n_samples, const float *d_params, const float *d_inputs,
                                    float *d_out, void *stream_);
+
+// The chunk engine's arguments for n_chunks chunks of this program (workspaces as the caller has sized them)
+static dusp::ChunkArgs chunk_args(dusp_program *prog, uint32_t n_inst, size_t n_samples, uint32_t n_chunks, const float *d_params, const float *d_inputs, float *d_out,
+                                  uint32_t flags) {
+    const dusp::Program &P = prog->P;
+    dusp::ChunkArgs a{};
+    a.ops = prog->d_ops.p;
+    a.out_bufs = prog->d_out_bufs.p;
+    a.scratch = prog->d_scratch.p;
+    a.state = prog->d_state.p;
+    a.rings = prog->d_rings.p;
+    a.params = d_params;
+    a.tables = prog->ctx->d_tables;
+    a.inputs = d_inputs;
+    a.out = d_out;
+    a.n_samples = n_samples;
+    a.clock0 = P.g.clock0;
+    a.n_ops = (uint32_t)P.ops.size();
+    a.n_out = (uint32_t)P.out_bufs.size();
+    a.n_inst = n_inst;
+    a.n_pad = (n_inst + 63u) & ~63u;
+    a.n_chunks = n_chunks;
+    a.sample_rate = (uint32_t)P.g.sample_rate;
+    a.table_stride = prog->ctx->table_stride;
+    a.flags = flags;
+    a.n_warm = (uint32_t)P.warm_ops.size();
+    for (uint32_t k = 0, at = a.n_ops; k < a.n_warm; k++) {
+        a.warm_first[k] = at;
+        a.warm_n[k] = (uint32_t)P.warm_ops[k].size();
+        at += a.warm_n[k];
+    }
+    return a;
+}
 
 // DUSP_GUARD=1: wait for the render and look at the guard bytes behind every workspace it could have touched
 static int check_guards(dusp_program *prog, hipStream_t stream) {
@@ -1247,6 +1233,7 @@ static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_
     prog->last_stream = stream;
     const uint32_t n_inst = (uint32_t)n_instances;
     const uint32_t n_chunks = (uint32_t)((n_samples + dusp::kChunk - 1) / dusp::kChunk);
+    const uint32_t n_pad = (n_inst + 63u) & ~63u;
 
     if (prog->engine == DUSP_ENGINE_FUSED) {
         dusp::FusedLaunch L{};
@@ -1298,14 +1285,10 @@ static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_
             HIP_TRY(ctx, dusp::launch_fused(prog->fused, L, stream));
             HIP_TRY(ctx, hipEventRecord(prog->ev1, stream));
         }
-        prog->last_n_inst = n_inst;
-        prog->rendered = true;
-        prog->h_state_valid = false;
-        prog->next_clock = P.g.clock0 + (int64_t)n_chunks * dusp::kChunk;
+        finish_render(prog, n_inst, n_pad, n_chunks);  // (n_pad: only ever read for programs of the other engines, whose renders all set it)
         return DUSP_OK;
     }
 
-    const uint32_t n_pad = (n_inst + 63u) & ~63u;
     const size_t n_slots = P.init_state.size();
     prog->jit_waves = prog->jit_per_wave = 0;
     if (prog->engine == DUSP_ENGINE_WAVE && prog->jit_ok) {
@@ -1361,14 +1344,7 @@ static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_
         w.seg_groups = n_chunks;
         w.max_osc_level = prog->wave.max_osc_level;
         if (prog->wave.splittable) {
-            const uint64_t target = (uint64_t)ctx->n_cus * 8;  // wavefronts that fill the chip
-            uint64_t n_seg = n_inst >= target ? 1 : std::min<uint64_t>(target / n_inst, n_chunks / 8);
-            if (ctx->knobs.wave_segments >= 0) n_seg = (uint64_t)ctx->knobs.wave_segments;  // 0 / 1: off; n: force n segments
-            n_seg = std::max<uint64_t>(1, std::min<uint64_t>(n_seg, n_chunks));
-            if (n_seg > 1) {
-                w.seg_groups = (uint32_t)((n_chunks + n_seg - 1) / n_seg);
-                w.n_seg = (uint32_t)((n_chunks + w.seg_groups - 1) / w.seg_groups);  // no empty segments
-            }
+            dusp::jit_time_segments(ctx->n_cus, ctx->knobs.wave_segments, n_inst, n_chunks, w.n_seg, w.seg_groups);
             if (w.n_seg > 1) {
                 const size_t per = (size_t)w.n_ops * n_inst * w.n_seg;
                 HIP_TRY(ctx, prog->d_seg.ensure(2 * per));
@@ -1380,11 +1356,7 @@ static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_
         HIP_TRY(ctx, hipEventRecord(prog->ev0, stream));
         HIP_TRY(ctx, dusp::launch_wave_engine(w, lds_ok, ctx->knobs.wave_max_waves, stream));
         HIP_TRY(ctx, hipEventRecord(prog->ev1, stream));
-        prog->last_n_inst = n_inst;
-        prog->last_n_pad = n_pad;
-        prog->rendered = true;
-        prog->h_state_valid = false;
-        prog->next_clock = P.g.clock0 + (int64_t)n_chunks * dusp::kChunk;
+        finish_render(prog, n_inst, n_pad, n_chunks);
         return DUSP_OK;
     }
     // Channel counts that grow during the first chunks (Program::warm_ops): a single circuit renders those chunks here, on the chunk engine
@@ -1413,32 +1385,8 @@ static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_
             HIP_TRY(ctx, hipMemsetAsync(prog->d_scratch.p, 0, (size_t)n_bufs * dusp::kChunk * n_pad * sizeof(float), stream));
             if (P.ring_samples) HIP_TRY(ctx, hipMemsetAsync(prog->d_rings.p, 0, (size_t)P.ring_samples * n_pad * sizeof(float), stream));
             HIP_TRY(ctx, dusp::launch_state_init(prog->d_state.p, prog->d_init.p, (uint32_t)n_slots, n_pad, stream));
-            dusp::ChunkArgs a{};
-            a.ops = prog->d_ops.p;
-            a.out_bufs = prog->d_out_bufs.p;
-            a.scratch = prog->d_scratch.p;
-            a.state = prog->d_state.p;
-            a.rings = prog->d_rings.p;
-            a.params = d_params;
-            a.tables = ctx->d_tables;
-            a.inputs = d_inputs;
-            a.out = prog->d_handoff_out.p;
-            a.n_samples = n_head;
-            a.clock0 = P.g.clock0;
-            a.n_ops = (uint32_t)P.ops.size();
-            a.n_out = (uint32_t)n_ch;
-            a.n_inst = n_inst;
-            a.n_pad = n_pad;
-            a.n_chunks = W;
-            a.sample_rate = (uint32_t)P.g.sample_rate;
-            a.table_stride = ctx->table_stride;
-            a.flags = dusp::kChunkFlagResumable;  // (rings in the reference's own state: a compiled kernel continues them)
-            a.n_warm = n_warm;
-            for (uint32_t k = 0, at = a.n_ops; k < a.n_warm; k++) {
-                a.warm_first[k] = at;
-                a.warm_n[k] = (uint32_t)P.warm_ops[k].size();
-                at += a.warm_n[k];
-            }
+            // (resumable: rings in the reference's own state — a compiled kernel continues them)
+            const dusp::ChunkArgs a = chunk_args(prog, n_inst, n_head, W, d_params, d_inputs, prog->d_handoff_out.p, dusp::kChunkFlagResumable);
             HIP_TRY(ctx, hipEventRecord(prog->ev0, stream));
             HIP_TRY(ctx, dusp::launch_chunk_engine(a, stream));
             HIP_TRY(ctx, hipMemcpy2DAsync(d_out, n_samples * sizeof(float), prog->d_handoff_out.p, n_head * sizeof(float), n_head * sizeof(float), n_ch,
@@ -1481,40 +1429,11 @@ static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_
     prog->keep_memory = false;
     HIP_TRY(ctx, dusp::launch_state_init(prog->d_state.p, prog->d_init.p, (uint32_t)n_slots, n_pad, stream));
 
-    dusp::ChunkArgs a{};
-    a.ops = prog->d_ops.p;
-    a.out_bufs = prog->d_out_bufs.p;
-    a.scratch = prog->d_scratch.p;
-    a.state = prog->d_state.p;
-    a.rings = prog->d_rings.p;
-    a.params = d_params;
-    a.tables = ctx->d_tables;
-    a.inputs = d_inputs;
-    a.out = d_out;
-    a.n_samples = n_samples;
-    a.clock0 = P.g.clock0;
-    a.n_ops = (uint32_t)P.ops.size();
-    a.n_out = (uint32_t)P.out_bufs.size();
-    a.n_inst = n_inst;
-    a.n_pad = n_pad;
-    a.n_chunks = n_chunks;
-    a.sample_rate = (uint32_t)P.g.sample_rate;
-    a.table_stride = ctx->table_stride;
-    a.flags = (prog->resumable && prog->persistent) ? dusp::kChunkFlagResumable : 0u;
-    a.n_warm = (uint32_t)P.warm_ops.size();
-    for (uint32_t k = 0, at = a.n_ops; k < a.n_warm; k++) {
-        a.warm_first[k] = at;
-        a.warm_n[k] = (uint32_t)P.warm_ops[k].size();
-        at += a.warm_n[k];
-    }
+    const dusp::ChunkArgs a = chunk_args(prog, n_inst, n_samples, n_chunks, d_params, d_inputs, d_out, (prog->resumable && prog->persistent) ? dusp::kChunkFlagResumable : 0u);
     HIP_TRY(ctx, hipEventRecord(prog->ev0, stream));
     HIP_TRY(ctx, dusp::launch_chunk_engine(a, stream));
     HIP_TRY(ctx, hipEventRecord(prog->ev1, stream));
-    prog->last_n_inst = n_inst;
-    prog->last_n_pad = n_pad;
-    prog->rendered = true;
-    prog->h_state_valid = false;
-    prog->next_clock = P.g.clock0 + (int64_t)n_chunks * dusp::kChunk;
+    finish_render(prog, n_inst, n_pad, n_chunks);
     return DUSP_OK;
 }
 

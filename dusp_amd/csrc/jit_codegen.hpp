@@ -73,8 +73,8 @@ struct JitOptions {
 
 // The oscillators' half-table image in LDS, for the table `table_id` (-1: none wanted): only where one wavefront's scratch
 // (opt.scratch_floats) still fits beside it in the workgroup's 160 KiB.  Elsewhere — every circuit from 88.2 kHz on, where the image
-// alone takes 182 KB or more — the lookups gather from global memory (lds_table = -1).  The render path (dusp_abi.hip) and the
-// host-only option logic (jit_source_from_descriptor) both place the image through this one test.
+// alone takes 182 KB or more — the lookups gather from global memory (lds_table = -1).  Every caller places the image through this one
+// test (jit_site_options).
 inline void jit_place_table(JitOptions &opt, int table_id, uint32_t sample_rate) {
     const size_t bytes = (size_t)half_table_image_bytes(sample_rate);
     const bool fits = table_id >= 0 && bytes + opt.scratch_floats * 4 <= 160 * 1024;
@@ -2012,6 +2012,50 @@ inline bool jit_generate(const Program &P, const WavePlan &plan, const JitOption
     return e.run();
 }
 
+// What a context knows when it chooses a kernel's options: the chip, the knobs, and what it found out about its tables at upload.
+struct JitSite {
+    int n_cus = 256;
+    Knobs knobs;
+    int table_form[kNumTables] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // TABLE_FORM_* (device_util.hpp)
+    int table_delta[kNumTables] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // the lerp's delta form (device_util.hpp lerp_delta)
+    int table_bound[kNumTables] = {1000, 1000, 1000, 1000, 1000, 1000, 1000, 1000, 1000};  // every |entry| <= 2^bound (1000: not finite / not set)
+    bool table_antisym[kNumTables] = {false, false, false, false, false, false, false, false, false};
+};
+
+// The options that follow from the site and the circuit alone — table forms, the LDS image, scan / stages / mod, the delay lines' fit
+// test — for both callers: a render (jit_plan.hpp jit_plan) and jit_source_from_descriptor below.  opt.persistent and opt.voice_loop are
+// set by the caller beforehand.  warm: the render is cut into segments that warm up.  lines_ok: what the CALLER adds to the delay
+// lines' gate — a render: one segment, no voice loop, no forced geometry of several instances per wavefront; a given geometry: one
+// instance per wavefront.
+inline void jit_site_options(JitOptions &opt, const Program &P, const JitSite &site, bool warm, bool lines_ok) {
+    const Knobs &knobs = site.knobs;
+    for (int k = 0; k < kNumTables; k++) opt.table_form[k] = site.table_form[k], opt.table_delta[k] = knobs.jit_lean ? site.table_delta[k] : 0, opt.table_bound[k] = site.table_bound[k];
+    opt.scratch_floats = jit_scratch_floats(P);
+    // the LDS image goes to the first oscillator table that needs one (saw / square / triangle are evaluated, not looked up), where it fits
+    int image = -1;
+    for (const DevOp &op : P.ops)
+        if ((op.op == OP_OSC || op.op == OP_MULTI_OSC) && image < 0 && knobs.jit_lds_table != 0 && site.table_antisym[op.attr] && P.g.sample_rate % 2 == 0 &&
+            !(site.table_form[op.attr] >= 1 && site.table_form[op.attr] <= 3))  // TABLE_FORM_SAW .. TABLE_FORM_TRIANGLE
+            image = site.table_form[op.attr] == 4 && site.table_antisym[0] ? 0 : op.attr;  // (TABLE_FORM_8BIT: the sine image serves 8bit too)
+    jit_place_table(opt, image, (uint32_t)P.g.sample_rate);
+    // Filters whose cutoff is a constant of the circuit, high enough for the bound of jit_filter_scan_ok: a scan over the chunk, the circuit
+    // an ordinary one (no Filter stage).  Not for programs that are continued (the stage's y1 / y2 are what the other engines hand over).
+    opt.filter_scan = knobs.filter_scan != 0 && !opt.persistent && !warm && jit_filter_scan_ok(P, site.table_bound, knobs.filter_scan == 2 ? 2 : 1);
+    opt.filter_stages = opt.filter_scan ? 0 : jit_filter_stages(P);
+    opt.filter_mod = !opt.filter_scan && jit_filter_mod(P);
+    // Constant delays of a chunk at least as lines of input samples in LDS (JitDelayLine) instead of rings in memory: where the circuit
+    // has no Filter stage (whose overlap splits a Delay's tick), the render is not continued, and all the lines fit at 16 wavefronts next
+    // to the table image and the shared scratch — one instance per wavefront.
+    if (knobs.delay_line != 0 && !opt.persistent && opt.filter_stages == 0 && lines_ok) {
+        opt.line_whole_only = knobs.delay_line == 2;
+        const size_t lines = jit_delay_lines(P, opt.line_whole_only);
+        if (lines && opt.table_bytes + 16 * (opt.scratch_floats + lines) * 4 <= 160 * 1024) {
+            opt.line_floats = lines;
+            opt.scratch_floats += lines;
+        }
+    }
+}
+
 // Descriptor words -> kernel text for a given workgroup geometry, WITHOUT a device: what dusp_circuit_kernel_source (dusp_abi.hip) does in
 // front of the run-time compiler, as one host-only function — parse and expand the descriptor (program.hpp), plan it for the wave engine
 // (fused_plan.hpp), choose the options a context would choose for the reference's own tables, generate.  Everything the untrusted input
@@ -2054,32 +2098,28 @@ inline int jit_source_from_descriptor(const double *desc, size_t n_words, const 
         err = "not a circuit the compiler takes (" + why + ")";
         return 2;
     }
+    JitSite site;  // a context with the reference's own tables: sine and 8bit antisymmetric, the rest closed forms
+    site.knobs.filter_scan = rq.scan_knob;
+    site.knobs.jit_lean = rq.lean ? 1 : 0;
+    site.knobs.delay_line = rq.delay_line;
+    if (rq.lds_table && P.g.sample_rate % 2 == 0) {
+        site.table_form[1] = 1;  // TABLE_FORM_SAW
+        site.table_form[2] = 2;  // TABLE_FORM_SQUARE
+        if (P.g.sample_rate % 4 == 0) site.table_form[3] = 3;  // TABLE_FORM_TRIANGLE
+        site.table_form[4] = 4;  // TABLE_FORM_8BIT
+        for (int k = 0; k < 5; k++) site.table_bound[k] = 1;  // (the oscillators' tables stay within [-1, 1])
+        site.table_delta[0] = 1;  // (the sine table: differences of neighbours exact in f64 at any sample rate, in f32 at some — 44.1 kHz, not 48)
+        site.table_antisym[0] = site.table_antisym[4] = true;
+    }
     JitOptions opt;
     opt.waves = rq.waves;
     opt.per_wave = rq.per_wave;
     opt.persistent = continued;
-    opt.voice_loop = !continued;  // (where the circuit is a sum of isomorphic voices: the form an unsplit render gets)
+    opt.voice_loop = !continued;  // (where the circuit is a sum of isomorphic voices: the form an unsplit render gets; a render asks jit_find_voices first)
     if (rq.lean_recurrence) opt.filter_block = 4;
-    opt.scratch_floats = jit_scratch_floats(P);
-    if (rq.lds_table && P.g.sample_rate % 2 == 0) {  // what a context finds for the reference's tables: sine and 8bit antisymmetric, the rest closed forms
-        opt.table_form[1] = 1;  // TABLE_FORM_SAW
-        opt.table_form[2] = 2;  // TABLE_FORM_SQUARE
-        if (P.g.sample_rate % 4 == 0) opt.table_form[3] = 3;  // TABLE_FORM_TRIANGLE
-        opt.table_form[4] = 4;  // TABLE_FORM_8BIT
-        for (int k = 0; k < 5; k++) opt.table_bound[k] = 1;  // (the oscillators' tables stay within [-1, 1])
-        opt.table_delta[0] = rq.lean ? 1 : 0;  // (the sine table: differences of neighbours exact in f64 at any sample rate, in f32 at some — 44.1 kHz, not 48)
-        bool wants_image = false;
-        for (const DevOp &op : P.ops) wants_image = wants_image || ((op.op == OP_OSC || op.op == OP_MULTI_OSC) && (op.attr == 0 || op.attr == 4));
-        jit_place_table(opt, wants_image ? 0 : -1, (uint32_t)P.g.sample_rate);
-    }
-    opt.filter_scan = !continued && rq.scan_knob != 0 && jit_filter_scan_ok(P, opt.table_bound, rq.scan_knob == 2 ? 2 : 1);
-    opt.filter_stages = opt.filter_scan ? 0 : jit_filter_stages(P);
-    opt.filter_mod = !opt.filter_scan && jit_filter_mod(P);
-    if (!continued && opt.filter_stages == 0 && rq.per_wave == 1 && rq.delay_line) {
-        opt.line_whole_only = rq.delay_line == 2;
-        const size_t lines = jit_delay_lines(P, opt.line_whole_only);
-        if (lines && opt.table_bytes + 16 * (opt.scratch_floats + lines) * 4 <= 160 * 1024) opt.line_floats = lines, opt.scratch_floats += lines;
-    }
+    jit_site_options(opt, P, site, /*warm=*/false, /*lines_ok=*/rq.per_wave == 1);
+    // The geometry is the caller's, not searched (jit_plan.hpp jit_plan): the Filter rows take what this many wavefronts' scratch leaves, and
+    // where they do not fit the table image goes before the call fails (a render shrinks the geometry first, and fails under DUSP_JIT_FORCE).
     if (plan.has_filter && !opt.filter_scan) {
         for (;;) {
             const size_t used = opt.table_bytes + (size_t)rq.waves * opt.scratch_floats * 4;

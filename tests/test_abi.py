@@ -127,3 +127,60 @@ def test_the_filter_scan_stays_within_its_stated_bound(tmp_path):
     assert rep["cases"] >= 30 and rep["bad"] == 0 and rep["worst_of_bound"] <= 1.0 and rep["worst_of_scale"] <= 1.9e-6
     # ... and inside configs[3]'s feedback loop at gains 0.5 .. 0.99, resonant and other inputs: within the loop-gain bound of jit_filter_scan_ok (2)
     assert rep["loop_cases"] == 24 and rep["loop_bad"] == 0 and rep["loop_worst_of_bound"] <= 1.0 and rep["loop_worst_of_scale"] <= 1e-5
+
+
+def plan_check_circuits():
+    """The circuits tests/native/jit_plan_check.cpp plans (name -> descriptor words), built as bench.py and the GPU tests build them."""
+    import dusp_amd as d
+    from dusp_amd import descriptor
+
+    def loop(k):  # BASELINE configs[3]'s voice (bench.py --config cfg4)
+        s = d.Sum(d.Osc(110.0 + k / 64.0), 0)
+        f = d.Filter(d.Delay(s, 480, 4096), 2000)
+        s.B = d.Multiply(f, 0.5)
+        return f
+
+    def fm(k):
+        return d.Multiply(d.Osc(d.Sum(d.Multiply(d.Osc(3 + k / 4), 40), 220.5 + 10 * k)), d.Ramp(4000, 1, 0.25).trigger())
+
+    out = {}
+    d.configure(48000)
+    out["light"] = descriptor.extract(d.Multiply(d.Ramp(4000, 1, 0).trigger(), 0.5)).words
+    out["osc"] = descriptor.unify([descriptor.extract(d.Osc(20.0 + k / 8.0)) for k in (0, 1)]).words
+    out["filter_stage"] = descriptor.extract(d.Filter(d.Osc(220), d.Sum(d.Multiply(d.Osc(2), 500), 1000))).words
+    out["cfg4"] = descriptor.unify([descriptor.extract(loop(k)) for k in (0, 64)]).words
+    out["filter_long"] = descriptor.extract(d.Filter(d.Osc(220), 2000)).words
+    out["fm"] = descriptor.unify([descriptor.extract(fm(k)) for k in (0, 1)]).words
+    out["delay"] = descriptor.extract(d.Delay(d.Osc(220), 300.5, 4096)).words
+    comb = d.CombFilter(0.0007, d.Multiply(d.Osc(3), 0.9))
+    comb.IN = d.Osc(333.3)
+    out["comb_filter"] = descriptor.extract(d.Filter(comb, d.Sum(d.Multiply(d.Osc(2), 500), 1000))).words
+    d.configure(96000)
+    out["osc96k"] = descriptor.extract(d.Osc(440)).words
+    d.configure(48000)
+    return out
+
+
+def test_compiled_launches_are_planned_as_before_the_planner_was_a_module(tmp_path):
+    """dusp_amd/csrc/jit_plan.hpp (everything a render on a compiled circuit kernel decides before it touches the device: time segments and
+    whether they warm up, table image, scan or Filter stage, delay lines, wavefronts x instances per wavefront) on the CPU, against the plans
+    recorded from the render path as it stood before (tests/native/jit_plan_check.cpp says how): light, oscillator, Filter-stage, FM and
+    delay circuits at 1 .. 65 536 instances, BASELINE configs[3], one long Filter circuit (segments that warm up), 96 kHz (no table image),
+    and the knobs DUSP_JIT_FORCE / WAVE_SEGMENTS / FILTER_WARM / WAVE_PER_WAVE / WAVE_MAX_WAVES / DELAY_LINE.  Every spill ladder is walked
+    to its end; the key of the generated texts tells apart every field a text depends on (segments that warm up included); the time-segment
+    count equals the expression the two engines used to carry, with no empty segment."""
+    import json
+    import subprocess
+    import numpy as np
+    exe = str(tmp_path / "jit_plan_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Wno-unused-parameter", "-o", exe, os.path.join(ROOT, "tests", "native", "jit_plan_check.cpp")])
+    args = []
+    for name, words in plan_check_circuits().items():
+        path = str(tmp_path / (name + ".f64"))
+        np.asarray(words, dtype=np.float64).tofile(path)
+        args.append(name + "=" + path)
+    p = subprocess.run([exe] + args, stdout=subprocess.PIPE)
+    out = p.stdout.decode()
+    rep = json.loads(out.strip().splitlines()[-1])
+    assert p.returncode == 0 and rep["bad"] == 0, out[-4000:]
+    assert rep["rows"] >= 58 and rep["cases"] >= 58 + 7 + 16 * 4 * 32 + 8 * 7 * 6  # (rows, keys one field apart, keys over all geometries, segment counts)

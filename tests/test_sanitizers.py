@@ -10,10 +10,11 @@ from conftest import GOLDEN, ROOT
 
 
 def test_descriptor_path_under_asan_and_ubsan():
-    """make -C dusp_amd/csrc hostcheck: program.hpp + fused_plan.hpp + jit_codegen.hpp + ring_windows.hpp compiled by g++ with
+    """make -C dusp_amd/csrc hostcheck: program.hpp + fused_plan.hpp + jit_codegen.hpp + jit_plan.hpp + ring_windows.hpp compiled by g++ with
     -fsanitize=address,undefined -fno-sanitize-recover=all, driven (tests/native/hostcheck.cpp) by every golden descriptor over a spread of
     workgroup geometries and knobs, by their truncations and by single- and double-word corruptions: every call ends in a verdict with a
-    message (kernel text / malformed / unsupported), and the sanitizers — leak detection included — have nothing to report."""
+    message (kernel text / malformed / unsupported), every descriptor the compiler takes is planned for a spread of batches and knobs with
+    its spill ladder walked to the end, and the sanitizers — leak detection included — have nothing to report."""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "dusp_amd", "csrc"), "-s", "hostcheck"])
     exe = os.path.join(ROOT, "dusp_amd", "csrc", "build", "hostcheck")
     files = sorted(glob.glob(os.path.join(GOLDEN, "*.desc.f64")))
@@ -25,6 +26,7 @@ def test_descriptor_path_under_asan_and_ubsan():
     rep = json.loads(out.strip().splitlines()[-1])
     assert rep["files"] == len(files) and rep["bad"] == 0
     assert rep["text"] > 10000 and rep["malformed"] > 40000 and rep["unsupported"] > 500  # (all three verdicts are exercised)
+    assert rep["plans"] > 0
 
 
 def test_oracle_under_asan_and_ubsan():
