@@ -23,6 +23,7 @@
 #include "jit_codegen.hpp"
 #include "jit_engine.hpp"
 #include "jit_plan.hpp"
+#include "pcm_quant.hpp"
 #include "program.hpp"
 #include "ring_windows.hpp"
 #include "table_checks.hpp"
@@ -36,6 +37,10 @@ hipError_t launch_wave_to_chunk(const float *wave_rings, float *chunk_rings, uin
 hipError_t launch_chunk_to_wave(const float *chunk_rings, float *wave_rings, uint64_t ring_samples, const float *chunk_scratch, float *saved_bufs, uint32_t n_bufs,
                                 uint32_t n_inst, uint32_t n_pad, const double *state, double *init_state, uint32_t n_slots, hipStream_t stream);
 hipError_t launch_interleave(const float *d_planar, float *d_out, uint32_t n_instances, uint32_t n_channels, uint64_t n_samples, hipStream_t stream);
+hipError_t launch_pcm_peak(const float *d_planar, float *d_peaks, uint32_t n_instances, uint32_t n_channels, uint64_t n_samples, int n_cus, hipStream_t stream);
+hipError_t launch_pcm_encode(const float *d_planar, const float *d_peaks, int format, int normalise, void *d_out, uint32_t n_instances, uint32_t n_channels,
+                             uint64_t n_samples, int n_cus, hipStream_t stream);
+uint64_t pcm_encode_tiles(uint64_t n_instances, uint32_t n_channels, uint64_t n_samples, int format);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -135,6 +140,8 @@ struct dusp_program {
     std::vector<double> h_state;   // copy of d_state / d_fused_state, fetched once per render on the first state download
     bool h_state_valid = false;
     DevBuf<float> d_host_out, d_host_par, d_host_frames, d_host_in;  // dusp_render_host staging, grown on demand
+    DevBuf<unsigned char> d_host_pcm;                                // dusp_render_host_pcm: the encoded frames ...
+    DevBuf<float> d_host_peaks;                                      // ... and the instances' peaks
     int requested_engine = DUSP_ENGINE_AUTO;
     bool resumable = false;      // built with DUSP_ENGINE_RESUMABLE
     bool persistent = false;     // rings / feedback edges: device memory carries over between segments (CHUNK engine only)
@@ -180,6 +187,8 @@ struct dusp_program {
         if (ctx) (void)hipSetDevice(ctx->device);
         for (DevBuf<float> *b : {&d_scratch, &d_rings, &d_host_out, &d_host_par, &d_host_frames, &d_host_in, &d_saved_bufs, &d_rings_wave, &d_jit_fk}) b->release();
         for (DevBuf<double> *b : {&d_init, &d_state, &d_fused_state, &d_jit_dk}) b->release();
+        d_host_pcm.release();
+        d_host_peaks.release();
         d_jit_scan.release();
         d_jit_regime.release();
         d_handoff_init.release();
@@ -196,8 +205,8 @@ struct dusp_program {
         if (ev1) (void)hipEventDestroy(ev1);
     }
     // dusp_render_host* into pageable memory: pinned staging tiles, two per copy worker (download_staged)
-    float *pin[1] = {nullptr};
-    size_t pin_floats = 0;
+    unsigned char *pin[1] = {nullptr};
+    size_t pin_bytes = 0;
 };
 
 #define CTX_FAIL(ctx, code, msg)  \
@@ -1198,6 +1207,7 @@ static int check_guards(dusp_program *prog, hipStream_t stream) {
     else if (!prog->d_rings_wave.intact()) hit = "parked rings";
     else if (!prog->d_host_out.intact()) hit = "staging PCM";
     else if (!prog->d_host_frames.intact()) hit = "staging frames";
+    else if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact()) hit = "staging PCM frames / peaks";
     else if (!prog->d_host_par.intact()) hit = "staging parameters";
     else if (!prog->d_host_in.intact()) hit = "staging inputs";
     else if (!prog->d_handoff_init.intact() || !prog->d_handoff_out.intact()) hit = "hand-off buffers";
@@ -1437,8 +1447,9 @@ static int render_device_unguarded(dusp_program *prog, size_t n_instances, size_
     return DUSP_OK;
 }
 
-static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, float *h_out,
-                       bool interleaved);
+// (pcm_format 0: f32 as rendered, planar or interleaved; DUSP_PCM_*: encoded frames, dusp_render_host_pcm)
+static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, void *h_out,
+                       bool interleaved, int pcm_format = 0, int normalise = 0, float *h_peaks = nullptr);
 
 int dusp_render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, float *h_out) {
     return render_host(prog, n_instances, n_samples, h_params, nullptr, h_out, false);
@@ -1468,15 +1479,58 @@ int dusp_interleave_device(dusp_ctx *ctx, const float *d_planar, size_t n_instan
     return DUSP_OK;
 }
 
+int dusp_peak_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples, float *d_peaks, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (!d_planar || !d_peaks) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_peak_device: NULL buffer");
+    if (n_channels < 1 || n_channels > 64 || n_instances < 1 || n_instances > (1u << 24) || n_samples < 1 || n_samples > (1ull << 31))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_peak_device: need 1..64 channels, 1..2^24 instances and 1..2^31 samples");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dusp::launch_pcm_peak(d_planar, d_peaks, (uint32_t)n_instances, (uint32_t)n_channels, n_samples, ctx->n_cus,
+                                       stream_ ? (hipStream_t)stream_ : ctx->stream));
+    return DUSP_OK;
+}
+
+int dusp_encode_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples, int format, int normalise,
+                       const float *d_peaks, void *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (!d_planar || !d_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: NULL buffer");
+    if (format != DUSP_PCM_S16 && format != DUSP_PCM_S24 && format != DUSP_PCM_F32)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: format must be DUSP_PCM_S16 (1), DUSP_PCM_S24 (2) or DUSP_PCM_F32 (3)");
+    if (normalise != DUSP_NORMALISE_NONE && normalise != DUSP_NORMALISE_CLIP && normalise != DUSP_NORMALISE_FULL)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
+    if (normalise != DUSP_NORMALISE_NONE && !d_peaks) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: normalising needs d_peaks (dusp_peak_device)");
+    if (n_channels < 1 || n_channels > 64 || n_instances < 1 || n_instances > (1u << 24) || n_samples < 1 || n_samples > (1ull << 31) ||
+        dusp::pcm_encode_tiles(n_instances, (uint32_t)n_channels, n_samples, format) > 0x7fffffffull)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: need 1..64 channels, 1..2^24 instances, 1..2^31 samples and at most 2^31 tiles");
+    if (format == DUSP_PCM_F32 && ((uintptr_t)d_out & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: f32 frames need a 4-byte aligned d_out");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dusp::launch_pcm_encode(d_planar, d_peaks, format, normalise, d_out, (uint32_t)n_instances, (uint32_t)n_channels, n_samples, ctx->n_cus,
+                                         stream_ ? (hipStream_t)stream_ : ctx->stream));
+    return DUSP_OK;
+}
+
+int dusp_render_host_pcm(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, int format, int normalise,
+                         void *h_out, float *h_peaks) {
+    if (!prog) return DUSP_ERR_ARG;
+    dusp_ctx *ctx = prog->ctx;
+    if (format != DUSP_PCM_S16 && format != DUSP_PCM_S24 && format != DUSP_PCM_F32)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_pcm: format must be DUSP_PCM_S16 (1), DUSP_PCM_S24 (2) or DUSP_PCM_F32 (3)");
+    if (normalise != DUSP_NORMALISE_NONE && normalise != DUSP_NORMALISE_CLIP && normalise != DUSP_NORMALISE_FULL)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_pcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
+    if (prog->P.out_bufs.size() < 1 || prog->P.out_bufs.size() > 64) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_pcm: the outlet must have 1..64 channels");
+    if (prog->P.g.n_inputs > 0 && !h_inputs) CTX_FAIL(ctx, DUSP_ERR_ARG, "render: the program has input streams but h_inputs is NULL");
+    return render_host(prog, n_instances, n_samples, h_params, prog->P.g.n_inputs > 0 ? h_inputs : nullptr, h_out, false, format, normalise, h_peaks);
+}
+
 // Device -> host delivery of the rendered PCM (what renderChannelData's caller finally holds).
 //   * h_out is pinned memory (dusp_host_alloc, or registered by the caller): one asynchronous DMA straight into it.
 //   * h_out is pageable and large: kCopyWorkers worker threads, each with its own stream and a pair of pinned staging
 //     tiles, walk disjoint ranges of the output — DMA of tile i+1 into one tile while the CPU copies tile i out of the
 //     other.  (A plain hipMemcpy to pageable memory stages through ONE pinned buffer with ONE copying thread: 10-13 GB/s.)
 //   * small outputs (event-segmented rendering: hundreds of short renders a second): plain asynchronous copy.
-constexpr size_t kCopyTileFloats = (size_t)2 << 20;   // 8 MiB staging tiles
+constexpr size_t kCopyTileBytes = (size_t)8 << 20;   // 8 MiB staging tiles
 constexpr int kCopyWorkers = 4;
-constexpr size_t kStagedMinFloats = (size_t)8 << 20;  // 32 MiB: below this the staging pipeline is not worth its threads
+constexpr size_t kStagedMinBytes = (size_t)32 << 20;  // 32 MiB: below this the staging pipeline is not worth its threads
 
 static bool is_pinned_host(const void *p) {
     hipPointerAttribute_t attr;
@@ -1487,51 +1541,53 @@ static bool is_pinned_host(const void *p) {
     return attr.type == hipMemoryTypeHost;
 }
 
-static hipError_t download_staged(dusp_program *prog, float *h_out, const float *d_src, size_t n_floats) {
+static hipError_t download_staged(dusp_program *prog, void *h_out_, const void *d_src_, size_t n_bytes) {
     dusp_ctx *ctx = prog->ctx;
-    const size_t need = (size_t)kCopyWorkers * 2 * kCopyTileFloats;
-    if (prog->pin_floats < need) {
+    unsigned char *h_out = (unsigned char *)h_out_;
+    const unsigned char *d_src = (const unsigned char *)d_src_;
+    const size_t need = (size_t)kCopyWorkers * 2 * kCopyTileBytes;
+    if (prog->pin_bytes < need) {
         if (prog->pin[0]) (void)hipHostFree(prog->pin[0]);
         prog->pin[0] = nullptr;
-        prog->pin_floats = 0;
-        hipError_t e = hipHostMalloc((void **)&prog->pin[0], need * sizeof(float), hipHostMallocDefault);
+        prog->pin_bytes = 0;
+        hipError_t e = hipHostMalloc((void **)&prog->pin[0], need, hipHostMallocDefault);
         if (e != hipSuccess) return e;
-        prog->pin_floats = need;
+        prog->pin_bytes = need;
     }
     hipError_t e = hipStreamSynchronize(ctx->stream);  // the render (and the interleave) have finished: the workers only copy
     if (e != hipSuccess) return e;
     hipError_t results[kCopyWorkers];
     std::thread workers[kCopyWorkers];
-    const size_t n_tiles = (n_floats + kCopyTileFloats - 1) / kCopyTileFloats;
+    const size_t n_tiles = (n_bytes + kCopyTileBytes - 1) / kCopyTileBytes;
     for (int w = 0; w < kCopyWorkers; w++) {
         results[w] = hipSuccess;
         workers[w] = std::thread([&, w]() {
             hipError_t &r = results[w];
             hipStream_t st = nullptr;
             if ((r = hipSetDevice(ctx->device)) != hipSuccess || (r = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) return;
-            float *tile[2] = {prog->pin[0] + (size_t)(2 * w) * kCopyTileFloats, prog->pin[0] + (size_t)(2 * w + 1) * kCopyTileFloats};
+            unsigned char *tile[2] = {prog->pin[0] + (size_t)(2 * w) * kCopyTileBytes, prog->pin[0] + (size_t)(2 * w + 1) * kCopyTileBytes};
             // this worker's tiles: a contiguous range (neighbouring pages of h_out are faulted in by one thread)
             const size_t t0 = n_tiles * (size_t)w / kCopyWorkers, t1 = n_tiles * (size_t)(w + 1) / kCopyWorkers;
             auto span = [&](size_t t, size_t &at, size_t &n) {
-                at = t * kCopyTileFloats;
-                n = std::min(kCopyTileFloats, n_floats - at);
+                at = t * kCopyTileBytes;
+                n = std::min(kCopyTileBytes, n_bytes - at);
             };
             hipEvent_t done[2] = {nullptr, nullptr};
             if ((r = hipEventCreateWithFlags(&done[0], hipEventDisableTiming)) == hipSuccess) r = hipEventCreateWithFlags(&done[1], hipEventDisableTiming);
             size_t at, n;
             for (size_t t = t0; r == hipSuccess && t < std::min(t0 + 2, t1); t++) {  // prime both tiles
                 span(t, at, n);
-                if ((r = hipMemcpyAsync(tile[(t - t0) & 1], d_src + at, n * sizeof(float), hipMemcpyDeviceToHost, st)) == hipSuccess)
+                if ((r = hipMemcpyAsync(tile[(t - t0) & 1], d_src + at, n, hipMemcpyDeviceToHost, st)) == hipSuccess)
                     r = hipEventRecord(done[(t - t0) & 1], st);
             }
             for (size_t t = t0; r == hipSuccess && t < t1; t++) {
                 const int k = (int)((t - t0) & 1);
                 if ((r = hipEventSynchronize(done[k])) != hipSuccess) break;
                 span(t, at, n);
-                std::memcpy(h_out + at, tile[k], n * sizeof(float));
+                std::memcpy(h_out + at, tile[k], n);
                 if (t + 2 < t1) {
                     span(t + 2, at, n);
-                    if ((r = hipMemcpyAsync(tile[k], d_src + at, n * sizeof(float), hipMemcpyDeviceToHost, st)) == hipSuccess)
+                    if ((r = hipMemcpyAsync(tile[k], d_src + at, n, hipMemcpyDeviceToHost, st)) == hipSuccess)
                         r = hipEventRecord(done[k], st);
                 }
             }
@@ -1547,8 +1603,8 @@ static hipError_t download_staged(dusp_program *prog, float *h_out, const float 
     return hipSuccess;
 }
 
-static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, float *h_out,
-                       bool interleaved) {
+static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, void *h_out,
+                       bool interleaved, int pcm_format, int normalise, float *h_peaks) {
     if (!prog) return DUSP_ERR_ARG;
     dusp_ctx *ctx = prog->ctx;
     return guarded(ctx->err, "render", [&]() -> int {
@@ -1587,11 +1643,30 @@ static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples,
         d_frames = prog->d_host_frames.p;
         if (int rc = dusp_interleave_device(ctx, d_out, n_instances, n_ch, n_samples, d_frames, ctx->stream)) return rc;
     }
-    const float *d_src = d_frames ? d_frames : d_out;
-    if (n_out >= kStagedMinFloats && !is_pinned_host(h_out)) {
-        HIP_TRY(ctx, download_staged(prog, h_out, d_src, n_out));
+    const void *d_src = d_frames ? d_frames : d_out;
+    size_t n_bytes = n_out * sizeof(float);
+    if (pcm_format) {  // peak, gain, quantisation and interleave on the device: 2 or 3 bytes a sample cross the link
+        const float *d_peaks = nullptr;
+        if (normalise || h_peaks) {
+            HIP_TRY(ctx, prog->d_host_peaks.ensure(n_instances));
+            d_peaks = prog->d_host_peaks.p;
+            if (int rc = dusp_peak_device(ctx, d_out, n_instances, n_ch, n_samples, prog->d_host_peaks.p, ctx->stream)) return rc;
+            if (h_peaks) HIP_TRY(ctx, hipMemcpyAsync(h_peaks, d_peaks, n_instances * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        n_bytes = n_out * (size_t)dusp::pcm_bytes_per_sample(pcm_format);
+        HIP_TRY(ctx, prog->d_host_pcm.ensure(n_bytes));
+        if (int rc = dusp_encode_device(ctx, d_out, n_instances, n_ch, n_samples, pcm_format, normalise, d_peaks, prog->d_host_pcm.p, ctx->stream)) return rc;
+        if (g_guard_bytes) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact())
+                CTX_FAIL(ctx, DUSP_ERR_HIP, "render: the PCM encoder wrote past the end of a device buffer: guard bytes overwritten");
+        }
+        d_src = prog->d_host_pcm.p;
+    }
+    if (n_bytes >= kStagedMinBytes && !is_pinned_host(h_out)) {
+        HIP_TRY(ctx, download_staged(prog, h_out, d_src, n_bytes));
     } else {  // pinned destination: one DMA at link speed; small output: not worth more
-        HIP_TRY(ctx, hipMemcpyAsync(h_out, d_src, n_out * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_out, d_src, n_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: where a host render's time goes)

@@ -372,6 +372,9 @@ typedef struct {
     float *inputs; /* host-generated streams [nInputs][nInstances][nSamples] (copied: the caller may reuse its array) */
     float *out;
     int interleaved; /* frames [instance][sample][channel] instead of planar [instance][channel][sample] */
+    int pcm_format, normalise; /* renderPcm: DUSP_PCM_* (0: a plain render) and DUSP_NORMALISE_* */
+    size_t n_bytes;            /* size of out: n_floats f32, or the encoded frames */
+    float *peaks;              /* renderPcm: every instance's peak */
     int rc;
     char err[512];
 } render_job;
@@ -385,7 +388,9 @@ static void render_execute(napi_env env, void *data) {
         j->rc = DUSP_ERR_STATE;
         snprintf(j->err, sizeof j->err, "dusp-hip: render: the program has been destroyed");
     } else {
-        if (j->inputs) j->rc = dusp_render_host_inputs(prog, j->n_instances, j->n_samples, j->params, j->inputs, j->out, j->interleaved);
+        if (j->pcm_format)
+            j->rc = dusp_render_host_pcm(prog, j->n_instances, j->n_samples, j->params, j->inputs, j->pcm_format, j->normalise, j->out, j->peaks);
+        else if (j->inputs) j->rc = dusp_render_host_inputs(prog, j->n_instances, j->n_samples, j->params, j->inputs, j->out, j->interleaved);
         else
             j->rc = j->interleaved ? dusp_render_host_interleaved(prog, j->n_instances, j->n_samples, j->params, j->out)
                                    : dusp_render_host(prog, j->n_instances, j->n_samples, j->params, j->out);
@@ -431,7 +436,22 @@ static void render_complete(napi_env env, napi_status status, void *data) {
         j->rc = DUSP_ERR_STATE;
         snprintf(j->err, sizeof j->err, "dusp-hip: render was cancelled");
     }
-    if (j->rc == DUSP_OK) {
+    if (j->rc == DUSP_OK && j->pcm_format) { /* { data: Buffer over the encoded frames, peaks: Float32Array } */
+        napi_value data, peaks_ab, peaks;
+        void *peaks_mem;
+        if (napi_create_arraybuffer(env, j->n_instances * sizeof(float), &peaks_mem, &peaks_ab) == napi_ok &&
+            napi_create_typedarray(env, napi_float32_array, j->n_instances, peaks_ab, 0, &peaks) == napi_ok && napi_create_object(env, &result) == napi_ok &&
+            napi_create_external_buffer(env, j->n_bytes, j->out, j->out_pinned ? free_pinned_pcm : free_pcm, j->out_pinned ? (void *)j->pb->cb : NULL, &data) == napi_ok) {
+            j->out = NULL; /* owned by the Buffer now */
+            memcpy(peaks_mem, j->peaks, j->n_instances * sizeof(float));
+            napi_set_named_property(env, result, "data", data);
+            napi_set_named_property(env, result, "peaks", peaks);
+            napi_resolve_deferred(env, j->deferred, result);
+        } else {
+            napi_create_string_utf8(env, "dusp-hip: could not wrap the PCM buffer", NAPI_AUTO_LENGTH, &result);
+            napi_reject_deferred(env, j->deferred, result);
+        }
+    } else if (j->rc == DUSP_OK) {
         napi_value ab;
         if (napi_create_external_arraybuffer(env, j->out, j->n_floats * sizeof(float), j->out_pinned ? free_pinned_pcm : free_pcm,
                                              j->out_pinned ? (void *)j->pb->cb : NULL, &ab) == napi_ok &&
@@ -452,19 +472,34 @@ static void render_complete(napi_env env, napi_status status, void *data) {
     napi_delete_async_work(env, j->work);
     free(j->params);
     free(j->inputs);
+    free(j->peaks);
     free(j);
 }
 
-/* render(prog, nInstances, nSamples, params | null [, interleaved]) -> Promise<Float32Array> */
-static napi_value fn_render(napi_env env, napi_callback_info info) {
-    napi_value argv[6];
-    size_t argc = 6;
-    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 4) {
+/* render(prog, nInstances, nSamples, params | null [, interleaved [, inputs]]) -> Promise<Float32Array>
+ * renderPcm(prog, nInstances, nSamples, params | null, format, normalise [, inputs]) -> Promise<{ data: Buffer, peaks: Float32Array }>
+ *   (dusp_render_host_pcm: peak, gain, quantisation and interleave on the device; format DUSP_PCM_*, normalise DUSP_NORMALISE_*) */
+static napi_value render_call(napi_env env, napi_callback_info info, int pcm) {
+    napi_value argv[7];
+    size_t argc = 7;
+    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < (pcm ? 6u : 4u)) {
         throw_string(env, "dusp-hip: wrong number of arguments");
         return NULL;
     }
+    const size_t inputs_at = pcm ? 6 : 5;
     bool interleaved = false;
-    if (argc >= 5) napi_get_value_bool(env, argv[4], &interleaved);
+    double format = 0, normalise = 0;
+    if (!pcm && argc >= 5) napi_get_value_bool(env, argv[4], &interleaved);
+    if (pcm) {
+        if (napi_get_value_double(env, argv[4], &format) != napi_ok || !(format == DUSP_PCM_S16 || format == DUSP_PCM_S24 || format == DUSP_PCM_F32)) {
+            throw_string(env, "dusp-hip: renderPcm: format must be 1 (s16), 2 (s24) or 3 (f32)");
+            return NULL;
+        }
+        if (napi_get_value_double(env, argv[5], &normalise) != napi_ok || !(normalise == 0 || normalise == 1 || normalise == 2)) {
+            throw_string(env, "dusp-hip: renderPcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
+            return NULL;
+        }
+    }
     prog_box *pb = as_prog(env, argv[0]);
     if (!pb) return NULL;
     double n_inst = 0, n_samples = 0;
@@ -486,34 +521,46 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {
     j->n_samples = (size_t)n_samples;
     j->n_floats = j->n_instances * pi.n_out_channels * j->n_samples;
     j->interleaved = interleaved ? 1 : 0;
+    j->pcm_format = (int)format;
+    j->normalise = (int)normalise;
+    j->n_bytes = j->n_floats * (size_t)(!pcm || j->pcm_format == DUSP_PCM_F32 ? 4 : j->pcm_format == DUSP_PCM_S16 ? 2 : 3);
+    if (pcm && !(j->peaks = (float *)malloc(j->n_instances * sizeof(float)))) {
+        free(j);
+        throw_string(env, "dusp-hip: render: out of host memory");
+        return NULL;
+    }
     napi_valuetype vt;
     napi_typeof(env, argv[3], &vt);
     if (vt != napi_null && vt != napi_undefined) {
         void *data;
         size_t len;
         if (!typed_array(env, argv[3], napi_float32_array, &data, &len) || len != (size_t)pi.n_params * j->n_instances) {
+            free(j->peaks);
             free(j);
             throw_string(env, "dusp-hip: render: params must be a Float32Array of nParams * nInstances values");
             return NULL;
         }
         j->params = (float *)malloc(len * sizeof(float) + 1);
         if (!j->params) {
+            free(j->peaks);
             free(j);
             throw_string(env, "dusp-hip: render: out of host memory for the parameter table");
             return NULL;
         }
         memcpy(j->params, data, len * sizeof(float));
     } else if (pi.n_params) {
+        free(j->peaks);
         free(j);
         throw_string(env, "dusp-hip: render: this program needs a parameter table");
         return NULL;
     }
-    if (argc >= 6) napi_typeof(env, argv[5], &vt);
-    if (argc >= 6 && vt != napi_null && vt != napi_undefined) { /* inputs: Float32Array of nInputs * nInstances * nSamples values */
+    if (argc > inputs_at) napi_typeof(env, argv[inputs_at], &vt);
+    if (argc > inputs_at && vt != napi_null && vt != napi_undefined) { /* inputs: Float32Array of nInputs * nInstances * nSamples values */
         void *data;
         size_t len;
-        if (!typed_array(env, argv[5], napi_float32_array, &data, &len) || len != (size_t)pi.n_inputs * j->n_instances * j->n_samples || !len) {
+        if (!typed_array(env, argv[inputs_at], napi_float32_array, &data, &len) || len != (size_t)pi.n_inputs * j->n_instances * j->n_samples || !len) {
             free(j->params);
+            free(j->peaks);
             free(j);
             throw_string(env, "dusp-hip: render: inputs must be a Float32Array of nInputs * nInstances * nSamples values");
             return NULL;
@@ -521,6 +568,7 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {
         j->inputs = (float *)malloc(len * sizeof(float) + 1);
         if (!j->inputs) {
             free(j->params);
+            free(j->peaks);
             free(j);
             throw_string(env, "dusp-hip: render: out of host memory for the input streams");
             return NULL;
@@ -528,6 +576,7 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {
         memcpy(j->inputs, data, len * sizeof(float));
     } else if (pi.n_inputs) {
         free(j->params);
+        free(j->peaks);
         free(j);
         throw_string(env, "dusp-hip: render: this program reads host-generated input streams");
         return NULL;
@@ -535,10 +584,10 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {
     /* The result buffer IS the ArrayBuffer JavaScript gets (renderChannelData.js:39 allocates per call; no copy here).  Large
      * results come from the context's pinned pool so that the download is one DMA at link speed; small ones (event-segmented
      * rendering makes hundreds a second) from malloc. */
-    if (j->n_floats * sizeof(float) >= PINNED_MIN_BYTES) {
+    if (j->n_bytes >= PINNED_MIN_BYTES) {
         void *p = NULL;
         pthread_mutex_lock(&pb->cb->lock);
-        int rc = dusp_host_alloc(pb->cb->ctx, j->n_floats * sizeof(float), &p);
+        int rc = dusp_host_alloc(pb->cb->ctx, j->n_bytes, &p);
         pthread_mutex_unlock(&pb->cb->lock);
         if (rc == DUSP_OK) {
             j->out = (float *)p;
@@ -547,10 +596,11 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {
             pb->cb->refs++;
         }
     }
-    if (!j->out) j->out = (float *)malloc(j->n_floats * sizeof(float) + 1);
+    if (!j->out) j->out = (float *)malloc(j->n_bytes + 1);
     if (!j->out) {
         free(j->inputs);
         free(j->params);
+        free(j->peaks);
         free(j);
         throw_string(env, "dusp-hip: render: out of host memory for the PCM buffer");
         return NULL;
@@ -562,6 +612,7 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {
         release_out(j);
         free(j->inputs);
         free(j->params);
+        free(j->peaks);
         free(j);
         throw_string(env, "dusp-hip: render: could not queue the render");
         return NULL;
@@ -572,12 +623,15 @@ static napi_value fn_render(napi_env env, napi_callback_info info) {
         release_out(j);
         free(j->inputs);
         free(j->params);
+        free(j->peaks);
         free(j);
         throw_string(env, "dusp-hip: render: could not queue the render");
         return NULL;
     }
     return promise;
 }
+static napi_value fn_render(napi_env env, napi_callback_info info) { return render_call(env, info, 0); }
+static napi_value fn_render_pcm(napi_env env, napi_callback_info info) { return render_call(env, info, 1); }
 
 static napi_value init(napi_env env, napi_value exports) {
     static const struct {
@@ -588,6 +642,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ctxDestroy", fn_ctx_destroy},   {"tableUpload", fn_table_upload},   {"programBuild", fn_program_build},
         {"programDestroy", fn_program_destroy}, {"programInfo", fn_program_info}, {"stateDownload", fn_state_download},
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
+        {"renderPcm", fn_render_pcm},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

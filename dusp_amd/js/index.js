@@ -11,6 +11,8 @@ const dusp = require('./lib/dusp')
 module.exports = {
   renderChannelData,
   renderMany: renderChannelData.renderMany,
+  renderPcm: renderChannelData.renderPcm,
+  renderWav: renderChannelData.renderWav,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),
@@ -20,6 +22,7 @@ module.exports = {
   SegmentRenderer: renderChannelData.SegmentRenderer,
   encodeWav: require('./lib/wav').encodeWav,
   decodeWav: require('./lib/wav').decodeWav,
+  encodeFrames: require('./lib/wav').encodeFrames,
   parse: require('./lib/parse'),
   config: require('./lib/config'),
   extract: require('./lib/extract').extract,

@@ -14,6 +14,7 @@ const native = require('./native')
 const { extract, unify, deviceRetrigger } = require('./extract')
 const { makeTables } = require('./wavetables')
 const { OP, UNITS } = require('./ops')
+const { encodeWav, encodeFrames } = require('./wav')
 
 const contexts = new Map() // "sampleRate|device|slot" -> native context with that rate's wave tables
 
@@ -224,7 +225,9 @@ class SegmentRenderer {
         inputs = new Float32Array(ex.sources.length * len)
         ex.sources.forEach((u, k) => u.takeSegment(len, inputs, k * len))
       }
-      const pcm = await n.render(this.prog, 1, len, null, false, inputs) // Float32Array [channel][len]
+      // Float32Array [channel][len]; or, for renderPcm's single segment, { data: Buffer of encoded frames, peaks }
+      const pcm = this.encode ? await n.renderPcm(this.prog, 1, len, null, this.encode.format, this.encode.normalise, inputs)
+        : await n.render(this.prog, 1, len, null, false, inputs)
       writeBack(n, this.prog, this.circuit, chunk, len) // advances circuit.clock to `next`
       pieces.push({ pcm, len, nChannels: n.programInfo(this.prog).nOutChannels })
       this.clock = next
@@ -262,6 +265,39 @@ async function renderChannelData(outlet, duration = 1, { TypedArray = Float32Arr
   } finally {
     renderer.close()
   }
+}
+
+const PCM_FORMAT = { 16: 1, 24: 2, 32: 3 } // DUSP_PCM_S16 / _S24 / _F32 (include/dusp_hip.h)
+
+/* renderChannelData, delivering peak-normalised frames: resolves to { data: Buffer, bitDepth, numberOfChannels, sampleRate, peak }
+ * — data holds interleaved little-endian int16 / packed int24 (or f32 at bitDepth 32), peak the render's max |x| before the gain;
+ * normalise 0: none, 1: shrink only a render that would clip, 2: to full scale (one gain for all channels; the sample contract is in
+ * include/dusp_hip.h, "Device-side PCM delivery").
+ *
+ * A circuit without scheduled events and host-ticked units is ONE device render: the peak search, the gain, the quantisation and the
+ * interleave run on the GPU (dusp_render_host_pcm) and 2 or 3 bytes per sample are downloaded.  A circuit that is rendered in segments
+ * arrives as f32 on the host and is encoded here by the same contract (wav.js encodeFrames), the peak taken over the whole render.
+ * The bytes are the same either way. */
+async function renderPcm(outlet, duration = 1, { bitDepth = 16, normalise = 0, engine = 0 } = {}) {
+  if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderPcm: bitDepth must be 16, 24 or 32' // (numbers: '16' is refused like 8)
+  if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderPcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
+  const renderer = new SegmentRenderer(outlet, { engine })
+  try {
+    const sampleRate = renderer.sampleRate, nSamples = sampleCount(duration, sampleRate)
+    if (nSamples === 0) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
+    if (!renderer.hasEvents) renderer.encode = { format: PCM_FORMAT[bitDepth], normalise }
+    const { pcm, nChannels } = await renderer.next(nSamples)
+    if (renderer.encode) return { data: pcm.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: pcm.peaks[0] }
+    const { data, peak } = encodeFrames(pcm, nChannels, nSamples, bitDepth, normalise)
+    return { data, bitDepth, numberOfChannels: nChannels, sampleRate, peak }
+  } finally {
+    renderer.close()
+  }
+}
+
+/* renderPcm plus the RIFF/WAVE header: resolves to a Buffer holding a complete file. */
+async function renderWav(outlet, duration = 1, opts = {}) {
+  return encodeWav(await renderPcm(outlet, duration, opts))
 }
 
 /* N structurally identical circuits (voices, a parameter sweep) as ONE GPU program per device:
@@ -350,6 +386,8 @@ module.exports = renderChannelData
 module.exports.renderChannelData = renderChannelData
 module.exports.renderDescriptor = renderDescriptor
 module.exports.renderMany = renderMany
+module.exports.renderPcm = renderPcm
+module.exports.renderWav = renderWav
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

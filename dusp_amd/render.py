@@ -11,7 +11,7 @@ program with a per-instance parameter table.
 """
 import numpy as np
 
-from . import descriptor, runtime
+from . import descriptor, runtime, wav
 
 _contexts = {}
 
@@ -92,7 +92,10 @@ def renderChannelData(outlet, duration=1, TypedArray=np.float32, engine=runtime.
     ONE device program is continued from segment to segment (dusp_program_continue), so delay lines, CircleBuffers
     and feedback chunks stay resident on the device.  Afterwards the circuit is consumed like the reference's:
     circuit.clock has advanced and the unit objects hold their post-render state."""
-    first = descriptor.extract(outlet, allow_events=True)
+    return _render_extracted(outlet, descriptor.extract(outlet, allow_events=True), duration, TypedArray, engine, device)
+
+
+def _render_extracted(outlet, first, duration, TypedArray, engine, device):
     circuit, chunk = first.circuit, first.chunk_size
     n = _n_samples(duration, first.sample_rate)
     result = ChannelData()
@@ -143,3 +146,51 @@ def render_many(outlets, duration=1, engine=runtime.ENGINE_AUTO, device=-1):
         return prog.render(n, uni.n_instances, uni.params)
     finally:
         prog.close()
+
+
+class PcmData:
+    """Encoded frames of one render: `data` int16 [samples, channels] (bitDepth 16), uint8 [samples, channels, 3] (24) or float32
+    [samples, channels] (32); `peak` is the render's max |x| before the gain.  wav.encode_wav(data, sampleRate, bitDepth) makes a file of it."""
+
+    def __init__(self, data, bit_depth, sample_rate, peak):
+        self.data, self.bitDepth, self.sampleRate, self.peak = data, bit_depth, sample_rate, np.float32(peak)
+        self.numberOfChannels = data.shape[1]
+
+
+_PCM_FORMAT = {16: "s16", 24: "s24", 32: "f32"}
+
+
+def render_pcm(outlet, duration=1, bit_depth=16, normalise=0, engine=runtime.ENGINE_AUTO, device=-1):
+    """renderChannelData, delivering peak-normalised 16- / 24-bit (or f32) frames -> PcmData.  normalise: 0 none, 1 shrink only a render
+    that would clip, 2 to full scale; one gain for all channels (include/dusp_hip.h "Device-side PCM delivery" is the sample contract).
+
+    An event-free circuit is encoded on the device (Program.render_pcm): peak, gain, quantisation and interleave run there and 2 or 3
+    bytes per sample are downloaded.  A circuit with scheduled events is rendered in segments that arrive as f32 on the host
+    (renderChannelData); those are encoded here by the same contract (wav.encode_frames), the peak taken over the whole render.  The
+    bytes are the same either way.  Like renderChannelData this consumes the circuit."""
+    if bit_depth not in _PCM_FORMAT:
+        raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
+    if normalise not in (0, 1, 2):
+        raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
+    first = descriptor.extract(outlet, allow_events=True)
+    n = _n_samples(duration, first.sample_rate)
+    if n > 0 and not first.circuit.events:
+        prog = context(first.sample_rate, device).build(first.words, engine)
+        try:
+            data, peaks = prog.render_pcm(n, 1, format=_PCM_FORMAT[bit_depth], normalise=normalise, inputs=_host_inputs(first.sources, 0, n))
+            write_back(prog, first.circuit, first.chunk_size, n)
+        finally:
+            prog.close()
+        return PcmData(data[0], bit_depth, first.sample_rate, peaks[0])
+    channels = _render_extracted(outlet, first, duration, np.float32, engine, device)
+    planar = np.stack([np.asarray(c, dtype=np.float32) for c in channels]) if n > 0 else np.zeros((1, 0), dtype=np.float32)
+    data, peak = wav.encode_frames(planar, bit_depth, normalise)
+    return PcmData(data, bit_depth, first.sample_rate, peak)
+
+
+def render_wav(outlet, duration=1, bit_depth=16, normalise=0, engine=runtime.ENGINE_AUTO, device=-1):
+    """A complete RIFF/WAVE file (bytes) of the render: render_pcm plus the header (wav.encode_wav)."""
+    pcm = render_pcm(outlet, duration, bit_depth, normalise, engine, device)
+    if bit_depth == 32:
+        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
+    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)

@@ -24,7 +24,13 @@ EXPORTS = [
     "dusp_render_device", "dusp_render_host", "dusp_render_host_interleaved", "dusp_interleave_device", "dusp_state_download",
     "dusp_last_kernel_ms", "dusp_fill_device", "dusp_render_device_inputs", "dusp_render_host_inputs",
     "dusp_host_alloc", "dusp_host_free", "dusp_circuit_kernel_source", "dusp_jit_cache_dir", "dusp_render_chain_window", "dusp_device_count",
+    "dusp_peak_device", "dusp_encode_device", "dusp_render_host_pcm",
 ]
+
+PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
+PCM_FORMATS = {"s16": PCM_S16, "s24": PCM_S24, "f32": PCM_F32}
+PCM_BYTES = {PCM_S16: 2, PCM_S24: 3, PCM_F32: 4}
+NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL = 0, 1, 2  # dusp_normalise
 
 
 class DuspHipError(RuntimeError):
@@ -77,6 +83,9 @@ def load():
     L.dusp_render_host.argtypes = [vp, sz, sz, vp, vp]
     L.dusp_render_host_interleaved.argtypes = [vp, sz, sz, vp, vp]
     L.dusp_interleave_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
+    L.dusp_peak_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
+    L.dusp_encode_device.argtypes = [vp, vp, sz, sz, sz, ci, ci, vp, vp, vp]
+    L.dusp_render_host_pcm.argtypes = [vp, sz, sz, vp, vp, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -123,6 +132,15 @@ def circuit_kernel_source(words, waves=16, per_wave=1, lds_table=True, compile=F
     return buf.value.decode()
 
 
+def _pcm_format(format):
+    """"s16" | "s24" | "f32" (or the DUSP_PCM_* number) -> DUSP_PCM_*"""
+    if isinstance(format, str):
+        if format not in PCM_FORMATS:
+            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
+        return PCM_FORMATS[format]
+    return int(format)
+
+
 class Context:
     """One HIP device + stream + the uploaded wave tables."""
 
@@ -148,20 +166,25 @@ class Context:
         """float32 array for a render result (replaces `new TypedArray(lengthInSamples)`, renderChannelData.js:39).  Large
         results live in the context's pinned pool so that the download is a direct DMA; the block returns to the pool when
         the array (and every view of it) has been collected."""
-        n = int(np.prod(shape))
+        return self.host_empty_bytes(shape, np.float32, pinned)
+
+    def host_empty_bytes(self, shape, dtype, pinned=None):
+        """host_empty for any sample type (int16 / uint8 frames of render_pcm): sized in bytes, same pool, same rules."""
+        dtype = np.dtype(dtype)
+        nbytes = int(np.prod(shape)) * dtype.itemsize
         if pinned is None:
             with self._host_lock:
-                pinned = n * 4 >= PINNED_MIN_BYTES and self._host_live_bytes + n * 4 <= PINNED_MAX_LIVE_BYTES
-        if not pinned or n == 0:
-            return np.empty(shape, dtype=np.float32)
+                pinned = nbytes >= PINNED_MIN_BYTES and self._host_live_bytes + nbytes <= PINNED_MAX_LIVE_BYTES
+        if not pinned or nbytes == 0:
+            return np.empty(shape, dtype=dtype)
         p = ctypes.c_void_p()
         with self._host_lock:
-            self._check(self._L.dusp_host_alloc(self._h, n * 4, ctypes.byref(p)))
+            self._check(self._L.dusp_host_alloc(self._h, nbytes, ctypes.byref(p)))
             self._host_live += 1
-            self._host_live_bytes += n * 4
-        buf = (ctypes.c_float * n).from_address(p.value)
-        buf._dusp_owner = _PinnedBlock(self, p.value, n * 4)
-        return np.frombuffer(buf, dtype=np.float32).reshape(shape)
+            self._host_live_bytes += nbytes
+        buf = (ctypes.c_ubyte * nbytes).from_address(p.value)
+        buf._dusp_owner = _PinnedBlock(self, p.value, nbytes)
+        return np.frombuffer(buf, dtype=dtype).reshape(shape)
 
     def _host_release(self, ptr, nbytes=0):
         with self._host_lock:
@@ -194,6 +217,15 @@ class Context:
     def interleave(self, d_planar, n_instances, n_channels, n_samples, d_out, stream=None):
         """Device pointers: planar f32 [instance][channel][sample] -> frames f32 [instance][sample][channel]."""
         self._check(self._L.dusp_interleave_device(self._h, d_planar, n_instances, n_channels, n_samples, d_out, stream))
+
+    def peak(self, d_planar, n_instances, n_channels, n_samples, d_peaks, stream=None):
+        """Device pointers: planar f32 [instance][channel][sample] -> f32 [instance], each instance's exact max |x| (NaN if it holds one)."""
+        self._check(self._L.dusp_peak_device(self._h, d_planar, n_instances, n_channels, n_samples, d_peaks, stream))
+
+    def encode(self, d_planar, n_instances, n_channels, n_samples, d_out, format="s16", normalise=NORMALISE_NONE, d_peaks=None, stream=None):
+        """Device pointers: planar f32 -> interleaved s16 / packed s24 / f32 frames [instance][sample][channel], each instance scaled by the
+        gain its peak (d_peaks, from Context.peak) gives under `normalise` (include/dusp_hip.h: the sample contract)."""
+        self._check(self._L.dusp_encode_device(self._h, d_planar, n_instances, n_channels, n_samples, _pcm_format(format), int(normalise), d_peaks, d_out, stream))
 
     def fill(self, d_ptr, n_floats, value=0.0, stream=None):
         self._check(self._L.dusp_fill_device(self._h, d_ptr, n_floats, value, stream))
@@ -268,6 +300,33 @@ class Program:
         call = self._L.dusp_render_host_interleaved if interleaved else self._L.dusp_render_host
         self.ctx._check(call(self._h, n_instances, n_samples, pp, out.ctypes.data))
         return out
+
+    def render_pcm(self, n_samples, n_instances=1, params=None, format="s16", normalise=NORMALISE_NONE, inputs=None, pinned=None):
+        """Host round trip that delivers encoded frames (dusp_render_host_pcm): peak, gain, quantisation and interleave run on the device
+        and 2 (s16) or 3 (s24) bytes per sample are downloaded.  Returns (data, peaks): data int16 [n_instances, n_samples, n_out_channels]
+        for "s16", uint8 [.., .., .., 3] (little-endian 24-bit) for "s24", float32 for "f32"; peaks float32 [n_instances], every instance's
+        max |x| before the gain.  normalise: 0 none, 1 shrink only an instance that would clip, 2 every instance to full scale."""
+        fmt = _pcm_format(format)
+        if fmt not in PCM_BYTES:
+            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
+        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
+            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
+        shape = (n_instances, n_samples, self.n_out_channels)
+        out = self.ctx.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
+        peaks = np.empty(n_instances, dtype=np.float32)
+        pp = ip = None
+        if self.n_params:
+            params = np.ascontiguousarray(params, dtype=np.float32)
+            if params.shape != (self.n_params, n_instances):
+                raise ValueError("params must have shape (n_params=%d, n_instances=%d)" % (self.n_params, n_instances))
+            pp = params.ctypes.data
+        if self.n_inputs:
+            inputs = np.ascontiguousarray(inputs, dtype=np.float32)
+            if inputs.shape != (self.n_inputs, n_instances, n_samples):
+                raise ValueError("inputs must have shape (n_inputs=%d, n_instances=%d, n_samples=%d)" % (self.n_inputs, n_instances, n_samples))
+            ip = inputs.ctypes.data
+        self.ctx._check(self._L.dusp_render_host_pcm(self._h, n_instances, n_samples, pp, ip, fmt, int(normalise), out.ctypes.data, peaks.ctypes.data))
+        return out, peaks
 
     def render_device(self, n_samples, n_instances, d_params, d_out, stream=None, d_inputs=None):
         """Asynchronous render between device pointers (ints), e.g. torch tensors' data_ptr()."""

@@ -227,6 +227,41 @@ int dusp_interleave_device(dusp_ctx *ctx, const float *d_planar, size_t n_instan
 /* dusp_render_host, delivering interleaved frames: h_out is f32 [n_instances][n_samples][n_out_channels]. */
 int dusp_render_host_interleaved(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, float *h_out);
 
+/* Device-side PCM delivery (additions to ABI v7: DUSP_ABI_VERSION is unchanged, a binder detects them by symbol).  Replaces
+ * the host's per-sample encode loop: the peak search, the gain, the quantisation and the interleave run on the device, and
+ * 2 (s16) or 3 (s24) bytes per sample are downloaded instead of 4.
+ *
+ * The sample contract (dusp_amd/csrc/pcm_quant.hpp; dusp_amd/wav.py and dusp_amd/js/lib/wav.js compute the same bytes), for
+ * an f32 sample x, the instance's gain g (a double) and S = 32767 (s16) or 8388607 (s24):
+ *     t = (double)x * g;  t = NaN ? 0 : min(max(t, -1), 1);  q = t * S rounded to the nearest integer, halves away from zero
+ * as little-endian int16 / packed 3-byte int24, interleaved [instance][frame][channel].  DUSP_PCM_F32 is (float)((double)x * g),
+ * interleaved, not clamped, NaN left as it is.
+ *   peak  of an instance: the exact maximum of |x| over all its channels and samples, as an f32; NaN if any sample is NaN.
+ *   gain  DUSP_NORMALISE_NONE: 1.  DUSP_NORMALISE_CLIP: 1 / (double)peak when the peak is finite and > 1 (shrink only what
+ *         would clip), else 1.  DUSP_NORMALISE_FULL: 1 / (double)peak when the peak is finite and > 0, else 1.  One gain
+ *         per instance covers all its channels. */
+typedef enum { DUSP_PCM_S16 = 1, DUSP_PCM_S24 = 2, DUSP_PCM_F32 = 3 } dusp_pcm_format;
+typedef enum { DUSP_NORMALISE_NONE = 0, DUSP_NORMALISE_CLIP = 1, DUSP_NORMALISE_FULL = 2 } dusp_normalise;
+
+/* Peaks of planar PCM f32 [n_instances][n_channels][n_samples] -> d_peaks f32 [n_instances].  Device pointers, asynchronous. */
+int dusp_peak_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples,
+                     float *d_peaks, void *stream);
+
+/* Planar PCM -> encoded frames: d_out receives n_instances * n_samples * n_channels * (2 | 3 | 4) bytes, exactly (any byte
+ * alignment for s16 / s24, 4-byte aligned for f32; fastest from 16-byte boundaries).  Every instance's gain is derived on
+ * the device from d_peaks (what dusp_peak_device wrote; NULL allowed only when normalise == 0): no host round trip, no
+ * synchronisation.  Device pointers, asynchronous; the buffers must not overlap. */
+int dusp_encode_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples,
+                       int format, int normalise, const float *d_peaks, void *d_out, void *stream);
+
+/* dusp_render_host, delivering encoded frames: renders, measures the peaks (when normalise != 0 or h_peaks is given),
+ * encodes, and downloads n_instances * n_samples * n_out_channels * bytes into h_out by the delivery paths of
+ * dusp_render_host (pinned: one DMA; large and pageable: the staged workers; small: a plain copy).
+ *   h_inputs  f32 [n_inputs][n_instances][n_samples]; NULL unless the program has input streams
+ *   h_peaks   f32 [n_instances], may be NULL */
+int dusp_render_host_pcm(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs,
+                         int format, int normalise, void *h_out, float *h_peaks);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:
