@@ -76,6 +76,9 @@ struct Knobs {
     int filter_fma = 0;          // DUSP_FILTER_FMA=1 (EXPERIMENT, off): the Filter stage's recurrence as fma(-b1, y1, P - b2 y2) — three dependent instructions a step
                                  // instead of five, but ANOTHER rounding than Filter.js:40-46's (tolerance-level; compiled kernels only)
     int jit_profile = 0;         // DUSP_JIT_PROFILE=1: diagnostic kernels that stamp the cycle counter; sums printed to stderr after each render
+    int mix_width = 0;           // DUSP_MIX_WIDTH=1 | 4 (measurements, tests): the mix kernel with one float a lane everywhere / four wherever 16-byte accesses are possible (0: by grid size, launch_mix)
+    int mix_depth = 0;           // DUSP_MIX_DEPTH=8 | 32 (measurements): rows a lane of the mix kernel's dword form keeps in flight (0: 32 only where the grid cannot fill the chip)
+    int mix_tile_mb = 0;         // DUSP_MIX_TILE_MB=n (measurements): dusp_render_host_mix sizes its default tile for n MiB of PCM (0: the batch that fills the chip, within kMixTileBytes)
 };
 
 #if defined(__HIPCC__)

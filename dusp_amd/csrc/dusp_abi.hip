@@ -41,6 +41,8 @@ hipError_t launch_pcm_peak(const float *d_planar, float *d_peaks, uint32_t n_ins
 hipError_t launch_pcm_encode(const float *d_planar, const float *d_peaks, int format, int normalise, void *d_out, uint32_t n_instances, uint32_t n_channels,
                              uint64_t n_samples, int n_cus, hipStream_t stream);
 uint64_t pcm_encode_tiles(uint64_t n_instances, uint32_t n_channels, uint64_t n_samples, int format);
+hipError_t launch_mix(const float *d_planar, const float *d_gains, const float *d_init, float *d_out, uint64_t row_len, uint32_t n_inst, int raw, int n_cus,
+                      int width_knob, int depth_knob, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -142,6 +144,16 @@ struct dusp_program {
     DevBuf<float> d_host_out, d_host_par, d_host_frames, d_host_in;  // dusp_render_host staging, grown on demand
     DevBuf<unsigned char> d_host_pcm;                                // dusp_render_host_pcm: the encoded frames ...
     DevBuf<float> d_host_peaks;                                      // ... and the instances' peaks
+    DevBuf<float> d_mix, d_mix_gains;                                // dusp_render_host_mix: the running sums [n_out_channels][n_samples]; one tile's gains
+    bool mixed = false;  // the last thing rendered was a mix: unit state describes its last tile only (dusp_state_download refuses)
+    // ... while its tiles render: the range of every parameter column over the WHOLE batch, [n_params][3] as dusp_column_range_kernel
+    // states it (empty otherwise).  What a render decides from a column's values and that changes bits (Filters as scans:
+    // jit_classify_columns) is decided from these, so every tile renders as the one render of the whole batch would
+    std::vector<unsigned> mix_range;
+    // ... and the instance count of the whole batch (0 otherwise).  A tile waits for its compiled kernel whatever DUSP_WAVE_JIT says
+    // (render_jit), and plans warming segments — which keep the Filter stage where an unsplit render may scan — as the whole batch would
+    // (jit_plan.hpp JitBatch::whole_n_inst): all tiles of a mix run the same arithmetic, the one render of all instances' own
+    uint32_t mix_n_inst = 0;
     int requested_engine = DUSP_ENGINE_AUTO;
     bool resumable = false;      // built with DUSP_ENGINE_RESUMABLE
     bool persistent = false;     // rings / feedback edges: device memory carries over between segments (CHUNK engine only)
@@ -189,6 +201,8 @@ struct dusp_program {
         for (DevBuf<double> *b : {&d_init, &d_state, &d_fused_state, &d_jit_dk}) b->release();
         d_host_pcm.release();
         d_host_peaks.release();
+        d_mix.release();
+        d_mix_gains.release();
         d_jit_scan.release();
         d_jit_regime.release();
         d_handoff_init.release();
@@ -274,6 +288,9 @@ static dusp::Knobs read_knobs() {
     k.delay_line = num("DUSP_DELAY_LINE", k.delay_line);
     k.jit_rotate = num("DUSP_JIT_ROTATE", k.jit_rotate);
     k.ring_poison = num("DUSP_RING_POISON", k.ring_poison);
+    k.mix_width = num("DUSP_MIX_WIDTH", k.mix_width);
+    k.mix_depth = num("DUSP_MIX_DEPTH", k.mix_depth);
+    k.mix_tile_mb = num("DUSP_MIX_TILE_MB", k.mix_tile_mb);
     if (const char *f = getenv("DUSP_JIT_FORCE")) {
         int w = 0, r = 0;
         if (std::sscanf(f, "%dx%d", &w, &r) == 2 && w >= 1 && w <= 16 && r >= 1 && r <= 4) k.jit_force_waves = w, k.jit_force_per_wave = r;
@@ -803,7 +820,10 @@ static int jit_classify_columns(dusp_program *prog, uint32_t n_inst, const float
         HIP_TRY(ctx, dusp::jit_launch_classify_delays(d_params, n_inst, d_entries, (int)n, d_bits, stream));
         HIP_TRY(ctx, hipMemcpyAsync(bits.data(), d_bits, n * sizeof(int), hipMemcpyDeviceToHost, stream));
     }
-    if (nf) {
+    if (nf && !prog->mix_range.empty()) {  // a tile of a mix: the range of the whole batch's column
+        for (size_t i = 0; i < nf; i++)
+            for (int j = 0; j < 3; j++) range[3 * i + j] = prog->mix_range[3 * (size_t)slots[i] + j];
+    } else if (nf) {
         HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), nf * sizeof(int), hipMemcpyHostToDevice, stream));
         HIP_TRY(ctx, hipMemsetAsync(d_range, 0, 3 * nf * sizeof(unsigned), stream));
         HIP_TRY(ctx, dusp::jit_launch_column_range(d_params, n_inst, d_slots, (int)nf, d_range, stream));
@@ -857,6 +877,7 @@ static int jit_plan_render(dusp_program *prog, JitRender &R, uint32_t n_inst, ui
     batch.handoff = handoff;
     batch.inputs = inputs;
     batch.voice_loop = prog->voice_loop != 0;
+    batch.whole_n_inst = prog->mix_n_inst;
     R.plan = dusp::jit_plan(site, batch, prog->P, prog->wave);
     if (R.plan.error) CTX_FAIL(ctx, DUSP_ERR_ARG, R.plan.error);
     R.a.n_seg = R.plan.n_seg;
@@ -1091,6 +1112,7 @@ static void finish_render(dusp_program *prog, uint32_t n_inst, uint32_t n_pad, u
     prog->last_n_pad = n_pad;
     prog->rendered = true;
     prog->h_state_valid = false;
+    prog->mixed = false;
     prog->next_clock = prog->P.g.clock0 + (int64_t)n_chunks_total * dusp::kChunk;
 }
 
@@ -1131,7 +1153,9 @@ static int render_jit(dusp_program *prog, uint32_t n_inst, size_t n_samples, uin
     a.vec4_ok = (n_samples % 4 == 0) && (((uintptr_t)d_out & 15) == 0);
     a.n_out = (uint32_t)P.out_bufs.size();
     if (int rc = jit_plan_render(prog, R, n_inst, n_chunks, persistent, resume, handoff_chunks > 0, d_inputs != nullptr)) return rc;
-    if (int rc = jit_obtain_kernel(prog, R, n_inst, n_chunks, /*wait=*/handoff_chunks && !probe)) return rc;  // (kJitLater included)
+    // (a tile of a mix waits like a hand-off: a mix whose first tiles ran on the interpreter and whose later ones on the kernel would sum the Filter
+    // stage's arithmetic and the scan's, split wherever the compile happened to finish)
+    if (int rc = jit_obtain_kernel(prog, R, n_inst, n_chunks, /*wait=*/(handoff_chunks && !probe) || prog->mix_n_inst)) return rc;  // (kJitLater included)
     if (probe) return DUSP_OK;
     if (int rc = jit_workspaces(prog, R, n_chunks, persistent, resume, stream)) return rc;
     const unsigned per_block = (unsigned)(R.plan.waves * R.plan.per_wave);
@@ -1208,6 +1232,7 @@ static int check_guards(dusp_program *prog, hipStream_t stream) {
     else if (!prog->d_host_out.intact()) hit = "staging PCM";
     else if (!prog->d_host_frames.intact()) hit = "staging frames";
     else if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact()) hit = "staging PCM frames / peaks";
+    else if (!prog->d_mix.intact() || !prog->d_mix_gains.intact()) hit = "mix sums / gains";
     else if (!prog->d_host_par.intact()) hit = "staging parameters";
     else if (!prog->d_host_in.intact()) hit = "staging inputs";
     else if (!prog->d_handoff_init.intact() || !prog->d_handoff_out.intact()) hit = "hand-off buffers";
@@ -1603,6 +1628,41 @@ static hipError_t download_staged(dusp_program *prog, void *h_out_, const void *
     return hipSuccess;
 }
 
+// What a host render ends with: d_planar f32 [n_instances][n_ch][n_samples] (or, already transposed, d_frames) reaches h_out — as it is,
+// or (pcm_format != 0) through the peak and encode kernels — by the delivery paths above; waits for the stream.
+static int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
+                        int normalise, float *h_peaks, void *h_out) {
+    dusp_ctx *ctx = prog->ctx;
+    const size_t n_out = n_instances * n_ch * n_samples;
+    const void *d_src = d_frames ? d_frames : d_planar;
+    size_t n_bytes = n_out * sizeof(float);
+    if (pcm_format) {  // peak, gain, quantisation and interleave on the device: 2 or 3 bytes a sample cross the link
+        const float *d_peaks = nullptr;
+        if (normalise || h_peaks) {
+            HIP_TRY(ctx, prog->d_host_peaks.ensure(n_instances));
+            d_peaks = prog->d_host_peaks.p;
+            if (int rc = dusp_peak_device(ctx, d_planar, n_instances, n_ch, n_samples, prog->d_host_peaks.p, ctx->stream)) return rc;
+            if (h_peaks) HIP_TRY(ctx, hipMemcpyAsync(h_peaks, d_peaks, n_instances * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        n_bytes = n_out * (size_t)dusp::pcm_bytes_per_sample(pcm_format);
+        HIP_TRY(ctx, prog->d_host_pcm.ensure(n_bytes));
+        if (int rc = dusp_encode_device(ctx, d_planar, n_instances, n_ch, n_samples, pcm_format, normalise, d_peaks, prog->d_host_pcm.p, ctx->stream)) return rc;
+        if (g_guard_bytes) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact())
+                CTX_FAIL(ctx, DUSP_ERR_HIP, "render: the PCM encoder wrote past the end of a device buffer: guard bytes overwritten");
+        }
+        d_src = prog->d_host_pcm.p;
+    }
+    if (n_bytes >= kStagedMinBytes && !is_pinned_host(h_out)) {
+        HIP_TRY(ctx, download_staged(prog, h_out, d_src, n_bytes));
+    } else {  // pinned destination: one DMA at link speed; small output: not worth more
+        HIP_TRY(ctx, hipMemcpyAsync(h_out, d_src, n_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return DUSP_OK;
+}
+
 static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, void *h_out,
                        bool interleaved, int pcm_format, int normalise, float *h_peaks) {
     if (!prog) return DUSP_ERR_ARG;
@@ -1643,35 +1703,133 @@ static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples,
         d_frames = prog->d_host_frames.p;
         if (int rc = dusp_interleave_device(ctx, d_out, n_instances, n_ch, n_samples, d_frames, ctx->stream)) return rc;
     }
-    const void *d_src = d_frames ? d_frames : d_out;
-    size_t n_bytes = n_out * sizeof(float);
-    if (pcm_format) {  // peak, gain, quantisation and interleave on the device: 2 or 3 bytes a sample cross the link
-        const float *d_peaks = nullptr;
-        if (normalise || h_peaks) {
-            HIP_TRY(ctx, prog->d_host_peaks.ensure(n_instances));
-            d_peaks = prog->d_host_peaks.p;
-            if (int rc = dusp_peak_device(ctx, d_out, n_instances, n_ch, n_samples, prog->d_host_peaks.p, ctx->stream)) return rc;
-            if (h_peaks) HIP_TRY(ctx, hipMemcpyAsync(h_peaks, d_peaks, n_instances * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        n_bytes = n_out * (size_t)dusp::pcm_bytes_per_sample(pcm_format);
-        HIP_TRY(ctx, prog->d_host_pcm.ensure(n_bytes));
-        if (int rc = dusp_encode_device(ctx, d_out, n_instances, n_ch, n_samples, pcm_format, normalise, d_peaks, prog->d_host_pcm.p, ctx->stream)) return rc;
-        if (g_guard_bytes) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact())
-                CTX_FAIL(ctx, DUSP_ERR_HIP, "render: the PCM encoder wrote past the end of a device buffer: guard bytes overwritten");
-        }
-        d_src = prog->d_host_pcm.p;
-    }
-    if (n_bytes >= kStagedMinBytes && !is_pinned_host(h_out)) {
-        HIP_TRY(ctx, download_staged(prog, h_out, d_src, n_bytes));
-    } else {  // pinned destination: one DMA at link speed; small output: not worth more
-        HIP_TRY(ctx, hipMemcpyAsync(h_out, d_src, n_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (int rc = deliver_host(prog, d_out, d_frames, n_instances, n_ch, n_samples, pcm_format, normalise, h_peaks, h_out)) return rc;
     if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: where a host render's time goes)
         fprintf(stderr, "[dusp host render] output buffer %.0f us, render enqueued (workspaces, constants, launches) %.0f us, download + wait %.0f us\n", us_alloc, us_enqueued - us_alloc,
                 since() - us_enqueued);
+    return DUSP_OK;
+    });
+}
+
+constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)
+
+int dusp_mix_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples, const float *d_gains, const float *d_init,
+                    int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    return guarded(ctx->err, "dusp_mix_device", [&]() -> int {
+    if (!d_planar || !d_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_mix_device: NULL buffer");
+    if (n_channels < 1 || n_channels > 64 || n_instances < 1 || n_instances > (1u << 24) || n_samples < 1 || n_samples > (1ull << 31))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_mix_device: need 1..64 channels, 1..2^24 instances and 1..2^31 samples");
+    if (n_channels * n_samples > kMixRowMax)  // (one lane per float of the row at the most: the grid's 2^32 threads)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_mix_device: channels x samples must not exceed 2^31: mix such a batch channel by channel or in windows of the timeline");
+    if ((((uintptr_t)d_planar | (uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_mix_device: the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dusp::launch_mix(d_planar, d_gains, d_init, d_out, (uint64_t)n_channels * n_samples, (uint32_t)n_instances, raw != 0, ctx->n_cus,
+                                  ctx->knobs.mix_width, ctx->knobs.mix_depth, stream_ ? (hipStream_t)stream_ : ctx->stream));
+    return DUSP_OK;
+    });
+}
+
+// The default tile of dusp_render_host_mix (tile_instances == 0).  The engines that take any voice are parallel over INSTANCES: the
+// wave engine and its compiled kernels run one wavefront per instance and fill the chip at 32 instances a CU, and
+// below that a tile's render costs about what the whole batch's would, since one instance's dependent steps are the floor.  So the
+// default is that many instances, cut down only where their PCM would not fit kMixTileBytes or half of the device's free memory.
+// DUSP_MIX_TILE_MB=n in the environment of dusp_ctx_create makes it what fits n MiB instead (tools/mix_bench.py sweeps that).
+constexpr size_t kMixTileBytes = (size_t)16 << 30;
+constexpr size_t kMixTileRowsPerCu = 32;
+
+int dusp_render_host_mix(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_gains, size_t tile_instances,
+                         int format, int normalise, void *h_out, float *h_peak) {
+    if (!prog) return DUSP_ERR_ARG;
+    dusp_ctx *ctx = prog->ctx;
+    return guarded(ctx->err, "dusp_render_host_mix", [&]() -> int {
+    if (!h_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: h_out is NULL");
+    if (n_instances < 1 || n_instances > (1u << 24) || n_samples < 1 || n_samples > (1ull << 31))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: n_instances must be in [1, 2^24] and n_samples in [1, 2^31]");
+    if (format != 0 && format != DUSP_PCM_S16 && format != DUSP_PCM_S24 && format != DUSP_PCM_F32)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: format must be 0 (planar f32), DUSP_PCM_S16 (1), DUSP_PCM_S24 (2) or DUSP_PCM_F32 (3)");
+    if (normalise != DUSP_NORMALISE_NONE && normalise != DUSP_NORMALISE_CLIP && normalise != DUSP_NORMALISE_FULL)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
+    if (prog->P.g.n_inputs > 0)
+        CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_mix: the program reads host-generated input streams; render it with dusp_render_host_inputs and mix on the host");
+    if (prog->resumable) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_mix: a resumable program (DUSP_ENGINE_RESUMABLE) is not mixed: its tiles would continue one another");
+    const size_t n_ch = prog->P.out_bufs.size(), n_params = prog->P.g.n_params;
+    if (n_ch < 1 || n_ch > 64) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_mix: the outlet must have 1..64 channels");
+    const size_t row = n_ch * n_samples;
+    if (row > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: channels x samples must not exceed 2^31: mix such a render in windows of the timeline");
+    if (n_params && !h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: program has parameters but h_params is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t tile = tile_instances;
+    if (tile == 0 && ctx->knobs.mix_tile_mb > 0) tile = ((size_t)ctx->knobs.mix_tile_mb << 20) / (row * sizeof(float));
+    else if (tile == 0) {
+        size_t free_bytes = 0, total_bytes = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
+        // (what the program's staging already holds is not free, but is this call's to use)
+        const size_t budget = std::min(kMixTileBytes, (free_bytes + prog->d_host_out.cap * sizeof(float)) / 2);
+        tile = std::min((size_t)ctx->n_cus * kMixTileRowsPerCu, budget / (row * sizeof(float)));
+    }
+    tile = std::min(std::max<size_t>(1, tile), n_instances);
+    // the tile's PCM, its parameter columns and gains, and the running sums: all that lives on the device, whatever n_instances is
+    HIP_TRY(ctx, prog->d_host_out.ensure(tile * row));
+    HIP_TRY(ctx, prog->d_mix.ensure(row));
+    if (n_params) HIP_TRY(ctx, prog->d_host_par.ensure(n_params * tile));
+    if (h_gains) HIP_TRY(ctx, prog->d_mix_gains.ensure(tile));
+    // Tiling must not change a bit.  What a render decides from the batch and that changes bits is, while the tiles render, decided from the
+    // WHOLE batch: a Filter with a per-instance cutoff runs as a scan or as a recurrence — not the same bits — by the range of its column
+    // (mix_range), and so does every scan-eligible Filter by whether the render is cut into warming segments, which the instance count
+    // decides (mix_n_inst, which also makes every tile wait for its compiled kernel).  Per-instance Delays are classified per tile: their
+    // regimes differ in speed only.
+    std::vector<float> cols;  // (declared in front of the guard: it outlives the guard's wait for the stream)
+    struct WholeBatch {
+        dusp_program *prog;
+        hipStream_t stream;
+        bool staged = false;  // host vectors of this call may still be on their way to the device
+        ~WholeBatch() {
+            if (staged) (void)hipStreamSynchronize(stream);  // (a return in the middle of the tiles)
+            prog->mix_range.clear();
+            prog->mix_n_inst = 0;
+            prog->mixed = true;  // (whichever tile was the last to render, the whole batch it was not)
+        }
+    } whole{prog, ctx->stream};
+    prog->mix_n_inst = (uint32_t)n_instances;
+    prog->mix_range.assign(3 * n_params, 0u);
+    for (size_t p = 0; p < n_params; p++)
+        for (size_t i = 0; i < n_instances; i++) {
+            const float v = h_params[p * n_instances + i];
+            if (!(v > 0.f && v <= 3.0e38f)) prog->mix_range[3 * p + 2] = 1u;
+            else {
+                unsigned b;
+                std::memcpy(&b, &v, 4);  // (positive floats order like their bits)
+                prog->mix_range[3 * p] = std::max(prog->mix_range[3 * p], 0x7fffffffu - b);
+                prog->mix_range[3 * p + 1] = std::max(prog->mix_range[3 * p + 1], b);
+            }
+        }
+    // every tile's columns of the slot-major table [n_params][n_instances], tile after tile, gathered once: nothing on the host is
+    // reused from one tile to the next, so the tiles queue up on the stream without the host waiting for any of them
+    cols.resize(n_params * n_instances);
+    for (size_t lo = 0; lo < n_instances && n_params; lo += tile) {
+        const size_t n = std::min(tile, n_instances - lo);
+        for (size_t p = 0; p < n_params; p++) std::memcpy(&cols[n_params * lo + p * n], h_params + p * n_instances + lo, n * sizeof(float));
+    }
+    for (size_t lo = 0; lo < n_instances; lo += tile) {
+        const size_t n = std::min(tile, n_instances - lo);
+        const bool last = lo + n == n_instances;
+        if (n_params) {
+            HIP_TRY(ctx, hipMemcpyAsync(prog->d_host_par.p, &cols[n_params * lo], n_params * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            whole.staged = true;
+        }
+        if (h_gains) HIP_TRY(ctx, hipMemcpyAsync(prog->d_mix_gains.p, h_gains + lo, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = render_device_unguarded(prog, n, n_samples, n_params ? prog->d_host_par.p : nullptr, nullptr, prog->d_host_out.p, ctx->stream)) return rc;
+        if (int rc = check_guards(prog, ctx->stream)) return rc;
+        if (int rc = dusp_mix_device(ctx, prog->d_host_out.p, n, n_ch, n_samples, h_gains ? prog->d_mix_gains.p : nullptr, lo > 0 ? prog->d_mix.p : nullptr, !last,
+                                     prog->d_mix.p, ctx->stream))
+            return rc;
+    }
+    if (int rc = deliver_host(prog, prog->d_mix.p, nullptr, 1, n_ch, n_samples, format, normalise, h_peak, h_out)) return rc;
+    whole.staged = false;  // (the delivery has waited for the stream)
+    if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact()))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, "dusp_render_host_mix: the mix kernel wrote past the end of a device buffer: guard bytes overwritten");
     return DUSP_OK;
     });
 }
@@ -1729,6 +1887,7 @@ int dusp_state_download(dusp_program *prog, size_t instance, size_t unit, double
     dusp_ctx *ctx = prog->ctx;
     return guarded(ctx->err, "dusp_state_download", [&]() -> int {
     if (!prog->rendered) CTX_FAIL(ctx, DUSP_ERR_STATE, "dusp_state_download: nothing has been rendered yet");
+    if (prog->mixed) CTX_FAIL(ctx, DUSP_ERR_STATE, "dusp_state_download: the last render was a mix (dusp_render_host_mix): unit state describes its last tile only");
     const dusp::Graph &g = prog->P.g;
     if (unit >= g.units.size() || instance >= prog->last_n_inst || !out)
         CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_state_download: unit / instance out of range");

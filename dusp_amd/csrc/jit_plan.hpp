@@ -19,6 +19,7 @@ struct JitBatch {
     bool handoff = false;     // ... namely the chunk engine's first chunks of this render (Program::warm_ops)
     bool inputs = false;      // the circuit reads host-generated signals
     bool voice_loop = false;  // the circuit's voices run in a loop (jit_find_voices said so, once per program)
+    uint32_t whole_n_inst = 0;  // a tile of a mix (dusp_render_host_mix): the instances of the whole batch, which decide whether segments warm up
 };
 
 struct JitPlan {
@@ -65,7 +66,11 @@ inline void jit_plan_segments(JitPlan &plan, const JitSite &site, const JitBatch
     // its Filters merge with the sequential trajectory on the way (checked after the launch), and only its own chunks are stored
     // (a Filter stage's serving wave runs 32 recurrences side by side at the price of one: the chip is full at 32 rows a CU, so up to a quarter of that many
     // instances are still worth cutting)
-    if ((uint64_t)n_inst * 4 <= (uint64_t)site.n_cus * 32 && !batch.persistent && !batch.resume && !batch.handoff && !batch.inputs && !knobs.jit_force_waves && knobs.filter_warm != 0 && knobs.wave_segments != 0 &&
+    // (warming segments keep the Filter stage — jit_site_options — where the unsplit render may scan: not the same bits.  The tiles of a mix
+    // must all decide alike, and as one render of the whole batch would: by ITS instance count.  Few enough there means few enough in every
+    // tile, and with fewer instances the segment count below only grows: every tile of such a batch warms up as well, or none does.)
+    const uint32_t n_decide = batch.whole_n_inst ? batch.whole_n_inst : n_inst;
+    if ((uint64_t)n_decide * 4 <= (uint64_t)site.n_cus * 32 && !batch.persistent && !batch.resume && !batch.handoff && !batch.inputs && !knobs.jit_force_waves && knobs.filter_warm != 0 && knobs.wave_segments != 0 &&
         knobs.wave_segments != 1) {
         const uint32_t warm_chunks = jit_warm_chunks(P, wave);
         if (warm_chunks) {

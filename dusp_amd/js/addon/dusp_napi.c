@@ -374,7 +374,11 @@ typedef struct {
     int interleaved; /* frames [instance][sample][channel] instead of planar [instance][channel][sample] */
     int pcm_format, normalise; /* renderPcm: DUSP_PCM_* (0: a plain render) and DUSP_NORMALISE_* */
     size_t n_bytes;            /* size of out: n_floats f32, or the encoded frames */
-    float *peaks;              /* renderPcm: every instance's peak */
+    float *peaks;              /* renderPcm: every instance's peak; renderMix: the mix's */
+    size_t n_peaks;
+    int mix;                   /* renderMix: dusp_render_host_mix — pcm_format 0 delivers the mix as planar f32 */
+    float *gains;              /* renderMix: a factor per instance, or NULL */
+    size_t tile_instances;     /* renderMix: instances per tile (0: the library's default) */
     int rc;
     char err[512];
 } render_job;
@@ -388,7 +392,9 @@ static void render_execute(napi_env env, void *data) {
         j->rc = DUSP_ERR_STATE;
         snprintf(j->err, sizeof j->err, "dusp-hip: render: the program has been destroyed");
     } else {
-        if (j->pcm_format)
+        if (j->mix)
+            j->rc = dusp_render_host_mix(prog, j->n_instances, j->n_samples, j->params, j->gains, j->tile_instances, j->pcm_format, j->normalise, j->out, j->peaks);
+        else if (j->pcm_format)
             j->rc = dusp_render_host_pcm(prog, j->n_instances, j->n_samples, j->params, j->inputs, j->pcm_format, j->normalise, j->out, j->peaks);
         else if (j->inputs) j->rc = dusp_render_host_inputs(prog, j->n_instances, j->n_samples, j->params, j->inputs, j->out, j->interleaved);
         else
@@ -397,6 +403,13 @@ static void render_execute(napi_env env, void *data) {
         if (j->rc != DUSP_OK) snprintf(j->err, sizeof j->err, "dusp-hip: %s", dusp_last_error(j->pb->cb->ctx));
     }
     pthread_mutex_unlock(&j->pb->cb->lock);
+}
+static void job_free(render_job *j) { /* the job and the host copies it owns (not `out`: release_out) */
+    free(j->params);
+    free(j->inputs);
+    free(j->gains);
+    free(j->peaks);
+    free(j);
 }
 static void free_pcm(napi_env env, void *data, void *hint) {
     (void)env; (void)hint;
@@ -439,11 +452,11 @@ static void render_complete(napi_env env, napi_status status, void *data) {
     if (j->rc == DUSP_OK && j->pcm_format) { /* { data: Buffer over the encoded frames, peaks: Float32Array } */
         napi_value data, peaks_ab, peaks;
         void *peaks_mem;
-        if (napi_create_arraybuffer(env, j->n_instances * sizeof(float), &peaks_mem, &peaks_ab) == napi_ok &&
-            napi_create_typedarray(env, napi_float32_array, j->n_instances, peaks_ab, 0, &peaks) == napi_ok && napi_create_object(env, &result) == napi_ok &&
+        if (napi_create_arraybuffer(env, j->n_peaks * sizeof(float), &peaks_mem, &peaks_ab) == napi_ok &&
+            napi_create_typedarray(env, napi_float32_array, j->n_peaks, peaks_ab, 0, &peaks) == napi_ok && napi_create_object(env, &result) == napi_ok &&
             napi_create_external_buffer(env, j->n_bytes, j->out, j->out_pinned ? free_pinned_pcm : free_pcm, j->out_pinned ? (void *)j->pb->cb : NULL, &data) == napi_ok) {
             j->out = NULL; /* owned by the Buffer now */
-            memcpy(peaks_mem, j->peaks, j->n_instances * sizeof(float));
+            memcpy(peaks_mem, j->peaks, j->n_peaks * sizeof(float));
             napi_set_named_property(env, result, "data", data);
             napi_set_named_property(env, result, "peaks", peaks);
             napi_resolve_deferred(env, j->deferred, result);
@@ -470,35 +483,46 @@ static void render_complete(napi_env env, napi_status status, void *data) {
     if (--j->pb->in_flight == 0 && j->pb->destroy_deferred) prog_destroy_now(j->pb); /* programDestroy came while this render ran */
     napi_delete_reference(env, j->prog_ref);
     napi_delete_async_work(env, j->work);
-    free(j->params);
-    free(j->inputs);
-    free(j->peaks);
-    free(j);
+    job_free(j);
 }
+
+enum { CALL_RENDER = 0, CALL_PCM = 1, CALL_MIX = 2 };
 
 /* render(prog, nInstances, nSamples, params | null [, interleaved [, inputs]]) -> Promise<Float32Array>
  * renderPcm(prog, nInstances, nSamples, params | null, format, normalise [, inputs]) -> Promise<{ data: Buffer, peaks: Float32Array }>
- *   (dusp_render_host_pcm: peak, gain, quantisation and interleave on the device; format DUSP_PCM_*, normalise DUSP_NORMALISE_*) */
-static napi_value render_call(napi_env env, napi_callback_info info, int pcm) {
-    napi_value argv[7];
-    size_t argc = 7;
-    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < (pcm ? 6u : 4u)) {
+ *   (dusp_render_host_pcm: peak, gain, quantisation and interleave on the device; format DUSP_PCM_*, normalise DUSP_NORMALISE_*)
+ * renderMix(prog, nInstances, nSamples, params | null, gains | null, tileInstances, format, normalise)
+ *   -> Promise<Float32Array [channel][nSamples]> (format 0) or Promise<{ data: Buffer, peaks: Float32Array(1) }> (format DUSP_PCM_*)
+ *   (dusp_render_host_mix: the instances rendered tile by tile and summed on the device in Sum.many's chain order) */
+static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
+    napi_value argv[8];
+    size_t argc = 8;
+    const int pcm = kind != CALL_RENDER; /* format and normalise are arguments */
+    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < (kind == CALL_MIX ? 8u : kind == CALL_PCM ? 6u : 4u)) {
         throw_string(env, "dusp-hip: wrong number of arguments");
         return NULL;
     }
-    const size_t inputs_at = pcm ? 6 : 5;
+    const size_t inputs_at = kind == CALL_MIX ? 8 : kind == CALL_PCM ? 6 : 5; /* (a mix takes no input streams) */
+    const size_t format_at = kind == CALL_MIX ? 6 : 4;
     bool interleaved = false;
-    double format = 0, normalise = 0;
-    if (!pcm && argc >= 5) napi_get_value_bool(env, argv[4], &interleaved);
+    double format = 0, normalise = 0, tile = 0;
+    if (kind == CALL_RENDER && argc >= 5) napi_get_value_bool(env, argv[4], &interleaved);
     if (pcm) {
-        if (napi_get_value_double(env, argv[4], &format) != napi_ok || !(format == DUSP_PCM_S16 || format == DUSP_PCM_S24 || format == DUSP_PCM_F32)) {
-            throw_string(env, "dusp-hip: renderPcm: format must be 1 (s16), 2 (s24) or 3 (f32)");
+        if (napi_get_value_double(env, argv[format_at], &format) != napi_ok ||
+            !(format == DUSP_PCM_S16 || format == DUSP_PCM_S24 || format == DUSP_PCM_F32 || (kind == CALL_MIX && format == 0))) {
+            throw_string(env, kind == CALL_MIX ? "dusp-hip: renderMix: format must be 0 (planar f32), 1 (s16), 2 (s24) or 3 (f32)"
+                                               : "dusp-hip: renderPcm: format must be 1 (s16), 2 (s24) or 3 (f32)");
             return NULL;
         }
-        if (napi_get_value_double(env, argv[5], &normalise) != napi_ok || !(normalise == 0 || normalise == 1 || normalise == 2)) {
-            throw_string(env, "dusp-hip: renderPcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
+        if (napi_get_value_double(env, argv[format_at + 1], &normalise) != napi_ok || !(normalise == 0 || normalise == 1 || normalise == 2)) {
+            throw_string(env, kind == CALL_MIX ? "dusp-hip: renderMix: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)"
+                                               : "dusp-hip: renderPcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
             return NULL;
         }
+    }
+    if (kind == CALL_MIX && (napi_get_value_double(env, argv[5], &tile) != napi_ok || !(tile >= 0 && tile <= 16777216.0 && tile == (double)(size_t)tile))) {
+        throw_string(env, "dusp-hip: renderMix: tileInstances must be 0 (the default tile) or a whole number of instances");
+        return NULL;
     }
     prog_box *pb = as_prog(env, argv[0]);
     if (!pb) return NULL;
@@ -519,13 +543,16 @@ static napi_value render_call(napi_env env, napi_callback_info info, int pcm) {
     j->pb = pb;
     j->n_instances = (size_t)n_inst;
     j->n_samples = (size_t)n_samples;
-    j->n_floats = j->n_instances * pi.n_out_channels * j->n_samples;
+    j->mix = kind == CALL_MIX;
+    j->tile_instances = (size_t)tile;
+    j->n_floats = (j->mix ? 1 : j->n_instances) * pi.n_out_channels * j->n_samples; /* (a mix is one instance's worth of samples) */
     j->interleaved = interleaved ? 1 : 0;
     j->pcm_format = (int)format;
     j->normalise = (int)normalise;
-    j->n_bytes = j->n_floats * (size_t)(!pcm || j->pcm_format == DUSP_PCM_F32 ? 4 : j->pcm_format == DUSP_PCM_S16 ? 2 : 3);
-    if (pcm && !(j->peaks = (float *)malloc(j->n_instances * sizeof(float)))) {
-        free(j);
+    j->n_bytes = j->n_floats * (size_t)(!j->pcm_format || j->pcm_format == DUSP_PCM_F32 ? 4 : j->pcm_format == DUSP_PCM_S16 ? 2 : 3);
+    j->n_peaks = j->mix ? 1 : j->n_instances;
+    if (j->pcm_format && !(j->peaks = (float *)malloc(j->n_peaks * sizeof(float)))) {
+        job_free(j);
         throw_string(env, "dusp-hip: render: out of host memory");
         return NULL;
     }
@@ -535,49 +562,57 @@ static napi_value render_call(napi_env env, napi_callback_info info, int pcm) {
         void *data;
         size_t len;
         if (!typed_array(env, argv[3], napi_float32_array, &data, &len) || len != (size_t)pi.n_params * j->n_instances) {
-            free(j->peaks);
-            free(j);
+            job_free(j);
             throw_string(env, "dusp-hip: render: params must be a Float32Array of nParams * nInstances values");
             return NULL;
         }
         j->params = (float *)malloc(len * sizeof(float) + 1);
         if (!j->params) {
-            free(j->peaks);
-            free(j);
+            job_free(j);
             throw_string(env, "dusp-hip: render: out of host memory for the parameter table");
             return NULL;
         }
         memcpy(j->params, data, len * sizeof(float));
     } else if (pi.n_params) {
-        free(j->peaks);
-        free(j);
+        job_free(j);
         throw_string(env, "dusp-hip: render: this program needs a parameter table");
         return NULL;
+    }
+    if (kind == CALL_MIX) napi_typeof(env, argv[4], &vt);
+    if (kind == CALL_MIX && vt != napi_null && vt != napi_undefined) { /* gains: Float32Array of nInstances values */
+        void *data;
+        size_t len;
+        if (!typed_array(env, argv[4], napi_float32_array, &data, &len) || len != j->n_instances) {
+            job_free(j);
+            throw_string(env, "dusp-hip: renderMix: gains must be a Float32Array of nInstances values");
+            return NULL;
+        }
+        j->gains = (float *)malloc(len * sizeof(float));
+        if (!j->gains) {
+            job_free(j);
+            throw_string(env, "dusp-hip: render: out of host memory for the gains");
+            return NULL;
+        }
+        memcpy(j->gains, data, len * sizeof(float));
     }
     if (argc > inputs_at) napi_typeof(env, argv[inputs_at], &vt);
     if (argc > inputs_at && vt != napi_null && vt != napi_undefined) { /* inputs: Float32Array of nInputs * nInstances * nSamples values */
         void *data;
         size_t len;
         if (!typed_array(env, argv[inputs_at], napi_float32_array, &data, &len) || len != (size_t)pi.n_inputs * j->n_instances * j->n_samples || !len) {
-            free(j->params);
-            free(j->peaks);
-            free(j);
+            job_free(j);
             throw_string(env, "dusp-hip: render: inputs must be a Float32Array of nInputs * nInstances * nSamples values");
             return NULL;
         }
         j->inputs = (float *)malloc(len * sizeof(float) + 1);
         if (!j->inputs) {
-            free(j->params);
-            free(j->peaks);
-            free(j);
+            job_free(j);
             throw_string(env, "dusp-hip: render: out of host memory for the input streams");
             return NULL;
         }
         memcpy(j->inputs, data, len * sizeof(float));
     } else if (pi.n_inputs) {
-        free(j->params);
-        free(j->peaks);
-        free(j);
+        job_free(j);
         throw_string(env, "dusp-hip: render: this program reads host-generated input streams");
         return NULL;
     }
@@ -598,10 +633,7 @@ static napi_value render_call(napi_env env, napi_callback_info info, int pcm) {
     }
     if (!j->out) j->out = (float *)malloc(j->n_bytes + 1);
     if (!j->out) {
-        free(j->inputs);
-        free(j->params);
-        free(j->peaks);
-        free(j);
+        job_free(j);
         throw_string(env, "dusp-hip: render: out of host memory for the PCM buffer");
         return NULL;
     }
@@ -610,10 +642,7 @@ static napi_value render_call(napi_env env, napi_callback_info info, int pcm) {
         napi_create_string_utf8(env, "dusp-hip render", NAPI_AUTO_LENGTH, &name) != napi_ok ||
         napi_create_async_work(env, NULL, name, render_execute, render_complete, j, &j->work) != napi_ok) {
         release_out(j);
-        free(j->inputs);
-        free(j->params);
-        free(j->peaks);
-        free(j);
+        job_free(j);
         throw_string(env, "dusp-hip: render: could not queue the render");
         return NULL;
     }
@@ -621,17 +650,15 @@ static napi_value render_call(napi_env env, napi_callback_info info, int pcm) {
     if (napi_queue_async_work(env, j->work) != napi_ok) {
         pb->in_flight--;
         release_out(j);
-        free(j->inputs);
-        free(j->params);
-        free(j->peaks);
-        free(j);
+        job_free(j);
         throw_string(env, "dusp-hip: render: could not queue the render");
         return NULL;
     }
     return promise;
 }
-static napi_value fn_render(napi_env env, napi_callback_info info) { return render_call(env, info, 0); }
-static napi_value fn_render_pcm(napi_env env, napi_callback_info info) { return render_call(env, info, 1); }
+static napi_value fn_render(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_RENDER); }
+static napi_value fn_render_pcm(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_PCM); }
+static napi_value fn_render_mix(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_MIX); }
 
 static napi_value init(napi_env env, napi_value exports) {
     static const struct {
@@ -642,7 +669,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ctxDestroy", fn_ctx_destroy},   {"tableUpload", fn_table_upload},   {"programBuild", fn_program_build},
         {"programDestroy", fn_program_destroy}, {"programInfo", fn_program_info}, {"stateDownload", fn_state_download},
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
-        {"renderPcm", fn_render_pcm},
+        {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

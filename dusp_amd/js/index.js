@@ -13,6 +13,9 @@ module.exports = {
   renderMany: renderChannelData.renderMany,
   renderPcm: renderChannelData.renderPcm,
   renderWav: renderChannelData.renderWav,
+  renderMix: renderChannelData.renderMix,
+  renderMixPcm: renderChannelData.renderMixPcm,
+  renderMixWav: renderChannelData.renderMixWav,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

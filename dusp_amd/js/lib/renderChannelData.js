@@ -300,6 +300,17 @@ async function renderWav(outlet, duration = 1, opts = {}) {
   return encodeWav(await renderPcm(outlet, duration, opts))
 }
 
+/* The circuits of a batch render as ONE program: extracted (scheduled events are refused there) and unified.  One launch for all
+ * circuits: nothing ticks on the host in between, so units that need that are refused, not ignored. */
+function unifyBatch(outlets, who) {
+  const extractions = outlets.map((o) => extract(o))
+  for (const ex of extractions)
+    for (const u of ex.circuit.units)
+      if ((u.isHostSignal || (UNITS[u.constructor.name] && UNITS[u.constructor.name].hostTick)) && !deviceRetrigger(u, ex.circuit.units))
+        throw 'dusp-hip: ' + who + ' does not take circuits with host-ticked units (' + u.label + '): render them one by one'
+  return unify(extractions)
+}
+
 /* N structurally identical circuits (voices, a parameter sweep) as ONE GPU program per device:
  * resolves to result[instance][channel] = Float32Array(duration * sampleRate).
  *
@@ -310,13 +321,7 @@ async function renderWav(outlet, duration = 1, opts = {}) {
  * The results come back in instance order whatever order the devices finish in.  A render rejects as a whole with the first
  * failing shard's string. */
 async function renderMany(outlets, duration = 1, { engine = 0, devices } = {}) {
-  const extractions = outlets.map((o) => extract(o))
-  // one launch for all circuits: nothing ticks on the host in between, so units that need that are refused, not ignored
-  for (const ex of extractions)
-    for (const u of ex.circuit.units)
-      if ((u.isHostSignal || (UNITS[u.constructor.name] && UNITS[u.constructor.name].hostTick)) && !deviceRetrigger(u, ex.circuit.units))
-        throw 'dusp-hip: renderMany does not take circuits with host-ticked units (' + u.label + '): render them one by one'
-  const uni = unify(extractions)
+  const uni = unifyBatch(outlets, 'renderMany')
   const nSamples = sampleCount(duration, uni.sampleRate)
   if (nSamples === 0) return outlets.map(() => [])
   const n = native()
@@ -363,6 +368,56 @@ async function renderMany(outlets, duration = 1, { engine = 0, devices } = {}) {
   }
 }
 
+/* The MIX of N structurally identical circuits — what renderChannelData(Sum.many(outlets), duration) computes: the reference's
+ * left-deep chain ((v0 + v1) + v2) + ..., one f32 rounding per add (Sum.js:18-29), with `gains` the chain over Multiply(outlet, g_i) —
+ * rendered as ONE program, tile by tile, and summed ON THE DEVICE in that order (dusp_render_host_mix).  Device memory is bounded
+ * by the tile (tileInstances; 0: the library's default), not by N, and one voice's worth of samples is downloaded, where renderMany
+ * downloads every voice.  One device.  A voice sample that is NaN drops that voice out of the sample (the reference's Sum would zero
+ * the mix sample there).  Resolves to channelData like renderChannelData; circuits with scheduled events or host-ticked units are
+ * refused as renderMany refuses them. */
+async function mixCall(who, outlets, duration, { gains, engine = 0, tileInstances = 0 }, format, normalise) {
+  const uni = unifyBatch(outlets, who)
+  const nSamples = sampleCount(duration, uni.sampleRate)
+  let g = null
+  if (gains !== undefined && gains !== null) {
+    g = gains instanceof Float32Array ? gains : Float32Array.from(gains)
+    if (g.length !== uni.nInstances) throw 'dusp-hip: ' + who + ': gains must hold one value per outlet'
+  }
+  if (!Number.isInteger(tileInstances) || tileInstances < 0) throw 'dusp-hip: ' + who + ': tileInstances must be 0 (the default tile) or a whole number of instances'
+  const n = native()
+  const prog = n.programBuild(contextFor(uni.sampleRate), uni.words, engine)
+  try {
+    const nChannels = n.programInfo(prog).nOutChannels
+    if (nSamples === 0) return { nSamples, nChannels, sampleRate: uni.sampleRate, result: null }
+    const result = await n.renderMix(prog, uni.nInstances, nSamples, uni.nParams ? uni.params : null, g, tileInstances, format, normalise)
+    return { nSamples, nChannels, sampleRate: uni.sampleRate, result }
+  } finally {
+    n.programDestroy(prog)
+  }
+}
+
+async function renderMix(outlets, duration = 1, opts = {}) {
+  const { nSamples, nChannels, sampleRate, result } = await mixCall('renderMix', outlets, duration, opts, 0, 0)
+  const channelData = []
+  channelData.sampleRate = sampleRate
+  if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
+  return channelData
+}
+
+/* renderMix, delivering what renderPcm delivers: the mix's frames, encoded on the device, and the mix's peak. */
+async function renderMixPcm(outlets, duration = 1, opts = {}) {
+  const { bitDepth = 16, normalise = 0 } = opts
+  if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderMixPcm: bitDepth must be 16, 24 or 32'
+  if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderMixPcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
+  const { nChannels, sampleRate, result } = await mixCall('renderMixPcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise)
+  if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
+  return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
+}
+
+async function renderMixWav(outlets, duration = 1, opts = {}) {
+  return encodeWav(await renderMixPcm(outlets, duration, opts))
+}
+
 /* A flat descriptor (what lib/extract.js produces — from this package's graph classes or from the reference's own objects,
  * patches included: their units reach the extractor as they are) rendered as it stands: no host objects, hence no events,
  * no host-ticked units, no state write-back.  Resolves to channelData like renderChannelData. */
@@ -388,6 +443,9 @@ module.exports.renderDescriptor = renderDescriptor
 module.exports.renderMany = renderMany
 module.exports.renderPcm = renderPcm
 module.exports.renderWav = renderWav
+module.exports.renderMix = renderMix
+module.exports.renderMixPcm = renderMixPcm
+module.exports.renderMixWav = renderMixWav
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

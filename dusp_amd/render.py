@@ -148,6 +148,52 @@ def render_many(outlets, duration=1, engine=runtime.ENGINE_AUTO, device=-1):
         prog.close()
 
 
+def _mix_program(outlets, duration, engine, device):
+    uni = descriptor.unify([descriptor.extract(o) for o in outlets])
+    return uni, _n_samples(duration, uni.sample_rate), context(uni.sample_rate, device).build(uni.words, engine)
+
+
+def render_mix(outlets, duration=1, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0):
+    """The mix of N isomorphic circuits — what `renderChannelData(Sum.many(outlets), duration)` computes (Sum.js:18-29: a left-deep chain,
+    one f32 rounding per add), with `gains` what Sum.many of Multiply(outlet, g_i) does — rendered as ONE program in tiles and summed on the
+    device in that order (Program.render_mix): memory is bounded by the tile, not by N, and one voice's worth of samples is downloaded.
+    A voice sample that is NaN drops that voice out of the sample (the reference's Sum would zero the whole mix sample there)."""
+    uni, n, prog = _mix_program(outlets, duration, engine, device)
+    result = ChannelData()
+    result.sampleRate = uni.sample_rate
+    try:
+        if n > 0:
+            result.extend(prog.render_mix(n, uni.n_instances, uni.params, gains, tile_instances))
+    finally:
+        prog.close()
+    return result
+
+
+def render_mix_pcm(outlets, duration=1, bit_depth=16, normalise=0, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0):
+    """render_mix, delivering what render_pcm delivers: the mix's frames encoded on the device, and its peak -> PcmData."""
+    if bit_depth not in _PCM_FORMAT:
+        raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
+    if normalise not in (0, 1, 2):
+        raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
+    uni, n, prog = _mix_program(outlets, duration, engine, device)
+    try:
+        if n == 0:
+            data, peak = wav.encode_frames(np.zeros((prog.n_out_channels, 0), dtype=np.float32), bit_depth, normalise)
+        else:
+            data, peak = prog.render_mix(n, uni.n_instances, uni.params, gains, tile_instances, _PCM_FORMAT[bit_depth], normalise)
+    finally:
+        prog.close()
+    return PcmData(data, bit_depth, uni.sample_rate, peak)
+
+
+def render_mix_wav(outlets, duration=1, bit_depth=16, normalise=0, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0):
+    """A complete RIFF/WAVE file (bytes) of the mix: render_mix_pcm plus the header (wav.encode_wav)."""
+    pcm = render_mix_pcm(outlets, duration, bit_depth, normalise, gains, engine, device, tile_instances)
+    if bit_depth == 32:
+        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
+    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+
+
 class PcmData:
     """Encoded frames of one render: `data` int16 [samples, channels] (bitDepth 16), uint8 [samples, channels, 3] (24) or float32
     [samples, channels] (32); `peak` is the render's max |x| before the gain.  wav.encode_wav(data, sampleRate, bitDepth) makes a file of it."""

@@ -24,7 +24,7 @@ EXPORTS = [
     "dusp_render_device", "dusp_render_host", "dusp_render_host_interleaved", "dusp_interleave_device", "dusp_state_download",
     "dusp_last_kernel_ms", "dusp_fill_device", "dusp_render_device_inputs", "dusp_render_host_inputs",
     "dusp_host_alloc", "dusp_host_free", "dusp_circuit_kernel_source", "dusp_jit_cache_dir", "dusp_render_chain_window", "dusp_device_count",
-    "dusp_peak_device", "dusp_encode_device", "dusp_render_host_pcm",
+    "dusp_peak_device", "dusp_encode_device", "dusp_render_host_pcm", "dusp_mix_device", "dusp_render_host_mix",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -86,6 +86,8 @@ def load():
     L.dusp_peak_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     L.dusp_encode_device.argtypes = [vp, vp, sz, sz, sz, ci, ci, vp, vp, vp]
     L.dusp_render_host_pcm.argtypes = [vp, sz, sz, vp, vp, ci, ci, vp, vp]
+    L.dusp_mix_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, ci, vp, vp]
+    L.dusp_render_host_mix.argtypes = [vp, sz, sz, vp, vp, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -227,6 +229,12 @@ class Context:
         gain its peak (d_peaks, from Context.peak) gives under `normalise` (include/dusp_hip.h: the sample contract)."""
         self._check(self._L.dusp_encode_device(self._h, d_planar, n_instances, n_channels, n_samples, _pcm_format(format), int(normalise), d_peaks, d_out, stream))
 
+    def mix(self, d_planar, n_instances, n_channels, n_samples, d_out, d_gains=None, d_init=None, raw=False, stream=None):
+        """Device pointers: planar f32 [instance][channel][sample] -> f32 [channel][sample], the instances' mix in Sum.many's chain order
+        (dusp_mix_device; dusp_amd/mix.py mix_chain is the contract): one f32 rounding per add, in index order, each instance first scaled by
+        its f32 gain (d_gains), the chain continued from d_init (which may be d_out); raw: a partial sum, NaN and -0 kept."""
+        self._check(self._L.dusp_mix_device(self._h, d_planar, n_instances, n_channels, n_samples, d_gains, d_init, int(bool(raw)), d_out, stream))
+
     def fill(self, d_ptr, n_floats, value=0.0, stream=None):
         self._check(self._L.dusp_fill_device(self._h, d_ptr, n_floats, value, stream))
 
@@ -327,6 +335,41 @@ class Program:
             ip = inputs.ctypes.data
         self.ctx._check(self._L.dusp_render_host_pcm(self._h, n_instances, n_samples, pp, ip, fmt, int(normalise), out.ctypes.data, peaks.ctypes.data))
         return out, peaks
+
+    def render_mix(self, n_samples, n_instances, params=None, gains=None, tile_instances=0, format=None, normalise=NORMALISE_NONE, pinned=None):
+        """Host round trip that delivers the MIX of the instances (dusp_render_host_mix): rendered tile by tile on the device and summed
+        there in Sum.many's chain order (bit for bit mix.mix_chain over what render() gives on the circuit's compiled kernel: a mix waits
+        for that kernel also where a first short render() under DUSP_WAVE_JIT=1 would not), so that device memory is bounded by the tile
+        and one instance's worth of samples is downloaded.  gains: float32 [n_instances], a factor per instance.  tile_instances: 0 lets the
+        library size the tile.  format None: float32 [n_out_channels, n_samples]; "s16" | "s24" | "f32": (data, peak) as render_pcm
+        delivers one instance — data [n_samples, n_out_channels(, 3)] — with the mix's peak as one float32."""
+        pp = gp = None
+        if self.n_params:
+            params = np.ascontiguousarray(params, dtype=np.float32)
+            if params.shape != (self.n_params, n_instances):
+                raise ValueError("params must have shape (n_params=%d, n_instances=%d)" % (self.n_params, n_instances))
+            pp = params.ctypes.data
+        if gains is not None:
+            gains = np.ascontiguousarray(gains, dtype=np.float32)
+            if gains.shape != (n_instances,):
+                raise ValueError("dusp-hip: gains must have shape (n_instances=%d,)" % n_instances)
+            gp = gains.ctypes.data
+        if int(tile_instances) < 0:
+            raise ValueError("dusp-hip: tile_instances must be 0 (the default tile) or at least 1")
+        if format is None:
+            out = self.ctx.host_empty((self.n_out_channels, n_samples), pinned)
+            self.ctx._check(self._L.dusp_render_host_mix(self._h, n_instances, n_samples, pp, gp, int(tile_instances), 0, 0, out.ctypes.data, None))
+            return out
+        fmt = _pcm_format(format)
+        if fmt not in PCM_BYTES:
+            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
+        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
+            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
+        shape = (n_samples, self.n_out_channels)
+        out = self.ctx.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
+        peak = np.empty(1, dtype=np.float32)
+        self.ctx._check(self._L.dusp_render_host_mix(self._h, n_instances, n_samples, pp, gp, int(tile_instances), fmt, int(normalise), out.ctypes.data, peak.ctypes.data))
+        return out, peak[0]
 
     def render_device(self, n_samples, n_instances, d_params, d_out, stream=None, d_inputs=None):
         """Asynchronous render between device pointers (ints), e.g. torch tensors' data_ptr()."""

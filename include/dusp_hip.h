@@ -262,6 +262,48 @@ int dusp_encode_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances,
 int dusp_render_host_pcm(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs,
                          int format, int normalise, void *h_out, float *h_peaks);
 
+/* The mix of a batch, on the device, in Sum.many's chain order (additions to ABI v7: DUSP_ABI_VERSION is unchanged, a binder
+ * detects them by symbol).  Replaces `Sum.many(voices)` as the thing that mixes rendered voices: the reference's left-deep
+ * chain ((v0 + v1) + v2) + ... of Sum units, each storing an f32 (src/components/Sum.js:18-29,33-44) — one f32 rounding per
+ * add, in index order.  For every channel c and sample t
+ *     acc = d_init ? d_init[c][t] : term(0);   acc = (float)(acc + term(i)) for the remaining instances, in index order
+ *     term(i) = d_gains ? (float)(x_i * g_i) : x_i        (a plain f32 product, as Multiply stores it, then a plain f32 add)
+ * Without d_init the chain starts from the first voice itself, not from 0 + v0.
+ *   d_planar       f32 [n_instances][n_channels][n_samples], as the render calls write it
+ *   d_gains        f32 [n_instances], or NULL
+ *   d_init, d_out  f32 [n_channels][n_samples]; d_init may be NULL, and may be d_out (in place); d_planar must not overlap d_out
+ *   raw            != 0: the sums as they stand (a partial sum that is continued: NaN and -0 kept); 0: `acc || 0`, NaN and -0
+ *                  leave as +0 (src/renderChannelData.js:44)
+ * Any 4-byte alignment and any n_samples; 16-byte accesses where the bases are 16-byte aligned and n_channels * n_samples is a
+ * multiple of 4, coalesced dword accesses elsewhere.  n_channels * n_samples must not exceed 2^31 (DUSP_ERR_ARG).  Device
+ * pointers, asynchronous.
+ * One divergence from the reference: a voice sample that is NaN travels through the reference's Sums and zeroes the MIX sample;
+ * a batch render maps NaN to +0 per voice on copy-out, so here only that voice drops out of the sample.  (The voices' -0 -> +0
+ * changes nothing after the final `|| 0`.)  The mix is the reference's wherever no voice sample is NaN. */
+int dusp_mix_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples,
+                    const float *d_gains, const float *d_init, int raw, float *d_out, void *stream);
+
+/* Render n_instances instances and deliver their mix: instances [lo, hi) are rendered tile by tile into a scratch buffer that
+ * lives with the program, and every tile continues the chain above into one [n_out_channels][n_samples] accumulator (raw for
+ * all tiles but the last).  Device memory is bounded by the tile, not by n_instances, and the tiling does not change a bit of
+ * the result: what a render decides from the batch and that changes bits — whether Filters run as scans, by the range of a
+ * per-instance cutoff column and by whether the instance count has the render cut into warming segments — is decided from the
+ * whole batch, and every tile runs on the circuit's compiled kernel, waiting for it where it is new (also under DUSP_WAVE_JIT=1,
+ * where a plain short render would not wait and run on the interpreter kernel): a tile renders as one render of all instances
+ * on the compiled kernel would.
+ *   h_params        f32 [n_params][n_instances] (slot-major), every tile takes its own columns; NULL without parameters
+ *   h_gains         f32 [n_instances], or NULL
+ *   tile_instances  instances per tile; 0: the batch that fills the chip, 32 instances per compute unit, or as many of them as
+ *                   fit 16 GiB and half of the device's free memory
+ *   format          0: h_out receives planar f32 [n_out_channels][n_samples]; DUSP_PCM_S16 / S24 / F32: the peak and encode
+ *                   kernels run over the mix as one instance and h_out receives frames, as from dusp_render_host_pcm
+ *   h_peak          one f32, may be NULL (only looked at for the PCM formats)
+ * Delivery paths of dusp_render_host.  DUSP_ERR_UNSUPPORTED for programs with INPUT streams and for resumable programs.  A fused
+ * sum-chain program is one instance like any other: n_instances = 1 is the voice itself.  Afterwards unit state describes the
+ * last tile only: dusp_state_download returns DUSP_ERR_STATE until the next plain render. */
+int dusp_render_host_mix(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_gains,
+                         size_t tile_instances, int format, int normalise, void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:
