@@ -1,0 +1,357 @@
+// abi_deliver.hip — the C ABI (include/dusp_hip.h): what happens to rendered PCM on the device (interleave, peak, encode, mix) and how
+// it reaches the host (dusp_render_host* and their delivery paths, dusp_render_host_mix).
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <thread>
+
+#include "abi_internal.hpp"
+#include "pcm_quant.hpp"
+#include "render_plan.hpp"
+
+extern "C" {
+
+// (pcm_format 0: f32 as rendered, planar or interleaved; DUSP_PCM_*: encoded frames, dusp_render_host_pcm)
+static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, void *h_out,
+                       bool interleaved, int pcm_format = 0, int normalise = 0, float *h_peaks = nullptr);
+
+// 1..64 channels of [1, 2^24] instances x [1, 2^31] samples: what the kernels over planar PCM take
+static int check_planar_pcm(dusp_ctx *ctx, const char *who, size_t n_instances, size_t n_channels, size_t n_samples) {
+    if (!channels_in_range(n_channels) || !batch_in_range(n_instances, n_samples))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": need 1..64 channels, 1..2^24 instances and 1..2^31 samples");
+    return DUSP_OK;
+}
+
+int dusp_render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, float *h_out) {
+    return render_host(prog, n_instances, n_samples, h_params, nullptr, h_out, false);
+}
+
+int dusp_render_host_interleaved(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, float *h_out) {
+    return render_host(prog, n_instances, n_samples, h_params, nullptr, h_out, true);
+}
+
+int dusp_render_host_inputs(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs,
+                            float *h_out, int interleaved) {
+    if (!prog) return DUSP_ERR_ARG;
+    if (prog->P.g.n_inputs > 0 && !h_inputs) CTX_FAIL(prog->ctx, DUSP_ERR_ARG, "render: the program has input streams but h_inputs is NULL");
+    return render_host(prog, n_instances, n_samples, h_params, h_inputs, h_out, interleaved != 0);
+}
+
+int dusp_interleave_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples, float *d_interleaved,
+                           void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (!d_planar || !d_interleaved) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_interleave_device: NULL buffer");
+    if (!channels_in_range(n_channels) || n_instances < 1 || !samples_in_range(n_samples) || (n_samples + 127) / 128 * n_instances > 0x7fffffffull)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_interleave_device: need 1..64 channels and at most 2^31 tiles of 128 frames");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dusp::launch_interleave(d_planar, d_interleaved, (uint32_t)n_instances, (uint32_t)n_channels, n_samples,
+                                         stream_of(ctx, stream_)));
+    return DUSP_OK;
+}
+
+int dusp_peak_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples, float *d_peaks, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (!d_planar || !d_peaks) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_peak_device: NULL buffer");
+    if (int rc = check_planar_pcm(ctx, "dusp_peak_device", n_instances, n_channels, n_samples)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dusp::launch_pcm_peak(d_planar, d_peaks, (uint32_t)n_instances, (uint32_t)n_channels, n_samples, ctx->n_cus,
+                                       stream_of(ctx, stream_)));
+    return DUSP_OK;
+}
+
+int dusp_encode_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples, int format, int normalise,
+                       const float *d_peaks, void *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (!d_planar || !d_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: NULL buffer");
+    if (int rc = check_pcm_format(ctx, "dusp_encode_device", format, /*allow_planar=*/false)) return rc;
+    if (int rc = check_normalise(ctx, "dusp_encode_device", normalise)) return rc;
+    if (normalise != DUSP_NORMALISE_NONE && !d_peaks) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: normalising needs d_peaks (dusp_peak_device)");
+    if (!channels_in_range(n_channels) || !batch_in_range(n_instances, n_samples) ||
+        dusp::pcm_encode_tiles(n_instances, (uint32_t)n_channels, n_samples, format) > 0x7fffffffull)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: need 1..64 channels, 1..2^24 instances, 1..2^31 samples and at most 2^31 tiles");
+    if (format == DUSP_PCM_F32 && ((uintptr_t)d_out & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_encode_device: f32 frames need a 4-byte aligned d_out");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dusp::launch_pcm_encode(d_planar, d_peaks, format, normalise, d_out, (uint32_t)n_instances, (uint32_t)n_channels, n_samples, ctx->n_cus,
+                                         stream_of(ctx, stream_)));
+    return DUSP_OK;
+}
+
+int dusp_render_host_pcm(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, int format, int normalise,
+                         void *h_out, float *h_peaks) {
+    if (!prog) return DUSP_ERR_ARG;
+    dusp_ctx *ctx = prog->ctx;
+    if (int rc = check_pcm_format(ctx, "dusp_render_host_pcm", format, /*allow_planar=*/false)) return rc;
+    if (int rc = check_normalise(ctx, "dusp_render_host_pcm", normalise)) return rc;
+    if (int rc = check_channels(ctx, "dusp_render_host_pcm", prog->P.out_bufs.size())) return rc;
+    if (prog->P.g.n_inputs > 0 && !h_inputs) CTX_FAIL(ctx, DUSP_ERR_ARG, "render: the program has input streams but h_inputs is NULL");
+    return render_host(prog, n_instances, n_samples, h_params, prog->P.g.n_inputs > 0 ? h_inputs : nullptr, h_out, false, format, normalise, h_peaks);
+}
+
+// Device -> host delivery of the rendered PCM (what renderChannelData's caller finally holds).
+//   * h_out is pinned memory (dusp_host_alloc, or registered by the caller): one asynchronous DMA straight into it.
+//   * h_out is pageable and large: kCopyWorkers worker threads, each with its own stream and a pair of pinned staging
+//     tiles, walk disjoint ranges of the output — DMA of tile i+1 into one tile while the CPU copies tile i out of the
+//     other.  (A plain hipMemcpy to pageable memory stages through ONE pinned buffer with ONE copying thread: 10-13 GB/s.)
+//   * small outputs (event-segmented rendering: hundreds of short renders a second): plain asynchronous copy.
+constexpr size_t kCopyTileBytes = (size_t)8 << 20;   // 8 MiB staging tiles
+constexpr int kCopyWorkers = 4;
+constexpr size_t kStagedMinBytes = (size_t)32 << 20;  // 32 MiB: below this the staging pipeline is not worth its threads
+
+static bool is_pinned_host(const void *p) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();  // an unregistered pointer is reported as an error: not one of ours
+        return false;
+    }
+    return attr.type == hipMemoryTypeHost;
+}
+
+static hipError_t download_staged(dusp_program *prog, void *h_out_, const void *d_src_, size_t n_bytes) {
+    dusp_ctx *ctx = prog->ctx;
+    unsigned char *h_out = (unsigned char *)h_out_;
+    const unsigned char *d_src = (const unsigned char *)d_src_;
+    const size_t need = (size_t)kCopyWorkers * 2 * kCopyTileBytes;
+    if (prog->pin_bytes < need) {
+        if (prog->pin[0]) (void)hipHostFree(prog->pin[0]);
+        prog->pin[0] = nullptr;
+        prog->pin_bytes = 0;
+        hipError_t e = hipHostMalloc((void **)&prog->pin[0], need, hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        prog->pin_bytes = need;
+    }
+    hipError_t e = hipStreamSynchronize(ctx->stream);  // the render (and the interleave) have finished: the workers only copy
+    if (e != hipSuccess) return e;
+    hipError_t results[kCopyWorkers];
+    std::thread workers[kCopyWorkers];
+    const size_t n_tiles = (n_bytes + kCopyTileBytes - 1) / kCopyTileBytes;
+    for (int w = 0; w < kCopyWorkers; w++) {
+        results[w] = hipSuccess;
+        workers[w] = std::thread([&, w]() {
+            hipError_t &r = results[w];
+            hipStream_t st = nullptr;
+            if ((r = hipSetDevice(ctx->device)) != hipSuccess || (r = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) return;
+            unsigned char *tile[2] = {prog->pin[0] + (size_t)(2 * w) * kCopyTileBytes, prog->pin[0] + (size_t)(2 * w + 1) * kCopyTileBytes};
+            // this worker's tiles: a contiguous range (neighbouring pages of h_out are faulted in by one thread)
+            const size_t t0 = n_tiles * (size_t)w / kCopyWorkers, t1 = n_tiles * (size_t)(w + 1) / kCopyWorkers;
+            auto span = [&](size_t t, size_t &at, size_t &n) {
+                at = t * kCopyTileBytes;
+                n = std::min(kCopyTileBytes, n_bytes - at);
+            };
+            hipEvent_t done[2] = {nullptr, nullptr};
+            if ((r = hipEventCreateWithFlags(&done[0], hipEventDisableTiming)) == hipSuccess) r = hipEventCreateWithFlags(&done[1], hipEventDisableTiming);
+            size_t at, n;
+            for (size_t t = t0; r == hipSuccess && t < std::min(t0 + 2, t1); t++) {  // prime both tiles
+                span(t, at, n);
+                if ((r = hipMemcpyAsync(tile[(t - t0) & 1], d_src + at, n, hipMemcpyDeviceToHost, st)) == hipSuccess)
+                    r = hipEventRecord(done[(t - t0) & 1], st);
+            }
+            for (size_t t = t0; r == hipSuccess && t < t1; t++) {
+                const int k = (int)((t - t0) & 1);
+                if ((r = hipEventSynchronize(done[k])) != hipSuccess) break;
+                span(t, at, n);
+                std::memcpy(h_out + at, tile[k], n);
+                if (t + 2 < t1) {
+                    span(t + 2, at, n);
+                    if ((r = hipMemcpyAsync(tile[k], d_src + at, n, hipMemcpyDeviceToHost, st)) == hipSuccess)
+                        r = hipEventRecord(done[k], st);
+                }
+            }
+            (void)hipStreamSynchronize(st);
+            if (done[0]) (void)hipEventDestroy(done[0]);
+            if (done[1]) (void)hipEventDestroy(done[1]);
+            (void)hipStreamDestroy(st);
+        });
+    }
+    for (auto &t : workers) t.join();
+    for (hipError_t r : results)
+        if (r != hipSuccess) return r;
+    return hipSuccess;
+}
+
+// What a host render ends with: d_planar f32 [n_instances][n_ch][n_samples] (or, already transposed, d_frames) reaches h_out — as it is,
+// or (pcm_format != 0) through the peak and encode kernels — by the delivery paths above; waits for the stream.
+static int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
+                        int normalise, float *h_peaks, void *h_out) {
+    dusp_ctx *ctx = prog->ctx;
+    const size_t n_out = n_instances * n_ch * n_samples;
+    const void *d_src = d_frames ? d_frames : d_planar;
+    size_t n_bytes = n_out * sizeof(float);
+    if (pcm_format) {  // peak, gain, quantisation and interleave on the device: 2 or 3 bytes a sample cross the link
+        const float *d_peaks = nullptr;
+        if (normalise || h_peaks) {
+            HIP_TRY(ctx, prog->d_host_peaks.ensure(n_instances));
+            d_peaks = prog->d_host_peaks.p;
+            if (int rc = dusp_peak_device(ctx, d_planar, n_instances, n_ch, n_samples, prog->d_host_peaks.p, ctx->stream)) return rc;
+            if (h_peaks) HIP_TRY(ctx, hipMemcpyAsync(h_peaks, d_peaks, n_instances * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        n_bytes = n_out * (size_t)dusp::pcm_bytes_per_sample(pcm_format);
+        HIP_TRY(ctx, prog->d_host_pcm.ensure(n_bytes));
+        if (int rc = dusp_encode_device(ctx, d_planar, n_instances, n_ch, n_samples, pcm_format, normalise, d_peaks, prog->d_host_pcm.p, ctx->stream)) return rc;
+        if (g_guard_bytes) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact())
+                CTX_FAIL(ctx, DUSP_ERR_HIP, "render: the PCM encoder wrote past the end of a device buffer: guard bytes overwritten");
+        }
+        d_src = prog->d_host_pcm.p;
+    }
+    if (n_bytes >= kStagedMinBytes && !is_pinned_host(h_out)) {
+        HIP_TRY(ctx, download_staged(prog, h_out, d_src, n_bytes));
+    } else {  // pinned destination: one DMA at link speed; small output: not worth more
+        HIP_TRY(ctx, hipMemcpyAsync(h_out, d_src, n_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return DUSP_OK;
+}
+
+static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_inputs, void *h_out,
+                       bool interleaved, int pcm_format, int normalise, float *h_peaks) {
+    if (!prog) return DUSP_ERR_ARG;
+    dusp_ctx *ctx = prog->ctx;
+    return guarded(ctx->err, "render", [&]() -> int {
+    if (!h_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "render: h_out is NULL");
+    if (int rc = check_batch(ctx, "render", n_instances, n_samples)) return rc;
+    const size_t n_par = (size_t)prog->P.g.n_params * n_instances;
+    if (n_par && !h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, "render: program has parameters but h_params is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t_start = std::chrono::steady_clock::now();
+    auto since = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(); };
+    const size_t n_out = n_instances * prog->P.out_bufs.size() * n_samples;
+    // staging buffers live with the program (grown on demand): a segmented render calls this hundreds of times a second
+    HIP_TRY(ctx, prog->d_host_out.ensure(std::max<size_t>(1, n_out)));
+    const double us_alloc = since();
+    float *d_out = prog->d_host_out.p, *d_par = nullptr, *d_frames = nullptr;
+    if (n_par) {
+        HIP_TRY(ctx, prog->d_host_par.ensure(n_par));
+        d_par = prog->d_host_par.p;
+        HIP_TRY(ctx, hipMemcpyAsync(d_par, h_params, n_par * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const size_t n_in = (size_t)prog->P.g.n_inputs * n_instances * n_samples;
+    float *d_in = nullptr;
+    if (n_in && !h_inputs) CTX_FAIL(ctx, DUSP_ERR_ARG, "render: the program reads host-generated input streams; use dusp_render_host_inputs");
+    if (n_in) {
+        HIP_TRY(ctx, prog->d_host_in.ensure(n_in));
+        d_in = prog->d_host_in.p;
+        HIP_TRY(ctx, hipMemcpyAsync(d_in, h_inputs, n_in * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (int rc = render_device_unguarded(prog, n_instances, n_samples, d_par, d_in, d_out, ctx->stream)) return rc;
+    const double us_enqueued = since();
+    if (int rc = check_guards(prog, ctx->stream)) return rc;
+    const size_t n_ch = prog->P.out_bufs.size();
+    if (interleaved && n_ch > 1) {  // frames: transpose on the device, then download those
+        HIP_TRY(ctx, prog->d_host_frames.ensure(n_out));
+        d_frames = prog->d_host_frames.p;
+        if (int rc = dusp_interleave_device(ctx, d_out, n_instances, n_ch, n_samples, d_frames, ctx->stream)) return rc;
+    }
+    if (int rc = deliver_host(prog, d_out, d_frames, n_instances, n_ch, n_samples, pcm_format, normalise, h_peaks, h_out)) return rc;
+    if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: where a host render's time goes)
+        fprintf(stderr, "[dusp host render] output buffer %.0f us, render enqueued (workspaces, constants, launches) %.0f us, download + wait %.0f us\n", us_alloc, us_enqueued - us_alloc,
+                since() - us_enqueued);
+    return DUSP_OK;
+    });
+}
+
+constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)
+
+int dusp_mix_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_samples, const float *d_gains, const float *d_init,
+                    int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    return guarded(ctx->err, "dusp_mix_device", [&]() -> int {
+    if (!d_planar || !d_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_mix_device: NULL buffer");
+    if (int rc = check_planar_pcm(ctx, "dusp_mix_device", n_instances, n_channels, n_samples)) return rc;
+    if (n_channels * n_samples > kMixRowMax)  // (one lane per float of the row at the most: the grid's 2^32 threads)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_mix_device: channels x samples must not exceed 2^31: mix such a batch channel by channel or in windows of the timeline");
+    if ((((uintptr_t)d_planar | (uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_mix_device: the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, dusp::launch_mix(d_planar, d_gains, d_init, d_out, (uint64_t)n_channels * n_samples, (uint32_t)n_instances, raw != 0, ctx->n_cus,
+                                  ctx->knobs.mix_width, ctx->knobs.mix_depth, stream_of(ctx, stream_)));
+    return DUSP_OK;
+    });
+}
+
+int dusp_render_host_mix(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_gains, size_t tile_instances,
+                         int format, int normalise, void *h_out, float *h_peak) {
+    if (!prog) return DUSP_ERR_ARG;
+    dusp_ctx *ctx = prog->ctx;
+    return guarded(ctx->err, "dusp_render_host_mix", [&]() -> int {
+    if (!h_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: h_out is NULL");
+    if (int rc = check_batch(ctx, "dusp_render_host_mix", n_instances, n_samples)) return rc;
+    if (int rc = check_pcm_format(ctx, "dusp_render_host_mix", format, /*allow_planar=*/true)) return rc;
+    if (int rc = check_normalise(ctx, "dusp_render_host_mix", normalise)) return rc;
+    if (prog->P.g.n_inputs > 0)
+        CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_mix: the program reads host-generated input streams; render it with dusp_render_host_inputs and mix on the host");
+    if (prog->resumable) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_mix: a resumable program (DUSP_ENGINE_RESUMABLE) is not mixed: its tiles would continue one another");
+    const size_t n_ch = prog->P.out_bufs.size(), n_params = prog->P.g.n_params;
+    if (int rc = check_channels(ctx, "dusp_render_host_mix", n_ch)) return rc;
+    const size_t row = n_ch * n_samples;
+    if (row > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: channels x samples must not exceed 2^31: mix such a render in windows of the timeline");
+    if (n_params && !h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: program has parameters but h_params is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t free_bytes = 0, total_bytes = 0;
+    if (tile_instances == 0 && ctx->knobs.mix_tile_mb <= 0) HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));  // (the default tile: by the device's free memory)
+    const size_t tile = dusp::mix_tile_instances(tile_instances, ctx->knobs.mix_tile_mb, free_bytes, prog->d_host_out.cap * sizeof(float), ctx->n_cus, row, n_instances);
+    // the tile's PCM, its parameter columns and gains, and the running sums: all that lives on the device, whatever n_instances is
+    HIP_TRY(ctx, prog->d_host_out.ensure(tile * row));
+    HIP_TRY(ctx, prog->d_mix.ensure(row));
+    if (n_params) HIP_TRY(ctx, prog->d_host_par.ensure(n_params * tile));
+    if (h_gains) HIP_TRY(ctx, prog->d_mix_gains.ensure(tile));
+    // Tiling must not change a bit.  What a render decides from the batch and that changes bits is, while the tiles render, decided from the
+    // WHOLE batch: a Filter with a per-instance cutoff runs as a scan or as a recurrence — not the same bits — by the range of its column
+    // (mix_range), and so does every scan-eligible Filter by whether the render is cut into warming segments, which the instance count
+    // decides (mix_n_inst, which also makes every tile wait for its compiled kernel).  Per-instance Delays are classified per tile: their
+    // regimes differ in speed only.
+    std::vector<float> cols;  // (declared in front of the guard: it outlives the guard's wait for the stream)
+    struct WholeBatch {
+        dusp_program *prog;
+        hipStream_t stream;
+        bool staged = false;  // host vectors of this call may still be on their way to the device
+        ~WholeBatch() {
+            if (staged) (void)hipStreamSynchronize(stream);  // (a return in the middle of the tiles)
+            prog->mix_range.clear();
+            prog->mix_n_inst = 0;
+            prog->mixed = true;  // (whichever tile was the last to render, the whole batch it was not)
+        }
+    } whole{prog, ctx->stream};
+    prog->mix_n_inst = (uint32_t)n_instances;
+    prog->mix_range.assign(3 * n_params, 0u);
+    for (size_t p = 0; p < n_params; p++)
+        for (size_t i = 0; i < n_instances; i++) {
+            const float v = h_params[p * n_instances + i];
+            if (!(v > 0.f && v <= 3.0e38f)) prog->mix_range[3 * p + 2] = 1u;
+            else {
+                unsigned b;
+                std::memcpy(&b, &v, 4);  // (positive floats order like their bits)
+                prog->mix_range[3 * p] = std::max(prog->mix_range[3 * p], 0x7fffffffu - b);
+                prog->mix_range[3 * p + 1] = std::max(prog->mix_range[3 * p + 1], b);
+            }
+        }
+    // every tile's columns of the slot-major table [n_params][n_instances], tile after tile, gathered once: nothing on the host is
+    // reused from one tile to the next, so the tiles queue up on the stream without the host waiting for any of them
+    cols.resize(n_params * n_instances);
+    for (size_t lo = 0; lo < n_instances && n_params; lo += tile) {
+        const size_t n = std::min(tile, n_instances - lo);
+        for (size_t p = 0; p < n_params; p++) std::memcpy(&cols[n_params * lo + p * n], h_params + p * n_instances + lo, n * sizeof(float));
+    }
+    for (size_t lo = 0; lo < n_instances; lo += tile) {
+        const size_t n = std::min(tile, n_instances - lo);
+        const bool last = lo + n == n_instances;
+        if (n_params) {
+            HIP_TRY(ctx, hipMemcpyAsync(prog->d_host_par.p, &cols[n_params * lo], n_params * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            whole.staged = true;
+        }
+        if (h_gains) HIP_TRY(ctx, hipMemcpyAsync(prog->d_mix_gains.p, h_gains + lo, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = render_device_unguarded(prog, n, n_samples, n_params ? prog->d_host_par.p : nullptr, nullptr, prog->d_host_out.p, ctx->stream)) return rc;
+        if (int rc = check_guards(prog, ctx->stream)) return rc;
+        if (int rc = dusp_mix_device(ctx, prog->d_host_out.p, n, n_ch, n_samples, h_gains ? prog->d_mix_gains.p : nullptr, lo > 0 ? prog->d_mix.p : nullptr, !last,
+                                     prog->d_mix.p, ctx->stream))
+            return rc;
+    }
+    if (int rc = deliver_host(prog, prog->d_mix.p, nullptr, 1, n_ch, n_samples, format, normalise, h_peak, h_out)) return rc;
+    whole.staged = false;  // (the delivery has waited for the stream)
+    if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact()))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, "dusp_render_host_mix: the mix kernel wrote past the end of a device buffer: guard bytes overwritten");
+    return DUSP_OK;
+    });
+}
+
+}  // extern "C"

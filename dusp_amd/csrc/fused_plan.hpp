@@ -477,8 +477,8 @@ inline void build_sum_voices(const FusedPlan &plan, uint32_t sample_rate, int gb
         }
 }
 
-// Regime of a per-instance (parameter) delay, found by looking at the parameter column when a render starts (dusp_abi.hip
-// classify_param_delays) and kept in the operand's spare word: every instance's delay of at least a chunk (and a chunk short of the
+// Regime of a per-instance (parameter) delay, found by looking at the parameter column when a render starts (abi_render_jit.hip
+// jit_classify_columns) and kept in the operand's spare word: every instance's delay of at least a chunk (and a chunk short of the
 // ring's length), every instance's below a chunk, or anything else (mixed, negative, NaN, within a sample of the chunk size).
 enum : int { DELAY_REGIME_UNKNOWN = 0, DELAY_REGIME_LONG = 1, DELAY_REGIME_SHORT = 2, DELAY_REGIME_OTHER = 4 };
 // one delay value's regime, as the compiled kernels' units will treat it (jit_prelude.hpp JitDelayK / JitDelayShort)
@@ -511,7 +511,7 @@ inline bool delay_write_once(const DevOp &op) {
 // Can the wave engine (one wavefront per instance, chunk buffers in LDS) run this program?
 // will_continue: the program is resumable, i.e. later launches pick up rings and parked chunk buffers in the reference's layout
 // settled_only: plan the settled op list of a program whose first chunks run op lists of their own (Program::warm_ops) — those chunks
-// are rendered by the chunk engine and the rest handed to a compiled kernel (dusp_abi.hip)
+// are rendered by the chunk engine and the rest handed to a compiled kernel (abi_render.hip render_handoff)
 inline bool plan_wave(const Program &P, WavePlan &plan, bool will_continue = false, bool settled_only = false) {
     const Graph &g = P.g;
     auto no = [&](const std::string &why) {

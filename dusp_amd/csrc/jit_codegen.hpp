@@ -271,7 +271,7 @@ inline bool jit_filter_scan_ok(const Program &P, const int *table_bound = nullpt
 // feedback) is cut into segments whose wavefronts start one segment EARLY, from rest, and store only their own chunks; the host then checks
 // that what every Filter held when a segment's own chunks began is what the segment before ended with (JitArgs::warm_records) — by
 // induction from the first segment the whole render is the sequential one's — and finishes a render whose check fails sequentially from the
-// last good segment (dusp_abi.hip render_jit).  How long the warm-up must be is a property of the QUANTISED recurrence (every y rounded to
+// last good segment (abi_render_jit.hip jit_check_warm).  How long the warm-up must be is a property of the QUANTISED recurrence (every y rounded to
 // f32): its all-pole part has a DC gain of sum|h|, and two trajectories an ulp apart stay an ulp apart with probability ~1 - 1/sum|h| a
 // step.  Measured (tools/filter_merge_experiment.c --from-rest, sines and saws): merged within 20 sum|h| samples in every trial down to 400 Hz,
 // effectively never at 200 Hz (sum|h| 1500: limit cycles).  Returns the chunks of warm-up to give — 32 sum|h| samples over the circuit's Filters
@@ -2056,7 +2056,7 @@ inline void jit_site_options(JitOptions &opt, const Program &P, const JitSite &s
     }
 }
 
-// Descriptor words -> kernel text for a given workgroup geometry, WITHOUT a device: what dusp_circuit_kernel_source (dusp_abi.hip) does in
+// Descriptor words -> kernel text for a given workgroup geometry, WITHOUT a device: what dusp_circuit_kernel_source (abi_program.hip) does in
 // front of the run-time compiler, as one host-only function — parse and expand the descriptor (program.hpp), plan it for the wave engine
 // (fused_plan.hpp), choose the options a context would choose for the reference's own tables, generate.  Everything the untrusted input
 // reaches on the way lives in these headers, so tests/native/hostcheck.cpp drives exactly this under AddressSanitizer / UBSan with

@@ -5,7 +5,7 @@
 // Caches.  Code objects are kept process-wide, keyed by the generated text (constants are not part of it, jit_codegen.hpp);
 // modules are loaded per device (a hipModule_t belongs to the device it was loaded on).  A render that finds its kernel
 // costs a map lookup; a new structure costs one hiprtc compile (0.3-0.8 s) — in the foreground when the render is worth
-// waiting for, else on the compile worker while the interpreter kernel renders this once (dusp_abi.hip decides).
+// waiting for, else on the compile worker while the interpreter kernel renders this once (abi_render_jit.hip jit_obtain_kernel decides).
 // Code objects are also kept ON DISK across processes, by default under $XDG_CACHE_HOME/dusp-hip (~/.cache/dusp-hip);
 // DUSP_JIT_CACHE=<directory> moves the cache, DUSP_JIT_CACHE=0 turns it off (read once per process, with the first
 // context).  A cache file is keyed by everything the code object depends on — the text, the embedded device library's

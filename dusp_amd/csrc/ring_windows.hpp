@@ -1,4 +1,4 @@
-// ring_windows.hpp — which slots of its delay rings can a render touch?  (host side; dusp_abi.hip zero_rings fills exactly these with zeros)
+// ring_windows.hpp — which slots of its delay rings can a render touch?  (host side; abi_render.hip zero_rings fills exactly these with zeros)
 //
 // Rings start as zeros (Delay.js:14, CircleBuffer.js:12).  A render that nothing continues only ever touches part of a long ring — a
 // Delay of constant length d reads [clock, clock + n) and writes up to d + 1 further on; a CircleBuffer node with an unconnected

@@ -2,7 +2,8 @@
 // program (program.hpp: parse, channel inference, expansion) -> plans (fused_plan.hpp: fused voice shapes, the wave engine) ->
 // kernel text (jit_codegen.hpp jit_source_from_descriptor — the very function dusp_circuit_kernel_source runs in front of the run-time
 // compiler; the text is generated, not compiled) and -> launch plans (jit_plan.hpp jit_plan / jit_spill_step: what a render decides before
-// it touches the device, over a spread of batches and knobs, every spill ladder walked to its end).  Driven with
+// it touches the device, over a spread of batches and knobs, every spill ladder walked to its end) and -> the engine a build or a continuation
+// chooses (engine_select.hpp engine_select, for every requested engine, plain and resumable, new and continued).  Driven with
 //   * every descriptor file named on the command line (the golden descriptors the reference generated) as it stands, over a spread of
 //     workgroup geometries and knob settings;
 //   * its truncations (every third length) and single-word corruptions (NaN, Inf, negative, fractional, huge, small-integer values at random
@@ -19,6 +20,7 @@
 
 #include "../../dusp_amd/csrc/jit_codegen.hpp"
 #ifndef HOSTCHECK_NO_PLANNER
+#include "../../dusp_amd/csrc/engine_select.hpp"
 #include "../../dusp_amd/csrc/jit_plan.hpp"
 #endif
 #include "../../dusp_amd/csrc/ring_windows.hpp"
@@ -28,9 +30,36 @@ using namespace dusp;
 static long g_text = 0, g_malformed = 0, g_unsupported = 0, g_calls = 0, g_bad = 0;
 static size_t g_text_bytes = 0;
 static unsigned long long g_text_hash = 1469598103934665603ull;
-static long g_plans = 0;
+static long g_plans = 0, g_selects = 0;
 
 #ifndef HOSTCHECK_NO_PLANNER
+// The engine choice as dusp_program_build / dusp_program_continue would ask for it: every call ends in an engine or in a refusal with a text
+static void drive_engine_select(const std::vector<double> &words, bool every_variant) {
+    Program P0;
+    std::string err;
+    if (!compile(words.data(), words.size(), P0, err)) return;
+    std::vector<WavePlan::RampChecked> checked;
+    for (int requested : {DUSP_ENGINE_AUTO, DUSP_ENGINE_CHUNK, DUSP_ENGINE_FUSED, DUSP_ENGINE_WAVE})
+        for (int variant = 0; variant < (every_variant ? 6 : 2); variant++) {
+            if (!every_variant && requested != DUSP_ENGINE_AUTO && requested != DUSP_ENGINE_WAVE) continue;
+            EngineRequest rq;
+            rq.requested = requested;
+            rq.resumable = variant >= 1;
+            rq.rendered = variant >= 3;  // a continuation, on the wave or the chunk engine so far, a Delay's constant changed
+            rq.engine_so_far = variant == 4 ? DUSP_ENGINE_CHUNK : DUSP_ENGINE_WAVE;
+            rq.delay_changed = variant == 5;
+            rq.wave_jit = variant == 2 ? 0 : 1;
+            for (int k = 0; k < kNumTables; k++) rq.table_set[k] = variant != 2, rq.table_fx32_ok[k] = variant % 2 == 0;
+            Program P = P0;
+            EngineChoice c = engine_select(P, rq, checked);
+            checked = c.wave.ramp_checked;  // (as a program keeps them from one plan to the next)
+            g_selects++;
+            const bool engine_ok = c.engine == DUSP_ENGINE_CHUNK || c.engine == DUSP_ENGINE_FUSED || c.engine == DUSP_ENGINE_WAVE;
+            if (c.error ? (c.error != DUSP_ERR_UNSUPPORTED || c.error_text.empty()) : (!engine_ok || !c.error_text.empty() || (c.jit_ok && c.engine != DUSP_ENGINE_WAVE) || (c.handoff_ok && c.engine != DUSP_ENGINE_CHUNK)))
+                g_bad++, std::printf("FAIL: engine_select: engine %d, error %d \"%s\"\n", c.engine, c.error, c.error_text.c_str());
+        }
+}
+
 // The planner over a spread of (n_inst, n_chunks, knobs), as dusp_program_build + render_jit would call it for this descriptor
 static void drive_planner(const std::vector<double> &words, bool every_variant) {
     Program P;
@@ -96,6 +125,7 @@ static void drive(const std::vector<double> &words, bool every_geometry) {
         }
     }
 #ifndef HOSTCHECK_NO_PLANNER
+    drive_engine_select(words, every_geometry);
     drive_planner(words, every_geometry);
 #endif
     static const int geo[][2] = {{4, 1}, {16, 1}, {16, 2}, {8, 4}, {1, 1}};
@@ -153,7 +183,7 @@ int main(int argc, char **argv) {
             drive(d2, false);
         }
     }
-    std::printf("{\"files\": %d, \"calls\": %ld, \"text\": %ld, \"malformed\": %ld, \"unsupported\": %ld, \"text_bytes\": %zu, \"text_hash\": \"%016llx\", \"plans\": %ld, \"bad\": %ld}\n",
-                files, g_calls, g_text, g_malformed, g_unsupported, g_text_bytes, g_text_hash, g_plans, g_bad);
+    std::printf("{\"files\": %d, \"calls\": %ld, \"text\": %ld, \"malformed\": %ld, \"unsupported\": %ld, \"text_bytes\": %zu, \"text_hash\": \"%016llx\", \"plans\": %ld, \"selects\": %ld, \"bad\": %ld}\n",
+                files, g_calls, g_text, g_malformed, g_unsupported, g_text_bytes, g_text_hash, g_plans, g_selects, g_bad);
     return g_bad ? 1 : 0;
 }

@@ -271,7 +271,7 @@ RING_GOLDEN = [n for n in ALL_GOLDEN if n.startswith(("delay_", "loop_", "circle
 
 @pytest.mark.parametrize("engine", ["auto", "chunk", "wave", "interp"])
 def test_rings_are_zeroed_wherever_a_render_can_touch_them(engine):
-    """A render nothing continues zero-fills only the part of each delay ring it can touch (dusp_abi.hip zero_rings: a five-second
+    """A render nothing continues zero-fills only the part of each delay ring it can touch (abi_render.hip zero_rings: a five-second
     default Delay line is mostly out of a short render's reach).  DUSP_RING_POISON=1 fills the rings with NaN patterns first, so a window
     cut too short shows in the PCM: every golden with a ring, alone and as a batch of 70 (two rows of instances), bit for bit against
     the reference's own output, and the same with the windows switched off."""

@@ -14,7 +14,7 @@ def test_descriptor_path_under_asan_and_ubsan():
     -fsanitize=address,undefined -fno-sanitize-recover=all, driven (tests/native/hostcheck.cpp) by every golden descriptor over a spread of
     workgroup geometries and knobs, by their truncations and by single- and double-word corruptions: every call ends in a verdict with a
     message (kernel text / malformed / unsupported), every descriptor the compiler takes is planned for a spread of batches and knobs with
-    its spill ladder walked to the end, and the sanitizers — leak detection included — have nothing to report."""
+    its spill ladder walked to the end and its engine chosen (engine_select.hpp: every requested engine, plain, resumable and continued), and the sanitizers — leak detection included — have nothing to report."""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "dusp_amd", "csrc"), "-s", "hostcheck"])
     exe = os.path.join(ROOT, "dusp_amd", "csrc", "build", "hostcheck")
     files = sorted(glob.glob(os.path.join(GOLDEN, "*.desc.f64")))
@@ -27,6 +27,7 @@ def test_descriptor_path_under_asan_and_ubsan():
     assert rep["files"] == len(files) and rep["bad"] == 0
     assert rep["text"] > 10000 and rep["malformed"] > 40000 and rep["unsupported"] > 500  # (all three verdicts are exercised)
     assert rep["plans"] > 0
+    assert rep["selects"] > 10000  # (engine_select.hpp: the engine choice for every descriptor that compiles)
 
 
 def test_oracle_under_asan_and_ubsan():
