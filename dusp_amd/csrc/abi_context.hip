@@ -43,6 +43,7 @@ static dusp::Knobs read_knobs() {
     k.mix_width = num("DUSP_MIX_WIDTH", k.mix_width);
     k.mix_depth = num("DUSP_MIX_DEPTH", k.mix_depth);
     k.mix_tile_mb = num("DUSP_MIX_TILE_MB", k.mix_tile_mb);
+    k.score_plan_kb = num("DUSP_SCORE_PLAN_KB", k.score_plan_kb);
     if (const char *f = getenv("DUSP_JIT_FORCE")) {
         int w = 0, r = 0;
         if (std::sscanf(f, "%dx%d", &w, &r) == 2 && w >= 1 && w <= 16 && r >= 1 && r <= 4) k.jit_force_waves = w, k.jit_force_per_wave = r;
@@ -121,6 +122,11 @@ void dusp_ctx_destroy(dusp_ctx *ctx) {
         (void)hipStreamDestroy(ctx->stream);
     }
     if (ctx->d_tables) (void)hipFree(ctx->d_tables);
+    if (ctx->d_score_plan) (void)hipFree(ctx->d_score_plan);
+    if (ctx->score_uploaded) (void)hipEventDestroy(ctx->score_uploaded);
+    if (ctx->score_done) (void)hipEventDestroy(ctx->score_done);
+    for (hipEvent_t ev : {ctx->score_up0, ctx->score_t0, ctx->score_t1})
+        if (ev) (void)hipEventDestroy(ev);
     for (auto &b : ctx->host_pool) (void)hipHostFree(b.p);
     delete ctx;
 }

@@ -1,5 +1,5 @@
-// abi_deliver.hip — the C ABI (include/dusp_hip.h): what happens to rendered PCM on the device (interleave, peak, encode, mix) and how
-// it reaches the host (dusp_render_host* and their delivery paths, dusp_render_host_mix).
+// abi_deliver.hip — the C ABI (include/dusp_hip.h): what happens to rendered PCM on the device (interleave, peak, encode, mix, score) and how
+// it reaches the host (dusp_render_host* and their delivery paths, dusp_render_host_mix, dusp_render_host_score).
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -269,79 +269,104 @@ int dusp_mix_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, si
     });
 }
 
+// The tiles of one batch (dusp_render_host_mix, dusp_render_host_score).  Tiling must not change a bit.  What a render decides from the
+// batch and that changes bits is, while the tiles render, decided from the WHOLE batch: a Filter with a per-instance cutoff runs as a scan
+// or as a recurrence — not the same bits — by the range of its column (mix_range), and so does every scan-eligible Filter by whether the
+// render is cut into warming segments, which the instance count decides (mix_n_inst, which also makes every tile wait for its compiled
+// kernel).  Per-instance Delays are classified per tile: their regimes differ in speed only.
+struct TiledBatch {
+    dusp_program *prog;
+    hipStream_t stream;
+    size_t n_instances, n_params, tile;
+    const float *h_gains;
+    bool staged = false;      // host vectors of this call may still be on their way to the device
+    std::vector<float> cols;  // (a member: it outlives the destructor's wait for the stream)
+
+    // every tile's columns of the slot-major table [n_params][n_instances], tile after tile, gathered once: nothing on the host is
+    // reused from one tile to the next, so the tiles queue up on the stream without the host waiting for any of them
+    TiledBatch(dusp_program *prog_, size_t n_instances_, const float *h_params, const float *h_gains_, size_t tile_)
+        : prog(prog_), stream(prog_->ctx->stream), n_instances(n_instances_), n_params(prog_->P.g.n_params), tile(tile_), h_gains(h_gains_) {
+        prog->mix_n_inst = (uint32_t)n_instances;
+        prog->mix_range.assign(3 * n_params, 0u);
+        for (size_t p = 0; p < n_params; p++)
+            for (size_t i = 0; i < n_instances; i++) {
+                const float v = h_params[p * n_instances + i];
+                if (!(v > 0.f && v <= 3.0e38f)) prog->mix_range[3 * p + 2] = 1u;
+                else {
+                    unsigned b;
+                    std::memcpy(&b, &v, 4);  // (positive floats order like their bits)
+                    prog->mix_range[3 * p] = std::max(prog->mix_range[3 * p], 0x7fffffffu - b);
+                    prog->mix_range[3 * p + 1] = std::max(prog->mix_range[3 * p + 1], b);
+                }
+            }
+        cols.resize(n_params * n_instances);
+        for (size_t lo = 0; lo < n_instances && n_params; lo += tile) {
+            const size_t n = std::min(tile, n_instances - lo);
+            for (size_t p = 0; p < n_params; p++) std::memcpy(&cols[n_params * lo + p * n], h_params + p * n_instances + lo, n * sizeof(float));
+        }
+    }
+    ~TiledBatch() {
+        if (staged) (void)hipStreamSynchronize(stream);  // (a return in the middle of the tiles)
+        prog->mix_range.clear();
+        prog->mix_n_inst = 0;
+        prog->mixed = true;  // (whichever tile was the last to render, the whole batch it was not)
+    }
+    // instances [lo, lo + n): their columns and gains to the device, their PCM into d_host_out
+    int render_tile(size_t lo, size_t n, size_t n_samples) {
+        dusp_ctx *ctx = prog->ctx;
+        if (n_params) {
+            HIP_TRY(ctx, hipMemcpyAsync(prog->d_host_par.p, &cols[n_params * lo], n_params * n * sizeof(float), hipMemcpyHostToDevice, stream));
+            staged = true;
+        }
+        if (h_gains) HIP_TRY(ctx, hipMemcpyAsync(prog->d_mix_gains.p, h_gains + lo, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (int rc = render_device_unguarded(prog, n, n_samples, n_params ? prog->d_host_par.p : nullptr, nullptr, prog->d_host_out.p, stream)) return rc;
+        return check_guards(prog, stream);
+    }
+};
+
+// what dusp_render_host_mix and dusp_render_host_score refuse alike, and the tile both render in: the tile's PCM, its parameter columns
+// and gains are all that lives on the device beside the sums, whatever n_instances is
+static int tiled_batch_prepare(dusp_program *prog, const char *who, size_t n_instances, size_t n_samples, const float *h_params, const float *h_gains,
+                               size_t tile_instances, int format, int normalise, const void *h_out, size_t *tile_out) {
+    dusp_ctx *ctx = prog->ctx;
+    const std::string w(who);
+    if (!h_out) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_out is NULL");
+    if (int rc = check_batch(ctx, who, n_instances, n_samples)) return rc;
+    if (int rc = check_pcm_format(ctx, who, format, /*allow_planar=*/true)) return rc;
+    if (int rc = check_normalise(ctx, who, normalise)) return rc;
+    if (prog->P.g.n_inputs > 0)
+        CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, w + ": the program reads host-generated input streams; render it with dusp_render_host_inputs and mix on the host");
+    if (prog->resumable) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, w + ": a resumable program (DUSP_ENGINE_RESUMABLE) is not mixed: its tiles would continue one another");
+    const size_t n_ch = prog->P.out_bufs.size(), n_params = prog->P.g.n_params;
+    if (int rc = check_channels(ctx, who, n_ch)) return rc;
+    const size_t row = n_ch * n_samples;
+    if (row > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x samples must not exceed 2^31: mix such a render in windows of the timeline");
+    if (n_params && !h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": program has parameters but h_params is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t free_bytes = 0, total_bytes = 0;
+    if (tile_instances == 0 && ctx->knobs.mix_tile_mb <= 0) HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));  // (the default tile: by the device's free memory)
+    const size_t tile = dusp::mix_tile_instances(tile_instances, ctx->knobs.mix_tile_mb, free_bytes, prog->d_host_out.cap * sizeof(float), ctx->n_cus, row, n_instances);
+    HIP_TRY(ctx, prog->d_host_out.ensure(tile * row));
+    if (n_params) HIP_TRY(ctx, prog->d_host_par.ensure(n_params * tile));
+    if (h_gains) HIP_TRY(ctx, prog->d_mix_gains.ensure(tile));
+    *tile_out = tile;
+    return DUSP_OK;
+}
+
 int dusp_render_host_mix(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_gains, size_t tile_instances,
                          int format, int normalise, void *h_out, float *h_peak) {
     if (!prog) return DUSP_ERR_ARG;
     dusp_ctx *ctx = prog->ctx;
     return guarded(ctx->err, "dusp_render_host_mix", [&]() -> int {
-    if (!h_out) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: h_out is NULL");
-    if (int rc = check_batch(ctx, "dusp_render_host_mix", n_instances, n_samples)) return rc;
-    if (int rc = check_pcm_format(ctx, "dusp_render_host_mix", format, /*allow_planar=*/true)) return rc;
-    if (int rc = check_normalise(ctx, "dusp_render_host_mix", normalise)) return rc;
-    if (prog->P.g.n_inputs > 0)
-        CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_mix: the program reads host-generated input streams; render it with dusp_render_host_inputs and mix on the host");
-    if (prog->resumable) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_host_mix: a resumable program (DUSP_ENGINE_RESUMABLE) is not mixed: its tiles would continue one another");
-    const size_t n_ch = prog->P.out_bufs.size(), n_params = prog->P.g.n_params;
-    if (int rc = check_channels(ctx, "dusp_render_host_mix", n_ch)) return rc;
-    const size_t row = n_ch * n_samples;
-    if (row > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: channels x samples must not exceed 2^31: mix such a render in windows of the timeline");
-    if (n_params && !h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_mix: program has parameters but h_params is NULL");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t free_bytes = 0, total_bytes = 0;
-    if (tile_instances == 0 && ctx->knobs.mix_tile_mb <= 0) HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));  // (the default tile: by the device's free memory)
-    const size_t tile = dusp::mix_tile_instances(tile_instances, ctx->knobs.mix_tile_mb, free_bytes, prog->d_host_out.cap * sizeof(float), ctx->n_cus, row, n_instances);
-    // the tile's PCM, its parameter columns and gains, and the running sums: all that lives on the device, whatever n_instances is
-    HIP_TRY(ctx, prog->d_host_out.ensure(tile * row));
-    HIP_TRY(ctx, prog->d_mix.ensure(row));
-    if (n_params) HIP_TRY(ctx, prog->d_host_par.ensure(n_params * tile));
-    if (h_gains) HIP_TRY(ctx, prog->d_mix_gains.ensure(tile));
-    // Tiling must not change a bit.  What a render decides from the batch and that changes bits is, while the tiles render, decided from the
-    // WHOLE batch: a Filter with a per-instance cutoff runs as a scan or as a recurrence — not the same bits — by the range of its column
-    // (mix_range), and so does every scan-eligible Filter by whether the render is cut into warming segments, which the instance count
-    // decides (mix_n_inst, which also makes every tile wait for its compiled kernel).  Per-instance Delays are classified per tile: their
-    // regimes differ in speed only.
-    std::vector<float> cols;  // (declared in front of the guard: it outlives the guard's wait for the stream)
-    struct WholeBatch {
-        dusp_program *prog;
-        hipStream_t stream;
-        bool staged = false;  // host vectors of this call may still be on their way to the device
-        ~WholeBatch() {
-            if (staged) (void)hipStreamSynchronize(stream);  // (a return in the middle of the tiles)
-            prog->mix_range.clear();
-            prog->mix_n_inst = 0;
-            prog->mixed = true;  // (whichever tile was the last to render, the whole batch it was not)
-        }
-    } whole{prog, ctx->stream};
-    prog->mix_n_inst = (uint32_t)n_instances;
-    prog->mix_range.assign(3 * n_params, 0u);
-    for (size_t p = 0; p < n_params; p++)
-        for (size_t i = 0; i < n_instances; i++) {
-            const float v = h_params[p * n_instances + i];
-            if (!(v > 0.f && v <= 3.0e38f)) prog->mix_range[3 * p + 2] = 1u;
-            else {
-                unsigned b;
-                std::memcpy(&b, &v, 4);  // (positive floats order like their bits)
-                prog->mix_range[3 * p] = std::max(prog->mix_range[3 * p], 0x7fffffffu - b);
-                prog->mix_range[3 * p + 1] = std::max(prog->mix_range[3 * p + 1], b);
-            }
-        }
-    // every tile's columns of the slot-major table [n_params][n_instances], tile after tile, gathered once: nothing on the host is
-    // reused from one tile to the next, so the tiles queue up on the stream without the host waiting for any of them
-    cols.resize(n_params * n_instances);
-    for (size_t lo = 0; lo < n_instances && n_params; lo += tile) {
-        const size_t n = std::min(tile, n_instances - lo);
-        for (size_t p = 0; p < n_params; p++) std::memcpy(&cols[n_params * lo + p * n], h_params + p * n_instances + lo, n * sizeof(float));
-    }
+    size_t tile = 0;
+    if (int rc = tiled_batch_prepare(prog, "dusp_render_host_mix", n_instances, n_samples, h_params, h_gains, tile_instances, format, normalise, h_out, &tile)) return rc;
+    const size_t n_ch = prog->P.out_bufs.size();
+    HIP_TRY(ctx, prog->d_mix.ensure(n_ch * n_samples));  // the running sums
+    TiledBatch whole(prog, n_instances, h_params, h_gains, tile);
     for (size_t lo = 0; lo < n_instances; lo += tile) {
         const size_t n = std::min(tile, n_instances - lo);
         const bool last = lo + n == n_instances;
-        if (n_params) {
-            HIP_TRY(ctx, hipMemcpyAsync(prog->d_host_par.p, &cols[n_params * lo], n_params * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            whole.staged = true;
-        }
-        if (h_gains) HIP_TRY(ctx, hipMemcpyAsync(prog->d_mix_gains.p, h_gains + lo, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (int rc = render_device_unguarded(prog, n, n_samples, n_params ? prog->d_host_par.p : nullptr, nullptr, prog->d_host_out.p, ctx->stream)) return rc;
-        if (int rc = check_guards(prog, ctx->stream)) return rc;
+        if (int rc = whole.render_tile(lo, n, n_samples)) return rc;
         if (int rc = dusp_mix_device(ctx, prog->d_host_out.p, n, n_ch, n_samples, h_gains ? prog->d_mix_gains.p : nullptr, lo > 0 ? prog->d_mix.p : nullptr, !last,
                                      prog->d_mix.p, ctx->stream))
             return rc;
@@ -350,6 +375,192 @@ int dusp_render_host_mix(dusp_program *prog, size_t n_instances, size_t n_sample
     whole.staged = false;  // (the delivery has waited for the stream)
     if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact()))
         CTX_FAIL(ctx, DUSP_ERR_HIP, "dusp_render_host_mix: the mix kernel wrote past the end of a device buffer: guard bytes overwritten");
+    return DUSP_OK;
+    });
+}
+
+// ---- scores: voices mixed at per-voice onsets (score_engine.hip; dusp_amd/mix.py score_chain is the contract) ----
+
+// one launch's plan inside the context's image
+struct ScoreLaunch {
+    size_t at = 0, n_voices = 0, n_block_first = 0;  // byte offset of the voices; block_first and the entries follow
+    uint64_t w_lo = 0, w_hi = 0, first_block = 0;
+    uint32_t block_shift = dusp::kScoreGroupShift;
+    bool any = false;  // some voice reaches the timeline (else: no plan in the image)
+};
+
+// before a call rewrites the context's host image: the last upload has read it
+static int score_image_begin(dusp_ctx *ctx) {
+    if (!ctx->score_uploaded) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_uploaded));  // (with timing: dusp_score_last_ms)
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->score_done, hipEventDisableTiming));
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_up0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_t0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_t1));
+    } else {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->score_uploaded));
+    }
+    ctx->h_score_plan.clear();
+    ctx->score_upload_timed = false;  // (score_up0 .. score_uploaded are about to be another call's)
+    return DUSP_OK;
+}
+
+// what the plans of ONE call may take together, on the host and on the device
+static size_t score_plan_budget(dusp_ctx *ctx) { return ctx->knobs.score_plan_kb > 0 ? (size_t)ctx->knobs.score_plan_kb << 10 : dusp::kScorePlanBytes; }
+
+// plans the voices [0, n) within budget_bytes and appends the plan to the context's host image
+static int score_image_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, size_t n, size_t first_voice, uint64_t n_voice,
+                           uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L) {
+    dusp::ScorePlan P;
+    const int64_t bad = dusp::score_plan(h_onsets, h_lengths, n, n_voice, n_total, whole_timeline, budget_bytes, P);
+    if (bad >= 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
+                                        ": lengths must lie in 0 .. n_voice_samples");
+    L = ScoreLaunch();
+    L.w_lo = (uint64_t)P.w_lo;
+    L.w_hi = (uint64_t)P.w_hi;
+    L.block_shift = P.block_shift;
+    L.first_block = P.first_block;
+    L.any = P.n_entries() > 0;
+    if (L.any) {
+        L.n_voices = n;
+        L.n_block_first = P.block_first.size();
+        L.at = dusp::score_plan_pack(P, ctx->h_score_plan);
+    }
+    return DUSP_OK;
+}
+
+// the image to the device, ordered on `stream` behind the last launch that read the buffer (whatever stream that one ran on)
+static int score_image_upload(dusp_ctx *ctx, hipStream_t stream) {
+    const size_t n_bytes = ctx->h_score_plan.size();
+    if (!n_bytes) return DUSP_OK;
+    if (n_bytes > ctx->score_plan_cap) {
+        if (ctx->d_score_plan) HIP_TRY(ctx, hipFree(ctx->d_score_plan));  // (waits for the device: no launch is reading it any more)
+        ctx->d_score_plan = nullptr;
+        ctx->score_plan_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_score_plan, n_bytes + g_guard_bytes));
+        if (g_guard_bytes) HIP_TRY(ctx, hipMemset(ctx->d_score_plan + n_bytes, kGuardPattern, g_guard_bytes));
+        ctx->score_plan_cap = n_bytes;
+    }
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->score_done, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->score_up0, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_score_plan, ctx->h_score_plan.data(), n_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->score_uploaded, stream));
+    return DUSP_OK;
+}
+
+static int score_launch(dusp_ctx *ctx, const ScoreLaunch &L, const float *d_planar, size_t n_channels, size_t n_voice, size_t n_total, const float *d_gains,
+                        const float *d_init, int raw, float *d_out, hipStream_t stream) {
+    if (L.w_hi <= L.w_lo) return DUSP_OK;
+    const dusp::ScoreVoice *d_voices = L.any ? (const dusp::ScoreVoice *)(ctx->d_score_plan + L.at) : nullptr;
+    const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices) : nullptr;
+    HIP_TRY(ctx, dusp::launch_score(d_planar, d_gains, d_voices, d_block_first, L.any ? d_block_first + L.n_block_first : nullptr, d_init, d_out, (uint32_t)n_channels, n_voice,
+                                    n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
+    if (L.any) HIP_TRY(ctx, hipEventRecord(ctx->score_done, stream));
+    return DUSP_OK;
+}
+
+static bool score_plan_intact(dusp_ctx *ctx) { return !ctx->d_score_plan || !g_guard_bytes || guard_intact(ctx->d_score_plan + ctx->score_plan_cap); }
+
+int dusp_score_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_voice_samples, const int64_t *h_onsets,
+                      const int64_t *h_lengths, const float *d_gains, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    return guarded(ctx->err, "dusp_score_device", [&]() -> int {
+    if (!d_out || (n_instances && (!d_planar || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: NULL buffer");
+    if (!channels_in_range(n_channels) || n_instances > (1u << 24) || !samples_in_range(n_voice_samples) || !samples_in_range(n_total_samples))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: need 1..64 channels, 0..2^24 instances, 1..2^31 samples a voice and 1..2^31 samples of timeline");
+    if (n_channels * n_total_samples > dusp::kScoreRowMax)  // (one lane per float of the timeline: the grid, and the kernel's 32-bit sample positions)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
+    if (n_channels * n_voice_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: channels x voice samples must not exceed 2^31");
+    if ((((uintptr_t)d_planar | (uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    ScoreLaunch L;
+    L.w_hi = n_total_samples;  // (no voices: `|| 0`, or a copy, of d_init alone)
+    if (n_instances) {
+        if (int rc = score_image_begin(ctx)) return rc;
+        const auto t_plan = std::chrono::steady_clock::now();
+        if (int rc = score_image_add(ctx, "dusp_score_device", h_onsets, h_lengths, n_instances, 0, n_voice_samples, n_total_samples, /*whole_timeline=*/true,
+                                     score_plan_budget(ctx), L))
+            return rc;
+        ctx->score_plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan).count();
+        if (int rc = score_image_upload(ctx, stream)) return rc;
+    } else {
+        if (!ctx->score_t0) {  // (no plan, but the launch is timed like any other)
+            if (int rc = score_image_begin(ctx)) return rc;
+        }
+        ctx->score_plan_ms = 0;
+    }
+    ctx->score_timed = false;
+    ctx->score_upload_timed = L.any;
+    HIP_TRY(ctx, hipEventRecord(ctx->score_t0, stream));
+    if (int rc = score_launch(ctx, L, d_planar, n_channels, n_voice_samples, n_total_samples, d_gains, d_init, raw != 0, d_out, stream)) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->score_t1, stream));
+    ctx->score_timed = true;
+    return DUSP_OK;
+    });
+}
+
+int dusp_score_last_ms(dusp_ctx *ctx, float *kernel_ms, float *plan_ms, float *upload_ms) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (!ctx->score_timed) CTX_FAIL(ctx, DUSP_ERR_STATE, "dusp_score_last_ms: no dusp_score_device call has been launched on this context");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->score_t1));
+    float k = 0, u = 0;
+    HIP_TRY(ctx, hipEventElapsedTime(&k, ctx->score_t0, ctx->score_t1));
+    if (ctx->score_upload_timed) HIP_TRY(ctx, hipEventElapsedTime(&u, ctx->score_up0, ctx->score_uploaded));
+    if (kernel_ms) *kernel_ms = k;
+    if (plan_ms) *plan_ms = (float)ctx->score_plan_ms;
+    if (upload_ms) *upload_ms = u;
+    return DUSP_OK;
+}
+
+int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voice_samples, size_t n_total_samples, const float *h_params, const float *h_gains,
+                           const int64_t *h_onsets, const int64_t *h_lengths, size_t tile_instances, int format, int normalise, void *h_out, float *h_peak) {
+    if (!prog) return DUSP_ERR_ARG;
+    dusp_ctx *ctx = prog->ctx;
+    return guarded(ctx->err, "dusp_render_host_score", [&]() -> int {
+    const size_t n_ch = prog->P.out_bufs.size();
+    if (!h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_score: h_onsets is NULL");
+    if (!samples_in_range(n_total_samples) || n_ch * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_score: the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
+    size_t tile = 0;  // (sized over the VOICE's row: the tile holds voices, the timeline is one row beside it)
+    if (int rc = tiled_batch_prepare(prog, "dusp_render_host_score", n_instances, n_voice_samples, h_params, h_gains, tile_instances, format, normalise, h_out, &tile))
+        return rc;
+    // every tile's plan, over the tile's union window, made and uploaded once: the tiles queue up on the stream without the host waiting
+    // (the byte budget is the CALL's, shared out over the tiles: a tile whose lists do not fit its share doubles its block.  What no block
+    // size takes away is 28 bytes a voice — its record, one list entry, one block_first word — and 40 a tile)
+    std::vector<ScoreLaunch> launches((n_instances + tile - 1) / tile);
+    const size_t tile_budget = score_plan_budget(ctx) / launches.size();
+    if (int rc = score_image_begin(ctx)) return rc;
+    const auto t_plan = std::chrono::steady_clock::now();
+    for (size_t lo = 0, i = 0; lo < n_instances; lo += tile, i++)
+        if (int rc = score_image_add(ctx, "dusp_render_host_score", h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, std::min(tile, n_instances - lo), lo, n_voice_samples,
+                                     n_total_samples, /*whole_timeline=*/false, tile_budget, launches[i]))
+            return rc;
+    if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: what the plans cost the host)
+        fprintf(stderr, "[dusp host score] %zu plans (tiles of %zu voices) in %.0f us on the host: %zu bytes, blocks of %u samples in the first tile\n", launches.size(), tile,
+                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count(), ctx->h_score_plan.size(), 1u << launches[0].block_shift);
+    HIP_TRY(ctx, prog->d_mix.ensure(n_ch * n_total_samples));  // the timeline's running sums
+    if (int rc = score_image_upload(ctx, ctx->stream)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(prog->d_mix.p, 0, n_ch * n_total_samples * sizeof(float), ctx->stream));
+    TiledBatch whole(prog, n_instances, h_params, h_gains, tile);
+    for (size_t lo = 0, i = 0; lo < n_instances; lo += tile, i++) {
+        if (launches[i].w_hi <= launches[i].w_lo) continue;  // (no voice of the tile reaches the timeline: nothing to render)
+        if (int rc = whole.render_tile(lo, std::min(tile, n_instances - lo), n_voice_samples)) return rc;
+        if (int rc = score_launch(ctx, launches[i], prog->d_host_out.p, n_ch, n_voice_samples, n_total_samples, h_gains ? prog->d_mix_gains.p : nullptr, prog->d_mix.p,
+                                  /*raw=*/1, prog->d_mix.p, ctx->stream))
+            return rc;
+    }
+    ScoreLaunch all;  // `|| 0` over the whole timeline
+    all.w_hi = n_total_samples;
+    if (int rc = score_launch(ctx, all, nullptr, n_ch, n_voice_samples, n_total_samples, nullptr, prog->d_mix.p, /*raw=*/0, prog->d_mix.p, ctx->stream)) return rc;
+    if (int rc = deliver_host(prog, prog->d_mix.p, nullptr, 1, n_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
+    whole.staged = false;  // (the delivery has waited for the stream)
+    if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, "dusp_render_host_score: the score kernel wrote past the end of a device buffer: guard bytes overwritten");
     return DUSP_OK;
     });
 }

@@ -4,7 +4,7 @@
 //   abi_program.hip     build / continue / destroy, program info, state download
 //   abi_render.hip      device renders: one step per engine
 //   abi_render_jit.hip  ... the render on a compiled circuit kernel
-//   abi_deliver.hip     interleave / peak / encode / mix, host renders and their delivery
+//   abi_deliver.hip     interleave / peak / encode / mix / score, host renders and their delivery
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +25,7 @@
 #include "fused_plan.hpp"
 #include "jit_codegen.hpp"
 #include "program.hpp"
+#include "score_plan.hpp"
 
 namespace dusp {
 hipError_t launch_chunk_engine(const ChunkArgs &a, hipStream_t stream);
@@ -41,6 +42,9 @@ hipError_t launch_pcm_encode(const float *d_planar, const float *d_peaks, int fo
 uint64_t pcm_encode_tiles(uint64_t n_instances, uint32_t n_channels, uint64_t n_samples, int format);
 hipError_t launch_mix(const float *d_planar, const float *d_gains, const float *d_init, float *d_out, uint64_t row_len, uint32_t n_inst, int raw, int n_cus,
                       int width_knob, int depth_knob, hipStream_t stream);
+hipError_t launch_score(const float *d_planar, const float *d_gains, const ScoreVoice *d_voices, const uint32_t *d_block_first, const uint32_t *d_entries,
+                        const float *d_init, float *d_out, uint32_t n_channels, uint64_t n_voice, uint64_t n_total, uint64_t w_lo, uint64_t w_hi,
+                        uint32_t block_shift, uint64_t first_block, int raw, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -75,6 +79,18 @@ struct dusp_ctx {
     // (closed forms, antisymmetry, the LDS image's table), so a program's generated text is dropped when this has moved on
     uint64_t table_generation = 0;
     bool tables_guarded = false;
+    // the plans of score launches (score_plan.hpp), as the device reads them: one image per call, built in h_score_plan and uploaded into
+    // d_score_plan on the call's stream.  score_uploaded: the last upload has read h_score_plan (waited for before the next call rewrites
+    // it); score_done: the last launch has read d_score_plan (the next call's stream waits for it before the upload overwrites it)
+    std::vector<unsigned char> h_score_plan;
+    unsigned char *d_score_plan = nullptr;
+    size_t score_plan_cap = 0;
+    hipEvent_t score_uploaded = nullptr, score_done = nullptr;
+    // the last dusp_score_device call, for dusp_score_last_ms: events around its plan upload (score_up0 .. score_uploaded) and around its
+    // launch (score_t0 .. score_t1), and what its plan took on the host
+    hipEvent_t score_up0 = nullptr, score_t0 = nullptr, score_t1 = nullptr;
+    double score_plan_ms = 0;
+    bool score_timed = false, score_upload_timed = false;
 };
 
 // DUSP_GUARD=1 (tests): every device allocation of the library carries guard bytes behind its end, filled with a pattern and

@@ -229,7 +229,7 @@ int dusp_state_download(dusp_program *prog, size_t instance, size_t unit, double
     dusp_ctx *ctx = prog->ctx;
     return guarded(ctx->err, "dusp_state_download", [&]() -> int {
     if (!prog->rendered) CTX_FAIL(ctx, DUSP_ERR_STATE, "dusp_state_download: nothing has been rendered yet");
-    if (prog->mixed) CTX_FAIL(ctx, DUSP_ERR_STATE, "dusp_state_download: the last render was a mix (dusp_render_host_mix): unit state describes its last tile only");
+    if (prog->mixed) CTX_FAIL(ctx, DUSP_ERR_STATE, "dusp_state_download: the last render was a mix (dusp_render_host_mix, dusp_render_host_score): unit state describes its last tile only");
     const dusp::Graph &g = prog->P.g;
     if (unit >= g.units.size() || instance >= prog->last_n_inst || !out)
         CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_state_download: unit / instance out of range");

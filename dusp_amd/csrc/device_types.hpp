@@ -79,6 +79,7 @@ struct Knobs {
     int mix_width = 0;           // DUSP_MIX_WIDTH=1 | 4 (measurements, tests): the mix kernel with one float a lane everywhere / four wherever 16-byte accesses are possible (0: by grid size, launch_mix)
     int mix_depth = 0;           // DUSP_MIX_DEPTH=8 | 32 (measurements): rows a lane of the mix kernel's dword form keeps in flight (0: 32 only where the grid cannot fill the chip)
     int mix_tile_mb = 0;         // DUSP_MIX_TILE_MB=n (measurements): dusp_render_host_mix sizes its default tile for n MiB of PCM (0: the batch that fills the chip, within kMixTileBytes)
+    int score_plan_kb = 0;       // DUSP_SCORE_PLAN_KB=n (measurements, tests): the byte budget of a score launch's plan, in KiB, instead of kScorePlanBytes (score_plan.hpp): a small one doubles the block
 };
 
 #if defined(__HIPCC__)

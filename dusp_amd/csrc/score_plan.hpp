@@ -1,0 +1,123 @@
+// score_plan.hpp — the plan of a score launch (score_engine.hip): which voices of a tile a block of the timeline has to look at.  Plain data
+// in, plain data out: host code only (no HIP), checked against brute force on the CPU (tests/native/score_plan_check.cpp).
+//
+// A score places voice k — a row of n_voice samples per channel, of which the first len_k count — at sample onset_k of a timeline of
+// n_total samples (dusp_amd/mix.py score_chain is the contract).  A lane of the kernel owns one sample of the timeline and adds, in index
+// order, the voices that cover it.  Testing every voice of the tile against every sample would be n tests for a handful of hits, so the
+// timeline is cut into blocks of B samples — a power of two, at least the kScoreGroup samples one workgroup covers — and every block gets
+// the ascending list of the voices whose span, clipped to the timeline, intersects it: CSR, block_first[n_blocks + 1] into entries[].
+// A lane walks its block's list and tests only those.  The list costs 4 bytes per (voice, block) pair; B is doubled until the whole
+// plan fits the byte budget (kScorePlanBytes by default), or one block covers the window.
+//
+// All arithmetic is in int64 and nothing overflows for any int64 onset: a voice is clipped before anything is added to its onset.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace dusp {
+
+constexpr uint32_t kScoreGroupShift = 8;                    // one workgroup: 256 lanes, one sample each
+constexpr uint32_t kScoreGroup = 1u << kScoreGroupShift;
+constexpr size_t kScorePlanBytes = (size_t)16 << 20;        // what a plan may take on the device: voices + block_first + entries
+constexpr uint64_t kScoreRowMax = (uint64_t)1 << 31;        // floats in one voice's PCM, and in the timeline's (the kernel's 32-bit sample positions)
+
+// A voice as the kernel reads it: timeline samples [lo, hi) take planar[k][c][t - onset].  (lo < hi <= n_total <= 2^31, and
+// -2^31 < onset < 2^31 for every voice that is in a list; the others are never read.)
+// (16 bytes on a 16-byte boundary: one four-dword scalar load a voice)
+struct alignas(16) ScoreVoice {
+    int64_t onset;
+    uint32_t lo, hi;
+};
+// entries[] ends in this many zeros behind the last list: the kernel reads a batch of 8 indices with one wide scalar load, also where
+// fewer than 8 of them are left in the list, and masks the rest
+constexpr size_t kScoreEntryPad = 8;
+
+struct ScorePlan {
+    int64_t t_lo = 0, t_hi = 0;   // the union of the voices' clipped spans (t_lo == t_hi: no voice reaches the timeline)
+    int64_t w_lo = 0, w_hi = 0;   // the window of the timeline the plan covers: the union, or the whole timeline
+    uint32_t block_shift = kScoreGroupShift;  // B = 1 << block_shift
+    uint64_t first_block = 0;     // block_first[0] is block first_block of the timeline (w_lo >> block_shift)
+    std::vector<ScoreVoice> voices;      // [n]; lo == hi == 0 for a voice that appears nowhere
+    std::vector<uint32_t> block_first;   // [n_blocks + 1]
+    std::vector<uint32_t> entries;       // voice indices, ascending within a block; then kScoreEntryPad zeros (block_first.back() is where they begin)
+    size_t n_entries() const { return block_first.empty() ? 0 : block_first.back(); }
+    size_t n_blocks() const { return block_first.empty() ? 0 : block_first.size() - 1; }
+    size_t bytes() const { return voices.size() * sizeof(ScoreVoice) + (block_first.size() + entries.size()) * sizeof(uint32_t); }
+};
+
+// lengths: nullptr for n_voice everywhere.  whole_timeline: the plan covers [0, n_total) (a launch that writes every sample), else the
+// union window only (a raw launch in place: samples no voice of the tile reaches stay as they are).
+// Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, n_voice].
+// Needs n <= 2^32 - 1, n_voice and n_total <= kScoreRowMax.
+inline int64_t score_plan(const int64_t *onsets, const int64_t *lengths, size_t n, uint64_t n_voice, uint64_t n_total, bool whole_timeline,
+                          size_t budget_bytes, ScorePlan &P) {
+    P = ScorePlan();
+    P.voices.assign(n, ScoreVoice{0, 0u, 0u});
+    const int64_t total = (int64_t)n_total;
+    int64_t t_lo = total, t_hi = 0;
+    for (size_t k = 0; k < n; k++) {
+        const int64_t len = lengths ? lengths[k] : (int64_t)n_voice, onset = onsets[k];
+        if (len < 0 || len > (int64_t)n_voice) return (int64_t)k;
+        if (len == 0 || onset >= total || onset <= -len) continue;  // empty, behind the end, wholly in front of sample 0
+        // here -2^31 <= -len < onset < n_total <= 2^31: onset + len cannot overflow
+        const int64_t lo = std::max<int64_t>(onset, 0), hi = std::min(onset + len, total);
+        P.voices[k] = ScoreVoice{onset, (uint32_t)lo, (uint32_t)hi};
+        t_lo = std::min(t_lo, lo);
+        t_hi = std::max(t_hi, hi);
+    }
+    if (t_hi <= t_lo) t_lo = t_hi = 0;
+    P.t_lo = t_lo;
+    P.t_hi = t_hi;
+    P.w_lo = whole_timeline ? 0 : t_lo;
+    P.w_hi = whole_timeline ? total : t_hi;
+    if (P.w_hi <= P.w_lo) return -1;  // nothing to launch
+    auto blocks_of = [&](uint32_t shift, uint64_t &first, uint64_t &count, uint64_t &n_entries) {
+        first = (uint64_t)P.w_lo >> shift;
+        count = (((uint64_t)P.w_hi - 1) >> shift) - first + 1;
+        n_entries = 0;
+        for (const ScoreVoice &v : P.voices)
+            if (v.hi > v.lo) n_entries += ((uint64_t)(v.hi - 1) >> shift) - ((uint64_t)v.lo >> shift) + 1;
+    };
+    uint32_t shift = kScoreGroupShift;
+    uint64_t first, count, n_entries;
+    for (;; shift++) {
+        blocks_of(shift, first, count, n_entries);
+        const uint64_t bytes = (uint64_t)n * sizeof(ScoreVoice) + (count + 1 + n_entries + kScoreEntryPad) * sizeof(uint32_t);
+        if ((bytes <= budget_bytes && n_entries <= 0xffffffffull) || count == 1) break;
+    }
+    P.block_shift = shift;
+    P.first_block = first;
+    P.block_first.assign((size_t)count + 1, 0u);
+    for (const ScoreVoice &v : P.voices)  // counts, one place up ...
+        if (v.hi > v.lo)
+            for (uint64_t b = ((uint64_t)v.lo >> shift) - first, b1 = ((uint64_t)(v.hi - 1) >> shift) - first; b <= b1; b++) P.block_first[(size_t)b + 1]++;
+    for (size_t b = 0; b < (size_t)count; b++) P.block_first[b + 1] += P.block_first[b];  // ... become the lists' starts
+    P.entries.assign((size_t)n_entries + kScoreEntryPad, 0u);
+    std::vector<uint32_t> at(P.block_first.begin(), P.block_first.end() - 1);
+    for (size_t k = 0; k < n; k++) {  // voices in index order: every list comes out ascending
+        const ScoreVoice &v = P.voices[k];
+        if (v.hi > v.lo)
+            for (uint64_t b = ((uint64_t)v.lo >> shift) - first, b1 = ((uint64_t)(v.hi - 1) >> shift) - first; b <= b1; b++) P.entries[at[(size_t)b]++] = (uint32_t)k;
+    }
+    return -1;
+}
+
+// The plan as the device reads it, appended to `image` on a 16-byte boundary: voices, block_first, entries.  Returns the byte offset of
+// the voices; block_first follows at + n * sizeof(ScoreVoice), the entries (and their padding) behind it.
+inline size_t score_plan_pack(const ScorePlan &P, std::vector<unsigned char> &image) {
+    const size_t at = (image.size() + 15) & ~(size_t)15;
+    image.resize(at + P.bytes());
+    unsigned char *p = image.data() + at;
+    auto put = [&](const void *src, size_t n_bytes) {
+        if (n_bytes) std::copy((const unsigned char *)src, (const unsigned char *)src + n_bytes, p);
+        p += n_bytes;
+    };
+    put(P.voices.data(), P.voices.size() * sizeof(ScoreVoice));
+    put(P.block_first.data(), P.block_first.size() * sizeof(uint32_t));
+    put(P.entries.data(), P.entries.size() * sizeof(uint32_t));
+    return at;
+}
+
+}  // namespace dusp

@@ -379,6 +379,9 @@ typedef struct {
     int mix;                   /* renderMix: dusp_render_host_mix — pcm_format 0 delivers the mix as planar f32 */
     float *gains;              /* renderMix: a factor per instance, or NULL */
     size_t tile_instances;     /* renderMix: instances per tile (0: the library's default) */
+    int score;                 /* renderScore: dusp_render_host_score — a mix at per-voice onsets (n_samples is a voice's length) */
+    size_t n_total;            /* renderScore: samples of the timeline */
+    int64_t *onsets, *lengths; /* renderScore: per instance, in samples; lengths may be NULL */
     int rc;
     char err[512];
 } render_job;
@@ -392,7 +395,10 @@ static void render_execute(napi_env env, void *data) {
         j->rc = DUSP_ERR_STATE;
         snprintf(j->err, sizeof j->err, "dusp-hip: render: the program has been destroyed");
     } else {
-        if (j->mix)
+        if (j->score)
+            j->rc = dusp_render_host_score(prog, j->n_instances, j->n_samples, j->n_total, j->params, j->gains, j->onsets, j->lengths, j->tile_instances, j->pcm_format,
+                                           j->normalise, j->out, j->peaks);
+        else if (j->mix)
             j->rc = dusp_render_host_mix(prog, j->n_instances, j->n_samples, j->params, j->gains, j->tile_instances, j->pcm_format, j->normalise, j->out, j->peaks);
         else if (j->pcm_format)
             j->rc = dusp_render_host_pcm(prog, j->n_instances, j->n_samples, j->params, j->inputs, j->pcm_format, j->normalise, j->out, j->peaks);
@@ -408,6 +414,8 @@ static void job_free(render_job *j) { /* the job and the host copies it owns (no
     free(j->params);
     free(j->inputs);
     free(j->gains);
+    free(j->onsets);
+    free(j->lengths);
     free(j->peaks);
     free(j);
 }
@@ -486,19 +494,58 @@ static void render_complete(napi_env env, napi_status status, void *data) {
     job_free(j);
 }
 
-enum { CALL_RENDER = 0, CALL_PCM = 1, CALL_MIX = 2 };
+enum { CALL_RENDER = 0, CALL_PCM = 1, CALL_MIX = 2, CALL_SCORE = 3 };
+
+/* onsets / lengths of a score: a BigInt64Array, or a Float64Array of whole numbers, of n values -> a malloc'ed int64 [n].
+ * Anything else: NULL, and *why says what (a static string). */
+static int64_t *whole_samples(napi_env env, napi_value v, size_t n, const char **why) {
+    bool is = false;
+    napi_typedarray_type type;
+    napi_value ab;
+    size_t off, len = 0;
+    void *data = NULL;
+    *why = "must be a BigInt64Array, or a Float64Array of whole numbers, of nInstances values (in samples)";
+    if (napi_is_typedarray(env, v, &is) != napi_ok || !is) return NULL;
+    if (napi_get_typedarray_info(env, v, &type, &len, &data, &ab, &off) != napi_ok || (type != napi_bigint64_array && type != napi_float64_array) || len != n) return NULL;
+    int64_t *out = (int64_t *)malloc(n * sizeof(int64_t) + 1);
+    if (!out) {
+        *why = "out of host memory";
+        return NULL;
+    }
+    if (type == napi_bigint64_array) {
+        memcpy(out, data, n * sizeof(int64_t));
+        return out;
+    }
+    for (size_t i = 0; i < n; i++) {
+        const double x = ((const double *)data)[i];
+        if (!(x >= -9223372036854775808.0 && x < 9223372036854775808.0) || x != (double)(int64_t)x) { /* (NaN fails the range) */
+            free(out);
+            *why = "are in samples, whole numbers: a fraction (or what is no number) is refused";
+            return NULL;
+        }
+        out[i] = (int64_t)x;
+    }
+    return out;
+}
 
 /* render(prog, nInstances, nSamples, params | null [, interleaved [, inputs]]) -> Promise<Float32Array>
  * renderPcm(prog, nInstances, nSamples, params | null, format, normalise [, inputs]) -> Promise<{ data: Buffer, peaks: Float32Array }>
  *   (dusp_render_host_pcm: peak, gain, quantisation and interleave on the device; format DUSP_PCM_*, normalise DUSP_NORMALISE_*)
  * renderMix(prog, nInstances, nSamples, params | null, gains | null, tileInstances, format, normalise)
  *   -> Promise<Float32Array [channel][nSamples]> (format 0) or Promise<{ data: Buffer, peaks: Float32Array(1) }> (format DUSP_PCM_*)
- *   (dusp_render_host_mix: the instances rendered tile by tile and summed on the device in Sum.many's chain order) */
+ *   (dusp_render_host_mix: the instances rendered tile by tile and summed on the device in Sum.many's chain order)
+ * renderScore(prog, nInstances, nVoiceSamples, params | null, gains | null, tileInstances, format, normalise, nTotalSamples, onsets, lengths | null)
+ *   -> as renderMix, over nTotalSamples (dusp_render_host_score: instance k mixed in at sample onsets[k] of the timeline; onsets and
+ *   lengths are BigInt64Arrays, or Float64Arrays of whole numbers) */
 static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
-    napi_value argv[8];
-    size_t argc = 8;
+    napi_value argv[11];
+    size_t argc = 11;
+    const int call = kind;
+    const char *who = kind == CALL_SCORE ? "renderScore" : kind == CALL_MIX ? "renderMix" : kind == CALL_PCM ? "renderPcm" : "render";
+    char msg[256];
+    if (kind == CALL_SCORE) kind = CALL_MIX; /* a score is a mix with three more arguments (`who` keeps its name for the messages) */
     const int pcm = kind != CALL_RENDER; /* format and normalise are arguments */
-    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < (kind == CALL_MIX ? 8u : kind == CALL_PCM ? 6u : 4u)) {
+    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < (call == CALL_SCORE ? 10u : kind == CALL_MIX ? 8u : kind == CALL_PCM ? 6u : 4u)) {
         throw_string(env, "dusp-hip: wrong number of arguments");
         return NULL;
     }
@@ -510,18 +557,19 @@ static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
     if (pcm) {
         if (napi_get_value_double(env, argv[format_at], &format) != napi_ok ||
             !(format == DUSP_PCM_S16 || format == DUSP_PCM_S24 || format == DUSP_PCM_F32 || (kind == CALL_MIX && format == 0))) {
-            throw_string(env, kind == CALL_MIX ? "dusp-hip: renderMix: format must be 0 (planar f32), 1 (s16), 2 (s24) or 3 (f32)"
-                                               : "dusp-hip: renderPcm: format must be 1 (s16), 2 (s24) or 3 (f32)");
+            snprintf(msg, sizeof msg, "dusp-hip: %s: format must be %s1 (s16), 2 (s24) or 3 (f32)", who, kind == CALL_MIX ? "0 (planar f32), " : "");
+            throw_string(env, msg);
             return NULL;
         }
         if (napi_get_value_double(env, argv[format_at + 1], &normalise) != napi_ok || !(normalise == 0 || normalise == 1 || normalise == 2)) {
-            throw_string(env, kind == CALL_MIX ? "dusp-hip: renderMix: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)"
-                                               : "dusp-hip: renderPcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
+            snprintf(msg, sizeof msg, "dusp-hip: %s: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)", who);
+            throw_string(env, msg);
             return NULL;
         }
     }
     if (kind == CALL_MIX && (napi_get_value_double(env, argv[5], &tile) != napi_ok || !(tile >= 0 && tile <= 16777216.0 && tile == (double)(size_t)tile))) {
-        throw_string(env, "dusp-hip: renderMix: tileInstances must be 0 (the default tile) or a whole number of instances");
+        snprintf(msg, sizeof msg, "dusp-hip: %s: tileInstances must be 0 (the default tile) or a whole number of instances", who);
+        throw_string(env, msg);
         return NULL;
     }
     prog_box *pb = as_prog(env, argv[0]);
@@ -531,6 +579,11 @@ static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
     napi_get_value_double(env, argv[2], &n_samples);
     if (!(n_inst >= 1 && n_inst <= 16777216.0 && n_samples >= 1 && n_samples <= 2147483648.0)) {
         throw_string(env, "dusp-hip: render: nInstances / nSamples out of range");
+        return NULL;
+    }
+    double n_total = 0;
+    if (call == CALL_SCORE && (napi_get_value_double(env, argv[8], &n_total) != napi_ok || !(n_total >= 1 && n_total <= 2147483648.0 && n_total == (double)(size_t)n_total))) {
+        throw_string(env, "dusp-hip: renderScore: nTotalSamples out of range");
         return NULL;
     }
     dusp_program_info pi;
@@ -545,7 +598,10 @@ static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
     j->n_samples = (size_t)n_samples;
     j->mix = kind == CALL_MIX;
     j->tile_instances = (size_t)tile;
-    j->n_floats = (j->mix ? 1 : j->n_instances) * pi.n_out_channels * j->n_samples; /* (a mix is one instance's worth of samples) */
+    j->score = call == CALL_SCORE;
+    j->n_total = (size_t)n_total;
+    /* (a mix is one instance's worth of samples, a score one timeline's) */
+    j->n_floats = (j->mix ? 1 : j->n_instances) * pi.n_out_channels * (j->score ? j->n_total : j->n_samples);
     j->interleaved = interleaved ? 1 : 0;
     j->pcm_format = (int)format;
     j->normalise = (int)normalise;
@@ -584,7 +640,8 @@ static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
         size_t len;
         if (!typed_array(env, argv[4], napi_float32_array, &data, &len) || len != j->n_instances) {
             job_free(j);
-            throw_string(env, "dusp-hip: renderMix: gains must be a Float32Array of nInstances values");
+            snprintf(msg, sizeof msg, "dusp-hip: %s: gains must be a Float32Array of nInstances values", who);
+            throw_string(env, msg);
             return NULL;
         }
         j->gains = (float *)malloc(len * sizeof(float));
@@ -595,8 +652,26 @@ static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
         }
         memcpy(j->gains, data, len * sizeof(float));
     }
-    if (argc > inputs_at) napi_typeof(env, argv[inputs_at], &vt);
-    if (argc > inputs_at && vt != napi_null && vt != napi_undefined) { /* inputs: Float32Array of nInputs * nInstances * nSamples values */
+    if (j->score) {
+        const char *why = NULL;
+        if (!(j->onsets = whole_samples(env, argv[9], j->n_instances, &why))) {
+            snprintf(msg, sizeof msg, "dusp-hip: renderScore: onsets %s", why);
+            job_free(j);
+            throw_string(env, msg);
+            return NULL;
+        }
+        vt = napi_undefined;
+        if (argc > 10) napi_typeof(env, argv[10], &vt);
+        if (vt != napi_null && vt != napi_undefined && !(j->lengths = whole_samples(env, argv[10], j->n_instances, &why))) {
+            snprintf(msg, sizeof msg, "dusp-hip: renderScore: lengths %s", why);
+            job_free(j);
+            throw_string(env, msg);
+            return NULL;
+        }
+    }
+    const int has_inputs_arg = !j->score && argc > inputs_at; /* (a score's further arguments are not input streams) */
+    if (has_inputs_arg) napi_typeof(env, argv[inputs_at], &vt);
+    if (has_inputs_arg && vt != napi_null && vt != napi_undefined) { /* inputs: Float32Array of nInputs * nInstances * nSamples values */
         void *data;
         size_t len;
         if (!typed_array(env, argv[inputs_at], napi_float32_array, &data, &len) || len != (size_t)pi.n_inputs * j->n_instances * j->n_samples || !len) {
@@ -659,6 +734,7 @@ static napi_value render_call(napi_env env, napi_callback_info info, int kind) {
 static napi_value fn_render(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_RENDER); }
 static napi_value fn_render_pcm(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_PCM); }
 static napi_value fn_render_mix(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_MIX); }
+static napi_value fn_render_score(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_SCORE); }
 
 static napi_value init(napi_env env, napi_value exports) {
     static const struct {
@@ -669,7 +745,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ctxDestroy", fn_ctx_destroy},   {"tableUpload", fn_table_upload},   {"programBuild", fn_program_build},
         {"programDestroy", fn_program_destroy}, {"programInfo", fn_program_info}, {"stateDownload", fn_state_download},
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
-        {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},
+        {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -16,6 +16,9 @@ module.exports = {
   renderMix: renderChannelData.renderMix,
   renderMixPcm: renderChannelData.renderMixPcm,
   renderMixWav: renderChannelData.renderMixWav,
+  renderScore: renderChannelData.renderScore,
+  renderScorePcm: renderChannelData.renderScorePcm,
+  renderScoreWav: renderChannelData.renderScoreWav,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

@@ -375,9 +375,17 @@ async function renderMany(outlets, duration = 1, { engine = 0, devices } = {}) {
  * downloads every voice.  One device.  A voice sample that is NaN drops that voice out of the sample (the reference's Sum would zero
  * the mix sample there).  Resolves to channelData like renderChannelData; circuits with scheduled events or host-ticked units are
  * refused as renderMany refuses them. */
-async function mixCall(who, outlets, duration, { gains, engine = 0, tileInstances = 0 }, format, normalise) {
+async function mixCall(who, outlets, duration, opts, format, normalise, score = false) {
+  const { gains, engine = 0, tileInstances = 0 } = opts
   const uni = unifyBatch(outlets, who)
-  const nSamples = sampleCount(duration, uni.sampleRate)
+  const nSamples = sampleCount(duration, uni.sampleRate) // (of a score: the timeline's)
+  let nVoiceSamples = 0, onsets = null, lengths = null
+  if (score) {
+    nVoiceSamples = sampleCount(opts.voiceDuration === undefined ? 1 : opts.voiceDuration, uni.sampleRate)
+    if (nVoiceSamples === 0) throw 'dusp-hip: ' + who + ': voiceDuration must cover at least one sample'
+    onsets = wholeSamples(who, 'onsets', opts.onsets, uni.nInstances)
+    if (opts.lengths !== undefined && opts.lengths !== null) lengths = wholeSamples(who, 'lengths', opts.lengths, uni.nInstances)
+  }
   let g = null
   if (gains !== undefined && gains !== null) {
     g = gains instanceof Float32Array ? gains : Float32Array.from(gains)
@@ -389,7 +397,10 @@ async function mixCall(who, outlets, duration, { gains, engine = 0, tileInstance
   try {
     const nChannels = n.programInfo(prog).nOutChannels
     if (nSamples === 0) return { nSamples, nChannels, sampleRate: uni.sampleRate, result: null }
-    const result = await n.renderMix(prog, uni.nInstances, nSamples, uni.nParams ? uni.params : null, g, tileInstances, format, normalise)
+    const params = uni.nParams ? uni.params : null
+    const result = score
+      ? await n.renderScore(prog, uni.nInstances, nVoiceSamples, params, g, tileInstances, format, normalise, nSamples, onsets, lengths)
+      : await n.renderMix(prog, uni.nInstances, nSamples, params, g, tileInstances, format, normalise)
     return { nSamples, nChannels, sampleRate: uni.sampleRate, result }
   } finally {
     n.programDestroy(prog)
@@ -416,6 +427,45 @@ async function renderMixPcm(outlets, duration = 1, opts = {}) {
 
 async function renderMixWav(outlets, duration = 1, opts = {}) {
   return encodeWav(await renderMixPcm(outlets, duration, opts))
+}
+
+/* onsets / lengths of a score, one per outlet, in SAMPLES: a BigInt64Array, a Float64Array or an array of whole numbers (the addon
+ * refuses a fraction) */
+function wholeSamples(who, name, values, count) {
+  let a = values
+  if (Array.isArray(a)) a = a.length && typeof a[0] === 'bigint' ? BigInt64Array.from(a) : Float64Array.from(a)
+  if (!(a instanceof BigInt64Array) && !(a instanceof Float64Array)) throw 'dusp-hip: ' + who + ': ' + name + ' must be a BigInt64Array, a Float64Array or an array of whole numbers (in samples)'
+  if (a.length !== count) throw 'dusp-hip: ' + who + ': ' + name + ' must hold one value per outlet'
+  if (a instanceof Float64Array && !a.every(Number.isInteger)) throw 'dusp-hip: ' + who + ': ' + name + ' are in samples, whole numbers: a fraction is refused'
+  return a
+}
+
+/* A PIECE of N structurally identical circuits: voice k starts at sample onsets[k] of a timeline of `duration` seconds — what
+ * renderChannelData(Sum.many(outlets.map((v, k) => new Delay(v, onsets[k], maxDelay))), duration) computes (a Delay by whole samples
+ * is its input behind zeros; the voice with onset 0 bare) — rendered as ONE program for `voiceDuration` seconds a voice, tile by tile,
+ * and mixed ON THE DEVICE at the onsets in Sum.many's chain order (dusp_render_host_score).  onsets and lengths are in samples, whole
+ * numbers of any sign (a negative onset: the voice began before the timeline; lengths clip a voice to its first samples); the
+ * durations are in seconds.  gains, engine, tileInstances and the refusals are renderMix's. */
+async function renderScore(outlets, opts = {}) {
+  const { duration = 1 } = opts
+  const { nSamples, nChannels, sampleRate, result } = await mixCall('renderScore', outlets, duration, opts, 0, 0, true)
+  const channelData = []
+  channelData.sampleRate = sampleRate
+  if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
+  return channelData
+}
+
+async function renderScorePcm(outlets, opts = {}) {
+  const { duration = 1, bitDepth = 16, normalise = 0 } = opts
+  if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderScorePcm: bitDepth must be 16, 24 or 32'
+  if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderScorePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
+  const { nChannels, sampleRate, result } = await mixCall('renderScorePcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise, true)
+  if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
+  return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
+}
+
+async function renderScoreWav(outlets, opts = {}) {
+  return encodeWav(await renderScorePcm(outlets, opts))
 }
 
 /* A flat descriptor (what lib/extract.js produces — from this package's graph classes or from the reference's own objects,
@@ -446,6 +496,9 @@ module.exports.renderWav = renderWav
 module.exports.renderMix = renderMix
 module.exports.renderMixPcm = renderMixPcm
 module.exports.renderMixWav = renderMixWav
+module.exports.renderScore = renderScore
+module.exports.renderScorePcm = renderScorePcm
+module.exports.renderScoreWav = renderScoreWav
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

@@ -37,3 +37,66 @@ def mix_chain(planar, gains=None, init=None, raw=False):
         if not raw:
             acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
     return acc
+
+
+def score_chain(planar, onsets, n_total, lengths=None, gains=None, init=None, raw=False):
+    """planar float32 [instances, channels, voice samples], onsets int64 [instances] -> float32 [channels, n_total]: the contract of
+    dusp_score_device.  Voice k lies on the timeline at samples onset_k .. onset_k + len_k - 1 (any sign; lengths None: the whole row);
+    for every channel c and timeline sample t
+
+        acc = init[c][t] if init is given else +0
+        for k in index order:  s = t - onset_k;  if 0 <= s < len_k:  acc = f32(acc + term_k),
+                               term_k = f32(planar[k][c][s] * gains[k]) if gains is given else planar[k][c][s]
+        out[c][t] = acc if raw else (acc || 0)
+
+    A voice takes no part in a sample outside its span: nothing is added there, not even a zero, so a raw partial sum continued through
+    `init` is the same chain wherever it is cut (tiles of voices, windows of the timeline with their onsets shifted).  Unlike mix_chain
+    the chain starts from +0, not from the first voice itself: a lone -0 sample leaves a raw chain as +0.  It is what the reference's
+    `Sum.many(Delay(voice_k, onset_k, maxDelay))` renders (Delay.js:27-38: an integer delay is the input shifted behind zeros)."""
+    planar = np.asarray(planar, dtype=np.float32)
+    if planar.ndim != 3:
+        raise ValueError("dusp-hip: planar must have shape (instances, channels, samples)")
+    n_inst, n_ch, n_voice = planar.shape
+    if int(n_total) != n_total or n_total < 0:
+        raise ValueError("dusp-hip: n_total must be a whole number of samples, not negative")
+    n_total = int(n_total)
+
+    def whole(values, name):
+        a = np.asarray(values)
+        if a.shape != (n_inst,):
+            raise ValueError("dusp-hip: %s must have shape (instances=%d,)" % (name, n_inst))
+        if a.dtype.kind not in "iu":
+            if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
+                raise ValueError("dusp-hip: %s are whole numbers of samples" % name)
+        return a.astype(np.int64)
+
+    onsets = whole(onsets, "onsets")
+    if lengths is None:
+        lengths = np.full(n_inst, n_voice, dtype=np.int64)
+    else:
+        lengths = whole(lengths, "lengths")
+        if np.any(lengths < 0) or np.any(lengths > n_voice):
+            raise ValueError("dusp-hip: lengths must lie in 0 .. samples=%d" % n_voice)
+    if gains is not None:
+        gains = np.asarray(gains, dtype=np.float32)
+        if gains.shape != (n_inst,):
+            raise ValueError("dusp-hip: gains must have shape (instances=%d,)" % n_inst)
+    if init is not None:
+        init = np.asarray(init, dtype=np.float32)
+        if init.shape != (n_ch, n_total):
+            raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
+    with np.errstate(all="ignore"):
+        acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
+        for k in range(n_inst):
+            onset, length = int(onsets[k]), int(lengths[k])
+            t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
+            if t1 <= t0:
+                continue
+            term = planar[k, :, t0 - onset:t1 - onset]
+            if gains is not None:
+                term = term * gains[k]  # float32 * float32 scalar: one f32 rounding
+            acc[:, t0:t1] = acc[:, t0:t1] + term  # float32 + float32: one f32 rounding
+        assert acc.dtype == np.float32
+        if not raw:
+            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
+    return acc

@@ -194,6 +194,69 @@ def render_mix_wav(outlets, duration=1, bit_depth=16, normalise=0, gains=None, e
     return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
 
 
+def _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device):
+    """-> unified voices, samples a voice, samples of timeline, onsets, lengths, gains (checked, whatever the durations), program"""
+    uni = descriptor.unify([descriptor.extract(o) for o in outlets])
+    n_voice, n_total = _n_samples(voice_duration, uni.sample_rate), _n_samples(duration, uni.sample_rate)
+    if n_voice == 0:
+        raise descriptor.DuspError("dusp-hip: voice_duration must cover at least one sample")
+    onsets = runtime._whole_samples(onsets, uni.n_instances, "onsets")
+    if lengths is not None:
+        lengths = runtime._whole_samples(lengths, uni.n_instances, "lengths")
+        if np.any(lengths < 0) or np.any(lengths > n_voice):
+            raise ValueError("dusp-hip: lengths must lie in 0 .. the voice's %d samples" % n_voice)
+    if gains is not None:
+        gains = np.ascontiguousarray(gains, dtype=np.float32)
+        if gains.shape != (uni.n_instances,):
+            raise ValueError("dusp-hip: gains must have shape (n_instances=%d,)" % uni.n_instances)
+    return uni, n_voice, n_total, onsets, lengths, gains, context(uni.sample_rate, device).build(uni.words, engine)
+
+
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0):
+    """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
+    `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
+    zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
+    tiles, and mixed on the device at the onsets (Program.render_score; mix.score_chain is the contract).  onsets and lengths are in
+    SAMPLES, whole numbers of any sign (lengths clip a voice to its first len_k samples); the durations are in seconds.  A voice_duration
+    of no samples is refused, and onsets, lengths and gains are checked whatever the durations."""
+    uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
+    result = ChannelData()
+    result.sampleRate = uni.sample_rate
+    try:
+        if n_total > 0:
+            result.extend(prog.render_score(n_voice, n_total, uni.n_instances, onsets, lengths, uni.params, gains, tile_instances))
+    finally:
+        prog.close()
+    return result
+
+
+def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
+                     tile_instances=0):
+    """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
+    if bit_depth not in _PCM_FORMAT:
+        raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
+    if normalise not in (0, 1, 2):
+        raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
+    uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
+    try:
+        if n_total == 0:
+            data, peak = wav.encode_frames(np.zeros((prog.n_out_channels, n_total), dtype=np.float32), bit_depth, normalise)
+        else:
+            data, peak = prog.render_score(n_voice, n_total, uni.n_instances, onsets, lengths, uni.params, gains, tile_instances, _PCM_FORMAT[bit_depth], normalise)
+    finally:
+        prog.close()
+    return PcmData(data, bit_depth, uni.sample_rate, peak)
+
+
+def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
+                     tile_instances=0):
+    """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
+    pcm = render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances)
+    if bit_depth == 32:
+        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
+    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+
+
 class PcmData:
     """Encoded frames of one render: `data` int16 [samples, channels] (bitDepth 16), uint8 [samples, channels, 3] (24) or float32
     [samples, channels] (32); `peak` is the render's max |x| before the gain.  wav.encode_wav(data, sampleRate, bitDepth) makes a file of it."""

@@ -25,6 +25,7 @@ EXPORTS = [
     "dusp_last_kernel_ms", "dusp_fill_device", "dusp_render_device_inputs", "dusp_render_host_inputs",
     "dusp_host_alloc", "dusp_host_free", "dusp_circuit_kernel_source", "dusp_jit_cache_dir", "dusp_render_chain_window", "dusp_device_count",
     "dusp_peak_device", "dusp_encode_device", "dusp_render_host_pcm", "dusp_mix_device", "dusp_render_host_mix",
+    "dusp_score_device", "dusp_render_host_score", "dusp_score_last_ms",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -88,6 +89,9 @@ def load():
     L.dusp_render_host_pcm.argtypes = [vp, sz, sz, vp, vp, ci, ci, vp, vp]
     L.dusp_mix_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, ci, vp, vp]
     L.dusp_render_host_mix.argtypes = [vp, sz, sz, vp, vp, sz, ci, ci, vp, vp]
+    L.dusp_score_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, ci, vp, vp]
+    L.dusp_score_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.dusp_render_host_score.argtypes = [vp, sz, sz, sz, vp, vp, vp, vp, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -141,6 +145,17 @@ def _pcm_format(format):
             raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
         return PCM_FORMATS[format]
     return int(format)
+
+
+def _whole_samples(values, n, name):
+    """onsets / lengths of a score -> contiguous int64 [n]: in samples, whole numbers (a fraction is refused)"""
+    a = np.asarray(values)
+    if a.shape != (n,):
+        raise ValueError("dusp-hip: %s must have shape (n_instances=%d,)" % (name, n))
+    if a.dtype.kind not in "iu":
+        if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
+            raise ValueError("dusp-hip: %s are in samples, whole numbers: a fraction (or what is no number) is refused" % name)
+    return np.ascontiguousarray(a, dtype=np.int64)
 
 
 class Context:
@@ -234,6 +249,27 @@ class Context:
         (dusp_mix_device; dusp_amd/mix.py mix_chain is the contract): one f32 rounding per add, in index order, each instance first scaled by
         its f32 gain (d_gains), the chain continued from d_init (which may be d_out); raw: a partial sum, NaN and -0 kept."""
         self._check(self._L.dusp_mix_device(self._h, d_planar, n_instances, n_channels, n_samples, d_gains, d_init, int(bool(raw)), d_out, stream))
+
+    def score_device(self, d_planar, n_instances, n_channels, n_voice_samples, onsets, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None,
+                     raw=False, stream=None):
+        """Device pointers: planar f32 [instance][channel][voice sample] -> f32 [channel][timeline sample], the instances mixed in Sum.many's
+        chain order with instance k at timeline sample onsets[k] (dusp_score_device; dusp_amd/mix.py score_chain is the contract).  onsets
+        and lengths are HOST arrays of whole numbers of samples (any sign; lengths in 0 .. n_voice_samples, None: whole voices): the
+        launch's plan is made on the host.  d_gains, d_init (which may be d_out) and raw as for mix()."""
+        onsets = _whole_samples(onsets, n_instances, "onsets")
+        lp = None
+        if lengths is not None:
+            lengths = _whole_samples(lengths, n_instances, "lengths")
+            lp = lengths.ctypes.data
+        self._check(self._L.dusp_score_device(self._h, d_planar, n_instances, n_channels, n_voice_samples, onsets.ctypes.data if n_instances else None, lp, d_gains,
+                                              n_total_samples, d_init, int(bool(raw)), d_out, stream))
+
+    def score_last_ms(self):
+        """-> (kernel_ms, plan_ms, upload_ms) of the most recent score_device call (dusp_score_last_ms; waits for that launch): the kernel
+        alone by HIP events, the plan on the host's clock, the plan's upload by events."""
+        k, p, u = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._check(self._L.dusp_score_last_ms(self._h, ctypes.byref(k), ctypes.byref(p), ctypes.byref(u)))
+        return k.value, p.value, u.value
 
     def fill(self, d_ptr, n_floats, value=0.0, stream=None):
         self._check(self._L.dusp_fill_device(self._h, d_ptr, n_floats, value, stream))
@@ -369,6 +405,47 @@ class Program:
         out = self.ctx.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
         peak = np.empty(1, dtype=np.float32)
         self.ctx._check(self._L.dusp_render_host_mix(self._h, n_instances, n_samples, pp, gp, int(tile_instances), fmt, int(normalise), out.ctypes.data, peak.ctypes.data))
+        return out, peak[0]
+
+    def render_score(self, n_voice_samples, n_total_samples, n_instances, onsets, lengths=None, params=None, gains=None, tile_instances=0, format=None,
+                     normalise=NORMALISE_NONE, pinned=None):
+        """Host round trip that delivers a SCORE (dusp_render_host_score): the instances are rendered for n_voice_samples each, tile by
+        tile as render_mix renders them, and mixed on the device into a timeline of n_total_samples with instance k at sample onsets[k]
+        — bit for bit mix.score_chain over what render() gives on the circuit's compiled kernel.  onsets, lengths: whole numbers of
+        samples (onsets of any sign; lengths in 0 .. n_voice_samples clip a voice, None: whole voices).  gains, tile_instances, format,
+        normalise and what is returned: as render_mix, over the timeline."""
+        onsets = _whole_samples(onsets, n_instances, "onsets")
+        pp = gp = lp = None
+        if lengths is not None:
+            lengths = _whole_samples(lengths, n_instances, "lengths")
+            lp = lengths.ctypes.data
+        if self.n_params:
+            params = np.ascontiguousarray(params, dtype=np.float32)
+            if params.shape != (self.n_params, n_instances):
+                raise ValueError("params must have shape (n_params=%d, n_instances=%d)" % (self.n_params, n_instances))
+            pp = params.ctypes.data
+        if gains is not None:
+            gains = np.ascontiguousarray(gains, dtype=np.float32)
+            if gains.shape != (n_instances,):
+                raise ValueError("dusp-hip: gains must have shape (n_instances=%d,)" % n_instances)
+            gp = gains.ctypes.data
+        if int(tile_instances) < 0:
+            raise ValueError("dusp-hip: tile_instances must be 0 (the default tile) or at least 1")
+        call = self._L.dusp_render_host_score
+        if format is None:
+            out = self.ctx.host_empty((self.n_out_channels, n_total_samples), pinned)
+            self.ctx._check(call(self._h, n_instances, n_voice_samples, n_total_samples, pp, gp, onsets.ctypes.data, lp, int(tile_instances), 0, 0, out.ctypes.data, None))
+            return out
+        fmt = _pcm_format(format)
+        if fmt not in PCM_BYTES:
+            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
+        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
+            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
+        shape = (n_total_samples, self.n_out_channels)
+        out = self.ctx.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
+        peak = np.empty(1, dtype=np.float32)
+        self.ctx._check(call(self._h, n_instances, n_voice_samples, n_total_samples, pp, gp, onsets.ctypes.data, lp, int(tile_instances), fmt, int(normalise),
+                             out.ctypes.data, peak.ctypes.data))
         return out, peak[0]
 
     def render_device(self, n_samples, n_instances, d_params, d_out, stream=None, d_inputs=None):

@@ -304,6 +304,60 @@ int dusp_mix_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, si
 int dusp_render_host_mix(dusp_program *prog, size_t n_instances, size_t n_samples, const float *h_params, const float *h_gains,
                          size_t tile_instances, int format, int normalise, void *h_out, float *h_peak);
 
+/* A score: voices mixed at per-voice onsets into a timeline that is longer than a voice, on the device, in Sum.many's chain order
+ * (additions to ABI v7: DUSP_ABI_VERSION is unchanged, a binder detects them by symbol).  Replaces
+ * `Sum.many(voices.map((v, k) => new Delay(v, onset_k, maxDelay)))` as the thing that places rendered notes on a timeline: a Delay by
+ * a whole number of samples is its input behind zeros (src/components/Delay.js:27-38), and the Sum chain adds in index order with one
+ * f32 rounding per add.  Voice k covers the timeline samples onset_k .. onset_k + len_k - 1; for every channel c and timeline sample t
+ *     acc = d_init ? d_init[c][t] : +0
+ *     for k = 0 .. n_instances - 1:   s = t - onset_k;   if (0 <= s < len_k)  acc = (float)(acc + term_k)
+ *     term_k = d_gains ? (float)(d_planar[k][c][s] * g_k) : d_planar[k][c][s]      (a plain f32 product, then a plain f32 add)
+ *     d_out[c][t] = raw ? acc : (acc || 0)
+ * A voice takes no part in a sample outside its span: nothing is added there, not even a zero.  A raw partial sum continued through
+ * d_init is therefore the same chain wherever it is cut: tiles of voices, windows of the timeline (with the onsets shifted, negative
+ * ones included), other devices.  Unlike dusp_mix_device's, the chain starts from +0 and NOT from the first voice itself: a -0 sample
+ * alone on a raw timeline sample gives +0.  (Against zero-padded rows under dusp_mix_device that is the only difference, and none
+ * after `|| 0`.)
+ *   d_planar          f32 [n_instances][n_channels][n_voice_samples], as the render calls write it
+ *   h_onsets          int64 [n_instances], in samples, any sign: a negative onset is a voice that began before the timeline.  HOST memory:
+ *                     the launch's plan (which voices a block of the timeline looks at) is made on the host, and both arrays have been
+ *                     read when the call returns
+ *   h_lengths         int64 [n_instances], 0 <= len_k <= n_voice_samples, HOST memory; NULL: every voice counts whole
+ *   d_gains           f32 [n_instances], or NULL
+ *   d_init, d_out     f32 [n_channels][n_total_samples]; d_init may be NULL, and may be d_out (in place); d_planar must not overlap d_out
+ *   raw               as for dusp_mix_device
+ * n_instances = 0 is legal: the `|| 0` pass (or, raw, a copy) over d_init alone.  Any 4-byte alignment, any sizes with
+ * n_channels * n_total_samples and n_channels * n_voice_samples at most 2^31; coalesced dword accesses.  DUSP_ERR_ARG, with a message,
+ * for NULL or misaligned buffers, sizes out of range and a length outside 0 .. n_voice_samples.  The plan is uploaded into a buffer
+ * that lives with the context and the launch is asynchronous on `stream`; a call may wait for the previous call's plan to have been
+ * uploaded.  The NaN divergence of dusp_mix_device applies unchanged; and an infinite voice sample stays infinite here, where the
+ * reference's Delay makes NaN of it (inf * 0 in its second tap). */
+int dusp_score_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_voice_samples,
+                      const int64_t *h_onsets, const int64_t *h_lengths, const float *d_gains, size_t n_total_samples,
+                      const float *d_init, int raw, float *d_out, void *stream);
+
+/* Where the most recent dusp_score_device call on this context spent its time (synchronises with that launch): the kernel alone, by
+ * HIP events around the launch on its stream; the plan on the host's clock (made before the call returned); and the plan's upload, by
+ * events around the copy (0 when no voice reached the timeline: nothing was uploaded).  Any pointer may be NULL.  DUSP_ERR_STATE
+ * before the first dusp_score_device call.  Not for two threads at once on one context, like every call on a context. */
+int dusp_score_last_ms(dusp_ctx *ctx, float *kernel_ms, float *plan_ms, float *upload_ms);
+
+/* Render n_instances instances for n_voice_samples each and deliver their score over n_total_samples: the instances are rendered tile
+ * by tile, in voice order, exactly as dusp_render_host_mix renders its tiles (the same whole-batch decisions keep the tiling from
+ * changing a bit), and every tile continues the chain above, raw and in place, in one [n_out_channels][n_total_samples] accumulator
+ * that was zeroed once — over the union window of the tile's voices only, so a tile of notes bunched in time does not stream the whole
+ * timeline; a last launch without voices applies `|| 0`.  Device memory is the tile plus the timeline plus the call's plans: all tiles'
+ * plans are made up front and share ONE 16 MiB budget (a tile whose lists exceed its share takes larger blocks), beyond which only 28
+ * bytes a voice and 40 a tile remain.
+ *   h_params, h_gains, format, normalise, h_peak   as for dusp_render_host_mix
+ *   h_onsets, h_lengths                            as for dusp_score_device
+ *   tile_instances  instances per tile; 0: dusp_render_host_mix's default, sized over a voice's row
+ *   h_out           planar f32 [n_out_channels][n_total_samples], or the frames of the PCM format
+ * Refusals and the state afterwards are dusp_render_host_mix's. */
+int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voice_samples, size_t n_total_samples, const float *h_params,
+                           const float *h_gains, const int64_t *h_onsets, const int64_t *h_lengths, size_t tile_instances, int format,
+                           int normalise, void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Score rendering, measured (run by hand on the GPU; the output is kept as profiles/score_mix.txt).
+
+  dense   the score kernel with every onset 0 and full lengths — the mix, as a score — over rows of the shapes of mix_bench.py's cases
+          a-d (seeded noise: the kernels' time does not depend on the values), against dusp_mix_device over the same rows, which is the
+          yardstick, and against bytes read / the float4-copy rate.  The mix kernel by HIP events on the launch stream (its call does no
+          host work); the score kernel by the events the library records around the launch alone (dusp_score_last_ms), with the plan's
+          host time and the upload's time, which precede the launch inside the call, reported beside it.  The plan's default block and a
+          block forced to cover the whole timeline (DUSP_SCORE_PLAN_KB=1: one list for every workgroup) side by side.
+  piece   8192 notes of 0.5 s placed over 60 s in onset order: Program.render_score on the host's clock, against the render of the same
+          notes alone (render_device into a preallocated buffer) and against the same piece with the onsets shuffled — every tile's
+          union window is then the whole timeline, which is what the window is worth.  One run under DUSP_JIT_LOG=2 prints the plans'
+          host time and block (stderr).
+
+Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import dusp_amd as d  # noqa: E402
+from dusp_amd import descriptor  # noqa: E402
+from mix_bench import COPY_RATE, SR, context, timed  # noqa: E402
+
+DENSE = {"a": (8192, 10 * SR), "b": (1024, 60 * SR), "c": (16384, SR), "d": (65536, SR)}  # voices, samples (one channel)
+
+
+def dense(key, scale, ctxs, reps):
+    import torch
+    V, n = max(64, DENSE[key][0] // scale), DENSE[key][1]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    rows = torch.empty((V, 1, n), dtype=torch.float32, device="cuda").normal_()
+    acc = torch.empty((1, n), dtype=torch.float32, device="cuda")
+    onsets = np.zeros(V, dtype=np.int64)
+    torch.cuda.synchronize()
+    read = (V + 0) * n * 4
+    print("dense %s: %d rows x %d samples = %.2f GB of f32; bytes / %.2f TB/s = %.3f ms" % (key, V, n, read / 1e9, COPY_RATE / 1e12, read / COPY_RATE * 1e3), flush=True)
+    med, best = timed(lambda: ctxs["default"].mix(rows.data_ptr(), V, 1, n, acc.data_ptr(), None, None, False, s), stream, reps)
+    t_mix = med
+    line = "  %-30s kernel median %9.3f ms  fastest %9.3f   %6.2f TB/s = %4.1f%% of the copy rate   x%.3f of the mix kernel by grid%s"
+    rate = lambda ms: (read / ms / 1e9, 100 * read / ms * 1e3 / COPY_RATE, ms / t_mix)
+    print(line % (("mix kernel, by grid", med, best) + rate(med) + ("",)), flush=True)
+    med, best = timed(lambda: ctxs["dword8"].mix(rows.data_ptr(), V, 1, n, acc.data_ptr(), None, None, False, s), stream, reps)
+    print(line % (("mix kernel, 1 float x 8", med, best) + rate(med) + ("",)), flush=True)
+    # the score kernel ALONE: events around the launch inside the library (dusp_score_last_ms), behind the plan and its upload, which
+    # are host work and a copy of their own and are reported beside it
+    for label, ctx in [("score kernel, default block", ctxs["default"]), ("score kernel, one block", ctxs["one_block"])]:
+        kernel, plan, upload = [], [], []
+        for r in range(reps + 1):
+            ctx.score_device(rows.data_ptr(), V, 1, n, onsets, n, acc.data_ptr(), stream=s)
+            k, p, u = ctx.score_last_ms()
+            if r:
+                kernel.append(k), plan.append(p), upload.append(u)
+        med = float(np.median(kernel))
+        print(line % ((label, med, min(kernel)) + rate(med) + ("   [plan on the host %.2f ms, its upload %.2f ms]" % (float(np.median(plan)), float(np.median(upload))),)), flush=True)
+
+
+def piece(scale, ctxs, reps):
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
+    d.configure(SR)
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    in_order = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    shuffled = np.random.RandomState(2).permutation(in_order)
+    prog = ctxs["default"].build(uni.words)
+    stream = torch.cuda.Stream()
+    out = torch.empty((V, prog.n_out_channels, nv), dtype=torch.float32, device="cuda")
+    dp = torch.from_numpy(params).cuda()
+    torch.cuda.synchronize()
+    med, best = timed(lambda: prog.render_device(nv, V, dp.data_ptr(), out.data_ptr(), stream.cuda_stream), stream, reps)
+    print("piece: %d notes of %d samples over %d samples (%.0f MB of notes, %.1f MB of timeline), engine %s" % (V, nv, nt, V * nv * 4 / 1e6, nt * 4 / 1e6, prog.engine), flush=True)
+    print("  render of the notes alone (HIP events)         median %9.3f ms  fastest %9.3f   [%s]" % (med, best, prog.read_shape()), flush=True)
+    del out
+    for label, onsets, tile in [("onset order, default tile", in_order, 0), ("onset order, tiles of 1024", in_order, 1024), ("shuffled, default tile", shuffled, 0),
+                                ("shuffled, tiles of 1024", shuffled, 1024)]:
+        times = []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = prog.render_score(nv, nt, V, onsets, None, params, tile_instances=tile, pinned=True)
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+        print("  render_score, host clock, %-27s median %9.2f ms  fastest %9.2f" % (label, float(np.median(times[1:])), min(times[1:])), flush=True)
+    prog.close()
+    logged = ctxs["log"].build(uni.words)
+    print("  (DUSP_JIT_LOG=2, stderr: the plans' host time and block)", flush=True)
+    logged.render_score(nv, nt, V, in_order, None, params, tile_instances=1024)
+    logged.render_score(nv, nt, V, shuffled, None, params)
+    logged.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--scale", type=int, default=1, help="divide every voice count by this (a quick look)")
+    a = ap.parse_args()
+    os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
+    ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
+    for key in a.cases:
+        if key in DENSE:
+            dense(key, a.scale, ctxs, a.reps)
+    if "p" in a.cases:
+        piece(a.scale, ctxs, a.reps)
+
+
+if __name__ == "__main__":
+    main()
