@@ -1,8 +1,9 @@
-// abi_deliver.hip — the C ABI (include/dusp_hip.h): what happens to rendered PCM on the device (interleave, peak, encode, mix, score) and how
-// it reaches the host (dusp_render_host* and their delivery paths, dusp_render_host_mix, dusp_render_host_score).
+// abi_deliver.hip — the C ABI (include/dusp_hip.h): what happens to rendered PCM on the device (interleave, peak, encode, mix, score, score over rows) and how
+// it reaches the host (dusp_render_host* and their delivery paths, dusp_render_host_mix, dusp_render_host_score, dusp_render_host_score_parts).
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <thread>
 
 #include "abi_internal.hpp"
@@ -286,6 +287,22 @@ struct TiledBatch {
     // reused from one tile to the next, so the tiles queue up on the stream without the host waiting for any of them
     TiledBatch(dusp_program *prog_, size_t n_instances_, const float *h_params, const float *h_gains_, size_t tile_)
         : prog(prog_), stream(prog_->ctx->stream), n_instances(n_instances_), n_params(prog_->P.g.n_params), tile(tile_), h_gains(h_gains_) {
+        whole_batch_decisions(h_params);
+        cols.resize(n_params * n_instances);
+        for (size_t lo = 0; lo < n_instances && n_params; lo += tile) gather(h_params, lo, std::min(tile, n_instances - lo));
+    }
+    // ... or the tiles are the instance ranges [starts[i], starts[i + 1]) (dusp_render_host_score_parts: a part's share of every tile of
+    // the piece), gathered the same way
+    TiledBatch(dusp_program *prog_, size_t n_instances_, const float *h_params, const std::vector<size_t> &starts)
+        : prog(prog_), stream(prog_->ctx->stream), n_instances(n_instances_), n_params(prog_->P.g.n_params), tile(0), h_gains(nullptr) {
+        whole_batch_decisions(h_params);
+        cols.resize(n_params * n_instances);
+        for (size_t i = 0; i + 1 < starts.size() && n_params; i++) gather(h_params, starts[i], starts[i + 1] - starts[i]);
+    }
+    void gather(const float *h_params, size_t lo, size_t n) {
+        for (size_t p = 0; p < n_params; p++) std::memcpy(&cols[n_params * lo + p * n], h_params + p * n_instances + lo, n * sizeof(float));
+    }
+    void whole_batch_decisions(const float *h_params) {
         prog->mix_n_inst = (uint32_t)n_instances;
         prog->mix_range.assign(3 * n_params, 0u);
         for (size_t p = 0; p < n_params; p++)
@@ -299,11 +316,6 @@ struct TiledBatch {
                     prog->mix_range[3 * p + 1] = std::max(prog->mix_range[3 * p + 1], b);
                 }
             }
-        cols.resize(n_params * n_instances);
-        for (size_t lo = 0; lo < n_instances && n_params; lo += tile) {
-            const size_t n = std::min(tile, n_instances - lo);
-            for (size_t p = 0; p < n_params; p++) std::memcpy(&cols[n_params * lo + p * n], h_params + p * n_instances + lo, n * sizeof(float));
-        }
     }
     ~TiledBatch() {
         if (staged) (void)hipStreamSynchronize(stream);  // (a return in the middle of the tiles)
@@ -561,6 +573,218 @@ int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voic
     whole.staged = false;  // (the delivery has waited for the stream)
     if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
         CTX_FAIL(ctx, DUSP_ERR_HIP, "dusp_render_host_score: the score kernel wrote past the end of a device buffer: guard bytes overwritten");
+    return DUSP_OK;
+    });
+}
+
+// ---- rows: scores over voices that each lie in a buffer of their own (score_rows_engine.hip; dusp_amd/mix.py score_chain_rows) ----
+
+// score_image_add for rows: plans the voices [0, n) — voice k row_samples[k] samples a channel at device address rows[k] — within
+// budget_bytes and appends the plan to the context's host image.  listed (optional): which voices reach the timeline.
+static int score_rows_image_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n,
+                                size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L, std::vector<unsigned char> *listed = nullptr) {
+    dusp::ScoreRowsPlan P;
+    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P);
+    if (bad >= 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
+                                        ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
+    L = ScoreLaunch();
+    L.w_lo = (uint64_t)P.w_lo;
+    L.w_hi = (uint64_t)P.w_hi;
+    L.block_shift = P.block_shift;
+    L.first_block = P.first_block;
+    L.any = P.n_entries() > 0;
+    if (L.any) {
+        L.n_voices = n;
+        L.n_block_first = P.block_first.size();
+        L.at = dusp::score_rows_plan_pack(P, ctx->h_score_plan);
+    }
+    if (listed) {
+        listed->resize(n);
+        for (size_t k = 0; k < n; k++) (*listed)[k] = P.voices[k].hi > P.voices[k].lo;
+    }
+    return DUSP_OK;
+}
+
+static int score_rows_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, size_t n_total, const float *d_gains, const float *d_init, int raw, float *d_out,
+                             hipStream_t stream) {
+    if (L.w_hi <= L.w_lo) return DUSP_OK;
+    const dusp::ScoreRow *d_voices = L.any ? (const dusp::ScoreRow *)(ctx->d_score_plan + L.at) : nullptr;  // (the buffer and L.at: both on 32-byte boundaries)
+    const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices) : nullptr;
+    HIP_TRY(ctx, dusp::launch_score_rows(d_gains, d_voices, d_block_first, L.any ? d_block_first + L.n_block_first : nullptr, d_init, d_out, (uint32_t)n_channels, n_total, L.w_lo,
+                                         L.w_hi, L.block_shift, L.first_block, raw, stream));
+    if (L.any) HIP_TRY(ctx, hipEventRecord(ctx->score_done, stream));
+    return DUSP_OK;
+}
+
+int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                           const int64_t *h_lengths, const float *d_gains, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    return guarded(ctx->err, "dusp_score_rows_device", [&]() -> int {
+    if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: NULL buffer");
+    if (!channels_in_range(n_channels) || n_voices > (1u << 24) || !samples_in_range(n_total_samples))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: need 1..64 channels, 0..2^24 voices and 1..2^31 samples of timeline");
+    if (n_channels * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
+    if ((((uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: the buffers must be 4-byte aligned");
+    for (size_t k = 0; k < n_voices; k++) {
+        if ((uint64_t)h_row_samples[k] * n_channels > dusp::kScoreRowMax)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: voice " + std::to_string(k) + ": channels x row samples must not exceed 2^31");
+        if (h_row_samples[k] && !h_rows[k]) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: the row of voice " + std::to_string(k) + " is NULL");
+        if (h_row_samples[k] && ((uintptr_t)h_rows[k] & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: the row of voice " + std::to_string(k) + " must be 4-byte aligned");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    ScoreLaunch L;
+    L.w_hi = n_total_samples;  // (no voices: `|| 0`, or a copy, of d_init alone)
+    if (n_voices) {
+        if (int rc = score_image_begin(ctx)) return rc;
+        const auto t_plan = std::chrono::steady_clock::now();
+        static_assert(sizeof(const float *) == sizeof(uint64_t), "rows are handed to the planner as 64-bit addresses");
+        if (int rc = score_rows_image_add(ctx, "dusp_score_rows_device", h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples,
+                                          /*whole_timeline=*/true, score_plan_budget(ctx), L))
+            return rc;
+        ctx->score_plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan).count();
+        if (int rc = score_image_upload(ctx, stream)) return rc;
+    } else {
+        if (!ctx->score_t0) {  // (no plan, but the launch is timed like any other)
+            if (int rc = score_image_begin(ctx)) return rc;
+        }
+        ctx->score_plan_ms = 0;
+    }
+    ctx->score_timed = false;
+    ctx->score_upload_timed = L.any;
+    HIP_TRY(ctx, hipEventRecord(ctx->score_t0, stream));
+    if (int rc = score_rows_launch(ctx, L, n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream)) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->score_t1, stream));
+    ctx->score_timed = true;
+    return DUSP_OK;
+    });
+}
+
+int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                 const int64_t *h_lengths, const float *h_gains, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out,
+                                 float *h_peak) {
+    const char *who = "dusp_render_host_score_parts";
+    if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
+    dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
+    dusp_ctx *ctx = prog0->ctx;
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    const size_t n_ch = prog0->P.out_bufs.size();
+    if (!h_part_of || !h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of or h_onsets is NULL");
+    if (n_voices < 1 || n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^24 voices");
+    size_t n_listed = 0;
+    for (size_t p = 0; p < n_parts; p++) {
+        if (!parts[p].prog) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the program of part " + std::to_string(p) + " is NULL");
+        if (parts[p].prog->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " was built on another context: all parts of a piece share one");
+        if (parts[p].prog->P.out_bufs.size() != n_ch)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) + " output channels, part 0 has " +
+                                            std::to_string(n_ch) + ": all parts of a piece have the same number");
+        for (size_t q = 0; q < p; q++)
+            if (parts[q].prog == parts[p].prog)
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": parts " + std::to_string(q) + " and " + std::to_string(p) + " are the same program: its tile buffer would be used twice; make them one part or build it twice");
+        n_listed += parts[p].n_instances;
+    }
+    if (!samples_in_range(n_total_samples) || n_ch * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
+    // voice k of the chain: the next unused instance of part h_part_of[k]
+    std::vector<size_t> instance_of(n_voices), used(n_parts, 0);
+    for (size_t k = 0; k < n_voices; k++) {
+        if (h_part_of[k] >= n_parts) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + " names part " + std::to_string(h_part_of[k]) + " of " + std::to_string(n_parts));
+        instance_of[k] = used[h_part_of[k]]++;
+    }
+    for (size_t p = 0; p < n_parts; p++)
+        if (used[p] != parts[p].n_instances || n_listed != n_voices)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of names part " + std::to_string(p) + " " + std::to_string(used[p]) + " times, the part has " +
+                                            std::to_string(parts[p].n_instances) + " instances: every instance is one voice of the chain");
+    for (size_t p = 0; p < n_parts; p++) {  // (the sizes the tiles are made from; tiled_batch_prepare below refuses the rest, in front of any render)
+        if (int rc = check_batch(ctx, who, parts[p].n_instances, parts[p].n_voice_samples)) return rc;
+        if (n_ch * parts[p].n_voice_samples > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x voice samples must not exceed 2^31");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the tiles: runs of the chain's voices whose rows together fit tile_bytes
+    std::vector<uint64_t> row_bytes(n_voices);
+    std::vector<uint32_t> row_samples(n_voices);
+    size_t staged = 0, free_bytes = 0, total_bytes = 0;
+    for (size_t k = 0; k < n_voices; k++) {
+        row_samples[k] = (uint32_t)parts[h_part_of[k]].n_voice_samples;  // (at most 2^31 / channels: tiled_batch_prepare)
+        row_bytes[k] = (uint64_t)n_ch * row_samples[k] * sizeof(float);
+    }
+    for (size_t p = 0; p < n_parts; p++) staged += parts[p].prog->d_host_out.cap * sizeof(float);
+    if (tile_bytes == 0 && ctx->knobs.mix_tile_mb <= 0) HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
+    const std::vector<size_t> starts = dusp::piece_tile_starts(row_bytes.data(), n_voices, tile_bytes, ctx->knobs.mix_tile_mb, free_bytes, staged, ctx->n_cus);
+    const size_t n_tiles = starts.size() - 1;
+    // a part's share of tile i: its instances [share[p][i], share[p][i + 1]), one contiguous range since its instances enter the chain in
+    // their own order; its tile buffer holds the largest share
+    std::vector<std::vector<size_t>> share(n_parts, std::vector<size_t>(n_tiles + 1, 0));
+    {
+        std::vector<size_t> seen(n_parts, 0);
+        for (size_t i = 0; i < n_tiles; i++) {
+            for (size_t k = starts[i]; k < starts[i + 1]; k++) seen[h_part_of[k]]++;
+            for (size_t p = 0; p < n_parts; p++) share[p][i + 1] = seen[p];
+        }
+    }
+    for (size_t p = 0; p < n_parts; p++) {
+        size_t most = 1, unused = 0;
+        for (size_t i = 0; i < n_tiles; i++) most = std::max(most, share[p][i + 1] - share[p][i]);
+        if (int rc = tiled_batch_prepare(parts[p].prog, who, parts[p].n_instances, parts[p].n_voice_samples, parts[p].h_params, nullptr, most, format, normalise, h_out, &unused)) return rc;
+    }
+    // every tile's plan, over the tile's union window, made up front under the call's one budget and uploaded once: the rows' addresses
+    // are known, since the tile buffers stand
+    std::vector<ScoreLaunch> launches(n_tiles);
+    std::vector<std::vector<unsigned char>> renders(n_tiles, std::vector<unsigned char>(n_parts, 0));  // does part p render in tile i?
+    const size_t tile_budget = score_plan_budget(ctx) / n_tiles;
+    if (int rc = score_image_begin(ctx)) return rc;
+    const auto t_plan = std::chrono::steady_clock::now();
+    {
+        std::vector<uint64_t> rows;
+        std::vector<unsigned char> listed;
+        for (size_t i = 0; i < n_tiles; i++) {
+            const size_t lo = starts[i], n = starts[i + 1] - lo;
+            rows.resize(n);
+            for (size_t k = 0; k < n; k++) {
+                const size_t p = h_part_of[lo + k];
+                rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * n_ch * parts[p].n_voice_samples);
+            }
+            if (int rc = score_rows_image_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
+                                              /*whole_timeline=*/false, tile_budget, launches[i], &listed))
+                return rc;
+            for (size_t k = 0; k < n; k++)
+                if (listed[k]) renders[i][h_part_of[lo + k]] = 1;
+        }
+    }
+    if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: what the plans cost the host)
+        fprintf(stderr, "[dusp host piece] %zu plans over %zu voices of %zu parts in %.0f us on the host: %zu bytes\n", n_tiles, n_voices, n_parts,
+                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count(), ctx->h_score_plan.size());
+    HIP_TRY(ctx, prog0->d_mix.ensure(n_ch * n_total_samples));  // the timeline's running sums
+    if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once)
+        HIP_TRY(ctx, prog0->d_mix_gains.ensure(n_voices));
+        HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (int rc = score_image_upload(ctx, ctx->stream)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix.p, 0, n_ch * n_total_samples * sizeof(float), ctx->stream));
+    std::vector<std::unique_ptr<TiledBatch>> whole;  // what changes bits is decided from the WHOLE part
+    for (size_t p = 0; p < n_parts; p++) whole.emplace_back(new TiledBatch(parts[p].prog, parts[p].n_instances, parts[p].h_params, share[p]));
+    auto waited = [&]() {
+        for (auto &b : whole) b->staged = false;
+    };
+    for (size_t i = 0; i < n_tiles; i++) {
+        if (launches[i].w_hi <= launches[i].w_lo) continue;  // (no voice of the tile reaches the timeline: nothing to render)
+        for (size_t p = 0; p < n_parts; p++)
+            if (renders[i][p])
+                if (int rc = whole[p]->render_tile(share[p][i], share[p][i + 1] - share[p][i], parts[p].n_voice_samples)) return rc;
+        if (int rc = score_rows_launch(ctx, launches[i], n_ch, n_total_samples, h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p,
+                                       ctx->stream))
+            return rc;
+    }
+    ScoreLaunch all;  // `|| 0` over the whole timeline
+    all.w_hi = n_total_samples;
+    if (int rc = score_rows_launch(ctx, all, n_ch, n_total_samples, nullptr, prog0->d_mix.p, /*raw=*/0, prog0->d_mix.p, ctx->stream)) return rc;
+    if (int rc = deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
+    waited();  // (the delivery has waited for the stream)
+    if (g_guard_bytes && (!prog0->d_mix.intact() || !prog0->d_mix_gains.intact() || !score_plan_intact(ctx)))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, w + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
     return DUSP_OK;
     });
 }

@@ -355,4 +355,20 @@ int dusp_circuit_kernel_source(const double *desc, size_t n_words, int waves, in
     });
 }
 
+int dusp_descriptor_channels(const double *desc, size_t n_words) {
+    return guarded(g_error, "dusp_descriptor_channels", [&]() -> int {
+    if (!desc) {
+        g_error = "dusp_descriptor_channels: NULL argument";
+        return DUSP_ERR_ARG;
+    }
+    dusp::Program P;  // (descriptor -> program: host code only, what dusp_program_build does first)
+    std::string err;
+    if (!dusp::compile(desc, n_words, P, err, /*continuation=*/false)) {
+        g_error = "dusp_descriptor_channels: " + err;
+        return DUSP_ERR_ARG;
+    }
+    return (int)P.out_bufs.size();
+    });
+}
+
 }  // extern "C"

@@ -1,9 +1,10 @@
-// render_plan.hpp — three small decisions a render takes between its HIP calls, as plain data in, plain data out: host code only (no HIP),
+// render_plan.hpp — a few small decisions a render takes between its HIP calls, as plain data in, plain data out: host code only (no HIP),
 // checked at their boundary values on the CPU (tests/native/render_plan_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "device_types.hpp"
 
@@ -37,6 +38,32 @@ inline size_t mix_tile_instances(size_t tile_instances, int mix_tile_mb, size_t 
         tile = std::min((size_t)n_cus * kMixTileRowsPerCu, budget / (row_floats * sizeof(float)));
     }
     return std::min(std::max<size_t>(1, tile), n_instances);
+}
+
+// The tiles of dusp_render_host_score_parts: runs [starts[i], starts[i + 1]) of the chain's voices whose rows (row_bytes[k] each: the
+// voices are of several programs and several lengths) together fit tile_bytes, at most max_voices voices and at least one voice a tile.
+// tile_bytes == 0: the default, derived as mix_tile_instances derives its own but over bytes — what fits mix_tile_mb MiB, else
+// kMixTileBytes or half of the device's free memory (staged_bytes counted as the call's own) and no more voices than fill the chip.
+inline std::vector<size_t> piece_tile_starts(const uint64_t *row_bytes, size_t n_voices, size_t tile_bytes, int mix_tile_mb, size_t free_bytes, size_t staged_bytes,
+                                             int n_cus) {
+    uint64_t budget = tile_bytes;
+    size_t max_voices = n_voices;
+    if (budget == 0 && mix_tile_mb > 0) budget = (uint64_t)mix_tile_mb << 20;
+    else if (budget == 0) {
+        budget = std::min(kMixTileBytes, (free_bytes + staged_bytes) / 2);
+        max_voices = (size_t)n_cus * kMixTileRowsPerCu;
+    }
+    std::vector<size_t> starts{0};
+    uint64_t used = 0;
+    for (size_t k = 0; k < n_voices; k++) {
+        if (k > starts.back() && (used + row_bytes[k] > budget || k - starts.back() >= max_voices)) {
+            starts.push_back(k);
+            used = 0;
+        }
+        used += row_bytes[k];
+    }
+    starts.push_back(n_voices);
+    return starts;
 }
 
 // Of a render's n_chunks chunks from circuit clock clock0 (a multiple of the chunk), how many are among the program's n_warm warm-up

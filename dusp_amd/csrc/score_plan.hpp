@@ -47,6 +47,43 @@ struct ScorePlan {
     size_t bytes() const { return voices.size() * sizeof(ScoreVoice) + (block_first.size() + entries.size()) * sizeof(uint32_t); }
 };
 
+// The lists of a plan whose records (ScoreVoice, ScoreRow: anything with lo and hi) are made: the block, doubled from kScoreGroup until
+// records + block_first + entries (+ kScoreEntryPad) fit budget_bytes or one block covers the window [w_lo, w_hi), w_lo < w_hi; then the
+// CSR lists, every one ascending, and the padding's zeros behind the last.
+template <class Record>
+inline void score_plan_lists(const std::vector<Record> &voices, int64_t w_lo, int64_t w_hi, size_t budget_bytes, uint32_t &block_shift, uint64_t &first_block,
+                             std::vector<uint32_t> &block_first, std::vector<uint32_t> &entries) {
+    const size_t n = voices.size();
+    auto blocks_of = [&](uint32_t shift, uint64_t &first, uint64_t &count, uint64_t &n_entries) {
+        first = (uint64_t)w_lo >> shift;
+        count = (((uint64_t)w_hi - 1) >> shift) - first + 1;
+        n_entries = 0;
+        for (const Record &v : voices)
+            if (v.hi > v.lo) n_entries += ((uint64_t)(v.hi - 1) >> shift) - ((uint64_t)v.lo >> shift) + 1;
+    };
+    uint32_t shift = kScoreGroupShift;
+    uint64_t first, count, n_entries;
+    for (;; shift++) {
+        blocks_of(shift, first, count, n_entries);
+        const uint64_t bytes = (uint64_t)n * sizeof(Record) + (count + 1 + n_entries + kScoreEntryPad) * sizeof(uint32_t);
+        if ((bytes <= budget_bytes && n_entries <= 0xffffffffull) || count == 1) break;
+    }
+    block_shift = shift;
+    first_block = first;
+    block_first.assign((size_t)count + 1, 0u);
+    for (const Record &v : voices)  // counts, one place up ...
+        if (v.hi > v.lo)
+            for (uint64_t b = ((uint64_t)v.lo >> shift) - first, b1 = ((uint64_t)(v.hi - 1) >> shift) - first; b <= b1; b++) block_first[(size_t)b + 1]++;
+    for (size_t b = 0; b < (size_t)count; b++) block_first[b + 1] += block_first[b];  // ... become the lists' starts
+    entries.assign((size_t)n_entries + kScoreEntryPad, 0u);
+    std::vector<uint32_t> at(block_first.begin(), block_first.end() - 1);
+    for (size_t k = 0; k < n; k++) {  // voices in index order: every list comes out ascending
+        const Record &v = voices[k];
+        if (v.hi > v.lo)
+            for (uint64_t b = ((uint64_t)v.lo >> shift) - first, b1 = ((uint64_t)(v.hi - 1) >> shift) - first; b <= b1; b++) entries[at[(size_t)b]++] = (uint32_t)k;
+    }
+}
+
 // lengths: nullptr for n_voice everywhere.  whole_timeline: the plan covers [0, n_total) (a launch that writes every sample), else the
 // union window only (a raw launch in place: samples no voice of the tile reaches stay as they are).
 // Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, n_voice].
@@ -73,34 +110,7 @@ inline int64_t score_plan(const int64_t *onsets, const int64_t *lengths, size_t 
     P.w_lo = whole_timeline ? 0 : t_lo;
     P.w_hi = whole_timeline ? total : t_hi;
     if (P.w_hi <= P.w_lo) return -1;  // nothing to launch
-    auto blocks_of = [&](uint32_t shift, uint64_t &first, uint64_t &count, uint64_t &n_entries) {
-        first = (uint64_t)P.w_lo >> shift;
-        count = (((uint64_t)P.w_hi - 1) >> shift) - first + 1;
-        n_entries = 0;
-        for (const ScoreVoice &v : P.voices)
-            if (v.hi > v.lo) n_entries += ((uint64_t)(v.hi - 1) >> shift) - ((uint64_t)v.lo >> shift) + 1;
-    };
-    uint32_t shift = kScoreGroupShift;
-    uint64_t first, count, n_entries;
-    for (;; shift++) {
-        blocks_of(shift, first, count, n_entries);
-        const uint64_t bytes = (uint64_t)n * sizeof(ScoreVoice) + (count + 1 + n_entries + kScoreEntryPad) * sizeof(uint32_t);
-        if ((bytes <= budget_bytes && n_entries <= 0xffffffffull) || count == 1) break;
-    }
-    P.block_shift = shift;
-    P.first_block = first;
-    P.block_first.assign((size_t)count + 1, 0u);
-    for (const ScoreVoice &v : P.voices)  // counts, one place up ...
-        if (v.hi > v.lo)
-            for (uint64_t b = ((uint64_t)v.lo >> shift) - first, b1 = ((uint64_t)(v.hi - 1) >> shift) - first; b <= b1; b++) P.block_first[(size_t)b + 1]++;
-    for (size_t b = 0; b < (size_t)count; b++) P.block_first[b + 1] += P.block_first[b];  // ... become the lists' starts
-    P.entries.assign((size_t)n_entries + kScoreEntryPad, 0u);
-    std::vector<uint32_t> at(P.block_first.begin(), P.block_first.end() - 1);
-    for (size_t k = 0; k < n; k++) {  // voices in index order: every list comes out ascending
-        const ScoreVoice &v = P.voices[k];
-        if (v.hi > v.lo)
-            for (uint64_t b = ((uint64_t)v.lo >> shift) - first, b1 = ((uint64_t)(v.hi - 1) >> shift) - first; b <= b1; b++) P.entries[at[(size_t)b]++] = (uint32_t)k;
-    }
+    score_plan_lists(P.voices, P.w_lo, P.w_hi, budget_bytes, P.block_shift, P.first_block, P.block_first, P.entries);
     return -1;
 }
 
@@ -115,6 +125,86 @@ inline size_t score_plan_pack(const ScorePlan &P, std::vector<unsigned char> &im
         p += n_bytes;
     };
     put(P.voices.data(), P.voices.size() * sizeof(ScoreVoice));
+    put(P.block_first.data(), P.block_first.size() * sizeof(uint32_t));
+    put(P.entries.data(), P.entries.size() * sizeof(uint32_t));
+    return at;
+}
+
+// ---- rows: every voice a buffer of its own (score_rows_engine.hip; dusp_amd/mix.py score_chain_rows is the contract) ----
+
+// A voice as the rows kernel reads it: timeline samples [lo, hi) take ((const float *)row)[c * stride + (t - onset)].
+// (32 bytes on a 32-byte boundary: one eight-dword scalar load a voice)
+// A record that is in no list (lo == hi == 0) still carries a READABLE row: the first listed voice's.  The kernel points the load of a
+// lane that an entry does not cover at the entry's own row[0], and the entries it may meet are (a) its list's, (b) another list's — both
+// name voices with lo < hi, whose rows hold at least one float — and (c) the padding's zeros, which name voice 0 whether or not voice 0
+// is anywhere on the timeline (its own row may be NULL or empty).
+struct alignas(32) ScoreRow {
+    int64_t onset;
+    uint32_t lo, hi;
+    uint64_t row;     // device address of the voice's channel 0, sample 0
+    uint32_t stride;  // floats from one channel of this voice to the next
+    uint32_t pad;
+};
+static_assert(sizeof(ScoreRow) == 32, "one eight-dword scalar load");
+
+struct ScoreRowsPlan {
+    int64_t t_lo = 0, t_hi = 0, w_lo = 0, w_hi = 0;  // as ScorePlan's
+    uint32_t block_shift = kScoreGroupShift;
+    uint64_t first_block = 0;
+    std::vector<ScoreRow> voices;        // [n]
+    std::vector<uint32_t> block_first;   // [n_blocks + 1]
+    std::vector<uint32_t> entries;       // as ScorePlan's, kScoreEntryPad zeros behind the last list
+    size_t n_entries() const { return block_first.empty() ? 0 : block_first.back(); }
+    size_t n_blocks() const { return block_first.empty() ? 0 : block_first.size() - 1; }
+    size_t bytes() const { return voices.size() * sizeof(ScoreRow) + (block_first.size() + entries.size()) * sizeof(uint32_t); }
+};
+
+// score_plan over voices of their own row lengths: row_samples[k] samples a channel (which is also the voice's channel stride) at device
+// address rows[k] (nullptr: all 0, for a plan that is only looked at).  lengths: nullptr for row_samples[k] everywhere.
+// Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, row_samples[k]].
+// Needs n <= 2^32 - 1, row_samples and n_total <= kScoreRowMax.
+inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n, uint64_t n_total,
+                               bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P) {
+    P = ScoreRowsPlan();
+    P.voices.assign(n, ScoreRow{0, 0u, 0u, 0u, 0u, 0u});
+    const int64_t total = (int64_t)n_total;
+    int64_t t_lo = total, t_hi = 0;
+    size_t first_listed = n;
+    for (size_t k = 0; k < n; k++) {
+        const int64_t len = lengths ? lengths[k] : (int64_t)row_samples[k], onset = onsets[k];
+        if (len < 0 || len > (int64_t)row_samples[k]) return (int64_t)k;
+        if (len == 0 || onset >= total || onset <= -len) continue;  // empty, behind the end, wholly in front of sample 0
+        // here -2^31 <= -len < onset < n_total <= 2^31: onset + len cannot overflow
+        const int64_t lo = std::max<int64_t>(onset, 0), hi = std::min(onset + len, total);
+        P.voices[k] = ScoreRow{onset, (uint32_t)lo, (uint32_t)hi, rows ? rows[k] : 0, row_samples[k], 0u};
+        if (first_listed == n) first_listed = k;
+        t_lo = std::min(t_lo, lo);
+        t_hi = std::max(t_hi, hi);
+    }
+    if (first_listed < n)  // (the records nobody adds from: readable all the same, see ScoreRow)
+        for (ScoreRow &v : P.voices)
+            if (v.hi == v.lo) v.row = P.voices[first_listed].row;
+    if (t_hi <= t_lo) t_lo = t_hi = 0;
+    P.t_lo = t_lo;
+    P.t_hi = t_hi;
+    P.w_lo = whole_timeline ? 0 : t_lo;
+    P.w_hi = whole_timeline ? total : t_hi;
+    if (P.w_hi <= P.w_lo) return -1;  // nothing to launch
+    score_plan_lists(P.voices, P.w_lo, P.w_hi, budget_bytes, P.block_shift, P.first_block, P.block_first, P.entries);
+    return -1;
+}
+
+// The rows plan as the device reads it, appended to `image` on a 32-byte boundary (the image itself starts on one on the device): voices,
+// block_first, entries.  Returns the byte offset of the voices.
+inline size_t score_rows_plan_pack(const ScoreRowsPlan &P, std::vector<unsigned char> &image) {
+    const size_t at = (image.size() + 31) & ~(size_t)31;
+    image.resize(at + P.bytes());
+    unsigned char *p = image.data() + at;
+    auto put = [&](const void *src, size_t n_bytes) {
+        if (n_bytes) std::copy((const unsigned char *)src, (const unsigned char *)src + n_bytes, p);
+        p += n_bytes;
+    };
+    put(P.voices.data(), P.voices.size() * sizeof(ScoreRow));
     put(P.block_first.data(), P.block_first.size() * sizeof(uint32_t));
     put(P.entries.data(), P.entries.size() * sizeof(uint32_t));
     return at;

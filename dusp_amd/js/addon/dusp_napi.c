@@ -8,6 +8,8 @@
  *   render(prog, nInstances, nSamples, Float32Array params | null[, interleaved[, Float32Array inputs]]) -> Promise<Float32Array>
  *         (runs dusp_render_host on the libuv pool so the event loop stays live)
  *   stateDownload(prog, instance, unit) -> Float64Array
+ *   renderPiece(progs[], ...) -> Promise: a piece of several instruments (dusp_render_host_score_parts; see fn_render_piece)
+ *   descriptorChannels(Float64Array words) -> the circuit's output channels (host code only: no context)
  *   programDestroy(prog), ctxDestroy(ctx), version(), abiVersion()
  * Failures surface the way the reference's do: synchronous calls THROW A STRING, render() REJECTS
  * WITH A STRING (reference src/renderChannelData.js:12-17 throws strings inside an async function).
@@ -736,6 +738,259 @@ static napi_value fn_render_pcm(napi_env env, napi_callback_info info) { return 
 static napi_value fn_render_mix(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_MIX); }
 static napi_value fn_render_score(napi_env env, napi_callback_info info) { return render_call(env, info, CALL_SCORE); }
 
+/* ---- a piece of several instruments: dusp_render_host_score_parts ---- */
+typedef struct {
+    napi_async_work work;
+    napi_deferred deferred;
+    size_t n_parts, n_voices, n_total, tile_bytes, n_floats, n_bytes;
+    napi_ref *refs;   /* keep the program externals alive while the render is in flight */
+    prog_box **pbs;
+    dusp_score_part *parts;
+    float **params;   /* host copies (the caller may reuse its arrays) */
+    uint32_t *part_of;
+    int64_t *onsets, *lengths;
+    float *gains, *out;
+    float peak;
+    int format, normalise, rc;
+    char err[512];
+} piece_job;
+
+static void piece_free(napi_env env, piece_job *j) {
+    for (size_t p = 0; p < j->n_parts; p++) {
+        if (j->params) free(j->params[p]);
+        if (j->refs && j->refs[p]) napi_delete_reference(env, j->refs[p]);
+    }
+    free(j->params);
+    free(j->refs);
+    free(j->pbs);
+    free(j->parts);
+    free(j->part_of);
+    free(j->onsets);
+    free(j->lengths);
+    free(j->gains);
+    free(j->out);
+    free(j);
+}
+static void piece_execute(napi_env env, void *data) {
+    (void)env;
+    piece_job *j = (piece_job *)data;
+    ctx_box *cb = j->pbs[0]->cb;
+    pthread_mutex_lock(&cb->lock);
+    j->rc = DUSP_OK;
+    for (size_t p = 0; p < j->n_parts; p++) {
+        if (!j->pbs[p]->prog) {
+            j->rc = DUSP_ERR_STATE;
+            snprintf(j->err, sizeof j->err, "dusp-hip: renderPiece: a program has been destroyed");
+        }
+        j->parts[p].prog = j->pbs[p]->prog;
+    }
+    if (j->rc == DUSP_OK) {
+        j->rc = dusp_render_host_score_parts(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, j->n_total, j->tile_bytes, j->format, j->normalise,
+                                             j->out, j->format ? &j->peak : NULL);
+        if (j->rc != DUSP_OK) snprintf(j->err, sizeof j->err, "dusp-hip: %s", dusp_last_error(cb->ctx));
+    }
+    pthread_mutex_unlock(&cb->lock);
+}
+static void piece_complete(napi_env env, napi_status status, void *data) {
+    piece_job *j = (piece_job *)data;
+    napi_value result;
+    if (status != napi_ok && j->rc == DUSP_OK) {
+        j->rc = DUSP_ERR_STATE;
+        snprintf(j->err, sizeof j->err, "dusp-hip: render was cancelled");
+    }
+    int ok = 0;
+    if (j->rc == DUSP_OK && j->format) { /* { data: Buffer over the encoded frames, peaks: Float32Array(1) } */
+        napi_value buf, peaks_ab, peaks;
+        void *peaks_mem;
+        if (napi_create_arraybuffer(env, sizeof(float), &peaks_mem, &peaks_ab) == napi_ok && napi_create_typedarray(env, napi_float32_array, 1, peaks_ab, 0, &peaks) == napi_ok &&
+            napi_create_object(env, &result) == napi_ok && napi_create_external_buffer(env, j->n_bytes, j->out, free_pcm, NULL, &buf) == napi_ok) {
+            j->out = NULL; /* owned by the Buffer now */
+            memcpy(peaks_mem, &j->peak, sizeof(float));
+            napi_set_named_property(env, result, "data", buf);
+            napi_set_named_property(env, result, "peaks", peaks);
+            ok = 1;
+        }
+    } else if (j->rc == DUSP_OK) {
+        napi_value ab;
+        if (napi_create_external_arraybuffer(env, j->out, j->n_floats * sizeof(float), free_pcm, NULL, &ab) == napi_ok &&
+            napi_create_typedarray(env, napi_float32_array, j->n_floats, ab, 0, &result) == napi_ok) {
+            j->out = NULL; /* owned by the ArrayBuffer now */
+            ok = 1;
+        }
+    }
+    if (ok) napi_resolve_deferred(env, j->deferred, result);
+    else {
+        napi_create_string_utf8(env, j->rc == DUSP_OK ? "dusp-hip: could not wrap the PCM buffer" : j->err, NAPI_AUTO_LENGTH, &result);
+        napi_reject_deferred(env, j->deferred, result); /* a string, like the reference's rejections */
+    }
+    for (size_t p = 0; p < j->n_parts; p++)
+        if (--j->pbs[p]->in_flight == 0 && j->pbs[p]->destroy_deferred) prog_destroy_now(j->pbs[p]);
+    napi_delete_async_work(env, j->work);
+    piece_free(env, j);
+}
+
+/* renderPiece(progs[], nInstances Float64Array, nVoiceSamples Float64Array, params[] (Float32Array | null each), partOf Uint32Array, onsets, lengths | null,
+ *             gains | null, nTotalSamples, tileBytes, format, normalise)
+ *   -> as renderScore (dusp_render_host_score_parts: voice k of the chain is the next unused instance of part partOf[k]) */
+static napi_value fn_render_piece(napi_env env, napi_callback_info info) {
+    napi_value argv[12];
+    char msg[256];
+    if (!get_args(env, info, 12, argv)) return NULL;
+    uint32_t n_parts = 0;
+    bool is_array = false;
+    if (napi_is_array(env, argv[0], &is_array) != napi_ok || !is_array || napi_get_array_length(env, argv[0], &n_parts) != napi_ok || n_parts < 1) {
+        throw_string(env, "dusp-hip: renderPiece: parts must be an array of at least one program");
+        return NULL;
+    }
+    void *inst = NULL, *vs = NULL, *po = NULL;
+    size_t n_inst = 0, n_vs = 0, n_voices = 0;
+    if (!typed_array(env, argv[1], napi_float64_array, &inst, &n_inst) || !typed_array(env, argv[2], napi_float64_array, &vs, &n_vs) || n_inst != n_parts || n_vs != n_parts) {
+        throw_string(env, "dusp-hip: renderPiece: nInstances and nVoiceSamples must be Float64Arrays of one value per part");
+        return NULL;
+    }
+    if (!typed_array(env, argv[4], napi_uint32_array, &po, &n_voices) || n_voices < 1 || n_voices > 16777216u) {
+        throw_string(env, "dusp-hip: renderPiece: partOf must be a Uint32Array of 1 .. 2^24 voices");
+        return NULL;
+    }
+    double n_total = 0, tile = 0, format = 0, normalise = 0;
+    if (napi_get_value_double(env, argv[8], &n_total) != napi_ok || !(n_total >= 1 && n_total <= 2147483648.0 && n_total == (double)(size_t)n_total)) {
+        throw_string(env, "dusp-hip: renderPiece: nTotalSamples out of range");
+        return NULL;
+    }
+    if (napi_get_value_double(env, argv[9], &tile) != napi_ok || !(tile >= 0 && tile <= 1e15 && tile == (double)(size_t)tile)) {
+        throw_string(env, "dusp-hip: renderPiece: tileBytes must be 0 (the default tile) or a whole number of bytes");
+        return NULL;
+    }
+    if (napi_get_value_double(env, argv[10], &format) != napi_ok || !(format == 0 || format == DUSP_PCM_S16 || format == DUSP_PCM_S24 || format == DUSP_PCM_F32)) {
+        throw_string(env, "dusp-hip: renderPiece: format must be 0 (planar f32), 1 (s16), 2 (s24) or 3 (f32)");
+        return NULL;
+    }
+    if (napi_get_value_double(env, argv[11], &normalise) != napi_ok || !(normalise == 0 || normalise == 1 || normalise == 2)) {
+        throw_string(env, "dusp-hip: renderPiece: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)");
+        return NULL;
+    }
+    piece_job *j = (piece_job *)calloc(1, sizeof *j);
+    if (j) {
+        j->n_parts = n_parts;
+        j->refs = (napi_ref *)calloc(n_parts, sizeof *j->refs);
+        j->pbs = (prog_box **)calloc(n_parts, sizeof *j->pbs);
+        j->parts = (dusp_score_part *)calloc(n_parts, sizeof *j->parts);
+        j->params = (float **)calloc(n_parts, sizeof *j->params);
+        j->part_of = (uint32_t *)malloc(n_voices * sizeof(uint32_t));
+    }
+    if (!j || !j->refs || !j->pbs || !j->parts || !j->params || !j->part_of) {
+        if (j) piece_free(env, j);
+        throw_string(env, "dusp-hip: renderPiece: out of host memory");
+        return NULL;
+    }
+    memcpy(j->part_of, po, n_voices * sizeof(uint32_t));
+    j->n_voices = n_voices;
+    j->n_total = (size_t)n_total;
+    j->tile_bytes = (size_t)tile;
+    j->format = (int)format;
+    j->normalise = (int)normalise;
+    uint32_t n_channels = 0;
+    const char *bad = NULL;
+    for (uint32_t p = 0; p < n_parts && !bad; p++) {
+        napi_value prog_v, par_v;
+        napi_valuetype vt = napi_undefined;
+        if (napi_get_element(env, argv[0], p, &prog_v) != napi_ok || !(j->pbs[p] = as_prog(env, prog_v))) { /* (as_prog has thrown) */
+            piece_free(env, j);
+            return NULL;
+        }
+        dusp_program_info pi;
+        dusp_program_info_get(j->pbs[p]->prog, &pi);
+        const double ni = ((const double *)inst)[p], nv = ((const double *)vs)[p];
+        if (j->pbs[p]->cb != j->pbs[0]->cb) bad = "all parts of a piece are built on one context";
+        else if (!(ni >= 1 && ni <= 16777216.0 && ni == (double)(size_t)ni && nv >= 1 && nv <= 2147483648.0 && nv == (double)(size_t)nv)) bad = "nInstances / nVoiceSamples out of range";
+        else if (p && pi.n_out_channels != n_channels) bad = "all parts of a piece have one number of output channels";
+        if (bad) break;
+        n_channels = pi.n_out_channels;
+        j->parts[p].n_instances = (size_t)ni;
+        j->parts[p].n_voice_samples = (size_t)nv;
+        is_array = false;
+        if (napi_is_array(env, argv[3], &is_array) == napi_ok && is_array && napi_get_element(env, argv[3], p, &par_v) == napi_ok) napi_typeof(env, par_v, &vt);
+        if (vt != napi_null && vt != napi_undefined) {
+            void *data;
+            size_t len;
+            if (!typed_array(env, par_v, napi_float32_array, &data, &len) || len != (size_t)pi.n_params * (size_t)ni) bad = "params must be a Float32Array of nParams * nInstances values for every part";
+            else if (!(j->params[p] = (float *)malloc(len * sizeof(float) + 1))) bad = "out of host memory for a parameter table";
+            else memcpy(j->params[p], data, len * sizeof(float));
+        } else if (pi.n_params) bad = "a part's program needs a parameter table";
+        j->parts[p].h_params = j->params[p];
+    }
+    const char *why = NULL;
+    if (!bad && !(j->onsets = whole_samples(env, argv[5], n_voices, &why))) {
+        snprintf(msg, sizeof msg, "onsets %s", why);
+        bad = msg;
+    }
+    napi_valuetype vt = napi_undefined;
+    napi_typeof(env, argv[6], &vt);
+    if (!bad && vt != napi_null && vt != napi_undefined && !(j->lengths = whole_samples(env, argv[6], n_voices, &why))) {
+        snprintf(msg, sizeof msg, "lengths %s", why);
+        bad = msg;
+    }
+    napi_typeof(env, argv[7], &vt);
+    if (!bad && vt != napi_null && vt != napi_undefined) {
+        void *data;
+        size_t len;
+        if (!typed_array(env, argv[7], napi_float32_array, &data, &len) || len != n_voices) bad = "gains must be a Float32Array of one value per voice";
+        else if (!(j->gains = (float *)malloc(len * sizeof(float)))) bad = "out of host memory for the gains";
+        else memcpy(j->gains, data, len * sizeof(float));
+    }
+    j->n_floats = (size_t)n_channels * j->n_total;
+    j->n_bytes = j->n_floats * (size_t)(!j->format || j->format == DUSP_PCM_F32 ? 4 : j->format == DUSP_PCM_S16 ? 2 : 3);
+    if (!bad && !(j->out = (float *)malloc(j->n_bytes + 1))) bad = "out of host memory for the PCM buffer";
+    if (bad) {
+        char full[320];
+        snprintf(full, sizeof full, "dusp-hip: renderPiece: %s", bad);
+        piece_free(env, j);
+        throw_string(env, full);
+        return NULL;
+    }
+    napi_value promise, name;
+    int queued = napi_create_promise(env, &j->deferred, &promise) == napi_ok && napi_create_string_utf8(env, "dusp-hip render", NAPI_AUTO_LENGTH, &name) == napi_ok;
+    for (uint32_t p = 0; p < n_parts && queued; p++) {
+        napi_value prog_v;
+        queued = napi_get_element(env, argv[0], p, &prog_v) == napi_ok && napi_create_reference(env, prog_v, 1, &j->refs[p]) == napi_ok;
+    }
+    queued = queued && napi_create_async_work(env, NULL, name, piece_execute, piece_complete, j, &j->work) == napi_ok;
+    if (queued) {
+        for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight++;
+        if (napi_queue_async_work(env, j->work) != napi_ok) {
+            for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight--;
+            queued = 0;
+        }
+    }
+    if (!queued) {
+        piece_free(env, j);
+        throw_string(env, "dusp-hip: renderPiece: could not queue the render");
+        return NULL;
+    }
+    return promise;
+}
+
+/* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
+static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
+    napi_value argv[1], out;
+    void *data;
+    size_t len;
+    if (!get_args(env, info, 1, argv)) return NULL;
+    if (!typed_array(env, argv[0], napi_float64_array, &data, &len)) {
+        throw_string(env, "dusp-hip: descriptorChannels: the descriptor must be a Float64Array");
+        return NULL;
+    }
+    const int n = dusp_descriptor_channels((const double *)data, len);
+    if (n < 0) {
+        char msg[512];
+        snprintf(msg, sizeof msg, "dusp-hip: %s", dusp_last_error(NULL));
+        throw_string(env, msg);
+        return NULL;
+    }
+    NAPI_OK(napi_create_uint32(env, (uint32_t)n, &out));
+    return out;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
     static const struct {
         const char *name;
@@ -746,6 +1001,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"programDestroy", fn_program_destroy}, {"programInfo", fn_program_info}, {"stateDownload", fn_state_download},
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
+        {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

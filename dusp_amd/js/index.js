@@ -19,6 +19,9 @@ module.exports = {
   renderScore: renderChannelData.renderScore,
   renderScorePcm: renderChannelData.renderScorePcm,
   renderScoreWav: renderChannelData.renderScoreWav,
+  renderPiece: renderChannelData.renderPiece,
+  renderPiecePcm: renderChannelData.renderPiecePcm,
+  renderPieceWav: renderChannelData.renderPieceWav,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

@@ -468,6 +468,113 @@ async function renderScoreWav(outlets, opts = {}) {
   return encodeWav(await renderScorePcm(outlets, opts))
 }
 
+/* What two extractions have in common exactly when unify takes them as instances of one program: the descriptor's words with the
+ * values at the constant sites masked (twin of render.py structure_key). */
+function structureKey(extraction) {
+  const words = Float64Array.from(extraction.words)
+  for (const s of extraction.constSites) for (let k = 0; k < s.n; k++) words[s.valPos + k] = 0
+  return Buffer.from(words.buffer, words.byteOffset, words.byteLength).toString('latin1')
+}
+
+/* Group the voices of a piece into parts by structure and by voiceSamples[k]; parts are numbered in the order their first voice comes
+ * in the list.  Needs no device.  -> { parts: [{ uni, nVoiceSamples }], partOf: Uint32Array, instanceOf: [], sampleRate } — voice k is
+ * instance instanceOf[k] of part partOf[k], which is also the next unused instance of that part (twin of render.py piece_parts). */
+function pieceParts(extractions, voiceSamples) {
+  if (extractions.length === 0) throw 'dusp-hip: no instances'
+  const rates = [...new Set(extractions.map((e) => e.sampleRate))]
+  if (rates.length !== 1) throw 'dusp-hip: the voices of a piece have one sample rate, not ' + rates.sort()
+  const index = new Map(), members = [], samples = [], partOf = new Uint32Array(extractions.length), instanceOf = []
+  extractions.forEach((e, k) => {
+    const key = voiceSamples[k] + ':' + structureKey(e)
+    if (!index.has(key)) {
+      index.set(key, members.length)
+      members.push([])
+      samples.push(voiceSamples[k])
+    }
+    const p = index.get(key)
+    partOf[k] = p
+    instanceOf.push(members[p].length)
+    members[p].push(e)
+  })
+  return { parts: members.map((m, p) => ({ uni: unify(m), nVoiceSamples: samples[p] })), partOf, instanceOf, sampleRate: rates[0] }
+}
+
+/* channels[p]: the output channels of part p's circuit.  A piece has one channel count: refused by string otherwise. */
+function checkPieceChannels(channels) {
+  channels.forEach((c, p) => {
+    if (c !== channels[0]) throw 'dusp-hip: the voices of a piece must have one number of output channels: part ' + p + ' has ' + c + ', part 0 has ' + channels[0]
+  })
+  return channels[0]
+}
+
+async function pieceCall(who, outlets, opts, format, normalise) {
+  const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
+  const extractions = outlets.map((o) => extract(o))
+  if (extractions.length === 0) throw 'dusp-hip: no instances'
+  for (const ex of extractions)
+    for (const u of ex.circuit.units)
+      if ((u.isHostSignal || (UNITS[u.constructor.name] && UNITS[u.constructor.name].hostTick)) && !deviceRetrigger(u, ex.circuit.units))
+        throw 'dusp-hip: ' + who + ' does not take circuits with host-ticked units (' + u.label + '): render them one by one'
+  const count = extractions.length, sampleRate = extractions[0].sampleRate
+  const durations = typeof voiceDurations === 'number' ? new Array(count).fill(voiceDurations) : Array.from(voiceDurations)
+  if (durations.length !== count) throw 'dusp-hip: ' + who + ': voiceDurations must be one number or hold one value per outlet'
+  const voiceSamples = durations.map((x) => sampleCount(x, sampleRate))
+  if (voiceSamples.some((x) => x === 0)) throw 'dusp-hip: ' + who + ': voiceDuration must cover at least one sample'
+  const nSamples = sampleCount(duration, sampleRate)
+  const onsets = wholeSamples(who, 'onsets', opts.onsets, count)
+  let lengths = null
+  if (opts.lengths !== undefined && opts.lengths !== null) {
+    lengths = wholeSamples(who, 'lengths', opts.lengths, count)
+    for (let k = 0; k < count; k++) if (Number(lengths[k]) < 0 || Number(lengths[k]) > voiceSamples[k]) throw 'dusp-hip: ' + who + ": lengths must lie in 0 .. the voice's own samples"
+  }
+  let g = null
+  if (gains !== undefined && gains !== null) {
+    g = gains instanceof Float32Array ? gains : Float32Array.from(gains)
+    if (g.length !== count) throw 'dusp-hip: ' + who + ': gains must hold one value per outlet'
+  }
+  if (!Number.isInteger(tileBytes) || tileBytes < 0) throw 'dusp-hip: ' + who + ': tileBytes must be 0 (the default tile) or a whole number of bytes'
+  const grouped = pieceParts(extractions, voiceSamples)
+  const n = native()
+  const nChannels = checkPieceChannels(grouped.parts.map((part) => n.descriptorChannels(part.uni.words)))
+  if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
+  const progs = []
+  try {
+    for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
+    const result = await n.renderPiece(progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
+      grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise)
+    return { nSamples, nChannels, sampleRate, result }
+  } finally {
+    for (const prog of progs) n.programDestroy(prog)
+  }
+}
+
+/* A PIECE of several instruments: renderScore over voices of ANY circuits, each rendered for its own voiceDurations[k] seconds (one
+ * number: all alike).  The voices are grouped into parts by structure and by samples a voice (pieceParts), every part is ONE program,
+ * and the device walks the caller's voice list in its own order (dusp_render_host_score_parts): what
+ * renderChannelData(Sum.many(outlets.map((v, k) => new Delay(v, onsets[k], maxDelay))), duration) computes, however the instruments
+ * interleave.  Voices whose circuits differ in output channels are refused before anything is built.  onsets, lengths (within the
+ * voice's own samples), gains and engine as renderScore; tileBytes: what a tile of voices may take on the device (0: the default). */
+async function renderPiece(outlets, opts = {}) {
+  const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
+  const channelData = []
+  channelData.sampleRate = sampleRate
+  if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
+  return channelData
+}
+
+async function renderPiecePcm(outlets, opts = {}) {
+  const { bitDepth = 16, normalise = 0 } = opts
+  if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderPiecePcm: bitDepth must be 16, 24 or 32'
+  if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderPiecePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
+  const { nChannels, sampleRate, result } = await pieceCall('renderPiecePcm', outlets, opts, PCM_FORMAT[bitDepth], normalise)
+  if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
+  return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
+}
+
+async function renderPieceWav(outlets, opts = {}) {
+  return encodeWav(await renderPiecePcm(outlets, opts))
+}
+
 /* A flat descriptor (what lib/extract.js produces — from this package's graph classes or from the reference's own objects,
  * patches included: their units reach the extractor as they are) rendered as it stands: no host objects, hence no events,
  * no host-ticked units, no state write-back.  Resolves to channelData like renderChannelData. */
@@ -499,6 +606,12 @@ module.exports.renderMixWav = renderMixWav
 module.exports.renderScore = renderScore
 module.exports.renderScorePcm = renderScorePcm
 module.exports.renderScoreWav = renderScoreWav
+module.exports.renderPiece = renderPiece
+module.exports.renderPiecePcm = renderPiecePcm
+module.exports.renderPieceWav = renderPieceWav
+module.exports.pieceParts = pieceParts
+module.exports.structureKey = structureKey
+module.exports.checkPieceChannels = checkPieceChannels
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

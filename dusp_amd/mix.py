@@ -100,3 +100,69 @@ def score_chain(planar, onsets, n_total, lengths=None, gains=None, init=None, ra
         if not raw:
             acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
     return acc
+
+
+def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None, raw=False):
+    """rows: a list of float32 arrays [channels, samples_k] — every voice a row of its own length, all of one channel count — onsets
+    int64 [voices] -> float32 [channels, n_total]: the contract of dusp_score_rows_device.  The chain is score_chain's, word for word: it
+    starts from `init` or +0, the voices go in index order, voice k takes part only where 0 <= t - onset_k < len_k (lengths None: the
+    whole row; else 0 <= len_k <= samples_k), a term is f32(x * g_k) when gains are given, one f32 rounding per add, and `acc || 0`
+    unless raw.  Rows of one length give exactly score_chain of their stack; a piece of several instruments, each rendered for its own
+    note length, is one such chain over the voices in the caller's order."""
+    rows = [np.asarray(r, dtype=np.float32) for r in rows]
+    n = len(rows)
+    if any(r.ndim != 2 for r in rows):
+        raise ValueError("dusp-hip: every row must have shape (channels, samples)")
+    if int(n_total) != n_total or n_total < 0:
+        raise ValueError("dusp-hip: n_total must be a whole number of samples, not negative")
+    n_total = int(n_total)
+    if n:
+        n_ch = rows[0].shape[0]
+    elif init is not None:
+        n_ch = np.asarray(init).shape[0] if np.asarray(init).ndim == 2 else 0
+    else:
+        n_ch = 1
+    if any(r.shape[0] != n_ch for r in rows):
+        raise ValueError("dusp-hip: every row must have the same number of channels (%d)" % n_ch)
+
+    def whole(values, name):
+        a = np.asarray(values)
+        if a.shape != (n,):
+            raise ValueError("dusp-hip: %s must have shape (voices=%d,)" % (name, n))
+        if a.dtype.kind not in "iu":
+            if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
+                raise ValueError("dusp-hip: %s are whole numbers of samples" % name)
+        return a.astype(np.int64)
+
+    onsets = whole(onsets, "onsets")
+    samples = np.array([r.shape[1] for r in rows], dtype=np.int64)
+    if lengths is None:
+        lengths = samples
+    else:
+        lengths = whole(lengths, "lengths")
+        if np.any(lengths < 0) or np.any(lengths > samples):
+            k = int(np.argmax((lengths < 0) | (lengths > samples)))
+            raise ValueError("dusp-hip: the length of voice %d is %d: lengths must lie in 0 .. the row's samples (%d)" % (k, int(lengths[k]), int(samples[k])))
+    if gains is not None:
+        gains = np.asarray(gains, dtype=np.float32)
+        if gains.shape != (n,):
+            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+    if init is not None:
+        init = np.asarray(init, dtype=np.float32)
+        if init.shape != (n_ch, n_total):
+            raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
+    with np.errstate(all="ignore"):
+        acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
+        for k in range(n):
+            onset, length = int(onsets[k]), int(lengths[k])
+            t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
+            if t1 <= t0:
+                continue
+            term = rows[k][:, t0 - onset:t1 - onset]
+            if gains is not None:
+                term = term * gains[k]  # float32 * float32 scalar: one f32 rounding
+            acc[:, t0:t1] = acc[:, t0:t1] + term  # float32 + float32: one f32 rounding
+        assert acc.dtype == np.float32
+        if not raw:
+            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
+    return acc

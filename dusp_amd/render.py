@@ -257,6 +257,137 @@ def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16
     return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
 
 
+class PieceParts:
+    """A voice list grouped into the parts of a piece (piece_parts): parts[p] = (Unified, n_voice_samples) — the voices of one structure
+    and one length in samples, unified in the order they come in the list — and, per voice of the list, part_of[k] and instance_of[k]:
+    voice k is instance instance_of[k] of part part_of[k], which is also the next unused instance of that part."""
+
+    def __init__(self, parts, part_of, instance_of, sample_rate):
+        self.parts, self.part_of, self.instance_of, self.sample_rate = parts, part_of, instance_of, sample_rate
+
+
+def structure_key(extraction):
+    """What two extractions have in common exactly when descriptor.unify takes them as instances of one program: the descriptor's words
+    with the values at the constant sites masked (twin of extract.js structureKey)."""
+    words = np.array(extraction.words, dtype=np.float64)
+    for (_, vpos, cnt) in extraction.const_sites:
+        words[vpos:vpos + cnt] = 0
+    return words.tobytes()
+
+
+def piece_parts(extractions, voice_samples):
+    """Group the voices of a piece into parts by structure (structure_key) and by voice_samples[k]; parts are numbered in the order their
+    first voice comes in the list.  Needs no device.  -> PieceParts"""
+    if len(extractions) == 0:
+        raise descriptor.DuspError("dusp-hip: no instances")
+    rates = {e.sample_rate for e in extractions}
+    if len(rates) != 1:
+        raise descriptor.DuspError("dusp-hip: the voices of a piece have one sample rate, not %s" % sorted(rates))
+    index, members, part_of, instance_of = {}, [], [], []
+    for e, n in zip(extractions, voice_samples):
+        key = (int(n), structure_key(e))
+        if key not in index:
+            index[key] = len(members)
+            members.append([])
+        p = index[key]
+        part_of.append(p)
+        instance_of.append(len(members[p]))
+        members[p].append(e)
+    samples = [n for (n, _) in index]  # (dicts keep insertion order: part p's key is the p-th)
+    parts = [(descriptor.unify(m), samples[p]) for p, m in enumerate(members)]
+    return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
+
+
+def check_piece_channels(channels):
+    """channels[p]: the output channels of part p's circuit.  A piece has one channel count: refused by string otherwise."""
+    for p, c in enumerate(channels):
+        if c != channels[0]:
+            raise descriptor.DuspError("dusp-hip: the voices of a piece must have one number of output channels: part %d has %d, part 0 has %d" % (p, c, channels[0]))
+    return channels[0]
+
+
+def _piece(outlets, onsets, voice_durations, duration, lengths, gains):
+    """-> PieceParts, samples per voice, samples of timeline, onsets, lengths, gains, channels (all checked: nothing is built yet)"""
+    extractions = [descriptor.extract(o) for o in outlets]
+    n = len(extractions)
+    if n == 0:
+        raise descriptor.DuspError("dusp-hip: no instances")
+    rate = extractions[0].sample_rate
+    durations = np.asarray(voice_durations, dtype=np.float64)
+    if durations.ndim == 0:
+        durations = np.full(n, float(durations))
+    if durations.shape != (n,):
+        raise ValueError("dusp-hip: voice_durations must be one number or have shape (voices=%d,)" % n)
+    voice_samples = [_n_samples(float(x), rate) for x in durations]
+    if min(voice_samples) == 0:
+        raise descriptor.DuspError("dusp-hip: voice_duration must cover at least one sample")
+    n_total = _n_samples(duration, rate)
+    onsets = runtime._whole_samples(onsets, n, "onsets")
+    if lengths is not None:
+        lengths = runtime._whole_samples(lengths, n, "lengths")
+        if np.any(lengths < 0) or np.any(lengths > np.array(voice_samples)):
+            raise ValueError("dusp-hip: lengths must lie in 0 .. the voice's own samples")
+    if gains is not None:
+        gains = np.ascontiguousarray(gains, dtype=np.float32)
+        if gains.shape != (n,):
+            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+    grouped = piece_parts(extractions, voice_samples)
+    channels = check_piece_channels([runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts])
+    return grouped, n_total, onsets, lengths, gains, channels
+
+
+def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0):
+    ctx = context(grouped.sample_rate, device)
+    programs = []
+    try:
+        for uni, _ in grouped.parts:
+            programs.append(ctx.build(uni.words, engine))
+        parts = [(prog, n_voice, uni.n_instances, uni.params) for prog, (uni, n_voice) in zip(programs, grouped.parts)]
+        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise)
+    finally:
+        for prog in programs:
+            prog.close()
+
+
+def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0):
+    """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
+    (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
+    program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
+    renders — what `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes, however the instruments
+    interleave.  Voices of one structure and one duration give render_score's bits.  Voices whose circuits differ in output channels are
+    refused before anything is built.  onsets and lengths are in SAMPLES (lengths within the voice's own samples), durations in seconds."""
+    grouped, n_total, onsets, lengths, gains, _ = _piece(outlets, onsets, voice_durations, duration, lengths, gains)
+    result = ChannelData()
+    result.sampleRate = grouped.sample_rate
+    if n_total > 0:
+        result.extend(_render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes))
+    return result
+
+
+def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
+                     tile_bytes=0):
+    """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
+    if bit_depth not in _PCM_FORMAT:
+        raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
+    if normalise not in (0, 1, 2):
+        raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
+    grouped, n_total, onsets, lengths, gains, channels = _piece(outlets, onsets, voice_durations, duration, lengths, gains)
+    if n_total == 0:
+        data, peak = wav.encode_frames(np.zeros((channels, 0), dtype=np.float32), bit_depth, normalise)
+    else:
+        data, peak = _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, _PCM_FORMAT[bit_depth], normalise)
+    return PcmData(data, bit_depth, grouped.sample_rate, peak)
+
+
+def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
+                     tile_bytes=0):
+    """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
+    pcm = render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes)
+    if bit_depth == 32:
+        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
+    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+
+
 class PcmData:
     """Encoded frames of one render: `data` int16 [samples, channels] (bitDepth 16), uint8 [samples, channels, 3] (24) or float32
     [samples, channels] (32); `peak` is the render's max |x| before the gain.  wav.encode_wav(data, sampleRate, bitDepth) makes a file of it."""

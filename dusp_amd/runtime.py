@@ -26,6 +26,7 @@ EXPORTS = [
     "dusp_host_alloc", "dusp_host_free", "dusp_circuit_kernel_source", "dusp_jit_cache_dir", "dusp_render_chain_window", "dusp_device_count",
     "dusp_peak_device", "dusp_encode_device", "dusp_render_host_pcm", "dusp_mix_device", "dusp_render_host_mix",
     "dusp_score_device", "dusp_render_host_score", "dusp_score_last_ms",
+    "dusp_score_rows_device", "dusp_render_host_score_parts", "dusp_descriptor_channels",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -92,6 +93,9 @@ def load():
     L.dusp_score_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, ci, vp, vp]
     L.dusp_score_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.dusp_render_host_score.argtypes = [vp, sz, sz, sz, vp, vp, vp, vp, sz, ci, ci, vp, vp]
+    L.dusp_score_rows_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, ci, vp, vp]
+    L.dusp_render_host_score_parts.argtypes = [vp, sz, sz, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    L.dusp_descriptor_channels.argtypes = [vp, sz]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -105,6 +109,11 @@ def load():
     L.dusp_circuit_kernel_source.argtypes = [vp, sz, ci, ci, ci, ci, ctypes.c_char_p, sz]
     _lib = L
     return L
+
+
+class ScorePart(ctypes.Structure):
+    """dusp_score_part: one instrument of a piece (dusp_render_host_score_parts)"""
+    _fields_ = [("prog", ctypes.c_void_p), ("n_instances", ctypes.c_size_t), ("n_voice_samples", ctypes.c_size_t), ("h_params", ctypes.c_void_p)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -136,6 +145,16 @@ def circuit_kernel_source(words, waves=16, per_wave=1, lds_table=True, compile=F
     if n < 0:
         raise DuspHipError(n, L.dusp_last_error(None).decode())
     return buf.value.decode()
+
+
+def descriptor_channels(words):
+    """How many output channels the circuit of a descriptor has (dusp_descriptor_channels: host code only, needs no GPU)."""
+    L = load()
+    words = np.ascontiguousarray(words, dtype=np.float64)
+    n = L.dusp_descriptor_channels(words.ctypes.data, words.size)
+    if n < 0:
+        raise DuspHipError(n, L.dusp_last_error(None).decode())
+    return n
 
 
 def _pcm_format(format):
@@ -263,6 +282,79 @@ class Context:
             lp = lengths.ctypes.data
         self._check(self._L.dusp_score_device(self._h, d_planar, n_instances, n_channels, n_voice_samples, onsets.ctypes.data if n_instances else None, lp, d_gains,
                                               n_total_samples, d_init, int(bool(raw)), d_out, stream))
+
+    def score_rows_device(self, rows, row_samples, n_channels, onsets, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, stream=None):
+        """score_device over voices that each lie in a buffer of their own (dusp_score_rows_device; dusp_amd/mix.py score_chain_rows is the
+        contract): rows are the voices' DEVICE pointers (ints; None or 0 for a voice of no samples), voice k planar f32
+        [n_channels][row_samples[k]].  onsets and lengths are HOST arrays of whole numbers of samples, lengths in 0 .. row_samples[k].
+        Everything else as score_device; score_last_ms() reports the call."""
+        n = len(rows)
+        samples = np.asarray(row_samples) if n else np.zeros(0, dtype=np.uint32)
+        if samples.shape != (n,) or samples.dtype.kind not in "iu" or np.any(samples < 0) or np.any(samples > 0xffffffff):
+            raise ValueError("dusp-hip: row_samples must be whole numbers 0 .. 2^32 - 1 of shape (voices=%d,)" % n)
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        pointers = np.array([int(r or 0) for r in rows], dtype=np.uint64)
+        onsets = _whole_samples(onsets, n, "onsets")
+        lp = None
+        if lengths is not None:
+            lengths = _whole_samples(lengths, n, "lengths")
+            lp = lengths.ctypes.data
+        self._check(self._L.dusp_score_rows_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, n_channels,
+                                                   onsets.ctypes.data if n else None, lp, d_gains, n_total_samples, d_init, int(bool(raw)), d_out, stream))
+
+    def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None):
+        """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
+        (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
+        chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
+        on its compiled kernel, in the caller's voice order, whatever tile_bytes (0: the library's default) cuts the voice list into.
+        onsets, lengths, gains: per voice, in chain order; format, normalise and what is returned: as Program.render_score."""
+        if not parts:
+            raise ValueError("dusp-hip: a piece has at least one part")
+        n = len(part_of)
+        part_of = np.asarray(part_of)
+        if part_of.shape != (n,) or part_of.dtype.kind not in "iu" or np.any(part_of < 0) or np.any(part_of >= len(parts)):
+            raise ValueError("dusp-hip: part_of names a part, 0 .. %d, for each voice" % (len(parts) - 1))
+        part_of = np.ascontiguousarray(part_of, dtype=np.uint32)
+        onsets = _whole_samples(onsets, n, "onsets")
+        lp = gp = None
+        if lengths is not None:
+            lengths = _whole_samples(lengths, n, "lengths")
+            lp = lengths.ctypes.data
+        if gains is not None:
+            gains = np.ascontiguousarray(gains, dtype=np.float32)
+            if gains.shape != (n,):
+                raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+            gp = gains.ctypes.data
+        if int(tile_bytes) < 0:
+            raise ValueError("dusp-hip: tile_bytes must be 0 (the default tile) or a number of bytes")
+        table = (ScorePart * len(parts))()
+        keep = []  # (the parameter tables, alive across the call)
+        for p, (prog, n_voice_samples, n_instances, params) in enumerate(parts):
+            pp = None
+            if prog.n_params:
+                params = np.ascontiguousarray(params, dtype=np.float32)
+                if params.shape != (prog.n_params, n_instances):
+                    raise ValueError("dusp-hip: the params of part %d must have shape (n_params=%d, n_instances=%d)" % (p, prog.n_params, n_instances))
+                keep.append(params)
+                pp = params.ctypes.data
+            table[p] = ScorePart(prog._h, n_instances, n_voice_samples, pp)
+        n_ch = parts[0][0].n_out_channels
+        call = self._L.dusp_render_host_score_parts
+        if format is None:
+            out = self.host_empty((n_ch, n_total_samples), pinned)
+            self._check(call(table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, lp, gp, n_total_samples, int(tile_bytes), 0, 0, out.ctypes.data, None))
+            return out
+        fmt = _pcm_format(format)
+        if fmt not in PCM_BYTES:
+            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
+        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
+            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
+        shape = (n_total_samples, n_ch)
+        out = self.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
+        peak = np.empty(1, dtype=np.float32)
+        self._check(call(table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, lp, gp, n_total_samples, int(tile_bytes), fmt, int(normalise), out.ctypes.data,
+                         peak.ctypes.data))
+        return out, peak[0]
 
     def score_last_ms(self):
         """-> (kernel_ms, plan_ms, upload_ms) of the most recent score_device call (dusp_score_last_ms; waits for that launch): the kernel
@@ -471,9 +563,9 @@ class Program:
         return ms.value
 
     def close(self):
-        if self._h:
+        if self._h and self.ctx._h:  # (a context finalized first — the collector's order at exit — has taken its device with it)
             self._L.dusp_program_destroy(self._h)
-            self._h = None
+        self._h = None
 
     def __del__(self):
         try:

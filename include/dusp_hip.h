@@ -358,6 +358,48 @@ int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voic
                            const float *h_gains, const int64_t *h_onsets, const int64_t *h_lengths, size_t tile_instances, int format,
                            int normalise, void *h_out, float *h_peak);
 
+/* The score's chain over voices that each lie in a buffer of their own (additions to ABI v7, detected by symbol): voice k is planar f32
+ * [n_channels][h_row_samples[k]] at the DEVICE address h_rows[k] — rows of any length, rendered by any program — and
+ *   out[c][t] = acc || 0,  acc = init ? init[c][t] : +0;  for k in index order: s = t - onset_k;
+ *                                                           if (0 <= s < len_k) acc = f32(acc + term_k)
+ * with term_k = d_gains ? f32(row_k[c][s] * g_k) : row_k[c][s]: dusp_score_device's chain word for word (dusp_amd/mix.py
+ * score_chain_rows is the contract in numpy), so that a piece of several instruments, each rendered for its own note length, is ONE chain
+ * over the caller's voice list, in its index order, however the instruments interleave.
+ *   h_rows, h_row_samples   HOST arrays [n_voices]: the rows' device addresses (4-byte aligned; ignored, and may be NULL, where
+ *                           h_row_samples[k] is 0) and their samples per channel; n_channels * h_row_samples[k] <= 2^31
+ *   h_lengths               HOST array, 0 <= len_k <= h_row_samples[k], or NULL for the whole rows
+ *   everything else         as dusp_score_device: asynchronous on `stream`, the plan in the context's plan buffer, n_voices = 0 legal,
+ *                           d_init may be d_out, dusp_score_last_ms reports the call
+ * The rows must stay as they are until the launch has run.  DUSP_ERR_ARG, with a message, for a NULL or misaligned row of a voice that
+ * has samples, a length outside its row, a row beyond 2^31 floats, and dusp_score_device's timeline limits. */
+int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels,
+                           const int64_t *h_onsets, const int64_t *h_lengths, const float *d_gains, size_t n_total_samples,
+                           const float *d_init, int raw, float *d_out, void *stream);
+
+/* A piece of several instruments: part p is a program, rendered for n_voice_samples per instance with the slot-major parameter table
+ * h_params [n_params][n_instances].  Voice k of the chain is the NEXT UNUSED instance of part h_part_of[k]: a part's instances enter the
+ * chain in their own order, parts may interleave freely (notes in time order, say), and h_part_of must name part p exactly
+ * parts[p].n_instances times.  The result is dusp_score_rows_device's chain over what each program renders, bit for bit whatever the
+ * tiles.  A tile is a run of the chain's voices whose rows together fit tile_bytes (0: a default derived as dusp_render_host_mix
+ * derives its own, over bytes); a part's share of a tile is one contiguous instance range, rendered as one batch by that part's program
+ * — with what changes bits decided from the WHOLE part, as dusp_render_host_mix decides it — and skipped where none of its voices in
+ * the tile reaches the timeline; then one raw launch continues the timeline in place over the tile's union window.  All tiles' plans
+ * are made up front under the one 16 MiB budget.  Device memory: one tile buffer per part, the timeline, the plans, 4 bytes a voice
+ * for the gains.
+ *   h_onsets, h_lengths, h_gains   [n_voices], in chain order; lengths within the voice's own part's n_voice_samples
+ *   format, normalise, h_out, h_peak   as for dusp_render_host_score
+ * Refused with a message: programs of different contexts or output channel counts, a program listed twice (its tile buffer would be
+ * used twice), and what dusp_render_host_score refuses of any one part.  The state afterwards is dusp_render_host_mix's, for every part. */
+typedef struct {
+    dusp_program *prog;
+    size_t n_instances;
+    size_t n_voice_samples;
+    const float *h_params;
+} dusp_score_part;
+int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                 const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains, size_t n_total_samples,
+                                 size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:
@@ -365,6 +407,12 @@ int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voic
  * Shape: t,playing,finished; AHD: state,playing,t; SampleRateRedux: timeSinceLastUpdate,n,val*n).
  * Returns the number of words (>= 0) or a negative dusp_status. */
 int dusp_state_download(dusp_program *prog, size_t instance, size_t unit, double *out, size_t cap);
+
+/* How many output channels the circuit of a descriptor has, as dusp_program_build would find (dusp_program_info.n_out_channels) — on
+ * the host alone: no context, no GPU.  A binder that groups voices into the parts of a piece (dusp_render_host_score_parts) refuses
+ * parts of different channel counts with this, before it builds anything.  Negative: DUSP_ERR_ARG for a descriptor that does not parse
+ * (dusp_last_error(NULL) has the message).  An addition to ABI v7, detected by symbol. */
+int dusp_descriptor_channels(const double *desc, size_t n_words);
 
 /* The circuit compiler, on its own (needs no device).  Programs on the WAVE engine whose units it knows are rendered by ONE
  * kernel generated for that circuit — the chunk loop of src/Circuit.js:19-41 with every unit's `_tick` inlined in process

@@ -6,7 +6,8 @@
           yardstick, and against bytes read / the float4-copy rate.  The mix kernel by HIP events on the launch stream (its call does no
           host work); the score kernel by the events the library records around the launch alone (dusp_score_last_ms), with the plan's
           host time and the upload's time, which precede the launch inside the call, reported beside it.  The plan's default block and a
-          block forced to cover the whole timeline (DUSP_SCORE_PLAN_KB=1: one list for every workgroup) side by side.
+          block forced to cover the whole timeline (DUSP_SCORE_PLAN_KB=1: one list for every workgroup) side by side.  Then the rows
+          kernel (dusp_score_rows_device) over the same buffer, its rows handed over as pointers of their own (profiles/score_rows.txt).
   piece   8192 notes of 0.5 s placed over 60 s in onset order: Program.render_score on the host's clock, against the render of the same
           notes alone (render_device into a preallocated buffer) and against the same piece with the onsets shuffled — every tile's
           union window is then the whole timeline, which is what the window is worth.  One run under DUSP_JIT_LOG=2 prints the plans'
@@ -58,6 +59,18 @@ def dense(key, scale, ctxs, reps):
                 kernel.append(k), plan.append(p), upload.append(u)
         med = float(np.median(kernel))
         print(line % ((label, med, min(kernel)) + rate(med) + ("   [plan on the host %.2f ms, its upload %.2f ms]" % (float(np.median(plan)), float(np.median(upload))),)), flush=True)
+    # the rows kernel (dusp_score_rows_device) over the SAME buffer, every row handed over as a pointer of its own: what the 32-byte record
+    # and the address taken from it cost against the score kernel above, which is the yardstick (profiles/score_rows.txt)
+    pointers = [rows.data_ptr() + 4 * n * k for k in range(V)]
+    samples = np.full(V, n, dtype=np.uint32)
+    kernel, plan, upload = [], [], []
+    for r in range(reps + 1):
+        ctxs["default"].score_rows_device(pointers, samples, 1, onsets, n, acc.data_ptr(), stream=s)
+        k, p, u = ctxs["default"].score_last_ms()
+        if r:
+            kernel.append(k), plan.append(p), upload.append(u)
+    med = float(np.median(kernel))
+    print(line % (("rows kernel, default block", med, min(kernel)) + rate(med) + ("   [plan on the host %.2f ms, its upload %.2f ms]" % (float(np.median(plan)), float(np.median(upload))),)), flush=True)
 
 
 def piece(scale, ctxs, reps):
