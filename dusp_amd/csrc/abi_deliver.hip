@@ -1,6 +1,7 @@
 // abi_deliver.hip — the C ABI (include/dusp_hip.h): what happens to rendered PCM on the device (interleave, peak, encode, mix, score, score over rows) and how
 // it reaches the host (dusp_render_host* and their delivery paths, dusp_render_host_mix, dusp_render_host_score, dusp_render_host_score_parts).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -399,6 +400,7 @@ struct ScoreLaunch {
     uint64_t w_lo = 0, w_hi = 0, first_block = 0;
     uint32_t block_shift = dusp::kScoreGroupShift;
     bool any = false;  // some voice reaches the timeline (else: no plan in the image)
+    size_t pan_at = 0;  // a panned launch: byte offset of its voices' coefficients (dusp::ScorePan), behind the plan
 };
 
 // before a call rewrites the context's host image: the last upload has read it
@@ -617,22 +619,64 @@ static int score_rows_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_chann
     return DUSP_OK;
 }
 
-int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
-                           const int64_t *h_lengths, const float *d_gains, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
+// ---- pans: mono rows placed in the stereo field where they are added (score_pan_engine.hip; dusp_amd/mix.py score_chain_rows_panned) ----
+
+static int check_pans(dusp_ctx *ctx, const char *who, const float *h_pans, const double *h_comp, size_t n) {
+    for (size_t k = 0; k < n; k++) {
+        if (!std::isfinite(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
+        if (h_comp && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
+    }
+    return DUSP_OK;
+}
+
+// the coefficients of the voices [0, n) of the plan just added (L), appended to the context's host image on a 32-byte boundary: they go
+// up with the plan.  h_comp NULL: the reference's compensation by the host's pow (Pan.js:20)
+static void score_pan_image_add(dusp_ctx *ctx, const float *h_pans, const double *h_comp, size_t n, ScoreLaunch &L) {
+    if (!L.any) return;
+    std::vector<unsigned char> &image = ctx->h_score_plan;
+    L.pan_at = (image.size() + 31) & ~(size_t)31;
+    image.resize(L.pan_at + n * sizeof(dusp::ScorePan));
+    for (size_t k = 0; k < n; k++) {
+        const double comp = h_comp ? h_comp[k] : std::pow(10.0, ((1.0 - std::fabs((double)h_pans[k])) * 1.5) / 20.0);
+        const dusp::ScorePan c = dusp::score_pan_coefficients(h_pans[k], comp);
+        std::memcpy(image.data() + L.pan_at + k * sizeof c, &c, sizeof c);
+    }
+}
+
+// score_rows_launch over mono rows into a timeline of two channels
+static int score_pan_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_total, const float *d_gains, const float *d_init, int raw, float *d_out, hipStream_t stream) {
+    if (L.w_hi <= L.w_lo) return DUSP_OK;
+    const dusp::ScoreRow *d_voices = L.any ? (const dusp::ScoreRow *)(ctx->d_score_plan + L.at) : nullptr;
+    const dusp::ScorePan *d_pans = L.any ? (const dusp::ScorePan *)(ctx->d_score_plan + L.pan_at) : nullptr;
+    const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices) : nullptr;
+    HIP_TRY(ctx, dusp::launch_score_pan(d_gains, d_pans, d_voices, d_block_first, L.any ? d_block_first + L.n_block_first : nullptr, d_init, d_out, n_total, L.w_lo, L.w_hi,
+                                        L.block_shift, L.first_block, raw, stream));
+    if (L.any) HIP_TRY(ctx, hipEventRecord(ctx->score_done, stream));
+    return DUSP_OK;
+}
+
+// dusp_score_rows_device, and (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device
+static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                             const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw,
+                             float *d_out, void *stream_) {
     if (!ctx) return DUSP_ERR_ARG;
-    return guarded(ctx->err, "dusp_score_rows_device", [&]() -> int {
-    if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: NULL buffer");
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    const size_t n_out_channels = h_pans ? 2 : n_channels;  // (the timeline's)
+    if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
     if (!channels_in_range(n_channels) || n_voices > (1u << 24) || !samples_in_range(n_total_samples))
-        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: need 1..64 channels, 0..2^24 voices and 1..2^31 samples of timeline");
-    if (n_channels * n_total_samples > dusp::kScoreRowMax)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
-    if ((((uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: the buffers must be 4-byte aligned");
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..64 channels, 0..2^24 voices and 1..2^31 samples of timeline");
+    if (n_out_channels * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
+    if ((((uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
     for (size_t k = 0; k < n_voices; k++) {
         if ((uint64_t)h_row_samples[k] * n_channels > dusp::kScoreRowMax)
-            CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: voice " + std::to_string(k) + ": channels x row samples must not exceed 2^31");
-        if (h_row_samples[k] && !h_rows[k]) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: the row of voice " + std::to_string(k) + " is NULL");
-        if (h_row_samples[k] && ((uintptr_t)h_rows[k] & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_device: the row of voice " + std::to_string(k) + " must be 4-byte aligned");
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + ": channels x row samples must not exceed 2^31");
+        if (h_row_samples[k] && !h_rows[k]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " is NULL");
+        if (h_row_samples[k] && ((uintptr_t)h_rows[k] & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " must be 4-byte aligned");
     }
+    if (h_pans)
+        if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_of(ctx, stream_);
     ScoreLaunch L;
@@ -641,9 +685,10 @@ int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint
         if (int rc = score_image_begin(ctx)) return rc;
         const auto t_plan = std::chrono::steady_clock::now();
         static_assert(sizeof(const float *) == sizeof(uint64_t), "rows are handed to the planner as 64-bit addresses");
-        if (int rc = score_rows_image_add(ctx, "dusp_score_rows_device", h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples,
+        if (int rc = score_rows_image_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples,
                                           /*whole_timeline=*/true, score_plan_budget(ctx), L))
             return rc;
+        if (h_pans) score_pan_image_add(ctx, h_pans, h_comp, n_voices, L);
         ctx->score_plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan).count();
         if (int rc = score_image_upload(ctx, stream)) return rc;
     } else {
@@ -655,29 +700,51 @@ int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint
     ctx->score_timed = false;
     ctx->score_upload_timed = L.any;
     HIP_TRY(ctx, hipEventRecord(ctx->score_t0, stream));
-    if (int rc = score_rows_launch(ctx, L, n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream)) return rc;
+    if (h_pans) {
+        if (int rc = score_pan_launch(ctx, L, n_total_samples, d_gains, d_init, raw != 0, d_out, stream)) return rc;
+    } else if (int rc = score_rows_launch(ctx, L, n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream))
+        return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->score_t1, stream));
     ctx->score_timed = true;
     return DUSP_OK;
     });
 }
 
-int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
-                                 const int64_t *h_lengths, const float *h_gains, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out,
-                                 float *h_peak) {
-    const char *who = "dusp_render_host_score_parts";
+int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                           const int64_t *h_lengths, const float *d_gains, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
+    return score_rows_device(ctx, "dusp_score_rows_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, nullptr, nullptr, n_total_samples, d_init,
+                             raw, d_out, stream_);
+}
+
+int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, const int64_t *h_onsets, const int64_t *h_lengths,
+                               const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw, float *d_out,
+                               void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (n_voices && !h_pans) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_pan_device: h_pans is NULL");
+    static const float no_pans[1] = {0.0f};  // (no voices: `|| 0`, or a copy, of both channels of d_init)
+    return score_rows_device(ctx, "dusp_score_rows_pan_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, h_pans ? h_pans : no_pans, h_comp,
+                             n_total_samples, d_init, raw, d_out, stream_);
+}
+
+// dusp_render_host_score_parts, and (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan
+static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                   const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
+                                   int format, int normalise, void *h_out, float *h_peak) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
-    const size_t n_ch = prog0->P.out_bufs.size();
+    const size_t n_ch = prog0->P.out_bufs.size(), n_out_ch = h_pans ? 2 : n_ch;  // (a voice's, the timeline's)
     if (!h_part_of || !h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of or h_onsets is NULL");
     if (n_voices < 1 || n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^24 voices");
     size_t n_listed = 0;
     for (size_t p = 0; p < n_parts; p++) {
         if (!parts[p].prog) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the program of part " + std::to_string(p) + " is NULL");
         if (parts[p].prog->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " was built on another context: all parts of a piece share one");
+        if (h_pans && parts[p].prog->P.out_bufs.size() != 1)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) +
+                                            " output channels: a panned voice is mono");
         if (parts[p].prog->P.out_bufs.size() != n_ch)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) + " output channels, part 0 has " +
                                             std::to_string(n_ch) + ": all parts of a piece have the same number");
@@ -686,8 +753,10 @@ int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, s
                 CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": parts " + std::to_string(q) + " and " + std::to_string(p) + " are the same program: its tile buffer would be used twice; make them one part or build it twice");
         n_listed += parts[p].n_instances;
     }
-    if (!samples_in_range(n_total_samples) || n_ch * n_total_samples > dusp::kScoreRowMax)
+    if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
+    if (h_pans)
+        if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
     // voice k of the chain: the next unused instance of part h_part_of[k]
     std::vector<size_t> instance_of(n_voices), used(n_parts, 0);
     for (size_t k = 0; k < n_voices; k++) {
@@ -750,6 +819,7 @@ int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, s
             if (int rc = score_rows_image_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
                                               /*whole_timeline=*/false, tile_budget, launches[i], &listed))
                 return rc;
+            if (h_pans) score_pan_image_add(ctx, h_pans + lo, h_comp ? h_comp + lo : nullptr, n, launches[i]);
             for (size_t k = 0; k < n; k++)
                 if (listed[k]) renders[i][h_part_of[lo + k]] = 1;
         }
@@ -757,13 +827,13 @@ int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, s
     if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: what the plans cost the host)
         fprintf(stderr, "[dusp host piece] %zu plans over %zu voices of %zu parts in %.0f us on the host: %zu bytes\n", n_tiles, n_voices, n_parts,
                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count(), ctx->h_score_plan.size());
-    HIP_TRY(ctx, prog0->d_mix.ensure(n_ch * n_total_samples));  // the timeline's running sums
+    HIP_TRY(ctx, prog0->d_mix.ensure(n_out_ch * n_total_samples));  // the timeline's running sums
     if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once)
         HIP_TRY(ctx, prog0->d_mix_gains.ensure(n_voices));
         HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
     if (int rc = score_image_upload(ctx, ctx->stream)) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix.p, 0, n_ch * n_total_samples * sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix.p, 0, n_out_ch * n_total_samples * sizeof(float), ctx->stream));
     std::vector<std::unique_ptr<TiledBatch>> whole;  // what changes bits is decided from the WHOLE part
     for (size_t p = 0; p < n_parts; p++) whole.emplace_back(new TiledBatch(parts[p].prog, parts[p].n_instances, parts[p].h_params, share[p]));
     auto waited = [&]() {
@@ -774,19 +844,37 @@ int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, s
         for (size_t p = 0; p < n_parts; p++)
             if (renders[i][p])
                 if (int rc = whole[p]->render_tile(share[p][i], share[p][i + 1] - share[p][i], parts[p].n_voice_samples)) return rc;
-        if (int rc = score_rows_launch(ctx, launches[i], n_ch, n_total_samples, h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p,
-                                       ctx->stream))
+        const float *d_gains = h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr;
+        if (h_pans) {
+            if (int rc = score_pan_launch(ctx, launches[i], n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream)) return rc;
+        } else if (int rc = score_rows_launch(ctx, launches[i], n_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream))
             return rc;
     }
     ScoreLaunch all;  // `|| 0` over the whole timeline
     all.w_hi = n_total_samples;
-    if (int rc = score_rows_launch(ctx, all, n_ch, n_total_samples, nullptr, prog0->d_mix.p, /*raw=*/0, prog0->d_mix.p, ctx->stream)) return rc;
-    if (int rc = deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
+    if (int rc = score_rows_launch(ctx, all, n_out_ch, n_total_samples, nullptr, prog0->d_mix.p, /*raw=*/0, prog0->d_mix.p, ctx->stream)) return rc;
+    if (int rc = deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
     waited();  // (the delivery has waited for the stream)
     if (g_guard_bytes && (!prog0->d_mix.intact() || !prog0->d_mix_gains.intact() || !score_plan_intact(ctx)))
         CTX_FAIL(ctx, DUSP_ERR_HIP, w + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
     return DUSP_OK;
     });
+}
+
+int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                 const int64_t *h_lengths, const float *h_gains, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out,
+                                 float *h_peak) {
+    return render_host_score_parts("dusp_render_host_score_parts", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, nullptr, nullptr, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak);
+}
+
+int dusp_render_host_score_parts_pan(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                     const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
+                                     int format, int normalise, void *h_out, float *h_peak) {
+    if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
+    if (!h_pans) CTX_FAIL(parts[0].prog->ctx, DUSP_ERR_ARG, "dusp_render_host_score_parts_pan: h_pans is NULL");
+    return render_host_score_parts("dusp_render_host_score_parts_pan", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak);
 }
 
 }  // extern "C"

@@ -210,4 +210,26 @@ inline size_t score_rows_plan_pack(const ScoreRowsPlan &P, std::vector<unsigned 
     return at;
 }
 
+// ---- pans: a place in the stereo field per voice of a rows plan (score_pan_engine.hip; dusp_amd/mix.py score_chain_rows_panned) ----
+
+// What the panned kernel multiplies a voice's sample by, made on the host: the reference's Pan unit (Pan.js:21-22) gives a sample x of a
+// voice panned to p
+//     left = f32(((f64(x) * (1 - f64(p))) / 2) * comp),   right = f32(((f64(x) * (1 + f64(p))) / 2) * comp),   comp = 10^((1 - |p|) * 1.5 / 20)
+// every f64 operation rounded by itself.  lm and rp are the IEEE operations 1 -+ f64(p) themselves.  The kernel computes
+// f32((f64(x) * lm) * ch) with ch = comp / 2 — one division a voice on the host instead of two a sample on the device — which is the same
+// f32: with y = f64(x) * lm, y / 2 is exact (y is 0, infinite, NaN, or no smaller than 2^-149 * 2^-24: halving a double so far above
+// the subnormals only lowers its exponent) and, as long as comp is a normal double (|p| < 4100), so is comp / 2; then (y / 2) * comp and
+// y * (comp / 2) are roundings of one and the same real number.  A comp that has underflowed to a subnormal or to 0 may lose its last
+// bit in the halving, and there both products are below 1e-260 in magnitude whatever x and p are: the same +-0 in f32, or the same NaN
+// from an infinite x.  tests/native/score_pan_kernel_check.cpp holds both statements.
+// (32 bytes on a 32-byte boundary: one eight-dword scalar load a voice, as ScoreRow)
+struct alignas(32) ScorePan {
+    double lm, rp;  // 1 - f64(p), 1 + f64(p)
+    double ch;      // comp / 2
+    double pad;
+};
+static_assert(sizeof(ScorePan) == 32, "one eight-dword scalar load");
+
+inline ScorePan score_pan_coefficients(float pan, double comp) { return ScorePan{1.0 - (double)pan, 1.0 + (double)pan, comp / 2.0, 0.0}; }
+
 }  // namespace dusp

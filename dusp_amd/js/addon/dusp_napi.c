@@ -750,6 +750,8 @@ typedef struct {
     uint32_t *part_of;
     int64_t *onsets, *lengths;
     float *gains, *out;
+    float *pans;      /* renderPiecePan: a pan per voice and its compensation (Math.pow's), else NULL */
+    double *comp;
     float peak;
     int format, normalise, rc;
     char err[512];
@@ -768,6 +770,8 @@ static void piece_free(napi_env env, piece_job *j) {
     free(j->onsets);
     free(j->lengths);
     free(j->gains);
+    free(j->pans);
+    free(j->comp);
     free(j->out);
     free(j);
 }
@@ -785,8 +789,12 @@ static void piece_execute(napi_env env, void *data) {
         j->parts[p].prog = j->pbs[p]->prog;
     }
     if (j->rc == DUSP_OK) {
-        j->rc = dusp_render_host_score_parts(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, j->n_total, j->tile_bytes, j->format, j->normalise,
-                                             j->out, j->format ? &j->peak : NULL);
+        if (j->pans)
+            j->rc = dusp_render_host_score_parts_pan(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, j->pans, j->comp, j->n_total, j->tile_bytes,
+                                                     j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+        else
+            j->rc = dusp_render_host_score_parts(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, j->n_total, j->tile_bytes, j->format,
+                                                 j->normalise, j->out, j->format ? &j->peak : NULL);
         if (j->rc != DUSP_OK) snprintf(j->err, sizeof j->err, "dusp-hip: %s", dusp_last_error(cb->ctx));
     }
     pthread_mutex_unlock(&cb->lock);
@@ -831,11 +839,14 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
 
 /* renderPiece(progs[], nInstances Float64Array, nVoiceSamples Float64Array, params[] (Float32Array | null each), partOf Uint32Array, onsets, lengths | null,
  *             gains | null, nTotalSamples, tileBytes, format, normalise)
- *   -> as renderScore (dusp_render_host_score_parts: voice k of the chain is the next unused instance of part partOf[k]) */
-static napi_value fn_render_piece(napi_env env, napi_callback_info info) {
-    napi_value argv[12];
+ *   -> as renderScore (dusp_render_host_score_parts: voice k of the chain is the next unused instance of part partOf[k])
+ * renderPiecePan(the same twelve, pans Float32Array, comp Float64Array)
+ *   -> the same over MONO parts, two channels out (dusp_render_host_score_parts_pan: voice k panned to pans[k] where it is added; comp[k] is
+ *      the reference's compensation, computed by the caller with Math.pow) */
+static napi_value render_piece_call(napi_env env, napi_callback_info info, int panned) {
+    napi_value argv[14];
     char msg[256];
-    if (!get_args(env, info, 12, argv)) return NULL;
+    if (!get_args(env, info, panned ? 14 : 12, argv)) return NULL;
     uint32_t n_parts = 0;
     bool is_array = false;
     if (napi_is_array(env, argv[0], &is_array) != napi_ok || !is_array || napi_get_array_length(env, argv[0], &n_parts) != napi_ok || n_parts < 1) {
@@ -904,6 +915,7 @@ static napi_value fn_render_piece(napi_env env, napi_callback_info info) {
         if (j->pbs[p]->cb != j->pbs[0]->cb) bad = "all parts of a piece are built on one context";
         else if (!(ni >= 1 && ni <= 16777216.0 && ni == (double)(size_t)ni && nv >= 1 && nv <= 2147483648.0 && nv == (double)(size_t)nv)) bad = "nInstances / nVoiceSamples out of range";
         else if (p && pi.n_out_channels != n_channels) bad = "all parts of a piece have one number of output channels";
+        else if (panned && pi.n_out_channels != 1) bad = "a panned voice is mono: every part has one output channel";
         if (bad) break;
         n_channels = pi.n_out_channels;
         j->parts[p].n_instances = (size_t)ni;
@@ -938,6 +950,18 @@ static napi_value fn_render_piece(napi_env env, napi_callback_info info) {
         else if (!(j->gains = (float *)malloc(len * sizeof(float)))) bad = "out of host memory for the gains";
         else memcpy(j->gains, data, len * sizeof(float));
     }
+    if (!bad && panned) {
+        void *pd, *cd;
+        size_t n_p = 0, n_c = 0;
+        if (!typed_array(env, argv[12], napi_float32_array, &pd, &n_p) || n_p != n_voices) bad = "pans must be a Float32Array of one value per voice";
+        else if (!typed_array(env, argv[13], napi_float64_array, &cd, &n_c) || n_c != n_voices) bad = "comp must be a Float64Array of one value per voice";
+        else if (!(j->pans = (float *)malloc(n_p * sizeof(float))) || !(j->comp = (double *)malloc(n_c * sizeof(double)))) bad = "out of host memory for the pans";
+        else {
+            memcpy(j->pans, pd, n_p * sizeof(float));
+            memcpy(j->comp, cd, n_c * sizeof(double));
+        }
+        n_channels = 2; /* the timeline's */
+    }
     j->n_floats = (size_t)n_channels * j->n_total;
     j->n_bytes = j->n_floats * (size_t)(!j->format || j->format == DUSP_PCM_F32 ? 4 : j->format == DUSP_PCM_S16 ? 2 : 3);
     if (!bad && !(j->out = (float *)malloc(j->n_bytes + 1))) bad = "out of host memory for the PCM buffer";
@@ -970,6 +994,9 @@ static napi_value fn_render_piece(napi_env env, napi_callback_info info) {
     return promise;
 }
 
+static napi_value fn_render_piece(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 0); }
+static napi_value fn_render_piece_pan(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 1); }
+
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
     napi_value argv[1], out;
@@ -1001,7 +1028,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"programDestroy", fn_program_destroy}, {"programInfo", fn_program_info}, {"stateDownload", fn_state_download},
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
-        {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels},
+        {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -445,10 +445,17 @@ function wholeSamples(who, name, values, count) {
  * is its input behind zeros; the voice with onset 0 bare) — rendered as ONE program for `voiceDuration` seconds a voice, tile by tile,
  * and mixed ON THE DEVICE at the onsets in Sum.many's chain order (dusp_render_host_score).  onsets and lengths are in samples, whole
  * numbers of any sign (a negative onset: the voice began before the timeline; lengths clip a voice to its first samples); the
- * durations are in seconds.  gains, engine, tileInstances and the refusals are renderMix's. */
+ * durations are in seconds.  gains, engine, tileInstances and the refusals are renderMix's.  pans: as renderPiece's — mono voices, two
+ * channels out, through the piece's call with the score as its one part (voiceDuration is one number; tileInstances does not apply). */
+function scoreAsPiece(opts) { // renderScore with pans: the piece's call with the score as its one part
+  return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
+}
+
 async function renderScore(outlets, opts = {}) {
   const { duration = 1 } = opts
-  const { nSamples, nChannels, sampleRate, result } = await mixCall('renderScore', outlets, duration, opts, 0, 0, true)
+  const { nSamples, nChannels, sampleRate, result } = opts.pans !== undefined && opts.pans !== null
+    ? await pieceCall('renderScore', outlets, scoreAsPiece(opts), 0, 0, true)
+    : await mixCall('renderScore', outlets, duration, opts, 0, 0, true)
   const channelData = []
   channelData.sampleRate = sampleRate
   if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
@@ -459,7 +466,9 @@ async function renderScorePcm(outlets, opts = {}) {
   const { duration = 1, bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderScorePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderScorePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result } = await mixCall('renderScorePcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise, true)
+  const { nChannels, sampleRate, result } = opts.pans !== undefined && opts.pans !== null
+    ? await pieceCall('renderScorePcm', outlets, scoreAsPiece(opts), PCM_FORMAT[bitDepth], normalise, true)
+    : await mixCall('renderScorePcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise, true)
   if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
   return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
 }
@@ -507,7 +516,26 @@ function checkPieceChannels(channels) {
   return channels[0]
 }
 
-async function pieceCall(who, outlets, opts, format, normalise) {
+/* channels[p]: the output channels of part p's circuit.  A panned voice is mono: refused by string otherwise (twin of render.py
+ * check_pan_channels). */
+function checkPanChannels(channels) {
+  channels.forEach((c, p) => {
+    if (c !== 1) throw 'dusp-hip: a panned voice is mono: part ' + p + ' has ' + c + ' output channels'
+  })
+  return 2
+}
+
+/* pans of `count` voices -> { pans: Float32Array, comp: Float64Array }: checked — one finite pan a voice, not clamped — with the
+ * reference Pan unit's compensation 10^((1 - |pan|) * 1.5 / 20) by Math.pow, as Pan.js computes it (twin of runtime.py pan_arrays). */
+function panArrays(pans, count) {
+  const ok = Array.isArray(pans) || pans instanceof Float32Array || pans instanceof Float64Array
+  const p = ok ? (pans instanceof Float32Array ? pans : Float32Array.from(pans)) : null
+  if (!p || p.length !== count) throw 'dusp-hip: pans must have shape (voices=' + count + ',)'
+  for (let k = 0; k < count; k++) if (!Number.isFinite(p[k])) throw 'dusp-hip: the pan of voice ' + k + ' is not finite'
+  return { pans: p, comp: Float64Array.from(p, (x) => Math.pow(10, ((1 - Math.abs(x)) * 1.5) / 20)) }
+}
+
+async function pieceCall(who, outlets, opts, format, normalise, onePart = false) {
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
   const extractions = outlets.map((o) => extract(o))
   if (extractions.length === 0) throw 'dusp-hip: no instances'
@@ -533,15 +561,19 @@ async function pieceCall(who, outlets, opts, format, normalise) {
     if (g.length !== count) throw 'dusp-hip: ' + who + ': gains must hold one value per outlet'
   }
   if (!Number.isInteger(tileBytes) || tileBytes < 0) throw 'dusp-hip: ' + who + ': tileBytes must be 0 (the default tile) or a whole number of bytes'
+  const panned = opts.pans !== undefined && opts.pans !== null ? panArrays(opts.pans, count) : null
   const grouped = pieceParts(extractions, voiceSamples)
+  if (onePart && grouped.parts.length !== 1) throw 'dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments'
   const n = native()
-  const nChannels = checkPieceChannels(grouped.parts.map((part) => n.descriptorChannels(part.uni.words)))
+  const channels = grouped.parts.map((part) => n.descriptorChannels(part.uni.words))
+  const nChannels = panned ? checkPanChannels(channels) : checkPieceChannels(channels)
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
   const progs = []
   try {
     for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
-    const result = await n.renderPiece(progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
-      grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise)
+    const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
+      grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
+    const result = panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
     return { nSamples, nChannels, sampleRate, result }
   } finally {
     for (const prog of progs) n.programDestroy(prog)
@@ -553,7 +585,10 @@ async function pieceCall(who, outlets, opts, format, normalise) {
  * and the device walks the caller's voice list in its own order (dusp_render_host_score_parts): what
  * renderChannelData(Sum.many(outlets.map((v, k) => new Delay(v, onsets[k], maxDelay))), duration) computes, however the instruments
  * interleave.  Voices whose circuits differ in output channels are refused before anything is built.  onsets, lengths (within the
- * voice's own samples), gains and engine as renderScore; tileBytes: what a tile of voices may take on the device (0: the default). */
+ * voice's own samples), gains and engine as renderScore; tileBytes: what a tile of voices may take on the device (0: the default).
+ * pans (one finite number a voice, -1 left .. +1 right, not clamped): the voices are MONO circuits and voice k is placed in the stereo
+ * field where it is added to the timeline (dusp_render_host_score_parts_pan) — what the reference renders for new Pan(voice_k, pans[k])
+ * in the voice's place, bit for bit, the compensation being this engine's own Math.pow.  The result has two channels. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   const channelData = []
@@ -612,6 +647,8 @@ module.exports.renderPieceWav = renderPieceWav
 module.exports.pieceParts = pieceParts
 module.exports.structureKey = structureKey
 module.exports.checkPieceChannels = checkPieceChannels
+module.exports.checkPanChannels = checkPanChannels
+module.exports.panArrays = panArrays
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

@@ -166,3 +166,91 @@ def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None,
         if not raw:
             acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
     return acc
+
+
+def pan_comp(pans):
+    """The reference Pan unit's compensation per voice, 10^((1 - |pan|) * 1.5 / 20) (Pan.js:14-16), by the host's pow -> float64 [n]."""
+    import math
+    return np.array([math.pow(10, ((1 - abs(float(p))) * 1.5) / 20) for p in np.asarray(pans, dtype=np.float32).ravel()], dtype=np.float64)
+
+
+def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=None, init=None, raw=False, comp=None):
+    """rows: a list of MONO float32 arrays [1, samples_k], onsets int64 [voices], pans float32 [voices] (finite, NOT clamped) -> float32
+    [2, n_total]: the contract of dusp_score_rows_pan_device.  It is score_chain_rows with the reference's Pan unit (Pan.js:21-22) applied
+    where a voice is added to the timeline: for every timeline sample t
+
+        accL, accR = init[0][t], init[1][t] if init is given else +0, +0
+        for k in index order:  s = t - onset_k;  if 0 <= s < len_k:
+            x    = f32(row_k[0][s] * g_k) if gains is given else row_k[0][s]
+            accL = f32(accL + f32(((f64(x) * (1 - f64(p_k))) / 2) * comp_k))
+            accR = f32(accR + f32(((f64(x) * (1 + f64(p_k))) / 2) * comp_k))
+        out = acc if raw else (acc || 0)
+
+    every f64 operation rounded by itself.  comp: float64 [voices], None for pan_comp(pans).  Everything else — skipped adds, lengths
+    clipped in int64, onsets of any sign, raw partial sums continued through init, windows of the timeline — is score_chain_rows' word for
+    word.  It is what the reference renders for Sum.many(Delay(Pan(Multiply(voice_k, g_k), pan_k), onset_k, maxDelay))."""
+    rows = [np.asarray(r, dtype=np.float32) for r in rows]
+    n = len(rows)
+    if any(r.ndim != 2 or r.shape[0] != 1 for r in rows):
+        raise ValueError("dusp-hip: every panned row must be mono, of shape (1, samples)")
+    if int(n_total) != n_total or n_total < 0:
+        raise ValueError("dusp-hip: n_total must be a whole number of samples, not negative")
+    n_total = int(n_total)
+
+    def whole(values, name):
+        a = np.asarray(values)
+        if a.shape != (n,):
+            raise ValueError("dusp-hip: %s must have shape (voices=%d,)" % (name, n))
+        if a.dtype.kind not in "iu":
+            if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
+                raise ValueError("dusp-hip: %s are whole numbers of samples" % name)
+        return a.astype(np.int64)
+
+    onsets = whole(onsets, "onsets")
+    with np.errstate(all="ignore"):
+        pans = np.asarray(pans, dtype=np.float32)
+    if pans.shape != (n,):
+        raise ValueError("dusp-hip: pans must have shape (voices=%d,)" % n)
+    if not np.all(np.isfinite(pans)):
+        raise ValueError("dusp-hip: pans must be finite")
+    if comp is None:
+        comp = pan_comp(pans)
+    else:
+        comp = np.asarray(comp, dtype=np.float64)
+        if comp.shape != (n,):
+            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
+    samples = np.array([r.shape[1] for r in rows], dtype=np.int64)
+    if lengths is None:
+        lengths = samples
+    else:
+        lengths = whole(lengths, "lengths")
+        if np.any(lengths < 0) or np.any(lengths > samples):
+            k = int(np.argmax((lengths < 0) | (lengths > samples)))
+            raise ValueError("dusp-hip: the length of voice %d is %d: lengths must lie in 0 .. the row's samples (%d)" % (k, int(lengths[k]), int(samples[k])))
+    if gains is not None:
+        gains = np.asarray(gains, dtype=np.float32)
+        if gains.shape != (n,):
+            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+    if init is not None:
+        init = np.asarray(init, dtype=np.float32)
+        if init.shape != (2, n_total):
+            raise ValueError("dusp-hip: init must have shape (channels=2, n_total=%d)" % n_total)
+    with np.errstate(all="ignore"):
+        acc = init.copy() if init is not None else np.zeros((2, n_total), dtype=np.float32)
+        for k in range(n):
+            onset, length = int(onsets[k]), int(lengths[k])
+            t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
+            if t1 <= t0:
+                continue
+            x = rows[k][0, t0 - onset:t1 - onset]
+            if gains is not None:
+                x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
+            xd, p = x.astype(np.float64), np.float64(pans[k])
+            left = (((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32)  # float64 operations, each rounded by itself; one rounding to f32
+            right = (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)
+            acc[0, t0:t1] = acc[0, t0:t1] + left  # float32 + float32: one f32 rounding
+            acc[1, t0:t1] = acc[1, t0:t1] + right
+        assert acc.dtype == np.float32
+        if not raw:
+            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
+    return acc

@@ -4,6 +4,7 @@ There is deliberately no CPU fallback here: if the HIP library is missing or no
 GPU is usable, every entry point raises.
 """
 import ctypes
+import math
 import threading
 import os
 
@@ -27,6 +28,7 @@ EXPORTS = [
     "dusp_peak_device", "dusp_encode_device", "dusp_render_host_pcm", "dusp_mix_device", "dusp_render_host_mix",
     "dusp_score_device", "dusp_render_host_score", "dusp_score_last_ms",
     "dusp_score_rows_device", "dusp_render_host_score_parts", "dusp_descriptor_channels",
+    "dusp_score_rows_pan_device", "dusp_render_host_score_parts_pan",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -96,6 +98,8 @@ def load():
     L.dusp_score_rows_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, ci, vp, vp]
     L.dusp_render_host_score_parts.argtypes = [vp, sz, sz, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_descriptor_channels.argtypes = [vp, sz]
+    L.dusp_score_rows_pan_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
+    L.dusp_render_host_score_parts_pan.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -114,6 +118,24 @@ def load():
 class ScorePart(ctypes.Structure):
     """dusp_score_part: one instrument of a piece (dusp_render_host_score_parts)"""
     _fields_ = [("prog", ctypes.c_void_p), ("n_instances", ctypes.c_size_t), ("n_voice_samples", ctypes.c_size_t), ("h_params", ctypes.c_void_p)]
+
+
+def pan_arrays(pans, n, comp=None):
+    """pans of n voices -> (float32 [n], float64 [n] compensation): checked — one finite pan a voice, not clamped — with the reference Pan
+    unit's compensation 10^((1 - |pan|) * 1.5 / 20) by math.pow where comp is None (dusp_amd/mix.py pan_comp).  Needs no device."""
+    with np.errstate(all="ignore"):
+        pans = np.ascontiguousarray(pans, dtype=np.float32)
+    if pans.shape != (n,):
+        raise ValueError("dusp-hip: pans must have shape (voices=%d,)" % n)
+    if not np.all(np.isfinite(pans)):
+        raise ValueError("dusp-hip: the pan of voice %d is not finite" % int(np.argmax(~np.isfinite(pans))))
+    if comp is None:
+        comp = np.array([math.pow(10, ((1 - abs(float(p))) * 1.5) / 20) for p in pans], dtype=np.float64)
+    else:
+        comp = np.ascontiguousarray(comp, dtype=np.float64)
+        if comp.shape != (n,):
+            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
+    return pans, comp
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -302,12 +324,36 @@ class Context:
         self._check(self._L.dusp_score_rows_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, n_channels,
                                                    onsets.ctypes.data if n else None, lp, d_gains, n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
-    def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None):
+    def score_rows_pan(self, rows, row_samples, onsets, pans, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, comp=None, stream=None):
+        """score_rows_device over MONO rows, voice k panned to pans[k] where it is added to a timeline of TWO channels
+        (dusp_score_rows_pan_device; dusp_amd/mix.py score_chain_rows_panned is the contract): rows are the voices' DEVICE pointers, voice
+        k f32 [row_samples[k]]; pans a HOST array of finite f32, not clamped; comp the f64 compensation per voice (None: math.pow's, the
+        reference's formula); d_init (which may be d_out) and d_out f32 [2][n_total_samples].  score_last_ms() reports the call."""
+        n = len(rows)
+        samples = np.asarray(row_samples) if n else np.zeros(0, dtype=np.uint32)
+        if samples.shape != (n,) or samples.dtype.kind not in "iu" or np.any(samples < 0) or np.any(samples > 0xffffffff):
+            raise ValueError("dusp-hip: row_samples must be whole numbers 0 .. 2^32 - 1 of shape (voices=%d,)" % n)
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        pointers = np.array([int(r or 0) for r in rows], dtype=np.uint64)
+        onsets = _whole_samples(onsets, n, "onsets")
+        pans, comp = pan_arrays(pans, n, comp)
+        lp = None
+        if lengths is not None:
+            lengths = _whole_samples(lengths, n, "lengths")
+            lp = lengths.ctypes.data
+        self._check(self._L.dusp_score_rows_pan_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, onsets.ctypes.data if n else None,
+                                                       lp, d_gains, pans.ctypes.data if n else None, comp.ctypes.data if n else None, n_total_samples, d_init, int(bool(raw)),
+                                                       d_out, stream))
+
+    def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
+                           pans=None):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
         on its compiled kernel, in the caller's voice order, whatever tile_bytes (0: the library's default) cuts the voice list into.
-        onsets, lengths, gains: per voice, in chain order; format, normalise and what is returned: as Program.render_score."""
+        onsets, lengths, gains: per voice, in chain order; format, normalise and what is returned: as Program.render_score.
+        pans (one finite f32 a voice): the parts are MONO and voice k is panned where it is added (dusp_render_host_score_parts_pan;
+        mix.score_chain_rows_panned): the result has two channels."""
         if not parts:
             raise ValueError("dusp-hip: a piece has at least one part")
         n = len(part_of)
@@ -339,7 +385,15 @@ class Context:
                 pp = params.ctypes.data
             table[p] = ScorePart(prog._h, n_instances, n_voice_samples, pp)
         n_ch = parts[0][0].n_out_channels
-        call = self._L.dusp_render_host_score_parts
+        if pans is None:
+            def call(*args):
+                return self._L.dusp_render_host_score_parts(*args)
+        else:
+            pans, comp = pan_arrays(pans, n)
+            n_ch = 2  # (parts that are not mono: the library refuses them)
+
+            def call(*args):  # (the pans and their compensation behind the gains)
+                return self._L.dusp_render_host_score_parts_pan(*(args[:7] + (pans.ctypes.data, comp.ctypes.data) + args[7:]))
         if format is None:
             out = self.host_empty((n_ch, n_total_samples), pinned)
             self._check(call(table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, lp, gp, n_total_samples, int(tile_bytes), 0, 0, out.ctypes.data, None))

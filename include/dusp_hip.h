@@ -400,6 +400,41 @@ int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, s
                                  const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains, size_t n_total_samples,
                                  size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak);
 
+/* Stereo placement: dusp_score_rows_device over MONO rows, every voice panned where it is added to a timeline of TWO channels
+ * (additions to ABI v7, detected by symbol).  A pan that is constant over a note is a property of the placement, not of the voice; this
+ * is the reference's Pan unit (src/components/Pan.js:19-25) behind every voice, without the voice becoming a two-channel circuit:
+ *     accL, accR = d_init ? d_init[0][t], d_init[1][t] : +0, +0
+ *     for k in index order:  s = t - onset_k;  if (0 <= s < len_k):
+ *         x    = d_gains ? f32(row_k[s] * g_k) : row_k[s]
+ *         accL = f32(accL + f32(((f64(x) * (1 - f64(p_k))) / 2) * comp_k))
+ *         accR = f32(accR + f32(((f64(x) * (1 + f64(p_k))) / 2) * comp_k))
+ *     d_out[0][t], d_out[1][t] = raw ? acc : (acc || 0)
+ * every f64 operation rounded by itself (dusp_amd/mix.py score_chain_rows_panned is the contract in numpy).  Skipped adds, clipped
+ * lengths, onsets of any sign, raw partial sums continued through d_init and windows of the timeline are dusp_score_rows_device's.
+ *   h_rows, h_row_samples   as dusp_score_rows_device, with n_channels = 1
+ *   h_pans                  f32 [n_voices], HOST memory, finite; NOT clamped to [-1, 1] (the reference does not clamp either)
+ *   h_comp                  f64 [n_voices], HOST memory: comp_k.  NULL: pow(10, ((1 - |p_k|) * 1.5) / 20) by the host's pow.  The
+ *                           reference computes it with the JavaScript engine's Math.pow: a JavaScript binder passes those values, so
+ *                           that under Node the result is the reference's own bits
+ *   d_init, d_out           f32 [2][n_total_samples], 2 * n_total_samples <= 2^31; d_init may be NULL, and may be d_out
+ * The voices' coefficients (1 - p, 1 + p and comp / 2 as doubles, 32 bytes a voice) go up with the plan; dusp_score_last_ms reports
+ * this call too.  DUSP_ERR_ARG, with a message, for a pan that is not finite, a comp that is NaN, and everything
+ * dusp_score_rows_device refuses. */
+int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices,
+                               const int64_t *h_onsets, const int64_t *h_lengths, const float *d_gains, const float *h_pans,
+                               const double *h_comp, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream);
+
+/* dusp_render_host_score_parts with a pan per voice: every part's circuit has ONE output channel (refused by message otherwise, before
+ * any render), the tiles' launches are dusp_score_rows_pan_device's, and the timeline, its `|| 0`, its peak and its PCM frames have two
+ * channels.  Tiles are by bytes as before: mono rows, so twice the voices of a panned two-channel circuit fit a tile.
+ *   h_pans, h_comp   [n_voices], in chain order, as for dusp_score_rows_pan_device
+ *   h_out            planar f32 [2][n_total_samples], or the two-channel frames of the PCM format
+ * Everything else, refusals included, is dusp_render_host_score_parts'. */
+int dusp_render_host_score_parts_pan(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                     const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains, const float *h_pans,
+                                     const double *h_comp, size_t n_total_samples, size_t tile_bytes, int format, int normalise,
+                                     void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

@@ -8,6 +8,9 @@
           host time and the upload's time, which precede the launch inside the call, reported beside it.  The plan's default block and a
           block forced to cover the whole timeline (DUSP_SCORE_PLAN_KB=1: one list for every workgroup) side by side.  Then the rows
           kernel (dusp_score_rows_device) over the same buffer, its rows handed over as pointers of their own (profiles/score_rows.txt).
+  pan     (--pan; profiles/score_pan.txt) the panned kernel (dusp_score_rows_pan_device) over dense MONO rows of the dense shapes, kernel
+          alone by dusp_score_last_ms, against dusp_score_rows_device over the same voices as TWO-CHANNEL rows — unchanged code, and what a
+          panned piece costs without it: every voice a two-channel circuit with a Pan unit inside.
   piece   8192 notes of 0.5 s placed over 60 s in onset order: Program.render_score on the host's clock, against the render of the same
           notes alone (render_device into a preallocated buffer) and against the same piece with the onsets shuffled — every tile's
           union window is then the whole timeline, which is what the window is worth.  One run under DUSP_JIT_LOG=2 prints the plans'
@@ -73,6 +76,48 @@ def dense(key, scale, ctxs, reps):
     print(line % (("rows kernel, default block", med, min(kernel)) + rate(med) + ("   [plan on the host %.2f ms, its upload %.2f ms]" % (float(np.median(plan)), float(np.median(upload))),)), flush=True)
 
 
+def pan(key, scale, ctxs, reps):
+    import torch
+    V, n = max(64, DENSE[key][0] // scale), DENSE[key][1]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    ctx = ctxs["default"]
+    onsets = np.zeros(V, dtype=np.int64)
+    samples = np.full(V, n, dtype=np.uint32)
+    pans = (np.random.RandomState(5).random_sample(V) * 2 - 1).astype(np.float32)
+    acc = torch.empty((2, n), dtype=torch.float32, device="cuda")
+
+    def median_of(call):
+        kernel, plan, upload = [], [], []
+        for r in range(reps + 1):
+            call()
+            k, p, u = ctx.score_last_ms()
+            if r:
+                kernel.append(k), plan.append(p), upload.append(u)
+        return float(np.median(kernel)), min(kernel), float(np.median(plan)), float(np.median(upload))
+
+    line = "  %-44s kernel median %9.3f ms  fastest %9.3f   %6.2f GB read = %5.2f TB/s   [plan on the host %.2f ms, its upload %.2f ms]"
+    print("pan %s: %d voices x %d samples, all onsets 0, full lengths, into a timeline of 2 x %d" % (key, V, n, n), flush=True)
+    # the yardstick first, and its rows freed before the mono ones are made: (b) is 23.6 GB of two-channel rows
+    wide = torch.empty((V, 2, n), dtype=torch.float32, device="cuda").normal_()
+    torch.cuda.synchronize()
+    pointers = [wide.data_ptr() + 8 * n * k for k in range(V)]
+    t_wide = median_of(lambda: ctx.score_rows_device(pointers, samples, 2, onsets, n, acc.data_ptr(), stream=s))
+    read = V * 2 * n * 4
+    print(line % (("rows kernel over two-channel rows", t_wide[0], t_wide[1], read / 1e9, read / t_wide[0] / 1e9) + t_wide[2:]), flush=True)
+    del wide
+    mono = torch.empty((V, 1, n), dtype=torch.float32, device="cuda").normal_()
+    torch.cuda.synchronize()
+    pointers = [mono.data_ptr() + 4 * n * k for k in range(V)]
+    t_pan = median_of(lambda: ctx.score_rows_pan(pointers, samples, onsets, pans, n, acc.data_ptr(), stream=s))
+    read = V * n * 4
+    print(line % (("panned kernel over mono rows", t_pan[0], t_pan[1], read / 1e9, read / t_pan[0] / 1e9) + t_pan[2:]), flush=True)
+    d_gains = torch.ones(V, dtype=torch.float32, device="cuda")
+    t_gain = median_of(lambda: ctx.score_rows_pan(pointers, samples, onsets, pans, n, acc.data_ptr(), d_gains=d_gains.data_ptr(), stream=s))
+    print(line % (("panned kernel over mono rows, with gains", t_gain[0], t_gain[1], read / 1e9, read / t_gain[0] / 1e9) + t_gain[2:]), flush=True)
+    print("  panned / two-channel rows: x%.3f (with gains x%.3f); %.1f voice terms per ns and channel pair" % (t_pan[0] / t_wide[0], t_gain[0] / t_wide[0], V * n / t_pan[0] / 1e6), flush=True)
+
+
 def piece(scale, ctxs, reps):
     import torch
     V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
@@ -113,13 +158,14 @@ def main():
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--scale", type=int, default=1, help="divide every voice count by this (a quick look)")
+    ap.add_argument("--pan", action="store_true", help="the pan leg alone, over the dense cases named by --cases")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
     for key in a.cases:
         if key in DENSE:
-            dense(key, a.scale, ctxs, a.reps)
-    if "p" in a.cases:
+            (pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
+    if "p" in a.cases and not a.pan:
         piece(a.scale, ctxs, a.reps)
 
 
