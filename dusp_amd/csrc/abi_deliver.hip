@@ -401,6 +401,8 @@ struct ScoreLaunch {
     uint32_t block_shift = dusp::kScoreGroupShift;
     bool any = false;  // some voice reaches the timeline (else: no plan in the image)
     size_t pan_at = 0;  // a panned launch: byte offset of its voices' coefficients (dusp::ScorePan), behind the plan
+    bool frac = false;   // some listed voice starts between samples: the launch is score_frac_engine.hip's ...
+    size_t frac_at = 0;  // ... and this the byte offset of its voices' weights (dusp::ScoreFrac), behind the plan
 };
 
 // before a call rewrites the context's host image: the last upload has read it
@@ -583,10 +585,13 @@ int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voic
 
 // score_image_add for rows: plans the voices [0, n) — voice k row_samples[k] samples a channel at device address rows[k] — within
 // budget_bytes and appends the plan to the context's host image.  listed (optional): which voices reach the timeline.
+// h_fracs (optional): the voices' fractions of a sample, checked; where a listed voice has one, its weights (dusp::ScoreFrac, 16 bytes a
+// voice on top of the budget) follow the plan and the launch is the two-tap kernel's — else the image and the launch are as without.
 static int score_rows_image_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n,
-                                size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L, std::vector<unsigned char> *listed = nullptr) {
+                                size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L, std::vector<unsigned char> *listed = nullptr,
+                                const double *h_fracs = nullptr) {
     dusp::ScoreRowsPlan P;
-    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P);
+    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, h_fracs);
     if (bad >= 0)
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
                                         ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
@@ -600,6 +605,16 @@ static int score_rows_image_add(dusp_ctx *ctx, const char *who, const int64_t *h
         L.n_voices = n;
         L.n_block_first = P.block_first.size();
         L.at = dusp::score_rows_plan_pack(P, ctx->h_score_plan);
+        for (size_t k = 0; k < n && !L.frac; k++) L.frac = P.voices[k].hi > P.voices[k].lo && P.voices[k].pad != 0;
+        if (L.frac) {
+            std::vector<unsigned char> &image = ctx->h_score_plan;
+            L.frac_at = (image.size() + 15) & ~(size_t)15;
+            image.resize(L.frac_at + n * sizeof(dusp::ScoreFrac));
+            for (size_t k = 0; k < n; k++) {
+                const dusp::ScoreFrac w = dusp::score_frac_weights(h_fracs[k]);
+                std::memcpy(image.data() + L.frac_at + k * sizeof w, &w, sizeof w);
+            }
+        }
     }
     if (listed) {
         listed->resize(n);
@@ -608,9 +623,23 @@ static int score_rows_image_add(dusp_ctx *ctx, const char *who, const int64_t *h
     return DUSP_OK;
 }
 
+// a launch some voice of which starts between samples (score_frac_engine.hip): plain rows of n_channels, or (L.pan_at: panned) mono rows
+static int score_frac_launch(dusp_ctx *ctx, const ScoreLaunch &L, bool panned, size_t n_channels, size_t n_total, const float *d_gains, const float *d_init, int raw,
+                             float *d_out, hipStream_t stream) {
+    const dusp::ScoreRow *d_voices = (const dusp::ScoreRow *)(ctx->d_score_plan + L.at);
+    const dusp::ScorePan *d_pans = panned ? (const dusp::ScorePan *)(ctx->d_score_plan + L.pan_at) : nullptr;
+    const dusp::ScoreFrac *d_fracs = (const dusp::ScoreFrac *)(ctx->d_score_plan + L.frac_at);
+    const uint32_t *d_block_first = (const uint32_t *)(d_voices + L.n_voices);
+    HIP_TRY(ctx, dusp::launch_score_frac(d_gains, d_pans, d_fracs, d_voices, d_block_first, d_block_first + L.n_block_first, d_init, d_out, (uint32_t)n_channels, n_total,
+                                         L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->score_done, stream));
+    return DUSP_OK;
+}
+
 static int score_rows_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, size_t n_total, const float *d_gains, const float *d_init, int raw, float *d_out,
                              hipStream_t stream) {
     if (L.w_hi <= L.w_lo) return DUSP_OK;
+    if (L.any && L.frac) return score_frac_launch(ctx, L, false, n_channels, n_total, d_gains, d_init, raw, d_out, stream);
     const dusp::ScoreRow *d_voices = L.any ? (const dusp::ScoreRow *)(ctx->d_score_plan + L.at) : nullptr;  // (the buffer and L.at: both on 32-byte boundaries)
     const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices) : nullptr;
     HIP_TRY(ctx, dusp::launch_score_rows(d_gains, d_voices, d_block_first, L.any ? d_block_first + L.n_block_first : nullptr, d_init, d_out, (uint32_t)n_channels, n_total, L.w_lo,
@@ -625,6 +654,14 @@ static int check_pans(dusp_ctx *ctx, const char *who, const float *h_pans, const
     for (size_t k = 0; k < n; k++) {
         if (!std::isfinite(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
         if (h_comp && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
+    }
+    return DUSP_OK;
+}
+
+static int check_fracs(dusp_ctx *ctx, const char *who, const double *h_fracs, size_t n) {
+    for (size_t k = 0; h_fracs && k < n; k++) {
+        if (!std::isfinite(h_fracs[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is not finite");
+        if (h_fracs[k] < 0.0 || h_fracs[k] >= 1.0) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is outside [0, 1)");
     }
     return DUSP_OK;
 }
@@ -646,6 +683,7 @@ static void score_pan_image_add(dusp_ctx *ctx, const float *h_pans, const double
 // score_rows_launch over mono rows into a timeline of two channels
 static int score_pan_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_total, const float *d_gains, const float *d_init, int raw, float *d_out, hipStream_t stream) {
     if (L.w_hi <= L.w_lo) return DUSP_OK;
+    if (L.any && L.frac) return score_frac_launch(ctx, L, true, 1, n_total, d_gains, d_init, raw, d_out, stream);
     const dusp::ScoreRow *d_voices = L.any ? (const dusp::ScoreRow *)(ctx->d_score_plan + L.at) : nullptr;
     const dusp::ScorePan *d_pans = L.any ? (const dusp::ScorePan *)(ctx->d_score_plan + L.pan_at) : nullptr;
     const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices) : nullptr;
@@ -655,10 +693,11 @@ static int score_pan_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_total,
     return DUSP_OK;
 }
 
-// dusp_score_rows_device, and (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device
+// dusp_score_rows_device, (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device, and (h_fracs: onsets between
+// samples) dusp_score_rows_frac_device
 static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
                              const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw,
-                             float *d_out, void *stream_) {
+                             float *d_out, void *stream_, const double *h_fracs = nullptr) {
     if (!ctx) return DUSP_ERR_ARG;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
@@ -677,6 +716,7 @@ static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const 
     }
     if (h_pans)
         if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
+    if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_of(ctx, stream_);
     ScoreLaunch L;
@@ -686,7 +726,7 @@ static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const 
         const auto t_plan = std::chrono::steady_clock::now();
         static_assert(sizeof(const float *) == sizeof(uint64_t), "rows are handed to the planner as 64-bit addresses");
         if (int rc = score_rows_image_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples,
-                                          /*whole_timeline=*/true, score_plan_budget(ctx), L))
+                                          /*whole_timeline=*/true, score_plan_budget(ctx), L, nullptr, h_fracs))
             return rc;
         if (h_pans) score_pan_image_add(ctx, h_pans, h_comp, n_voices, L);
         ctx->score_plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan).count();
@@ -726,10 +766,11 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
                              n_total_samples, d_init, raw, d_out, stream_);
 }
 
-// dusp_render_host_score_parts, and (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan
+// dusp_render_host_score_parts, (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan, and (h_fracs:
+// onsets between samples, with or without pans) dusp_render_host_score_parts_frac
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
-                                   int format, int normalise, void *h_out, float *h_peak) {
+                                   int format, int normalise, void *h_out, float *h_peak, const double *h_fracs = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
@@ -757,6 +798,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
     if (h_pans)
         if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
+    if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
     // voice k of the chain: the next unused instance of part h_part_of[k]
     std::vector<size_t> instance_of(n_voices), used(n_parts, 0);
     for (size_t k = 0; k < n_voices; k++) {
@@ -817,7 +859,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
                 rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * n_ch * parts[p].n_voice_samples);
             }
             if (int rc = score_rows_image_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
-                                              /*whole_timeline=*/false, tile_budget, launches[i], &listed))
+                                              /*whole_timeline=*/false, tile_budget, launches[i], &listed, h_fracs ? h_fracs + lo : nullptr))
                 return rc;
             if (h_pans) score_pan_image_add(ctx, h_pans + lo, h_comp ? h_comp + lo : nullptr, n, launches[i]);
             for (size_t k = 0; k < n; k++)
@@ -875,6 +917,22 @@ int dusp_render_host_score_parts_pan(const dusp_score_part *parts, size_t n_part
     if (!h_pans) CTX_FAIL(parts[0].prog->ctx, DUSP_ERR_ARG, "dusp_render_host_score_parts_pan: h_pans is NULL");
     return render_host_score_parts("dusp_render_host_score_parts_pan", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
                                    tile_bytes, format, normalise, h_out, h_peak);
+}
+
+int dusp_score_rows_frac_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                                const double *h_fracs, const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples,
+                                const float *d_init, int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (h_pans && n_channels != 1) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_frac_device: a panned voice is mono: n_channels must be 1 with h_pans");
+    return score_rows_device(ctx, "dusp_score_rows_frac_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, h_pans, h_comp, n_total_samples, d_init,
+                             raw, d_out, stream_, h_fracs);
+}
+
+int dusp_render_host_score_parts_frac(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const double *h_fracs,
+                                      const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
+                                      int format, int normalise, void *h_out, float *h_peak) {
+    return render_host_score_parts("dusp_render_host_score_parts_frac", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak, h_fracs);
 }
 
 }  // extern "C"

@@ -143,7 +143,7 @@ struct alignas(32) ScoreRow {
     uint32_t lo, hi;
     uint64_t row;     // device address of the voice's channel 0, sample 0
     uint32_t stride;  // floats from one channel of this voice to the next
-    uint32_t pad;
+    uint32_t pad;     // 0; a voice with a fraction of a sample in its onset (score_rows_plan's fracs): its unclipped length, never 0
 };
 static_assert(sizeof(ScoreRow) == 32, "one eight-dword scalar load");
 
@@ -161,10 +161,18 @@ struct ScoreRowsPlan {
 
 // score_plan over voices of their own row lengths: row_samples[k] samples a channel (which is also the voice's channel stride) at device
 // address rows[k] (nullptr: all 0, for a plan that is only looked at).  lengths: nullptr for row_samples[k] everywhere.
+// fracs (nullptr: none): voice k starts at onset_k + fracs[k] samples, 0 <= fracs[k] < 1 (the caller has checked that).  A voice whose
+// fraction is not 0 is heard through two taps (score_frac_engine.hip; dusp_amd/mix.py two_tap_terms) and covers ONE MORE sample, the
+// ceil tap of its last: its span is [onset, onset + len + 1) before clipping, it is dropped only when onset + len + 1 <= 0 (a voice
+// that ends exactly at sample 0 still has its tail tap ON sample 0), and its record carries pad = len — the unclipped length, which the
+// kernel needs to tell s < len where hi is clipped by the timeline, and, being non-zero, the wave-uniform mark of a voice with a
+// fraction.  A voice without one has pad = 0 and is today's voice.  t_hi and the union window grow by that one sample.
+// The weights of such voices go up as a parallel array of ScoreFrac (below), 16 bytes a voice ON TOP of the plan's byte budget, which
+// counts records and lists as before.
 // Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, row_samples[k]].
 // Needs n <= 2^32 - 1, row_samples and n_total <= kScoreRowMax.
 inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n, uint64_t n_total,
-                               bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P) {
+                               bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P, const double *fracs = nullptr) {
     P = ScoreRowsPlan();
     P.voices.assign(n, ScoreRow{0, 0u, 0u, 0u, 0u, 0u});
     const int64_t total = (int64_t)n_total;
@@ -173,10 +181,12 @@ inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, co
     for (size_t k = 0; k < n; k++) {
         const int64_t len = lengths ? lengths[k] : (int64_t)row_samples[k], onset = onsets[k];
         if (len < 0 || len > (int64_t)row_samples[k]) return (int64_t)k;
-        if (len == 0 || onset >= total || onset <= -len) continue;  // empty, behind the end, wholly in front of sample 0
-        // here -2^31 <= -len < onset < n_total <= 2^31: onset + len cannot overflow
-        const int64_t lo = std::max<int64_t>(onset, 0), hi = std::min(onset + len, total);
-        P.voices[k] = ScoreRow{onset, (uint32_t)lo, (uint32_t)hi, rows ? rows[k] : 0, row_samples[k], 0u};
+        const bool two_taps = fracs && fracs[k] != 0.0;
+        // empty, behind the end, wholly in front of sample 0 (two taps: the tail tap too, onset + len + 1 <= 0)
+        if (len == 0 || onset >= total || (two_taps ? onset < -len : onset <= -len)) continue;
+        // here -2^31 <= -len <= onset < n_total <= 2^31: onset + len + 1 cannot overflow
+        const int64_t lo = std::max<int64_t>(onset, 0), hi = std::min(onset + len + (two_taps ? 1 : 0), total);
+        P.voices[k] = ScoreRow{onset, (uint32_t)lo, (uint32_t)hi, rows ? rows[k] : 0, row_samples[k], two_taps ? (uint32_t)len : 0u};
         if (first_listed == n) first_listed = k;
         t_lo = std::min(t_lo, lo);
         t_hi = std::max(t_hi, hi);
@@ -231,5 +241,18 @@ struct alignas(32) ScorePan {
 static_assert(sizeof(ScorePan) == 32, "one eight-dword scalar load");
 
 inline ScorePan score_pan_coefficients(float pan, double comp) { return ScorePan{1.0 - (double)pan, 1.0 + (double)pan, comp / 2.0, 0.0}; }
+
+// ---- fractions: onsets between samples (score_frac_engine.hip; dusp_amd/mix.py two_tap_terms) ----
+
+// The weights of a voice's two taps, made on the host: the reference's Delay (Delay.js:36-38) writes a sample to the ring slot at
+// floor(delay) with the weight 1 - frac and to the next with frac.  w0 = 1.0 - frac is the IEEE subtraction itself.  One record a voice
+// of the plan, whole voices included (theirs is never read): a parallel array behind the plan in the context's image, as ScorePan.
+// (16 bytes on a 16-byte boundary: one four-dword scalar load a voice)
+struct alignas(16) ScoreFrac {
+    double w0, w1;  // 1.0 - frac, frac
+};
+static_assert(sizeof(ScoreFrac) == 16, "one four-dword scalar load");
+
+inline ScoreFrac score_frac_weights(double frac) { return ScoreFrac{1.0 - frac, frac}; }
 
 }  // namespace dusp

@@ -752,6 +752,7 @@ typedef struct {
     float *gains, *out;
     float *pans;      /* renderPiecePan: a pan per voice and its compensation (Math.pow's), else NULL */
     double *comp;
+    double *fracs;    /* renderPieceFrac: a fraction of a sample per voice, else NULL */
     float peak;
     int format, normalise, rc;
     char err[512];
@@ -772,6 +773,7 @@ static void piece_free(napi_env env, piece_job *j) {
     free(j->gains);
     free(j->pans);
     free(j->comp);
+    free(j->fracs);
     free(j->out);
     free(j);
 }
@@ -789,7 +791,10 @@ static void piece_execute(napi_env env, void *data) {
         j->parts[p].prog = j->pbs[p]->prog;
     }
     if (j->rc == DUSP_OK) {
-        if (j->pans)
+        if (j->fracs)
+            j->rc = dusp_render_host_score_parts_frac(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->fracs, j->lengths, j->gains, j->pans, j->comp, j->n_total,
+                                                      j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+        else if (j->pans)
             j->rc = dusp_render_host_score_parts_pan(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, j->pans, j->comp, j->n_total, j->tile_bytes,
                                                      j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
         else
@@ -842,11 +847,20 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *   -> as renderScore (dusp_render_host_score_parts: voice k of the chain is the next unused instance of part partOf[k])
  * renderPiecePan(the same twelve, pans Float32Array, comp Float64Array)
  *   -> the same over MONO parts, two channels out (dusp_render_host_score_parts_pan: voice k panned to pans[k] where it is added; comp[k] is
- *      the reference's compensation, computed by the caller with Math.pow) */
-static napi_value render_piece_call(napi_env env, napi_callback_info info, int panned) {
-    napi_value argv[14];
+ *      the reference's compensation, computed by the caller with Math.pow)
+ * renderPieceFrac(the same twelve, fracs Float64Array, pans Float32Array | null, comp Float64Array | null)
+ *   -> either of the two with voice k starting at onsets[k] + fracs[k] samples, 0 <= fracs[k] < 1 (dusp_render_host_score_parts_frac) */
+static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions */
+    napi_value argv[15];
     char msg[256];
-    if (!get_args(env, info, panned ? 14 : 12, argv)) return NULL;
+    if (!get_args(env, info, form == 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    int panned = form == 1;
+    const int pans_at = form == 2 ? 13 : 12;
+    if (form == 2) {
+        napi_valuetype pt = napi_undefined;
+        napi_typeof(env, argv[13], &pt);
+        panned = pt != napi_null && pt != napi_undefined;
+    }
     uint32_t n_parts = 0;
     bool is_array = false;
     if (napi_is_array(env, argv[0], &is_array) != napi_ok || !is_array || napi_get_array_length(env, argv[0], &n_parts) != napi_ok || n_parts < 1) {
@@ -953,14 +967,21 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int p
     if (!bad && panned) {
         void *pd, *cd;
         size_t n_p = 0, n_c = 0;
-        if (!typed_array(env, argv[12], napi_float32_array, &pd, &n_p) || n_p != n_voices) bad = "pans must be a Float32Array of one value per voice";
-        else if (!typed_array(env, argv[13], napi_float64_array, &cd, &n_c) || n_c != n_voices) bad = "comp must be a Float64Array of one value per voice";
+        if (!typed_array(env, argv[pans_at], napi_float32_array, &pd, &n_p) || n_p != n_voices) bad = "pans must be a Float32Array of one value per voice";
+        else if (!typed_array(env, argv[pans_at + 1], napi_float64_array, &cd, &n_c) || n_c != n_voices) bad = "comp must be a Float64Array of one value per voice";
         else if (!(j->pans = (float *)malloc(n_p * sizeof(float))) || !(j->comp = (double *)malloc(n_c * sizeof(double)))) bad = "out of host memory for the pans";
         else {
             memcpy(j->pans, pd, n_p * sizeof(float));
             memcpy(j->comp, cd, n_c * sizeof(double));
         }
         n_channels = 2; /* the timeline's */
+    }
+    if (!bad && form == 2) {
+        void *fd;
+        size_t n_f = 0;
+        if (!typed_array(env, argv[12], napi_float64_array, &fd, &n_f) || n_f != n_voices) bad = "fracs must be a Float64Array of one value per voice";
+        else if (!(j->fracs = (double *)malloc(n_f * sizeof(double)))) bad = "out of host memory for the fractions";
+        else memcpy(j->fracs, fd, n_f * sizeof(double));
     }
     j->n_floats = (size_t)n_channels * j->n_total;
     j->n_bytes = j->n_floats * (size_t)(!j->format || j->format == DUSP_PCM_F32 ? 4 : j->format == DUSP_PCM_S16 ? 2 : 3);
@@ -996,6 +1017,7 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int p
 
 static napi_value fn_render_piece(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 0); }
 static napi_value fn_render_piece_pan(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 1); }
+static napi_value fn_render_piece_frac(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 2); }
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1029,6 +1051,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
+        {"renderPieceFrac", fn_render_piece_frac},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

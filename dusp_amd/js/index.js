@@ -22,6 +22,7 @@ module.exports = {
   renderPiece: renderChannelData.renderPiece,
   renderPiecePcm: renderChannelData.renderPiecePcm,
   renderPieceWav: renderChannelData.renderPieceWav,
+  splitOnsets: renderChannelData.splitOnsets,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

@@ -446,14 +446,17 @@ function wholeSamples(who, name, values, count) {
  * and mixed ON THE DEVICE at the onsets in Sum.many's chain order (dusp_render_host_score).  onsets and lengths are in samples, whole
  * numbers of any sign (a negative onset: the voice began before the timeline; lengths clip a voice to its first samples); the
  * durations are in seconds.  gains, engine, tileInstances and the refusals are renderMix's.  pans: as renderPiece's — mono voices, two
- * channels out, through the piece's call with the score as its one part (voiceDuration is one number; tileInstances does not apply). */
-function scoreAsPiece(opts) { // renderScore with pans: the piece's call with the score as its one part
+ * channels out, through the piece's call with the score as its one part (voiceDuration is one number; tileInstances does not apply).
+ * fracs: as renderPiece's — voice k starts at onsets[k] + fracs[k] samples — through the piece's call too. */
+const asPiece = (opts) => (opts.pans !== undefined && opts.pans !== null) || (opts.fracs !== undefined && opts.fracs !== null)
+
+function scoreAsPiece(opts) { // renderScore with pans or fracs: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
 }
 
 async function renderScore(outlets, opts = {}) {
   const { duration = 1 } = opts
-  const { nSamples, nChannels, sampleRate, result } = opts.pans !== undefined && opts.pans !== null
+  const { nSamples, nChannels, sampleRate, result } = asPiece(opts)
     ? await pieceCall('renderScore', outlets, scoreAsPiece(opts), 0, 0, true)
     : await mixCall('renderScore', outlets, duration, opts, 0, 0, true)
   const channelData = []
@@ -466,7 +469,7 @@ async function renderScorePcm(outlets, opts = {}) {
   const { duration = 1, bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderScorePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderScorePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result } = opts.pans !== undefined && opts.pans !== null
+  const { nChannels, sampleRate, result } = asPiece(opts)
     ? await pieceCall('renderScorePcm', outlets, scoreAsPiece(opts), PCM_FORMAT[bitDepth], normalise, true)
     : await mixCall('renderScorePcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise, true)
   if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
@@ -535,6 +538,32 @@ function panArrays(pans, count) {
   return { pans: p, comp: Float64Array.from(p, (x) => Math.pow(10, ((1 - Math.abs(x)) * 1.5) / 20)) }
 }
 
+/* fracs of `count` voices -> Float64Array: checked — one finite fraction of a sample a voice, 0 <= f < 1 — by the strings the library
+ * uses (twin of mix.py check_fracs). */
+function fracArrays(fracs, count) {
+  const ok = Array.isArray(fracs) || fracs instanceof Float32Array || fracs instanceof Float64Array
+  const f = ok ? (fracs instanceof Float64Array ? fracs : Float64Array.from(fracs)) : null
+  if (!f || f.length !== count) throw 'dusp-hip: fracs must have shape (voices=' + count + ',)'
+  for (let k = 0; k < count; k++) if (!Number.isFinite(f[k])) throw 'dusp-hip: the fraction of voice ' + k + ' is not finite'
+  for (let k = 0; k < count; k++) if (f[k] < 0 || f[k] >= 1) throw 'dusp-hip: the fraction of voice ' + k + ' is outside [0, 1)'
+  return f
+}
+
+/* Positions on the timeline in samples, real numbers of any sign -> { onsets: Float64Array of whole numbers, fracs: Float64Array } by
+ * floor: position = onset + frac with 0 <= frac < 1, what the `onsets` and `fracs` options take.  A negative position so close to a whole
+ * number that position - floor(position) rounds to 1 is that whole number (twin of mix.py split_onsets). */
+function splitOnsets(positions) {
+  const p = Float64Array.from(positions)
+  if (!p.every(Number.isFinite) || p.some((x) => x >= 2 ** 63 || x < -(2 ** 63))) throw 'dusp-hip: positions are finite numbers of samples within int64'
+  const onsets = new Float64Array(p.length), fracs = new Float64Array(p.length)
+  p.forEach((x, k) => {
+    const whole = Math.floor(x), frac = x - whole
+    onsets[k] = frac >= 1 ? whole + 1 : whole
+    fracs[k] = frac >= 1 ? 0 : frac
+  })
+  return { onsets, fracs }
+}
+
 async function pieceCall(who, outlets, opts, format, normalise, onePart = false) {
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
   const extractions = outlets.map((o) => extract(o))
@@ -562,6 +591,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   }
   if (!Number.isInteger(tileBytes) || tileBytes < 0) throw 'dusp-hip: ' + who + ': tileBytes must be 0 (the default tile) or a whole number of bytes'
   const panned = opts.pans !== undefined && opts.pans !== null ? panArrays(opts.pans, count) : null
+  const fracs = opts.fracs !== undefined && opts.fracs !== null ? fracArrays(opts.fracs, count) : null
   const grouped = pieceParts(extractions, voiceSamples)
   if (onePart && grouped.parts.length !== 1) throw 'dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments'
   const n = native()
@@ -573,7 +603,8 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
-    const result = panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
+    const result = fracs ? await n.renderPieceFrac(...args, fracs, panned ? panned.pans : null, panned ? panned.comp : null)
+      : panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
     return { nSamples, nChannels, sampleRate, result }
   } finally {
     for (const prog of progs) n.programDestroy(prog)
@@ -588,7 +619,11 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * voice's own samples), gains and engine as renderScore; tileBytes: what a tile of voices may take on the device (0: the default).
  * pans (one finite number a voice, -1 left .. +1 right, not clamped): the voices are MONO circuits and voice k is placed in the stereo
  * field where it is added to the timeline (dusp_render_host_score_parts_pan) — what the reference renders for new Pan(voice_k, pans[k])
- * in the voice's place, bit for bit, the compensation being this engine's own Math.pow.  The result has two channels. */
+ * in the voice's place, bit for bit, the compensation being this engine's own Math.pow.  The result has two channels.
+ * fracs (one number a voice, 0 <= f < 1; onsets stay whole numbers): voice k starts at onsets[k] + fracs[k] samples — what the reference
+ * renders for new Delay(., onsets[k] + fracs[k], maxDelay), whose two taps carry the weights 1 - frac and frac
+ * (dusp_render_host_score_parts_frac; include/dusp_hip.h says where the reference's ring departs from it).  splitOnsets makes both
+ * arrays from positions in samples written as real numbers.  All fractions zero gives the bits of the call without. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   const channelData = []
@@ -649,6 +684,8 @@ module.exports.structureKey = structureKey
 module.exports.checkPieceChannels = checkPieceChannels
 module.exports.checkPanChannels = checkPanChannels
 module.exports.panArrays = panArrays
+module.exports.fracArrays = fracArrays
+module.exports.splitOnsets = splitOnsets
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

@@ -102,13 +102,73 @@ def score_chain(planar, onsets, n_total, lengths=None, gains=None, init=None, ra
     return acc
 
 
-def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None, raw=False):
+def check_fracs(fracs, n):
+    """fracs of n voices -> contiguous float64 [n]: checked — one finite fraction of a sample a voice, 0 <= f < 1 — by the strings the C
+    calls use (dusp_score_rows_frac_device).  Needs no device."""
+    with np.errstate(all="ignore"):
+        fracs = np.ascontiguousarray(fracs, dtype=np.float64)
+    if fracs.shape != (n,):
+        raise ValueError("dusp-hip: fracs must have shape (voices=%d,)" % n)
+    if not np.all(np.isfinite(fracs)):
+        raise ValueError("dusp-hip: the fraction of voice %d is not finite" % int(np.argmax(~np.isfinite(fracs))))
+    if np.any((fracs < 0) | (fracs >= 1)):
+        raise ValueError("dusp-hip: the fraction of voice %d is outside [0, 1)" % int(np.argmax((fracs < 0) | (fracs >= 1))))
+    return fracs
+
+
+def split_onsets(positions):
+    """Positions on the timeline in samples, real numbers of any sign -> (int64 onsets, float64 fracs) by floor: position = onset + frac
+    with 0 <= frac < 1, what the `onsets` and `fracs` of a score or piece take.  position - floor(position) is exact in float64 except
+    for a negative position so close to a whole number that the difference rounds to 1.0 (-1e-300, say): that position IS the whole
+    number above it as far as a double can tell, and becomes (floor + 1, 0.0).  A position of magnitude 2^52 and beyond is a whole
+    number already.  Positions are finite and within int64."""
+    with np.errstate(all="ignore"):
+        p = np.asarray(positions, dtype=np.float64)
+    if not np.all(np.isfinite(p)) or np.any(p >= 2.0 ** 63) or np.any(p < -2.0 ** 63):
+        raise ValueError("dusp-hip: positions are finite numbers of samples within int64")
+    whole = np.floor(p)
+    frac = p - whole
+    up = frac >= 1.0
+    return (whole + up).astype(np.int64), np.where(up, 0.0, frac)
+
+
+def two_tap_terms(x, frac):
+    """What a voice with a fraction adds to the timeline: x float32 [..., len] (len >= 1), the voice's samples after gain (and pan) ->
+    float32 [..., len + 1], the terms of the timeline samples onset .. onset + len.  The reference's Delay writes every input sample to
+    two neighbouring ring slots with the weights 1 - frac and frac (Delay.js:36-38); the ceil tap of sample s - 1 is alone in its slot
+    when the floor tap of sample s is added to it:
+
+        w1 = frac, w0 = 1.0 - frac                       (one f64 subtraction)
+        c(s)      = f32(f64(x[s-1]) * w1)                1 <= s <= len
+        term(0)   = f32(f64(x[0]) * w0)
+        term(s)   = f32(f64(c(s)) + f64(x[s]) * w0)      1 <= s < len     (every f64 operation rounded by itself: no FMA)
+        term(len) = c(len)"""
+    x = np.asarray(x, dtype=np.float32)
+    w1 = np.float64(frac)
+    w0 = np.float64(1.0) - w1
+    with np.errstate(all="ignore"):
+        xd = x.astype(np.float64)
+        c = (xd * w1).astype(np.float32)  # c[..., s - 1] is c(s)
+        floor_tap = xd * w0
+        terms = np.empty(x.shape[:-1] + (x.shape[-1] + 1,), dtype=np.float32)
+        terms[..., 0] = floor_tap[..., 0].astype(np.float32)
+        terms[..., 1:-1] = (c[..., :-1].astype(np.float64) + floor_tap[..., 1:]).astype(np.float32)
+        terms[..., -1] = c[..., -1]
+    return terms
+
+
+def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None, raw=False, fracs=None):
     """rows: a list of float32 arrays [channels, samples_k] — every voice a row of its own length, all of one channel count — onsets
     int64 [voices] -> float32 [channels, n_total]: the contract of dusp_score_rows_device.  The chain is score_chain's, word for word: it
     starts from `init` or +0, the voices go in index order, voice k takes part only where 0 <= t - onset_k < len_k (lengths None: the
     whole row; else 0 <= len_k <= samples_k), a term is f32(x * g_k) when gains are given, one f32 rounding per add, and `acc || 0`
     unless raw.  Rows of one length give exactly score_chain of their stack; a piece of several instruments, each rendered for its own
-    note length, is one such chain over the voices in the caller's order."""
+    note length, is one such chain over the voices in the caller's order.
+
+    fracs (float64 [voices], 0 <= f < 1; None: today's chain, untouched): voice k starts at onset_k + frac_k samples.  A voice whose
+    fraction is 0 is the voice above.  One whose fraction is not covers the len_k + 1 samples onset_k .. onset_k + len_k with the terms
+    of two_tap_terms over x[s] = f32(row_k[c][s] * g_k) (or row_k[c][s]), each added by a plain f32 add in voice order — the reference's
+    Delay by a fraction (the contract of dusp_score_rows_frac_device).  A voice of length 0 takes no part."""
     rows = [np.asarray(r, dtype=np.float32) for r in rows]
     n = len(rows)
     if any(r.ndim != 2 for r in rows):
@@ -147,6 +207,8 @@ def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None,
         gains = np.asarray(gains, dtype=np.float32)
         if gains.shape != (n,):
             raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+    if fracs is not None:
+        fracs = check_fracs(fracs, n)
     if init is not None:
         init = np.asarray(init, dtype=np.float32)
         if init.shape != (n_ch, n_total):
@@ -155,6 +217,15 @@ def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None,
         acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
         for k in range(n):
             onset, length = int(onsets[k]), int(lengths[k])
+            if fracs is not None and fracs[k] != 0 and length > 0:  # the span is one sample longer: the last sample's ceil tap
+                t0, t1 = max(onset, 0), min(onset + length + 1, n_total)
+                if t1 <= t0:
+                    continue
+                x = rows[k][:, :length]
+                if gains is not None:
+                    x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
+                acc[:, t0:t1] = acc[:, t0:t1] + two_tap_terms(x, fracs[k])[:, t0 - onset:t1 - onset]  # float32 + float32: one f32 rounding
+                continue
             t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
             if t1 <= t0:
                 continue
@@ -174,7 +245,7 @@ def pan_comp(pans):
     return np.array([math.pow(10, ((1 - abs(float(p))) * 1.5) / 20) for p in np.asarray(pans, dtype=np.float32).ravel()], dtype=np.float64)
 
 
-def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=None, init=None, raw=False, comp=None):
+def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=None, init=None, raw=False, comp=None, fracs=None):
     """rows: a list of MONO float32 arrays [1, samples_k], onsets int64 [voices], pans float32 [voices] (finite, NOT clamped) -> float32
     [2, n_total]: the contract of dusp_score_rows_pan_device.  It is score_chain_rows with the reference's Pan unit (Pan.js:21-22) applied
     where a voice is added to the timeline: for every timeline sample t
@@ -188,7 +259,10 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
 
     every f64 operation rounded by itself.  comp: float64 [voices], None for pan_comp(pans).  Everything else — skipped adds, lengths
     clipped in int64, onsets of any sign, raw partial sums continued through init, windows of the timeline — is score_chain_rows' word for
-    word.  It is what the reference renders for Sum.many(Delay(Pan(Multiply(voice_k, g_k), pan_k), onset_k, maxDelay))."""
+    word.  It is what the reference renders for Sum.many(Delay(Pan(Multiply(voice_k, g_k), pan_k), onset_k, maxDelay)).
+
+    fracs: as score_chain_rows' (None: today's chain, untouched).  The two taps are applied per channel to the Pan unit's output: the
+    f32 left and right values above take the place of x in two_tap_terms — Delay(Pan(Multiply(v, g), p), onset + frac)."""
     rows = [np.asarray(r, dtype=np.float32) for r in rows]
     n = len(rows)
     if any(r.ndim != 2 or r.shape[0] != 1 for r in rows):
@@ -231,6 +305,8 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
         gains = np.asarray(gains, dtype=np.float32)
         if gains.shape != (n,):
             raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+    if fracs is not None:
+        fracs = check_fracs(fracs, n)
     if init is not None:
         init = np.asarray(init, dtype=np.float32)
         if init.shape != (2, n_total):
@@ -239,6 +315,18 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
         acc = init.copy() if init is not None else np.zeros((2, n_total), dtype=np.float32)
         for k in range(n):
             onset, length = int(onsets[k]), int(lengths[k])
+            if fracs is not None and fracs[k] != 0 and length > 0:  # the span is one sample longer: the last sample's ceil tap
+                t0, t1 = max(onset, 0), min(onset + length + 1, n_total)
+                if t1 <= t0:
+                    continue
+                x = rows[k][0, :length]
+                if gains is not None:
+                    x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
+                xd, p = x.astype(np.float64), np.float64(pans[k])
+                both = np.stack([(((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32),
+                                 (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)])
+                acc[:, t0:t1] = acc[:, t0:t1] + two_tap_terms(both, fracs[k])[:, t0 - onset:t1 - onset]  # float32 + float32: one f32 rounding
+                continue
             t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
             if t1 <= t0:
                 continue

@@ -213,13 +213,13 @@ def _score_program(outlets, onsets, voice_duration, duration, lengths, gains, en
 
 
 def _score_voice_duration(voice_duration):
-    """render_score with pans goes through the piece's call as ONE part: one duration for all voices"""
+    """render_score with pans or fracs goes through the piece's call as ONE part: one duration for all voices"""
     if np.ndim(voice_duration) != 0:
         raise ValueError("dusp-hip: voice_duration is one number")
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -228,9 +228,12 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     of no samples is refused, and onsets, lengths and gains are checked whatever the durations.
 
     pans: as render_piece's — mono voices, two channels out; the piece's call with the score as its one part (tile_instances does not
-    apply: the tiles are the piece's default, by bytes)."""
-    if pans is not None:
-        return render_piece(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, _one_part=True)
+    apply: the tiles are the piece's default, by bytes).
+
+    fracs: as render_piece's — voice k starts at onsets[k] + fracs[k] samples; the piece's call with the score as its one part, as
+    with pans."""
+    if pans is not None or fracs is not None:
+        return render_piece(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, _one_part=True, fracs=fracs)
     uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
     result = ChannelData()
     result.sampleRate = uni.sample_rate
@@ -243,10 +246,11 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None):
+                     tile_instances=0, pans=None, fracs=None):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
-    if pans is not None:
-        return render_piece_pcm(outlets, onsets, _score_voice_duration(voice_duration), duration, bit_depth, normalise, lengths, gains, engine, device, 0, pans, _one_part=True)
+    if pans is not None or fracs is not None:
+        return render_piece_pcm(outlets, onsets, _score_voice_duration(voice_duration), duration, bit_depth, normalise, lengths, gains, engine, device, 0, pans, _one_part=True,
+                                fracs=fracs)
     if bit_depth not in _PCM_FORMAT:
         raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
     if normalise not in (0, 1, 2):
@@ -263,9 +267,9 @@ def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None):
+                     tile_instances=0, pans=None, fracs=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
-    pcm = render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans)
+    pcm = render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs)
     if bit_depth == 32:
         return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
     return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
@@ -328,9 +332,9 @@ def check_pan_channels(channels):
     return 2
 
 
-def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None, one_part=False):
-    """-> PieceParts, samples per voice, samples of timeline, onsets, lengths, gains, channels (all checked: nothing is built yet);
-    with pans: the checked pans behind them, and channels is the timeline's two"""
+def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None, one_part=False, fracs=None):
+    """-> PieceParts, samples of timeline, onsets, lengths, gains, channels, pans, fracs (all checked: nothing is built yet).  With pans
+    the voices are mono and channels is the timeline's two; pans and fracs come back as None where none were given."""
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
     if n == 0:
@@ -356,31 +360,30 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None
             raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
     if pans is not None:
         pans, _ = runtime.pan_arrays(pans, n)
+    if fracs is not None:
+        fracs = runtime.frac_arrays(fracs, n)
     grouped = piece_parts(extractions, voice_samples)
-    if one_part and len(grouped.parts) != 1:  # (render_score with pans)
+    if one_part and len(grouped.parts) != 1:  # (render_score with pans or fracs)
         raise descriptor.DuspError("dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments")
     channels = [runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts]
-    if pans is not None:
-        return grouped, n_total, onsets, lengths, gains, check_pan_channels(channels), pans
-    return grouped, n_total, onsets, lengths, gains, check_piece_channels(channels)
+    return grouped, n_total, onsets, lengths, gains, check_pan_channels(channels) if pans is not None else check_piece_channels(channels), pans, fracs
 
 
-def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0, pans=None):
+def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0, pans=None, fracs=None):
     ctx = context(grouped.sample_rate, device)
     programs = []
     try:
         for uni, _ in grouped.parts:
             programs.append(ctx.build(uni.words, engine))
         parts = [(prog, n_voice, uni.n_instances, uni.params) for prog, (uni, n_voice) in zip(programs, grouped.parts)]
-        if pans is not None:
-            return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, pans=pans)
-        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise)
+        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, pans=pans, fracs=fracs)
     finally:
         for prog in programs:
             prog.close()
 
 
-def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False):
+def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
+                 fracs=None):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -390,40 +393,39 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
 
     pans (one finite number a voice, -1 left .. +1 right, not clamped): the voices are MONO circuits and voice k is placed in the stereo
     field where it is added to the timeline — what the reference renders for `Pan(voice_k, pans[k])` in the voice's place (with gains:
-    `Pan(Multiply(voice_k, g_k), pans[k])`), bit for bit (mix.score_chain_rows_panned).  The result has two channels."""
-    if pans is not None:
-        grouped, n_total, onsets, lengths, gains, channels, pans = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, _one_part)
-    else:
-        grouped, n_total, onsets, lengths, gains, channels = _piece(outlets, onsets, voice_durations, duration, lengths, gains)
+    `Pan(Multiply(voice_k, g_k), pans[k])`), bit for bit (mix.score_chain_rows_panned).  The result has two channels.
+
+    fracs (one number a voice, 0 <= f < 1; onsets stay whole numbers): voice k starts at onsets[k] + fracs[k] samples — what the
+    reference renders for `Delay(., onsets[k] + fracs[k], maxDelay)`, whose two taps carry the weights 1 - frac and frac (mix.two_tap_terms;
+    DESIGN.md 6.11 says where the reference's ring departs from it).  dusp_amd.split_onsets makes both arrays from positions in samples
+    written as real numbers.  A voice with a fraction covers one more sample; all fractions zero gives the bits of the call without."""
+    grouped, n_total, onsets, lengths, gains, channels, pans, fracs = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, _one_part, fracs)
     result = ChannelData()
     result.sampleRate = grouped.sample_rate
     if n_total > 0:
-        result.extend(_render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, pans=pans))
+        result.extend(_render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, pans=pans, fracs=fracs))
     return result
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     if bit_depth not in _PCM_FORMAT:
         raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
     if normalise not in (0, 1, 2):
         raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
-    if pans is not None:
-        grouped, n_total, onsets, lengths, gains, channels, pans = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, _one_part)
-    else:
-        grouped, n_total, onsets, lengths, gains, channels = _piece(outlets, onsets, voice_durations, duration, lengths, gains)
+    grouped, n_total, onsets, lengths, gains, channels, pans, fracs = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, _one_part, fracs)
     if n_total == 0:
         data, peak = wav.encode_frames(np.zeros((channels, 0), dtype=np.float32), bit_depth, normalise)
     else:
-        data, peak = _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, _PCM_FORMAT[bit_depth], normalise, pans=pans)
+        data, peak = _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, _PCM_FORMAT[bit_depth], normalise, pans=pans, fracs=fracs)
     return PcmData(data, bit_depth, grouped.sample_rate, peak)
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None):
+                     tile_bytes=0, pans=None, fracs=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
-    pcm = render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans)
+    pcm = render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs)
     if bit_depth == 32:
         return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
     return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)

@@ -29,6 +29,7 @@ EXPORTS = [
     "dusp_score_device", "dusp_render_host_score", "dusp_score_last_ms",
     "dusp_score_rows_device", "dusp_render_host_score_parts", "dusp_descriptor_channels",
     "dusp_score_rows_pan_device", "dusp_render_host_score_parts_pan",
+    "dusp_score_rows_frac_device", "dusp_render_host_score_parts_frac",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -100,6 +101,8 @@ def load():
     L.dusp_descriptor_channels.argtypes = [vp, sz]
     L.dusp_score_rows_pan_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
     L.dusp_render_host_score_parts_pan.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    L.dusp_score_rows_frac_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
+    L.dusp_render_host_score_parts_frac.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -136,6 +139,13 @@ def pan_arrays(pans, n, comp=None):
         if comp.shape != (n,):
             raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
     return pans, comp
+
+
+def frac_arrays(fracs, n):
+    """fracs of n voices -> float64 [n]: checked — one finite fraction of a sample a voice, 0 <= f < 1 — by the strings the library uses
+    (dusp_amd/mix.py check_fracs).  Needs no device."""
+    from .mix import check_fracs
+    return check_fracs(fracs, n)
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -345,15 +355,47 @@ class Context:
                                                        lp, d_gains, pans.ctypes.data if n else None, comp.ctypes.data if n else None, n_total_samples, d_init, int(bool(raw)),
                                                        d_out, stream))
 
+    def score_rows_frac(self, rows, row_samples, n_channels, onsets, fracs, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, pans=None,
+                        comp=None, stream=None):
+        """score_rows_device — or, with pans, score_rows_pan (n_channels must be 1, the timeline has two) — with voice k starting at
+        onsets[k] + fracs[k] samples (dusp_score_rows_frac_device; dusp_amd/mix.py score_chain_rows / score_chain_rows_panned with fracs is
+        the contract): fracs a HOST array of finite f64 in [0, 1), None for all zero.  A voice with a fraction is heard through the
+        reference Delay's two taps and covers one more sample; one without is the voice of those calls, and a call without any fraction
+        launches their kernels.  score_last_ms() reports the call."""
+        n = len(rows)
+        samples = np.asarray(row_samples) if n else np.zeros(0, dtype=np.uint32)
+        if samples.shape != (n,) or samples.dtype.kind not in "iu" or np.any(samples < 0) or np.any(samples > 0xffffffff):
+            raise ValueError("dusp-hip: row_samples must be whole numbers 0 .. 2^32 - 1 of shape (voices=%d,)" % n)
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        pointers = np.array([int(r or 0) for r in rows], dtype=np.uint64)
+        onsets = _whole_samples(onsets, n, "onsets")
+        if fracs is not None:
+            fracs = frac_arrays(fracs, n)
+        pp = cp = None
+        if pans is not None:
+            pans, comp = pan_arrays(pans, n, comp)
+            if n == 0:  # (no voices: `|| 0`, or a copy, of both channels of d_init; the pointer only says "two channels")
+                pans, comp = np.zeros(1, dtype=np.float32), np.ones(1, dtype=np.float64)
+            pp, cp = pans.ctypes.data, comp.ctypes.data
+        lp = None
+        if lengths is not None:
+            lengths = _whole_samples(lengths, n, "lengths")
+            lp = lengths.ctypes.data
+        self._check(self._L.dusp_score_rows_frac_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, n_channels,
+                                                        onsets.ctypes.data if n else None, fracs.ctypes.data if fracs is not None and n else None, lp, d_gains, pp, cp,
+                                                        n_total_samples, d_init, int(bool(raw)), d_out, stream))
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None):
+                           pans=None, fracs=None):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
         on its compiled kernel, in the caller's voice order, whatever tile_bytes (0: the library's default) cuts the voice list into.
         onsets, lengths, gains: per voice, in chain order; format, normalise and what is returned: as Program.render_score.
         pans (one finite f32 a voice): the parts are MONO and voice k is panned where it is added (dusp_render_host_score_parts_pan;
-        mix.score_chain_rows_panned): the result has two channels."""
+        mix.score_chain_rows_panned): the result has two channels.
+        fracs (one finite f64 in [0, 1) a voice): voice k starts at onsets[k] + fracs[k] samples (dusp_render_host_score_parts_frac; the
+        contracts above with fracs), with or without pans."""
         if not parts:
             raise ValueError("dusp-hip: a piece has at least one part")
         n = len(part_of)
@@ -385,7 +427,17 @@ class Context:
                 pp = params.ctypes.data
             table[p] = ScorePart(prog._h, n_instances, n_voice_samples, pp)
         n_ch = parts[0][0].n_out_channels
-        if pans is None:
+        if fracs is not None:
+            fracs = frac_arrays(fracs, n)
+            comp = None
+            if pans is not None:
+                pans, comp = pan_arrays(pans, n)
+                n_ch = 2  # (parts that are not mono: the library refuses them)
+
+            def call(*args):  # (the fractions behind the onsets; the pans and their compensation, or two NULLs, behind the gains)
+                return self._L.dusp_render_host_score_parts_frac(*(args[:5] + (fracs.ctypes.data,) + args[5:7] +
+                                                                   ((pans.ctypes.data, comp.ctypes.data) if pans is not None else (None, None)) + args[7:]))
+        elif pans is None:
             def call(*args):
                 return self._L.dusp_render_host_score_parts(*args)
         else:

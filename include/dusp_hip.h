@@ -435,6 +435,52 @@ int dusp_render_host_score_parts_pan(const dusp_score_part *parts, size_t n_part
                                      const double *h_comp, size_t n_total_samples, size_t tile_bytes, int format, int normalise,
                                      void *h_out, float *h_peak);
 
+/* Sub-sample onsets: dusp_score_rows_device and dusp_score_rows_pan_device with voice k starting at onset_k + frac_k samples,
+ * 0 <= frac_k < 1 (additions to ABI v7, detected by symbol).  The reference's Delay takes any delay (src/components/Delay.js:36-38): it
+ * writes every input sample to two neighbouring ring slots with the weights 1 - frac and frac.  Write x[s] for voice k's sample s after
+ * the gain — f32(row_k[c][s] * g_k), or row_k[c][s]; with h_pans the Pan unit's f32 output per channel, as dusp_score_rows_pan_device
+ * forms it — and len for its length.
+ *   frac_k == 0: the voice is exactly dusp_score_rows_device's: span onset_k .. onset_k + len - 1, term x[s].  A call whose fractions
+ *                are all zero (or h_fracs NULL) launches the kernels of those calls and gives their bits.
+ *   frac_k != 0: w1 = frac_k, w0 = 1.0 - frac_k (one f64 subtraction); the voice covers the len + 1 samples onset_k .. onset_k + len,
+ *                and with s = t - onset_k
+ *                    c(s)      = f32(f64(x[s-1]) * w1)                 1 <= s <= len
+ *                    term(0)   = f32(f64(x[0]) * w0)
+ *                    term(s)   = f32(f64(c(s)) + f64(x[s]) * w0)       1 <= s <  len   (every f64 operation rounded by itself: no FMA)
+ *                    term(len) = c(len)
+ *                    acc       = f32(acc + term(s))                                    (in voice index order)
+ *                A voice of length 0 takes no part.
+ * Everything else — the skipped add outside the span, d_init, raw, `acc || 0`, lengths clipped in int64, onsets at the int64 limits,
+ * windows of the timeline as the same chain with onset_k - lo — is dusp_score_rows_device's (dusp_amd/mix.py score_chain_rows and
+ * score_chain_rows_panned with fracs are the contract in numpy).
+ * It is what the reference renders for Sum.many(Delay(Pan(Multiply(v_k, g_k), p_k), onset_k + frac_k, maxDelay)), within three limits:
+ *   1. the reference's ring drops a ceil tap that lands on ring index maxDelay, once per trip round the ring: a quirk of the ring, not
+ *      of the placement, not reproduced (the reference agrees where maxDelay > timeline + largest onset + 2);
+ *   2. a delay in (0, 1) puts the floor tap into the slot the unit has just read, so that it is heard a whole ring later: not
+ *      reproduced (the reference agrees where onset_k >= 1);
+ *   3. the reference rounds an inlet constant to f32: it agrees where onset_k + frac_k is an f32; elsewhere this call is more exact,
+ *      since the fraction stays a double.
+ *   h_fracs   f64 [n_voices], HOST memory, finite, in [0, 1); NULL: all zero
+ *   h_pans    NULL: rows of n_channels into a timeline of n_channels, as dusp_score_rows_device.  Else n_channels must be 1 and the
+ *             timeline has two channels, as dusp_score_rows_pan_device; h_comp as there
+ * The voices' weights (w0 and w1 as doubles, 16 bytes a voice) go up with the plan, on top of the plan's byte budget, which counts
+ * records and lists as before; dusp_score_last_ms reports this call too.  DUSP_ERR_ARG, with a message ("the fraction of voice k is
+ * not finite", "... is outside [0, 1)"), checked before anything is launched, and for everything the calls without fractions refuse. */
+int dusp_score_rows_frac_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices,
+                                size_t n_channels, const int64_t *h_onsets, const double *h_fracs, const int64_t *h_lengths,
+                                const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples,
+                                const float *d_init, int raw, float *d_out, void *stream);
+
+/* dusp_render_host_score_parts (h_pans NULL) or dusp_render_host_score_parts_pan with a fraction of a sample per voice: a tile one of
+ * whose voices has a fraction is dusp_score_rows_frac_device's launch, the others are launched as before.  The fractions are checked
+ * before anything is rendered.
+ *   h_fracs   f64 [n_voices], in chain order, as for dusp_score_rows_frac_device; NULL: all zero
+ * Everything else, refusals included, is dusp_render_host_score_parts[_pan]'s. */
+int dusp_render_host_score_parts_frac(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                      const int64_t *h_onsets, const double *h_fracs, const int64_t *h_lengths, const float *h_gains,
+                                      const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes, int format,
+                                      int normalise, void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

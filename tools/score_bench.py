@@ -11,6 +11,10 @@
   pan     (--pan; profiles/score_pan.txt) the panned kernel (dusp_score_rows_pan_device) over dense MONO rows of the dense shapes, kernel
           alone by dusp_score_last_ms, against dusp_score_rows_device over the same voices as TWO-CHANNEL rows — unchanged code, and what a
           panned piece costs without it: every voice a two-channel circuit with a Pan unit inside.
+  frac    (--frac; profiles/score_frac.txt) the two-tap kernel (dusp_score_rows_frac_device) over dense MONO rows of the dense shapes, every
+          fraction non-zero — plain, with gains and panned — kernel alone by dusp_score_last_ms, against dusp_score_rows_device (and
+          dusp_score_rows_pan_device for the panned case) over the same rows, which is unchanged code; and the new entry point with all
+          fractions zero, which launches those kernels.
   piece   8192 notes of 0.5 s placed over 60 s in onset order: Program.render_score on the host's clock, against the render of the same
           notes alone (render_device into a preallocated buffer) and against the same piece with the onsets shuffled — every tile's
           union window is then the whole timeline, which is what the window is worth.  One run under DUSP_JIT_LOG=2 prints the plans'
@@ -118,6 +122,58 @@ def pan(key, scale, ctxs, reps):
     print("  panned / two-channel rows: x%.3f (with gains x%.3f); %.1f voice terms per ns and channel pair" % (t_pan[0] / t_wide[0], t_gain[0] / t_wide[0], V * n / t_pan[0] / 1e6), flush=True)
 
 
+def frac(key, scale, ctxs, reps):
+    import torch
+    V, n = max(64, DENSE[key][0] // scale), DENSE[key][1]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    ctx = ctxs["default"]
+    onsets = np.zeros(V, dtype=np.int64)
+    samples = np.full(V, n, dtype=np.uint32)
+    rng = np.random.RandomState(6)
+    pans = (rng.random_sample(V) * 2 - 1).astype(np.float32)
+    fracs = rng.randint(1, 1024, V) / 1024.0
+    zeros = np.zeros(V)
+    mono = torch.empty((V, 1, n), dtype=torch.float32, device="cuda").normal_()
+    acc = torch.empty((2, n), dtype=torch.float32, device="cuda")
+    d_gains = torch.ones(V, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    pointers = [mono.data_ptr() + 4 * n * k for k in range(V)]
+    read = V * n * 4
+
+    def median_of(call):
+        kernel, plan, upload = [], [], []
+        for r in range(reps + 1):
+            call()
+            k, p, u = ctx.score_last_ms()
+            if r:
+                kernel.append(k), plan.append(p), upload.append(u)
+        return float(np.median(kernel)), min(kernel), float(np.median(plan)), float(np.median(upload))
+
+    line = "  %-52s kernel median %9.3f ms  fastest %9.3f   %5.2f TB/s of rows   x%.3f   [plan on the host %.2f ms, its upload %.2f ms]"
+    print("frac %s: %d mono voices x %d samples = %.2f GB of rows, all onsets 0, full lengths" % (key, V, n, read / 1e9), flush=True)
+    g = d_gains.data_ptr()
+    for label, old, new, zero in [
+        ("plain", lambda: ctx.score_rows_device(pointers, samples, 1, onsets, n, acc.data_ptr(), stream=s),
+         lambda: ctx.score_rows_frac(pointers, samples, 1, onsets, fracs, n, acc.data_ptr(), stream=s),
+         lambda: ctx.score_rows_frac(pointers, samples, 1, onsets, zeros, n, acc.data_ptr(), stream=s)),
+        ("gains", lambda: ctx.score_rows_device(pointers, samples, 1, onsets, n, acc.data_ptr(), d_gains=g, stream=s),
+         lambda: ctx.score_rows_frac(pointers, samples, 1, onsets, fracs, n, acc.data_ptr(), d_gains=g, stream=s), None),
+        ("panned", lambda: ctx.score_rows_pan(pointers, samples, onsets, pans, n, acc.data_ptr(), stream=s),
+         lambda: ctx.score_rows_frac(pointers, samples, 1, onsets, fracs, n, acc.data_ptr(), pans=pans, stream=s),
+         lambda: ctx.score_rows_frac(pointers, samples, 1, onsets, zeros, n, acc.data_ptr(), pans=pans, stream=s)),
+        ("panned, gains", lambda: ctx.score_rows_pan(pointers, samples, onsets, pans, n, acc.data_ptr(), d_gains=g, stream=s),
+         lambda: ctx.score_rows_frac(pointers, samples, 1, onsets, fracs, n, acc.data_ptr(), d_gains=g, pans=pans, stream=s), None),
+    ]:
+        t_old = median_of(old)
+        print(line % (("%s: whole-sample kernel (unchanged code)" % label, t_old[0], t_old[1], read / t_old[0] / 1e9, 1.0) + t_old[2:]), flush=True)
+        t_new = median_of(new)
+        print(line % (("%s: two-tap kernel, every fraction non-zero" % label, t_new[0], t_new[1], read / t_new[0] / 1e9, t_new[0] / t_old[0]) + t_new[2:]), flush=True)
+        if zero:
+            t_zero = median_of(zero)
+            print(line % (("%s: new entry point, all fractions zero" % label, t_zero[0], t_zero[1], read / t_zero[0] / 1e9, t_zero[0] / t_old[0]) + t_zero[2:]), flush=True)
+
+
 def piece(scale, ctxs, reps):
     import torch
     V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
@@ -159,13 +215,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--scale", type=int, default=1, help="divide every voice count by this (a quick look)")
     ap.add_argument("--pan", action="store_true", help="the pan leg alone, over the dense cases named by --cases")
+    ap.add_argument("--frac", action="store_true", help="the sub-sample-onset leg alone, over the dense cases named by --cases")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
     for key in a.cases:
         if key in DENSE:
-            (pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
-    if "p" in a.cases and not a.pan:
+            (frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
+    if "p" in a.cases and not a.pan and not a.frac:
         piece(a.scale, ctxs, a.reps)
 
 
