@@ -4,7 +4,9 @@
 //   abi_program.hip     build / continue / destroy, program info, state download
 //   abi_render.hip      device renders: one step per engine
 //   abi_render_jit.hip  ... the render on a compiled circuit kernel
-//   abi_deliver.hip     interleave / peak / encode / mix / score, host renders and their delivery
+//   abi_deliver.hip     interleave / peak / encode, host renders and their delivery
+//   abi_mix.hip         mix of a batch on the device, the tiles of a large batch, the host render of a mix
+//   abi_score.hip       scores: plans' image, the one launch path, device entries and host renders of scores and pieces
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -367,3 +369,48 @@ void finish_render(dusp_program *prog, uint32_t n_inst, uint32_t n_pad, uint64_t
 // abi_render_jit.hip
 int render_jit(dusp_program *prog, uint32_t n_inst, size_t n_samples, uint32_t n_chunks, const float *d_params, const float *d_inputs, float *d_out,
                hipStream_t stream, uint32_t handoff_chunks = 0, bool probe = false);
+
+#pragma GCC visibility push(hidden)  // (what follows crosses files of the library and is no symbol of it)
+// 1..64 channels of [1, 2^24] instances x [1, 2^31] samples: what the kernels over planar PCM take (dusp_peak_device, dusp_mix_device)
+inline int check_planar_pcm(dusp_ctx *ctx, const char *who, size_t n_instances, size_t n_channels, size_t n_samples) {
+    if (!channels_in_range(n_channels) || !batch_in_range(n_instances, n_samples))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": need 1..64 channels, 1..2^24 instances and 1..2^31 samples");
+    return DUSP_OK;
+}
+
+// abi_deliver.hip
+// What a host render ends with: d_planar f32 [n_instances][n_ch][n_samples] (or, already transposed, d_frames) reaches h_out — as it is,
+// or (pcm_format != 0) through the peak and encode kernels; waits for the stream.
+int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
+                 int normalise, float *h_peaks, void *h_out);
+
+// abi_mix.hip
+constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)
+
+// The tiles of one batch (dusp_render_host_mix, dusp_render_host_score, a part of dusp_render_host_score_parts).  Tiling must not change a
+// bit.  What a render decides from the batch and that changes bits is, while the tiles render, decided from the WHOLE batch: a Filter with
+// a per-instance cutoff runs as a scan or as a recurrence — not the same bits — by the range of its column (mix_range), and so does every
+// scan-eligible Filter by whether the render is cut into warming segments, which the instance count decides (mix_n_inst, which also makes
+// every tile wait for its compiled kernel).  Per-instance Delays are classified per tile: their regimes differ in speed only.
+struct TiledBatch {
+    dusp_program *prog;
+    hipStream_t stream;
+    size_t n_instances, n_params, tile;
+    const float *h_gains;
+    bool staged = false;      // host vectors of this call may still be on their way to the device
+    std::vector<float> cols;  // (a member: it outlives the destructor's wait for the stream)
+
+    TiledBatch(dusp_program *prog, size_t n_instances, const float *h_params, const float *h_gains, size_t tile);  // tiles of `tile` instances
+    TiledBatch(dusp_program *prog, size_t n_instances, const float *h_params, const std::vector<size_t> &starts);  // tiles [starts[i], starts[i + 1])
+    ~TiledBatch();
+    // instances [lo, lo + n): their columns and gains to the device, their PCM into d_host_out
+    int render_tile(size_t lo, size_t n, size_t n_samples);
+
+private:
+    void gather(const float *h_params, size_t lo, size_t n);
+    void whole_batch_decisions(const float *h_params);
+};
+// what dusp_render_host_mix and the host renders of scores refuse alike, and the tile a program renders in
+int tiled_batch_prepare(dusp_program *prog, const char *who, size_t n_instances, size_t n_samples, const float *h_params, const float *h_gains, size_t tile_instances,
+                        int format, int normalise, const void *h_out, size_t *tile_out);
+#pragma GCC visibility pop

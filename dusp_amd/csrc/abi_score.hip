@@ -1,0 +1,533 @@
+// abi_score.hip — the C ABI (include/dusp_hip.h): voices mixed at per-voice onsets into a timeline (score_plan.hpp and the four score
+// engines): the plans' image on the device, the one launch path, the device entries (dusp_score_device, dusp_score_rows_device and its
+// pan and frac forms) and the host round trips (dusp_render_host_score, dusp_render_host_score_parts and its pan and frac forms).
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+
+#include "abi_internal.hpp"
+#include "render_plan.hpp"
+
+// ---- the plans of a call: an image on the host, uploaded once, and one description per launch ----
+
+// which kernel a launch is: voices of one contiguous batch (score_engine.hip; dusp_amd/mix.py score_chain is the contract), rows of their
+// own (score_rows_engine.hip; score_chain_rows), or mono rows placed in the stereo field (score_pan_engine.hip; score_chain_rows_panned)
+enum class ScoreKind { contiguous, rows, pan };
+
+// one launch's plan inside the context's image
+struct ScoreLaunch {
+    ScoreKind kind;      // a launch without voices (`|| 0`, or a copy, of d_init alone) keeps the kind of its call
+    size_t at = 0, n_voices = 0, n_block_first = 0;  // byte offset of the voices; block_first and the entries follow
+    uint64_t w_lo = 0, w_hi = 0, first_block = 0;
+    uint32_t block_shift = dusp::kScoreGroupShift;
+    bool any = false;  // some voice reaches the timeline (else: no plan in the image)
+    size_t pan_at = 0;  // a panned launch: byte offset of its voices' coefficients (dusp::ScorePan), behind the plan
+    bool frac = false;   // some listed voice starts between samples: the launch is score_frac_engine.hip's, plain rows or panned ...
+    size_t frac_at = 0;  // ... and this the byte offset of its voices' weights (dusp::ScoreFrac), behind the plan
+    explicit ScoreLaunch(ScoreKind kind_, uint64_t n_total = 0) : kind(kind_), w_hi(n_total) {}  // (n_total: over the whole timeline)
+};
+
+// before a call rewrites the context's host image: the last upload has read it
+static int score_image_begin(dusp_ctx *ctx) {
+    if (!ctx->score_uploaded) {
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_uploaded));  // (with timing: dusp_score_last_ms)
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->score_done, hipEventDisableTiming));
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_up0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_t0));
+        HIP_TRY(ctx, hipEventCreate(&ctx->score_t1));
+    } else {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->score_uploaded));
+    }
+    ctx->h_score_plan.clear();
+    ctx->score_upload_timed = false;  // (score_up0 .. score_uploaded are about to be another call's)
+    return DUSP_OK;
+}
+
+// what the plans of ONE call may take together, on the host and on the device
+static size_t score_plan_budget(dusp_ctx *ctx) { return ctx->knobs.score_plan_kb > 0 ? (size_t)ctx->knobs.score_plan_kb << 10 : dusp::kScorePlanBytes; }
+
+// a made plan of n voices: appended to the context's host image on the boundary of its record, and its launch described in L
+template <class Record>
+static void score_image_add(dusp_ctx *ctx, const dusp::ScorePlanT<Record> &P, size_t n, ScoreLaunch &L) {
+    L.w_lo = (uint64_t)P.w_lo;
+    L.w_hi = (uint64_t)P.w_hi;
+    L.block_shift = P.block_shift;
+    L.first_block = P.first_block;
+    L.any = P.n_entries() > 0;
+    if (L.any) {
+        L.n_voices = n;
+        L.n_block_first = P.block_first.size();
+        L.at = dusp::score_plan_pack(P, ctx->h_score_plan);
+    }
+}
+// one record a voice of the plan just added (L), appended behind it on the boundary of the record: they go up with the plan
+template <class Record, class Make>
+static size_t score_image_append(dusp_ctx *ctx, size_t n, Make &&make) {
+    std::vector<unsigned char> &image = ctx->h_score_plan;
+    const size_t at = (image.size() + alignof(Record) - 1) & ~(alignof(Record) - 1);
+    image.resize(at + n * sizeof(Record));
+    for (size_t k = 0; k < n; k++) {
+        const Record r = make(k);
+        std::memcpy(image.data() + at + k * sizeof r, &r, sizeof r);
+    }
+    return at;
+}
+
+// plans the voices [0, n) of a contiguous batch within budget_bytes and adds the plan to the image
+static int score_voices_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, size_t n, size_t first_voice, uint64_t n_voice,
+                            uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L) {
+    dusp::ScorePlan P;
+    const int64_t bad = dusp::score_plan(h_onsets, h_lengths, n, n_voice, n_total, whole_timeline, budget_bytes, P);
+    if (bad >= 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
+                                        ": lengths must lie in 0 .. n_voice_samples");
+    score_image_add(ctx, P, n, L);
+    return DUSP_OK;
+}
+
+// ... and the voices [0, n) that are rows — voice k row_samples[k] samples a channel at device address rows[k].  listed (optional): which
+// voices reach the timeline.  h_fracs (optional): the voices' fractions of a sample, checked; where a listed voice has one, its weights
+// (dusp::ScoreFrac, 16 bytes a voice on top of the budget) follow the plan and the launch is the two-tap kernel's — else the image and
+// the launch are as without.
+static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n,
+                          size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L, std::vector<unsigned char> *listed = nullptr,
+                          const double *h_fracs = nullptr) {
+    dusp::ScoreRowsPlan P;
+    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, h_fracs);
+    if (bad >= 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
+                                        ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
+    score_image_add(ctx, P, n, L);
+    for (size_t k = 0; k < n && L.any && !L.frac; k++) L.frac = P.voices[k].hi > P.voices[k].lo && P.voices[k].pad != 0;
+    if (L.frac) L.frac_at = score_image_append<dusp::ScoreFrac>(ctx, n, [&](size_t k) { return dusp::score_frac_weights(h_fracs[k]); });
+    if (listed) {
+        listed->resize(n);
+        for (size_t k = 0; k < n; k++) (*listed)[k] = P.voices[k].hi > P.voices[k].lo;
+    }
+    return DUSP_OK;
+}
+
+// the pan coefficients of the voices [0, n) of the rows plan just added (L).  h_comp NULL: the reference's compensation by the host's
+// pow (Pan.js:20)
+static void score_pans_add(dusp_ctx *ctx, const float *h_pans, const double *h_comp, size_t n, ScoreLaunch &L) {
+    if (!L.any) return;
+    L.pan_at = score_image_append<dusp::ScorePan>(ctx, n, [&](size_t k) {
+        const double comp = h_comp ? h_comp[k] : std::pow(10.0, ((1.0 - std::fabs((double)h_pans[k])) * 1.5) / 20.0);
+        return dusp::score_pan_coefficients(h_pans[k], comp);
+    });
+}
+
+// the image to the device, ordered on `stream` behind the last launch that read the buffer (whatever stream that one ran on)
+static int score_image_upload(dusp_ctx *ctx, hipStream_t stream) {
+    const size_t n_bytes = ctx->h_score_plan.size();
+    if (!n_bytes) return DUSP_OK;
+    if (n_bytes > ctx->score_plan_cap) {
+        if (ctx->d_score_plan) HIP_TRY(ctx, hipFree(ctx->d_score_plan));  // (waits for the device: no launch is reading it any more)
+        ctx->d_score_plan = nullptr;
+        ctx->score_plan_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_score_plan, n_bytes + g_guard_bytes));
+        if (g_guard_bytes) HIP_TRY(ctx, hipMemset(ctx->d_score_plan + n_bytes, kGuardPattern, g_guard_bytes));
+        ctx->score_plan_cap = n_bytes;
+    }
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->score_done, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->score_up0, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_score_plan, ctx->h_score_plan.data(), n_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->score_uploaded, stream));
+    return DUSP_OK;
+}
+
+static bool score_plan_intact(dusp_ctx *ctx) { return !ctx->d_score_plan || !g_guard_bytes || guard_intact(ctx->d_score_plan + ctx->score_plan_cap); }
+
+// ---- the one launch path ----
+
+// The launch L describes, over its window of a timeline [n_channels][n_total] (pan: mono rows, [2][n_total]).  Its plan is in the image
+// on the device (the buffer and L.at: both on 32-byte boundaries); a launch without voices has none and hands the kernel of its kind NULLs.
+// d_planar, n_voice: the batch of a contiguous launch.
+static int score_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, size_t n_total, const float *d_gains, const float *d_init, int raw, float *d_out,
+                        hipStream_t stream, const float *d_planar = nullptr, size_t n_voice = 0) {
+    if (L.w_hi <= L.w_lo) return DUSP_OK;
+    const unsigned char *d_image = ctx->d_score_plan;
+    const unsigned char *d_voices = L.any ? d_image + L.at : nullptr;
+    const size_t record = L.kind == ScoreKind::contiguous ? sizeof(dusp::ScoreVoice) : sizeof(dusp::ScoreRow);
+    const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices * record) : nullptr, *d_entries = L.any ? d_block_first + L.n_block_first : nullptr;
+    const dusp::ScoreRow *d_rows = (const dusp::ScoreRow *)d_voices;
+    const dusp::ScorePan *d_pans = L.any && L.kind == ScoreKind::pan ? (const dusp::ScorePan *)(d_image + L.pan_at) : nullptr;
+    if (L.any && L.frac)  // (score_frac_engine.hip: plain rows of n_channels, or — d_pans — panned mono rows)
+        HIP_TRY(ctx, dusp::launch_score_frac(d_gains, d_pans, (const dusp::ScoreFrac *)(d_image + L.frac_at), d_rows, d_block_first, d_entries, d_init, d_out,
+                                             L.kind == ScoreKind::pan ? 1u : (uint32_t)n_channels, n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
+    else if (L.kind == ScoreKind::pan)
+        HIP_TRY(ctx, dusp::launch_score_pan(d_gains, d_pans, d_rows, d_block_first, d_entries, d_init, d_out, n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
+    else if (L.kind == ScoreKind::rows)
+        HIP_TRY(ctx, dusp::launch_score_rows(d_gains, d_rows, d_block_first, d_entries, d_init, d_out, (uint32_t)n_channels, n_total, L.w_lo, L.w_hi, L.block_shift,
+                                             L.first_block, raw, stream));
+    else
+        HIP_TRY(ctx, dusp::launch_score(d_planar, d_gains, (const dusp::ScoreVoice *)d_voices, d_block_first, d_entries, d_init, d_out, (uint32_t)n_channels, n_voice, n_total,
+                                        L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
+    if (L.any) HIP_TRY(ctx, hipEventRecord(ctx->score_done, stream));
+    return DUSP_OK;
+}
+
+// What a device entry does once its arguments hold (dusp_score_device, score_rows_device): a fresh image, the call's plan — plan() adds
+// it and describes the launch in L; it is not called without voices, and what it takes on the host is score_plan_ms — its upload, and
+// launch() between the events score_t0 and score_t1 (dusp_score_last_ms)
+template <class Plan, class Launch>
+static int score_device_call(dusp_ctx *ctx, hipStream_t stream, bool voices, const ScoreLaunch &L, Plan &&plan, Launch &&launch) {
+    if (voices) {
+        if (int rc = score_image_begin(ctx)) return rc;
+        const auto t_plan = std::chrono::steady_clock::now();
+        if (int rc = plan()) return rc;
+        ctx->score_plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_plan).count();
+        if (int rc = score_image_upload(ctx, stream)) return rc;
+    } else {
+        if (!ctx->score_t0) {  // (no plan, but the launch is timed like any other)
+            if (int rc = score_image_begin(ctx)) return rc;
+        }
+        ctx->score_plan_ms = 0;
+    }
+    ctx->score_timed = false;
+    ctx->score_upload_timed = L.any;
+    HIP_TRY(ctx, hipEventRecord(ctx->score_t0, stream));
+    if (int rc = launch()) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->score_t1, stream));
+    ctx->score_timed = true;
+    return DUSP_OK;
+}
+
+// What a host render ends with once its tiles are added to the timeline's running sums (prog->d_mix, [n_ch][n_total]): `|| 0` over the
+// whole timeline — a launch of `kind` without voices — the delivery, which waits for the stream, and the guard check
+static int score_deliver_host(dusp_program *prog, const char *who, ScoreKind kind, size_t n_ch, size_t n_total, int format, int normalise, float *h_peak, void *h_out) {
+    dusp_ctx *ctx = prog->ctx;
+    if (int rc = score_launch(ctx, ScoreLaunch(kind, n_total), n_ch, n_total, nullptr, prog->d_mix.p, /*raw=*/0, prog->d_mix.p, ctx->stream)) return rc;
+    if (int rc = deliver_host(prog, prog->d_mix.p, nullptr, 1, n_ch, n_total, format, normalise, h_peak, h_out)) return rc;
+    if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
+    return DUSP_OK;
+}
+
+static int check_pans(dusp_ctx *ctx, const char *who, const float *h_pans, const double *h_comp, size_t n) {
+    for (size_t k = 0; k < n; k++) {
+        if (!std::isfinite(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
+        if (h_comp && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
+    }
+    return DUSP_OK;
+}
+
+static int check_fracs(dusp_ctx *ctx, const char *who, const double *h_fracs, size_t n) {
+    for (size_t k = 0; h_fracs && k < n; k++) {
+        if (!std::isfinite(h_fracs[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is not finite");
+        if (h_fracs[k] < 0.0 || h_fracs[k] >= 1.0) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is outside [0, 1)");
+    }
+    return DUSP_OK;
+}
+
+// ---- device entries ----
+
+extern "C" {
+
+int dusp_score_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, size_t n_channels, size_t n_voice_samples, const int64_t *h_onsets,
+                      const int64_t *h_lengths, const float *d_gains, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    return guarded(ctx->err, "dusp_score_device", [&]() -> int {
+    if (!d_out || (n_instances && (!d_planar || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: NULL buffer");
+    if (!channels_in_range(n_channels) || n_instances > (1u << 24) || !samples_in_range(n_voice_samples) || !samples_in_range(n_total_samples))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: need 1..64 channels, 0..2^24 instances, 1..2^31 samples a voice and 1..2^31 samples of timeline");
+    if (n_channels * n_total_samples > dusp::kScoreRowMax)  // (one lane per float of the timeline: the grid, and the kernel's 32-bit sample positions)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
+    if (n_channels * n_voice_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: channels x voice samples must not exceed 2^31");
+    if ((((uintptr_t)d_planar | (uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_device: the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    ScoreLaunch L(ScoreKind::contiguous, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
+    return score_device_call(
+        ctx, stream, n_instances != 0, L,
+        [&]() {
+            return score_voices_add(ctx, "dusp_score_device", h_onsets, h_lengths, n_instances, 0, n_voice_samples, n_total_samples, /*whole_timeline=*/true,
+                                    score_plan_budget(ctx), L);
+        },
+        [&]() { return score_launch(ctx, L, n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream, d_planar, n_voice_samples); });
+    });
+}
+
+// dusp_score_rows_device, (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device, and (h_fracs: onsets between
+// samples) dusp_score_rows_frac_device
+static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                             const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw,
+                             float *d_out, void *stream_, const double *h_fracs = nullptr) {
+    if (!ctx) return DUSP_ERR_ARG;
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    const size_t n_out_channels = h_pans ? 2 : n_channels;  // (the timeline's)
+    if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (!channels_in_range(n_channels) || n_voices > (1u << 24) || !samples_in_range(n_total_samples))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..64 channels, 0..2^24 voices and 1..2^31 samples of timeline");
+    if (n_out_channels * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
+    if ((((uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
+    for (size_t k = 0; k < n_voices; k++) {
+        if ((uint64_t)h_row_samples[k] * n_channels > dusp::kScoreRowMax)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + ": channels x row samples must not exceed 2^31");
+        if (h_row_samples[k] && !h_rows[k]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " is NULL");
+        if (h_row_samples[k] && ((uintptr_t)h_rows[k] & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " must be 4-byte aligned");
+    }
+    if (h_pans)
+        if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
+    if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    ScoreLaunch L(h_pans ? ScoreKind::pan : ScoreKind::rows, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
+    return score_device_call(
+        ctx, stream, n_voices != 0, L,
+        [&]() {
+            static_assert(sizeof(const float *) == sizeof(uint64_t), "rows are handed to the planner as 64-bit addresses");
+            if (int rc = score_rows_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples, /*whole_timeline=*/true,
+                                        score_plan_budget(ctx), L, nullptr, h_fracs))
+                return rc;
+            if (h_pans) score_pans_add(ctx, h_pans, h_comp, n_voices, L);
+            return (int)DUSP_OK;
+        },
+        [&]() { return score_launch(ctx, L, n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream); });
+    });
+}
+
+// ---- what the last device entry took, and the host renders ----
+
+int dusp_score_last_ms(dusp_ctx *ctx, float *kernel_ms, float *plan_ms, float *upload_ms) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (!ctx->score_timed) CTX_FAIL(ctx, DUSP_ERR_STATE, "dusp_score_last_ms: no dusp_score_device call has been launched on this context");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->score_t1));
+    float k = 0, u = 0;
+    HIP_TRY(ctx, hipEventElapsedTime(&k, ctx->score_t0, ctx->score_t1));
+    if (ctx->score_upload_timed) HIP_TRY(ctx, hipEventElapsedTime(&u, ctx->score_up0, ctx->score_uploaded));
+    if (kernel_ms) *kernel_ms = k;
+    if (plan_ms) *plan_ms = (float)ctx->score_plan_ms;
+    if (upload_ms) *upload_ms = u;
+    return DUSP_OK;
+}
+
+int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voice_samples, size_t n_total_samples, const float *h_params, const float *h_gains,
+                           const int64_t *h_onsets, const int64_t *h_lengths, size_t tile_instances, int format, int normalise, void *h_out, float *h_peak) {
+    if (!prog) return DUSP_ERR_ARG;
+    dusp_ctx *ctx = prog->ctx;
+    return guarded(ctx->err, "dusp_render_host_score", [&]() -> int {
+    const size_t n_ch = prog->P.out_bufs.size();
+    if (!h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_score: h_onsets is NULL");
+    if (!samples_in_range(n_total_samples) || n_ch * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_render_host_score: the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
+    size_t tile = 0;  // (sized over the VOICE's row: the tile holds voices, the timeline is one row beside it)
+    if (int rc = tiled_batch_prepare(prog, "dusp_render_host_score", n_instances, n_voice_samples, h_params, h_gains, tile_instances, format, normalise, h_out, &tile))
+        return rc;
+    // every tile's plan, over the tile's union window, made and uploaded once: the tiles queue up on the stream without the host waiting
+    // (the byte budget is the CALL's, shared out over the tiles: a tile whose lists do not fit its share doubles its block.  What no block
+    // size takes away is 28 bytes a voice — its record, one list entry, one block_first word — and 40 a tile)
+    std::vector<ScoreLaunch> launches((n_instances + tile - 1) / tile, ScoreLaunch(ScoreKind::contiguous));
+    const size_t tile_budget = score_plan_budget(ctx) / launches.size();
+    if (int rc = score_image_begin(ctx)) return rc;
+    const auto t_plan = std::chrono::steady_clock::now();
+    for (size_t lo = 0, i = 0; lo < n_instances; lo += tile, i++)
+        if (int rc = score_voices_add(ctx, "dusp_render_host_score", h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, std::min(tile, n_instances - lo), lo, n_voice_samples,
+                                     n_total_samples, /*whole_timeline=*/false, tile_budget, launches[i]))
+            return rc;
+    if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: what the plans cost the host)
+        fprintf(stderr, "[dusp host score] %zu plans (tiles of %zu voices) in %.0f us on the host: %zu bytes, blocks of %u samples in the first tile\n", launches.size(), tile,
+                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count(), ctx->h_score_plan.size(), 1u << launches[0].block_shift);
+    HIP_TRY(ctx, prog->d_mix.ensure(n_ch * n_total_samples));  // the timeline's running sums
+    if (int rc = score_image_upload(ctx, ctx->stream)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(prog->d_mix.p, 0, n_ch * n_total_samples * sizeof(float), ctx->stream));
+    TiledBatch whole(prog, n_instances, h_params, h_gains, tile);
+    for (size_t lo = 0, i = 0; lo < n_instances; lo += tile, i++) {
+        if (launches[i].w_hi <= launches[i].w_lo) continue;  // (no voice of the tile reaches the timeline: nothing to render)
+        if (int rc = whole.render_tile(lo, std::min(tile, n_instances - lo), n_voice_samples)) return rc;
+        if (int rc = score_launch(ctx, launches[i], n_ch, n_total_samples, h_gains ? prog->d_mix_gains.p : nullptr, prog->d_mix.p, /*raw=*/1, prog->d_mix.p, ctx->stream,
+                                  prog->d_host_out.p, n_voice_samples))
+            return rc;
+    }
+    if (int rc = score_deliver_host(prog, "dusp_render_host_score", ScoreKind::contiguous, n_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
+    whole.staged = false;  // (the delivery has waited for the stream)
+    return DUSP_OK;
+    });
+}
+
+int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                           const int64_t *h_lengths, const float *d_gains, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
+    return score_rows_device(ctx, "dusp_score_rows_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, nullptr, nullptr, n_total_samples, d_init,
+                             raw, d_out, stream_);
+}
+
+int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, const int64_t *h_onsets, const int64_t *h_lengths,
+                               const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw, float *d_out,
+                               void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (n_voices && !h_pans) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_pan_device: h_pans is NULL");
+    static const float no_pans[1] = {0.0f};  // (no voices: `|| 0`, or a copy, of both channels of d_init)
+    return score_rows_device(ctx, "dusp_score_rows_pan_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, h_pans ? h_pans : no_pans, h_comp,
+                             n_total_samples, d_init, raw, d_out, stream_);
+}
+
+// dusp_render_host_score_parts, (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan, and (h_fracs:
+// onsets between samples, with or without pans) dusp_render_host_score_parts_frac
+static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                   const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
+                                   int format, int normalise, void *h_out, float *h_peak, const double *h_fracs = nullptr) {
+    if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
+    dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
+    dusp_ctx *ctx = prog0->ctx;
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    const size_t n_ch = prog0->P.out_bufs.size(), n_out_ch = h_pans ? 2 : n_ch;  // (a voice's, the timeline's)
+    if (!h_part_of || !h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of or h_onsets is NULL");
+    if (n_voices < 1 || n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^24 voices");
+    size_t n_listed = 0;
+    for (size_t p = 0; p < n_parts; p++) {
+        if (!parts[p].prog) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the program of part " + std::to_string(p) + " is NULL");
+        if (parts[p].prog->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " was built on another context: all parts of a piece share one");
+        if (h_pans && parts[p].prog->P.out_bufs.size() != 1)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) +
+                                            " output channels: a panned voice is mono");
+        if (parts[p].prog->P.out_bufs.size() != n_ch)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) + " output channels, part 0 has " +
+                                            std::to_string(n_ch) + ": all parts of a piece have the same number");
+        for (size_t q = 0; q < p; q++)
+            if (parts[q].prog == parts[p].prog)
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": parts " + std::to_string(q) + " and " + std::to_string(p) + " are the same program: its tile buffer would be used twice; make them one part or build it twice");
+        n_listed += parts[p].n_instances;
+    }
+    if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
+    if (h_pans)
+        if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
+    if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
+    // voice k of the chain: the next unused instance of part h_part_of[k]
+    std::vector<size_t> instance_of(n_voices), used(n_parts, 0);
+    for (size_t k = 0; k < n_voices; k++) {
+        if (h_part_of[k] >= n_parts) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + " names part " + std::to_string(h_part_of[k]) + " of " + std::to_string(n_parts));
+        instance_of[k] = used[h_part_of[k]]++;
+    }
+    for (size_t p = 0; p < n_parts; p++)
+        if (used[p] != parts[p].n_instances || n_listed != n_voices)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of names part " + std::to_string(p) + " " + std::to_string(used[p]) + " times, the part has " +
+                                            std::to_string(parts[p].n_instances) + " instances: every instance is one voice of the chain");
+    for (size_t p = 0; p < n_parts; p++) {  // (the sizes the tiles are made from; tiled_batch_prepare below refuses the rest, in front of any render)
+        if (int rc = check_batch(ctx, who, parts[p].n_instances, parts[p].n_voice_samples)) return rc;
+        if (n_ch * parts[p].n_voice_samples > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x voice samples must not exceed 2^31");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the tiles: runs of the chain's voices whose rows together fit tile_bytes
+    std::vector<uint64_t> row_bytes(n_voices);
+    std::vector<uint32_t> row_samples(n_voices);
+    size_t staged = 0, free_bytes = 0, total_bytes = 0;
+    for (size_t k = 0; k < n_voices; k++) {
+        row_samples[k] = (uint32_t)parts[h_part_of[k]].n_voice_samples;  // (at most 2^31 / channels: tiled_batch_prepare)
+        row_bytes[k] = (uint64_t)n_ch * row_samples[k] * sizeof(float);
+    }
+    for (size_t p = 0; p < n_parts; p++) staged += parts[p].prog->d_host_out.cap * sizeof(float);
+    if (tile_bytes == 0 && ctx->knobs.mix_tile_mb <= 0) HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
+    const std::vector<size_t> starts = dusp::piece_tile_starts(row_bytes.data(), n_voices, tile_bytes, ctx->knobs.mix_tile_mb, free_bytes, staged, ctx->n_cus);
+    const size_t n_tiles = starts.size() - 1;
+    // a part's share of tile i: its instances [share[p][i], share[p][i + 1]), one contiguous range since its instances enter the chain in
+    // their own order; its tile buffer holds the largest share
+    std::vector<std::vector<size_t>> share(n_parts, std::vector<size_t>(n_tiles + 1, 0));
+    {
+        std::vector<size_t> seen(n_parts, 0);
+        for (size_t i = 0; i < n_tiles; i++) {
+            for (size_t k = starts[i]; k < starts[i + 1]; k++) seen[h_part_of[k]]++;
+            for (size_t p = 0; p < n_parts; p++) share[p][i + 1] = seen[p];
+        }
+    }
+    for (size_t p = 0; p < n_parts; p++) {
+        size_t most = 1, unused = 0;
+        for (size_t i = 0; i < n_tiles; i++) most = std::max(most, share[p][i + 1] - share[p][i]);
+        if (int rc = tiled_batch_prepare(parts[p].prog, who, parts[p].n_instances, parts[p].n_voice_samples, parts[p].h_params, nullptr, most, format, normalise, h_out, &unused)) return rc;
+    }
+    // every tile's plan, over the tile's union window, made up front under the call's one budget and uploaded once: the rows' addresses
+    // are known, since the tile buffers stand
+    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(h_pans ? ScoreKind::pan : ScoreKind::rows));
+    std::vector<std::vector<unsigned char>> renders(n_tiles, std::vector<unsigned char>(n_parts, 0));  // does part p render in tile i?
+    const size_t tile_budget = score_plan_budget(ctx) / n_tiles;
+    if (int rc = score_image_begin(ctx)) return rc;
+    const auto t_plan = std::chrono::steady_clock::now();
+    {
+        std::vector<uint64_t> rows;
+        std::vector<unsigned char> listed;
+        for (size_t i = 0; i < n_tiles; i++) {
+            const size_t lo = starts[i], n = starts[i + 1] - lo;
+            rows.resize(n);
+            for (size_t k = 0; k < n; k++) {
+                const size_t p = h_part_of[lo + k];
+                rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * n_ch * parts[p].n_voice_samples);
+            }
+            if (int rc = score_rows_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
+                                        /*whole_timeline=*/false, tile_budget, launches[i], &listed, h_fracs ? h_fracs + lo : nullptr))
+                return rc;
+            if (h_pans) score_pans_add(ctx, h_pans + lo, h_comp ? h_comp + lo : nullptr, n, launches[i]);
+            for (size_t k = 0; k < n; k++)
+                if (listed[k]) renders[i][h_part_of[lo + k]] = 1;
+        }
+    }
+    if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: what the plans cost the host)
+        fprintf(stderr, "[dusp host piece] %zu plans over %zu voices of %zu parts in %.0f us on the host: %zu bytes\n", n_tiles, n_voices, n_parts,
+                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count(), ctx->h_score_plan.size());
+    HIP_TRY(ctx, prog0->d_mix.ensure(n_out_ch * n_total_samples));  // the timeline's running sums
+    if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once)
+        HIP_TRY(ctx, prog0->d_mix_gains.ensure(n_voices));
+        HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (int rc = score_image_upload(ctx, ctx->stream)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix.p, 0, n_out_ch * n_total_samples * sizeof(float), ctx->stream));
+    std::vector<std::unique_ptr<TiledBatch>> whole;  // what changes bits is decided from the WHOLE part
+    for (size_t p = 0; p < n_parts; p++) whole.emplace_back(new TiledBatch(parts[p].prog, parts[p].n_instances, parts[p].h_params, share[p]));
+    auto waited = [&]() {
+        for (auto &b : whole) b->staged = false;
+    };
+    for (size_t i = 0; i < n_tiles; i++) {
+        if (launches[i].w_hi <= launches[i].w_lo) continue;  // (no voice of the tile reaches the timeline: nothing to render)
+        for (size_t p = 0; p < n_parts; p++)
+            if (renders[i][p])
+                if (int rc = whole[p]->render_tile(share[p][i], share[p][i + 1] - share[p][i], parts[p].n_voice_samples)) return rc;
+        const float *d_gains = h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr;
+        if (int rc = score_launch(ctx, launches[i], n_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream)) return rc;
+    }
+    // (`|| 0` is the rows kernel's over the timeline's channels, panned or not)
+    if (int rc = score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
+    waited();  // (the delivery has waited for the stream)
+    return DUSP_OK;
+    });
+}
+
+int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                 const int64_t *h_lengths, const float *h_gains, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out,
+                                 float *h_peak) {
+    return render_host_score_parts("dusp_render_host_score_parts", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, nullptr, nullptr, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak);
+}
+
+int dusp_render_host_score_parts_pan(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                     const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
+                                     int format, int normalise, void *h_out, float *h_peak) {
+    if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
+    if (!h_pans) CTX_FAIL(parts[0].prog->ctx, DUSP_ERR_ARG, "dusp_render_host_score_parts_pan: h_pans is NULL");
+    return render_host_score_parts("dusp_render_host_score_parts_pan", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak);
+}
+
+int dusp_score_rows_frac_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                                const double *h_fracs, const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples,
+                                const float *d_init, int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (h_pans && n_channels != 1) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_frac_device: a panned voice is mono: n_channels must be 1 with h_pans");
+    return score_rows_device(ctx, "dusp_score_rows_frac_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, h_pans, h_comp, n_total_samples, d_init,
+                             raw, d_out, stream_, h_fracs);
+}
+
+int dusp_render_host_score_parts_frac(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const double *h_fracs,
+                                      const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
+                                      int format, int normalise, void *h_out, float *h_peak) {
+    return render_host_score_parts("dusp_render_host_score_parts_frac", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak, h_fracs);
+}
+
+}  // extern "C"

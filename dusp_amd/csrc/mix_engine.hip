@@ -96,7 +96,7 @@ static hipError_t launch_mix_as(const float *d_planar, const float *d_gains, con
     return hipGetLastError();
 }
 
-// row_len = n_channels * n_samples.  The caller bounds it at 2^31 floats (abi_deliver.hip kMixRowMax): with one lane per float at the
+// row_len = n_channels * n_samples.  The caller bounds it at 2^31 floats (abi_internal.hpp kMixRowMax): with one lane per float at the
 // most, the grid stays below the 2^32 threads in x that a launch may have.
 // width_knob (Knobs::mix_width): 1 the dword form everywhere, 4 the float4 form wherever it is possible, else the choice below.
 // depth_knob (Knobs::mix_depth): 8 / 32 rows in flight in the dword form whatever the grid, else the choice below.

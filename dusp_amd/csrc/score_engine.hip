@@ -30,13 +30,11 @@
 
 #include <cstdint>
 
-#include "score_plan.hpp"
+#include "score_device.hpp"
 
 namespace dusp {
 
 constexpr int kScoreDepth = 8;  // entries a lane has in flight
-
-static __device__ __forceinline__ float score_or0(float a) { return (a != a || a == 0.0f) ? 0.0f : a; }
 
 // voice_row: floats from one voice's PCM to the next (n_channels * n_voice).  group0: the first group of kScoreGroup samples the grid
 // covers (w_lo >> kScoreGroupShift); groups: how many per channel.  block_first == nullptr: no voices at all (init -> out alone).
@@ -46,8 +44,8 @@ __global__ void __launch_bounds__(256) dusp_score_kernel(const float *__restrict
                                                           float *out, uint64_t voice_row, uint32_t n_voice, uint32_t n_total, uint32_t w_lo, uint32_t w_hi,
                                                           uint32_t group0, uint32_t groups, uint32_t group_to_block, uint32_t first_block, int raw) {
     const uint32_t c = blockIdx.x / groups, group = group0 + (blockIdx.x - c * groups);
-    const uint32_t t = (group << kScoreGroupShift) + threadIdx.x;  // (group <= 2^23, t < 2^31 + 256)
-    if (t < w_lo || t >= w_hi) return;
+    uint32_t t;
+    if (!score_lane_sample(group, w_lo, w_hi, t)) return;
     const uint64_t o = (uint64_t)c * n_total + t;
     float acc = init ? init[o] : 0.0f;
     uint32_t e = 0, e_end = 0;
@@ -91,15 +89,15 @@ __global__ void __launch_bounds__(256) dusp_score_kernel(const float *__restrict
 hipError_t launch_score(const float *d_planar, const float *d_gains, const ScoreVoice *d_voices, const uint32_t *d_block_first, const uint32_t *d_entries,
                         const float *d_init, float *d_out, uint32_t n_channels, uint64_t n_voice, uint64_t n_total, uint64_t w_lo, uint64_t w_hi,
                         uint32_t block_shift, uint64_t first_block, int raw, hipStream_t stream) {
-    const uint32_t group0 = (uint32_t)(w_lo >> kScoreGroupShift), groups = (uint32_t)((w_hi - 1) >> kScoreGroupShift) - group0 + 1;
-    const dim3 grid(groups * n_channels), block(kScoreGroup);
+    const ScoreGroups G = score_groups(w_lo, w_hi);
+    const dim3 grid(G.count * n_channels), block(kScoreGroup);
     const uint64_t voice_row = (uint64_t)n_channels * n_voice;
     if (d_gains && d_block_first)
         hipLaunchKernelGGL((dusp_score_kernel<kScoreDepth, true>), grid, block, 0, stream, d_planar, d_gains, d_voices, d_block_first, d_entries, d_init, d_out, voice_row,
-                           (uint32_t)n_voice, (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, group0, groups, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
+                           (uint32_t)n_voice, (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, G.first, G.count, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
     else
         hipLaunchKernelGGL((dusp_score_kernel<kScoreDepth, false>), grid, block, 0, stream, d_planar, d_gains, d_voices, d_block_first, d_entries, d_init, d_out, voice_row,
-                           (uint32_t)n_voice, (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, group0, groups, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
+                           (uint32_t)n_voice, (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, G.first, G.count, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
     return hipGetLastError();
 }
 

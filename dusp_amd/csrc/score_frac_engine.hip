@@ -37,55 +37,26 @@
 
 #include <cstdint>
 
-#include "score_plan.hpp"
+#include "score_device.hpp"
 
 namespace dusp {
 
 constexpr int kScoreFracDepth = 8;  // entries of a list whose indices are read at once
 constexpr int kScoreFracSub = 4;    // entries a lane has in flight: two vector loads each
 
-static __device__ __forceinline__ float score_frac_or0(float a) { return (a != a || a == 0.0f) ? 0.0f : a; }
-
-// a record, and a voice's pan coefficients, as ONE 32-byte load each; the weights as one 16-byte load
-typedef uint32_t ScoreFracWords8 __attribute__((vector_size(32), may_alias));
-typedef uint32_t ScoreFracWords4 __attribute__((vector_size(16), may_alias));
-template <class T>
-static __device__ __forceinline__ T score_frac_load32(const T *p) {
-    static_assert(sizeof(T) == 32, "eight dwords");
-    const ScoreFracWords8 w = *(const ScoreFracWords8 *)p;
-    T r;
-    __builtin_memcpy(&r, &w, sizeof r);
-    return r;
-}
-static __device__ __forceinline__ ScoreFrac score_frac_load16(const ScoreFrac *p) {
-    const ScoreFracWords4 w = *(const ScoreFracWords4 *)p;
-    ScoreFrac r;
-    __builtin_memcpy(&r, &w, sizeof r);
-    return r;
-}
 // a voice's pan coefficients without the record's unused last quarter: four dwords and two, six scalar registers an entry, not eight
 struct ScoreFracPan {
     double lm, rp, ch;
 };
 typedef uint32_t ScoreFracWords2 __attribute__((vector_size(8), may_alias));
 static __device__ __forceinline__ ScoreFracPan score_frac_load_pan(const ScorePan *p) {
-    const ScoreFracWords4 a = *(const ScoreFracWords4 *)p;
+    const ScoreWords4 a = *(const ScoreWords4 *)p;
     const ScoreFracWords2 b = *(const ScoreFracWords2 *)&p->ch;
     ScoreFracPan r;
     __builtin_memcpy(&r.lm, &a, sizeof a);
     __builtin_memcpy(&r.ch, &b, sizeof b);
     return r;
 }
-
-// a batch's eight indices as one load too: contiguous in entries[], on a 4-byte boundary only
-typedef uint32_t ScoreFracEntryWords __attribute__((vector_size(32), aligned(4), may_alias));
-
-// a row's address is a number in the record: on the device it names GLOBAL memory (a global load, not a flat one)
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const __attribute__((address_space(1))) float *ScoreFracFloats;
-#else
-typedef const float *ScoreFracFloats;
-#endif
 
 // the two taps of one timeline sample: x0 = x[s] (used where s < len), x1 = x[s - 1] (used where s >= 1)
 static __device__ __forceinline__ float score_frac_term(float x0, float x1, bool has0, bool has1, const ScoreFrac &w) {
@@ -104,8 +75,8 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
                                                                const uint32_t *__restrict__ entries, const float *init, float *out, uint32_t n_total, uint32_t w_lo,
                                                                uint32_t w_hi, uint32_t group0, uint32_t groups, uint32_t group_to_block, uint32_t first_block, int raw) {
     const uint32_t c = PAN ? 0u : blockIdx.x / groups, group = group0 + (blockIdx.x - c * groups);
-    const uint32_t t = (group << kScoreGroupShift) + threadIdx.x;  // (group <= 2^23, t < 2^31 + 256)
-    if (t < w_lo || t >= w_hi) return;
+    uint32_t t;
+    if (!score_lane_sample(group, w_lo, w_hi, t)) return;
     const uint64_t o0 = (uint64_t)c * n_total + t, o1 = (uint64_t)n_total + t;  // (PAN: left and right)
     float acc0 = init ? init[o0] : 0.0f, acc1 = (PAN && init) ? init[o1] : 0.0f;
     const uint32_t b = (group >> group_to_block) - first_block;
@@ -115,7 +86,7 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
         uint32_t idx[DEPTH];
 #pragma unroll
         for (int k = 0; k < DEPTH; k += 8) {  // (past the list's end: another list's entry, or the padding's voice 0; nobody's either way)
-            const ScoreFracEntryWords w = *(const ScoreFracEntryWords *)(entries + e + k);
+            const ScoreEntryWords w = *(const ScoreEntryWords *)(entries + e + k);
 #pragma unroll
             for (int j = 0; j < 8; j++) idx[k + j] = w[j];
         }
@@ -132,7 +103,7 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
             // the scalar loads the addresses need first, side by side — the records (and gains) — so that one wait covers them
 #pragma unroll
             for (int k = 0; k < SUB; k++) {
-                V[k] = score_frac_load32(voices + idx[h + k]);
+                V[k] = score_load32(voices + idx[h + k]);
                 g[k] = GAINS ? gains[idx[h + k]] : 1.0f;
             }
 #pragma unroll
@@ -146,14 +117,14 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
                 // dropped: no branch around the loads, and the sub-batch's are issued back to back
                 // (has0: c * stride + s < channels * row_samples <= 2^31 floats)
                 const uint64_t at = (uint64_t)c * V[k].stride + (uint64_t)s;
-                v0[k] = ((ScoreFracFloats)V[k].row)[has0[k] ? at : (uint64_t)0];
-                v1[k] = ((ScoreFracFloats)V[k].row)[has1[k] ? at - 1 : (uint64_t)0];
+                v0[k] = ((ScoreRowFloats)V[k].row)[has0[k] ? at : (uint64_t)0];
+                v1[k] = ((ScoreRowFloats)V[k].row)[has1[k] ? at - 1 : (uint64_t)0];
             }
             // what only the arithmetic needs is fetched behind the vector loads, while they are in flight: by now a record's address,
             // onset and bounds are used up, and their scalar registers are free
 #pragma unroll
             for (int k = 0; k < SUB; k++) {
-                W[k] = score_frac_load16(fracs + idx[h + k]);
+                W[k] = score_load16(fracs + idx[h + k]);
                 if (PAN) P[k] = score_frac_load_pan(pans + idx[h + k]);
             }
 #pragma unroll
@@ -179,22 +150,22 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
                 }
         }
     }
-    out[o0] = raw ? acc0 : score_frac_or0(acc0);
-    if (PAN) out[o1] = raw ? acc1 : score_frac_or0(acc1);
+    out[o0] = raw ? acc0 : score_or0(acc0);
+    if (PAN) out[o1] = raw ? acc1 : score_or0(acc1);
 }
 
 // One launch over the window [w_lo, w_hi) of the timeline, 0 <= w_lo < w_hi <= n_total, for a plan at least one of whose voices has a
 // fraction.  d_pans nullptr: rows of n_channels into a timeline of n_channels, n_channels * n_total <= 2^31.  With d_pans: mono rows
 // (n_channels == 1) into a timeline of two, n_total <= 2^30.  d_voices / d_block_first / d_entries: the plan's image on the device
-// (score_rows_plan_pack), made for this window, d_fracs (and d_pans) the weights (and coefficients) of the same voices; none is nullptr.
+// (score_plan_pack), made for this window, d_fracs (and d_pans) the weights (and coefficients) of the same voices; none is nullptr.
 hipError_t launch_score_frac(const float *d_gains, const ScorePan *d_pans, const ScoreFrac *d_fracs, const ScoreRow *d_voices, const uint32_t *d_block_first,
                              const uint32_t *d_entries, const float *d_init, float *d_out, uint32_t n_channels, uint64_t n_total, uint64_t w_lo, uint64_t w_hi,
                              uint32_t block_shift, uint64_t first_block, int raw, hipStream_t stream) {
-    const uint32_t group0 = (uint32_t)(w_lo >> kScoreGroupShift), groups = (uint32_t)((w_hi - 1) >> kScoreGroupShift) - group0 + 1;
-    const dim3 grid(d_pans ? groups : groups * n_channels), block(kScoreGroup);
+    const ScoreGroups G = score_groups(w_lo, w_hi);
+    const dim3 grid(d_pans ? G.count : G.count * n_channels), block(kScoreGroup);
 #define DUSP_SCORE_FRAC_LAUNCH(GAINS, PAN)                                                                                                                              \
     hipLaunchKernelGGL((dusp_score_frac_kernel<kScoreFracDepth, kScoreFracSub, GAINS, PAN>), grid, block, 0, stream, d_gains, d_pans, d_fracs, d_voices, d_block_first, d_entries, d_init, \
-                       d_out, (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, group0, groups, block_shift - kScoreGroupShift, (uint32_t)first_block, raw)
+                       d_out, (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, G.first, G.count, block_shift - kScoreGroupShift, (uint32_t)first_block, raw)
     if (d_pans) {
         if (d_gains) DUSP_SCORE_FRAC_LAUNCH(true, true);
         else DUSP_SCORE_FRAC_LAUNCH(false, true);

@@ -26,34 +26,11 @@
 
 #include <cstdint>
 
-#include "score_plan.hpp"
+#include "score_device.hpp"
 
 namespace dusp {
 
 constexpr int kScorePanDepth = 8;  // entries a lane has in flight
-
-static __device__ __forceinline__ float score_pan_or0(float a) { return (a != a || a == 0.0f) ? 0.0f : a; }
-
-// a record, and a voice's coefficients, as ONE 32-byte load each (field by field the compiler splits them)
-typedef uint32_t ScorePanWords __attribute__((vector_size(32), may_alias));
-template <class T>
-static __device__ __forceinline__ T score_pan_load32(const T *p) {
-    static_assert(sizeof(T) == 32, "eight dwords");
-    const ScorePanWords w = *(const ScorePanWords *)p;
-    T r;
-    __builtin_memcpy(&r, &w, sizeof r);
-    return r;
-}
-
-// a batch's eight indices as one load too: contiguous in entries[], on a 4-byte boundary only
-typedef uint32_t ScorePanEntryWords __attribute__((vector_size(32), aligned(4), may_alias));
-
-// a row's address is a number in the record: on the device it names GLOBAL memory (a global load, not a flat one)
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const __attribute__((address_space(1))) float *ScorePanFloats;
-#else
-typedef const float *ScorePanFloats;
-#endif
 
 // group0: the first group of kScoreGroup samples the grid covers (w_lo >> kScoreGroupShift).  init, out: [2][n_total].
 // block_first == nullptr: no voices at all (init -> out alone).
@@ -63,8 +40,8 @@ __global__ void __launch_bounds__(256) dusp_score_pan_kernel(const float *__rest
                                                               uint32_t n_total, uint32_t w_lo, uint32_t w_hi, uint32_t group0, uint32_t group_to_block, uint32_t first_block,
                                                               int raw) {
     const uint32_t group = group0 + blockIdx.x;
-    const uint32_t t = (group << kScoreGroupShift) + threadIdx.x;  // (group <= 2^22, t < 2^30 + 256)
-    if (t < w_lo || t >= w_hi) return;
+    uint32_t t;
+    if (!score_lane_sample(group, w_lo, w_hi, t)) return;  // (here group <= 2^22 and t < 2^30 + 256)
     const uint64_t oL = t, oR = (uint64_t)n_total + t;
     float accL = init ? init[oL] : 0.0f, accR = init ? init[oR] : 0.0f;
     uint32_t e = 0, e_end = 0;
@@ -82,14 +59,14 @@ __global__ void __launch_bounds__(256) dusp_score_pan_kernel(const float *__rest
         // the batch's scalar loads first, side by side — the indices, then the records, coefficients (and gains) — so that one wait covers each stage
 #pragma unroll
         for (int k = 0; k < DEPTH; k += 8) {  // (past the list's end: another list's entry, or the padding's voice 0; nobody's either way)
-            const ScorePanEntryWords w = *(const ScorePanEntryWords *)(entries + e + k);
+            const ScoreEntryWords w = *(const ScoreEntryWords *)(entries + e + k);
 #pragma unroll
             for (int j = 0; j < 8; j++) idx[k + j] = w[j];
         }
 #pragma unroll
         for (int k = 0; k < DEPTH; k++) {
-            V[k] = score_pan_load32(voices + idx[k]);
-            P[k] = score_pan_load32(pans + idx[k]);
+            V[k] = score_load32(voices + idx[k]);
+            P[k] = score_load32(pans + idx[k]);
             g[k] = GAINS ? gains[idx[k]] : 1.0f;
         }
 #pragma unroll
@@ -98,7 +75,7 @@ __global__ void __launch_bounds__(256) dusp_score_pan_kernel(const float *__rest
             // a lane the entry does not cover reads the entry's own row[0] instead (readable for every record: ScoreRow) and drops it
             // (in: s < row_samples <= 2^31 floats)
             const uint64_t at = (uint64_t)((int64_t)t - V[k].onset);
-            v[k] = ((ScorePanFloats)V[k].row)[in[k] ? at : (uint64_t)0];
+            v[k] = ((ScoreRowFloats)V[k].row)[in[k] ? at : (uint64_t)0];
         }
 #pragma unroll
         for (int k = 0; k < DEPTH; k++)
@@ -109,24 +86,24 @@ __global__ void __launch_bounds__(256) dusp_score_pan_kernel(const float *__rest
                 accR = accR + right;
             }
     }
-    out[oL] = raw ? accL : score_pan_or0(accL);
-    out[oR] = raw ? accR : score_pan_or0(accR);
+    out[oL] = raw ? accL : score_or0(accL);
+    out[oR] = raw ? accR : score_or0(accR);
 }
 
 // One launch over the window [w_lo, w_hi) of both channels of the timeline, 0 <= w_lo < w_hi <= n_total <= 2^30.  d_voices /
-// d_block_first / d_entries: the plan's image on the device (score_rows_plan_pack), made for this window over MONO rows, and d_pans the
+// d_block_first / d_entries: the plan's image on the device (score_plan_pack), made for this window over MONO rows, and d_pans the
 // coefficients of the same voices — or all nullptr for a launch without voices.
 hipError_t launch_score_pan(const float *d_gains, const ScorePan *d_pans, const ScoreRow *d_voices, const uint32_t *d_block_first, const uint32_t *d_entries,
                             const float *d_init, float *d_out, uint64_t n_total, uint64_t w_lo, uint64_t w_hi, uint32_t block_shift, uint64_t first_block, int raw,
                             hipStream_t stream) {
-    const uint32_t group0 = (uint32_t)(w_lo >> kScoreGroupShift), groups = (uint32_t)((w_hi - 1) >> kScoreGroupShift) - group0 + 1;
-    const dim3 grid(groups), block(kScoreGroup);
+    const ScoreGroups G = score_groups(w_lo, w_hi);
+    const dim3 grid(G.count), block(kScoreGroup);
     if (d_gains && d_block_first)
         hipLaunchKernelGGL((dusp_score_pan_kernel<kScorePanDepth, true>), grid, block, 0, stream, d_gains, d_pans, d_voices, d_block_first, d_entries, d_init, d_out,
-                           (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, group0, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
+                           (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, G.first, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
     else
         hipLaunchKernelGGL((dusp_score_pan_kernel<kScorePanDepth, false>), grid, block, 0, stream, d_gains, d_pans, d_voices, d_block_first, d_entries, d_init, d_out,
-                           (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, group0, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
+                           (uint32_t)n_total, (uint32_t)w_lo, (uint32_t)w_hi, G.first, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
     return hipGetLastError();
 }
 

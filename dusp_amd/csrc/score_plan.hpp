@@ -1,4 +1,4 @@
-// score_plan.hpp — the plan of a score launch (score_engine.hip): which voices of a tile a block of the timeline has to look at.  Plain data
+// score_plan.hpp — the plan of a score launch (score_engine.hip and its kin): which voices of a tile a block of the timeline has to look at.  Plain data
 // in, plain data out: host code only (no HIP), checked against brute force on the CPU (tests/native/score_plan_check.cpp).
 //
 // A score places voice k — a row of n_voice samples per channel, of which the first len_k count — at sample onset_k of a timeline of
@@ -30,22 +30,42 @@ struct alignas(16) ScoreVoice {
     int64_t onset;
     uint32_t lo, hi;
 };
+
+// A voice as the rows kernel reads it: timeline samples [lo, hi) take ((const float *)row)[c * stride + (t - onset)].
+// (32 bytes on a 32-byte boundary: one eight-dword scalar load a voice)
+// A record that is in no list (lo == hi == 0) still carries a READABLE row: the first listed voice's.  The kernel points the load of a
+// lane that an entry does not cover at the entry's own row[0], and the entries it may meet are (a) its list's, (b) another list's — both
+// name voices with lo < hi, whose rows hold at least one float — and (c) the padding's zeros, which name voice 0 whether or not voice 0
+// is anywhere on the timeline (its own row may be NULL or empty).
+struct alignas(32) ScoreRow {
+    int64_t onset;
+    uint32_t lo, hi;
+    uint64_t row;     // device address of the voice's channel 0, sample 0
+    uint32_t stride;  // floats from one channel of this voice to the next
+    uint32_t pad;     // 0; a voice with a fraction of a sample in its onset (score_rows_plan's fracs): its unclipped length, never 0
+};
+static_assert(sizeof(ScoreRow) == 32, "one eight-dword scalar load");
+
 // entries[] ends in this many zeros behind the last list: the kernel reads a batch of 8 indices with one wide scalar load, also where
 // fewer than 8 of them are left in the list, and masks the rest
 constexpr size_t kScoreEntryPad = 8;
 
-struct ScorePlan {
+// The plan of one launch over records of either kind
+template <class Record>
+struct ScorePlanT {
     int64_t t_lo = 0, t_hi = 0;   // the union of the voices' clipped spans (t_lo == t_hi: no voice reaches the timeline)
     int64_t w_lo = 0, w_hi = 0;   // the window of the timeline the plan covers: the union, or the whole timeline
     uint32_t block_shift = kScoreGroupShift;  // B = 1 << block_shift
     uint64_t first_block = 0;     // block_first[0] is block first_block of the timeline (w_lo >> block_shift)
-    std::vector<ScoreVoice> voices;      // [n]; lo == hi == 0 for a voice that appears nowhere
+    std::vector<Record> voices;          // [n]; lo == hi == 0 for a voice that appears nowhere
     std::vector<uint32_t> block_first;   // [n_blocks + 1]
     std::vector<uint32_t> entries;       // voice indices, ascending within a block; then kScoreEntryPad zeros (block_first.back() is where they begin)
     size_t n_entries() const { return block_first.empty() ? 0 : block_first.back(); }
     size_t n_blocks() const { return block_first.empty() ? 0 : block_first.size() - 1; }
-    size_t bytes() const { return voices.size() * sizeof(ScoreVoice) + (block_first.size() + entries.size()) * sizeof(uint32_t); }
+    size_t bytes() const { return voices.size() * sizeof(Record) + (block_first.size() + entries.size()) * sizeof(uint32_t); }
 };
+using ScorePlan = ScorePlanT<ScoreVoice>;    // score_engine.hip: the voices of one contiguous batch
+using ScoreRowsPlan = ScorePlanT<ScoreRow>;  // score_rows_engine.hip and what stands on it: every voice a buffer of its own
 
 // The lists of a plan whose records (ScoreVoice, ScoreRow: anything with lo and hi) are made: the block, doubled from kScoreGroup until
 // records + block_first + entries (+ kScoreEntryPad) fit budget_bytes or one block covers the window [w_lo, w_hi), w_lo < w_hi; then the
@@ -84,6 +104,37 @@ inline void score_plan_lists(const std::vector<Record> &voices, int64_t w_lo, in
     }
 }
 
+// What a planner ends with, its records clipped and [t_lo, t_hi) the union of their spans (t_hi <= t_lo: no voice reaches the timeline of
+// `total` samples): the window — the whole timeline or the union — and, unless it is empty (nothing to launch), the lists.
+template <class Record>
+inline void score_plan_finish(ScorePlanT<Record> &P, int64_t t_lo, int64_t t_hi, int64_t total, bool whole_timeline, size_t budget_bytes) {
+    if (t_hi <= t_lo) t_lo = t_hi = 0;
+    P.t_lo = t_lo;
+    P.t_hi = t_hi;
+    P.w_lo = whole_timeline ? 0 : t_lo;
+    P.w_hi = whole_timeline ? total : t_hi;
+    if (P.w_hi > P.w_lo) score_plan_lists(P.voices, P.w_lo, P.w_hi, budget_bytes, P.block_shift, P.first_block, P.block_first, P.entries);
+}
+
+// The plan as the device reads it, appended to `image` on a boundary of the record's own alignment — 16 bytes for ScoreVoice, 32 for
+// ScoreRow (the image itself starts on one on the device): voices, block_first, entries.  Returns the byte offset of the voices;
+// block_first follows at + n * sizeof(Record), the entries (and their padding) behind it.
+template <class Record>
+inline size_t score_plan_pack(const ScorePlanT<Record> &P, std::vector<unsigned char> &image) {
+    const size_t at = (image.size() + alignof(Record) - 1) & ~(alignof(Record) - 1);
+    image.resize(at + P.bytes());
+    unsigned char *p = image.data() + at;
+    auto put = [&](const void *src, size_t n_bytes) {
+        if (n_bytes) std::copy((const unsigned char *)src, (const unsigned char *)src + n_bytes, p);
+        p += n_bytes;
+    };
+    put(P.voices.data(), P.voices.size() * sizeof(Record));
+    put(P.block_first.data(), P.block_first.size() * sizeof(uint32_t));
+    put(P.entries.data(), P.entries.size() * sizeof(uint32_t));
+    return at;
+}
+inline size_t score_rows_plan_pack(const ScoreRowsPlan &P, std::vector<unsigned char> &image) { return score_plan_pack(P, image); }  // (the name the rows' callers know)
+
 // lengths: nullptr for n_voice everywhere.  whole_timeline: the plan covers [0, n_total) (a launch that writes every sample), else the
 // union window only (a raw launch in place: samples no voice of the tile reaches stay as they are).
 // Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, n_voice].
@@ -104,60 +155,11 @@ inline int64_t score_plan(const int64_t *onsets, const int64_t *lengths, size_t 
         t_lo = std::min(t_lo, lo);
         t_hi = std::max(t_hi, hi);
     }
-    if (t_hi <= t_lo) t_lo = t_hi = 0;
-    P.t_lo = t_lo;
-    P.t_hi = t_hi;
-    P.w_lo = whole_timeline ? 0 : t_lo;
-    P.w_hi = whole_timeline ? total : t_hi;
-    if (P.w_hi <= P.w_lo) return -1;  // nothing to launch
-    score_plan_lists(P.voices, P.w_lo, P.w_hi, budget_bytes, P.block_shift, P.first_block, P.block_first, P.entries);
+    score_plan_finish(P, t_lo, t_hi, total, whole_timeline, budget_bytes);
     return -1;
 }
 
-// The plan as the device reads it, appended to `image` on a 16-byte boundary: voices, block_first, entries.  Returns the byte offset of
-// the voices; block_first follows at + n * sizeof(ScoreVoice), the entries (and their padding) behind it.
-inline size_t score_plan_pack(const ScorePlan &P, std::vector<unsigned char> &image) {
-    const size_t at = (image.size() + 15) & ~(size_t)15;
-    image.resize(at + P.bytes());
-    unsigned char *p = image.data() + at;
-    auto put = [&](const void *src, size_t n_bytes) {
-        if (n_bytes) std::copy((const unsigned char *)src, (const unsigned char *)src + n_bytes, p);
-        p += n_bytes;
-    };
-    put(P.voices.data(), P.voices.size() * sizeof(ScoreVoice));
-    put(P.block_first.data(), P.block_first.size() * sizeof(uint32_t));
-    put(P.entries.data(), P.entries.size() * sizeof(uint32_t));
-    return at;
-}
-
 // ---- rows: every voice a buffer of its own (score_rows_engine.hip; dusp_amd/mix.py score_chain_rows is the contract) ----
-
-// A voice as the rows kernel reads it: timeline samples [lo, hi) take ((const float *)row)[c * stride + (t - onset)].
-// (32 bytes on a 32-byte boundary: one eight-dword scalar load a voice)
-// A record that is in no list (lo == hi == 0) still carries a READABLE row: the first listed voice's.  The kernel points the load of a
-// lane that an entry does not cover at the entry's own row[0], and the entries it may meet are (a) its list's, (b) another list's — both
-// name voices with lo < hi, whose rows hold at least one float — and (c) the padding's zeros, which name voice 0 whether or not voice 0
-// is anywhere on the timeline (its own row may be NULL or empty).
-struct alignas(32) ScoreRow {
-    int64_t onset;
-    uint32_t lo, hi;
-    uint64_t row;     // device address of the voice's channel 0, sample 0
-    uint32_t stride;  // floats from one channel of this voice to the next
-    uint32_t pad;     // 0; a voice with a fraction of a sample in its onset (score_rows_plan's fracs): its unclipped length, never 0
-};
-static_assert(sizeof(ScoreRow) == 32, "one eight-dword scalar load");
-
-struct ScoreRowsPlan {
-    int64_t t_lo = 0, t_hi = 0, w_lo = 0, w_hi = 0;  // as ScorePlan's
-    uint32_t block_shift = kScoreGroupShift;
-    uint64_t first_block = 0;
-    std::vector<ScoreRow> voices;        // [n]
-    std::vector<uint32_t> block_first;   // [n_blocks + 1]
-    std::vector<uint32_t> entries;       // as ScorePlan's, kScoreEntryPad zeros behind the last list
-    size_t n_entries() const { return block_first.empty() ? 0 : block_first.back(); }
-    size_t n_blocks() const { return block_first.empty() ? 0 : block_first.size() - 1; }
-    size_t bytes() const { return voices.size() * sizeof(ScoreRow) + (block_first.size() + entries.size()) * sizeof(uint32_t); }
-};
 
 // score_plan over voices of their own row lengths: row_samples[k] samples a channel (which is also the voice's channel stride) at device
 // address rows[k] (nullptr: all 0, for a plan that is only looked at).  lengths: nullptr for row_samples[k] everywhere.
@@ -194,30 +196,8 @@ inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, co
     if (first_listed < n)  // (the records nobody adds from: readable all the same, see ScoreRow)
         for (ScoreRow &v : P.voices)
             if (v.hi == v.lo) v.row = P.voices[first_listed].row;
-    if (t_hi <= t_lo) t_lo = t_hi = 0;
-    P.t_lo = t_lo;
-    P.t_hi = t_hi;
-    P.w_lo = whole_timeline ? 0 : t_lo;
-    P.w_hi = whole_timeline ? total : t_hi;
-    if (P.w_hi <= P.w_lo) return -1;  // nothing to launch
-    score_plan_lists(P.voices, P.w_lo, P.w_hi, budget_bytes, P.block_shift, P.first_block, P.block_first, P.entries);
+    score_plan_finish(P, t_lo, t_hi, total, whole_timeline, budget_bytes);
     return -1;
-}
-
-// The rows plan as the device reads it, appended to `image` on a 32-byte boundary (the image itself starts on one on the device): voices,
-// block_first, entries.  Returns the byte offset of the voices.
-inline size_t score_rows_plan_pack(const ScoreRowsPlan &P, std::vector<unsigned char> &image) {
-    const size_t at = (image.size() + 31) & ~(size_t)31;
-    image.resize(at + P.bytes());
-    unsigned char *p = image.data() + at;
-    auto put = [&](const void *src, size_t n_bytes) {
-        if (n_bytes) std::copy((const unsigned char *)src, (const unsigned char *)src + n_bytes, p);
-        p += n_bytes;
-    };
-    put(P.voices.data(), P.voices.size() * sizeof(ScoreRow));
-    put(P.block_first.data(), P.block_first.size() * sizeof(uint32_t));
-    put(P.entries.data(), P.entries.size() * sizeof(uint32_t));
-    return at;
 }
 
 // ---- pans: a place in the stereo field per voice of a rows plan (score_pan_engine.hip; dusp_amd/mix.py score_chain_rows_panned) ----

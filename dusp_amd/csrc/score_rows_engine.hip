@@ -24,32 +24,11 @@
 
 #include <cstdint>
 
-#include "score_plan.hpp"
+#include "score_device.hpp"
 
 namespace dusp {
 
 constexpr int kScoreRowsDepth = 8;  // entries a lane has in flight
-
-static __device__ __forceinline__ float score_rows_or0(float a) { return (a != a || a == 0.0f) ? 0.0f : a; }
-
-// a record as ONE 32-byte load (its eight words as a vector: field by field the compiler splits it into four, two and one dwords)
-typedef uint32_t ScoreRowWords __attribute__((vector_size(32), may_alias));
-static __device__ __forceinline__ ScoreRow score_row_load(const ScoreRow *p) {
-    const ScoreRowWords w = *(const ScoreRowWords *)p;
-    ScoreRow r;
-    __builtin_memcpy(&r, &w, sizeof r);
-    return r;
-}
-
-// a batch's eight indices as one load too: contiguous in entries[], on a 4-byte boundary only
-typedef uint32_t ScoreEntryWords __attribute__((vector_size(32), aligned(4), may_alias));
-
-// a row's address is a number in the record: on the device it names GLOBAL memory (a global load, not a flat one)
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const __attribute__((address_space(1))) float *ScoreRowFloats;
-#else
-typedef const float *ScoreRowFloats;
-#endif
 
 // group0: the first group of kScoreGroup samples the grid covers (w_lo >> kScoreGroupShift); groups: how many per channel.
 // block_first == nullptr: no voices at all (init -> out alone).
@@ -58,8 +37,8 @@ __global__ void __launch_bounds__(256) dusp_score_rows_kernel(const float *__res
                                                                const uint32_t *__restrict__ entries, const float *init, float *out, uint32_t n_total, uint32_t w_lo,
                                                                uint32_t w_hi, uint32_t group0, uint32_t groups, uint32_t group_to_block, uint32_t first_block, int raw) {
     const uint32_t c = blockIdx.x / groups, group = group0 + (blockIdx.x - c * groups);
-    const uint32_t t = (group << kScoreGroupShift) + threadIdx.x;  // (group <= 2^23, t < 2^31 + 256)
-    if (t < w_lo || t >= w_hi) return;
+    uint32_t t;
+    if (!score_lane_sample(group, w_lo, w_hi, t)) return;
     const uint64_t o = (uint64_t)c * n_total + t;
     float acc = init ? init[o] : 0.0f;
     uint32_t e = 0, e_end = 0;
@@ -82,7 +61,7 @@ __global__ void __launch_bounds__(256) dusp_score_rows_kernel(const float *__res
         }
 #pragma unroll
         for (int k = 0; k < DEPTH; k++) {
-            V[k] = score_row_load(voices + idx[k]);
+            V[k] = score_load32(voices + idx[k]);
             g[k] = GAINS ? gains[idx[k]] : 1.0f;
         }
 #pragma unroll
@@ -98,23 +77,23 @@ __global__ void __launch_bounds__(256) dusp_score_rows_kernel(const float *__res
         for (int k = 0; k < DEPTH; k++)
             if (in[k]) acc = acc + (GAINS ? v[k] * g[k] : v[k]);
     }
-    out[o] = raw ? acc : score_rows_or0(acc);
+    out[o] = raw ? acc : score_or0(acc);
 }
 
 // One launch over the window [w_lo, w_hi) of every channel of the timeline, 0 <= w_lo < w_hi <= n_total <= 2^31 and
-// n_channels * n_total <= 2^31.  d_voices / d_block_first / d_entries: the plan's image on the device (score_rows_plan_pack), made for
+// n_channels * n_total <= 2^31.  d_voices / d_block_first / d_entries: the plan's image on the device (score_plan_pack), made for
 // this window — or all nullptr for a launch without voices.
 hipError_t launch_score_rows(const float *d_gains, const ScoreRow *d_voices, const uint32_t *d_block_first, const uint32_t *d_entries, const float *d_init, float *d_out,
                              uint32_t n_channels, uint64_t n_total, uint64_t w_lo, uint64_t w_hi, uint32_t block_shift, uint64_t first_block, int raw,
                              hipStream_t stream) {
-    const uint32_t group0 = (uint32_t)(w_lo >> kScoreGroupShift), groups = (uint32_t)((w_hi - 1) >> kScoreGroupShift) - group0 + 1;
-    const dim3 grid(groups * n_channels), block(kScoreGroup);
+    const ScoreGroups G = score_groups(w_lo, w_hi);
+    const dim3 grid(G.count * n_channels), block(kScoreGroup);
     if (d_gains && d_block_first)
         hipLaunchKernelGGL((dusp_score_rows_kernel<kScoreRowsDepth, true>), grid, block, 0, stream, d_gains, d_voices, d_block_first, d_entries, d_init, d_out, (uint32_t)n_total,
-                           (uint32_t)w_lo, (uint32_t)w_hi, group0, groups, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
+                           (uint32_t)w_lo, (uint32_t)w_hi, G.first, G.count, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
     else
         hipLaunchKernelGGL((dusp_score_rows_kernel<kScoreRowsDepth, false>), grid, block, 0, stream, d_gains, d_voices, d_block_first, d_entries, d_init, d_out, (uint32_t)n_total,
-                           (uint32_t)w_lo, (uint32_t)w_hi, group0, groups, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
+                           (uint32_t)w_lo, (uint32_t)w_hi, G.first, G.count, block_shift - kScoreGroupShift, (uint32_t)first_block, raw);
     return hipGetLastError();
 }
 

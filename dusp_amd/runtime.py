@@ -209,6 +209,20 @@ def _whole_samples(values, n, name):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _score_rows(rows, row_samples, onsets, lengths):
+    """what the score_rows_* entries take alike -> (pointers uint64 [n], samples uint32 [n], onsets int64 [n], lengths int64 [n] or None)"""
+    n = len(rows)
+    samples = np.asarray(row_samples) if n else np.zeros(0, dtype=np.uint32)
+    if samples.shape != (n,) or samples.dtype.kind not in "iu" or np.any(samples < 0) or np.any(samples > 0xffffffff):
+        raise ValueError("dusp-hip: row_samples must be whole numbers 0 .. 2^32 - 1 of shape (voices=%d,)" % n)
+    samples = np.ascontiguousarray(samples, dtype=np.uint32)
+    pointers = np.array([int(r or 0) for r in rows], dtype=np.uint64)
+    onsets = _whole_samples(onsets, n, "onsets")
+    if lengths is not None:
+        lengths = _whole_samples(lengths, n, "lengths")
+    return pointers, samples, onsets, lengths
+
+
 class Context:
     """One HIP device + stream + the uploaded wave tables."""
 
@@ -321,16 +335,8 @@ class Context:
         [n_channels][row_samples[k]].  onsets and lengths are HOST arrays of whole numbers of samples, lengths in 0 .. row_samples[k].
         Everything else as score_device; score_last_ms() reports the call."""
         n = len(rows)
-        samples = np.asarray(row_samples) if n else np.zeros(0, dtype=np.uint32)
-        if samples.shape != (n,) or samples.dtype.kind not in "iu" or np.any(samples < 0) or np.any(samples > 0xffffffff):
-            raise ValueError("dusp-hip: row_samples must be whole numbers 0 .. 2^32 - 1 of shape (voices=%d,)" % n)
-        samples = np.ascontiguousarray(samples, dtype=np.uint32)
-        pointers = np.array([int(r or 0) for r in rows], dtype=np.uint64)
-        onsets = _whole_samples(onsets, n, "onsets")
-        lp = None
-        if lengths is not None:
-            lengths = _whole_samples(lengths, n, "lengths")
-            lp = lengths.ctypes.data
+        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
+        lp = lengths.ctypes.data if lengths is not None else None
         self._check(self._L.dusp_score_rows_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, n_channels,
                                                    onsets.ctypes.data if n else None, lp, d_gains, n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
@@ -340,17 +346,9 @@ class Context:
         k f32 [row_samples[k]]; pans a HOST array of finite f32, not clamped; comp the f64 compensation per voice (None: math.pow's, the
         reference's formula); d_init (which may be d_out) and d_out f32 [2][n_total_samples].  score_last_ms() reports the call."""
         n = len(rows)
-        samples = np.asarray(row_samples) if n else np.zeros(0, dtype=np.uint32)
-        if samples.shape != (n,) or samples.dtype.kind not in "iu" or np.any(samples < 0) or np.any(samples > 0xffffffff):
-            raise ValueError("dusp-hip: row_samples must be whole numbers 0 .. 2^32 - 1 of shape (voices=%d,)" % n)
-        samples = np.ascontiguousarray(samples, dtype=np.uint32)
-        pointers = np.array([int(r or 0) for r in rows], dtype=np.uint64)
-        onsets = _whole_samples(onsets, n, "onsets")
+        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
         pans, comp = pan_arrays(pans, n, comp)
-        lp = None
-        if lengths is not None:
-            lengths = _whole_samples(lengths, n, "lengths")
-            lp = lengths.ctypes.data
+        lp = lengths.ctypes.data if lengths is not None else None
         self._check(self._L.dusp_score_rows_pan_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, onsets.ctypes.data if n else None,
                                                        lp, d_gains, pans.ctypes.data if n else None, comp.ctypes.data if n else None, n_total_samples, d_init, int(bool(raw)),
                                                        d_out, stream))
@@ -363,12 +361,7 @@ class Context:
         reference Delay's two taps and covers one more sample; one without is the voice of those calls, and a call without any fraction
         launches their kernels.  score_last_ms() reports the call."""
         n = len(rows)
-        samples = np.asarray(row_samples) if n else np.zeros(0, dtype=np.uint32)
-        if samples.shape != (n,) or samples.dtype.kind not in "iu" or np.any(samples < 0) or np.any(samples > 0xffffffff):
-            raise ValueError("dusp-hip: row_samples must be whole numbers 0 .. 2^32 - 1 of shape (voices=%d,)" % n)
-        samples = np.ascontiguousarray(samples, dtype=np.uint32)
-        pointers = np.array([int(r or 0) for r in rows], dtype=np.uint64)
-        onsets = _whole_samples(onsets, n, "onsets")
+        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
         if fracs is not None:
             fracs = frac_arrays(fracs, n)
         pp = cp = None
@@ -377,10 +370,7 @@ class Context:
             if n == 0:  # (no voices: `|| 0`, or a copy, of both channels of d_init; the pointer only says "two channels")
                 pans, comp = np.zeros(1, dtype=np.float32), np.ones(1, dtype=np.float64)
             pp, cp = pans.ctypes.data, comp.ctypes.data
-        lp = None
-        if lengths is not None:
-            lengths = _whole_samples(lengths, n, "lengths")
-            lp = lengths.ctypes.data
+        lp = lengths.ctypes.data if lengths is not None else None
         self._check(self._L.dusp_score_rows_frac_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, n_channels,
                                                         onsets.ctypes.data if n else None, fracs.ctypes.data if fracs is not None and n else None, lp, d_gains, pp, cp,
                                                         n_total_samples, d_init, int(bool(raw)), d_out, stream))
@@ -427,40 +417,36 @@ class Context:
                 pp = params.ctypes.data
             table[p] = ScorePart(prog._h, n_instances, n_voice_samples, pp)
         n_ch = parts[0][0].n_out_channels
+        entry = self._L.dusp_render_host_score_parts
+        args = [table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, lp, gp, n_total_samples, int(tile_bytes)]
         if fracs is not None:
             fracs = frac_arrays(fracs, n)
-            comp = None
-            if pans is not None:
-                pans, comp = pan_arrays(pans, n)
-                n_ch = 2  # (parts that are not mono: the library refuses them)
-
-            def call(*args):  # (the fractions behind the onsets; the pans and their compensation, or two NULLs, behind the gains)
-                return self._L.dusp_render_host_score_parts_frac(*(args[:5] + (fracs.ctypes.data,) + args[5:7] +
-                                                                   ((pans.ctypes.data, comp.ctypes.data) if pans is not None else (None, None)) + args[7:]))
-        elif pans is None:
-            def call(*args):
-                return self._L.dusp_render_host_score_parts(*args)
-        else:
+        if pans is not None:
             pans, comp = pan_arrays(pans, n)
             n_ch = 2  # (parts that are not mono: the library refuses them)
-
-            def call(*args):  # (the pans and their compensation behind the gains)
-                return self._L.dusp_render_host_score_parts_pan(*(args[:7] + (pans.ctypes.data, comp.ctypes.data) + args[7:]))
-        if format is None:
+        pan_args = (pans.ctypes.data, comp.ctypes.data) if pans is not None else (None, None)
+        if fracs is not None:  # (the fractions behind the onsets; the pans and their compensation, or two NULLs, behind the gains)
+            entry = self._L.dusp_render_host_score_parts_frac
+            args[7:7] = pan_args
+            args[5:5] = (fracs.ctypes.data,)
+        elif pans is not None:  # (the pans and their compensation behind the gains)
+            entry = self._L.dusp_render_host_score_parts_pan
+            args[7:7] = pan_args
+        pcm = format is not None  # (else planar f32, and no peak)
+        fmt = 0
+        if pcm:
+            fmt = _pcm_format(format)
+            if fmt not in PCM_BYTES:
+                raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
+            if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
+                raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
+            shape = (n_total_samples, n_ch)
+            out = self.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
+        else:
             out = self.host_empty((n_ch, n_total_samples), pinned)
-            self._check(call(table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, lp, gp, n_total_samples, int(tile_bytes), 0, 0, out.ctypes.data, None))
-            return out
-        fmt = _pcm_format(format)
-        if fmt not in PCM_BYTES:
-            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
-        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
-            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
-        shape = (n_total_samples, n_ch)
-        out = self.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
         peak = np.empty(1, dtype=np.float32)
-        self._check(call(table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, lp, gp, n_total_samples, int(tile_bytes), fmt, int(normalise), out.ctypes.data,
-                         peak.ctypes.data))
-        return out, peak[0]
+        self._check(entry(*args, fmt, int(normalise) if pcm else 0, out.ctypes.data, peak.ctypes.data if pcm else None))
+        return (out, peak[0]) if pcm else out
 
     def score_last_ms(self):
         """-> (kernel_ms, plan_ms, upload_ms) of the most recent score_device call (dusp_score_last_ms; waits for that launch): the kernel
