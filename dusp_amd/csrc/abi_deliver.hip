@@ -1,5 +1,6 @@
 // abi_deliver.hip — the C ABI (include/dusp_hip.h): what happens to rendered PCM on the device before it leaves (interleave, peak, encode) and how
 // it reaches the host (dusp_render_host* and the delivery paths every host render ends with: deliver_host).
+#include <limits>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -229,7 +230,10 @@ static int render_host(dusp_program *prog, size_t n_instances, size_t n_samples,
         d_in = prog->d_host_in.p;
         HIP_TRY(ctx, hipMemcpyAsync(d_in, h_inputs, n_in * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
-    if (int rc = render_device_unguarded(prog, n_instances, n_samples, d_par, d_in, d_out, ctx->stream)) return rc;
+    host_param_bounds(prog, n_par ? h_params : nullptr, n_instances);  // (for the planner's time-split gate)
+    const int rc_render = render_device_unguarded(prog, n_instances, n_samples, d_par, d_in, d_out, ctx->stream);
+    prog->param_bound.clear();  // (a render from device memory brings no table the host can read)
+    if (rc_render) return rc_render;
     const double us_enqueued = since();
     if (int rc = check_guards(prog, ctx->stream)) return rc;
     const size_t n_ch = prog->P.out_bufs.size();

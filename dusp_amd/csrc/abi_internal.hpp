@@ -8,6 +8,8 @@
 //   abi_mix.hip         mix of a batch on the device, the tiles of a large batch, the host render of a mix
 //   abi_score.hip       scores: plans' image, the one launch path, device entries and host renders of scores and pieces
 #pragma once
+#include <limits>
+#include <cmath>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -261,6 +263,8 @@ struct dusp_program : dusp_workspaces {
     uint64_t jit_table_generation = 0;  // ctx->table_generation the texts in jit_src were generated against
     int jit_waves = 0, jit_per_wave = 0;  // geometry of the last compiled launch (shown in dusp_program_info.shape)
     unsigned jit_segments = 1;            // ... the time segments it was cut into
+    unsigned wave_segments = 1;           // the interpreter kernel's last render: the time segments it was cut into
+    std::vector<double> param_bound;      // during a render whose parameter table is in host memory: largest magnitude of every column (else empty: not known)
     bool jit_voices = false;              // ... its voices ran in a loop (jit_codegen.hpp VoicePlan)
     bool jit_scan = false;                // ... its Filters ran as scans over the chunk (jit_filter_scan_ok)
     // channel counts that grow during the first chunks (Program::warm_ops): those chunks on the chunk engine, the rest on a compiled kernel
@@ -387,6 +391,21 @@ int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frame
 // abi_mix.hip
 constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)
 
+// What a parameter table in host memory ([n_params][n_instances]) bounds its columns by — for the planner's time-split gate
+// (fused_plan.hpp wave_split_exact).  Every host path that renders from such a table sets it before it renders and clears it behind.
+inline void host_param_bounds(dusp_program *prog, const float *h_params, size_t n_instances) {
+    const size_t n_params = (size_t)prog->P.g.n_params;
+    prog->param_bound.clear();
+    if (!h_params || !n_params || !n_instances) return;
+    prog->param_bound.assign(n_params, 0.0);
+    for (size_t p = 0; p < n_params; p++)
+        for (size_t i = 0; i < n_instances; i++) {
+            const double a = std::fabs((double)h_params[p * n_instances + i]);
+            double &b = prog->param_bound[p];
+            b = a <= b ? b : a == a ? a : std::numeric_limits<double>::infinity();
+        }
+}
+
 // The tiles of one batch (dusp_render_host_mix, dusp_render_host_score, a part of dusp_render_host_score_parts).  Tiling must not change a
 // bit.  What a render decides from the batch and that changes bits is, while the tiles render, decided from the WHOLE batch: a Filter with
 // a per-instance cutoff runs as a scan or as a recurrence — not the same bits — by the range of its column (mix_range), and so does every
@@ -399,6 +418,7 @@ struct TiledBatch {
     const float *h_gains;
     bool staged = false;      // host vectors of this call may still be on their way to the device
     std::vector<float> cols;  // (a member: it outlives the destructor's wait for the stream)
+
 
     TiledBatch(dusp_program *prog, size_t n_instances, const float *h_params, const float *h_gains, size_t tile);  // tiles of `tile` instances
     TiledBatch(dusp_program *prog, size_t n_instances, const float *h_params, const std::vector<size_t> &starts);  // tiles [starts[i], starts[i + 1])

@@ -49,6 +49,7 @@ void TiledBatch::gather(const float *h_params, size_t lo, size_t n) {
 }
 void TiledBatch::whole_batch_decisions(const float *h_params) {
     prog->mix_n_inst = (uint32_t)n_instances;
+    host_param_bounds(prog, n_params ? h_params : nullptr, n_instances);  // (the whole batch's: every tile decides alike)
     prog->mix_range.assign(3 * n_params, 0u);
     for (size_t p = 0; p < n_params; p++)
         for (size_t i = 0; i < n_instances; i++) {
@@ -66,6 +67,7 @@ TiledBatch::~TiledBatch() {
     if (staged) (void)hipStreamSynchronize(stream);  // (a return in the middle of the tiles)
     prog->mix_range.clear();
     prog->mix_n_inst = 0;
+    prog->param_bound.clear();
     prog->mixed = true;  // (whichever tile was the last to render, the whole batch it was not)
 }
 int TiledBatch::render_tile(size_t lo, size_t n, size_t n_samples) {

@@ -214,6 +214,8 @@ int dusp_program_info_get(const dusp_program *prog, dusp_program_info *info) {
     }
     else if (prog->engine == DUSP_ENGINE_WAVE && prog->jit_ok)
         std::snprintf(info->shape, sizeof info->shape, "%s, %d chunk buffers in LDS (kernel compiling)", prog->P.feed_forward ? "feed-forward" : "feedback", prog->wave.n_slots);
+    else if (prog->engine == DUSP_ENGINE_WAVE && prog->rendered && prog->wave_segments > 1)
+        std::snprintf(info->shape, sizeof info->shape, "%s, %d chunk buffers in LDS, %u seg", prog->P.feed_forward ? "feed-forward" : "feedback", prog->wave.n_slots, prog->wave_segments);
     else if (prog->engine == DUSP_ENGINE_WAVE)
         std::snprintf(info->shape, sizeof info->shape, "%s, %d chunk buffers in LDS", prog->P.feed_forward ? "feed-forward" : "feedback", prog->wave.n_slots);
     if (prog->engine == DUSP_ENGINE_CHUNK && !prog->P.warm_ops.empty() && !prog->handoff_ok && !prog->handoff_why.empty())

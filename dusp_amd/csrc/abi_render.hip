@@ -239,7 +239,7 @@ static int render_wave_interpreter(dusp_program *prog, const RenderCall &c) {
     w.n_seg = 1;
     w.seg_groups = n_chunks;
     w.max_osc_level = prog->wave.max_osc_level;
-    if (prog->wave.splittable) {
+    if (prog->wave.splittable && dusp::wave_split_exact(P, ctx->table_bound, prog->param_bound.empty() ? nullptr : prog->param_bound.data())) {  // (fused_plan.hpp: only where segment totals are the reference's phases)
         dusp::jit_time_segments(ctx->n_cus, ctx->knobs.wave_segments, n_inst, n_chunks, w.n_seg, w.seg_groups);
         if (w.n_seg > 1) {
             const size_t per = (size_t)w.n_ops * n_inst * w.n_seg;
@@ -248,6 +248,7 @@ static int render_wave_interpreter(dusp_program *prog, const RenderCall &c) {
             w.seg_start = prog->d_seg.p + per;
         }
     }
+    prog->wave_segments = w.n_seg;
     const bool lds_ok = w.lds_table_id >= 0 && ctx->table_antisym[w.lds_table_id] && P.g.sample_rate % 2 == 0;
     HIP_TRY(ctx, hipEventRecord(prog->ev0, stream));
     HIP_TRY(ctx, dusp::launch_wave_engine(w, lds_ok, ctx->knobs.wave_max_waves, stream));

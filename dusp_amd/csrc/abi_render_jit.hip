@@ -118,6 +118,8 @@ static int jit_plan_render(dusp_program *prog, JitRender &R, uint32_t n_inst, ui
     batch.inputs = inputs;
     batch.voice_loop = prog->voice_loop != 0;
     batch.whole_n_inst = prog->mix_n_inst;
+    batch.param_bound = prog->param_bound.empty() ? nullptr : prog->param_bound.data();
+    batch.params_unknown = prog->P.g.n_params > 0 && prog->param_bound.empty();
     R.plan = dusp::jit_plan(site, batch, prog->P, prog->wave);
     if (R.plan.error) CTX_FAIL(ctx, DUSP_ERR_ARG, R.plan.error);
     R.a.n_seg = R.plan.n_seg;

@@ -31,6 +31,56 @@ __device__ __forceinline__ uint64_t mulmod(uint64_t a, uint64_t n, uint64_t S) {
     return acc;
 }
 
+// ---- Oscillator increments beyond the exact regime.  The parallel oscillator forms keep phases as exact 2^-36 fixed point and fold an
+// increment at or above the sample rate by (a + b) % m == (a + b % m) % m.  That identity is true of real numbers; the reference adds in
+// f64 (`phase += f[t]; phase %= sampleRate`, Osc.js:39-40), and its sum is exact on that grid only while |phase + f| < 2^17 (SURVEY.md
+// §8a note ii).  Above that the reference's addition rounds low phase bits away — from |f| ~ 2^53 on, all of them — and the only way to
+// its bits is its own loop.  The test is conservative and meant to be asked wave-wide over a chunk's increments: a phase is below the
+// sample rate, so |f| < 2^17 - sampleRate keeps every sum below 2^17.  (NaN / Inf: not this regime's business, the poison flags'.)
+__device__ __forceinline__ bool osc_beyond_exact(float f, uint32_t sr) {
+    return fabsf(f) >= (float)(sr < 131072u ? 131072u - sr : 0u) && fabsf(f) <= 3.4028235e38f;  // (finite: FLT_MAX is an increment like any other)
+}
+// ... and for an oscillator whose f is a constant or a per-instance parameter, the other end as well: 0 < |f| < 2^-13, off the 2^-36
+// grid, where every sum of the reference rounds — and where, from phase 0, an increment in (-2^-38, 0) makes `phase += sampleRate`
+// round up to the sample rate itself, the table's last entry.  Such an oscillator runs the reference's loop for the whole render.
+__device__ __forceinline__ bool osc_const_beyond_exact(float f, uint32_t sr) {
+    return osc_beyond_exact(f, sr) || (fabsf(f) < 0x1p-13f && f != 0.f);
+}
+__device__ __forceinline__ double osc_reference_step(double phase, double f, double srd) {  // Osc.js:39-42 as written
+    double p = fmod(phase + f, srd);
+    if (p < 0.0) p += srd;
+    return p;
+}
+// One chunk of that loop, run by every lane of the wavefront alike (`get(lane, c)`: the increment of sample 4 lane + c, the same value in
+// whatever lane asks); each lane keeps the phases of its own four samples.  -> the phase after the chunk's last sample
+template <class GetF>
+__device__ __forceinline__ double osc_reference_chunk(double phase, double srd, uint32_t lane, GetF get, double (&mine)[4]) {
+    for (uint32_t l = 0; l < 64u; ++l)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            phase = osc_reference_step(phase, (double)get(l, c), srd);
+            if (l == lane) mine[c] = phase;
+        }
+    return phase;
+}
+// Osc.js:43-45 on such a phase, from the table in memory (sr + 1 entries): waveTable[floor] * (1 - fraction) + waveTable[ceil] * fraction;
+// NaN reads `undefined`.  phase == sampleRate (see above) reads the last entry.
+__device__ __forceinline__ float osc_reference_lookup(const float *tbl, double phase, double srd) {
+    if (!(phase >= 0.0 && phase <= srd)) return __builtin_nanf("");
+    const double lo = floor(phase), fraction = phase - lo;
+    const uint32_t idx = (uint32_t)lo;
+    return (float)((double)tbl[idx] * (1.0 - fraction) + (double)tbl[fraction != 0.0 ? idx + 1u : idx] * fraction);
+}
+// ... and back onto the fixed-point grid, where the carry resumes: a phase the f64 sum has rounded is still a multiple of 2^-36.
+// dead: the phase is NaN (every sample from here on is).  S itself — the phase AT the sample rate — is a value of its own: a carry
+// that holds it keeps its oscillator on the reference's loop (with f = 0 it stays there, with f < 0 it moves on from there).
+__device__ __forceinline__ unsigned long long osc_phase_fixed(double phase, unsigned long long S, bool &dead) {
+    dead = !(phase >= 0.0);
+    if (dead) return 0ull;
+    const unsigned long long P = (unsigned long long)(phase * 68719476736.0);
+    return P < S ? P : S;
+}
+
 __device__ __forceinline__ float operand_value(const DevOperand &o, const float *params, uint32_t n_inst, uint32_t inst) {
     return o.kind == SRC_PARAM ? params[(size_t)o.idx * n_inst + inst] : o.cval;
 }

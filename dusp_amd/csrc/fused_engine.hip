@@ -79,14 +79,17 @@ __device__ __forceinline__ void start_phase(const OscRec &rc, uint32_t seg, uint
 
 // One thread per voice: decompose f into exact fixed point, precompute the strides the render
 // kernel needs, and write the end-of-render state (state write-back).
-__global__ void dusp_fused_prepare(FusedArgs A, OscRec *recs) {
-    const uint32_t inst = blockIdx.x * blockDim.x + threadIdx.x;
-    if (inst >= A.n_inst) return;
+static __device__ int fused_prepare_voice(const FusedArgs &A, OscRec *recs, const uint32_t inst) {
     const uint32_t sr = A.sample_rate;
     const double srd = (double)sr;
     OscRec rc;
     double fd = (double)operand_value(A.f, A.params, A.n_inst, inst);
-    rc.bad = !(fabs(fd) <= 3.0e38);  // non-finite f: every sample is NaN -> 0 after `|| 0`
+    const float f_in = operand_value(A.f, A.params, A.n_inst, inst);
+    rc.bad = !(fabs(fd) <= 3.4028234663852886e38);  // non-finite f: every sample is NaN -> 0 after `|| 0`
+    // ... 2: a finite f beyond the exact regime (device_util.hpp osc_const_beyond_exact: 2^17 - sampleRate or more, or below 2^-13), where
+    // the reference's f64 sum rounds and no fixed-point form stands in for it: the prepare kernel itself writes such a voice, as the
+    // reference's own loop computes it (fused_reference_voice), and the render kernel stores nothing for it
+    if (!rc.bad && osc_const_beyond_exact(f_in, sr)) rc.bad = 2;
     if (rc.bad) fd = 0.0;
     if (fabs(fd) >= srd) fd = fmod(fd, srd);
     int E = 0;
@@ -112,7 +115,11 @@ __global__ void dusp_fused_prepare(FusedArgs A, OscRec *recs) {
     // the state every unit holds after ceil(n_samples/256) ticks
     const uint64_t T_end = (uint64_t)A.n_chunks * kChunk;
     double phase_end = (double)addmod(rc.P0, mulmod(rc.Fm, T_end, rc.S), rc.S) * rc.u;
-    if (rc.bad) phase_end = __builtin_nan("");
+    if (rc.bad == 1) phase_end = __builtin_nan("");
+    if (rc.bad == 2) {
+        phase_end = A.phase0;
+        for (uint64_t n = 0; n < T_end; ++n) phase_end = osc_reference_step(phase_end, (double)f_in, srd);
+    }
     A.end_state[(size_t)A.osc_state_word * A.n_inst + inst] = phase_end;
     if (A.ramp_state_word >= 0) {
         const double t_end = A.r_playing ? fmin(A.r_t0 + (double)T_end, A.r_d) : A.r_t0;
@@ -126,6 +133,42 @@ __global__ void dusp_fused_prepare(FusedArgs A, OscRec *recs) {
         A.end_state[(size_t)(A.shape_state_word + 1) * A.n_inst + inst] = A.s_playing ? 1.0 : 0.0;
         A.end_state[(size_t)(A.shape_state_word + 2) * A.n_inst + inst] = (A.s_finished || (T_end > 0 && t_end > srd)) ? 1.0 : 0.0;
     }
+    return rc.bad;
+}
+
+// A voice whose f is beyond the exact regime (OscRec::bad == 2): one wavefront, the whole render.  Every lane runs the
+// reference's 256 phase additions of a step (device_util.hpp osc_reference_chunk) and keeps its own four samples; table lookups from memory;
+// the envelope by the closed forms the render kernel uses (without the verified reciprocal: the same values).  Any speed will do here —
+// what matters is that the render kernel carries nothing for these voices but a store it leaves out.
+static __device__ void fused_reference_voice(const FusedArgs &A, const OscRec *recs, const uint32_t inst, const uint32_t lane, const int kind) {
+    const double srd = (double)A.sample_rate, dy = A.r_y1 - A.r_y0;
+    const float f = operand_value(A.f, A.params, A.n_inst, inst), gain = recs[inst].gain;
+    float *row = A.out + (size_t)inst * A.n_samples;
+    double phase = A.phase0;
+    for (uint32_t g = 0; g < A.n_groups; ++g) {
+        double mine[4];
+        phase = osc_reference_chunk(phase, srd, lane, [&](uint32_t, int) { return f; }, mine);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint64_t n = (uint64_t)g * kChunk + lane * 4 + c;
+            float v = osc_reference_lookup(A.table, mine[c], srd);
+            if (kind == FUSED_OSC_RAMP) v = v * ramp_value<false>(A, A.r_playing ? A.r_t0 + (double)(n + 1) : A.r_t0, dy);
+            if (kind == FUSED_OSC_SHAPE) v = v * shape_value(A, A.s_playing ? repeat_add(A.s_t0, A.s_c, n + 1) : A.s_t0, srd);
+            if (kind == FUSED_OSC_GAIN) v = v * gain;
+            if (n < A.n_samples) row[n] = fix_out<false>(v);
+        }
+    }
+}
+
+// One thread per voice: fused_prepare_voice.  Then the block's voices beyond the exact regime, if it has any, one wavefront each in turn.
+__global__ void __launch_bounds__(256) dusp_fused_prepare(FusedArgs A, OscRec *recs, int kind) {
+    __shared__ uint32_t flagged[256], n_flagged;
+    if (threadIdx.x == 0) n_flagged = 0u;
+    __syncthreads();
+    const uint32_t inst = blockIdx.x * blockDim.x + threadIdx.x;
+    if (inst < A.n_inst && fused_prepare_voice(A, recs, inst) == 2) flagged[atomicAdd(&n_flagged, 1u)] = inst;
+    __syncthreads();  // (the records these wavefronts read were written by this block)
+    for (uint32_t k = threadIdx.x >> 6; k < n_flagged; k += 4u) fused_reference_voice(A, recs, flagged[k], threadIdx.x & 63u, kind);
 }
 
 // KIND: fused shape.  TBL: table placement.  R: voices per work item.  FASTDIV / FINITE:
@@ -419,7 +462,7 @@ __global__ void __launch_bounds__(BLOCK) dusp_fused_kernel(FusedArgs A, const Os
                 double ph[RS][4], D[RS];
                 size_t roff[RS];
                 float gain[RS];
-                bool bad[RS];
+                int bad[RS];  // (OscRec::bad: 1 every sample NaN; 2 written by the prepare kernel, nothing is stored here)
 #pragma unroll
                 for (int r = 0; r < RS; ++r) {
                     const OscRec rc = recs[inst[sub + r]];
@@ -453,7 +496,7 @@ __global__ void __launch_bounds__(BLOCK) dusp_fused_kernel(FusedArgs A, const Os
                                 ph[r][c] += D[r];
                                 if (ph[r][c] >= srd) ph[r][c] -= srd;
                             }
-                            store4<decltype(vec)::value>(row + roff[r], v, (uint64_t)g * kChunk + lane * 4, A.n_samples);
+                            if (bad[r] != 2) store4<decltype(vec)::value>(row + roff[r], v, (uint64_t)g * kChunk + lane * 4, A.n_samples);
                         }
                         row += kChunk;
                     }
@@ -547,10 +590,11 @@ hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t
     A.n_seg = (A.n_groups + A.seg_groups - 1) / A.seg_groups;
     const bool finite = L.table_finite && plan.kind != FUSED_OSC_GAIN && std::isfinite(plan.r_y0) && std::isfinite(plan.r_y1);
 
-    hipLaunchKernelGGL(dusp_fused_prepare, dim3((A.n_inst + 255) / 256), dim3(256), 0, stream, A, L.recs);
+    hipLaunchKernelGGL(dusp_fused_prepare, dim3((A.n_inst + 255) / 256), dim3(256), 0, stream, A, L.recs, (int)plan.kind);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
+    auto render = [&]() -> hipError_t {
 #define DUSP_L3(KIND, RR, FD, FIN) \
     return tbl == 1 ? launch_one<KIND, 1, RR, FD, FIN, 1024>(A, L.recs, grid, lds_bytes, stream) \
                     : launch_one<KIND, 0, RR, FD, FIN, 256>(A, L.recs, grid, 0, stream)
@@ -571,7 +615,9 @@ hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t
     }
 #undef DUSP_L2
 #undef DUSP_L3
-    return hipErrorInvalidValue;
+        return hipErrorInvalidValue;
+    };
+    return render();
 }
 
 }  // namespace dusp

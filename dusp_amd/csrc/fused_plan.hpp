@@ -11,7 +11,9 @@
 //     mul(osc(k),shape)    Osc under a Shape envelope with constant duration / min / max: the canonical Dusp voice "O440 * D1"
 // Everything else runs on the chunk engine.
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -55,7 +57,7 @@ struct OscRec {
     uint64_t S, Fm, P0;               // modulus sr * 2^-E, increment f * 2^-E mod S, start phase
     uint64_t step4, step256, segstep; // (4 f), (256 f), (segment length * f) mod S
     double u;                         // 2^E
-    int32_t E, bad;                   // bad: non-finite f (every sample NaN -> 0)
+    int32_t E, bad;                   // bad: 1 non-finite f (every sample NaN -> 0); 2 a finite f beyond the exact regime (the reference's own loop)
     float gain, pad;
 };
 
@@ -749,6 +751,49 @@ inline bool plan_wave(const Program &P, WavePlan &plan, bool will_continue = fal
     plan.splittable_but_for_filters = plan.splittable && plan.has_filter;
     plan.splittable = plan.splittable && !plan.has_filter;
     plan.ok = true;
+    return true;
+}
+
+// Time segments stand on phase TOTALS: a segment's start phase is the modular sum of the increments before it.  That is the reference's
+// phase only while its f64 `phase += f` is exact — every |phase + f| below 2^17 (SURVEY.md §8a note ii); one rounded sum and the phase
+// behind it is no function of totals any more.  So a render is cut only where every modulated oscillator's increments are PROVABLY below
+// 2^17 - sampleRate in magnitude: bounds from the tables (|entry| <= 2^table_bound), Ramps, constants, products and sums, and per-instance
+// parameters where the render call brought its parameter table in host memory (param_bound[slot] = the column's largest magnitude; a
+// render from device memory has none); anything else on the way is not known, and the circuit renders unsplit (where its kernels run the
+// reference's loop on such a chunk).  Constant and per-instance f need no proof: their oscillators find a segment's start phase on their own.
+// params_assumed: the caller has no parameter table to show and vouches for none (a planner asked about a launch's shape alone:
+// tests/native/jit_plan_check.cpp); every render states what it knows — its columns' bounds, or that it has none to give.
+inline bool wave_split_exact(const Program &P, const int *table_bound, const double *param_bound = nullptr, bool params_assumed = false) {
+    const double inf = std::numeric_limits<double>::infinity(), limit = 131072.0 - (double)P.g.sample_rate;
+    std::vector<double> bound((size_t)std::max(1, P.n_bufs), inf);
+    auto of = [&](const DevOperand &o) {
+        if (o.kind == SRC_BUF) return o.idx >= 0 && o.idx < P.n_bufs ? bound[(size_t)o.idx] : inf;
+        if (o.kind == SRC_CONST) return std::isfinite(o.cval) ? std::fabs((double)o.cval) : inf;
+        if (o.kind == SRC_PARAM && param_bound && o.idx >= 0 && o.idx < P.g.n_params) return param_bound[o.idx];  // (a host render's parameter table: max |p| of the column)
+        if (o.kind == SRC_PARAM && params_assumed) return 0.0;
+        return inf;
+    };
+    for (const DevOp &op : P.ops) {
+        double b = inf;
+        switch (op.op) {
+        case OP_OSC:
+            if (op.in[0].kind == SRC_BUF && !(of(op.in[0]) < limit)) return false;
+            if (table_bound && op.attr >= 0 && op.attr < kNumTables && table_bound[op.attr] < 64) b = std::ldexp(1.0, table_bound[op.attr]);
+            break;
+        case OP_RAMP:  // between y0 and y1 (plan_wave admits t in [0, duration] only)
+            if (P.init_state[(size_t)op.state_slot] >= 0) b = std::max(std::fabs(op.d[1]), std::fabs(op.d[2]));
+            break;
+        case OP_MULTIPLY: {
+            const double x = of(op.in[0]), y = of(op.in[1]);
+            b = std::isfinite(x) && std::isfinite(y) ? x * y : inf;
+            break;
+        }
+        case OP_SUM: case OP_SUBTRACT: b = of(op.in[0]) + of(op.in[1]); break;
+        case OP_REPEATER: case OP_POLARITY_INVERT: case OP_ABS: b = of(op.in[0]); break;
+        default: break;
+        }
+        if (op.out_buf >= 0 && op.out_buf < P.n_bufs) bound[(size_t)op.out_buf] = std::isfinite(b) ? b : inf;
+    }
     return true;
 }
 

@@ -20,6 +20,8 @@ struct JitBatch {
     bool inputs = false;      // the circuit reads host-generated signals
     bool voice_loop = false;  // the circuit's voices run in a loop (jit_find_voices said so, once per program)
     uint32_t whole_n_inst = 0;  // a tile of a mix (dusp_render_host_mix): the instances of the whole batch, which decide whether segments warm up
+    const double *param_bound = nullptr;  // [n_params] largest magnitude of every parameter column, where the caller's table is in host memory (fused_plan.hpp wave_split_exact)
+    bool params_unknown = false;          // the render has per-instance parameters and no table in host memory (a render from device memory): nothing bounds them
 };
 
 struct JitPlan {
@@ -55,13 +57,19 @@ inline std::pair<int, int> jit_source_key(const JitOptions &opt) {
     return {opt.waves, opt.per_wave * 8 + opt.filter_block % 8 + (opt.voice_loop ? 64 : 0) + (opt.filter_scan ? 128 : 0) + (opt.rotate ? 0 : 256) + (opt.warm ? 512 : 0)};
 }
 
+// May this render be cut in time?  Segment totals stand for the reference's phases only where the modulated increments are bounded
+// (fused_plan.hpp wave_split_exact) — for plain segments and for segments that warm up alike: both start their modulated oscillators from totals.
+inline bool jit_split_exact(const JitSite &site, const JitBatch &batch, const Program &P) {
+    return wave_split_exact(P, site.table_bound, batch.param_bound, /*params_assumed=*/!batch.param_bound && !batch.params_unknown);
+}
+
 // The time segments of a render on a compiled kernel: plan.n_seg, plan.seg_groups, plan.warm
 inline void jit_plan_segments(JitPlan &plan, const JitSite &site, const JitBatch &batch, const Program &P, const WavePlan &wave) {
     const Knobs &knobs = site.knobs;
     const uint32_t n_inst = batch.n_inst, n_chunks = batch.n_chunks;
     // Few instances, long render: cut time into segments so that the whole chip works on it
     plan.seg_groups = n_chunks;
-    if (wave.splittable && !knobs.jit_force_waves) jit_time_segments(site.n_cus, knobs.wave_segments, n_inst, n_chunks, plan.n_seg, plan.seg_groups);
+    if (wave.splittable && !knobs.jit_force_waves && jit_split_exact(site, batch, P)) jit_time_segments(site.n_cus, knobs.wave_segments, n_inst, n_chunks, plan.n_seg, plan.seg_groups);
     // A few circuits with Filters, long: segments that warm up (jit_codegen.hpp jit_warm_chunks) — every segment starts a segment early, from rest,
     // its Filters merge with the sequential trajectory on the way (checked after the launch), and only its own chunks are stored
     // (a Filter stage's serving wave runs 32 recurrences side by side at the price of one: the chip is full at 32 rows a CU, so up to a quarter of that many
@@ -71,7 +79,7 @@ inline void jit_plan_segments(JitPlan &plan, const JitSite &site, const JitBatch
     // tile, and with fewer instances the segment count below only grows: every tile of such a batch warms up as well, or none does.)
     const uint32_t n_decide = batch.whole_n_inst ? batch.whole_n_inst : n_inst;
     if ((uint64_t)n_decide * 4 <= (uint64_t)site.n_cus * 32 && !batch.persistent && !batch.resume && !batch.handoff && !batch.inputs && !knobs.jit_force_waves && knobs.filter_warm != 0 && knobs.wave_segments != 0 &&
-        knobs.wave_segments != 1) {
+        knobs.wave_segments != 1 && jit_split_exact(site, batch, P)) {
         const uint32_t warm_chunks = jit_warm_chunks(P, wave);
         if (warm_chunks) {
             // (DUSP_FILTER_WARM=n > 1, tests: segments of n chunks whatever the Filters need — too short a warm-up shows in the check, and the render is finished sequentially)

@@ -207,17 +207,25 @@ struct JitOscK {
     unsigned long long PD;         // LEAN: this lane's first sample of the next chunk, index.fraction as a biased 64-bit integer (LeanPhase)
     unsigned long long Q1, Q2, Q3, C; // LEAN: q, 2q, 3q, 256q mod S as 32.32 integers (wave-uniform)
     bool bad, fx32, lean;          // bad: f is NaN / Inf (every sample NaN); fx32 / lean: qualifies for the FX / LEAN form
+    bool beyond;                   // f is beyond the exact regime (device_util.hpp osc_const_beyond_exact): the reference's own loop, below
+    float fconst;                  // ... its increment
+    double ref;                    // ... and its phase before the next chunk (wave-uniform)
 
     __device__ __forceinline__ void begin(const JitArgs &A, const JitCtx &X, float f, int state_slot) {
         double fd = (double)f;
-        bad = !(fabs(fd) <= 3.0e38);
+        bad = !(fabs(fd) <= 3.4028234663852886e38);
         if (bad) fd = 0.0;
         if (fabs(fd) >= X.srd) fd = fmod(fd, X.srd);  // (a + b) % m == (a + b % m) % m
         const long long qs = (long long)(fd * kJ36);  // exact for |f| >= 2^-13 (or f == 0)
         q = qs >= 0 ? (unsigned long long)qs : X.S - (unsigned long long)(-qs);
         if (q >= X.S) q -= X.S;
-        if (bad) q = 1ull;  // (every sample is NaN whatever the phase; an increment off the 2^-32 grid keeps such an oscillator out of the FX / LEAN copies, which carry no select for it)
+        beyond = jit_u(osc_const_beyond_exact(f, X.sr));
+        fconst = jit_u(f);
+        if (bad || beyond) q = 1ull;  // (an increment off the 2^-32 grid keeps such an oscillator out of the FX / LEAN copies, which carry no select for it: every sample is NaN whatever the phase, or comes from the reference's loop)
         P_init = (unsigned long long)(A.init_state[state_slot] * kJ36);
+        ref = A.init_state[state_slot];
+        if (beyond)  // the reference's phase before this wavefront's first chunk: no closed form, its loop from the render's first sample
+            for (uint64_t n = 0; n < (uint64_t)X.g_begin * kChunk; ++n) ref = osc_reference_step(ref, (double)fconst, X.srd);
         q256 = jit_mulmod(q, kChunk, X.S, X.inv_S);
         P = addmod(P_init, jit_mulmod(q, X.n0(X.g_begin) + 1, X.S, X.inv_S), X.S);
         q = jit_u(q);
@@ -249,6 +257,14 @@ struct JitOscK {
     template <int TF, int FORM, int MODE>  // MODE: 0 general, 1 FX, 2 LEAN (differences of neighbours in f64), 3 LEAN (in f32)
     __device__ __forceinline__ void tick(const JitCtx &X, const float *gtab, float (&out)[4]) {
         float ta[4], tb[4];
+        if (MODE == 0 && beyond) {  // (wave-uniform) every lane runs the chunk's 256 additions as the reference does and keeps its own four phases
+            double mine[4];
+            const float fc = fconst;
+            ref = osc_reference_chunk(ref, X.srd, X.lane, [&](uint32_t, int) { return fc; }, mine);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) out[c] = osc_reference_lookup(gtab, mine[c], X.srd);
+            return;
+        }
         if (MODE >= 2) {  // LEAN (device_util.hpp LeanPhase, lerp_delta)
             double da[4], dd[4], fr[4];
 #pragma unroll
@@ -310,6 +326,11 @@ struct JitOscK {
     // the phase after ceil(n_samples / 256) ticks (state write-back)
     __device__ __forceinline__ double end_phase(const JitArgs &A, const JitCtx &X) const {
         if (bad) return __builtin_nan("");
+        if (beyond) {
+            double p = (double)P_init * (1.0 / kJ36);  // (the start phase is on the grid: fused_plan.hpp plan_wave)
+            for (uint64_t n = 0; n < (uint64_t)A.n_groups * kChunk; ++n) p = osc_reference_step(p, (double)fconst, X.srd);
+            return p;
+        }
         return (double)addmod(P_init, jit_mulmod(q256, A.n_groups, X.S, X.inv_S), X.S) * (1.0 / kJ36);  // n_groups * 256 samples
     }
 };
@@ -321,12 +342,17 @@ struct JitOscKV {
     unsigned long long PD, Q1, Q2, Q3, C;  // LEAN
     unsigned long long P, q, q256;         // general form
     double end;                            // end_phase()
-    uint32_t bad;
+    double ref;                            // beyond the exact regime: the reference's phase, its increment
+    float fconst;
+    uint32_t bad, beyond;
     __device__ __forceinline__ void keep(const JitArgs &A, const JitCtx &X, const JitOscK &o) {
         PD = o.PD; Q1 = o.Q1; Q2 = o.Q2; Q3 = o.Q3; C = o.C;
         P = o.P; q = o.q; q256 = o.q256;
         end = o.end_phase(A, X);
         bad = o.bad ? 1u : 0u;
+        beyond = o.beyond ? 1u : 0u;
+        ref = o.ref;
+        fconst = o.fconst;
     }
     template <int MODE>
     __device__ __forceinline__ void lend(JitOscK &o) const {  // the fields tick<.., MODE> reads (wave-uniform ones made known as such)
@@ -336,11 +362,15 @@ struct JitOscKV {
             o.P = P; o.q = jit_u(q); o.q256 = jit_u(q256);
         }
         o.bad = jit_u(bad) != 0u;
+        o.beyond = jit_u(beyond) != 0u;
+        o.ref = ref;
+        o.fconst = fconst;
     }
     template <int MODE>
     __device__ __forceinline__ void take(const JitOscK &o) {
         if (MODE >= 2) PD = o.PD;
         else P = o.P;
+        if (MODE == 0) ref = o.ref;
     }
 };
 
@@ -369,9 +399,25 @@ struct JitOscS {
     // first and then runs ONE straight-line block for all of them, so that their independent work can interleave.
     __device__ __forceinline__ bool rare(const JitCtx &X, const float (&f)[4]) const {
         bool big = false;
+        const float lim = (float)min(X.sr, X.sr < 131072u ? 131072u - X.sr : 0u);  // (above 65536 Hz the exact regime ends below the sample rate: osc_beyond_exact)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) big = big || !(fabsf(f[c]) < (float)X.sr);
-        return poison != 0 || __any(big);
+        for (int c = 0; c < 4; ++c) big = big || !(fabsf(f[c]) < lim) || (f[c] < 0.f && f[c] > -0x1p-36f);  // (... or what, from phase 0, takes the reference's phase to the sample rate itself)
+        return poison != 0 || carry >= X.S || __any(big);
+    }
+    // Beyond the exact regime (device_util.hpp osc_beyond_exact): the chunk's phases as the reference adds them, in f64, sample after sample,
+    // on every lane alike (the increments come round by ds_bpermute); lookups from the table in memory.
+    template <bool LOOKUP>
+    __device__ __forceinline__ void reference_chunk(const JitCtx &X, const float *gtab, const float (&f)[4], float (&out)[4]) {
+        double ph = poison ? __builtin_nan("") : (double)carry * (1.0 / kJ36), mine[4];
+        ph = osc_reference_chunk(ph, X.srd, X.lane, [&](uint32_t l, int c) {
+            return __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)(l << 2), (int)__float_as_uint(f[c]))); }, mine);
+        if (LOOKUP) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) out[c] = osc_reference_lookup(gtab, mine[c], X.srd);
+        }
+        bool dead;
+        carry = jit_u((unsigned long long)osc_phase_fixed(ph, X.S, dead));
+        poison = jit_u(dead ? 1u : 0u);
     }
     // RARE = false: every increment finite and below the sample rate in magnitude, the oscillator not poisoned (rare() said so).
     // S = sr << 36 has a zero low word, so every "+- S" and every comparison with S touches the HIGH word of a phase only.
@@ -389,7 +435,7 @@ struct JitOscS {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     double fd = (double)f[c];
-                    const bool fin = fabs(fd) <= 3.0e38;
+                    const bool fin = fabs(fd) <= 3.4028234663852886e38;
                     bad = bad || !fin;
                     if (!fin) fd = 0.0;
                     if (fabs(fd) >= X.srd) fd = fmod(fd, X.srd);
@@ -422,6 +468,15 @@ struct JitOscS {
             hi[c] = t;
             lo[c] = (uint32_t)sum;
         }
+        if (RARE) {  // (wave-uniform) an increment of 2^17 - sampleRate or more, phase 0 meeting an increment in (-2^-36, 0), a carry at the sample rate
+            bool careful = carry >= X.S;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) careful = careful || osc_beyond_exact(f[c], X.sr) || (f[c] < 0.f && qv[c] == 0 && (hi[c] | lo[c]) == 0u);
+            if (__any(careful)) {
+                reference_chunk<LOOKUP>(X, gtab, f, out);
+                return;
+            }
+        }
         if (LOOKUP) {  // all the lookups of the chunk first, then the lerps
             float ta[4], tb[4];
 #pragma unroll
@@ -438,7 +493,7 @@ struct JitOscS {
             bool dead = poison != 0 || (bad_lanes & ((1ull << X.lane) - 1ull)) != 0;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                dead = dead || !(fabs((double)f[c]) <= 3.0e38);
+                dead = dead || !(fabs((double)f[c]) <= 3.4028234663852886e38);
                 if (dead) out[c] = __builtin_nanf("");
             }
         }

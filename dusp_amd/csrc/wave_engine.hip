@@ -349,7 +349,7 @@ __global__ void __launch_bounds__(WAVES * 64) dusp_wave_kernel(WaveArgs A) {
                 for (int c = 0; c < 4; ++c) {
                     if (lane_constant && c > 0) { q[c] = q[0]; continue; }
                     double fd = (double)f.v[c];
-                    const bool fin = fabs(fd) <= 3.0e38;
+                    const bool fin = fabs(fd) <= 3.4028234663852886e38;
                     bad = bad || !fin;
                     if (!fin) fd = 0.0;
                     if (fabs(fd) >= srd) fd = fmod(fd, srd);  // (a + b) % m == (a + b % m) % m
@@ -371,17 +371,58 @@ __global__ void __launch_bounds__(WAVES * 64) dusp_wave_kernel(WaveArgs A) {
                 const float *gtab = A.tables + (size_t)op.attr * A.table_stride;
                 const bool in_lds = TBL == 1 && op.attr == A.lds_table_id;
                 // phase of this lane's first sample by one exact modulo; the next three by add + single wrap (|q| < S)
-                unsigned long long P = mod_u64_lifted((unsigned long long)(before + s0) + lift, S, inv_S);
+                unsigned long long Pv[4];
+                Pv[0] = mod_u64_lifted((unsigned long long)(before + s0) + lift, S, inv_S);
+#pragma unroll
+                for (int c = 1; c < 4; ++c) {
+                    long long Pn = (long long)Pv[c - 1] + q[c];
+                    if (Pn < 0) Pn += (long long)S;
+                    if (Pn >= (long long)S) Pn -= (long long)S;
+                    Pv[c] = (unsigned long long)Pn;
+                }
+                // Beyond the exact regime (device_util.hpp osc_beyond_exact) somewhere in the chunk — an increment of 2^17 - sampleRate or
+                // more; a constant f below 2^-13; phase 0 meeting an increment in (-2^-36, 0), which takes the reference's phase to the
+                // sample rate itself; a carry that sits there: the chunk's phases as the reference adds them, in f64, sample after sample,
+                // on every lane alike.  Wave-uniform.  (A time-split render only meets the first kind with a constant or per-instance f —
+                // the host cuts no circuit whose modulated increments it cannot bound — and then a segment's start phase is no sum of
+                // totals: the loop runs from the render's first sample.)
+                bool careful = *carry >= S;
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    careful = careful || (lane_constant ? osc_const_beyond_exact(f.v[c], sr) : osc_beyond_exact(f.v[c], sr)) ||
+                              (f.v[c] < 0.f && q[c] == 0 && Pv[c] == 0ull);
+                if (__any(careful)) {
+                    double ph = *poison != 0 ? __builtin_nan("") : (double)*carry * (1.0 / kTwo36), mine[4];
+                    double *kept = (double *)(carry + 2);  // [0] a constant-f oscillator's phase in f64 (an f below 2^-13 leaves the grid), [1] != 0: it holds one
+                    if (lane_constant) {
+                        const float fc = f.v[0];
+                        if (kept[1] != 0.0) ph = kept[0];
+                        if (A.n_seg > 1 && g == g_begin) {
+                            ph = A.init_state[op.state_slot];
+                            for (uint64_t n = 0; n < (uint64_t)g_begin * kChunk; ++n) ph = osc_reference_step(ph, (double)fc, srd);
+                        }
+                        ph = osc_reference_chunk(ph, srd, lane, [&](uint32_t, int) { return fc; }, mine);
+                    } else {
+                        const float *fbuf = (const float *)(bufs + (size_t)op.in[0].idx * 64);
+                        ph = osc_reference_chunk(ph, srd, lane, [&](uint32_t l, int c) { return fbuf[l * 4 + c]; }, mine);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) out.v[c] = osc_reference_lookup(gtab, mine[c], srd);
+                    bool dead_end;
+                    const unsigned long long endP = osc_phase_fixed(ph, S, dead_end);
+                    __builtin_amdgcn_wave_barrier();
+                    if (lane == 0) {
+                        *carry = endP;
+                        *poison = dead_end ? 1u : 0u;
+                        if (lane_constant) { kept[0] = ph; kept[1] = 1.0; }
+                    }
+                    break;
+                }
                 bool dead = poisoned_before;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    if (c > 0) {
-                        long long Pn = (long long)P + q[c];
-                        if (Pn < 0) Pn += (long long)S;
-                        if (Pn >= (long long)S) Pn -= (long long)S;
-                        P = (unsigned long long)Pn;
-                    }
-                    dead = dead || (lane_constant ? bad : !(fabs((double)f.v[c]) <= 3.0e38));
+                    const unsigned long long P = Pv[c];
+                    dead = dead || (lane_constant ? bad : !(fabs((double)f.v[c]) <= 3.4028234663852886e38));
                     const uint32_t idx = (uint32_t)(P >> kFracBits);
                     const double fraction = (double)(P & ((1ull << kFracBits) - 1ull)) * (1.0 / kTwo36);
                     float ta, tb;
@@ -389,7 +430,7 @@ __global__ void __launch_bounds__(WAVES * 64) dusp_wave_kernel(WaveArgs A) {
                     else { ta = gtab[idx]; tb = gtab[idx + 1]; }
                     out.v[c] = dead ? __builtin_nanf("") : (float)((double)ta * (1.0 - fraction) + (double)tb * fraction);
                 }
-                const unsigned long long lastP = __shfl(P, 63, 64);  // phase of the chunk's last sample
+                const unsigned long long lastP = __shfl(Pv[3], 63, 64);  // phase of the chunk's last sample
                 __builtin_amdgcn_wave_barrier();
                 if (lane == 0) {
                     *carry = lastP;
@@ -1057,7 +1098,7 @@ __global__ void __launch_bounds__(WAVES * 64) dusp_wave_kernel(WaveArgs A) {
             const DevOp &op = A.ops[u];
             double *st = A.state + (size_t)op.state_slot * A.n_pad + inst;
             const double *os = opstate + (size_t)op.lds_slot * kOpState;
-            if (op.op == OP_OSC) st[0] = ((const uint32_t *)(os + 1))[0] ? __builtin_nan("") : (double)*(const unsigned long long *)os * (1.0 / kTwo36);
+            if (op.op == OP_OSC) st[0] = ((const uint32_t *)(os + 1))[0] ? __builtin_nan("") : os[3] != 0.0 ? os[2] : (double)*(const unsigned long long *)os * (1.0 / kTwo36);
             if (op.op == OP_DELAY || op.op == OP_TIMER || op.op == OP_FIXED_DELAY || op.op == OP_COMB_FILTER || op.op == OP_ALL_PASS ||
                 op.op == OP_CB_READER || op.op == OP_CB_WRITER || op.op == OP_MULTI_OSC || op.op == OP_READBACK_DELAY || op.op == OP_RETRIGGER)
                 st[0] = os[0];

@@ -750,6 +750,13 @@ int dusp_oracle_render(dusp_oracle *o, size_t n_samples, float *out, int max_cha
 /* ---- descriptor -> circuit ---------------------------------------------- */
 #define FAIL(...) do { snprintf(err, errlen, __VA_ARGS__); dusp_oracle_destroy(o); return NULL; } while (0)
 
+/* The tables a circuit's units read, computed when the first of them is parsed (a circuit of maps and delays needs none). */
+static void need_table(dusp_oracle *o, int w) {
+    if (w < 0 || w >= N_TABLES || o->tables[w]) return;
+    o->tables[w] = (float *)malloc((size_t)(o->sr + 1) * sizeof(float));
+    if (dusp_oracle_wavetable(w, o->sr, o->tables[w])) memset(o->tables[w], 0, (size_t)(o->sr + 1) * sizeof(float));
+}
+
 dusp_oracle *dusp_oracle_create(const double *d, size_t nw, const float *params, size_t n_inst, size_t inst,
                                 char *err, size_t errlen) {
     dusp_oracle *o = (dusp_oracle *)calloc(1, sizeof *o);
@@ -773,10 +780,6 @@ dusp_oracle *dusp_oracle_create(const double *d, size_t nw, const float *params,
         o->rings[r].data = (float **)calloc((size_t)o->rings[r].nch, sizeof(float *));
         for (int c = 0; c < o->rings[r].nch; c++)
             o->rings[r].data[c] = (float *)calloc((size_t)o->rings[r].len, sizeof(float));
-    }
-    for (int w = 0; w < N_TABLES; w++) {
-        o->tables[w] = (float *)malloc((size_t)(o->sr + 1) * sizeof(float));
-        if (dusp_oracle_wavetable(w, o->sr, o->tables[w])) memset(o->tables[w], 0, (size_t)(o->sr + 1) * sizeof(float));
     }
     o->units = (unit_t *)calloc(o->n_units, sizeof(unit_t));
     for (size_t i = 0; i < o->n_units; i++) {
@@ -822,6 +825,7 @@ dusp_oracle *dusp_oracle_create(const double *d, size_t nw, const float *params,
             if (n_attr != 1 || n_state != 1 || u->n_inlets != 1) FAIL("unit %zu: bad Osc record", i);
             u->waveform = (int)a[0];
             if (u->waveform < 0 || u->waveform > 4) FAIL("bad waveform");
+            need_table(o, u->waveform);
             u->phase = s[0];
             break;
         case OP_RAMP:
@@ -895,6 +899,7 @@ dusp_oracle *dusp_oracle_create(const double *d, size_t nw, const float *params,
             if (u->n_inlets != 1 || n_attr != 1 || n_state < 1 || n_state != (size_t)(1 + s[0])) FAIL("unit %zu: bad MultiChannelOsc record", i);
             u->waveform = (int)a[0];
             if (u->waveform < 0 || u->waveform > 4) FAIL("bad waveform");
+            need_table(o, u->waveform);
             u->nphase = (int)s[0];
             u->phases = (double *)calloc((size_t)u->nphase + 1, sizeof(double));
             for (int c = 0; c < u->nphase; c++) u->phases[c] = s[1 + c];
@@ -946,6 +951,7 @@ dusp_oracle *dusp_oracle_create(const double *d, size_t nw, const float *params,
         case OP_SHAPE:
             if (u->n_inlets != 3 || n_attr != 5 || n_state != 3 || !(a[0] >= 5 && a[0] <= 8)) FAIL("unit %zu: bad Shape record", i);
             u->shape_table = (int)a[0];
+            need_table(o, u->shape_table);
             u->left_is_shape = a[1] != 0; u->left_edge = a[2];
             u->right_is_shape = a[3] != 0; u->right_edge = a[4];
             u->t = s[0]; u->playing = s[1] != 0; u->finished = s[2] != 0;
