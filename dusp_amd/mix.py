@@ -57,45 +57,84 @@ def score_chain(planar, onsets, n_total, lengths=None, gains=None, init=None, ra
     if planar.ndim != 3:
         raise ValueError("dusp-hip: planar must have shape (instances, channels, samples)")
     n_inst, n_ch, n_voice = planar.shape
-    if int(n_total) != n_total or n_total < 0:
-        raise ValueError("dusp-hip: n_total must be a whole number of samples, not negative")
-    n_total = int(n_total)
-
-    def whole(values, name):
-        a = np.asarray(values)
-        if a.shape != (n_inst,):
-            raise ValueError("dusp-hip: %s must have shape (instances=%d,)" % (name, n_inst))
-        if a.dtype.kind not in "iu":
-            if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
-                raise ValueError("dusp-hip: %s are whole numbers of samples" % name)
-        return a.astype(np.int64)
-
-    onsets = whole(onsets, "onsets")
+    n_total = _timeline(n_total)
+    onsets = _whole(onsets, n_inst, "onsets", "instances")
     if lengths is None:
         lengths = np.full(n_inst, n_voice, dtype=np.int64)
     else:
-        lengths = whole(lengths, "lengths")
+        lengths = _whole(lengths, n_inst, "lengths", "instances")
         if np.any(lengths < 0) or np.any(lengths > n_voice):
             raise ValueError("dusp-hip: lengths must lie in 0 .. samples=%d" % n_voice)
+    return _chain(list(planar), n_ch, n_total, onsets, lengths, gains, None, init, raw, noun="instances")
+
+
+def _timeline(n_total):
+    if int(n_total) != n_total or n_total < 0:
+        raise ValueError("dusp-hip: n_total must be a whole number of samples, not negative")
+    return int(n_total)
+
+
+def _whole(values, n, name, noun="voices", refusal="dusp-hip: %s are whole numbers of samples"):
+    """onsets / lengths of n voices -> int64 [n] (contiguous): whole numbers of samples, refused otherwise in the caller's words (the
+    noun of the shape, and the sentence for what is no whole number; dusp_amd/runtime.py _whole_samples has its own)"""
+    a = np.asarray(values)
+    if a.shape != (n,):
+        raise ValueError("dusp-hip: %s must have shape (%s=%d,)" % (name, noun, n))
+    if a.dtype.kind not in "iu":
+        if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
+            raise ValueError(refusal % name)
+    return a.astype(np.int64)
+
+
+def _row_lengths(rows, lengths):
+    """lengths of voices that each lie in a row of their own -> int64 [voices]: None for the whole rows, else checked against them"""
+    samples = np.array([r.shape[1] for r in rows], dtype=np.int64)
+    if lengths is None:
+        return samples
+    lengths = _whole(lengths, len(rows), "lengths")
+    if np.any(lengths < 0) or np.any(lengths > samples):
+        k = int(np.argmax((lengths < 0) | (lengths > samples)))
+        raise ValueError("dusp-hip: the length of voice %d is %d: lengths must lie in 0 .. the row's samples (%d)" % (k, int(lengths[k]), int(samples[k])))
+    return lengths
+
+
+def _chain(rows, n_ch, n_total, onsets, lengths, gains, fracs, init, raw, noun="voices", place=None):
+    """The one chain behind score_chain, score_chain_rows and score_chain_rows_panned.  rows: a list of float32 [channels, samples_k];
+    onsets, lengths: int64 [voices], checked by the caller; gains, fracs and init are checked here, in that order (they are refused in
+    the same words by all three, but for the noun of the gains' shape).  place(k, x): what becomes of voice k's samples after the gain
+    before they are added, float32 [channels, len] -> float32 [n_ch, len] (None: x itself)."""
     if gains is not None:
         gains = np.asarray(gains, dtype=np.float32)
-        if gains.shape != (n_inst,):
-            raise ValueError("dusp-hip: gains must have shape (instances=%d,)" % n_inst)
+        if gains.shape != (len(rows),):
+            raise ValueError("dusp-hip: gains must have shape (%s=%d,)" % (noun, len(rows)))
+    if fracs is not None:
+        fracs = check_fracs(fracs, len(rows))
     if init is not None:
         init = np.asarray(init, dtype=np.float32)
         if init.shape != (n_ch, n_total):
             raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
     with np.errstate(all="ignore"):
         acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
-        for k in range(n_inst):
+        for k, row in enumerate(rows):
             onset, length = int(onsets[k]), int(lengths[k])
-            t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
+            frac = fracs[k] if fracs is not None and length > 0 else 0  # (a voice of length 0 takes no part)
+            span = length + 1 if frac != 0 else length  # with a fraction the span is one sample longer: the last sample's ceil tap
+            t0, t1 = max(onset, 0), min(onset + span, n_total)  # (Python integers: no overflow)
             if t1 <= t0:
                 continue
-            term = planar[k, :, t0 - onset:t1 - onset]
+            x = row[:, :length] if frac != 0 else row[:, t0 - onset:t1 - onset]
             if gains is not None:
-                term = term * gains[k]  # float32 * float32 scalar: one f32 rounding
-            acc[:, t0:t1] = acc[:, t0:t1] + term  # float32 + float32: one f32 rounding
+                x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
+            if place is not None:
+                x = place(k, x)
+            term = two_tap_terms(x, frac)[:, t0 - onset:t1 - onset] if frac != 0 else x
+            # float32 + float32: one f32 rounding.  A placed voice without a fraction is added channel by channel, as it always was: the
+            # sums are the same numbers, but where BOTH operands are NaN the arrays' layout decides which NaN's bits numpy keeps.
+            if place is None or frac != 0:
+                acc[:, t0:t1] = acc[:, t0:t1] + term
+            else:
+                for c in range(n_ch):
+                    acc[c, t0:t1] = acc[c, t0:t1] + term[c]
         assert acc.dtype == np.float32
         if not raw:
             acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
@@ -170,13 +209,10 @@ def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None,
     of two_tap_terms over x[s] = f32(row_k[c][s] * g_k) (or row_k[c][s]), each added by a plain f32 add in voice order — the reference's
     Delay by a fraction (the contract of dusp_score_rows_frac_device).  A voice of length 0 takes no part."""
     rows = [np.asarray(r, dtype=np.float32) for r in rows]
-    n = len(rows)
     if any(r.ndim != 2 for r in rows):
         raise ValueError("dusp-hip: every row must have shape (channels, samples)")
-    if int(n_total) != n_total or n_total < 0:
-        raise ValueError("dusp-hip: n_total must be a whole number of samples, not negative")
-    n_total = int(n_total)
-    if n:
+    n_total = _timeline(n_total)
+    if rows:
         n_ch = rows[0].shape[0]
     elif init is not None:
         n_ch = np.asarray(init).shape[0] if np.asarray(init).ndim == 2 else 0
@@ -184,59 +220,8 @@ def score_chain_rows(rows, onsets, n_total, lengths=None, gains=None, init=None,
         n_ch = 1
     if any(r.shape[0] != n_ch for r in rows):
         raise ValueError("dusp-hip: every row must have the same number of channels (%d)" % n_ch)
-
-    def whole(values, name):
-        a = np.asarray(values)
-        if a.shape != (n,):
-            raise ValueError("dusp-hip: %s must have shape (voices=%d,)" % (name, n))
-        if a.dtype.kind not in "iu":
-            if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
-                raise ValueError("dusp-hip: %s are whole numbers of samples" % name)
-        return a.astype(np.int64)
-
-    onsets = whole(onsets, "onsets")
-    samples = np.array([r.shape[1] for r in rows], dtype=np.int64)
-    if lengths is None:
-        lengths = samples
-    else:
-        lengths = whole(lengths, "lengths")
-        if np.any(lengths < 0) or np.any(lengths > samples):
-            k = int(np.argmax((lengths < 0) | (lengths > samples)))
-            raise ValueError("dusp-hip: the length of voice %d is %d: lengths must lie in 0 .. the row's samples (%d)" % (k, int(lengths[k]), int(samples[k])))
-    if gains is not None:
-        gains = np.asarray(gains, dtype=np.float32)
-        if gains.shape != (n,):
-            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
-    if fracs is not None:
-        fracs = check_fracs(fracs, n)
-    if init is not None:
-        init = np.asarray(init, dtype=np.float32)
-        if init.shape != (n_ch, n_total):
-            raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
-    with np.errstate(all="ignore"):
-        acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
-        for k in range(n):
-            onset, length = int(onsets[k]), int(lengths[k])
-            if fracs is not None and fracs[k] != 0 and length > 0:  # the span is one sample longer: the last sample's ceil tap
-                t0, t1 = max(onset, 0), min(onset + length + 1, n_total)
-                if t1 <= t0:
-                    continue
-                x = rows[k][:, :length]
-                if gains is not None:
-                    x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
-                acc[:, t0:t1] = acc[:, t0:t1] + two_tap_terms(x, fracs[k])[:, t0 - onset:t1 - onset]  # float32 + float32: one f32 rounding
-                continue
-            t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
-            if t1 <= t0:
-                continue
-            term = rows[k][:, t0 - onset:t1 - onset]
-            if gains is not None:
-                term = term * gains[k]  # float32 * float32 scalar: one f32 rounding
-            acc[:, t0:t1] = acc[:, t0:t1] + term  # float32 + float32: one f32 rounding
-        assert acc.dtype == np.float32
-        if not raw:
-            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
-    return acc
+    onsets = _whole(onsets, len(rows), "onsets")
+    return _chain(rows, n_ch, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw)
 
 
 def pan_comp(pans):
@@ -267,20 +252,8 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
     n = len(rows)
     if any(r.ndim != 2 or r.shape[0] != 1 for r in rows):
         raise ValueError("dusp-hip: every panned row must be mono, of shape (1, samples)")
-    if int(n_total) != n_total or n_total < 0:
-        raise ValueError("dusp-hip: n_total must be a whole number of samples, not negative")
-    n_total = int(n_total)
-
-    def whole(values, name):
-        a = np.asarray(values)
-        if a.shape != (n,):
-            raise ValueError("dusp-hip: %s must have shape (voices=%d,)" % (name, n))
-        if a.dtype.kind not in "iu":
-            if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
-                raise ValueError("dusp-hip: %s are whole numbers of samples" % name)
-        return a.astype(np.int64)
-
-    onsets = whole(onsets, "onsets")
+    n_total = _timeline(n_total)
+    onsets = _whole(onsets, n, "onsets")
     with np.errstate(all="ignore"):
         pans = np.asarray(pans, dtype=np.float32)
     if pans.shape != (n,):
@@ -293,52 +266,10 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
         comp = np.asarray(comp, dtype=np.float64)
         if comp.shape != (n,):
             raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
-    samples = np.array([r.shape[1] for r in rows], dtype=np.int64)
-    if lengths is None:
-        lengths = samples
-    else:
-        lengths = whole(lengths, "lengths")
-        if np.any(lengths < 0) or np.any(lengths > samples):
-            k = int(np.argmax((lengths < 0) | (lengths > samples)))
-            raise ValueError("dusp-hip: the length of voice %d is %d: lengths must lie in 0 .. the row's samples (%d)" % (k, int(lengths[k]), int(samples[k])))
-    if gains is not None:
-        gains = np.asarray(gains, dtype=np.float32)
-        if gains.shape != (n,):
-            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
-    if fracs is not None:
-        fracs = check_fracs(fracs, n)
-    if init is not None:
-        init = np.asarray(init, dtype=np.float32)
-        if init.shape != (2, n_total):
-            raise ValueError("dusp-hip: init must have shape (channels=2, n_total=%d)" % n_total)
-    with np.errstate(all="ignore"):
-        acc = init.copy() if init is not None else np.zeros((2, n_total), dtype=np.float32)
-        for k in range(n):
-            onset, length = int(onsets[k]), int(lengths[k])
-            if fracs is not None and fracs[k] != 0 and length > 0:  # the span is one sample longer: the last sample's ceil tap
-                t0, t1 = max(onset, 0), min(onset + length + 1, n_total)
-                if t1 <= t0:
-                    continue
-                x = rows[k][0, :length]
-                if gains is not None:
-                    x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
-                xd, p = x.astype(np.float64), np.float64(pans[k])
-                both = np.stack([(((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32),
-                                 (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)])
-                acc[:, t0:t1] = acc[:, t0:t1] + two_tap_terms(both, fracs[k])[:, t0 - onset:t1 - onset]  # float32 + float32: one f32 rounding
-                continue
-            t0, t1 = max(onset, 0), min(onset + length, n_total)  # (Python integers: no overflow)
-            if t1 <= t0:
-                continue
-            x = rows[k][0, t0 - onset:t1 - onset]
-            if gains is not None:
-                x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
-            xd, p = x.astype(np.float64), np.float64(pans[k])
-            left = (((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32)  # float64 operations, each rounded by itself; one rounding to f32
-            right = (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)
-            acc[0, t0:t1] = acc[0, t0:t1] + left  # float32 + float32: one f32 rounding
-            acc[1, t0:t1] = acc[1, t0:t1] + right
-        assert acc.dtype == np.float32
-        if not raw:
-            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
-    return acc
+
+    def pan(k, x):  # the Pan unit: float64 operations, each rounded by itself; one rounding to f32
+        xd, p = x[0].astype(np.float64), np.float64(pans[k])
+        return np.stack([(((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32),
+                         (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)])
+
+    return _chain(rows, 2, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw, place=pan)

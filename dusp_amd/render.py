@@ -158,40 +158,72 @@ def render_mix(outlets, duration=1, gains=None, engine=runtime.ENGINE_AUTO, devi
     one f32 rounding per add), with `gains` what Sum.many of Multiply(outlet, g_i) does — rendered as ONE program in tiles and summed on the
     device in that order (Program.render_mix): memory is bounded by the tile, not by N, and one voice's worth of samples is downloaded.
     A voice sample that is NaN drops that voice out of the sample (the reference's Sum would zero the whole mix sample there)."""
-    uni, n, prog = _mix_program(outlets, duration, engine, device)
-    result = ChannelData()
-    result.sampleRate = uni.sample_rate
-    try:
-        if n > 0:
-            result.extend(prog.render_mix(n, uni.n_instances, uni.params, gains, tile_instances))
-    finally:
-        prog.close()
-    return result
+    return _render_mix(outlets, duration, gains, engine, device, tile_instances)
 
 
-def render_mix_pcm(outlets, duration=1, bit_depth=16, normalise=0, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0):
-    """render_mix, delivering what render_pcm delivers: the mix's frames encoded on the device, and its peak -> PcmData."""
+def _check_pcm(bit_depth, normalise):
     if bit_depth not in _PCM_FORMAT:
         raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
     if normalise not in (0, 1, 2):
         raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
+
+
+def _wav(pcm, bit_depth):
+    """PcmData -> a complete RIFF/WAVE file (bytes)"""
+    if bit_depth == 32:
+        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
+    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+
+
+def _delivered(pcm, sample_rate, n, channels, run):
+    """What a mix, score or piece hands back.  pcm None: ChannelData of what run(None, 0) renders; pcm (bit_depth, normalise): PcmData
+    of the frames and the peak that run(format, normalise) renders.  A timeline of no samples (n == 0) renders nothing: an empty
+    ChannelData, or frames of no samples (of `channels` channels)."""
+    if pcm is None:
+        result = ChannelData()
+        result.sampleRate = sample_rate
+        if n > 0:
+            result.extend(run(None, 0))
+        return result
+    bit_depth, normalise = pcm
+    if n == 0:
+        data, peak = wav.encode_frames(np.zeros((channels, 0), dtype=np.float32), bit_depth, normalise)
+    else:
+        data, peak = run(_PCM_FORMAT[bit_depth], normalise)
+    return PcmData(data, bit_depth, sample_rate, peak)
+
+
+def _render_mix(outlets, duration, gains, engine, device, tile_instances, pcm=None):
+    """render_mix (pcm None) and render_mix_pcm (pcm = (bit_depth, normalise))"""
+    if pcm is not None:
+        _check_pcm(*pcm)
     uni, n, prog = _mix_program(outlets, duration, engine, device)
     try:
-        if n == 0:
-            data, peak = wav.encode_frames(np.zeros((prog.n_out_channels, 0), dtype=np.float32), bit_depth, normalise)
-        else:
-            data, peak = prog.render_mix(n, uni.n_instances, uni.params, gains, tile_instances, _PCM_FORMAT[bit_depth], normalise)
+        return _delivered(pcm, uni.sample_rate, n, prog.n_out_channels,
+                          lambda format, normalise: prog.render_mix(n, uni.n_instances, uni.params, gains, tile_instances, format, normalise))
     finally:
         prog.close()
-    return PcmData(data, bit_depth, uni.sample_rate, peak)
+
+
+def render_mix_pcm(outlets, duration=1, bit_depth=16, normalise=0, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0):
+    """render_mix, delivering what render_pcm delivers: the mix's frames encoded on the device, and its peak -> PcmData."""
+    return _render_mix(outlets, duration, gains, engine, device, tile_instances, (bit_depth, normalise))
 
 
 def render_mix_wav(outlets, duration=1, bit_depth=16, normalise=0, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0):
     """A complete RIFF/WAVE file (bytes) of the mix: render_mix_pcm plus the header (wav.encode_wav)."""
-    pcm = render_mix_pcm(outlets, duration, bit_depth, normalise, gains, engine, device, tile_instances)
-    if bit_depth == 32:
-        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
-    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+    return _wav(render_mix_pcm(outlets, duration, bit_depth, normalise, gains, engine, device, tile_instances), bit_depth)
+
+
+def _voice_arrays(onsets, lengths, gains, n, samples, noun, within):
+    """onsets, lengths and gains of n voices, checked -> int64, int64 or None, float32 or None.  samples: the most a length may be, one
+    number or one a voice; noun and within: the caller's words for the gains' shape and for where lengths must lie."""
+    onsets = runtime._whole_samples(onsets, n, "onsets")
+    if lengths is not None:
+        lengths = runtime._whole_samples(lengths, n, "lengths")
+        if np.any(lengths < 0) or np.any(lengths > samples):
+            raise ValueError("dusp-hip: lengths must lie in 0 .. " + within)
+    return onsets, lengths, runtime._gains_table(gains, n, noun)
 
 
 def _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device):
@@ -200,15 +232,7 @@ def _score_program(outlets, onsets, voice_duration, duration, lengths, gains, en
     n_voice, n_total = _n_samples(voice_duration, uni.sample_rate), _n_samples(duration, uni.sample_rate)
     if n_voice == 0:
         raise descriptor.DuspError("dusp-hip: voice_duration must cover at least one sample")
-    onsets = runtime._whole_samples(onsets, uni.n_instances, "onsets")
-    if lengths is not None:
-        lengths = runtime._whole_samples(lengths, uni.n_instances, "lengths")
-        if np.any(lengths < 0) or np.any(lengths > n_voice):
-            raise ValueError("dusp-hip: lengths must lie in 0 .. the voice's %d samples" % n_voice)
-    if gains is not None:
-        gains = np.ascontiguousarray(gains, dtype=np.float32)
-        if gains.shape != (uni.n_instances,):
-            raise ValueError("dusp-hip: gains must have shape (n_instances=%d,)" % uni.n_instances)
+    onsets, lengths, gains = _voice_arrays(onsets, lengths, gains, uni.n_instances, n_voice, "n_instances", "the voice's %d samples" % n_voice)
     return uni, n_voice, n_total, onsets, lengths, gains, context(uni.sample_rate, device).build(uni.words, engine)
 
 
@@ -232,47 +256,33 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
 
     fracs: as render_piece's — voice k starts at onsets[k] + fracs[k] samples; the piece's call with the score as its one part, as
     with pans."""
+    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs)
+
+
+def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, pcm=None):
+    """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
     if pans is not None or fracs is not None:
-        return render_piece(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, _one_part=True, fracs=fracs)
+        return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, True, fracs, pcm)
+    if pcm is not None:
+        _check_pcm(*pcm)
     uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
-    result = ChannelData()
-    result.sampleRate = uni.sample_rate
     try:
-        if n_total > 0:
-            result.extend(prog.render_score(n_voice, n_total, uni.n_instances, onsets, lengths, uni.params, gains, tile_instances))
+        return _delivered(pcm, uni.sample_rate, n_total, prog.n_out_channels,
+                          lambda format, normalise: prog.render_score(n_voice, n_total, uni.n_instances, onsets, lengths, uni.params, gains, tile_instances, format, normalise))
     finally:
         prog.close()
-    return result
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
                      tile_instances=0, pans=None, fracs=None):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
-    if pans is not None or fracs is not None:
-        return render_piece_pcm(outlets, onsets, _score_voice_duration(voice_duration), duration, bit_depth, normalise, lengths, gains, engine, device, 0, pans, _one_part=True,
-                                fracs=fracs)
-    if bit_depth not in _PCM_FORMAT:
-        raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
-    if normalise not in (0, 1, 2):
-        raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
-    uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
-    try:
-        if n_total == 0:
-            data, peak = wav.encode_frames(np.zeros((prog.n_out_channels, n_total), dtype=np.float32), bit_depth, normalise)
-        else:
-            data, peak = prog.render_score(n_voice, n_total, uni.n_instances, onsets, lengths, uni.params, gains, tile_instances, _PCM_FORMAT[bit_depth], normalise)
-    finally:
-        prog.close()
-    return PcmData(data, bit_depth, uni.sample_rate, peak)
+    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
                      tile_instances=0, pans=None, fracs=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
-    pcm = render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs)
-    if bit_depth == 32:
-        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
-    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+    return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs), bit_depth)
 
 
 class PieceParts:
@@ -349,15 +359,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None
     if min(voice_samples) == 0:
         raise descriptor.DuspError("dusp-hip: voice_duration must cover at least one sample")
     n_total = _n_samples(duration, rate)
-    onsets = runtime._whole_samples(onsets, n, "onsets")
-    if lengths is not None:
-        lengths = runtime._whole_samples(lengths, n, "lengths")
-        if np.any(lengths < 0) or np.any(lengths > np.array(voice_samples)):
-            raise ValueError("dusp-hip: lengths must lie in 0 .. the voice's own samples")
-    if gains is not None:
-        gains = np.ascontiguousarray(gains, dtype=np.float32)
-        if gains.shape != (n,):
-            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+    onsets, lengths, gains = _voice_arrays(onsets, lengths, gains, n, np.array(voice_samples), "voices", "the voice's own samples")
     if pans is not None:
         pans, _ = runtime.pan_arrays(pans, n)
     if fracs is not None:
@@ -399,36 +401,28 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     reference renders for `Delay(., onsets[k] + fracs[k], maxDelay)`, whose two taps carry the weights 1 - frac and frac (mix.two_tap_terms;
     DESIGN.md 6.11 says where the reference's ring departs from it).  dusp_amd.split_onsets makes both arrays from positions in samples
     written as real numbers.  A voice with a fraction covers one more sample; all fractions zero gives the bits of the call without."""
-    grouped, n_total, onsets, lengths, gains, channels, pans, fracs = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, _one_part, fracs)
-    result = ChannelData()
-    result.sampleRate = grouped.sample_rate
-    if n_total > 0:
-        result.extend(_render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, pans=pans, fracs=fracs))
-    return result
+    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs)
+
+
+def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, one_part, fracs, pcm=None):
+    """render_piece (pcm None) and render_piece_pcm (pcm = (bit_depth, normalise))"""
+    if pcm is not None:
+        _check_pcm(*pcm)
+    grouped, n_total, onsets, lengths, gains, channels, pans, fracs = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, one_part, fracs)
+    return _delivered(pcm, grouped.sample_rate, n_total, channels,
+                      lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format, normalise, pans=pans, fracs=fracs))
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
                      tile_bytes=0, pans=None, _one_part=False, fracs=None):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
-    if bit_depth not in _PCM_FORMAT:
-        raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
-    if normalise not in (0, 1, 2):
-        raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
-    grouped, n_total, onsets, lengths, gains, channels, pans, fracs = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, _one_part, fracs)
-    if n_total == 0:
-        data, peak = wav.encode_frames(np.zeros((channels, 0), dtype=np.float32), bit_depth, normalise)
-    else:
-        data, peak = _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, _PCM_FORMAT[bit_depth], normalise, pans=pans, fracs=fracs)
-    return PcmData(data, bit_depth, grouped.sample_rate, peak)
+    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
                      tile_bytes=0, pans=None, fracs=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
-    pcm = render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs)
-    if bit_depth == 32:
-        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
-    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+    return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs), bit_depth)
 
 
 class PcmData:
@@ -451,10 +445,7 @@ def render_pcm(outlet, duration=1, bit_depth=16, normalise=0, engine=runtime.ENG
     bytes per sample are downloaded.  A circuit with scheduled events is rendered in segments that arrive as f32 on the host
     (renderChannelData); those are encoded here by the same contract (wav.encode_frames), the peak taken over the whole render.  The
     bytes are the same either way.  Like renderChannelData this consumes the circuit."""
-    if bit_depth not in _PCM_FORMAT:
-        raise descriptor.DuspError("dusp-hip: bit depth must be 16, 24 or 32")
-    if normalise not in (0, 1, 2):
-        raise descriptor.DuspError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)")
+    _check_pcm(bit_depth, normalise)
     first = descriptor.extract(outlet, allow_events=True)
     n = _n_samples(duration, first.sample_rate)
     if n > 0 and not first.circuit.events:
@@ -473,7 +464,4 @@ def render_pcm(outlet, duration=1, bit_depth=16, normalise=0, engine=runtime.ENG
 
 def render_wav(outlet, duration=1, bit_depth=16, normalise=0, engine=runtime.ENGINE_AUTO, device=-1):
     """A complete RIFF/WAVE file (bytes) of the render: render_pcm plus the header (wav.encode_wav)."""
-    pcm = render_pcm(outlet, duration, bit_depth, normalise, engine, device)
-    if bit_depth == 32:
-        return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
-    return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
+    return _wav(render_pcm(outlet, duration, bit_depth, normalise, engine, device), bit_depth)

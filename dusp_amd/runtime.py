@@ -4,12 +4,12 @@ There is deliberately no CPU fallback here: if the HIP library is missing or no
 GPU is usable, every entry point raises.
 """
 import ctypes
-import math
 import threading
 import os
 
 import numpy as np
 
+from .mix import _whole, check_fracs, pan_comp
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -133,7 +133,7 @@ def pan_arrays(pans, n, comp=None):
     if not np.all(np.isfinite(pans)):
         raise ValueError("dusp-hip: the pan of voice %d is not finite" % int(np.argmax(~np.isfinite(pans))))
     if comp is None:
-        comp = np.array([math.pow(10, ((1 - abs(float(p))) * 1.5) / 20) for p in pans], dtype=np.float64)
+        comp = pan_comp(pans)
     else:
         comp = np.ascontiguousarray(comp, dtype=np.float64)
         if comp.shape != (n,):
@@ -144,7 +144,6 @@ def pan_arrays(pans, n, comp=None):
 def frac_arrays(fracs, n):
     """fracs of n voices -> float64 [n]: checked — one finite fraction of a sample a voice, 0 <= f < 1 — by the strings the library uses
     (dusp_amd/mix.py check_fracs).  Needs no device."""
-    from .mix import check_fracs
     return check_fracs(fracs, n)
 
 
@@ -200,13 +199,7 @@ def _pcm_format(format):
 
 def _whole_samples(values, n, name):
     """onsets / lengths of a score -> contiguous int64 [n]: in samples, whole numbers (a fraction is refused)"""
-    a = np.asarray(values)
-    if a.shape != (n,):
-        raise ValueError("dusp-hip: %s must have shape (n_instances=%d,)" % (name, n))
-    if a.dtype.kind not in "iu":
-        if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(np.abs(a) >= 2.0 ** 63):
-            raise ValueError("dusp-hip: %s are in samples, whole numbers: a fraction (or what is no number) is refused" % name)
-    return np.ascontiguousarray(a, dtype=np.int64)
+    return _whole(values, n, name, "n_instances", "dusp-hip: %s are in samples, whole numbers: a fraction (or what is no number) is refused")
 
 
 def _score_rows(rows, row_samples, onsets, lengths):
@@ -221,6 +214,38 @@ def _score_rows(rows, row_samples, onsets, lengths):
     if lengths is not None:
         lengths = _whole_samples(lengths, n, "lengths")
     return pointers, samples, onsets, lengths
+
+
+def _ptr(a, some=True):
+    """the address of a host array for the library: NULL for None, and where the caller has nothing to be read (a call without voices)"""
+    return a.ctypes.data if a is not None and some else None
+
+
+def _gains_table(gains, n, noun):
+    """gains -> contiguous float32 [n], checked, or None; noun: what the caller counts (n_instances, voices)"""
+    if gains is not None:
+        gains = np.ascontiguousarray(gains, dtype=np.float32)
+        if gains.shape != (n,):
+            raise ValueError("dusp-hip: gains must have shape (%s=%d,)" % (noun, n))
+    return gains
+
+
+def _pcm_out(ctx, format, normalise, frames, pinned, batch=None):
+    """What a delivering call hands the library -> (DUSP_PCM_* or 0, normalise, the array for the result, the array for the peaks or
+    None).  frames: (samples, channels) of one render; batch: so many of them (Program.render_pcm), each with a peak of its own.
+    format None, for one render: planar float32 [channels, samples], nothing normalised and no peak.  Else format and normalise
+    are checked, and the frames are int16, uint8 (.., 3) or float32."""
+    if format is None and batch is None:
+        return 0, 0, ctx.host_empty(frames[::-1], pinned), None
+    fmt = _pcm_format(format)
+    if fmt not in PCM_BYTES:
+        raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
+    if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
+        raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
+    if batch is not None:
+        frames = (batch,) + frames
+    out = ctx.host_empty_bytes(frames + (3,) if fmt == PCM_S24 else frames, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
+    return fmt, int(normalise), out, np.empty(1 if batch is None else batch, dtype=np.float32)
 
 
 class Context:
@@ -322,11 +347,9 @@ class Context:
         and lengths are HOST arrays of whole numbers of samples (any sign; lengths in 0 .. n_voice_samples, None: whole voices): the
         launch's plan is made on the host.  d_gains, d_init (which may be d_out) and raw as for mix()."""
         onsets = _whole_samples(onsets, n_instances, "onsets")
-        lp = None
         if lengths is not None:
             lengths = _whole_samples(lengths, n_instances, "lengths")
-            lp = lengths.ctypes.data
-        self._check(self._L.dusp_score_device(self._h, d_planar, n_instances, n_channels, n_voice_samples, onsets.ctypes.data if n_instances else None, lp, d_gains,
+        self._check(self._L.dusp_score_device(self._h, d_planar, n_instances, n_channels, n_voice_samples, _ptr(onsets, n_instances), _ptr(lengths), d_gains,
                                               n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def score_rows_device(self, rows, row_samples, n_channels, onsets, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, stream=None):
@@ -336,9 +359,8 @@ class Context:
         Everything else as score_device; score_last_ms() reports the call."""
         n = len(rows)
         pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
-        lp = lengths.ctypes.data if lengths is not None else None
-        self._check(self._L.dusp_score_rows_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, n_channels,
-                                                   onsets.ctypes.data if n else None, lp, d_gains, n_total_samples, d_init, int(bool(raw)), d_out, stream))
+        self._check(self._L.dusp_score_rows_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, n_channels, _ptr(onsets, n), _ptr(lengths), d_gains, n_total_samples,
+                                                   d_init, int(bool(raw)), d_out, stream))
 
     def score_rows_pan(self, rows, row_samples, onsets, pans, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, comp=None, stream=None):
         """score_rows_device over MONO rows, voice k panned to pans[k] where it is added to a timeline of TWO channels
@@ -348,10 +370,8 @@ class Context:
         n = len(rows)
         pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
         pans, comp = pan_arrays(pans, n, comp)
-        lp = lengths.ctypes.data if lengths is not None else None
-        self._check(self._L.dusp_score_rows_pan_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, onsets.ctypes.data if n else None,
-                                                       lp, d_gains, pans.ctypes.data if n else None, comp.ctypes.data if n else None, n_total_samples, d_init, int(bool(raw)),
-                                                       d_out, stream))
+        self._check(self._L.dusp_score_rows_pan_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, _ptr(onsets, n), _ptr(lengths), d_gains, _ptr(pans, n), _ptr(comp, n),
+                                                       n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def score_rows_frac(self, rows, row_samples, n_channels, onsets, fracs, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, pans=None,
                         comp=None, stream=None):
@@ -364,16 +384,14 @@ class Context:
         pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
         if fracs is not None:
             fracs = frac_arrays(fracs, n)
-        pp = cp = None
         if pans is not None:
             pans, comp = pan_arrays(pans, n, comp)
             if n == 0:  # (no voices: `|| 0`, or a copy, of both channels of d_init; the pointer only says "two channels")
                 pans, comp = np.zeros(1, dtype=np.float32), np.ones(1, dtype=np.float64)
-            pp, cp = pans.ctypes.data, comp.ctypes.data
-        lp = lengths.ctypes.data if lengths is not None else None
-        self._check(self._L.dusp_score_rows_frac_device(self._h, pointers.ctypes.data if n else None, samples.ctypes.data if n else None, n, n_channels,
-                                                        onsets.ctypes.data if n else None, fracs.ctypes.data if fracs is not None and n else None, lp, d_gains, pp, cp,
-                                                        n_total_samples, d_init, int(bool(raw)), d_out, stream))
+        else:
+            comp = None
+        self._check(self._L.dusp_score_rows_frac_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, n_channels, _ptr(onsets, n), _ptr(fracs, n), _ptr(lengths), d_gains,
+                                                        _ptr(pans), _ptr(comp), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
                            pans=None, fracs=None):
@@ -394,59 +412,35 @@ class Context:
             raise ValueError("dusp-hip: part_of names a part, 0 .. %d, for each voice" % (len(parts) - 1))
         part_of = np.ascontiguousarray(part_of, dtype=np.uint32)
         onsets = _whole_samples(onsets, n, "onsets")
-        lp = gp = None
         if lengths is not None:
             lengths = _whole_samples(lengths, n, "lengths")
-            lp = lengths.ctypes.data
-        if gains is not None:
-            gains = np.ascontiguousarray(gains, dtype=np.float32)
-            if gains.shape != (n,):
-                raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
-            gp = gains.ctypes.data
+        gains = _gains_table(gains, n, "voices")
         if int(tile_bytes) < 0:
             raise ValueError("dusp-hip: tile_bytes must be 0 (the default tile) or a number of bytes")
         table = (ScorePart * len(parts))()
         keep = []  # (the parameter tables, alive across the call)
         for p, (prog, n_voice_samples, n_instances, params) in enumerate(parts):
-            pp = None
-            if prog.n_params:
-                params = np.ascontiguousarray(params, dtype=np.float32)
-                if params.shape != (prog.n_params, n_instances):
-                    raise ValueError("dusp-hip: the params of part %d must have shape (n_params=%d, n_instances=%d)" % (p, prog.n_params, n_instances))
-                keep.append(params)
-                pp = params.ctypes.data
-            table[p] = ScorePart(prog._h, n_instances, n_voice_samples, pp)
+            keep.append(prog._params_table(params, n_instances, "dusp-hip: the params of part %d must have shape" % p))
+            table[p] = ScorePart(prog._h, n_instances, n_voice_samples, _ptr(keep[-1]))
         n_ch = parts[0][0].n_out_channels
         entry = self._L.dusp_render_host_score_parts
-        args = [table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, lp, gp, n_total_samples, int(tile_bytes)]
+        args = [table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, _ptr(lengths), _ptr(gains), n_total_samples, int(tile_bytes)]
         if fracs is not None:
             fracs = frac_arrays(fracs, n)
+        comp = None
         if pans is not None:
             pans, comp = pan_arrays(pans, n)
             n_ch = 2  # (parts that are not mono: the library refuses them)
-        pan_args = (pans.ctypes.data, comp.ctypes.data) if pans is not None else (None, None)
         if fracs is not None:  # (the fractions behind the onsets; the pans and their compensation, or two NULLs, behind the gains)
             entry = self._L.dusp_render_host_score_parts_frac
-            args[7:7] = pan_args
+            args[7:7] = (_ptr(pans), _ptr(comp))
             args[5:5] = (fracs.ctypes.data,)
         elif pans is not None:  # (the pans and their compensation behind the gains)
             entry = self._L.dusp_render_host_score_parts_pan
-            args[7:7] = pan_args
-        pcm = format is not None  # (else planar f32, and no peak)
-        fmt = 0
-        if pcm:
-            fmt = _pcm_format(format)
-            if fmt not in PCM_BYTES:
-                raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
-            if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
-                raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
-            shape = (n_total_samples, n_ch)
-            out = self.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
-        else:
-            out = self.host_empty((n_ch, n_total_samples), pinned)
-        peak = np.empty(1, dtype=np.float32)
-        self._check(entry(*args, fmt, int(normalise) if pcm else 0, out.ctypes.data, peak.ctypes.data if pcm else None))
-        return (out, peak[0]) if pcm else out
+            args[7:7] = (_ptr(pans), _ptr(comp))
+        fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
+        self._check(entry(*args, fmt, normalise, out.ctypes.data, _ptr(peak)))
+        return out if peak is None else (out, peak[0])
 
     def score_last_ms(self):
         """-> (kernel_ms, plan_ms, upload_ms) of the most recent score_device call (dusp_score_last_ms; waits for that launch): the kernel
@@ -507,18 +501,24 @@ class Program:
         self.ctx._check(self._L.dusp_program_continue(self._h, words.ctypes.data, words.size))
         self._read_info()
 
+    def _params_table(self, params, n_instances, must="params must have shape"):
+        """the parameter table of a call -> contiguous float32 [n_params, n_instances], checked (must: how the refusal begins), or None
+        for a program without parameters"""
+        if not self.n_params:
+            return None
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        if params.shape != (self.n_params, n_instances):
+            raise ValueError("%s (n_params=%d, n_instances=%d)" % (must, self.n_params, n_instances))
+        return params
+
     def render(self, n_samples, n_instances=1, params=None, interleaved=False, inputs=None, pinned=None):
         """Host round trip: float32 [n_instances, n_out_channels, n_samples], or — interleaved — frames
         [n_instances, n_samples, n_out_channels] (the RenderStream / WAV layout, transposed on the device).
         inputs: the host-generated streams of this call, float32 [n_inputs, n_instances, n_samples] (programs with INPUT units)."""
         shape = (n_instances, n_samples, self.n_out_channels) if interleaved else (n_instances, self.n_out_channels, n_samples)
         out = self.ctx.host_empty(shape, pinned)  # pinned=None: by size; False: pageable memory (the staged download)
-        pp = None
-        if self.n_params:
-            params = np.ascontiguousarray(params, dtype=np.float32)
-            if params.shape != (self.n_params, n_instances):
-                raise ValueError("params must have shape (n_params=%d, n_instances=%d)" % (self.n_params, n_instances))
-            pp = params.ctypes.data
+        params = self._params_table(params, n_instances)
+        pp = _ptr(params)
         if self.n_inputs:
             inputs = np.ascontiguousarray(inputs, dtype=np.float32)
             if inputs.shape != (self.n_inputs, n_instances, n_samples):
@@ -534,26 +534,15 @@ class Program:
         and 2 (s16) or 3 (s24) bytes per sample are downloaded.  Returns (data, peaks): data int16 [n_instances, n_samples, n_out_channels]
         for "s16", uint8 [.., .., .., 3] (little-endian 24-bit) for "s24", float32 for "f32"; peaks float32 [n_instances], every instance's
         max |x| before the gain.  normalise: 0 none, 1 shrink only an instance that would clip, 2 every instance to full scale."""
-        fmt = _pcm_format(format)
-        if fmt not in PCM_BYTES:
-            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
-        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
-            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
-        shape = (n_instances, n_samples, self.n_out_channels)
-        out = self.ctx.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
-        peaks = np.empty(n_instances, dtype=np.float32)
-        pp = ip = None
-        if self.n_params:
-            params = np.ascontiguousarray(params, dtype=np.float32)
-            if params.shape != (self.n_params, n_instances):
-                raise ValueError("params must have shape (n_params=%d, n_instances=%d)" % (self.n_params, n_instances))
-            pp = params.ctypes.data
+        fmt, normalise, out, peaks = _pcm_out(self.ctx, format, normalise, (n_samples, self.n_out_channels), pinned, batch=n_instances)
+        params = self._params_table(params, n_instances)
+        ip = None
         if self.n_inputs:
             inputs = np.ascontiguousarray(inputs, dtype=np.float32)
             if inputs.shape != (self.n_inputs, n_instances, n_samples):
                 raise ValueError("inputs must have shape (n_inputs=%d, n_instances=%d, n_samples=%d)" % (self.n_inputs, n_instances, n_samples))
             ip = inputs.ctypes.data
-        self.ctx._check(self._L.dusp_render_host_pcm(self._h, n_instances, n_samples, pp, ip, fmt, int(normalise), out.ctypes.data, peaks.ctypes.data))
+        self.ctx._check(self._L.dusp_render_host_pcm(self._h, n_instances, n_samples, _ptr(params), ip, fmt, normalise, out.ctypes.data, peaks.ctypes.data))
         return out, peaks
 
     def render_mix(self, n_samples, n_instances, params=None, gains=None, tile_instances=0, format=None, normalise=NORMALISE_NONE, pinned=None):
@@ -563,33 +552,12 @@ class Program:
         and one instance's worth of samples is downloaded.  gains: float32 [n_instances], a factor per instance.  tile_instances: 0 lets the
         library size the tile.  format None: float32 [n_out_channels, n_samples]; "s16" | "s24" | "f32": (data, peak) as render_pcm
         delivers one instance — data [n_samples, n_out_channels(, 3)] — with the mix's peak as one float32."""
-        pp = gp = None
-        if self.n_params:
-            params = np.ascontiguousarray(params, dtype=np.float32)
-            if params.shape != (self.n_params, n_instances):
-                raise ValueError("params must have shape (n_params=%d, n_instances=%d)" % (self.n_params, n_instances))
-            pp = params.ctypes.data
-        if gains is not None:
-            gains = np.ascontiguousarray(gains, dtype=np.float32)
-            if gains.shape != (n_instances,):
-                raise ValueError("dusp-hip: gains must have shape (n_instances=%d,)" % n_instances)
-            gp = gains.ctypes.data
+        params, gains = self._params_table(params, n_instances), _gains_table(gains, n_instances, "n_instances")
         if int(tile_instances) < 0:
             raise ValueError("dusp-hip: tile_instances must be 0 (the default tile) or at least 1")
-        if format is None:
-            out = self.ctx.host_empty((self.n_out_channels, n_samples), pinned)
-            self.ctx._check(self._L.dusp_render_host_mix(self._h, n_instances, n_samples, pp, gp, int(tile_instances), 0, 0, out.ctypes.data, None))
-            return out
-        fmt = _pcm_format(format)
-        if fmt not in PCM_BYTES:
-            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
-        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
-            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
-        shape = (n_samples, self.n_out_channels)
-        out = self.ctx.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
-        peak = np.empty(1, dtype=np.float32)
-        self.ctx._check(self._L.dusp_render_host_mix(self._h, n_instances, n_samples, pp, gp, int(tile_instances), fmt, int(normalise), out.ctypes.data, peak.ctypes.data))
-        return out, peak[0]
+        fmt, normalise, out, peak = _pcm_out(self.ctx, format, normalise, (n_samples, self.n_out_channels), pinned)
+        self.ctx._check(self._L.dusp_render_host_mix(self._h, n_instances, n_samples, _ptr(params), _ptr(gains), int(tile_instances), fmt, normalise, out.ctypes.data, _ptr(peak)))
+        return out if peak is None else (out, peak[0])
 
     def render_score(self, n_voice_samples, n_total_samples, n_instances, onsets, lengths=None, params=None, gains=None, tile_instances=0, format=None,
                      normalise=NORMALISE_NONE, pinned=None):
@@ -599,38 +567,15 @@ class Program:
         samples (onsets of any sign; lengths in 0 .. n_voice_samples clip a voice, None: whole voices).  gains, tile_instances, format,
         normalise and what is returned: as render_mix, over the timeline."""
         onsets = _whole_samples(onsets, n_instances, "onsets")
-        pp = gp = lp = None
         if lengths is not None:
             lengths = _whole_samples(lengths, n_instances, "lengths")
-            lp = lengths.ctypes.data
-        if self.n_params:
-            params = np.ascontiguousarray(params, dtype=np.float32)
-            if params.shape != (self.n_params, n_instances):
-                raise ValueError("params must have shape (n_params=%d, n_instances=%d)" % (self.n_params, n_instances))
-            pp = params.ctypes.data
-        if gains is not None:
-            gains = np.ascontiguousarray(gains, dtype=np.float32)
-            if gains.shape != (n_instances,):
-                raise ValueError("dusp-hip: gains must have shape (n_instances=%d,)" % n_instances)
-            gp = gains.ctypes.data
+        params, gains = self._params_table(params, n_instances), _gains_table(gains, n_instances, "n_instances")
         if int(tile_instances) < 0:
             raise ValueError("dusp-hip: tile_instances must be 0 (the default tile) or at least 1")
-        call = self._L.dusp_render_host_score
-        if format is None:
-            out = self.ctx.host_empty((self.n_out_channels, n_total_samples), pinned)
-            self.ctx._check(call(self._h, n_instances, n_voice_samples, n_total_samples, pp, gp, onsets.ctypes.data, lp, int(tile_instances), 0, 0, out.ctypes.data, None))
-            return out
-        fmt = _pcm_format(format)
-        if fmt not in PCM_BYTES:
-            raise ValueError('dusp-hip: format must be "s16", "s24" or "f32", not %r' % (format,))
-        if normalise not in (NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL):
-            raise ValueError("dusp-hip: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale), not %r" % (normalise,))
-        shape = (n_total_samples, self.n_out_channels)
-        out = self.ctx.host_empty_bytes(shape + (3,) if fmt == PCM_S24 else shape, {PCM_S16: np.int16, PCM_S24: np.uint8, PCM_F32: np.float32}[fmt], pinned)
-        peak = np.empty(1, dtype=np.float32)
-        self.ctx._check(call(self._h, n_instances, n_voice_samples, n_total_samples, pp, gp, onsets.ctypes.data, lp, int(tile_instances), fmt, int(normalise),
-                             out.ctypes.data, peak.ctypes.data))
-        return out, peak[0]
+        fmt, normalise, out, peak = _pcm_out(self.ctx, format, normalise, (n_total_samples, self.n_out_channels), pinned)
+        self.ctx._check(self._L.dusp_render_host_score(self._h, n_instances, n_voice_samples, n_total_samples, _ptr(params), _ptr(gains), onsets.ctypes.data, _ptr(lengths),
+                                                       int(tile_instances), fmt, normalise, out.ctypes.data, _ptr(peak)))
+        return out if peak is None else (out, peak[0])
 
     def render_device(self, n_samples, n_instances, d_params, d_out, stream=None, d_inputs=None):
         """Asynchronous render between device pointers (ints), e.g. torch tensors' data_ptr()."""
