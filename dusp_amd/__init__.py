@@ -6,7 +6,7 @@ ctypes binding of the HIP library (runtime.py).  Device side: dusp_amd/csrc/.
 """
 from . import config, descriptor, mix, quick, runtime  # noqa: F401
 from .descriptor import DuspError  # noqa: F401
-from .mix import split_onsets  # noqa: F401
+from .mix import space_taps, split_onsets  # noqa: F401
 from .graph import (Abs, AllPass, Circuit, CircleBuffer, CircleBufferReader, CircleBufferWriter, Clip, CombFilter, DecibelToScaler, Delay,  # noqa: F401
                     Divide, Filter, FixedDelay, FixedMultiply, Gain, MonoDelay, MultiChannelOsc, ReadBackDelay, HardClipAbove, HardClipBelow, Multiply, Osc, PolarityInvert, Pow,
                     Ramp, Repeater, SecondsToSamples, SemitoneToRatio, Subtract, Sum, Unit,

@@ -1,6 +1,7 @@
-// abi_score.hip — the C ABI (include/dusp_hip.h): voices mixed at per-voice onsets into a timeline (score_plan.hpp and the four score
+// abi_score.hip — the C ABI (include/dusp_hip.h): voices mixed at per-voice onsets into a timeline (score_plan.hpp and the five score
 // engines): the plans' image on the device, the one launch path, the device entries (dusp_score_device, dusp_score_rows_device and its
-// pan and frac forms) and the host round trips (dusp_render_host_score, dusp_render_host_score_parts and its pan and frac forms).
+// pan, frac and space forms) and the host round trips (dusp_render_host_score, dusp_render_host_score_parts and its pan, frac and space
+// forms).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -13,8 +14,15 @@
 // ---- the plans of a call: an image on the host, uploaded once, and one description per launch ----
 
 // which kernel a launch is: voices of one contiguous batch (score_engine.hip; dusp_amd/mix.py score_chain is the contract), rows of their
-// own (score_rows_engine.hip; score_chain_rows), or mono rows placed in the stereo field (score_pan_engine.hip; score_chain_rows_panned)
-enum class ScoreKind { contiguous, rows, pan };
+// own (score_rows_engine.hip; score_chain_rows), mono rows placed in the stereo field (score_pan_engine.hip; score_chain_rows_panned), or
+// mono rows placed in a space, a delay and a gain per speaker (score_space_engine.hip; score_chain_rows_placed)
+enum class ScoreKind { contiguous, rows, pan, space };
+
+// the taps of a space call: h_delays and h_gains f64 [voice][speaker] on the host (checked: check_taps)
+struct ScoreTaps {
+    size_t n_speakers;
+    const double *h_delays, *h_gains;
+};
 
 // one launch's plan inside the context's image
 struct ScoreLaunch {
@@ -26,6 +34,7 @@ struct ScoreLaunch {
     size_t pan_at = 0;  // a panned launch: byte offset of its voices' coefficients (dusp::ScorePan), behind the plan
     bool frac = false;   // some listed voice starts between samples: the launch is score_frac_engine.hip's, plain rows or panned ...
     size_t frac_at = 0;  // ... and this the byte offset of its voices' weights (dusp::ScoreFrac), behind the plan
+    size_t space_at = 0;  // a space launch: byte offset of its voices' taps (dusp::ScoreSpaceTap, [voice][speaker]), behind the plan
     explicit ScoreLaunch(ScoreKind kind_, uint64_t n_total = 0) : kind(kind_), w_hi(n_total) {}  // (n_total: over the whole timeline)
 };
 
@@ -93,14 +102,21 @@ static int score_voices_add(dusp_ctx *ctx, const char *who, const int64_t *h_ons
 // the launch are as without.
 static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n,
                           size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L, std::vector<unsigned char> *listed = nullptr,
-                          const double *h_fracs = nullptr) {
+                          const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr) {
     dusp::ScoreRowsPlan P;
-    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, h_fracs);
+    std::vector<dusp::ScoreSpaceTap> T;  // (space: the voices' taps, [voice][speaker], 32 bytes each on top of the budget as the weights are)
+    if (taps) {
+        T.resize(n * taps->n_speakers);
+        for (size_t j = 0; j < T.size(); j++) T[j] = dusp::score_space_tap(taps->h_delays[j], taps->h_gains[j]);
+    }
+    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, h_fracs, taps ? T.data() : nullptr,
+                                              taps ? taps->n_speakers : 0);
     if (bad >= 0)
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
                                         ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
     score_image_add(ctx, P, n, L);
-    for (size_t k = 0; k < n && L.any && !L.frac; k++) L.frac = P.voices[k].hi > P.voices[k].lo && P.voices[k].pad != 0;
+    if (taps && L.any) L.space_at = score_image_append<dusp::ScoreSpaceTap>(ctx, T.size(), [&](size_t j) { return T[j]; });
+    for (size_t k = 0; k < n && L.any && !L.frac && !taps; k++) L.frac = P.voices[k].hi > P.voices[k].lo && P.voices[k].pad != 0;
     if (L.frac) L.frac_at = score_image_append<dusp::ScoreFrac>(ctx, n, [&](size_t k) { return dusp::score_frac_weights(h_fracs[k]); });
     if (listed) {
         listed->resize(n);
@@ -154,12 +170,15 @@ static int score_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, 
     const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices * record) : nullptr, *d_entries = L.any ? d_block_first + L.n_block_first : nullptr;
     const dusp::ScoreRow *d_rows = (const dusp::ScoreRow *)d_voices;
     const dusp::ScorePan *d_pans = L.any && L.kind == ScoreKind::pan ? (const dusp::ScorePan *)(d_image + L.pan_at) : nullptr;
-    if (L.any && L.frac)  // (score_frac_engine.hip: plain rows of n_channels, or — d_pans — panned mono rows)
+    if (L.any && L.kind == ScoreKind::space)  // (score_space_engine.hip: mono rows into a timeline of n_channels speakers)
+        HIP_TRY(ctx, dusp::launch_score_space(d_gains, (const dusp::ScoreSpaceTap *)(d_image + L.space_at), d_rows, d_block_first, d_entries, d_init, d_out, (uint32_t)n_channels,
+                                              n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
+    else if (L.any && L.frac)  // (score_frac_engine.hip: plain rows of n_channels, or — d_pans — panned mono rows)
         HIP_TRY(ctx, dusp::launch_score_frac(d_gains, d_pans, (const dusp::ScoreFrac *)(d_image + L.frac_at), d_rows, d_block_first, d_entries, d_init, d_out,
                                              L.kind == ScoreKind::pan ? 1u : (uint32_t)n_channels, n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
     else if (L.kind == ScoreKind::pan)
         HIP_TRY(ctx, dusp::launch_score_pan(d_gains, d_pans, d_rows, d_block_first, d_entries, d_init, d_out, n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
-    else if (L.kind == ScoreKind::rows)
+    else if (L.kind == ScoreKind::rows || L.kind == ScoreKind::space)  // (space without voices: `|| 0`, or a copy, of d_init's channels)
         HIP_TRY(ctx, dusp::launch_score_rows(d_gains, d_rows, d_block_first, d_entries, d_init, d_out, (uint32_t)n_channels, n_total, L.w_lo, L.w_hi, L.block_shift,
                                              L.first_block, raw, stream));
     else
@@ -222,6 +241,25 @@ static int check_fracs(dusp_ctx *ctx, const char *who, const double *h_fracs, si
     return DUSP_OK;
 }
 
+// the taps of n voices at n_speakers speakers, checked before anything renders
+static int check_taps(dusp_ctx *ctx, const char *who, const double *h_delays, const double *h_gains, size_t n, size_t n_speakers, size_t n_total) {
+    const std::string w(who);
+    if (n_speakers < 1 || n_speakers > dusp::kScoreSpaceChannelsMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a Space has 1 .. 8 speakers, not " + std::to_string(n_speakers));
+    if (n && (!h_delays || !h_gains)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the taps' delays or gains are NULL");
+    if (n_speakers * n_total > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": speakers x timeline samples must not exceed 2^31: score such a piece speaker by speaker or in windows of the timeline");
+    for (size_t k = 0; k < n; k++)
+        for (size_t c = 0; c < n_speakers; c++) {
+            const double D = h_delays[k * n_speakers + c], G = h_gains[k * n_speakers + c];
+            const std::string at = " of voice " + std::to_string(k) + " at speaker " + std::to_string(c);
+            if (!std::isfinite(D)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the delay" + at + " is not finite");
+            if (D < 0.0 || D > (double)dusp::kScoreSpaceShiftMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the delay" + at + " is outside [0, 2^24] samples");
+            if (!std::isfinite(G)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the gain" + at + " is not finite");
+        }
+    return DUSP_OK;
+}
+
 // ---- device entries ----
 
 extern "C" {
@@ -252,15 +290,17 @@ int dusp_score_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, 
     });
 }
 
-// dusp_score_rows_device, (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device, and (h_fracs: onsets between
-// samples) dusp_score_rows_frac_device
+// dusp_score_rows_device, (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device, (h_fracs: onsets between
+// samples) dusp_score_rows_frac_device, and (taps: rows of one channel into a timeline of taps->n_speakers) dusp_score_rows_space_device
 static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
                              const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw,
-                             float *d_out, void *stream_, const double *h_fracs = nullptr) {
+                             float *d_out, void *stream_, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr) {
     if (!ctx) return DUSP_ERR_ARG;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
-    const size_t n_out_channels = h_pans ? 2 : n_channels;  // (the timeline's)
+    if (taps)  // (first: the timeline's channel count is theirs)
+        if (int rc = check_taps(ctx, who, taps->h_delays, taps->h_gains, n_voices, taps->n_speakers, n_total_samples)) return rc;
+    const size_t n_out_channels = taps ? taps->n_speakers : h_pans ? 2 : n_channels;  // (the timeline's)
     if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
     if (!channels_in_range(n_channels) || n_voices > (1u << 24) || !samples_in_range(n_total_samples))
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..64 channels, 0..2^24 voices and 1..2^31 samples of timeline");
@@ -278,18 +318,18 @@ static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const 
     if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_of(ctx, stream_);
-    ScoreLaunch L(h_pans ? ScoreKind::pan : ScoreKind::rows, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
+    ScoreLaunch L(taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
     return score_device_call(
         ctx, stream, n_voices != 0, L,
         [&]() {
             static_assert(sizeof(const float *) == sizeof(uint64_t), "rows are handed to the planner as 64-bit addresses");
             if (int rc = score_rows_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples, /*whole_timeline=*/true,
-                                        score_plan_budget(ctx), L, nullptr, h_fracs))
+                                        score_plan_budget(ctx), L, nullptr, h_fracs, taps))
                 return rc;
             if (h_pans) score_pans_add(ctx, h_pans, h_comp, n_voices, L);
             return (int)DUSP_OK;
         },
-        [&]() { return score_launch(ctx, L, n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream); });
+        [&]() { return score_launch(ctx, L, taps ? n_out_channels : n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream); });
     });
 }
 
@@ -368,19 +408,23 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
                              n_total_samples, d_init, raw, d_out, stream_);
 }
 
-// dusp_render_host_score_parts, (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan, and (h_fracs:
-// onsets between samples, with or without pans) dusp_render_host_score_parts_frac
+// dusp_render_host_score_parts, (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan, (h_fracs:
+// onsets between samples, with or without pans) dusp_render_host_score_parts_frac, and (taps: mono parts into a timeline of
+// taps->n_speakers channels) dusp_render_host_score_parts_space
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
-                                   int format, int normalise, void *h_out, float *h_peak, const double *h_fracs = nullptr) {
+                                   int format, int normalise, void *h_out, float *h_peak, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
-    const size_t n_ch = prog0->P.out_bufs.size(), n_out_ch = h_pans ? 2 : n_ch;  // (a voice's, the timeline's)
+    const size_t n_ch = prog0->P.out_bufs.size();  // (a voice's)
     if (!h_part_of || !h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of or h_onsets is NULL");
     if (n_voices < 1 || n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^24 voices");
+    if (taps)
+        if (int rc = check_taps(ctx, who, taps->h_delays, taps->h_gains, n_voices, taps->n_speakers, n_total_samples)) return rc;
+    const size_t n_out_ch = taps ? taps->n_speakers : h_pans ? 2 : n_ch;  // (the timeline's)
     size_t n_listed = 0;
     for (size_t p = 0; p < n_parts; p++) {
         if (!parts[p].prog) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the program of part " + std::to_string(p) + " is NULL");
@@ -388,6 +432,9 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         if (h_pans && parts[p].prog->P.out_bufs.size() != 1)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) +
                                             " output channels: a panned voice is mono");
+        if (taps && parts[p].prog->P.out_bufs.size() != 1)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) +
+                                            " output channels: a placed voice is mono");
         if (parts[p].prog->P.out_bufs.size() != n_ch)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) + " output channels, part 0 has " +
                                             std::to_string(n_ch) + ": all parts of a piece have the same number");
@@ -445,7 +492,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     }
     // every tile's plan, over the tile's union window, made up front under the call's one budget and uploaded once: the rows' addresses
     // are known, since the tile buffers stand
-    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(h_pans ? ScoreKind::pan : ScoreKind::rows));
+    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows));
     std::vector<std::vector<unsigned char>> renders(n_tiles, std::vector<unsigned char>(n_parts, 0));  // does part p render in tile i?
     const size_t tile_budget = score_plan_budget(ctx) / n_tiles;
     if (int rc = score_image_begin(ctx)) return rc;
@@ -455,13 +502,14 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         std::vector<unsigned char> listed;
         for (size_t i = 0; i < n_tiles; i++) {
             const size_t lo = starts[i], n = starts[i + 1] - lo;
+            const ScoreTaps tile_taps = taps ? ScoreTaps{taps->n_speakers, taps->h_delays + lo * taps->n_speakers, taps->h_gains + lo * taps->n_speakers} : ScoreTaps{0, nullptr, nullptr};
             rows.resize(n);
             for (size_t k = 0; k < n; k++) {
                 const size_t p = h_part_of[lo + k];
                 rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * n_ch * parts[p].n_voice_samples);
             }
             if (int rc = score_rows_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
-                                        /*whole_timeline=*/false, tile_budget, launches[i], &listed, h_fracs ? h_fracs + lo : nullptr))
+                                        /*whole_timeline=*/false, tile_budget, launches[i], &listed, h_fracs ? h_fracs + lo : nullptr, taps ? &tile_taps : nullptr))
                 return rc;
             if (h_pans) score_pans_add(ctx, h_pans + lo, h_comp ? h_comp + lo : nullptr, n, launches[i]);
             for (size_t k = 0; k < n; k++)
@@ -489,7 +537,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
             if (renders[i][p])
                 if (int rc = whole[p]->render_tile(share[p][i], share[p][i + 1] - share[p][i], parts[p].n_voice_samples)) return rc;
         const float *d_gains = h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr;
-        if (int rc = score_launch(ctx, launches[i], n_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream)) return rc;
+        if (int rc = score_launch(ctx, launches[i], taps ? n_out_ch : n_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream)) return rc;
     }
     // (`|| 0` is the rows kernel's over the timeline's channels, panned or not)
     if (int rc = score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
@@ -528,6 +576,22 @@ int dusp_render_host_score_parts_frac(const dusp_score_part *parts, size_t n_par
                                       int format, int normalise, void *h_out, float *h_peak) {
     return render_host_score_parts("dusp_render_host_score_parts_frac", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
                                    tile_bytes, format, normalise, h_out, h_peak, h_fracs);
+}
+
+int dusp_score_rows_space_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_speakers, const int64_t *h_onsets,
+                                 const int64_t *h_lengths, const float *d_gains, const double *h_delays, const double *h_tap_gains, size_t n_total_samples, const float *d_init,
+                                 int raw, float *d_out, void *stream_) {
+    const ScoreTaps taps{n_speakers, h_delays, h_tap_gains};
+    return score_rows_device(ctx, "dusp_score_rows_space_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, nullptr, nullptr, n_total_samples, d_init, raw,
+                             d_out, stream_, nullptr, &taps);
+}
+
+int dusp_render_host_score_parts_space(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                       const int64_t *h_lengths, const float *h_gains, size_t n_speakers, const double *h_delays, const double *h_tap_gains,
+                                       size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
+    const ScoreTaps taps{n_speakers, h_delays, h_tap_gains};
+    return render_host_score_parts("dusp_render_host_score_parts_space", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, nullptr, nullptr, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak, nullptr, &taps);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 // All arithmetic is in int64 and nothing overflows for any int64 onset: a voice is clipped before anything is added to its onset.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -159,6 +160,28 @@ inline int64_t score_plan(const int64_t *onsets, const int64_t *lengths, size_t 
     return -1;
 }
 
+// ---- space: a whole shift, two weights and a gain per voice and channel (score_space_engine.hip; dusp_amd/mix.py score_chain_rows_placed) ----
+
+// What the space kernel needs of voice k at channel c, made on the host from a delay D (finite, 0 <= D <= 2^24 samples) and a gain G:
+// shift = floor(D), w1 = D - shift (exact in f64), w0 = 1.0 - w1 (the IEEE subtraction itself), as the reference's MonoDelay writes a
+// sample to the ring slots floor and ceil of its delayed position with the weights 1 - frac and frac (MonoDelay.js:24-26), behind a
+// Gain whose factor is G (Gain.js:22).  w1 == 0: one tap, the voice shifted by whole samples.  The half the addresses need (w1's test,
+// the shift) is the second 16 bytes, the half only the arithmetic needs the first: two four-dword scalar loads.
+// (32 bytes on a 32-byte boundary)
+constexpr int64_t kScoreSpaceShiftMax = (int64_t)1 << 24;
+constexpr size_t kScoreSpaceChannelsMax = 8;
+struct alignas(32) ScoreSpaceTap {
+    double w0, gain;
+    double w1;
+    int64_t shift;
+};
+static_assert(sizeof(ScoreSpaceTap) == 32, "two four-dword scalar loads");
+
+inline ScoreSpaceTap score_space_tap(double delay, double gain) {
+    const double whole = std::floor(delay), frac = delay - whole;
+    return ScoreSpaceTap{1.0 - frac, gain, frac, (int64_t)whole};
+}
+
 // ---- rows: every voice a buffer of its own (score_rows_engine.hip; dusp_amd/mix.py score_chain_rows is the contract) ----
 
 // score_plan over voices of their own row lengths: row_samples[k] samples a channel (which is also the voice's channel stride) at device
@@ -171,10 +194,19 @@ inline int64_t score_plan(const int64_t *onsets, const int64_t *lengths, size_t 
 // fraction.  A voice without one has pad = 0 and is today's voice.  t_hi and the union window grow by that one sample.
 // The weights of such voices go up as a parallel array of ScoreFrac (below), 16 bytes a voice ON TOP of the plan's byte budget, which
 // counts records and lists as before.
+// taps (nullptr: none; then fracs is nullptr): voice k reaches channel c of taps_channels >= 1 behind a whole shift of taps[k *
+// taps_channels + c].shift samples, 0 <= shift <= kScoreSpaceShiftMax, through two taps where that entry's w1 is not 0 (ScoreSpaceTap
+// above; score_space_engine.hip; dusp_amd/mix.py score_chain_rows_placed).  The voice's span is the UNION over its channels,
+// [onset + min shift, onset + max(shift + len + (w1 != 0))) before clipping, and its record carries pad = len whether or not any of its
+// taps has a fraction: the kernel tells channel by channel which samples the voice covers.  A voice whose onset lies at or behind the
+// timeline's end takes no part whatever its shifts are (they are not negative), so nothing is ever added to an onset near the top of
+// int64; one far in front of sample 0 is dropped before its end is clipped.  The taps go up as a parallel array, 32 bytes a voice and
+// channel ON TOP of the plan's byte budget.
 // Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, row_samples[k]].
 // Needs n <= 2^32 - 1, row_samples and n_total <= kScoreRowMax.
 inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n, uint64_t n_total,
-                               bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P, const double *fracs = nullptr) {
+                               bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P, const double *fracs = nullptr, const ScoreSpaceTap *taps = nullptr,
+                               size_t taps_channels = 0) {
     P = ScoreRowsPlan();
     P.voices.assign(n, ScoreRow{0, 0u, 0u, 0u, 0u, 0u});
     const int64_t total = (int64_t)n_total;
@@ -183,6 +215,24 @@ inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, co
     for (size_t k = 0; k < n; k++) {
         const int64_t len = lengths ? lengths[k] : (int64_t)row_samples[k], onset = onsets[k];
         if (len < 0 || len > (int64_t)row_samples[k]) return (int64_t)k;
+        if (taps) {
+            // the union of the channels' spans, relative to the onset: [first, last), 0 <= first < last <= 2^24 + 2^31 + 1
+            int64_t first = INT64_MAX, last = 0;
+            for (size_t c = 0; c < taps_channels; c++) {
+                const ScoreSpaceTap &T = taps[k * taps_channels + c];
+                first = std::min(first, T.shift);
+                last = std::max(last, T.shift + len + (T.w1 != 0.0 ? 1 : 0));
+            }
+            if (len == 0 || onset >= total || onset <= -last) continue;  // (onset + first >= total: below, where the sum cannot overflow)
+            // here -2^33 < -last < onset < n_total <= 2^31: onset + first and onset + last cannot overflow
+            if (onset + first >= total) continue;
+            const int64_t lo = std::max<int64_t>(onset + first, 0), hi = std::min(onset + last, total);
+            P.voices[k] = ScoreRow{onset, (uint32_t)lo, (uint32_t)hi, rows ? rows[k] : 0, row_samples[k], (uint32_t)len};
+            if (first_listed == n) first_listed = k;
+            t_lo = std::min(t_lo, lo);
+            t_hi = std::max(t_hi, hi);
+            continue;
+        }
         const bool two_taps = fracs && fracs[k] != 0.0;
         // empty, behind the end, wholly in front of sample 0 (two taps: the tail tap too, onset + len + 1 <= 0)
         if (len == 0 || onset >= total || (two_taps ? onset < -len : onset <= -len)) continue;

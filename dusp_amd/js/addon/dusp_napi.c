@@ -753,6 +753,8 @@ typedef struct {
     float *pans;      /* renderPiecePan: a pan per voice and its compensation (Math.pow's), else NULL */
     double *comp;
     double *fracs;    /* renderPieceFrac: a fraction of a sample per voice, else NULL */
+    double *delays, *tap_gains; /* renderPieceSpace: a delay and a gain per voice and speaker, else NULL */
+    size_t n_speakers;
     float peak;
     int format, normalise, rc;
     char err[512];
@@ -774,6 +776,8 @@ static void piece_free(napi_env env, piece_job *j) {
     free(j->pans);
     free(j->comp);
     free(j->fracs);
+    free(j->delays);
+    free(j->tap_gains);
     free(j->out);
     free(j);
 }
@@ -791,7 +795,10 @@ static void piece_execute(napi_env env, void *data) {
         j->parts[p].prog = j->pbs[p]->prog;
     }
     if (j->rc == DUSP_OK) {
-        if (j->fracs)
+        if (j->delays)
+            j->rc = dusp_render_host_score_parts_space(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, j->n_speakers, j->delays, j->tap_gains,
+                                                       j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+        else if (j->fracs)
             j->rc = dusp_render_host_score_parts_frac(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->fracs, j->lengths, j->gains, j->pans, j->comp, j->n_total,
                                                       j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
         else if (j->pans)
@@ -849,11 +856,14 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *   -> the same over MONO parts, two channels out (dusp_render_host_score_parts_pan: voice k panned to pans[k] where it is added; comp[k] is
  *      the reference's compensation, computed by the caller with Math.pow)
  * renderPieceFrac(the same twelve, fracs Float64Array, pans Float32Array | null, comp Float64Array | null)
- *   -> either of the two with voice k starting at onsets[k] + fracs[k] samples, 0 <= fracs[k] < 1 (dusp_render_host_score_parts_frac) */
-static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions */
+ *   -> either of the two with voice k starting at onsets[k] + fracs[k] samples, 0 <= fracs[k] < 1 (dusp_render_host_score_parts_frac)
+ * renderPieceSpace(the same twelve, nSpeakers, delays Float64Array, tapGains Float64Array)
+ *   -> the first over MONO parts, nSpeakers channels out (dusp_render_host_score_parts_space: voice k heard by speaker c through the gain
+ *      tapGains[k * nSpeakers + c] and a delay of delays[k * nSpeakers + c] samples; the gains computed by the caller with Math.pow) */
+static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space */
     napi_value argv[15];
     char msg[256];
-    if (!get_args(env, info, form == 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    if (!get_args(env, info, form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
     int panned = form == 1;
     const int pans_at = form == 2 ? 13 : 12;
     if (form == 2) {
@@ -930,6 +940,7 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         else if (!(ni >= 1 && ni <= 16777216.0 && ni == (double)(size_t)ni && nv >= 1 && nv <= 2147483648.0 && nv == (double)(size_t)nv)) bad = "nInstances / nVoiceSamples out of range";
         else if (p && pi.n_out_channels != n_channels) bad = "all parts of a piece have one number of output channels";
         else if (panned && pi.n_out_channels != 1) bad = "a panned voice is mono: every part has one output channel";
+        else if (form == 3 && pi.n_out_channels != 1) bad = "a placed voice is mono: every part has one output channel";
         if (bad) break;
         n_channels = pi.n_out_channels;
         j->parts[p].n_instances = (size_t)ni;
@@ -983,6 +994,21 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         else if (!(j->fracs = (double *)malloc(n_f * sizeof(double)))) bad = "out of host memory for the fractions";
         else memcpy(j->fracs, fd, n_f * sizeof(double));
     }
+    if (!bad && form == 3) {
+        void *dd, *gd;
+        size_t n_d = 0, n_g = 0;
+        double speakers = 0;
+        if (napi_get_value_double(env, argv[12], &speakers) != napi_ok || !(speakers >= 1 && speakers <= 8 && speakers == (double)(size_t)speakers)) bad = "a Space has 1 .. 8 speakers";
+        else if (!typed_array(env, argv[13], napi_float64_array, &dd, &n_d) || n_d != n_voices * (size_t)speakers) bad = "delays must be a Float64Array of one value per voice and speaker";
+        else if (!typed_array(env, argv[14], napi_float64_array, &gd, &n_g) || n_g != n_d) bad = "tapGains must be a Float64Array of one value per voice and speaker";
+        else if (!(j->delays = (double *)malloc(n_d * sizeof(double))) || !(j->tap_gains = (double *)malloc(n_g * sizeof(double)))) bad = "out of host memory for the taps";
+        else {
+            memcpy(j->delays, dd, n_d * sizeof(double));
+            memcpy(j->tap_gains, gd, n_g * sizeof(double));
+            j->n_speakers = (size_t)speakers;
+            n_channels = (uint32_t)speakers; /* the timeline's */
+        }
+    }
     j->n_floats = (size_t)n_channels * j->n_total;
     j->n_bytes = j->n_floats * (size_t)(!j->format || j->format == DUSP_PCM_F32 ? 4 : j->format == DUSP_PCM_S16 ? 2 : 3);
     if (!bad && !(j->out = (float *)malloc(j->n_bytes + 1))) bad = "out of host memory for the PCM buffer";
@@ -1018,6 +1044,7 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
 static napi_value fn_render_piece(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 0); }
 static napi_value fn_render_piece_pan(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 1); }
 static napi_value fn_render_piece_frac(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 2); }
+static napi_value fn_render_piece_space(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 3); }
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1051,7 +1078,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
-        {"renderPieceFrac", fn_render_piece_frac},
+        {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

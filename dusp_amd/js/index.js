@@ -23,6 +23,7 @@ module.exports = {
   renderPiecePcm: renderChannelData.renderPiecePcm,
   renderPieceWav: renderChannelData.renderPieceWav,
   splitOnsets: renderChannelData.splitOnsets,
+  spaceTaps: renderChannelData.spaceTaps,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

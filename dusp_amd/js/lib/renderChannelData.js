@@ -11,6 +11,7 @@
  * (state write-back).
  */
 const native = require('./native')
+const config = require('./config')
 const { extract, unify, deviceRetrigger } = require('./extract')
 const { makeTables } = require('./wavetables')
 const { OP, UNITS } = require('./ops')
@@ -447,10 +448,13 @@ function wholeSamples(who, name, values, count) {
  * numbers of any sign (a negative onset: the voice began before the timeline; lengths clip a voice to its first samples); the
  * durations are in seconds.  gains, engine, tileInstances and the refusals are renderMix's.  pans: as renderPiece's — mono voices, two
  * channels out, through the piece's call with the score as its one part (voiceDuration is one number; tileInstances does not apply).
- * fracs: as renderPiece's — voice k starts at onsets[k] + fracs[k] samples — through the piece's call too. */
-const asPiece = (opts) => (opts.pans !== undefined && opts.pans !== null) || (opts.fracs !== undefined && opts.fracs !== null)
+ * fracs: as renderPiece's — voice k starts at onsets[k] + fracs[k] samples — through the piece's call too.
+ * places (with speakers, decibelsPerMetre, sampleDelayPerMetre): as renderPiece's — mono voices, one channel a speaker — through the
+ * piece's call too. */
+const given = (x) => x !== undefined && x !== null
+const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places)
 
-function scoreAsPiece(opts) { // renderScore with pans or fracs: the piece's call with the score as its one part
+function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
 }
 
@@ -564,8 +568,83 @@ function splitOnsets(positions) {
   return { onsets, fracs }
 }
 
+/* channels[p]: the output channels of part p's circuit.  A placed voice is mono: refused by string otherwise (twin of render.py
+ * check_space_channels). */
+function checkSpaceChannels(channels, speakers) {
+  channels.forEach((c, p) => {
+    if (c !== 1) throw 'dusp-hip: a placed voice is mono: part ' + p + ' has ' + c + ' output channels'
+  })
+  return speakers
+}
+
+const SPACE_ALONE = 'dusp-hip: places stand alone: together with pans or fracs they are refused (a sub-sample onset in front of a Space would be a second two-tap stage)'
+const SPACE_MAX_SPEAKERS = 8, SPACE_MAX_DELAY = 2 ** 24
+
+/* rows of coordinates -> [Float32Array] or null where they are no list of lists of numbers */
+function coordinateRows(rows) {
+  if (!Array.isArray(rows) || !rows.every((r) => (Array.isArray(r) || r instanceof Float32Array || r instanceof Float64Array) && Array.from(r).every((x) => typeof x === 'number'))) return null
+  return rows.map((r) => Float32Array.from(r))
+}
+
+/* places of `count` voices and the speakers -> { places, speakers }, Float32Array rows: 1 to 3 finite coordinates each, the same
+ * number; speakers undefined: the reference's stereo pair (twin of mix.py check_places, with its strings). */
+function checkPlaces(places, count, speakers) {
+  const p = coordinateRows(places), q = coordinateRows(given(speakers) ? speakers : [[-1, 0], [1, 0]])
+  if (!p || !q) throw 'dusp-hip: places and speakers are lists of 1 to 3 coordinates each'
+  const dims = p.length ? p[0].length : 0
+  if (p.length !== count || !(dims >= 1 && dims <= 3) || p.some((r) => r.length !== dims)) throw 'dusp-hip: places must have shape (voices=' + count + ', 1 .. 3 coordinates)'
+  const qdims = q.length ? q[0].length : 0
+  if (!q.length || !(qdims >= 1 && qdims <= 3) || q.some((r) => r.length !== qdims)) throw 'dusp-hip: speakers must have shape (speakers, 1 .. 3 coordinates)'
+  if (q.length > SPACE_MAX_SPEAKERS) throw 'dusp-hip: a Space has 1 .. ' + SPACE_MAX_SPEAKERS + ' speakers, not ' + q.length
+  if (qdims !== dims) throw 'dusp-hip: places have ' + dims + ' coordinates, speakers have ' + qdims + ': the same number'
+  // (finite as numbers, before the rounding to f32: a coordinate beyond the f32 range is refused as what it becomes below)
+  const rows = (v) => (given(v) ? v : [[-1, 0], [1, 0]]).map((r) => Array.from(r))
+  rows(places).forEach((r, k) => { if (!r.every(Number.isFinite)) throw 'dusp-hip: the place of voice ' + k + ' is not finite' })
+  rows(speakers).forEach((r, c) => { if (!r.every(Number.isFinite)) throw 'dusp-hip: the place of speaker ' + c + ' is not finite' })
+  return { places: p, speakers: q }
+}
+
+/* delays and gains of `count` voices at nSpeakers speakers, Float64Arrays [voice][speaker], checked by the strings the library uses
+ * (twin of mix.py check_taps) */
+function checkTaps(delays, gains, count, nSpeakers) {
+  if (!(delays instanceof Float64Array) || !(gains instanceof Float64Array) || delays.length !== count * nSpeakers || gains.length !== delays.length)
+    throw "dusp-hip: the taps' delays and gains must both have shape (voices=" + count + ', speakers)'
+  if (!(nSpeakers >= 1 && nSpeakers <= SPACE_MAX_SPEAKERS)) throw 'dusp-hip: a Space has 1 .. ' + SPACE_MAX_SPEAKERS + ' speakers, not ' + nSpeakers
+  const at = (j) => 'of voice ' + Math.floor(j / nSpeakers) + ' at speaker ' + (j % nSpeakers)
+  for (let j = 0; j < delays.length; j++) if (!Number.isFinite(delays[j])) throw 'dusp-hip: the delay ' + at(j) + ' is not finite'
+  for (let j = 0; j < delays.length; j++) if (delays[j] < 0 || delays[j] > SPACE_MAX_DELAY) throw 'dusp-hip: the delay ' + at(j) + ' is outside [0, 2^24] samples'
+  for (let j = 0; j < gains.length; j++) if (!Number.isFinite(gains[j])) throw 'dusp-hip: the gain ' + at(j) + ' is not finite'
+}
+
+/* The reference's SpaceChannel (src/patches/SpaceChannel.js) per voice and speaker, with its roundings -> { nSpeakers, delays, gains },
+ * Float64Arrays [voice][speaker], what the device takes (twin of mix.py space_taps, which spells the arithmetic out).  Every coordinate
+ * and factor is an inlet constant, rounded to f32; Subtract, VectorMagnitude and Multiply store f32; the gain is this engine's own
+ * Math.pow(10, dB / 20), as Gain.js computes it. */
+function spaceTaps(places, { speakers, decibelsPerMetre = -3, sampleDelayPerMetre, sampleRate } = {}) {
+  const checked = checkPlaces(places, Array.isArray(places) ? places.length : 0, speakers)
+  const f32 = Math.fround
+  const sdpm = f32(given(sampleDelayPerMetre) ? sampleDelayPerMetre : (given(sampleRate) ? sampleRate : config.sampleRate) / 343), dbpm = f32(decibelsPerMetre)
+  if (!Number.isFinite(sdpm) || !Number.isFinite(dbpm)) throw 'dusp-hip: decibels_per_metre and sample_delay_per_metre are finite numbers'
+  const n = checked.places.length, nSpeakers = checked.speakers.length
+  const delays = new Float64Array(n * nSpeakers), gains = new Float64Array(n * nSpeakers)
+  for (let k = 0; k < n; k++)
+    for (let c = 0; c < nSpeakers; c++) {
+      let total = 0
+      checked.places[k].forEach((p, i) => {
+        const dx = f32(p - checked.speakers[c][i])
+        total += dx * dx
+      })
+      const dist = f32(Math.sqrt(total)), dB = f32(dist * dbpm)
+      delays[k * nSpeakers + c] = f32(dist * sdpm)
+      gains[k * nSpeakers + c] = Number.isFinite(dB) ? Math.pow(10, dB / 20) : NaN
+    }
+  checkTaps(delays, gains, n, nSpeakers)
+  return { nSpeakers, delays, gains }
+}
+
 async function pieceCall(who, outlets, opts, format, normalise, onePart = false) {
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
+  if (given(opts.places) && (given(opts.pans) || given(opts.fracs))) throw SPACE_ALONE
   const extractions = outlets.map((o) => extract(o))
   if (extractions.length === 0) throw 'dusp-hip: no instances'
   for (const ex of extractions)
@@ -592,18 +671,24 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   if (!Number.isInteger(tileBytes) || tileBytes < 0) throw 'dusp-hip: ' + who + ': tileBytes must be 0 (the default tile) or a whole number of bytes'
   const panned = opts.pans !== undefined && opts.pans !== null ? panArrays(opts.pans, count) : null
   const fracs = opts.fracs !== undefined && opts.fracs !== null ? fracArrays(opts.fracs, count) : null
+  let taps = null
+  if (given(opts.places)) {
+    checkPlaces(opts.places, count, opts.speakers)
+    taps = spaceTaps(opts.places, { speakers: opts.speakers, decibelsPerMetre: opts.decibelsPerMetre, sampleDelayPerMetre: opts.sampleDelayPerMetre, sampleRate })
+  }
   const grouped = pieceParts(extractions, voiceSamples)
   if (onePart && grouped.parts.length !== 1) throw 'dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments'
   const n = native()
   const channels = grouped.parts.map((part) => n.descriptorChannels(part.uni.words))
-  const nChannels = panned ? checkPanChannels(channels) : checkPieceChannels(channels)
+  const nChannels = taps ? checkSpaceChannels(channels, taps.nSpeakers) : panned ? checkPanChannels(channels) : checkPieceChannels(channels)
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
   const progs = []
   try {
     for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
-    const result = fracs ? await n.renderPieceFrac(...args, fracs, panned ? panned.pans : null, panned ? panned.comp : null)
+    const result = taps ? await n.renderPieceSpace(...args, taps.nSpeakers, taps.delays, taps.gains)
+      : fracs ? await n.renderPieceFrac(...args, fracs, panned ? panned.pans : null, panned ? panned.comp : null)
       : panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
     return { nSamples, nChannels, sampleRate, result }
   } finally {
@@ -623,7 +708,12 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * fracs (one number a voice, 0 <= f < 1; onsets stay whole numbers): voice k starts at onsets[k] + fracs[k] samples — what the reference
  * renders for new Delay(., onsets[k] + fracs[k], maxDelay), whose two taps carry the weights 1 - frac and frac
  * (dusp_render_host_score_parts_frac; include/dusp_hip.h says where the reference's ring departs from it).  splitOnsets makes both
- * arrays from positions in samples written as real numbers.  All fractions zero gives the bits of the call without. */
+ * arrays from positions in samples written as real numbers.  All fractions zero gives the bits of the call without.
+ * places (one position a voice, 1 to 3 coordinates in metres), with speakers (default [[-1, 0], [1, 0]]; 1 to 8, the same number of
+ * coordinates), decibelsPerMetre (-3) and sampleDelayPerMetre (sample rate / 343): the voices are MONO circuits and every speaker — a
+ * channel of the result — hears voice k attenuated and delayed by its distance, what the reference's Space patch does behind a sound
+ * (dusp_render_host_score_parts_space; spaceTaps makes the gain and the delay per voice and speaker; include/dusp_hip.h says where
+ * the reference's own wiring departs from it).  Not together with pans or fracs. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   const channelData = []
@@ -686,6 +776,9 @@ module.exports.checkPanChannels = checkPanChannels
 module.exports.panArrays = panArrays
 module.exports.fracArrays = fracArrays
 module.exports.splitOnsets = splitOnsets
+module.exports.spaceTaps = spaceTaps
+module.exports.checkPlaces = checkPlaces
+module.exports.checkSpaceChannels = checkSpaceChannels
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

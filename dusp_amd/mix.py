@@ -273,3 +273,154 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
                          (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)])
 
     return _chain(rows, 2, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw, place=pan)
+
+
+# ---- Space placement: a delay and a gain per voice and speaker ----
+
+SPACE_MAX_SPEAKERS = 8
+SPACE_MAX_DELAY = 2.0 ** 24
+SPEED_OF_SOUND = 343  # metres a second (SpaceChannel.js)
+
+
+def check_taps(delays, tap_gains, n):
+    """The taps of n voices -> contiguous float64 (delays [n, C], gains [n, C]): checked — 1 <= C <= 8 speakers, a finite delay in
+    [0, 2^24] samples and a finite gain per voice and speaker — by the strings the C calls use (dusp_score_rows_space_device).  Needs no
+    device."""
+    with np.errstate(all="ignore"):
+        delays = np.ascontiguousarray(delays, dtype=np.float64)
+        tap_gains = np.ascontiguousarray(tap_gains, dtype=np.float64)
+    if delays.ndim != 2 or delays.shape[0] != n or delays.shape != tap_gains.shape:
+        raise ValueError("dusp-hip: the taps' delays and gains must both have shape (voices=%d, speakers)" % n)
+    if not 1 <= delays.shape[1] <= SPACE_MAX_SPEAKERS:
+        raise ValueError("dusp-hip: a Space has 1 .. %d speakers, not %d" % (SPACE_MAX_SPEAKERS, delays.shape[1]))
+    bad = ~np.isfinite(delays)
+    if bad.any():
+        raise ValueError("dusp-hip: the delay of voice %d at speaker %d is not finite" % tuple(int(i) for i in np.argwhere(bad)[0]))
+    bad = (delays < 0) | (delays > SPACE_MAX_DELAY)
+    if bad.any():
+        raise ValueError("dusp-hip: the delay of voice %d at speaker %d is outside [0, 2^24] samples" % tuple(int(i) for i in np.argwhere(bad)[0]))
+    bad = ~np.isfinite(tap_gains)
+    if bad.any():
+        raise ValueError("dusp-hip: the gain of voice %d at speaker %d is not finite" % tuple(int(i) for i in np.argwhere(bad)[0]))
+    return delays, tap_gains
+
+
+def score_chain_rows_placed(rows, onsets, delays, tap_gains, n_total, lengths=None, gains=None, init=None, raw=False):
+    """rows: a list of MONO float32 arrays [1, samples_k], onsets int64 [voices], delays and tap_gains float64 [voices, C] (check_taps)
+    -> float32 [C, n_total]: the contract of dusp_score_rows_space_device.  Voice k reaches speaker c through a gain G_kc and a delay of
+    D_kc samples, the reference's Gain and MonoDelay units behind the voice: with i = floor(D), fr = D - i (exact in f64), w1 = fr,
+    w0 = 1.0 - fr and x[s] the voice's sample after the per-voice gain (f32(row_k[s] * g_k) or row_k[s])
+
+        y_c[s]   = f32(G_kc * f64(x[s]))              (Gain.js:22: one f64 product, one rounding)
+        fr == 0:   term(s) = y_c[s], 0 <= s < len, at t = onset_k + i + s
+        fr != 0:   two_tap_terms(y_c, fr) over the len + 1 samples from t = onset_k + i
+        acc_c    = f32(acc_c + term)                  per channel, in voice index order; no add where a voice does not cover t
+
+    init, raw, `acc || 0`, a voice of length 0, clipping to the timeline and windows (the same chain with onset - lo) are
+    score_chain_rows' word for word.  onset_k + i is formed without wrapping (Python integers): a span that leaves int64 lies outside
+    every timeline."""
+    rows = [np.asarray(r, dtype=np.float32) for r in rows]
+    n = len(rows)
+    if any(r.ndim != 2 or r.shape[0] != 1 for r in rows):
+        raise ValueError("dusp-hip: every placed row must be mono, of shape (1, samples)")
+    n_total = _timeline(n_total)
+    onsets = _whole(onsets, n, "onsets")
+    delays, tap_gains = check_taps(delays, tap_gains, n)
+    n_ch = delays.shape[1]
+    lengths = _row_lengths(rows, lengths)
+    if gains is not None:
+        gains = np.asarray(gains, dtype=np.float32)
+        if gains.shape != (n,):
+            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
+    if init is not None:
+        init = np.asarray(init, dtype=np.float32)
+        if init.shape != (n_ch, n_total):
+            raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
+    with np.errstate(all="ignore"):
+        acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
+        for k, row in enumerate(rows):
+            length = int(lengths[k])
+            if length == 0:
+                continue
+            x = row[0, :length]
+            if gains is not None:
+                x = x * gains[k]  # float32 * float32 scalar: one f32 rounding
+            xd = x.astype(np.float64)
+            for c in range(n_ch):
+                whole = np.floor(delays[k, c])
+                frac = delays[k, c] - whole
+                onset = int(onsets[k]) + int(whole)
+                y = (tap_gains[k, c] * xd).astype(np.float32)
+                term = two_tap_terms(y, frac) if frac != 0 else y
+                t0, t1 = max(onset, 0), min(onset + len(term), n_total)
+                if t1 > t0:
+                    acc[c, t0:t1] = acc[c, t0:t1] + term[t0 - onset:t1 - onset]  # float32 + float32: one f32 rounding
+        assert acc.dtype == np.float32
+        if not raw:
+            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
+    return acc
+
+
+def check_places(places, n, speakers=None):
+    """places of n voices and the speakers -> float32 (places [n, dims], speakers [C, dims]): 1 to 3 finite coordinates each, the same
+    number; speakers None: the reference's stereo pair [[-1, 0], [1, 0]] (Space.js).  Refused by string; needs no device."""
+    with np.errstate(all="ignore"):
+        try:
+            places = np.array(places, dtype=np.float64)
+            speakers = np.array([[-1, 0], [1, 0]] if speakers is None else speakers, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("dusp-hip: places and speakers are lists of 1 to 3 coordinates each")
+    if places.ndim != 2 or places.shape[0] != n or not 1 <= places.shape[1] <= 3:
+        raise ValueError("dusp-hip: places must have shape (voices=%d, 1 .. 3 coordinates)" % n)
+    if speakers.ndim != 2 or not 1 <= speakers.shape[1] <= 3:
+        raise ValueError("dusp-hip: speakers must have shape (speakers, 1 .. 3 coordinates)")
+    if not 1 <= speakers.shape[0] <= SPACE_MAX_SPEAKERS:
+        raise ValueError("dusp-hip: a Space has 1 .. %d speakers, not %d" % (SPACE_MAX_SPEAKERS, speakers.shape[0]))
+    if speakers.shape[1] != places.shape[1]:
+        raise ValueError("dusp-hip: places have %d coordinates, speakers have %d: the same number" % (places.shape[1], speakers.shape[1]))
+    if not np.all(np.isfinite(places)):
+        raise ValueError("dusp-hip: the place of voice %d is not finite" % int(np.argwhere(~np.isfinite(places))[0][0]))
+    if not np.all(np.isfinite(speakers)):
+        raise ValueError("dusp-hip: the place of speaker %d is not finite" % int(np.argwhere(~np.isfinite(speakers))[0][0]))
+    with np.errstate(all="ignore"):
+        return places.astype(np.float32), speakers.astype(np.float32)
+
+
+def space_taps(places, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, sample_rate=None):
+    """The reference's SpaceChannel (src/patches/SpaceChannel.js) per voice and speaker, with its roundings -> (delays float64 [n, C],
+    gains float64 [n, C]), what score_chain_rows_placed and the device take.  Every coordinate and factor is an inlet constant, rounded
+    to f32 (Inlet.js:88-91); Subtract, VectorMagnitude and Multiply store f32:
+
+        dx   = f32(p - q) per coordinate          dist = f32(sqrt(sum of f64(dx)^2)), the sum in f64 in coordinate order
+        dB   = f32(dist * dBpm)                   D    = f32(dist * f32(sdpm)), sdpm = sample_rate / 343 by default
+        G    = pow(10, dB / 20) in f64, by the host's pow (Gain.js)
+
+    places [n][1 .. 3], speakers [C][the same]; speakers None: [[-1, 0], [1, 0]].  A delay the device would refuse (not finite, beyond
+    2^24 samples) is refused here, by its string."""
+    import math
+    places = np.asarray(places)
+    places, speakers = check_places(places, places.shape[0] if places.ndim else 0, speakers)
+    if sample_delay_per_metre is None:
+        if sample_rate is None:
+            from . import config
+            sample_rate = config.sampleRate
+        sample_delay_per_metre = sample_rate / SPEED_OF_SOUND
+    f32, f64 = np.float32, np.float64
+    with np.errstate(all="ignore"):
+        dbpm, sdpm = f32(decibels_per_metre), f32(sample_delay_per_metre)
+    if not np.isfinite(dbpm) or not np.isfinite(sdpm):
+        raise ValueError("dusp-hip: decibels_per_metre and sample_delay_per_metre are finite numbers")
+    n, n_ch = places.shape[0], speakers.shape[0]
+    delays, gains = np.zeros((n, n_ch), dtype=f64), np.zeros((n, n_ch), dtype=f64)
+    with np.errstate(all="ignore"):
+        for k in range(n):
+            for c in range(n_ch):
+                total = f64(0)
+                for p, q in zip(places[k], speakers[c]):
+                    dx = f64(f32(f64(p) - f64(q)))
+                    total = total + dx * dx
+                dist = f32(np.sqrt(total))
+                db = f32(f64(dist) * f64(dbpm))
+                delays[k, c] = f64(f32(f64(dist) * f64(sdpm)))
+                gains[k, c] = math.pow(10, float(db) / 20) if np.isfinite(db) else np.nan
+    return check_taps(delays, gains, n)

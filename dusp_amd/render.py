@@ -11,7 +11,7 @@ program with a per-instance parameter table.
 """
 import numpy as np
 
-from . import descriptor, runtime, wav
+from . import descriptor, mix, runtime, wav
 
 _contexts = {}
 
@@ -243,7 +243,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -255,14 +255,17 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     apply: the tiles are the piece's default, by bytes).
 
     fracs: as render_piece's — voice k starts at onsets[k] + fracs[k] samples; the piece's call with the score as its one part, as
-    with pans."""
-    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs)
+    with pans.
+
+    places (with speakers, decibels_per_metre, sample_delay_per_metre): as render_piece's — mono voices, one channel a speaker; the
+    piece's call with the score as its one part, as with pans."""
+    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre))
 
 
-def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, pcm=None):
+def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, pcm=None, space=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if pans is not None or fracs is not None:
-        return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, True, fracs, pcm)
+    if pans is not None or fracs is not None or space is not None:
+        return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, True, fracs, pcm, space)
     if pcm is not None:
         _check_pcm(*pcm)
     uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
@@ -274,15 +277,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
-    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, (bit_depth, normalise))
+    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, (bit_depth, normalise),
+                         _space(places, speakers, decibels_per_metre, sample_delay_per_metre))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
-    return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs), bit_depth)
+    return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
+                                 decibels_per_metre, sample_delay_per_metre), bit_depth)
 
 
 class PieceParts:
@@ -342,9 +347,26 @@ def check_pan_channels(channels):
     return 2
 
 
-def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None, one_part=False, fracs=None):
-    """-> PieceParts, samples of timeline, onsets, lengths, gains, channels, pans, fracs (all checked: nothing is built yet).  With pans
-    the voices are mono and channels is the timeline's two; pans and fracs come back as None where none were given."""
+def check_space_channels(channels, speakers):
+    """channels[p]: the output channels of part p's circuit.  A placed voice is mono: refused by string otherwise."""
+    for p, c in enumerate(channels):
+        if c != 1:
+            raise descriptor.DuspError("dusp-hip: a placed voice is mono: part %d has %d output channels" % (p, c))
+    return speakers
+
+
+def _space(places, speakers, decibels_per_metre, sample_delay_per_metre):
+    """the Space keywords of a call as one thing, None without places (the other three alone say nothing)"""
+    return None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre)
+
+
+def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None, one_part=False, fracs=None, space=None):
+    """-> PieceParts, samples of timeline, onsets, lengths, gains, channels, pans, fracs, taps (all checked: nothing is built yet).  With
+    pans the voices are mono and channels is the timeline's two; with a space (_space) they are mono, channels is the speakers' number
+    and taps the (delays, gains) of mix.space_taps at the voices' sample rate; pans, fracs and taps come back as None where none were
+    given."""
+    if space is not None and (pans is not None or fracs is not None):
+        raise ValueError(runtime.SPACE_ALONE)
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
     if n == 0:
@@ -364,28 +386,34 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None
         pans, _ = runtime.pan_arrays(pans, n)
     if fracs is not None:
         fracs = runtime.frac_arrays(fracs, n)
+    taps = None
+    if space is not None:
+        mix.check_places(space[0], n, space[1])
+        taps = mix.space_taps(space[0], space[1], space[2], space[3], sample_rate=rate)
     grouped = piece_parts(extractions, voice_samples)
     if one_part and len(grouped.parts) != 1:  # (render_score with pans or fracs)
         raise descriptor.DuspError("dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments")
     channels = [runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts]
-    return grouped, n_total, onsets, lengths, gains, check_pan_channels(channels) if pans is not None else check_piece_channels(channels), pans, fracs
+    if taps is not None:
+        return grouped, n_total, onsets, lengths, gains, check_space_channels(channels, taps[0].shape[1]), pans, fracs, taps
+    return grouped, n_total, onsets, lengths, gains, check_pan_channels(channels) if pans is not None else check_piece_channels(channels), pans, fracs, taps
 
 
-def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0, pans=None, fracs=None):
+def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0, pans=None, fracs=None, taps=None):
     ctx = context(grouped.sample_rate, device)
     programs = []
     try:
         for uni, _ in grouped.parts:
             programs.append(ctx.build(uni.words, engine))
         parts = [(prog, n_voice, uni.n_instances, uni.params) for prog, (uni, n_voice) in zip(programs, grouped.parts)]
-        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, pans=pans, fracs=fracs)
+        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps)
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -400,29 +428,40 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     fracs (one number a voice, 0 <= f < 1; onsets stay whole numbers): voice k starts at onsets[k] + fracs[k] samples — what the
     reference renders for `Delay(., onsets[k] + fracs[k], maxDelay)`, whose two taps carry the weights 1 - frac and frac (mix.two_tap_terms;
     DESIGN.md 6.11 says where the reference's ring departs from it).  dusp_amd.split_onsets makes both arrays from positions in samples
-    written as real numbers.  A voice with a fraction covers one more sample; all fractions zero gives the bits of the call without."""
-    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs)
+    written as real numbers.  A voice with a fraction covers one more sample; all fractions zero gives the bits of the call without.
+
+    places (one position a voice, 1 to 3 coordinates in metres), with speakers (default [[-1, 0], [1, 0]]; 1 to 8 of them, the same
+    number of coordinates), decibels_per_metre (-3) and sample_delay_per_metre (sample rate / 343): the voices are MONO circuits and
+    every speaker — a channel of the result — hears voice k attenuated and delayed by its distance, what the reference's Space patch
+    does behind a sound: Gain at decibels_per_metre and MonoDelay at sample_delay_per_metre (mix.space_taps makes the gain and the delay
+    per voice and speaker with the reference's roundings, mix.score_chain_rows_placed is the contract; DESIGN.md 6.12 says where the
+    reference's own wiring departs from it).  Level AND time differences between the speakers, where pans give level only.  Not
+    together with pans or fracs."""
+    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs,
+                                space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre))
 
 
-def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, one_part, fracs, pcm=None):
+def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, one_part, fracs, pcm=None, space=None):
     """render_piece (pcm None) and render_piece_pcm (pcm = (bit_depth, normalise))"""
     if pcm is not None:
         _check_pcm(*pcm)
-    grouped, n_total, onsets, lengths, gains, channels, pans, fracs = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, one_part, fracs)
+    grouped, n_total, onsets, lengths, gains, channels, pans, fracs, taps = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, one_part, fracs, space)
     return _delivered(pcm, grouped.sample_rate, n_total, channels,
-                      lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format, normalise, pans=pans, fracs=fracs))
+                      lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps))
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
-    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs, (bit_depth, normalise))
+    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs, (bit_depth, normalise),
+                                _space(places, speakers, decibels_per_metre, sample_delay_per_metre))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
-    return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs), bit_depth)
+    return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre), bit_depth)
 
 
 class PcmData:

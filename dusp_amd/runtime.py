@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .mix import _whole, check_fracs, pan_comp
+from .mix import _whole, check_fracs, check_taps, pan_comp
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,6 +30,7 @@ EXPORTS = [
     "dusp_score_rows_device", "dusp_render_host_score_parts", "dusp_descriptor_channels",
     "dusp_score_rows_pan_device", "dusp_render_host_score_parts_pan",
     "dusp_score_rows_frac_device", "dusp_render_host_score_parts_frac",
+    "dusp_score_rows_space_device", "dusp_render_host_score_parts_space",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -103,6 +104,8 @@ def load():
     L.dusp_render_host_score_parts_pan.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_score_rows_frac_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
     L.dusp_render_host_score_parts_frac.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    L.dusp_score_rows_space_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
+    L.dusp_render_host_score_parts_space.argtypes = [vp, sz, sz, vp, vp, vp, vp, sz, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -141,10 +144,23 @@ def pan_arrays(pans, n, comp=None):
     return pans, comp
 
 
+SPACE_ALONE = "dusp-hip: places stand alone: together with pans or fracs they are refused (a sub-sample onset in front of a Space would be a second two-tap stage)"
+
+
 def frac_arrays(fracs, n):
     """fracs of n voices -> float64 [n]: checked — one finite fraction of a sample a voice, 0 <= f < 1 — by the strings the library uses
     (dusp_amd/mix.py check_fracs).  Needs no device."""
     return check_fracs(fracs, n)
+
+
+def tap_arrays(taps, n):
+    """taps = (delays, gains) of n voices -> float64 (delays [n, C], gains [n, C]): checked — 1 .. 8 speakers, finite delays in
+    [0, 2^24] samples, finite gains — by the strings the library uses (dusp_amd/mix.py check_taps).  Needs no device."""
+    try:
+        delays, gains = taps
+    except (TypeError, ValueError):
+        raise ValueError("dusp-hip: taps are a pair (delays, gains), each of shape (voices=%d, speakers)" % n)
+    return check_taps(delays, gains, n)
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -393,8 +409,20 @@ class Context:
         self._check(self._L.dusp_score_rows_frac_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, n_channels, _ptr(onsets, n), _ptr(fracs, n), _ptr(lengths), d_gains,
                                                         _ptr(pans), _ptr(comp), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
+    def score_rows_space(self, rows, row_samples, onsets, delays, tap_gains, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, stream=None):
+        """score_rows_device over MONO rows, voice k heard by speaker c — channel c of a timeline of C — through the gain tap_gains[k][c]
+        and a delay of delays[k][c] samples (dusp_score_rows_space_device; dusp_amd/mix.py score_chain_rows_placed is the contract): rows
+        are the voices' DEVICE pointers, voice k f32 [row_samples[k]]; delays and tap_gains HOST arrays of f64 [voices][C], 1 <= C <= 8,
+        the delays finite in [0, 2^24] and the gains finite (dusp_amd.space_taps makes both from places and speakers); d_init (which may
+        be d_out) and d_out f32 [C][n_total_samples].  score_last_ms() reports the call."""
+        n = len(rows)
+        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
+        delays, tap_gains = tap_arrays((delays, tap_gains), n)
+        self._check(self._L.dusp_score_rows_space_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, delays.shape[1], _ptr(onsets, n), _ptr(lengths), d_gains,
+                                                         _ptr(delays, n), _ptr(tap_gains, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None):
+                           pans=None, fracs=None, taps=None):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -403,7 +431,12 @@ class Context:
         pans (one finite f32 a voice): the parts are MONO and voice k is panned where it is added (dusp_render_host_score_parts_pan;
         mix.score_chain_rows_panned): the result has two channels.
         fracs (one finite f64 in [0, 1) a voice): voice k starts at onsets[k] + fracs[k] samples (dusp_render_host_score_parts_frac; the
-        contracts above with fracs), with or without pans."""
+        contracts above with fracs), with or without pans.
+        taps = (delays, gains), f64 [voices][C] each: the parts are MONO and voice k is heard by speaker c through gains[k][c] and a
+        delay of delays[k][c] samples (dusp_render_host_score_parts_space; mix.score_chain_rows_placed): the result has C channels.
+        Not together with pans or fracs."""
+        if taps is not None and (pans is not None or fracs is not None):
+            raise ValueError(SPACE_ALONE)
         if not parts:
             raise ValueError("dusp-hip: a piece has at least one part")
         n = len(part_of)
@@ -428,6 +461,11 @@ class Context:
         if fracs is not None:
             fracs = frac_arrays(fracs, n)
         comp = None
+        if taps is not None:  # (the speakers and the taps behind the gains)
+            delays, tap_gains = tap_arrays(taps, n)
+            n_ch = delays.shape[1]  # (parts that are not mono: the library refuses them)
+            entry = self._L.dusp_render_host_score_parts_space
+            args[7:7] = (n_ch, delays.ctypes.data, tap_gains.ctypes.data)
         if pans is not None:
             pans, comp = pan_arrays(pans, n)
             n_ch = 2  # (parts that are not mono: the library refuses them)

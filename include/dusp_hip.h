@@ -481,6 +481,45 @@ int dusp_render_host_score_parts_frac(const dusp_score_part *parts, size_t n_par
                                       const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes, int format,
                                       int normalise, void *h_out, float *h_peak);
 
+/* Space placement: dusp_score_rows_device over MONO rows, voice k heard by each of n_speakers speakers — the timeline's channels —
+ * through a gain G_kc and a delay of D_kc samples of its own (additions to ABI v7, detected by symbol).  It is the reference's
+ * SpaceChannel (src/patches/SpaceChannel.js) behind a sound, a Gain in front of a MonoDelay, done where the voice is added to the
+ * timeline.  From a tap's delay the host makes i = floor(D), fr = D - i (exact in f64), w1 = fr, w0 = 1.0 - fr.  With x[s] voice k's
+ * sample after the per-voice gain — f32(row_k[s] * g_k), or row_k[s] — and len its length, channel c takes
+ *     y[s]      = f32(G_kc * f64(x[s]))                        (Gain.js:22: one f64 product, one rounding)
+ *     fr == 0:    term(s) = y[s], 0 <= s < len, at timeline sample t = onset_k + i + s
+ *     fr != 0:    dusp_score_rows_frac_device's four lines with x := y and onset := onset_k + i: the voice covers len + 1 samples
+ *     acc_c     = f32(acc_c + term)                            (per channel, in voice index order; no add where the voice does not cover t)
+ * Everything else — d_init, raw, `acc || 0`, a voice of length 0, clipping to the timeline, windows as the same chain with
+ * onset_k - lo — is dusp_score_rows_device's (dusp_amd/mix.py score_chain_rows_placed is the contract in numpy).  onset_k + i is formed
+ * in int64 without wrapping: a voice whose shifted span leaves int64 takes no part.
+ * Channel c is what the reference renders for the ONE-channel circuit
+ *     Sum.many(k -> MonoDelay(Gain(Delay(Multiply(v_k, g_k), onset_k, ring), dB_kc), D_kc))       with G_kc = pow(10, dB_kc / 20)
+ * (a voice at onset 0 without its Delay, a tap of delay 0 without its MonoDelay), where D_kc is an f32 (the reference rounds an inlet
+ * constant to f32; elsewhere this call is more exact) and the samples are finite (with fr == 0 the reference forms y + y * 0, which is
+ * NaN for an infinite y; this call keeps y).  The reference's ConcatChannels hears its second inlet one chunk late; that lag is not
+ * reproduced, which is why the anchor is taken channel by channel.
+ *   n_speakers   1 .. 8; n_speakers * n_total_samples <= 2^31
+ *   h_delays     f64 [n_voices][n_speakers], HOST memory, finite, in [0, 2^24]
+ *   h_tap_gains  f64 [n_voices][n_speakers], HOST memory, finite
+ *   d_init, d_out  f32 [n_speakers][n_total_samples]
+ * The taps (32 bytes a voice and speaker) go up with the plan, on top of the plan's byte budget; dusp_score_last_ms reports this call
+ * too.  DUSP_ERR_ARG, with a message that names the voice and the speaker, checked before anything is launched: NULL taps, n_speakers
+ * outside 1 .. 8, a delay that is not finite or outside [0, 2^24], a gain that is not finite, n_speakers * n_total_samples > 2^31; and
+ * for everything dusp_score_rows_device refuses. */
+int dusp_score_rows_space_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices,
+                                 size_t n_speakers, const int64_t *h_onsets, const int64_t *h_lengths, const float *d_gains,
+                                 const double *h_delays, const double *h_tap_gains, size_t n_total_samples, const float *d_init, int raw,
+                                 float *d_out, void *stream);
+
+/* dusp_render_host_score_parts over MONO parts placed in a space: every tile is dusp_score_rows_space_device's launch and the result
+ * has n_speakers channels.  The taps are per voice in chain order and checked before anything is rendered; a part that is not mono is
+ * refused.  Everything else, refusals included, is dusp_render_host_score_parts'. */
+int dusp_render_host_score_parts_space(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                       const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains, size_t n_speakers,
+                                       const double *h_delays, const double *h_tap_gains, size_t n_total_samples, size_t tile_bytes,
+                                       int format, int normalise, void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

@@ -15,6 +15,10 @@
           fraction non-zero — plain, with gains and panned — kernel alone by dusp_score_last_ms, against dusp_score_rows_device (and
           dusp_score_rows_pan_device for the panned case) over the same rows, which is unchanged code; and the new entry point with all
           fractions zero, which launches those kernels.
+  space   (--space; profiles/score_space.txt) the space kernel (dusp_score_rows_space_device) over dense MONO rows of the dense shapes,
+          kernel alone by dusp_score_last_ms: two speakers with every delay fractional, against the panned two-tap kernel over the same
+          rows with every fraction non-zero (the same four taps per output pair; unchanged code) and against the whole-sample panned
+          kernel; two speakers with every delay whole; six speakers with every delay fractional.
   piece   8192 notes of 0.5 s placed over 60 s in onset order: Program.render_score on the host's clock, against the render of the same
           notes alone (render_device into a preallocated buffer) and against the same piece with the onsets shuffled — every tile's
           union window is then the whole timeline, which is what the window is worth.  One run under DUSP_JIT_LOG=2 prints the plans'
@@ -174,6 +178,51 @@ def frac(key, scale, ctxs, reps):
             print(line % (("%s: new entry point, all fractions zero" % label, t_zero[0], t_zero[1], read / t_zero[0] / 1e9, t_zero[0] / t_old[0]) + t_zero[2:]), flush=True)
 
 
+def space(key, scale, ctxs, reps):
+    import torch
+    V, n = max(64, DENSE[key][0] // scale), DENSE[key][1]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    ctx = ctxs["default"]
+    onsets = np.zeros(V, dtype=np.int64)
+    samples = np.full(V, n, dtype=np.uint32)
+    rng = np.random.RandomState(7)
+    pans = (rng.random_sample(V) * 2 - 1).astype(np.float32)
+    fracs = rng.randint(1, 1024, V) / 1024.0
+    # delays up to 1024 samples (7 m at 48 kHz), every one with a fraction; gains as -3 dB a metre gives them
+    delays = {C: rng.randint(0, 1024, (V, C)) + rng.randint(1, 1024, (V, C)) / 1024.0 for C in (2, 6)}
+    tap_gains = {C: 10.0 ** (-3.0 * delays[C] / 140.0 / 20.0) for C in (2, 6)}
+    mono = torch.empty((V, 1, n), dtype=torch.float32, device="cuda").normal_()
+    acc = torch.empty((6, n), dtype=torch.float32, device="cuda")
+    d_gains = torch.ones(V, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    pointers = [mono.data_ptr() + 4 * n * k for k in range(V)]
+    read = V * n * 4
+
+    def median_of(call):
+        kernel, plan, upload = [], [], []
+        for r in range(reps + 1):
+            call()
+            k, p, u = ctx.score_last_ms()
+            if r:
+                kernel.append(k), plan.append(p), upload.append(u)
+        return float(np.median(kernel)), min(kernel), float(np.median(plan)), float(np.median(upload))
+
+    line = "  %-56s kernel median %9.3f ms  fastest %9.3f   %5.2f TB/s of rows   x%.3f   [plan on the host %.2f ms, its upload %.2f ms]"
+    print("space %s: %d mono voices x %d samples = %.2f GB of rows, all onsets 0, full lengths" % (key, V, n, read / 1e9), flush=True)
+    g = d_gains.data_ptr()
+    t_pan = median_of(lambda: ctx.score_rows_pan(pointers, samples, onsets, pans, n, acc.data_ptr(), stream=s))
+    print(line % (("panned whole-sample kernel (unchanged code)", t_pan[0], t_pan[1], read / t_pan[0] / 1e9, t_pan[0] / t_pan[0]) + t_pan[2:]), flush=True)
+    t_two = median_of(lambda: ctx.score_rows_frac(pointers, samples, 1, onsets, fracs, n, acc.data_ptr(), pans=pans, stream=s))
+    print(line % (("panned two-tap kernel, every fraction non-zero (unchanged)", t_two[0], t_two[1], read / t_two[0] / 1e9, t_two[0] / t_pan[0]) + t_two[2:]), flush=True)
+    for label, C, dl, kw in [("space kernel, 2 speakers, every delay fractional", 2, delays[2], {}),
+                             ("space kernel, 2 speakers, fractional, with gains", 2, delays[2], {"d_gains": g}),
+                             ("space kernel, 2 speakers, every delay whole", 2, np.floor(delays[2]), {}),
+                             ("space kernel, 6 speakers, every delay fractional", 6, delays[6], {})]:
+        t = median_of(lambda: ctx.score_rows_space(pointers, samples, onsets, dl, tap_gains[C], n, acc.data_ptr(), stream=s, **kw))
+        print(line % ((label, t[0], t[1], read / t[0] / 1e9, t[0] / t_pan[0]) + t[2:]) + "   x%.3f of the panned two-tap kernel" % (t[0] / t_two[0]), flush=True)
+
+
 def piece(scale, ctxs, reps):
     import torch
     V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
@@ -216,13 +265,14 @@ def main():
     ap.add_argument("--scale", type=int, default=1, help="divide every voice count by this (a quick look)")
     ap.add_argument("--pan", action="store_true", help="the pan leg alone, over the dense cases named by --cases")
     ap.add_argument("--frac", action="store_true", help="the sub-sample-onset leg alone, over the dense cases named by --cases")
+    ap.add_argument("--space", action="store_true", help="the Space-placement leg alone, over the dense cases named by --cases")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
     for key in a.cases:
         if key in DENSE:
-            (frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
-    if "p" in a.cases and not a.pan and not a.frac:
+            (space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
+    if "p" in a.cases and not a.pan and not a.frac and not a.space:
         piece(a.scale, ctxs, a.reps)
 
 
