@@ -164,7 +164,7 @@ struct dusp_workspaces {
     DevBuf<unsigned long long> d_seg;  // WAVE, time-split: segment phase totals + start phases
     DevBuf<double> d_fused_state;  // FUSED: [n_state_words][n_inst] end-of-render state
     DevBuf<dusp::OscRec> d_recs;   // FUSED: per-voice oscillator records
-    DevBuf<dusp::SumVoice> d_sum_voices;  // FUSED sum chain: per-oscillator records
+    DevBuf<dusp::SumVoice> d_sum_voices;  // FUSED sum chain: per-oscillator records, and behind them every oscillator's (256 x block step) mod S
     DevBuf<float> d_host_out, d_host_par, d_host_frames, d_host_in;  // dusp_render_host staging, grown on demand
     DevBuf<unsigned char> d_host_pcm;                                // dusp_render_host_pcm: the encoded frames ...
     DevBuf<float> d_host_peaks;                                      // ... and the instances' peaks

@@ -133,13 +133,13 @@ static int render_sum_chain(dusp_program *prog, const RenderCall &c, dusp::Fused
     hipStream_t stream = c.stream;
     if (!L.table_fx32_ok) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "render: wave table has entries below 2^-20; build this program with DUSP_ENGINE_CHUNK");
     const int gb = dusp::sumchain_group_blocks(n_inst, c.n_samples, ctx->n_cus);
-    if (!gb) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "render: too many samples for the fused sum chain; use DUSP_ENGINE_CHUNK");
+    if (!gb) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, "render: too many samples for the fused sum chain (at most 65535 blocks of 2048 samples: 134215680 samples a launch); use DUSP_ENGINE_CHUNK");
     if (window) {
         L.chain_first = window->first;
         L.chain_init = window->init;
         L.chain_raw = window->raw;
     }
-    dusp::build_sum_voices(prog->fused, (uint32_t)prog->P.g.sample_rate, gb, L.chain_first + (uint64_t)c.n_chunks * dusp::kChunk, prog->h_sum_voices, prog->h_sum_end);
+    dusp::build_sum_voices(prog->fused, (uint32_t)prog->P.g.sample_rate, gb, L.chain_first, L.chain_first + (uint64_t)c.n_chunks * dusp::kChunk, prog->h_sum_voices, prog->h_sum_end);
     HIP_TRY(ctx, prog->d_sum_voices.ensure(prog->h_sum_voices.size()));
     HIP_TRY(ctx, hipMemcpyAsync(prog->d_sum_voices.p, prog->h_sum_voices.data(), prog->h_sum_voices.size() * sizeof(dusp::SumVoice), hipMemcpyHostToDevice, stream));
     std::vector<double> end((size_t)prog->fused.n_state_words * n_inst);
@@ -401,7 +401,7 @@ int dusp_render_chain_window(dusp_program *prog, uint64_t first_sample, size_t n
         CTX_FAIL(prog->ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_chain_window: the program is not on the fused sum chain (a Sum.many of constant-f oscillators)");
     if (prog->P.g.n_params > 0) CTX_FAIL(prog->ctx, DUSP_ERR_UNSUPPORTED, "dusp_render_chain_window: programs with per-instance parameters are not chained");
     if (first_sample % 2048 != 0) CTX_FAIL(prog->ctx, DUSP_ERR_ARG, "dusp_render_chain_window: first_sample must be a multiple of 2048");
-    if (first_sample > (1ull << 40)) CTX_FAIL(prog->ctx, DUSP_ERR_ARG, "dusp_render_chain_window: first_sample out of range");
+    if (first_sample > (1ull << 40)) CTX_FAIL(prog->ctx, DUSP_ERR_ARG, "dusp_render_chain_window: first_sample must be at most 2^40");
     if ((((uintptr_t)d_init | (uintptr_t)d_out) & 15) != 0) CTX_FAIL(prog->ctx, DUSP_ERR_ARG, "dusp_render_chain_window: d_init and d_out must be 16-byte aligned");
     ChainWindow window;
     window.first = first_sample;

@@ -8,6 +8,7 @@
 
 #include "device_types.hpp"
 #include "filter_lamda.hpp"
+#include "modmath.hpp"
 
 namespace dusp {
 namespace {
@@ -18,18 +19,7 @@ __device__ __forceinline__ int lsb_exponent(double x) {  // x finite, != 0: expo
     const long long m = (long long)ldexp(fr, 53);
     return ex - 53 + __builtin_ctzll((unsigned long long)m);
 }
-__device__ __forceinline__ uint64_t addmod(uint64_t a, uint64_t b, uint64_t S) {  // a, b < S < 2^63
-    const uint64_t s = a + b;
-    return s >= S ? s - S : s;
-}
-__device__ __forceinline__ uint64_t mulmod(uint64_t a, uint64_t n, uint64_t S) {  // a < S
-    uint64_t acc = 0;
-    for (int bit = 63 - __builtin_clzll(n | 1); bit >= 0; --bit) {
-        acc = addmod(acc, acc, S);
-        if ((n >> bit) & 1) acc = addmod(acc, a, S);
-    }
-    return acc;
-}
+// (addmod, mulmod, mod_u32, mod_u64, jit_mulmod and the sum chain's block base: modmath.hpp, which host code includes too)
 
 // ---- Oscillator increments beyond the exact regime.  The parallel oscillator forms keep phases as exact 2^-36 fixed point and fold an
 // increment at or above the sample rate by (a + b) % m == (a + b % m) % m.  That identity is true of real numbers; the reference adds in
@@ -272,23 +262,6 @@ struct LeanPhase {
         return ((unsigned long long)(u >= kPhaseBias ? u : h) << 32) | (uint32_t)s;
     }
 };
-
-__device__ __forceinline__ uint32_t mod_u32(uint32_t x, uint32_t m, double inv_m) {
-    const uint32_t q = (uint32_t)((double)x * inv_m);
-    uint32_t r = x - q * m;
-    if ((int32_t)r < 0) r += m;
-    if (r >= m) r -= m;
-    return r;
-}
-__device__ __forceinline__ uint64_t mod_u64(uint64_t x, uint64_t m, double inv_m) {  // x < 2^64, m < 2^48
-    const uint64_t q = (uint64_t)((double)x * inv_m);
-    uint64_t r = x - q * m;
-    if ((int64_t)r < 0) r += m;
-    if ((int64_t)r < 0) r += m;
-    if (r >= m) r -= m;
-    if (r >= m) r -= m;
-    return r;
-}
 
 __device__ __forceinline__ unsigned long long mod_u64_lifted(unsigned long long x, unsigned long long m, double inv_m) {
     return mod_u64(x, m, inv_m);  // x already lifted to a non-negative value below 2^63

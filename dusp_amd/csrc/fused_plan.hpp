@@ -13,6 +13,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
@@ -62,7 +63,11 @@ struct OscRec {
 };
 
 // One oscillator of a Sum.many chain in exact 32.32 fixed point (units of 2^-32 table steps):
-// phase of (block b, lane l, sample c) = (B0 + b*bs + l*step4 + c*Fm) mod (sampleRate << 32).
+// phase of (block b, lane l, sample c) = (B0 + b*bs + l*step4 + c*Fm) mod (sampleRate << 32).  b counts the LAUNCH's blocks: B0 is
+// the phase of the launch's first sample, wherever in the timeline that is (build_sum_voices folds the window's first sample in, in
+// 128-bit integers).  The 32.32 path forms b*bs without passing 2^64 with the help of (256 bs) mod S (modmath.hpp sum_block_base),
+// which travels in an array of its own behind the records (SumArgs::bs256; one upload carries both: sum_voice_slots): the INT path
+// never reads it, and its records stay at the 48 bytes the scalar cache streams per voice and work item.
 struct SumVoice {
     uint64_t B0, bs, step4, step256, Fm;
     float gain;  // enveloped chains of kind 1: the voice's Multiply constant
@@ -71,6 +76,7 @@ struct SumVoice {
 
 struct SumArgs {
     const SumVoice *voices;
+    const uint64_t *bs256;  // [n_voices] (256 bs) mod S of every voice (read by the 32.32 path only)
     const float *table;
     float *out;
     uint64_t n_samples, S;
@@ -79,10 +85,13 @@ struct SumArgs {
     double r_d, r_y0, r_y1, r_t0;  // the voices' common Ramp (kernels instantiated with ENV == 2)
     int32_t r_playing, r_fastdiv;
     // A window of the render that continues a chain (dusp_render_chain_window: the voices of one `Sum.many` dealt over several
-    // GPUs): blocks first_block .. of the timeline go to `out`, whose first sample is the window's; the running sums start as
+    // GPUs): samples first .. of the timeline go to `out`, whose first sample is the window's; the running sums start as
     // `init` (same layout as `out`) instead of zeros; raw: no `x || 0` at the copy-out (a partial sum that another rank continues).
+    // Blocks and groups count from the window's first sample (the voices' B0 already stand there); only the Ramp envelope, a
+    // function of the timeline's sample index, adds `first` back — in 64 bits.
     const float *init;
-    uint32_t first_block, raw;
+    uint64_t first;
+    uint32_t raw, pad;
 };
 
 // Arguments of the wave engine's kernel (wave_engine.hip).
@@ -448,12 +457,17 @@ inline bool plan_fused(const Program &P, FusedPlan &plan) {
     return true;
 }
 
-// Exact 32.32 fixed-point records of a Sum.many chain's oscillators, and their phases after T_end samples.
-inline void build_sum_voices(const FusedPlan &plan, uint32_t sample_rate, int gb, uint64_t T_end, std::vector<SumVoice> &voices,
+// n voice records and, behind them, n uint64_t: so many records' worth of memory
+inline size_t sum_voice_slots(size_t n) { return n + (n * sizeof(uint64_t) + sizeof(SumVoice) - 1) / sizeof(SumVoice); }
+
+// Exact 32.32 fixed-point records of a Sum.many chain's oscillators for a launch whose first sample is sample `first` of the
+// timeline, and their phases after T_end samples (of the timeline).
+inline void build_sum_voices(const FusedPlan &plan, uint32_t sample_rate, int gb, uint64_t first, uint64_t T_end, std::vector<SumVoice> &voices,
                              std::vector<double> &end_phase) {
     typedef unsigned __int128 u128;
     const uint64_t S = (uint64_t)sample_rate << 32;
     voices.clear();
+    std::vector<uint64_t> bs256;
     end_phase.clear();
     for (size_t j = 0; j < plan.sum_f.size(); j++) {
         const double f = plan.sum_f[j];
@@ -462,15 +476,20 @@ inline void build_sum_voices(const FusedPlan &plan, uint32_t sample_rate, int gb
         const uint64_t P0 = (uint64_t)std::ldexp(plan.sum_phase0[j], 32);
         SumVoice v;
         v.Fm = Fm;
-        v.B0 = (uint64_t)(((u128)P0 + Fm) % S);
+        v.B0 = (uint64_t)(((u128)P0 + (u128)Fm * ((u128)first + 1)) % S);
         v.bs = (uint64_t)(((u128)Fm * (uint64_t)(gb * kChunk)) % S);
         v.step4 = (uint64_t)(((u128)Fm * 4) % S);
         v.step256 = (uint64_t)(((u128)Fm * kChunk) % S);
         v.gain = plan.sum_env == 1 ? plan.sum_gain[j] : 1.f;
         v.pad = 0;
         voices.push_back(v);
+        bs256.push_back((uint64_t)(((u128)v.bs * 256) % S));
         end_phase.push_back(std::ldexp((double)(uint64_t)(((u128)P0 + (u128)Fm * T_end) % S), -32));
     }
+    // ... and behind the n records, in the same vector (one upload), the n block steps x 256: sum_voice_slots(n) records in all
+    const size_t n = voices.size();
+    voices.resize(sum_voice_slots(n), SumVoice{});
+    if (n) std::memcpy((void *)(voices.data() + n), bs256.data(), n * sizeof(uint64_t));
     if (plan.sum_env == 2)  // what every Ramp holds after T_end ticks (Ramp.js:27-36): behind the phases, [t, playing] per unit
         for (size_t j = 0; j < plan.sum_ramp_units.size(); j++) {
             const double since = (double)T_end;

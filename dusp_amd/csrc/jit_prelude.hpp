@@ -120,15 +120,7 @@ __device__ __forceinline__ void jit_unpark(const JitArgs &A, const JitCtx &X, ui
     v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
 }
 
-// (a * n) mod S for a < S < 2^53 and n < 2^32, exactly: the product is cut into pieces that mod_u64 (x < 2^64) can take
-__device__ __forceinline__ unsigned long long jit_mulmod(unsigned long long a, unsigned long long n, unsigned long long S, double inv_S) {
-    const unsigned long long ah = a >> 32, al = a & 0xffffffffull;  // ah < 2^21
-    unsigned long long r = mod_u64(ah * n, S, inv_S);               // (ah n) < 2^53; now r 2^32 mod S in three shifts of <= 11 bits
-    r = mod_u64(r << 11, S, inv_S);
-    r = mod_u64(r << 11, S, inv_S);
-    r = mod_u64(r << 10, S, inv_S);
-    return addmod(r, mod_u64(al * n, S, inv_S), S);
-}
+// ((a * n) mod S for the phase jumps below: jit_mulmod, modmath.hpp)
 
 // Inclusive prefix sum of a 32-bit value over the 64 lanes, in the VALU's own cross-lane network (DPP): four shifts inside
 // each row of 16 lanes, then two row broadcasts — six adds, no LDS crossbar round trips (a ds_bpermute shuffle costs ~50

@@ -41,13 +41,13 @@ __global__ void __launch_bounds__(BLOCK) dusp_sumchain_kernel(SumArgs A) {
     const uint64_t n_items = (uint64_t)A.n_inst * A.n_blocks;
     const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
     const uint32_t sr = A.sample_rate;
-    const uint32_t n_full = A.first_block * GB + (A.vec4_ok ? (uint32_t)(A.n_samples / kChunk) : 0u);  // (groups counted like g0: from the render's first sample)
+    const uint32_t n_full = A.vec4_ok ? (uint32_t)(A.n_samples / kChunk) : 0u;  // (groups counted like g0: from the launch's first sample)
 
     for (uint64_t item = (uint64_t)blockIdx.x * waves_per_block + (threadIdx.x >> 6); item < n_items; item += total_waves) {
-        const uint32_t blk = (uint32_t)(item % A.n_blocks) + A.first_block;  // (a window: blocks counted from the render's first sample)
+        const uint32_t blk = (uint32_t)(item % A.n_blocks);  // (blocks count from the launch's first sample: below 2^16, wherever in the timeline a window lies)
         const uint32_t inst = (uint32_t)(item / A.n_blocks);
         const uint32_t g0 = blk * GB;
-        const size_t row_at = (size_t)inst * A.n_samples + (size_t)(g0 - A.first_block * GB) * kChunk + lane * 4;
+        const size_t row_at = (size_t)inst * A.n_samples + (size_t)g0 * kChunk + lane * 4;
         float acc[GB][4];
 #pragma unroll
         for (int g = 0; g < GB; ++g)
@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(BLOCK) dusp_sumchain_kernel(SumArgs A) {
                     const f32x4 v = *(const f32x4 *)(A.init + row_at + (size_t)g * kChunk);
                     acc[g][0] = v[0]; acc[g][1] = v[1]; acc[g][2] = v[2]; acc[g][3] = v[3];
                 } else if (g0 + g < A.n_groups) {  // (the window's last, partial group)
-                    const uint64_t t = (uint64_t)(g0 + g - A.first_block * GB) * kChunk + lane * 4;
+                    const uint64_t t = (uint64_t)(g0 + g) * kChunk + lane * 4;
                     for (int c = 0; c < 4; ++c)
                         if (t + c < A.n_samples) acc[g][c] = A.init[row_at + (size_t)g * kChunk + c];
                 }
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(BLOCK) dusp_sumchain_kernel(SumArgs A) {
             for (int g = 0; g < (ENV == 2 ? GB : 1); ++g)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const uint64_t n = (uint64_t)(g0 + g) * kChunk + lane * 4 + c;
+                    const uint64_t n = A.first + (uint64_t)(g0 + g) * kChunk + lane * 4 + c;  // (the timeline's sample index: 64 bits)
                     const double tt = A.r_playing ? fmin(A.r_t0 + (double)(n + 1), A.r_d) : A.r_t0;
                     double q;
                     if (A.r_fastdiv) {  // (the host has checked the refined reciprocal against the division on every t of this Ramp)
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(BLOCK) dusp_sumchain_kernel(SumArgs A) {
             if (INT) {
                 // every phase is an integer: out = table[phase] exactly (Osc.js:43-45 with fraction 0)
                 const uint32_t f = (uint32_t)(rc.Fm >> 32), s4 = (uint32_t)(rc.step4 >> 32), s256 = (uint32_t)(rc.step256 >> 32);
-                const uint32_t base = mod_u32((uint32_t)(rc.B0 >> 32) + blk * (uint32_t)(rc.bs >> 32), sr, A.inv_sr);
+                const uint32_t base = sum_block_base_int((uint32_t)(rc.B0 >> 32), (uint32_t)(rc.bs >> 32), blk, sr, A.inv_sr);
                 uint32_t idx[4];
                 idx[0] = mod_u32(base + lane * s4, sr, A.inv_sr);
 #pragma unroll
@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(BLOCK) dusp_sumchain_kernel(SumArgs A) {
                         idx[c] = min(idx[c], idx[c] - sr);
                     }
             } else {
-                const uint64_t base = mod_u64(rc.B0 + (uint64_t)blk * rc.bs, A.S, A.inv_S);
+                const uint64_t base = sum_block_base(rc.B0, rc.bs, A.bs256[j], blk, A.S, A.inv_S);
                 uint64_t P = mod_u64(base + (uint64_t)lane * rc.step4, A.S, A.inv_S);
                 uint32_t I[4], F[4];
 #pragma unroll
@@ -150,7 +150,7 @@ __global__ void __launch_bounds__(BLOCK) dusp_sumchain_kernel(SumArgs A) {
             if (gg < n_full)
                 store4<true>(row, v, 0, A.n_samples);
             else
-                store4<false>(row, v, (uint64_t)(gg - A.first_block * GB) * kChunk + lane * 4, A.n_samples);
+                store4<false>(row, v, (uint64_t)gg * kChunk + lane * 4, A.n_samples);
             row += kChunk;
         }
     }
@@ -170,6 +170,7 @@ static hipError_t launch_sum(const SumArgs &A, int grid, size_t lds_bytes, hipSt
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream) {
     SumArgs A{};
     A.voices = d_voices;
+    A.bs256 = (const uint64_t *)(d_voices + plan.sum_f.size());  // (behind the records: build_sum_voices)
     A.table = L.tables + (size_t)plan.table_id * L.table_stride;
     A.out = L.out;
     A.n_samples = L.n_samples;
@@ -178,12 +179,12 @@ hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const Su
     A.inv_sr = 1.0 / (double)L.sample_rate;
     A.n_voices = (uint32_t)plan.sum_f.size();
     A.n_inst = L.n_inst;
-    // (a window of a chain: L.chain_first is a whole number of blocks — the caller checks; groups and blocks count from the render's first sample)
-    A.first_block = (uint32_t)(L.chain_first / ((uint64_t)gb * kChunk));
+    // (a window of a chain: the voice records already stand at L.chain_first — build_sum_voices — and groups and blocks count from there)
+    A.first = L.chain_first;
     A.init = L.chain_init;
     A.raw = L.chain_raw ? 1u : 0u;
     const uint32_t window_groups = (uint32_t)((L.n_samples + kChunk - 1) / kChunk);
-    A.n_groups = A.first_block * (uint32_t)gb + window_groups;
+    A.n_groups = window_groups;
     A.n_blocks = (window_groups + gb - 1) / gb;
     A.sample_rate = L.sample_rate;
     A.vec4_ok = (L.n_samples % 4 == 0) && (((uintptr_t)L.out & 15) == 0);
@@ -198,8 +199,8 @@ hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const Su
     const size_t lds_bytes = tbl ? half_table_lds_bytes(L.sample_rate) : 0;
     const int grid = tbl ? L.n_cus : L.n_cus * 8;
     const bool finite = L.table_finite && plan.sum_env == 0;  // (enveloped voices: products may overflow, so the copy-out keeps the full `x || 0`)
-    // INT needs blk * (bs >> 32) < 2^32
-    const bool use_int = plan.sum_all_int && ((uint64_t)A.first_block + A.n_blocks) * L.sample_rate < (1ull << 32);
+    // INT needs (B0 >> 32) + blk * (bs >> 32) < 2^32 for every block of the launch
+    const bool use_int = plan.sum_all_int && sum_int_blocks_ok(A.n_blocks, L.sample_rate);
 
 #define DUSP_S5(TB, IN, G, FIN, EN) \
     return TB ? launch_sum<1, IN, G, FIN, 1024, EN>(A, grid, lds_bytes, stream) : launch_sum<0, IN, G, FIN, 256, EN>(A, grid, 0, stream)

@@ -4,6 +4,7 @@ There is deliberately no CPU fallback here: if the HIP library is missing or no
 GPU is usable, every entry point raises.
 """
 import ctypes
+import operator
 import threading
 import os
 
@@ -37,6 +38,8 @@ PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
 PCM_FORMATS = {"s16": PCM_S16, "s24": PCM_S24, "f32": PCM_F32}
 PCM_BYTES = {PCM_S16: 2, PCM_S24: 3, PCM_F32: 4}
 NORMALISE_NONE, NORMALISE_CLIP, NORMALISE_FULL = 0, 1, 2  # dusp_normalise
+# dusp_render_chain_window: windows start on whole blocks of 2048 samples up to sample 2^40 and hold at most 65535 blocks
+CHAIN_BLOCK, CHAIN_FIRST_MAX, CHAIN_SAMPLES_MAX = 2048, 1 << 40, 65535 * 2048
 
 
 class DuspHipError(RuntimeError):
@@ -624,7 +627,14 @@ class Program:
 
     def render_chain_window(self, first_sample, n_samples, d_init, raw, d_out, stream=None):
         """dusp_render_chain_window: the window [first_sample, first_sample + n_samples) of a fused sum-chain program's timeline, its sums
-        continued from d_init (None: the chain's first voices are this program's); raw: a partial sum for the next rank (shard.chain_mixdown)."""
+        continued from d_init (None: the chain's first voices are this program's); raw: a partial sum for the next rank (shard.chain_mixdown).
+        first_sample: a multiple of 2048 up to 2^40; n_samples: up to 65535 blocks of 2048 — every window in that range is exact, anything
+        else is refused here, before the library is called."""
+        first_sample, n_samples = operator.index(first_sample), operator.index(n_samples)
+        if first_sample < 0 or first_sample > CHAIN_FIRST_MAX:  # (whole blocks: the library's check)
+            raise ValueError("dusp-hip: first_sample of a chain window must be in 0 .. 2^40, not %d" % first_sample)
+        if n_samples < 1 or n_samples > CHAIN_SAMPLES_MAX:
+            raise ValueError("dusp-hip: n_samples of a chain window must be in 1 .. %d (65535 blocks of %d samples), not %d" % (CHAIN_SAMPLES_MAX, CHAIN_BLOCK, n_samples))
         self.ctx._check(self._L.dusp_render_chain_window(self._h, first_sample, n_samples, d_init, int(bool(raw)), d_out, stream))
 
     def state(self, unit, instance=0):

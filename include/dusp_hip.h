@@ -180,8 +180,11 @@ int dusp_render_device(dusp_program *prog, size_t n_instances, size_t n_samples,
  * same window — instead of from zero (d_init NULL: this rank holds the chain's first voices).  raw != 0 writes the sums as
  * they stand (a partial sum another rank continues: no `x || 0`, so a NaN travels on as the reference's would); the rank with
  * the chain's last voices passes raw = 0 and gets the mix as dusp_render_device would have written it.
- *   first_sample  a multiple of 2048 (whole blocks of the kernel)
+ *   first_sample  a multiple of 2048 (whole blocks of the kernel), at most 2^40 (DUSP_ERR_ARG beyond: 2^40 samples are 66 days at 192 kHz)
+ *   n_samples     at most 65535 blocks of 2048 samples, 134215680, like every launch of the fused sum chain (DUSP_ERR_UNSUPPORTED beyond)
  *   d_init, d_out device pointers, f32 [n_out_channels = 1][n_samples], 16-byte aligned; they may be the same buffer
+ * Every window in that range is exact at every sample rate: the window's place in the timeline is folded into the voices' start
+ * phases on the host in 128-bit integers, and the kernel counts blocks and samples from the window's first sample.
  * Asynchronous like dusp_render_device.  DUSP_ERR_UNSUPPORTED for a program that is not on the fused sum chain. */
 int dusp_render_chain_window(dusp_program *prog, uint64_t first_sample, size_t n_samples,
                              const float *d_init, int raw, float *d_out, void *stream);

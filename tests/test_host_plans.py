@@ -47,6 +47,16 @@ def test_render_plan_boundary_values(tmp_path):
     assert rep["cases"] >= 24, rep
 
 
+def test_jump_ahead_integer_helpers_and_the_sum_chains_block_base_are_exact(tmp_path):
+    """dusp_amd/csrc/modmath.hpp against unsigned __int128: addmod, mulmod, mod_u32, mod_u64 and jit_mulmod at every modulus in use
+    (sampleRate << 32 and << 36 over the sample-rate matrix, 2^17) with operands at their edges, the sum chain's block base for every
+    block count a launch can have — among them the ones whose plain 64-bit product passes 2^64 — and a voice's record from
+    build_sum_voices to the phase of a sample for windows up to sample 2^40."""
+    rep = _build_and_run(tmp_path, "sumchain_base_check")
+    assert rep["cases"] >= 100000 and rep["mod_u64"] >= 1500 and rep["mod_u32"] >= 300 and rep["jit_mulmod"] >= 10000, rep
+    assert rep["block_base"] >= 7000 and rep["block_base_int"] >= 800 and rep["voice_phases"] >= 100000 and rep["products_past_2_64"] >= 500, rep
+
+
 def test_workspace_registry_names_every_overwritten_guard(tmp_path):
     """Every DevBuf of a program is in the registry its destructor and the guard check walk: with "device" memory on the host
     (tests/native/hip_mem_stub), a byte flipped behind each workspace in turn is reported under that workspace's name.  The header's shared argument checks give every entry point the text it has always given."""
