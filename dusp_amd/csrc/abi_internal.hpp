@@ -61,6 +61,9 @@ hipError_t launch_score_frac(const float *d_gains, const ScorePan *d_pans, const
 hipError_t launch_score_space(const float *d_gains, const ScoreSpaceTap *d_taps, const ScoreRow *d_voices, const uint32_t *d_block_first, const uint32_t *d_entries,
                               const float *d_init, float *d_out, uint32_t n_channels, uint64_t n_total, uint64_t w_lo, uint64_t w_hi, uint32_t block_shift, uint64_t first_block,
                               int raw, hipStream_t stream);
+hipError_t launch_score_stereo(const float *d_gains, const ScorePan *d_pans, const ScoreFrac *d_fracs, const ScoreRow *d_voices, const uint32_t *d_block_first,
+                               const uint32_t *d_entries, const float *d_init, float *d_out, uint64_t n_total, uint64_t w_lo, uint64_t w_hi, uint32_t block_shift,
+                               uint64_t first_block, int raw, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);

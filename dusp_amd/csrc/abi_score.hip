@@ -1,7 +1,8 @@
-// abi_score.hip — the C ABI (include/dusp_hip.h): voices mixed at per-voice onsets into a timeline (score_plan.hpp and the five score
+// abi_score.hip — the C ABI (include/dusp_hip.h): voices mixed at per-voice onsets into a timeline (score_plan.hpp and the six score
 // engines): the plans' image on the device, the one launch path, the device entries (dusp_score_device, dusp_score_rows_device and its
 // pan, frac and space forms) and the host round trips (dusp_render_host_score, dusp_render_host_score_parts and its pan, frac and space
-// forms).
+// forms), and the stereo forms in which a voice is a panned mono row, a plain mono row or a row of two channels (score_stereo_engine.hip;
+// dusp_score_rows_stereo_device, dusp_render_host_score_parts_stereo).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -15,8 +16,9 @@
 
 // which kernel a launch is: voices of one contiguous batch (score_engine.hip; dusp_amd/mix.py score_chain is the contract), rows of their
 // own (score_rows_engine.hip; score_chain_rows), mono rows placed in the stereo field (score_pan_engine.hip; score_chain_rows_panned), or
-// mono rows placed in a space, a delay and a gain per speaker (score_space_engine.hip; score_chain_rows_placed)
-enum class ScoreKind { contiguous, rows, pan, space };
+// mono rows placed in a space, a delay and a gain per speaker (score_space_engine.hip; score_chain_rows_placed), or rows of one and of two
+// channels, the mono ones panned or not, into a timeline of two (score_stereo_engine.hip; score_chain_rows_stereo)
+enum class ScoreKind { contiguous, rows, pan, space, stereo };
 
 // the taps of a space call: h_delays and h_gains f64 [voice][speaker] on the host (checked: check_taps)
 struct ScoreTaps {
@@ -102,15 +104,15 @@ static int score_voices_add(dusp_ctx *ctx, const char *who, const int64_t *h_ons
 // the launch are as without.
 static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n,
                           size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L, std::vector<unsigned char> *listed = nullptr,
-                          const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr) {
-    dusp::ScoreRowsPlan P;
+                          const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr, const uint32_t *row_channels = nullptr, const float *h_pans = nullptr) {
+    dusp::ScoreRowsPlan P;  // (row_channels, h_pans: a stereo call's, the kind of every voice)
     std::vector<dusp::ScoreSpaceTap> T;  // (space: the voices' taps, [voice][speaker], 32 bytes each on top of the budget as the weights are)
     if (taps) {
         T.resize(n * taps->n_speakers);
         for (size_t j = 0; j < T.size(); j++) T[j] = dusp::score_space_tap(taps->h_delays[j], taps->h_gains[j]);
     }
     const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, h_fracs, taps ? T.data() : nullptr,
-                                              taps ? taps->n_speakers : 0);
+                                              taps ? taps->n_speakers : 0, row_channels, h_pans);
     if (bad >= 0)
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
                                         ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
@@ -126,10 +128,11 @@ static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onset
 }
 
 // the pan coefficients of the voices [0, n) of the rows plan just added (L).  h_comp NULL: the reference's compensation by the host's
-// pow (Pan.js:20)
+// pow (Pan.js:20).  A voice of a stereo call that is not placed (its pan NaN) has zeros, which nobody multiplies by
 static void score_pans_add(dusp_ctx *ctx, const float *h_pans, const double *h_comp, size_t n, ScoreLaunch &L) {
     if (!L.any) return;
     L.pan_at = score_image_append<dusp::ScorePan>(ctx, n, [&](size_t k) {
+        if (std::isnan(h_pans[k])) return dusp::ScorePan{0.0, 0.0, 0.0, 0.0};
         const double comp = h_comp ? h_comp[k] : std::pow(10.0, ((1.0 - std::fabs((double)h_pans[k])) * 1.5) / 20.0);
         return dusp::score_pan_coefficients(h_pans[k], comp);
     });
@@ -169,14 +172,17 @@ static int score_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, 
     const size_t record = L.kind == ScoreKind::contiguous ? sizeof(dusp::ScoreVoice) : sizeof(dusp::ScoreRow);
     const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices * record) : nullptr, *d_entries = L.any ? d_block_first + L.n_block_first : nullptr;
     const dusp::ScoreRow *d_rows = (const dusp::ScoreRow *)d_voices;
-    const dusp::ScorePan *d_pans = L.any && L.kind == ScoreKind::pan ? (const dusp::ScorePan *)(d_image + L.pan_at) : nullptr;
-    if (L.any && L.kind == ScoreKind::space)  // (score_space_engine.hip: mono rows into a timeline of n_channels speakers)
+    const dusp::ScorePan *d_pans = L.any && (L.kind == ScoreKind::pan || L.kind == ScoreKind::stereo) ? (const dusp::ScorePan *)(d_image + L.pan_at) : nullptr;
+    if (L.any && L.kind == ScoreKind::stereo)  // (score_stereo_engine.hip: rows of one and of two channels into a timeline of two)
+        HIP_TRY(ctx, dusp::launch_score_stereo(d_gains, d_pans, L.frac ? (const dusp::ScoreFrac *)(d_image + L.frac_at) : nullptr, d_rows, d_block_first, d_entries, d_init, d_out,
+                                               n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
+    else if (L.any && L.kind == ScoreKind::space)  // (score_space_engine.hip: mono rows into a timeline of n_channels speakers)
         HIP_TRY(ctx, dusp::launch_score_space(d_gains, (const dusp::ScoreSpaceTap *)(d_image + L.space_at), d_rows, d_block_first, d_entries, d_init, d_out, (uint32_t)n_channels,
                                               n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
     else if (L.any && L.frac)  // (score_frac_engine.hip: plain rows of n_channels, or — d_pans — panned mono rows)
         HIP_TRY(ctx, dusp::launch_score_frac(d_gains, d_pans, (const dusp::ScoreFrac *)(d_image + L.frac_at), d_rows, d_block_first, d_entries, d_init, d_out,
                                              L.kind == ScoreKind::pan ? 1u : (uint32_t)n_channels, n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
-    else if (L.kind == ScoreKind::pan)
+    else if (L.kind == ScoreKind::pan || L.kind == ScoreKind::stereo)  // (stereo without voices: `|| 0`, or a copy, of both channels of d_init)
         HIP_TRY(ctx, dusp::launch_score_pan(d_gains, d_pans, d_rows, d_block_first, d_entries, d_init, d_out, n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
     else if (L.kind == ScoreKind::rows || L.kind == ScoreKind::space)  // (space without voices: `|| 0`, or a copy, of d_init's channels)
         HIP_TRY(ctx, dusp::launch_score_rows(d_gains, d_rows, d_block_first, d_entries, d_init, d_out, (uint32_t)n_channels, n_total, L.w_lo, L.w_hi, L.block_shift,
@@ -229,6 +235,20 @@ static int check_pans(dusp_ctx *ctx, const char *who, const float *h_pans, const
     for (size_t k = 0; k < n; k++) {
         if (!std::isfinite(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
         if (h_comp && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
+    }
+    return DUSP_OK;
+}
+
+// the kinds of a stereo call: voice k a row of channels[k] channels, one or two; a pan that is NaN says "not placed", and a voice of two
+// channels is not placed
+static int check_stereo(dusp_ctx *ctx, const char *who, const uint32_t *channels, const float *h_pans, const double *h_comp, size_t n) {
+    for (size_t k = 0; k < n; k++) {
+        if (channels[k] != 1 && channels[k] != 2)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": voice " + std::to_string(k) + " has " + std::to_string(channels[k]) + " channels: a voice of a stereo piece has one or two");
+        if (std::isinf(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
+        if (channels[k] == 2 && !std::isnan(h_pans[k]))
+            CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": voice " + std::to_string(k) + " has two channels and a pan: a two-channel voice is not panned (its pan must be NaN)");
+        if (h_comp && !std::isnan(h_pans[k]) && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
     }
     return DUSP_OK;
 }
@@ -291,10 +311,12 @@ int dusp_score_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, 
 }
 
 // dusp_score_rows_device, (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device, (h_fracs: onsets between
-// samples) dusp_score_rows_frac_device, and (taps: rows of one channel into a timeline of taps->n_speakers) dusp_score_rows_space_device
+// samples) dusp_score_rows_frac_device, and (taps: rows of one channel into a timeline of taps->n_speakers) dusp_score_rows_space_device,
+// and (h_row_channels: rows of one and of two channels — n_channels is 1 — with NaN in h_pans for "not placed", into a timeline of two)
+// dusp_score_rows_stereo_device
 static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
                              const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw,
-                             float *d_out, void *stream_, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr) {
+                             float *d_out, void *stream_, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr, const uint32_t *h_row_channels = nullptr) {
     if (!ctx) return DUSP_ERR_ARG;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
@@ -302,29 +324,33 @@ static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const 
         if (int rc = check_taps(ctx, who, taps->h_delays, taps->h_gains, n_voices, taps->n_speakers, n_total_samples)) return rc;
     const size_t n_out_channels = taps ? taps->n_speakers : h_pans ? 2 : n_channels;  // (the timeline's)
     if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    const bool stereo = h_row_channels != nullptr;
+    if (stereo && n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 0..2^24 voices");
+    if (stereo)  // (before the rows' sizes are looked at: they are channels x samples)
+        if (int rc = check_stereo(ctx, who, h_row_channels, h_pans, h_comp, n_voices)) return rc;
     if (!channels_in_range(n_channels) || n_voices > (1u << 24) || !samples_in_range(n_total_samples))
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..64 channels, 0..2^24 voices and 1..2^31 samples of timeline");
     if (n_out_channels * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
     if ((((uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
     for (size_t k = 0; k < n_voices; k++) {
-        if ((uint64_t)h_row_samples[k] * n_channels > dusp::kScoreRowMax)
+        if ((uint64_t)h_row_samples[k] * (stereo ? h_row_channels[k] : n_channels) > dusp::kScoreRowMax)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + ": channels x row samples must not exceed 2^31");
         if (h_row_samples[k] && !h_rows[k]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " is NULL");
         if (h_row_samples[k] && ((uintptr_t)h_rows[k] & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " must be 4-byte aligned");
     }
-    if (h_pans)
+    if (h_pans && !stereo)
         if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
     if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_of(ctx, stream_);
-    ScoreLaunch L(taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
+    ScoreLaunch L(stereo ? ScoreKind::stereo : taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
     return score_device_call(
         ctx, stream, n_voices != 0, L,
         [&]() {
             static_assert(sizeof(const float *) == sizeof(uint64_t), "rows are handed to the planner as 64-bit addresses");
             if (int rc = score_rows_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples, /*whole_timeline=*/true,
-                                        score_plan_budget(ctx), L, nullptr, h_fracs, taps))
+                                        score_plan_budget(ctx), L, nullptr, h_fracs, taps, h_row_channels, stereo ? h_pans : nullptr))
                 return rc;
             if (h_pans) score_pans_add(ctx, h_pans, h_comp, n_voices, L);
             return (int)DUSP_OK;
@@ -410,10 +436,11 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
 
 // dusp_render_host_score_parts, (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan, (h_fracs:
 // onsets between samples, with or without pans) dusp_render_host_score_parts_frac, and (taps: mono parts into a timeline of
-// taps->n_speakers channels) dusp_render_host_score_parts_space
+// taps->n_speakers channels) dusp_render_host_score_parts_space, and (stereo: parts of one and of two output channels, h_pans with NaN for
+// "not placed", with or without h_fracs, into a timeline of two channels) dusp_render_host_score_parts_stereo
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
-                                   int format, int normalise, void *h_out, float *h_peak, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr) {
+                                   int format, int normalise, void *h_out, float *h_peak, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr, bool stereo = false) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
@@ -426,16 +453,20 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         if (int rc = check_taps(ctx, who, taps->h_delays, taps->h_gains, n_voices, taps->n_speakers, n_total_samples)) return rc;
     const size_t n_out_ch = taps ? taps->n_speakers : h_pans ? 2 : n_ch;  // (the timeline's)
     size_t n_listed = 0;
+    std::vector<size_t> part_ch(n_parts, n_ch);  // (a part's own: they differ in a stereo piece only)
     for (size_t p = 0; p < n_parts; p++) {
         if (!parts[p].prog) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the program of part " + std::to_string(p) + " is NULL");
         if (parts[p].prog->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " was built on another context: all parts of a piece share one");
-        if (h_pans && parts[p].prog->P.out_bufs.size() != 1)
+        part_ch[p] = parts[p].prog->P.out_bufs.size();
+        if (stereo && part_ch[p] != 1 && part_ch[p] != 2)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(part_ch[p]) + " output channels: a voice of a stereo piece has one or two");
+        if (!stereo && h_pans && parts[p].prog->P.out_bufs.size() != 1)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) +
                                             " output channels: a panned voice is mono");
         if (taps && parts[p].prog->P.out_bufs.size() != 1)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) +
                                             " output channels: a placed voice is mono");
-        if (parts[p].prog->P.out_bufs.size() != n_ch)
+        if (!stereo && parts[p].prog->P.out_bufs.size() != n_ch)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) + " output channels, part 0 has " +
                                             std::to_string(n_ch) + ": all parts of a piece have the same number");
         for (size_t q = 0; q < p; q++)
@@ -445,7 +476,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     }
     if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
-    if (h_pans)
+    if (h_pans && !stereo)
         if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
     if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
     // voice k of the chain: the next unused instance of part h_part_of[k]
@@ -454,13 +485,19 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         if (h_part_of[k] >= n_parts) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + " names part " + std::to_string(h_part_of[k]) + " of " + std::to_string(n_parts));
         instance_of[k] = used[h_part_of[k]]++;
     }
+    std::vector<uint32_t> row_channels;  // (a stereo piece: the voices' own)
+    if (stereo) {
+        row_channels.resize(n_voices);
+        for (size_t k = 0; k < n_voices; k++) row_channels[k] = (uint32_t)part_ch[h_part_of[k]];
+        if (int rc = check_stereo(ctx, who, row_channels.data(), h_pans, h_comp, n_voices)) return rc;
+    }
     for (size_t p = 0; p < n_parts; p++)
         if (used[p] != parts[p].n_instances || n_listed != n_voices)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of names part " + std::to_string(p) + " " + std::to_string(used[p]) + " times, the part has " +
                                             std::to_string(parts[p].n_instances) + " instances: every instance is one voice of the chain");
     for (size_t p = 0; p < n_parts; p++) {  // (the sizes the tiles are made from; tiled_batch_prepare below refuses the rest, in front of any render)
         if (int rc = check_batch(ctx, who, parts[p].n_instances, parts[p].n_voice_samples)) return rc;
-        if (n_ch * parts[p].n_voice_samples > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x voice samples must not exceed 2^31");
+        if (part_ch[p] * parts[p].n_voice_samples > kMixRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x voice samples must not exceed 2^31");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the tiles: runs of the chain's voices whose rows together fit tile_bytes
@@ -469,7 +506,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     size_t staged = 0, free_bytes = 0, total_bytes = 0;
     for (size_t k = 0; k < n_voices; k++) {
         row_samples[k] = (uint32_t)parts[h_part_of[k]].n_voice_samples;  // (at most 2^31 / channels: tiled_batch_prepare)
-        row_bytes[k] = (uint64_t)n_ch * row_samples[k] * sizeof(float);
+        row_bytes[k] = (uint64_t)part_ch[h_part_of[k]] * row_samples[k] * sizeof(float);
     }
     for (size_t p = 0; p < n_parts; p++) staged += parts[p].prog->d_host_out.cap * sizeof(float);
     if (tile_bytes == 0 && ctx->knobs.mix_tile_mb <= 0) HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
@@ -492,7 +529,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     }
     // every tile's plan, over the tile's union window, made up front under the call's one budget and uploaded once: the rows' addresses
     // are known, since the tile buffers stand
-    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows));
+    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(stereo ? ScoreKind::stereo : taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows));
     std::vector<std::vector<unsigned char>> renders(n_tiles, std::vector<unsigned char>(n_parts, 0));  // does part p render in tile i?
     const size_t tile_budget = score_plan_budget(ctx) / n_tiles;
     if (int rc = score_image_begin(ctx)) return rc;
@@ -506,10 +543,11 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
             rows.resize(n);
             for (size_t k = 0; k < n; k++) {
                 const size_t p = h_part_of[lo + k];
-                rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * n_ch * parts[p].n_voice_samples);
+                rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * part_ch[p] * parts[p].n_voice_samples);
             }
             if (int rc = score_rows_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
-                                        /*whole_timeline=*/false, tile_budget, launches[i], &listed, h_fracs ? h_fracs + lo : nullptr, taps ? &tile_taps : nullptr))
+                                        /*whole_timeline=*/false, tile_budget, launches[i], &listed, h_fracs ? h_fracs + lo : nullptr, taps ? &tile_taps : nullptr,
+                                        stereo ? row_channels.data() + lo : nullptr, stereo ? h_pans + lo : nullptr))
                 return rc;
             if (h_pans) score_pans_add(ctx, h_pans + lo, h_comp ? h_comp + lo : nullptr, n, launches[i]);
             for (size_t k = 0; k < n; k++)
@@ -592,6 +630,26 @@ int dusp_render_host_score_parts_space(const dusp_score_part *parts, size_t n_pa
     const ScoreTaps taps{n_speakers, h_delays, h_tap_gains};
     return render_host_score_parts("dusp_render_host_score_parts_space", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, nullptr, nullptr, n_total_samples,
                                    tile_bytes, format, normalise, h_out, h_peak, nullptr, &taps);
+}
+
+int dusp_score_rows_stereo_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, const uint32_t *h_row_channels, size_t n_voices,
+                                  const int64_t *h_onsets, const double *h_fracs, const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp,
+                                  size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (n_voices && !h_pans) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_stereo_device: h_pans is NULL");
+    if (n_voices && !h_row_channels) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_stereo_device: h_row_channels is NULL");
+    static const float no_pans[1] = {0.0f};  // (no voices: `|| 0`, or a copy, of both channels of d_init)
+    return score_rows_device(ctx, "dusp_score_rows_stereo_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, n_voices ? h_pans : no_pans, h_comp,
+                             n_total_samples, d_init, raw, d_out, stream_, h_fracs, nullptr, n_voices ? h_row_channels : nullptr);
+}
+
+int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                        const double *h_fracs, const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp,
+                                        size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
+    if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
+    if (!h_pans) CTX_FAIL(parts[0].prog->ctx, DUSP_ERR_ARG, "dusp_render_host_score_parts_stereo: h_pans is NULL");
+    return render_host_score_parts("dusp_render_host_score_parts_stereo", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak, h_fracs, nullptr, /*stereo=*/true);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// score_device.hpp — what the five score kernels share (score_engine.hip, score_rows_engine.hip, score_pan_engine.hip,
-// score_frac_engine.hip, score_space_engine.hip): `x || 0`, a plan record as one wide load, the typedefs of a batch's indices and of a row's floats, the head of
+// score_device.hpp — what the six score kernels share (score_engine.hip, score_rows_engine.hip, score_pan_engine.hip,
+// score_frac_engine.hip, score_space_engine.hip, score_stereo_engine.hip): `x || 0`, a plan record as one wide load, the typedefs of a batch's indices and of a row's floats, the head of
 // every kernel (lane to sample, window test) and the groups a launch covers.  The lookup of the block's list behind that head stays in
 // each kernel: as a shared function it changed the order of two scalar moves in three of the four device listings
 // (profiles/score_refactor.txt).  Like the engines, this compiles for the host under tests/native/hip_host_stub, where the kernels' text

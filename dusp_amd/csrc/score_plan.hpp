@@ -42,7 +42,7 @@ struct alignas(32) ScoreRow {
     int64_t onset;
     uint32_t lo, hi;
     uint64_t row;     // device address of the voice's channel 0, sample 0
-    uint32_t stride;  // floats from one channel of this voice to the next
+    uint32_t stride;  // floats from one channel of this voice to the next (a stereo plan's mono rows: kScoreStrideMono, kScoreStridePanned)
     uint32_t pad;     // 0; a voice with a fraction of a sample in its onset (score_rows_plan's fracs): its unclipped length, never 0
 };
 static_assert(sizeof(ScoreRow) == 32, "one eight-dword scalar load");
@@ -202,11 +202,17 @@ inline ScoreSpaceTap score_space_tap(double delay, double gain) {
 // timeline's end takes no part whatever its shifts are (they are not negative), so nothing is ever added to an onset near the top of
 // int64; one far in front of sample 0 is dropped before its end is clipped.  The taps go up as a parallel array, 32 bytes a voice and
 // channel ON TOP of the plan's byte budget.
+// row_channels (nullptr: every row has the call's one channel count and its record's stride is row_samples[k], as ever): voice k is a
+// row of row_channels[k] channels, 1 or 2, into a timeline of two (score_stereo_engine.hip; dusp_amd/mix.py score_chain_rows_stereo), and
+// its record's stride says which kind of voice it is: row_samples[k], the floats from channel 0 to channel 1, for a row of two channels
+// (1 .. 2^30), kScoreStridePanned for a mono row with a finite pans[k], kScoreStrideMono for a mono row that is not placed (pans
+// nullptr, or pans[k] NaN).  Spans, lists and everything else are the same arithmetic.
 // Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, row_samples[k]].
 // Needs n <= 2^32 - 1, row_samples and n_total <= kScoreRowMax.
+constexpr uint32_t kScoreStrideMono = 0u, kScoreStridePanned = 0xffffffffu;
 inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n, uint64_t n_total,
                                bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P, const double *fracs = nullptr, const ScoreSpaceTap *taps = nullptr,
-                               size_t taps_channels = 0) {
+                               size_t taps_channels = 0, const uint32_t *row_channels = nullptr, const float *pans = nullptr) {
     P = ScoreRowsPlan();
     P.voices.assign(n, ScoreRow{0, 0u, 0u, 0u, 0u, 0u});
     const int64_t total = (int64_t)n_total;
@@ -238,7 +244,8 @@ inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, co
         if (len == 0 || onset >= total || (two_taps ? onset < -len : onset <= -len)) continue;
         // here -2^31 <= -len <= onset < n_total <= 2^31: onset + len + 1 cannot overflow
         const int64_t lo = std::max<int64_t>(onset, 0), hi = std::min(onset + len + (two_taps ? 1 : 0), total);
-        P.voices[k] = ScoreRow{onset, (uint32_t)lo, (uint32_t)hi, rows ? rows[k] : 0, row_samples[k], two_taps ? (uint32_t)len : 0u};
+        const uint32_t stride = !row_channels || row_channels[k] == 2 ? row_samples[k] : pans && std::isfinite(pans[k]) ? kScoreStridePanned : kScoreStrideMono;
+        P.voices[k] = ScoreRow{onset, (uint32_t)lo, (uint32_t)hi, rows ? rows[k] : 0, stride, two_taps ? (uint32_t)len : 0u};
         if (first_listed == n) first_listed = k;
         t_lo = std::min(t_lo, lo);
         t_hi = std::max(t_hi, hi);

@@ -756,6 +756,7 @@ typedef struct {
     double *delays, *tap_gains; /* renderPieceSpace: a delay and a gain per voice and speaker, else NULL */
     size_t n_speakers;
     float peak;
+    int stereo;       /* renderPieceStereo: parts of one or two channels, pans with NaN for "not placed", fracs or NULL */
     int format, normalise, rc;
     char err[512];
 } piece_job;
@@ -795,7 +796,10 @@ static void piece_execute(napi_env env, void *data) {
         j->parts[p].prog = j->pbs[p]->prog;
     }
     if (j->rc == DUSP_OK) {
-        if (j->delays)
+        if (j->stereo)
+            j->rc = dusp_render_host_score_parts_stereo(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->fracs, j->lengths, j->gains, j->pans, j->comp, j->n_total,
+                                                        j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+        else if (j->delays)
             j->rc = dusp_render_host_score_parts_space(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, j->n_speakers, j->delays, j->tap_gains,
                                                        j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
         else if (j->fracs)
@@ -859,13 +863,22 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *   -> either of the two with voice k starting at onsets[k] + fracs[k] samples, 0 <= fracs[k] < 1 (dusp_render_host_score_parts_frac)
  * renderPieceSpace(the same twelve, nSpeakers, delays Float64Array, tapGains Float64Array)
  *   -> the first over MONO parts, nSpeakers channels out (dusp_render_host_score_parts_space: voice k heard by speaker c through the gain
- *      tapGains[k * nSpeakers + c] and a delay of delays[k * nSpeakers + c] samples; the gains computed by the caller with Math.pow) */
-static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space */
+ *      tapGains[k * nSpeakers + c] and a delay of delays[k * nSpeakers + c] samples; the gains computed by the caller with Math.pow)
+ * renderPieceStereo(the same twelve, fracs Float64Array | null, pans Float32Array, comp Float64Array)
+ *   -> the first over parts of ONE OR TWO output channels, two channels out (dusp_render_host_score_parts_stereo: a mono voice panned to
+ *      pans[k], or heard alike on both channels where pans[k] is NaN; a voice of two channels, whose pan is NaN, keeps its channels) */
+static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo */
     napi_value argv[15];
     char msg[256];
     if (!get_args(env, info, form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
-    int panned = form == 1;
-    const int pans_at = form == 2 ? 13 : 12;
+    int panned = form == 1 || form == 4;
+    int with_fracs = form == 2;
+    const int pans_at = form == 2 || form == 4 ? 13 : 12;
+    if (form == 4) {
+        napi_valuetype ft = napi_undefined;
+        napi_typeof(env, argv[12], &ft);
+        with_fracs = ft != napi_null && ft != napi_undefined;
+    }
     if (form == 2) {
         napi_valuetype pt = napi_undefined;
         napi_typeof(env, argv[13], &pt);
@@ -938,8 +951,9 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         const double ni = ((const double *)inst)[p], nv = ((const double *)vs)[p];
         if (j->pbs[p]->cb != j->pbs[0]->cb) bad = "all parts of a piece are built on one context";
         else if (!(ni >= 1 && ni <= 16777216.0 && ni == (double)(size_t)ni && nv >= 1 && nv <= 2147483648.0 && nv == (double)(size_t)nv)) bad = "nInstances / nVoiceSamples out of range";
-        else if (p && pi.n_out_channels != n_channels) bad = "all parts of a piece have one number of output channels";
-        else if (panned && pi.n_out_channels != 1) bad = "a panned voice is mono: every part has one output channel";
+        else if (form == 4 && pi.n_out_channels != 1 && pi.n_out_channels != 2) bad = "a voice of a stereo piece has one or two channels";
+        else if (form != 4 && p && pi.n_out_channels != n_channels) bad = "all parts of a piece have one number of output channels";
+        else if (form != 4 && panned && pi.n_out_channels != 1) bad = "a panned voice is mono: every part has one output channel";
         else if (form == 3 && pi.n_out_channels != 1) bad = "a placed voice is mono: every part has one output channel";
         if (bad) break;
         n_channels = pi.n_out_channels;
@@ -987,7 +1001,8 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         }
         n_channels = 2; /* the timeline's */
     }
-    if (!bad && form == 2) {
+    j->stereo = form == 4;
+    if (!bad && with_fracs) {
         void *fd;
         size_t n_f = 0;
         if (!typed_array(env, argv[12], napi_float64_array, &fd, &n_f) || n_f != n_voices) bad = "fracs must be a Float64Array of one value per voice";
@@ -1045,6 +1060,7 @@ static napi_value fn_render_piece(napi_env env, napi_callback_info info) { retur
 static napi_value fn_render_piece_pan(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 1); }
 static napi_value fn_render_piece_frac(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 2); }
 static napi_value fn_render_piece_space(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 3); }
+static napi_value fn_render_piece_stereo(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 4); }
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1078,7 +1094,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
-        {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space},
+        {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -450,9 +450,11 @@ function wholeSamples(who, name, values, count) {
  * channels out, through the piece's call with the score as its one part (voiceDuration is one number; tileInstances does not apply).
  * fracs: as renderPiece's — voice k starts at onsets[k] + fracs[k] samples — through the piece's call too.
  * places (with speakers, decibelsPerMetre, sampleDelayPerMetre): as renderPiece's — mono voices, one channel a speaker — through the
- * piece's call too. */
+ * piece's call too.
+ * stereo: true — as renderPiece's: voices of one or two channels, two channels out, pans optional and null / NaN for a voice that is not
+ * placed — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
-const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places)
+const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -541,6 +543,30 @@ function panArrays(pans, count) {
   for (let k = 0; k < count; k++) if (!Number.isFinite(p[k])) throw 'dusp-hip: the pan of voice ' + k + ' is not finite'
   return { pans: p, comp: Float64Array.from(p, (x) => Math.pow(10, ((1 - Math.abs(x)) * 1.5) / 20)) }
 }
+
+/* pans of `count` voices of a stereo piece -> { pans: Float32Array with NaN for "not placed", comp: Float64Array }: undefined / null
+ * (nothing placed) or one entry a voice, a number, null or NaN; an infinite pan is refused (twin of runtime.py stereo_pan_arrays).  The
+ * compensation is panArrays'; an unplaced voice's is 1 and is not read. */
+function stereoPanArrays(pans, count) {
+  if (!given(pans)) pans = new Float32Array(count).fill(NaN)
+  const ok = Array.isArray(pans) || pans instanceof Float32Array || pans instanceof Float64Array
+  const p = ok ? (pans instanceof Float32Array ? pans : Float32Array.from(pans, (x) => (x === null ? NaN : x))) : null
+  if (!p || p.length !== count) throw 'dusp-hip: pans must have shape (voices=' + count + ',)'
+  for (let k = 0; k < count; k++) if (p[k] === Infinity || p[k] === -Infinity) throw 'dusp-hip: the pan of voice ' + k + ' is not finite'
+  return { pans: p, comp: Float64Array.from(p, (x) => (Number.isNaN(x) ? 1 : Math.pow(10, ((1 - Math.abs(x)) * 1.5) / 20))) }
+}
+
+/* channels[k]: the channels of voice k, pans: stereoPanArrays'.  A voice of a stereo piece is mono or has two channels, and only a mono
+ * voice is placed: refused by string otherwise (twin of mix.py check_stereo_kinds). */
+function checkStereoKinds(channels, pans) {
+  channels.forEach((c, k) => {
+    if (c !== 1 && c !== 2) throw 'dusp-hip: a voice of a stereo piece has one or two channels: voice ' + k + ' has ' + c
+    if (c === 2 && !Number.isNaN(pans[k])) throw 'dusp-hip: a two-channel voice is not panned: the pan of voice ' + k + ' must be NaN (not placed)'
+  })
+  return 2
+}
+
+const STEREO_NO_PLACES = 'dusp-hip: places and stereo do not go together: a placed voice is mono and the speakers are the channels'
 
 /* fracs of `count` voices -> Float64Array: checked — one finite fraction of a sample a voice, 0 <= f < 1 — by the strings the library
  * uses (twin of mix.py check_fracs). */
@@ -644,6 +670,8 @@ function spaceTaps(places, { speakers, decibelsPerMetre = -3, sampleDelayPerMetr
 
 async function pieceCall(who, outlets, opts, format, normalise, onePart = false) {
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
+  const stereo = opts.stereo === true
+  if (given(opts.places) && stereo) throw STEREO_NO_PLACES
   if (given(opts.places) && (given(opts.pans) || given(opts.fracs))) throw SPACE_ALONE
   const extractions = outlets.map((o) => extract(o))
   if (extractions.length === 0) throw 'dusp-hip: no instances'
@@ -669,7 +697,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     if (g.length !== count) throw 'dusp-hip: ' + who + ': gains must hold one value per outlet'
   }
   if (!Number.isInteger(tileBytes) || tileBytes < 0) throw 'dusp-hip: ' + who + ': tileBytes must be 0 (the default tile) or a whole number of bytes'
-  const panned = opts.pans !== undefined && opts.pans !== null ? panArrays(opts.pans, count) : null
+  const panned = stereo ? stereoPanArrays(opts.pans, count) : opts.pans !== undefined && opts.pans !== null ? panArrays(opts.pans, count) : null
   const fracs = opts.fracs !== undefined && opts.fracs !== null ? fracArrays(opts.fracs, count) : null
   let taps = null
   if (given(opts.places)) {
@@ -680,14 +708,15 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   if (onePart && grouped.parts.length !== 1) throw 'dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments'
   const n = native()
   const channels = grouped.parts.map((part) => n.descriptorChannels(part.uni.words))
-  const nChannels = taps ? checkSpaceChannels(channels, taps.nSpeakers) : panned ? checkPanChannels(channels) : checkPieceChannels(channels)
+  const nChannels = stereo ? checkStereoKinds(Array.from(grouped.partOf, (p) => channels[p]), panned.pans) : taps ? checkSpaceChannels(channels, taps.nSpeakers) : panned ? checkPanChannels(channels) : checkPieceChannels(channels)
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
   const progs = []
   try {
     for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
-    const result = taps ? await n.renderPieceSpace(...args, taps.nSpeakers, taps.delays, taps.gains)
+    const result = stereo ? await n.renderPieceStereo(...args, fracs, panned.pans, panned.comp)
+      : taps ? await n.renderPieceSpace(...args, taps.nSpeakers, taps.delays, taps.gains)
       : fracs ? await n.renderPieceFrac(...args, fracs, panned ? panned.pans : null, panned ? panned.comp : null)
       : panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
     return { nSamples, nChannels, sampleRate, result }
@@ -713,7 +742,13 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * coordinates), decibelsPerMetre (-3) and sampleDelayPerMetre (sample rate / 343): the voices are MONO circuits and every speaker — a
  * channel of the result — hears voice k attenuated and delayed by its distance, what the reference's Space patch does behind a sound
  * (dusp_render_host_score_parts_space; spaceTaps makes the gain and the delay per voice and speaker; include/dusp_hip.h says where
- * the reference's own wiring departs from it).  Not together with pans or fracs. */
+ * the reference's own wiring departs from it).  Not together with pans or fracs.
+ * stereo: true — a voice may be a MONO circuit or one of TWO channels, side by side, and the result has two channels
+ * (dusp_render_host_score_parts_stereo).  pans may be left out (nothing is placed) or hold null / NaN for a voice that is not placed: a
+ * mono voice with a pan is the panned voice above, a mono voice without one is heard alike on both channels (the reference's Sum reads
+ * a mono input for every channel of a wider one), a voice of two channels keeps its channels and takes no pan (the Pan unit's inlet is
+ * mono).  What the reference renders for Sum.many over such voices behind their Delays, bit for bit.  fracs work as above; places are
+ * refused.  Without the option every call is what it was. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   const channelData = []
@@ -774,6 +809,8 @@ module.exports.structureKey = structureKey
 module.exports.checkPieceChannels = checkPieceChannels
 module.exports.checkPanChannels = checkPanChannels
 module.exports.panArrays = panArrays
+module.exports.stereoPanArrays = stereoPanArrays
+module.exports.checkStereoKinds = checkStereoKinds
 module.exports.fracArrays = fracArrays
 module.exports.splitOnsets = splitOnsets
 module.exports.spaceTaps = spaceTaps

@@ -275,6 +275,74 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
     return _chain(rows, 2, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw, place=pan)
 
 
+def stereo_pans(pans, n):
+    """pans of n voices of a stereo piece -> float32 [n], NaN where a voice is not placed: None (nothing placed), or one entry a voice,
+    a number or None.  An infinite pan is refused; NaN is "not placed".  Needs no device."""
+    if pans is None:
+        return np.full(n, np.nan, dtype=np.float32)
+    if isinstance(pans, (list, tuple)):
+        pans = [np.nan if p is None else p for p in pans]
+    with np.errstate(all="ignore"):
+        pans = np.ascontiguousarray(pans, dtype=np.float32)
+    if pans.shape != (n,):
+        raise ValueError("dusp-hip: pans must have shape (voices=%d,)" % n)
+    if np.any(np.isinf(pans)):
+        raise ValueError("dusp-hip: the pan of voice %d is not finite" % int(np.argmax(np.isinf(pans))))
+    return pans
+
+
+def check_stereo_kinds(channels, pans):
+    """channels[k]: the channels of voice k's row, pans: stereo_pans' array.  A voice of a stereo piece is mono or has two channels, and
+    only a mono voice is placed: refused by string otherwise."""
+    for k, c in enumerate(channels):
+        if c not in (1, 2):
+            raise ValueError("dusp-hip: a voice of a stereo piece has one or two channels: voice %d has %d" % (k, c))
+        if c == 2 and not np.isnan(pans[k]):
+            raise ValueError("dusp-hip: a two-channel voice is not panned: the pan of voice %d must be NaN (not placed)" % k)
+
+
+def score_chain_rows_stereo(rows, onsets, pans, n_total, lengths=None, gains=None, init=None, raw=False, comp=None, fracs=None):
+    """rows: a list of float32 arrays [1, samples_k] or [2, samples_k], onsets int64 [voices], pans float32 [voices] with NaN for "not
+    placed" (None: nothing placed) -> float32 [2, n_total]: the contract of dusp_score_rows_stereo_device.  The kind of a voice is the
+    voice's own: with x_c[s] = f32(row_k[c][s] * g_k) when there are gains and row_k[c][s] otherwise, voice k adds
+
+        mono, finite pan:   f32(((f64(x_0) * (1 - f64(p))) / 2) * comp_k)  left,  the same with 1 + f64(p) right  (score_chain_rows_panned's term, Pan.js:21-22)
+        mono, pan NaN:      x_0 left,  x_0 right     (Sum.js:37-38: a mono input feeds every channel of a wider one)
+        two channels:       x_0 left,  x_1 right     (its pan must be NaN: Pan's inlet is mono, Pan.js:6)
+
+    Everything else — acc = f32(acc + term) per channel in voice order, no add where a voice does not cover t, init, raw, `acc || 0`,
+    lengths clipped in int64, onsets of any sign, windows — is score_chain_rows' word for word, and with fracs the two taps of
+    two_tap_terms are applied per channel to the placed values, as score_chain_rows_panned does.  comp: float64 [voices] (None:
+    pan_comp(pans); an unplaced voice's is not used).  It is what the reference renders for Sum.many(Delay(P_k, onset_k + frac_k,
+    maxDelay)), P_k = Pan(Multiply(v_k, g_k), p_k) for a panned voice and Multiply(v_k, g_k), of one or two channels, otherwise.  All
+    voices mono with finite pans gives score_chain_rows_panned's bits, all voices two-channel score_chain_rows'."""
+    rows = [np.asarray(r, dtype=np.float32) for r in rows]
+    n = len(rows)
+    if any(r.ndim != 2 for r in rows):
+        raise ValueError("dusp-hip: every row must have shape (channels, samples)")
+    n_total = _timeline(n_total)
+    onsets = _whole(onsets, n, "onsets")
+    pans = stereo_pans(pans, n)
+    check_stereo_kinds([r.shape[0] for r in rows], pans)
+    if comp is None:
+        comp = pan_comp(np.where(np.isnan(pans), np.float32(0), pans))
+    else:
+        comp = np.asarray(comp, dtype=np.float64)
+        if comp.shape != (n,):
+            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
+
+    def place(k, x):
+        if x.shape[0] == 2:
+            return x
+        if np.isnan(pans[k]):
+            return np.concatenate([x, x])
+        xd, p = x[0].astype(np.float64), np.float64(pans[k])  # the Pan unit: float64 operations, each rounded by itself; one rounding to f32
+        return np.stack([(((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32),
+                         (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)])
+
+    return _chain(rows, 2, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw, place=place)
+
+
 # ---- Space placement: a delay and a gain per voice and speaker (DESIGN.md 6.12) ----
 
 SPACE_MAX_SPEAKERS = 8

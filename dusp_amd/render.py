@@ -243,7 +243,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -258,14 +258,18 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     with pans.
 
     places (with speakers, decibels_per_metre, sample_delay_per_metre): as render_piece's — mono voices, one channel a speaker; the
-    piece's call with the score as its one part, as with pans."""
-    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre))
+    piece's call with the score as its one part, as with pans.
+
+    stereo=True: as render_piece's — voices of one or two channels, two channels out, pans optional and None / NaN for a voice that is
+    not placed; the piece's call with the score as its one part, as with pans."""
+    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre),
+                         stereo=stereo)
 
 
-def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, pcm=None, space=None):
+def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, pcm=None, space=None, stereo=False):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if pans is not None or fracs is not None or space is not None:
-        return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, True, fracs, pcm, space)
+    if pans is not None or fracs is not None or space is not None or stereo:
+        return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, True, fracs, pcm, space, stereo)
     if pcm is not None:
         _check_pcm(*pcm)
     uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
@@ -277,17 +281,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, (bit_depth, normalise),
-                         _space(places, speakers, decibels_per_metre, sample_delay_per_metre))
+                         _space(places, speakers, decibels_per_metre, sample_delay_per_metre), stereo)
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo), bit_depth)
 
 
 class PieceParts:
@@ -360,11 +364,21 @@ def _space(places, speakers, decibels_per_metre, sample_delay_per_metre):
     return None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre)
 
 
-def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None, one_part=False, fracs=None, space=None):
+def check_stereo_channels(channels, part_of, pans):
+    """channels[p]: the output channels of part p's circuit; part_of[k]: voice k's part; pans: float32 with NaN for "not placed".  A
+    voice of a stereo piece has one or two channels, and one of two is not placed: refused by string otherwise."""
+    mix.check_stereo_kinds([channels[p] for p in part_of], pans)
+    return 2
+
+
+def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None, one_part=False, fracs=None, space=None, stereo=False):
     """-> PieceParts, samples of timeline, onsets, lengths, gains, channels, pans, fracs, taps (all checked: nothing is built yet).  With
     pans the voices are mono and channels is the timeline's two; with a space (_space) they are mono, channels is the speakers' number
     and taps the (delays, gains) of mix.space_taps at the voices' sample rate; pans, fracs and taps come back as None where none were
-    given."""
+    given.  stereo: the voices have one or two channels, channels is the timeline's two, and pans come back as float32 with NaN
+    for a voice that is not placed."""
+    if space is not None and stereo:
+        raise ValueError(runtime.STEREO_NO_PLACES)
     if space is not None and (pans is not None or fracs is not None):
         raise ValueError(runtime.SPACE_ALONE)
     extractions = [descriptor.extract(o) for o in outlets]
@@ -382,7 +396,9 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None
         raise descriptor.DuspError("dusp-hip: voice_duration must cover at least one sample")
     n_total = _n_samples(duration, rate)
     onsets, lengths, gains = _voice_arrays(onsets, lengths, gains, n, np.array(voice_samples), "voices", "the voice's own samples")
-    if pans is not None:
+    if stereo:
+        pans, _ = runtime.stereo_pan_arrays(pans, n)
+    elif pans is not None:
         pans, _ = runtime.pan_arrays(pans, n)
     if fracs is not None:
         fracs = runtime.frac_arrays(fracs, n)
@@ -394,26 +410,28 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None
     if one_part and len(grouped.parts) != 1:  # (render_score with pans or fracs)
         raise descriptor.DuspError("dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments")
     channels = [runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts]
+    if stereo:
+        return grouped, n_total, onsets, lengths, gains, check_stereo_channels(channels, grouped.part_of, pans), pans, fracs, taps
     if taps is not None:
         return grouped, n_total, onsets, lengths, gains, check_space_channels(channels, taps[0].shape[1]), pans, fracs, taps
     return grouped, n_total, onsets, lengths, gains, check_pan_channels(channels) if pans is not None else check_piece_channels(channels), pans, fracs, taps
 
 
-def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0, pans=None, fracs=None, taps=None):
+def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0, pans=None, fracs=None, taps=None, stereo=False):
     ctx = context(grouped.sample_rate, device)
     programs = []
     try:
         for uni, _ in grouped.parts:
             programs.append(ctx.build(uni.words, engine))
         parts = [(prog, n_voice, uni.n_instances, uni.params) for prog, (uni, n_voice) in zip(programs, grouped.parts)]
-        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps)
+        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps, stereo=stereo)
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -436,32 +454,39 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     does behind a sound: Gain at decibels_per_metre and MonoDelay at sample_delay_per_metre (mix.space_taps makes the gain and the delay
     per voice and speaker with the reference's roundings, mix.score_chain_rows_placed is the contract; DESIGN.md 6.12 says where the
     reference's own wiring departs from it).  Level AND time differences between the speakers, where pans give level only.  Not
-    together with pans or fracs."""
+    together with pans or fracs.
+
+    stereo=True: a voice may be a MONO circuit or one of TWO channels (StereoDetune, MultiChannelOsc, Multiply(osc, [a, b])), side by
+    side, and the result has two channels.  pans may be left out (nothing is placed) or hold None / NaN for a voice that is not placed:
+    a mono voice with a pan is the panned voice above, a mono voice without one is heard alike on both channels (the reference's Sum
+    reads a mono input for every channel of a wider one), a voice of two channels keeps its channels and takes no pan (the Pan unit's
+    inlet is mono).  What the reference renders for Sum.many over such voices behind their Delays, bit for bit
+    (mix.score_chain_rows_stereo).  fracs work as above; places are refused."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs,
-                                space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre))
+                                space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo)
 
 
-def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, one_part, fracs, pcm=None, space=None):
+def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, one_part, fracs, pcm=None, space=None, stereo=False):
     """render_piece (pcm None) and render_piece_pcm (pcm = (bit_depth, normalise))"""
     if pcm is not None:
         _check_pcm(*pcm)
-    grouped, n_total, onsets, lengths, gains, channels, pans, fracs, taps = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, one_part, fracs, space)
+    grouped, n_total, onsets, lengths, gains, channels, pans, fracs, taps = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, one_part, fracs, space, stereo)
     return _delivered(pcm, grouped.sample_rate, n_total, channels,
-                      lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps))
+                      lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps, stereo=stereo))
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs, (bit_depth, normalise),
-                                _space(places, speakers, decibels_per_metre, sample_delay_per_metre))
+                                _space(places, speakers, decibels_per_metre, sample_delay_per_metre), stereo)
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo), bit_depth)
 
 
 class PcmData:

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import _whole, check_fracs, check_taps, pan_comp
+from .mix import _whole, check_fracs, check_stereo_kinds, check_taps, pan_comp, stereo_pans
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -32,6 +32,7 @@ EXPORTS = [
     "dusp_score_rows_pan_device", "dusp_render_host_score_parts_pan",
     "dusp_score_rows_frac_device", "dusp_render_host_score_parts_frac",
     "dusp_score_rows_space_device", "dusp_render_host_score_parts_space",
+    "dusp_score_rows_stereo_device", "dusp_render_host_score_parts_stereo",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -109,6 +110,8 @@ def load():
     L.dusp_render_host_score_parts_frac.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_score_rows_space_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
     L.dusp_render_host_score_parts_space.argtypes = [vp, sz, sz, vp, vp, vp, vp, sz, vp, vp, sz, sz, ci, ci, vp, vp]
+    L.dusp_score_rows_stereo_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
+    L.dusp_render_host_score_parts_stereo.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -147,6 +150,23 @@ def pan_arrays(pans, n, comp=None):
     return pans, comp
 
 
+def stereo_pan_arrays(pans, n, comp=None):
+    """pans of n voices of a stereo piece -> (float32 [n] with NaN for "not placed", float64 [n] compensation): None (nothing placed)
+    or one entry a voice, a number, None or NaN; an infinite pan is refused (dusp_amd/mix.py stereo_pans).  The compensation is
+    pan_arrays'; an unplaced voice's is 1 and is not read.  Needs no device."""
+    pans = stereo_pans(pans, n)
+    placed = ~np.isnan(pans)
+    if comp is None:
+        comp = np.ones(n, dtype=np.float64)
+        comp[placed] = pan_comp(pans[placed])
+    else:
+        comp = np.ascontiguousarray(comp, dtype=np.float64)
+        if comp.shape != (n,):
+            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
+    return pans, comp
+
+
+STEREO_NO_PLACES = "dusp-hip: places and stereo do not go together: a placed voice is mono and the speakers are the channels"
 SPACE_ALONE = "dusp-hip: places stand alone: together with pans or fracs they are refused (a sub-sample onset in front of a Space would be a second two-tap stage)"
 
 
@@ -424,8 +444,28 @@ class Context:
         self._check(self._L.dusp_score_rows_space_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, delays.shape[1], _ptr(onsets, n), _ptr(lengths), d_gains,
                                                          _ptr(delays, n), _ptr(tap_gains, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
+    def score_rows_stereo(self, rows, row_samples, row_channels, onsets, pans, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, comp=None,
+                          fracs=None, stream=None):
+        """score_rows_device over rows of ONE OR TWO channels into a timeline of two (dusp_score_rows_stereo_device; dusp_amd/mix.py
+        score_chain_rows_stereo is the contract): rows are the voices' DEVICE pointers, voice k planar f32 [row_channels[k]][row_samples[k]];
+        pans a HOST array of f32 with NaN (or None) for a voice that is not placed (None: nothing placed) — a mono voice with a finite
+        pan is score_rows_pan's voice, one without feeds both channels, a voice of two channels is not placed; fracs as score_rows_frac's
+        (None: all zero); d_init (which may be d_out) and d_out f32 [2][n_total_samples].  score_last_ms() reports the call."""
+        n = len(rows)
+        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
+        channels = np.asarray(row_channels) if n else np.zeros(0, dtype=np.uint32)
+        if channels.shape != (n,) or channels.dtype.kind not in "iu":
+            raise ValueError("dusp-hip: row_channels must be whole numbers of shape (voices=%d,)" % n)
+        pans, comp = stereo_pan_arrays(pans, n, comp)
+        check_stereo_kinds(channels.tolist(), pans)
+        channels = np.ascontiguousarray(channels, dtype=np.uint32)
+        if fracs is not None:
+            fracs = frac_arrays(fracs, n)
+        self._check(self._L.dusp_score_rows_stereo_device(self._h, _ptr(pointers, n), _ptr(samples, n), _ptr(channels, n), n, _ptr(onsets, n), _ptr(fracs, n), _ptr(lengths),
+                                                          d_gains, _ptr(pans, n), _ptr(comp, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None, taps=None):
+                           pans=None, fracs=None, taps=None, stereo=False):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -437,7 +477,12 @@ class Context:
         contracts above with fracs), with or without pans.
         taps = (delays, gains), f64 [voices][C] each: the parts are MONO and voice k is heard by speaker c through gains[k][c] and a
         delay of delays[k][c] samples (dusp_render_host_score_parts_space; mix.score_chain_rows_placed): the result has C channels.
-        Not together with pans or fracs."""
+        Not together with pans or fracs.
+        stereo=True: the parts have ONE OR TWO output channels and the result has two (dusp_render_host_score_parts_stereo;
+        mix.score_chain_rows_stereo): pans may be None (nothing placed) or hold None / NaN for a voice that is not placed, and a voice
+        of a two-channel part is not placed; fracs as above.  Not together with taps."""
+        if taps is not None and stereo:
+            raise ValueError(STEREO_NO_PLACES)
         if taps is not None and (pans is not None or fracs is not None):
             raise ValueError(SPACE_ALONE)
         if not parts:
@@ -469,10 +514,18 @@ class Context:
             n_ch = delays.shape[1]  # (parts that are not mono: the library refuses them)
             entry = self._L.dusp_render_host_score_parts_space
             args[7:7] = (n_ch, delays.ctypes.data, tap_gains.ctypes.data)
-        if pans is not None:
+        if stereo:
+            pans, comp = stereo_pan_arrays(pans, n)
+            check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], pans)
+            n_ch = 2
+        elif pans is not None:
             pans, comp = pan_arrays(pans, n)
             n_ch = 2  # (parts that are not mono: the library refuses them)
-        if fracs is not None:  # (the fractions behind the onsets; the pans and their compensation, or two NULLs, behind the gains)
+        if stereo:  # (the fractions, or NULL, behind the onsets; the pans and their compensation behind the gains)
+            entry = self._L.dusp_render_host_score_parts_stereo
+            args[7:7] = (pans.ctypes.data, comp.ctypes.data)
+            args[5:5] = (_ptr(fracs),)
+        elif fracs is not None:  # (the fractions behind the onsets; the pans and their compensation, or two NULLs, behind the gains)
             entry = self._L.dusp_render_host_score_parts_frac
             args[7:7] = (_ptr(pans), _ptr(comp))
             args[5:5] = (fracs.ctypes.data,)

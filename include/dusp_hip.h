@@ -523,6 +523,42 @@ int dusp_render_host_score_parts_space(const dusp_score_part *parts, size_t n_pa
                                        const double *h_delays, const double *h_tap_gains, size_t n_total_samples, size_t tile_bytes,
                                        int format, int normalise, void *h_out, float *h_peak);
 
+/* Stereo pieces: voices of one and of two channels side by side in a timeline of two, a mono voice panned or not (additions to ABI v7,
+ * detected by symbol).  The kind of a voice is the voice's own: with x_c[s] = f32(row_k[c][s] * g_k), or row_k[c][s], voice k adds
+ *     a mono row, h_pans[k] finite:  f32(((f64(x_0) * (1 - f64(p))) / 2) * comp_k) left, the same with 1 + f64(p) right
+ *                                    (dusp_score_rows_pan_device's term)
+ *     a mono row, h_pans[k] NaN:     x_0 left, x_0 right     (the reference's Sum reads a[channel % a.length]: Sum.js:34-38)
+ *     a row of two channels:         x_0 left, x_1 right     (h_pans[k] must be NaN: the Pan unit's inlet is mono, Pan.js:6)
+ * by acc = f32(acc + term) per channel in voice index order; with h_fracs, dusp_score_rows_frac_device's two taps are applied per
+ * channel to those values.  Everything else is dusp_score_rows_device's (dusp_amd/mix.py score_chain_rows_stereo is the contract in
+ * numpy).  It is what the reference renders for Sum.many(k -> Delay(P_k, onset_k + frac_k, maxDelay)), P_k = Pan(Multiply(v_k, g_k),
+ * p_k) for a panned voice and Multiply(v_k, g_k), of one or two channels, otherwise — within dusp_score_rows_frac_device's three
+ * limits where there are fractions.  All voices mono and panned gives dusp_score_rows_pan_device's bits, all voices of two channels
+ * dusp_score_rows_device's.
+ *   h_rows          device addresses; row k is planar f32 [h_row_channels[k]][h_row_samples[k]]
+ *   h_row_channels  u32 [n_voices], HOST memory, 1 or 2
+ *   h_fracs         as dusp_score_rows_frac_device's, or NULL.  A call none of whose listed voices has a fraction launches the kernel
+ *                   without the two-tap form
+ *   h_pans          f32 [n_voices], HOST memory; NaN: not placed.  h_comp as dusp_score_rows_pan_device's (an unplaced voice's is not read)
+ *   d_init, d_out   f32 [2][n_total_samples]; n_total_samples <= 2^30
+ * dusp_score_last_ms reports this call too.  DUSP_ERR_ARG, with a message that names the voice, checked before anything is launched:
+ * NULL h_pans or h_row_channels, a channel count that is neither 1 nor 2, an infinite pan, a voice of two channels whose pan is not
+ * NaN; and for everything dusp_score_rows_frac_device refuses. */
+int dusp_score_rows_stereo_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, const uint32_t *h_row_channels,
+                                  size_t n_voices, const int64_t *h_onsets, const double *h_fracs, const int64_t *h_lengths,
+                                  const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples,
+                                  const float *d_init, int raw, float *d_out, void *stream);
+
+/* dusp_render_host_score_parts over parts of ONE OR TWO output channels into a timeline of two: every tile is
+ * dusp_score_rows_stereo_device's launch, and a tile's rows take the bytes of their part's own channel count.  h_pans (never NULL) and
+ * h_fracs (or NULL) are per voice in chain order and checked before anything is rendered, as is every part's channel count ("part p
+ * has N output channels: a voice of a stereo piece has one or two").  Everything else, refusals included, is
+ * dusp_render_host_score_parts_frac's. */
+int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                        const int64_t *h_onsets, const double *h_fracs, const int64_t *h_lengths, const float *h_gains,
+                                        const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes, int format,
+                                        int normalise, void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

@@ -19,6 +19,10 @@
           kernel alone by dusp_score_last_ms: two speakers with every delay fractional, against the panned two-tap kernel over the same
           rows with every fraction non-zero (the same four taps per output pair; unchanged code) and against the whole-sample panned
           kernel; two speakers with every delay whole; six speakers with every delay fractional.
+  stereo  (--stereo; profiles/score_stereo.txt) the stereo kernel (dusp_score_rows_stereo_device) over dense rows of the dense shapes,
+          kernel alone by dusp_score_last_ms: all voices mono and panned, against the panned kernel over the same rows; all voices of two
+          channels, against the rows kernel over the same rows (both unchanged code); and a list that cycles through panned mono, plain
+          mono and two channels.  A report: no ratio is fixed in advance.
   piece   8192 notes of 0.5 s placed over 60 s in onset order: Program.render_score on the host's clock, against the render of the same
           notes alone (render_device into a preallocated buffer) and against the same piece with the onsets shuffled — every tile's
           union window is then the whole timeline, which is what the window is worth.  One run under DUSP_JIT_LOG=2 prints the plans'
@@ -223,6 +227,55 @@ def space(key, scale, ctxs, reps):
         print(line % ((label, t[0], t[1], read / t[0] / 1e9, t[0] / t_pan[0]) + t[2:]) + "   x%.3f of the panned two-tap kernel" % (t[0] / t_two[0]), flush=True)
 
 
+def stereo(key, scale, ctxs, reps):
+    import torch
+    V, n = max(64, DENSE[key][0] // scale), DENSE[key][1]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    ctx = ctxs["default"]
+    onsets = np.zeros(V, dtype=np.int64)
+    samples = np.full(V, n, dtype=np.uint32)
+    pans = (np.random.RandomState(5).random_sample(V) * 2 - 1).astype(np.float32)
+    acc = torch.empty((2, n), dtype=torch.float32, device="cuda")
+
+    def median_of(call):
+        kernel, plan, upload = [], [], []
+        for r in range(reps + 1):
+            call()
+            k, p, u = ctx.score_last_ms()
+            if r:
+                kernel.append(k), plan.append(p), upload.append(u)
+        return float(np.median(kernel)), min(kernel), float(np.median(plan)), float(np.median(upload))
+
+    line = "  %-44s kernel median %9.3f ms  fastest %9.3f   %6.2f GB read = %5.2f TB/s   [plan on the host %.2f ms, its upload %.2f ms]"
+    show = lambda label, t, read: print(line % ((label, t[0], t[1], read / 1e9, read / t[0] / 1e9) + t[2:]), flush=True)
+    print("stereo %s: %d voices x %d samples, all onsets 0, full lengths, into a timeline of 2 x %d" % (key, V, n, n), flush=True)
+    # one buffer of two-channel rows; a mono voice's row is the first channel of its own
+    wide = torch.empty((V, 2, n), dtype=torch.float32, device="cuda").normal_()
+    torch.cuda.synchronize()
+    pointers = [wide.data_ptr() + 8 * n * k for k in range(V)]
+    ones, twos, unplaced = np.ones(V, dtype=np.uint32), np.full(V, 2, dtype=np.uint32), np.full(V, np.nan, dtype=np.float32)
+    t_pan = median_of(lambda: ctx.score_rows_pan(pointers, samples, onsets, pans, n, acc.data_ptr(), stream=s))
+    show("panned kernel over mono rows", t_pan, V * n * 4)
+    t_all_pan = median_of(lambda: ctx.score_rows_stereo(pointers, samples, ones, onsets, pans, n, acc.data_ptr(), stream=s))
+    show("stereo kernel, all voices mono and panned", t_all_pan, V * n * 4)
+    t_rows = median_of(lambda: ctx.score_rows_device(pointers, samples, 2, onsets, n, acc.data_ptr(), stream=s))
+    show("rows kernel over two-channel rows", t_rows, V * 2 * n * 4)
+    t_all_two = median_of(lambda: ctx.score_rows_stereo(pointers, samples, twos, onsets, unplaced, n, acc.data_ptr(), stream=s))
+    show("stereo kernel, all voices of two channels", t_all_two, V * 2 * n * 4)
+    t_mono = median_of(lambda: ctx.score_rows_stereo(pointers, samples, ones, onsets, unplaced, n, acc.data_ptr(), stream=s))
+    show("stereo kernel, all voices plain mono", t_mono, V * n * 4)
+    kinds = np.arange(V) % 3  # panned mono, plain mono, two channels, ...
+    channels = np.where(kinds == 2, 2, 1).astype(np.uint32)
+    t_cycle = median_of(lambda: ctx.score_rows_stereo(pointers, samples, channels, onsets, np.where(kinds == 0, pans, np.float32(np.nan)).astype(np.float32), n, acc.data_ptr(), stream=s))
+    show("stereo kernel, the three kinds in turn", t_cycle, int(channels.sum()) * n * 4)
+    d_gains = torch.ones(V, dtype=torch.float32, device="cuda")
+    t_gain = median_of(lambda: ctx.score_rows_stereo(pointers, samples, channels, onsets, np.where(kinds == 0, pans, np.float32(np.nan)).astype(np.float32), n, acc.data_ptr(),
+                                                     d_gains=d_gains.data_ptr(), stream=s))
+    show("stereo kernel, the three kinds, with gains", t_gain, int(channels.sum()) * n * 4)
+    print("  stereo / panned kernel, all panned: x%.3f; stereo / rows kernel, all two-channel: x%.3f" % (t_all_pan[0] / t_pan[0], t_all_two[0] / t_rows[0]), flush=True)
+
+
 def piece(scale, ctxs, reps):
     import torch
     V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
@@ -266,13 +319,14 @@ def main():
     ap.add_argument("--pan", action="store_true", help="the pan leg alone, over the dense cases named by --cases")
     ap.add_argument("--frac", action="store_true", help="the sub-sample-onset leg alone, over the dense cases named by --cases")
     ap.add_argument("--space", action="store_true", help="the Space-placement leg alone, over the dense cases named by --cases")
+    ap.add_argument("--stereo", action="store_true", help="the stereo-piece leg alone, over the dense cases named by --cases")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
     for key in a.cases:
         if key in DENSE:
-            (space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
-    if "p" in a.cases and not a.pan and not a.frac and not a.space:
+            (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
+    if "p" in a.cases and not a.pan and not a.frac and not a.space and not a.stereo:
         piece(a.scale, ctxs, a.reps)
 
 
