@@ -1,8 +1,7 @@
 // abi_score.hip — the C ABI (include/dusp_hip.h): voices mixed at per-voice onsets into a timeline (score_plan.hpp and the six score
-// engines): the plans' image on the device, the one launch path, the device entries (dusp_score_device, dusp_score_rows_device and its
-// pan, frac and space forms) and the host round trips (dusp_render_host_score, dusp_render_host_score_parts and its pan, frac and space
-// forms), and the stereo forms in which a voice is a panned mono row, a plain mono row or a row of two channels (score_stereo_engine.hip;
-// dusp_score_rows_stereo_device, dusp_render_host_score_parts_stereo).
+// engines): the plans' image on the device, the placement of a rows call, the one launch path, the device entries (dusp_score_device;
+// dusp_score_rows_device and its pan, frac, space and stereo forms) and the host round trips (dusp_render_host_score;
+// dusp_render_host_score_parts and its pan, frac, space and stereo forms).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -20,10 +19,83 @@
 // channels, the mono ones panned or not, into a timeline of two (score_stereo_engine.hip; score_chain_rows_stereo)
 enum class ScoreKind { contiguous, rows, pan, space, stereo };
 
-// the taps of a space call: h_delays and h_gains f64 [voice][speaker] on the host (checked: check_taps)
-struct ScoreTaps {
-    size_t n_speakers;
-    const double *h_delays, *h_gains;
+// What places the voices of a rows call: its kind and the host arrays that go with it, one entry a voice, which the caller owns.  An
+// entry fills one in (nothing but the kind set: plain rows) and everything between it and the launch takes it by reference.
+struct ScorePlacement {
+    ScoreKind kind;                    // what the call is, whether or not it has voices: the entry says it, once
+    const double *h_fracs = nullptr;   // rows, pan, stereo: the voices' fractions of a sample (NULL: none)
+    const float *h_pans = nullptr;     // pan: a finite pan a voice.  stereo: NaN says "not placed", and a voice of two channels is not
+    const double *h_comp = nullptr;    // ... and the compensation (NULL: the reference's, by the host's pow, Pan.js:20)
+    size_t n_speakers = 0;             // space: the taps, f64 [voice][speaker] each
+    const double *h_delays = nullptr, *h_tap_gains = nullptr;
+    const uint32_t *h_row_channels = nullptr;  // stereo: voice k is a row of h_row_channels[k] channels, one or two
+    explicit ScorePlacement(ScoreKind kind_) : kind(kind_) {}
+    ScorePlacement(ScoreKind kind_, const double *fracs, const float *pans, const double *comp) : kind(kind_), h_fracs(fracs), h_pans(pans), h_comp(comp) {}
+    ScorePlacement(size_t speakers, const double *delays, const double *tap_gains) : kind(ScoreKind::space), n_speakers(speakers), h_delays(delays), h_tap_gains(tap_gains) {}
+
+    size_t timeline_channels(size_t voice_channels) const { return kind == ScoreKind::space ? n_speakers : kind == ScoreKind::rows ? voice_channels : 2; }
+    ScorePlacement tile(size_t lo) const {  // the same placement for the voices from `lo` on
+        ScorePlacement t = *this;
+        if (h_fracs) t.h_fracs += lo;
+        if (h_pans) t.h_pans += lo;
+        if (h_comp) t.h_comp += lo;
+        if (h_delays) t.h_delays += lo * n_speakers;
+        if (h_tap_gains) t.h_tap_gains += lo * n_speakers;
+        if (h_row_channels) t.h_row_channels += lo;
+        return t;
+    }
+
+    // The checks of n voices, before anything renders; each holds where the kind has nothing of its sort.  The two entry families run
+    // them between checks of their own, each in its own order (which refusal a call with several faults gets is behaviour): the device
+    // entries taps, kinds, values; the host renders taps, values and — once the parts say how many channels a voice has — kinds.
+    // space: the taps at n_speakers speakers over a timeline of n_total samples
+    int check_taps(dusp_ctx *ctx, const char *who, size_t n, size_t n_total) const {
+        if (kind != ScoreKind::space) return DUSP_OK;
+        const std::string w(who);
+        if (n_speakers < 1 || n_speakers > dusp::kScoreSpaceChannelsMax)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a Space has 1 .. 8 speakers, not " + std::to_string(n_speakers));
+        if (n && (!h_delays || !h_tap_gains)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the taps' delays or gains are NULL");
+        if (n_speakers * n_total > dusp::kScoreRowMax)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": speakers x timeline samples must not exceed 2^31: score such a piece speaker by speaker or in windows of the timeline");
+        for (size_t k = 0; k < n; k++)
+            for (size_t c = 0; c < n_speakers; c++) {
+                const double D = h_delays[k * n_speakers + c], G = h_tap_gains[k * n_speakers + c];
+                const std::string at = " of voice " + std::to_string(k) + " at speaker " + std::to_string(c);
+                if (!std::isfinite(D)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the delay" + at + " is not finite");
+                if (D < 0.0 || D > (double)dusp::kScoreSpaceShiftMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the delay" + at + " is outside [0, 2^24] samples");
+                if (!std::isfinite(G)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the gain" + at + " is not finite");
+            }
+        return DUSP_OK;
+    }
+
+    // stereo: the kinds of the voices — a row of one or of two channels; a pan that is NaN says "not placed", and a voice of two
+    // channels is not placed
+    int check_kinds(dusp_ctx *ctx, const char *who, size_t n) const {
+        if (kind != ScoreKind::stereo) return DUSP_OK;
+        for (size_t k = 0; k < n; k++) {
+            const uint32_t channels = h_row_channels[k];
+            if (channels != 1 && channels != 2)
+                CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": voice " + std::to_string(k) + " has " + std::to_string(channels) + " channels: a voice of a stereo piece has one or two");
+            if (std::isinf(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
+            if (channels == 2 && !std::isnan(h_pans[k]))
+                CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": voice " + std::to_string(k) + " has two channels and a pan: a two-channel voice is not panned (its pan must be NaN)");
+            if (h_comp && !std::isnan(h_pans[k]) && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
+        }
+        return DUSP_OK;
+    }
+
+    // pan: the pans and their compensation; then, whatever the kind, the fractions
+    int check_values(dusp_ctx *ctx, const char *who, size_t n) const {
+        for (size_t k = 0; kind == ScoreKind::pan && k < n; k++) {
+            if (!std::isfinite(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
+            if (h_comp && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
+        }
+        for (size_t k = 0; h_fracs && k < n; k++) {
+            if (!std::isfinite(h_fracs[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is not finite");
+            if (h_fracs[k] < 0.0 || h_fracs[k] >= 1.0) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is outside [0, 1)");
+        }
+        return DUSP_OK;
+    }
 };
 
 // one launch's plan inside the context's image
@@ -98,21 +170,35 @@ static int score_voices_add(dusp_ctx *ctx, const char *who, const int64_t *h_ons
     return DUSP_OK;
 }
 
+// the pan coefficients of the voices [0, n) of the rows plan just added (L), where the call has pans.  h_comp NULL: the reference's
+// compensation by the host's pow (Pan.js:20).  A voice of a stereo call that is not placed (its pan NaN) has zeros, which nobody
+// multiplies by
+static void score_pans_add(dusp_ctx *ctx, const ScorePlacement &place, size_t n, ScoreLaunch &L) {
+    if (!L.any || (place.kind != ScoreKind::pan && place.kind != ScoreKind::stereo)) return;
+    L.pan_at = score_image_append<dusp::ScorePan>(ctx, n, [&](size_t k) {
+        if (std::isnan(place.h_pans[k])) return dusp::ScorePan{0.0, 0.0, 0.0, 0.0};
+        const double comp = place.h_comp ? place.h_comp[k] : std::pow(10.0, ((1.0 - std::fabs((double)place.h_pans[k])) * 1.5) / 20.0);
+        return dusp::score_pan_coefficients(place.h_pans[k], comp);
+    });
+}
+
 // ... and the voices [0, n) that are rows — voice k row_samples[k] samples a channel at device address rows[k].  listed (optional): which
-// voices reach the timeline.  h_fracs (optional): the voices' fractions of a sample, checked; where a listed voice has one, its weights
-// (dusp::ScoreFrac, 16 bytes a voice on top of the budget) follow the plan and the launch is the two-tap kernel's — else the image and
-// the launch are as without.
+// voices reach the timeline (NULL: nobody asks).  place: these voices' placement, checked.  Where a listed voice has a fraction, the
+// voices' weights (dusp::ScoreFrac, 16 bytes a voice on top of the budget) follow the plan and the launch is the two-tap kernel's —
+// else the image and the launch are as without.  Behind them the pan coefficients, where the call has pans (score_pans_add).
 static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n,
-                          size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, ScoreLaunch &L, std::vector<unsigned char> *listed = nullptr,
-                          const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr, const uint32_t *row_channels = nullptr, const float *h_pans = nullptr) {
-    dusp::ScoreRowsPlan P;  // (row_channels, h_pans: a stereo call's, the kind of every voice)
+                          size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, const ScorePlacement &place, ScoreLaunch &L,
+                          std::vector<unsigned char> *listed) {
+    const bool taps = place.kind == ScoreKind::space;
+    const double *h_fracs = place.h_fracs;
+    dusp::ScoreRowsPlan P;
     std::vector<dusp::ScoreSpaceTap> T;  // (space: the voices' taps, [voice][speaker], 32 bytes each on top of the budget as the weights are)
     if (taps) {
-        T.resize(n * taps->n_speakers);
-        for (size_t j = 0; j < T.size(); j++) T[j] = dusp::score_space_tap(taps->h_delays[j], taps->h_gains[j]);
+        T.resize(n * place.n_speakers);
+        for (size_t j = 0; j < T.size(); j++) T[j] = dusp::score_space_tap(place.h_delays[j], place.h_tap_gains[j]);
     }
-    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, h_fracs, taps ? T.data() : nullptr,
-                                              taps ? taps->n_speakers : 0, row_channels, h_pans);
+    const dusp::ScorePlacing by{h_fracs, taps ? T.data() : nullptr, place.n_speakers, place.h_row_channels, place.h_pans};  // (row_channels with pans: every voice's kind)
+    const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, by);
     if (bad >= 0)
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
                                         ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
@@ -120,22 +206,12 @@ static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onset
     if (taps && L.any) L.space_at = score_image_append<dusp::ScoreSpaceTap>(ctx, T.size(), [&](size_t j) { return T[j]; });
     for (size_t k = 0; k < n && L.any && !L.frac && !taps; k++) L.frac = P.voices[k].hi > P.voices[k].lo && P.voices[k].pad != 0;
     if (L.frac) L.frac_at = score_image_append<dusp::ScoreFrac>(ctx, n, [&](size_t k) { return dusp::score_frac_weights(h_fracs[k]); });
+    score_pans_add(ctx, place, n, L);
     if (listed) {
         listed->resize(n);
         for (size_t k = 0; k < n; k++) (*listed)[k] = P.voices[k].hi > P.voices[k].lo;
     }
     return DUSP_OK;
-}
-
-// the pan coefficients of the voices [0, n) of the rows plan just added (L).  h_comp NULL: the reference's compensation by the host's
-// pow (Pan.js:20).  A voice of a stereo call that is not placed (its pan NaN) has zeros, which nobody multiplies by
-static void score_pans_add(dusp_ctx *ctx, const float *h_pans, const double *h_comp, size_t n, ScoreLaunch &L) {
-    if (!L.any) return;
-    L.pan_at = score_image_append<dusp::ScorePan>(ctx, n, [&](size_t k) {
-        if (std::isnan(h_pans[k])) return dusp::ScorePan{0.0, 0.0, 0.0, 0.0};
-        const double comp = h_comp ? h_comp[k] : std::pow(10.0, ((1.0 - std::fabs((double)h_pans[k])) * 1.5) / 20.0);
-        return dusp::score_pan_coefficients(h_pans[k], comp);
-    });
 }
 
 // the image to the device, ordered on `stream` behind the last launch that read the buffer (whatever stream that one ran on)
@@ -163,9 +239,9 @@ static bool score_plan_intact(dusp_ctx *ctx) { return !ctx->d_score_plan || !g_g
 
 // The launch L describes, over its window of a timeline [n_channels][n_total] (pan: mono rows, [2][n_total]).  Its plan is in the image
 // on the device (the buffer and L.at: both on 32-byte boundaries); a launch without voices has none and hands the kernel of its kind NULLs.
-// d_planar, n_voice: the batch of a contiguous launch.
+// d_planar, n_voice: the batch of a contiguous launch (else NULL and 0).
 static int score_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, size_t n_total, const float *d_gains, const float *d_init, int raw, float *d_out,
-                        hipStream_t stream, const float *d_planar = nullptr, size_t n_voice = 0) {
+                        hipStream_t stream, const float *d_planar, size_t n_voice) {
     if (L.w_hi <= L.w_lo) return DUSP_OK;
     const unsigned char *d_image = ctx->d_score_plan;
     const unsigned char *d_voices = L.any ? d_image + L.at : nullptr;
@@ -224,59 +300,10 @@ static int score_device_call(dusp_ctx *ctx, hipStream_t stream, bool voices, con
 // whole timeline — a launch of `kind` without voices — the delivery, which waits for the stream, and the guard check
 static int score_deliver_host(dusp_program *prog, const char *who, ScoreKind kind, size_t n_ch, size_t n_total, int format, int normalise, float *h_peak, void *h_out) {
     dusp_ctx *ctx = prog->ctx;
-    if (int rc = score_launch(ctx, ScoreLaunch(kind, n_total), n_ch, n_total, nullptr, prog->d_mix.p, /*raw=*/0, prog->d_mix.p, ctx->stream)) return rc;
+    if (int rc = score_launch(ctx, ScoreLaunch(kind, n_total), n_ch, n_total, nullptr, prog->d_mix.p, /*raw=*/0, prog->d_mix.p, ctx->stream, nullptr, 0)) return rc;
     if (int rc = deliver_host(prog, prog->d_mix.p, nullptr, 1, n_ch, n_total, format, normalise, h_peak, h_out)) return rc;
     if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
         CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
-    return DUSP_OK;
-}
-
-static int check_pans(dusp_ctx *ctx, const char *who, const float *h_pans, const double *h_comp, size_t n) {
-    for (size_t k = 0; k < n; k++) {
-        if (!std::isfinite(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
-        if (h_comp && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
-    }
-    return DUSP_OK;
-}
-
-// the kinds of a stereo call: voice k a row of channels[k] channels, one or two; a pan that is NaN says "not placed", and a voice of two
-// channels is not placed
-static int check_stereo(dusp_ctx *ctx, const char *who, const uint32_t *channels, const float *h_pans, const double *h_comp, size_t n) {
-    for (size_t k = 0; k < n; k++) {
-        if (channels[k] != 1 && channels[k] != 2)
-            CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": voice " + std::to_string(k) + " has " + std::to_string(channels[k]) + " channels: a voice of a stereo piece has one or two");
-        if (std::isinf(h_pans[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the pan of voice " + std::to_string(k) + " is not finite");
-        if (channels[k] == 2 && !std::isnan(h_pans[k]))
-            CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": voice " + std::to_string(k) + " has two channels and a pan: a two-channel voice is not panned (its pan must be NaN)");
-        if (h_comp && !std::isnan(h_pans[k]) && std::isnan(h_comp[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the compensation of voice " + std::to_string(k) + " is NaN");
-    }
-    return DUSP_OK;
-}
-
-static int check_fracs(dusp_ctx *ctx, const char *who, const double *h_fracs, size_t n) {
-    for (size_t k = 0; h_fracs && k < n; k++) {
-        if (!std::isfinite(h_fracs[k])) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is not finite");
-        if (h_fracs[k] < 0.0 || h_fracs[k] >= 1.0) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the fraction of voice " + std::to_string(k) + " is outside [0, 1)");
-    }
-    return DUSP_OK;
-}
-
-// the taps of n voices at n_speakers speakers, checked before anything renders
-static int check_taps(dusp_ctx *ctx, const char *who, const double *h_delays, const double *h_gains, size_t n, size_t n_speakers, size_t n_total) {
-    const std::string w(who);
-    if (n_speakers < 1 || n_speakers > dusp::kScoreSpaceChannelsMax)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a Space has 1 .. 8 speakers, not " + std::to_string(n_speakers));
-    if (n && (!h_delays || !h_gains)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the taps' delays or gains are NULL");
-    if (n_speakers * n_total > dusp::kScoreRowMax)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": speakers x timeline samples must not exceed 2^31: score such a piece speaker by speaker or in windows of the timeline");
-    for (size_t k = 0; k < n; k++)
-        for (size_t c = 0; c < n_speakers; c++) {
-            const double D = h_delays[k * n_speakers + c], G = h_gains[k * n_speakers + c];
-            const std::string at = " of voice " + std::to_string(k) + " at speaker " + std::to_string(c);
-            if (!std::isfinite(D)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the delay" + at + " is not finite");
-            if (D < 0.0 || D > (double)dusp::kScoreSpaceShiftMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the delay" + at + " is outside [0, 2^24] samples");
-            if (!std::isfinite(G)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the gain" + at + " is not finite");
-        }
     return DUSP_OK;
 }
 
@@ -310,52 +337,43 @@ int dusp_score_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, 
     });
 }
 
-// dusp_score_rows_device, (h_pans: rows of one channel into a timeline of two) dusp_score_rows_pan_device, (h_fracs: onsets between
-// samples) dusp_score_rows_frac_device, and (taps: rows of one channel into a timeline of taps->n_speakers) dusp_score_rows_space_device,
-// and (h_row_channels: rows of one and of two channels — n_channels is 1 — with NaN in h_pans for "not placed", into a timeline of two)
-// dusp_score_rows_stereo_device
+// dusp_score_rows_device and its pan, frac, space and stereo forms: rows of n_channels, placed as `place` says (pan, space: rows of one
+// channel; stereo: n_channels is 1 and every row has place.h_row_channels[k]), into a timeline of place.timeline_channels(n_channels)
 static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
-                             const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, const float *d_init, int raw,
-                             float *d_out, void *stream_, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr, const uint32_t *h_row_channels = nullptr) {
+                             const int64_t *h_lengths, const float *d_gains, const ScorePlacement &place, size_t n_total_samples, const float *d_init, int raw, float *d_out,
+                             void *stream_) {
     if (!ctx) return DUSP_ERR_ARG;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
-    if (taps)  // (first: the timeline's channel count is theirs)
-        if (int rc = check_taps(ctx, who, taps->h_delays, taps->h_gains, n_voices, taps->n_speakers, n_total_samples)) return rc;
-    const size_t n_out_channels = taps ? taps->n_speakers : h_pans ? 2 : n_channels;  // (the timeline's)
+    if (int rc = place.check_taps(ctx, who, n_voices, n_total_samples)) return rc;  // (first: the timeline's channel count is theirs)
+    const size_t n_out_channels = place.timeline_channels(n_channels);
     if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
-    const bool stereo = h_row_channels != nullptr;
+    const bool stereo = place.kind == ScoreKind::stereo;
     if (stereo && n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 0..2^24 voices");
-    if (stereo)  // (before the rows' sizes are looked at: they are channels x samples)
-        if (int rc = check_stereo(ctx, who, h_row_channels, h_pans, h_comp, n_voices)) return rc;
+    if (int rc = place.check_kinds(ctx, who, n_voices)) return rc;  // (before the rows' sizes are looked at: they are channels x samples)
     if (!channels_in_range(n_channels) || n_voices > (1u << 24) || !samples_in_range(n_total_samples))
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..64 channels, 0..2^24 voices and 1..2^31 samples of timeline");
     if (n_out_channels * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": channels x timeline samples must not exceed 2^31: score such a piece channel by channel or in windows of the timeline");
     if ((((uintptr_t)d_gains | (uintptr_t)d_init | (uintptr_t)d_out) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
     for (size_t k = 0; k < n_voices; k++) {
-        if ((uint64_t)h_row_samples[k] * (stereo ? h_row_channels[k] : n_channels) > dusp::kScoreRowMax)
+        if ((uint64_t)h_row_samples[k] * (stereo ? place.h_row_channels[k] : n_channels) > dusp::kScoreRowMax)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + ": channels x row samples must not exceed 2^31");
         if (h_row_samples[k] && !h_rows[k]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " is NULL");
         if (h_row_samples[k] && ((uintptr_t)h_rows[k] & 3)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the row of voice " + std::to_string(k) + " must be 4-byte aligned");
     }
-    if (h_pans && !stereo)
-        if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
-    if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
+    if (int rc = place.check_values(ctx, who, n_voices)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_of(ctx, stream_);
-    ScoreLaunch L(stereo ? ScoreKind::stereo : taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
+    ScoreLaunch L(place.kind, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
     return score_device_call(
         ctx, stream, n_voices != 0, L,
         [&]() {
             static_assert(sizeof(const float *) == sizeof(uint64_t), "rows are handed to the planner as 64-bit addresses");
-            if (int rc = score_rows_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples, /*whole_timeline=*/true,
-                                        score_plan_budget(ctx), L, nullptr, h_fracs, taps, h_row_channels, stereo ? h_pans : nullptr))
-                return rc;
-            if (h_pans) score_pans_add(ctx, h_pans, h_comp, n_voices, L);
-            return (int)DUSP_OK;
+            return score_rows_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples, /*whole_timeline=*/true,
+                                  score_plan_budget(ctx), place, L, nullptr);
         },
-        [&]() { return score_launch(ctx, L, taps ? n_out_channels : n_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream); });
+        [&]() { return score_launch(ctx, L, n_out_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream, nullptr, 0); });
     });
 }
 
@@ -420,8 +438,8 @@ int dusp_render_host_score(dusp_program *prog, size_t n_instances, size_t n_voic
 
 int dusp_score_rows_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
                            const int64_t *h_lengths, const float *d_gains, size_t n_total_samples, const float *d_init, int raw, float *d_out, void *stream_) {
-    return score_rows_device(ctx, "dusp_score_rows_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, nullptr, nullptr, n_total_samples, d_init,
-                             raw, d_out, stream_);
+    return score_rows_device(ctx, "dusp_score_rows_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, ScorePlacement(ScoreKind::rows),
+                             n_total_samples, d_init, raw, d_out, stream_);
 }
 
 int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, const int64_t *h_onsets, const int64_t *h_lengths,
@@ -429,29 +447,29 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
                                void *stream_) {
     if (!ctx) return DUSP_ERR_ARG;
     if (n_voices && !h_pans) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_pan_device: h_pans is NULL");
-    static const float no_pans[1] = {0.0f};  // (no voices: `|| 0`, or a copy, of both channels of d_init)
-    return score_rows_device(ctx, "dusp_score_rows_pan_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, h_pans ? h_pans : no_pans, h_comp,
+    // (the kind stands without voices too: `|| 0`, or a copy, of both channels of d_init)
+    return score_rows_device(ctx, "dusp_score_rows_pan_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, ScorePlacement(ScoreKind::pan, nullptr, h_pans, h_comp),
                              n_total_samples, d_init, raw, d_out, stream_);
 }
 
-// dusp_render_host_score_parts, (h_pans: mono parts into a timeline of two channels) dusp_render_host_score_parts_pan, (h_fracs:
-// onsets between samples, with or without pans) dusp_render_host_score_parts_frac, and (taps: mono parts into a timeline of
-// taps->n_speakers channels) dusp_render_host_score_parts_space, and (stereo: parts of one and of two output channels, h_pans with NaN for
-// "not placed", with or without h_fracs, into a timeline of two channels) dusp_render_host_score_parts_stereo
+// dusp_render_host_score_parts and its pan, frac, space and stereo forms: the parts' voices placed as `given` says (pan, space: mono
+// parts; stereo: parts of one and of two output channels, and the voices' channels, given.h_row_channels, are made here from the
+// parts') into a timeline of given.timeline_channels(a voice's)
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
-                                   const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
-                                   int format, int normalise, void *h_out, float *h_peak, const double *h_fracs = nullptr, const ScoreTaps *taps = nullptr, bool stereo = false) {
+                                   const int64_t *h_lengths, const float *h_gains, const ScorePlacement &given, size_t n_total_samples, size_t tile_bytes, int format,
+                                   int normalise, void *h_out, float *h_peak) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
     const size_t n_ch = prog0->P.out_bufs.size();  // (a voice's)
+    ScorePlacement place = given;
+    const bool stereo = place.kind == ScoreKind::stereo, panned = place.kind == ScoreKind::pan, taps = place.kind == ScoreKind::space;
     if (!h_part_of || !h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of or h_onsets is NULL");
     if (n_voices < 1 || n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^24 voices");
-    if (taps)
-        if (int rc = check_taps(ctx, who, taps->h_delays, taps->h_gains, n_voices, taps->n_speakers, n_total_samples)) return rc;
-    const size_t n_out_ch = taps ? taps->n_speakers : h_pans ? 2 : n_ch;  // (the timeline's)
+    if (int rc = place.check_taps(ctx, who, n_voices, n_total_samples)) return rc;
+    const size_t n_out_ch = place.timeline_channels(n_ch);
     size_t n_listed = 0;
     std::vector<size_t> part_ch(n_parts, n_ch);  // (a part's own: they differ in a stereo piece only)
     for (size_t p = 0; p < n_parts; p++) {
@@ -460,7 +478,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         part_ch[p] = parts[p].prog->P.out_bufs.size();
         if (stereo && part_ch[p] != 1 && part_ch[p] != 2)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(part_ch[p]) + " output channels: a voice of a stereo piece has one or two");
-        if (!stereo && h_pans && parts[p].prog->P.out_bufs.size() != 1)
+        if (panned && parts[p].prog->P.out_bufs.size() != 1)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": part " + std::to_string(p) + " has " + std::to_string(parts[p].prog->P.out_bufs.size()) +
                                             " output channels: a panned voice is mono");
         if (taps && parts[p].prog->P.out_bufs.size() != 1)
@@ -476,9 +494,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     }
     if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
-    if (h_pans && !stereo)
-        if (int rc = check_pans(ctx, who, h_pans, h_comp, n_voices)) return rc;
-    if (int rc = check_fracs(ctx, who, h_fracs, n_voices)) return rc;
+    if (int rc = place.check_values(ctx, who, n_voices)) return rc;
     // voice k of the chain: the next unused instance of part h_part_of[k]
     std::vector<size_t> instance_of(n_voices), used(n_parts, 0);
     for (size_t k = 0; k < n_voices; k++) {
@@ -489,8 +505,9 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     if (stereo) {
         row_channels.resize(n_voices);
         for (size_t k = 0; k < n_voices; k++) row_channels[k] = (uint32_t)part_ch[h_part_of[k]];
-        if (int rc = check_stereo(ctx, who, row_channels.data(), h_pans, h_comp, n_voices)) return rc;
+        place.h_row_channels = row_channels.data();
     }
+    if (int rc = place.check_kinds(ctx, who, n_voices)) return rc;
     for (size_t p = 0; p < n_parts; p++)
         if (used[p] != parts[p].n_instances || n_listed != n_voices)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of names part " + std::to_string(p) + " " + std::to_string(used[p]) + " times, the part has " +
@@ -529,7 +546,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     }
     // every tile's plan, over the tile's union window, made up front under the call's one budget and uploaded once: the rows' addresses
     // are known, since the tile buffers stand
-    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(stereo ? ScoreKind::stereo : taps ? ScoreKind::space : h_pans ? ScoreKind::pan : ScoreKind::rows));
+    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(place.kind));
     std::vector<std::vector<unsigned char>> renders(n_tiles, std::vector<unsigned char>(n_parts, 0));  // does part p render in tile i?
     const size_t tile_budget = score_plan_budget(ctx) / n_tiles;
     if (int rc = score_image_begin(ctx)) return rc;
@@ -539,17 +556,14 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         std::vector<unsigned char> listed;
         for (size_t i = 0; i < n_tiles; i++) {
             const size_t lo = starts[i], n = starts[i + 1] - lo;
-            const ScoreTaps tile_taps = taps ? ScoreTaps{taps->n_speakers, taps->h_delays + lo * taps->n_speakers, taps->h_gains + lo * taps->n_speakers} : ScoreTaps{0, nullptr, nullptr};
             rows.resize(n);
             for (size_t k = 0; k < n; k++) {
                 const size_t p = h_part_of[lo + k];
                 rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * part_ch[p] * parts[p].n_voice_samples);
             }
             if (int rc = score_rows_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
-                                        /*whole_timeline=*/false, tile_budget, launches[i], &listed, h_fracs ? h_fracs + lo : nullptr, taps ? &tile_taps : nullptr,
-                                        stereo ? row_channels.data() + lo : nullptr, stereo ? h_pans + lo : nullptr))
+                                        /*whole_timeline=*/false, tile_budget, place.tile(lo), launches[i], &listed))
                 return rc;
-            if (h_pans) score_pans_add(ctx, h_pans + lo, h_comp ? h_comp + lo : nullptr, n, launches[i]);
             for (size_t k = 0; k < n; k++)
                 if (listed[k]) renders[i][h_part_of[lo + k]] = 1;
         }
@@ -575,7 +589,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
             if (renders[i][p])
                 if (int rc = whole[p]->render_tile(share[p][i], share[p][i + 1] - share[p][i], parts[p].n_voice_samples)) return rc;
         const float *d_gains = h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr;
-        if (int rc = score_launch(ctx, launches[i], taps ? n_out_ch : n_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream)) return rc;
+        if (int rc = score_launch(ctx, launches[i], n_out_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream, nullptr, 0)) return rc;
     }
     // (`|| 0` is the rows kernel's over the timeline's channels, panned or not)
     if (int rc = score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
@@ -587,8 +601,8 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
 int dusp_render_host_score_parts(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                  const int64_t *h_lengths, const float *h_gains, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out,
                                  float *h_peak) {
-    return render_host_score_parts("dusp_render_host_score_parts", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, nullptr, nullptr, n_total_samples,
-                                   tile_bytes, format, normalise, h_out, h_peak);
+    return render_host_score_parts("dusp_render_host_score_parts", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, ScorePlacement(ScoreKind::rows),
+                                   n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
 }
 
 int dusp_render_host_score_parts_pan(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
@@ -596,8 +610,8 @@ int dusp_render_host_score_parts_pan(const dusp_score_part *parts, size_t n_part
                                      int format, int normalise, void *h_out, float *h_peak) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     if (!h_pans) CTX_FAIL(parts[0].prog->ctx, DUSP_ERR_ARG, "dusp_render_host_score_parts_pan: h_pans is NULL");
-    return render_host_score_parts("dusp_render_host_score_parts_pan", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
-                                   tile_bytes, format, normalise, h_out, h_peak);
+    return render_host_score_parts("dusp_render_host_score_parts_pan", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains,
+                                   ScorePlacement(ScoreKind::pan, nullptr, h_pans, h_comp), n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
 }
 
 int dusp_score_rows_frac_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
@@ -605,31 +619,29 @@ int dusp_score_rows_frac_device(dusp_ctx *ctx, const float *const *h_rows, const
                                 const float *d_init, int raw, float *d_out, void *stream_) {
     if (!ctx) return DUSP_ERR_ARG;
     if (h_pans && n_channels != 1) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_frac_device: a panned voice is mono: n_channels must be 1 with h_pans");
-    return score_rows_device(ctx, "dusp_score_rows_frac_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, h_pans, h_comp, n_total_samples, d_init,
-                             raw, d_out, stream_, h_fracs);
+    return score_rows_device(ctx, "dusp_score_rows_frac_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains,
+                             ScorePlacement(h_pans ? ScoreKind::pan : ScoreKind::rows, h_fracs, h_pans, h_comp), n_total_samples, d_init, raw, d_out, stream_);
 }
 
 int dusp_render_host_score_parts_frac(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const double *h_fracs,
                                       const int64_t *h_lengths, const float *h_gains, const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes,
                                       int format, int normalise, void *h_out, float *h_peak) {
-    return render_host_score_parts("dusp_render_host_score_parts_frac", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
-                                   tile_bytes, format, normalise, h_out, h_peak, h_fracs);
+    return render_host_score_parts("dusp_render_host_score_parts_frac", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains,
+                                   ScorePlacement(h_pans ? ScoreKind::pan : ScoreKind::rows, h_fracs, h_pans, h_comp), n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
 }
 
 int dusp_score_rows_space_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_speakers, const int64_t *h_onsets,
                                  const int64_t *h_lengths, const float *d_gains, const double *h_delays, const double *h_tap_gains, size_t n_total_samples, const float *d_init,
                                  int raw, float *d_out, void *stream_) {
-    const ScoreTaps taps{n_speakers, h_delays, h_tap_gains};
-    return score_rows_device(ctx, "dusp_score_rows_space_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, nullptr, nullptr, n_total_samples, d_init, raw,
-                             d_out, stream_, nullptr, &taps);
+    return score_rows_device(ctx, "dusp_score_rows_space_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, ScorePlacement(n_speakers, h_delays, h_tap_gains),
+                             n_total_samples, d_init, raw, d_out, stream_);
 }
 
 int dusp_render_host_score_parts_space(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                        const int64_t *h_lengths, const float *h_gains, size_t n_speakers, const double *h_delays, const double *h_tap_gains,
                                        size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
-    const ScoreTaps taps{n_speakers, h_delays, h_tap_gains};
-    return render_host_score_parts("dusp_render_host_score_parts_space", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, nullptr, nullptr, n_total_samples,
-                                   tile_bytes, format, normalise, h_out, h_peak, nullptr, &taps);
+    return render_host_score_parts("dusp_render_host_score_parts_space", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains,
+                                   ScorePlacement(n_speakers, h_delays, h_tap_gains), n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
 }
 
 int dusp_score_rows_stereo_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, const uint32_t *h_row_channels, size_t n_voices,
@@ -638,9 +650,10 @@ int dusp_score_rows_stereo_device(dusp_ctx *ctx, const float *const *h_rows, con
     if (!ctx) return DUSP_ERR_ARG;
     if (n_voices && !h_pans) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_stereo_device: h_pans is NULL");
     if (n_voices && !h_row_channels) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_stereo_device: h_row_channels is NULL");
-    static const float no_pans[1] = {0.0f};  // (no voices: `|| 0`, or a copy, of both channels of d_init)
-    return score_rows_device(ctx, "dusp_score_rows_stereo_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, n_voices ? h_pans : no_pans, h_comp,
-                             n_total_samples, d_init, raw, d_out, stream_, h_fracs, nullptr, n_voices ? h_row_channels : nullptr);
+    ScorePlacement place(ScoreKind::stereo, h_fracs, h_pans, h_comp);  // (the kind stands without voices too: `|| 0`, or a copy, of both channels of d_init)
+    place.h_row_channels = h_row_channels;
+    return score_rows_device(ctx, "dusp_score_rows_stereo_device", h_rows, h_row_samples, n_voices, 1, h_onsets, h_lengths, d_gains, place, n_total_samples, d_init, raw, d_out,
+                             stream_);
 }
 
 int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
@@ -648,8 +661,8 @@ int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_p
                                         size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     if (!h_pans) CTX_FAIL(parts[0].prog->ctx, DUSP_ERR_ARG, "dusp_render_host_score_parts_stereo: h_pans is NULL");
-    return render_host_score_parts("dusp_render_host_score_parts_stereo", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, h_pans, h_comp, n_total_samples,
-                                   tile_bytes, format, normalise, h_out, h_peak, h_fracs, nullptr, /*stereo=*/true);
+    return render_host_score_parts("dusp_render_host_score_parts_stereo", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains,
+                                   ScorePlacement(ScoreKind::stereo, h_fracs, h_pans, h_comp), n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // score_device.hpp — what the six score kernels share (score_engine.hip, score_rows_engine.hip, score_pan_engine.hip,
-// score_frac_engine.hip, score_space_engine.hip, score_stereo_engine.hip): `x || 0`, a plan record as one wide load, the typedefs of a batch's indices and of a row's floats, the head of
-// every kernel (lane to sample, window test) and the groups a launch covers.  The lookup of the block's list behind that head stays in
+// score_frac_engine.hip, score_space_engine.hip, score_stereo_engine.hip): `x || 0`, a plan record as one wide load, the pan coefficients
+// that are used as two loads, the two-tap term, the typedefs of a batch's indices and of a row's floats, the head of every kernel (lane
+// to sample, window test) and the groups a launch covers.  The lookup of the block's list behind that head stays in
 // each kernel: as a shared function it changed the order of two scalar moves in three of the four device listings
 // (profiles/score_refactor.txt).  Like the engines, this compiles for the host under tests/native/hip_host_stub, where the kernels' text
 // runs lane after lane.
@@ -33,6 +34,30 @@ static __device__ __forceinline__ ScoreFrac score_load16(const ScoreFrac *p) {
     ScoreFrac r;
     __builtin_memcpy(&r, &w, sizeof r);
     return r;
+}
+
+// a voice's pan coefficients without the record's unused last quarter: four dwords and two, six scalar registers an entry, not eight
+// (score_frac_engine.hip, score_stereo_engine.hip)
+struct ScorePanUsed {
+    double lm, rp, ch;
+};
+typedef uint32_t ScoreWords2 __attribute__((vector_size(8), may_alias));
+static __device__ __forceinline__ ScorePanUsed score_load_pan(const ScorePan *p) {
+    const ScoreWords4 a = *(const ScoreWords4 *)p;
+    const ScoreWords2 b = *(const ScoreWords2 *)&p->ch;
+    ScorePanUsed r;
+    __builtin_memcpy(&r.lm, &a, sizeof a);
+    __builtin_memcpy(&r.ch, &b, sizeof b);
+    return r;
+}
+
+// the two taps of one timeline sample (score_frac_engine.hip says where they come from; score_stereo_engine.hip and, with a tap's own
+// weights, score_space_engine.hip): x0 = x[s] (used where s < len), x1 = x[s - 1] (used where s >= 1), w0 = 1.0 - frac, w1 = frac
+static __device__ __forceinline__ float score_two_tap_term(float x0, float x1, bool has0, bool has1, double w0, double w1) {
+    const float c = (float)((double)x1 * w1);
+    const double floor_tap = (double)x0 * w0;
+    const float both = (float)((double)c + floor_tap);
+    return has1 ? (has0 ? both : c) : (float)floor_tap;
 }
 
 // a batch's eight indices as one load too: contiguous in entries[], on a 4-byte boundary only

@@ -44,28 +44,6 @@ namespace dusp {
 constexpr int kScoreFracDepth = 8;  // entries of a list whose indices are read at once
 constexpr int kScoreFracSub = 4;    // entries a lane has in flight: two vector loads each
 
-// a voice's pan coefficients without the record's unused last quarter: four dwords and two, six scalar registers an entry, not eight
-struct ScoreFracPan {
-    double lm, rp, ch;
-};
-typedef uint32_t ScoreFracWords2 __attribute__((vector_size(8), may_alias));
-static __device__ __forceinline__ ScoreFracPan score_frac_load_pan(const ScorePan *p) {
-    const ScoreWords4 a = *(const ScoreWords4 *)p;
-    const ScoreFracWords2 b = *(const ScoreFracWords2 *)&p->ch;
-    ScoreFracPan r;
-    __builtin_memcpy(&r.lm, &a, sizeof a);
-    __builtin_memcpy(&r.ch, &b, sizeof b);
-    return r;
-}
-
-// the two taps of one timeline sample: x0 = x[s] (used where s < len), x1 = x[s - 1] (used where s >= 1)
-static __device__ __forceinline__ float score_frac_term(float x0, float x1, bool has0, bool has1, const ScoreFrac &w) {
-    const float c = (float)((double)x1 * w.w1);
-    const double floor_tap = (double)x0 * w.w0;
-    const float both = (float)((double)c + floor_tap);
-    return has1 ? (has0 ? both : c) : (float)floor_tap;
-}
-
 // group0: the first group of kScoreGroup samples the grid covers (w_lo >> kScoreGroupShift); groups: how many (per channel).
 // PAN false: init, out [n_channels][n_total], the grid groups x n_channels, pans unused.  PAN true: rows are mono, init, out [2][n_total],
 // the grid groups.  block_first is never nullptr: a launch without voices is the existing kernels'.
@@ -99,7 +77,7 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
             bool in[SUB], has0[SUB], has1[SUB];
             ScoreRow V[SUB];
             ScoreFrac W[SUB];
-            ScoreFracPan P[SUB];
+            ScorePanUsed P[SUB];
             // the scalar loads the addresses need first, side by side — the records (and gains) — so that one wait covers them
 #pragma unroll
             for (int k = 0; k < SUB; k++) {
@@ -125,7 +103,7 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
 #pragma unroll
             for (int k = 0; k < SUB; k++) {
                 W[k] = score_load16(fracs + idx[h + k]);
-                if (PAN) P[k] = score_frac_load_pan(pans + idx[h + k]);
+                if (PAN) P[k] = score_load_pan(pans + idx[h + k]);
             }
 #pragma unroll
             for (int k = 0; k < SUB; k++)
@@ -139,13 +117,13 @@ __global__ void __launch_bounds__(256) dusp_score_frac_kernel(const float *__res
                             acc1 = acc1 + r0;
                         } else {
                             const float l1 = (float)((d1 * P[k].lm) * P[k].ch), r1 = (float)((d1 * P[k].rp) * P[k].ch);
-                            acc0 = acc0 + score_frac_term(l0, l1, has0[k], has1[k], W[k]);
-                            acc1 = acc1 + score_frac_term(r0, r1, has0[k], has1[k], W[k]);
+                            acc0 = acc0 + score_two_tap_term(l0, l1, has0[k], has1[k], W[k].w0, W[k].w1);
+                            acc1 = acc1 + score_two_tap_term(r0, r1, has0[k], has1[k], W[k].w0, W[k].w1);
                         }
                     } else if (V[k].pad == 0) {
                         acc0 = acc0 + x0;
                     } else {
-                        acc0 = acc0 + score_frac_term(x0, x1, has0[k], has1[k], W[k]);
+                        acc0 = acc0 + score_two_tap_term(x0, x1, has0[k], has1[k], W[k].w0, W[k].w1);
                     }
                 }
         }

@@ -134,7 +134,6 @@ inline size_t score_plan_pack(const ScorePlanT<Record> &P, std::vector<unsigned 
     put(P.entries.data(), P.entries.size() * sizeof(uint32_t));
     return at;
 }
-inline size_t score_rows_plan_pack(const ScoreRowsPlan &P, std::vector<unsigned char> &image) { return score_plan_pack(P, image); }  // (the name the rows' callers know)
 
 // lengths: nullptr for n_voice everywhere.  whole_timeline: the plan covers [0, n_total) (a launch that writes every sample), else the
 // union window only (a raw launch in place: samples no voice of the tile reaches stay as they are).
@@ -210,9 +209,15 @@ inline ScoreSpaceTap score_space_tap(double delay, double gain) {
 // Returns -1 when the plan is made, else the index of the first voice whose length is not in [0, row_samples[k]].
 // Needs n <= 2^32 - 1, row_samples and n_total <= kScoreRowMax.
 constexpr uint32_t kScoreStrideMono = 0u, kScoreStridePanned = 0xffffffffu;
+struct ScorePlacing {  // what places the voices of a rows plan, each as described above; all null: plain rows
+    const double *fracs = nullptr;
+    const ScoreSpaceTap *taps = nullptr;
+    size_t taps_channels = 0;
+    const uint32_t *row_channels = nullptr;
+    const float *pans = nullptr;
+};
 inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n, uint64_t n_total,
-                               bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P, const double *fracs = nullptr, const ScoreSpaceTap *taps = nullptr,
-                               size_t taps_channels = 0, const uint32_t *row_channels = nullptr, const float *pans = nullptr) {
+                               bool whole_timeline, size_t budget_bytes, ScoreRowsPlan &P, const ScorePlacing &by) {
     P = ScoreRowsPlan();
     P.voices.assign(n, ScoreRow{0, 0u, 0u, 0u, 0u, 0u});
     const int64_t total = (int64_t)n_total;
@@ -221,11 +226,11 @@ inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, co
     for (size_t k = 0; k < n; k++) {
         const int64_t len = lengths ? lengths[k] : (int64_t)row_samples[k], onset = onsets[k];
         if (len < 0 || len > (int64_t)row_samples[k]) return (int64_t)k;
-        if (taps) {
+        if (by.taps) {
             // the union of the channels' spans, relative to the onset: [first, last), 0 <= first < last <= 2^24 + 2^31 + 1
             int64_t first = INT64_MAX, last = 0;
-            for (size_t c = 0; c < taps_channels; c++) {
-                const ScoreSpaceTap &T = taps[k * taps_channels + c];
+            for (size_t c = 0; c < by.taps_channels; c++) {
+                const ScoreSpaceTap &T = by.taps[k * by.taps_channels + c];
                 first = std::min(first, T.shift);
                 last = std::max(last, T.shift + len + (T.w1 != 0.0 ? 1 : 0));
             }
@@ -239,12 +244,12 @@ inline int64_t score_rows_plan(const int64_t *onsets, const int64_t *lengths, co
             t_hi = std::max(t_hi, hi);
             continue;
         }
-        const bool two_taps = fracs && fracs[k] != 0.0;
+        const bool two_taps = by.fracs && by.fracs[k] != 0.0;
         // empty, behind the end, wholly in front of sample 0 (two taps: the tail tap too, onset + len + 1 <= 0)
         if (len == 0 || onset >= total || (two_taps ? onset < -len : onset <= -len)) continue;
         // here -2^31 <= -len <= onset < n_total <= 2^31: onset + len + 1 cannot overflow
         const int64_t lo = std::max<int64_t>(onset, 0), hi = std::min(onset + len + (two_taps ? 1 : 0), total);
-        const uint32_t stride = !row_channels || row_channels[k] == 2 ? row_samples[k] : pans && std::isfinite(pans[k]) ? kScoreStridePanned : kScoreStrideMono;
+        const uint32_t stride = !by.row_channels || by.row_channels[k] == 2 ? row_samples[k] : by.pans && std::isfinite(by.pans[k]) ? kScoreStridePanned : kScoreStrideMono;
         P.voices[k] = ScoreRow{onset, (uint32_t)lo, (uint32_t)hi, rows ? rows[k] : 0, stride, two_taps ? (uint32_t)len : 0u};
         if (first_listed == n) first_listed = k;
         t_lo = std::min(t_lo, lo);

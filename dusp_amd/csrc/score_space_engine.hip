@@ -59,14 +59,6 @@ static __device__ __forceinline__ ScoreSpaceHow score_space_how(const ScoreSpace
     return r;
 }
 
-// the two taps of one timeline sample: y0 = y[s] (used where s < len), y1 = y[s - 1] (used where s >= 1)
-static __device__ __forceinline__ float score_space_term(float y0, float y1, bool has0, bool has1, double w0, double w1) {
-    const float c = (float)((double)y1 * w1);
-    const double floor_tap = (double)y0 * w0;
-    const float both = (float)((double)c + floor_tap);
-    return has1 ? (has0 ? both : c) : (float)floor_tap;
-}
-
 // group0: the first group of kScoreGroup samples the grid covers (w_lo >> kScoreGroupShift); groups: how many (per channel).
 // rows are mono; init, out [n_channels][n_total]; taps [n voices][n_channels]; the grid groups x n_channels.  block_first is never
 // nullptr: a launch without voices is the rows kernel's.
@@ -134,7 +126,7 @@ __global__ void __launch_bounds__(256) dusp_score_space_kernel(const float *__re
                     } else {
                         const float x1 = GAINS ? v1[k] * g[k] : v1[k];
                         const float y1 = (float)(H[k].gain * (double)x1);
-                        acc = acc + score_space_term(y0, y1, has0[k], has1[k], H[k].w0, W[k].w1);
+                        acc = acc + score_two_tap_term(y0, y1, has0[k], has1[k], H[k].w0, W[k].w1);
                     }
                 }
         }

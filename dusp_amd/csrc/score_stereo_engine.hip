@@ -38,28 +38,6 @@ constexpr int kScoreStereoDepth = 8;  // entries of a list whose indices are rea
 constexpr int kScoreStereoSub = 4;      // entries a lane has in flight without the two-tap form: up to two vector loads each
 constexpr int kScoreStereoFracSub = 2;  // ... and with it: up to four vector loads each, and 19 scalar registers an entry (four at once spill: DESIGN.md 6.13)
 
-// a voice's pan coefficients without the record's unused last quarter (as score_frac_engine.hip's): six scalar registers an entry
-struct ScoreStereoPan {
-    double lm, rp, ch;
-};
-typedef uint32_t ScoreStereoWords2 __attribute__((vector_size(8), may_alias));
-static __device__ __forceinline__ ScoreStereoPan score_stereo_load_pan(const ScorePan *p) {
-    const ScoreWords4 a = *(const ScoreWords4 *)p;
-    const ScoreStereoWords2 b = *(const ScoreStereoWords2 *)&p->ch;
-    ScoreStereoPan r;
-    __builtin_memcpy(&r.lm, &a, sizeof a);
-    __builtin_memcpy(&r.ch, &b, sizeof b);
-    return r;
-}
-
-// the two taps of one timeline sample (score_frac_engine.hip): x0 = x[s] (used where s < len), x1 = x[s - 1] (used where s >= 1)
-static __device__ __forceinline__ float score_stereo_term(float x0, float x1, bool has0, bool has1, const ScoreFrac &w) {
-    const float c = (float)((double)x1 * w.w1);
-    const double floor_tap = (double)x0 * w.w0;
-    const float both = (float)((double)c + floor_tap);
-    return has1 ? (has0 ? both : c) : (float)floor_tap;
-}
-
 // group0: the first group of kScoreGroup samples the grid covers (w_lo >> kScoreGroupShift).  init, out: [2][n_total].  block_first is
 // never nullptr: a launch without voices is the pan kernel's.  fracs: nullptr unless FRAC.
 template <int DEPTH, int SUB, bool GAINS, bool FRAC>  // (DEPTH: a multiple of 8, the padding of entries[]; SUB divides it)
@@ -90,7 +68,7 @@ __global__ void __launch_bounds__(256) dusp_score_stereo_kernel(const float *__r
             bool in[SUB], has0[SUB], has1[SUB], two[SUB], panned[SUB];
             ScoreRow V[SUB];
             ScoreFrac W[SUB];
-            ScoreStereoPan P[SUB];
+            ScorePanUsed P[SUB];
             // the scalar loads the addresses need first, side by side — the records (and gains) — so that one wait covers them
 #pragma unroll
             for (int k = 0; k < SUB; k++) {
@@ -120,7 +98,7 @@ __global__ void __launch_bounds__(256) dusp_score_stereo_kernel(const float *__r
             // what only the arithmetic needs is fetched behind the vector loads, while they are in flight
 #pragma unroll
             for (int k = 0; k < SUB; k++) {
-                P[k] = score_stereo_load_pan(pans + idx[h + k]);
+                P[k] = score_load_pan(pans + idx[h + k]);
                 if (FRAC) W[k] = score_load16(fracs + idx[h + k]);
             }
 #pragma unroll
@@ -136,8 +114,8 @@ __global__ void __launch_bounds__(256) dusp_score_stereo_kernel(const float *__r
                             accR = accR + r0;
                         } else {
                             const float l1 = (float)((d1 * P[k].lm) * P[k].ch), r1 = (float)((d1 * P[k].rp) * P[k].ch);
-                            accL = accL + score_stereo_term(l0, l1, has0[k], has1[k], W[k]);
-                            accR = accR + score_stereo_term(r0, r1, has0[k], has1[k], W[k]);
+                            accL = accL + score_two_tap_term(l0, l1, has0[k], has1[k], W[k].w0, W[k].w1);
+                            accR = accR + score_two_tap_term(r0, r1, has0[k], has1[k], W[k].w0, W[k].w1);
                         }
                     } else if (two[k]) {
                         const float y0 = GAINS ? b0[k] * g[k] : b0[k], y1 = GAINS ? b1[k] * g[k] : b1[k];
@@ -145,11 +123,11 @@ __global__ void __launch_bounds__(256) dusp_score_stereo_kernel(const float *__r
                             accL = accL + x0;
                             accR = accR + y0;
                         } else {
-                            accL = accL + score_stereo_term(x0, x1, has0[k], has1[k], W[k]);
-                            accR = accR + score_stereo_term(y0, y1, has0[k], has1[k], W[k]);
+                            accL = accL + score_two_tap_term(x0, x1, has0[k], has1[k], W[k].w0, W[k].w1);
+                            accR = accR + score_two_tap_term(y0, y1, has0[k], has1[k], W[k].w0, W[k].w1);
                         }
                     } else {  // (a mono row that is not placed: one term, both channels)
-                        const float term = whole ? x0 : score_stereo_term(x0, x1, has0[k], has1[k], W[k]);
+                        const float term = whole ? x0 : score_two_tap_term(x0, x1, has0[k], has1[k], W[k].w0, W[k].w1);
                         accL = accL + term;
                         accR = accR + term;
                     }

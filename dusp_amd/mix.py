@@ -5,6 +5,8 @@ a Float32Array (src/components/Sum.js:18-29,33-44): one f32 rounding per add, in
 front of the chain: one f32 rounding per product (Multiply.js:23-34)."""
 import numpy as np
 
+from .descriptor import DuspError
+
 
 def mix_chain(planar, gains=None, init=None, raw=False):
     """planar float32 [instances, channels, samples] -> float32 [channels, samples].
@@ -17,10 +19,7 @@ def mix_chain(planar, gains=None, init=None, raw=False):
     planar = np.asarray(planar, dtype=np.float32)
     if planar.ndim != 3 or planar.shape[0] < 1:
         raise ValueError("dusp-hip: planar must have shape (instances >= 1, channels, samples)")
-    if gains is not None:
-        gains = np.asarray(gains, dtype=np.float32)
-        if gains.shape != (planar.shape[0],):
-            raise ValueError("dusp-hip: gains must have shape (instances=%d,)" % planar.shape[0])
+    gains = _gains_table(gains, planar.shape[0], "instances")
     if init is not None:
         init = np.asarray(init, dtype=np.float32)
         if init.shape != planar.shape[1:]:
@@ -33,10 +32,7 @@ def mix_chain(planar, gains=None, init=None, raw=False):
         acc = init.copy() if init is not None else np.array(term(0), dtype=np.float32)
         for i in range(0 if init is not None else 1, planar.shape[0]):
             acc = acc + term(i)  # float32 + float32: one f32 rounding
-        assert acc.dtype == np.float32
-        if not raw:
-            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
-    return acc
+        return _chain_end(acc, raw)
 
 
 def score_chain(planar, onsets, n_total, lengths=None, gains=None, init=None, raw=False):
@@ -98,23 +94,42 @@ def _row_lengths(rows, lengths):
     return lengths
 
 
+def _gains_table(gains, n, noun="voices"):
+    """gains -> contiguous float32 [n], checked, or None; noun: what the caller counts (n_instances, instances, voices)"""
+    if gains is not None:
+        gains = np.ascontiguousarray(gains, dtype=np.float32)
+        if gains.shape != (n,):
+            raise ValueError("dusp-hip: gains must have shape (%s=%d,)" % (noun, n))
+    return gains
+
+
+def _chain_start(init, n_ch, n_total):
+    """what a chain starts from -> float32 [n_ch, n_total]: a copy of init, checked, or +0"""
+    if init is None:
+        return np.zeros((n_ch, n_total), dtype=np.float32)
+    init = np.asarray(init, dtype=np.float32)
+    if init.shape != (n_ch, n_total):
+        raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
+    return init.copy()
+
+
+def _chain_end(acc, raw):
+    """what a chain hands back: the sums as they stand (raw), or NaN and -0 as +0 (`acc || 0`)"""
+    assert acc.dtype == np.float32
+    with np.errstate(all="ignore"):
+        return acc if raw else np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
+
+
 def _chain(rows, n_ch, n_total, onsets, lengths, gains, fracs, init, raw, noun="voices", place=None):
     """The one chain behind score_chain, score_chain_rows and score_chain_rows_panned.  rows: a list of float32 [channels, samples_k];
     onsets, lengths: int64 [voices], checked by the caller; gains, fracs and init are checked here, in that order (they are refused in
     the same words by all three, but for the noun of the gains' shape).  place(k, x): what becomes of voice k's samples after the gain
     before they are added, float32 [channels, len] -> float32 [n_ch, len] (None: x itself)."""
-    if gains is not None:
-        gains = np.asarray(gains, dtype=np.float32)
-        if gains.shape != (len(rows),):
-            raise ValueError("dusp-hip: gains must have shape (%s=%d,)" % (noun, len(rows)))
+    gains = _gains_table(gains, len(rows), noun)
     if fracs is not None:
         fracs = check_fracs(fracs, len(rows))
-    if init is not None:
-        init = np.asarray(init, dtype=np.float32)
-        if init.shape != (n_ch, n_total):
-            raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
+    acc = _chain_start(init, n_ch, n_total)
     with np.errstate(all="ignore"):
-        acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
         for k, row in enumerate(rows):
             onset, length = int(onsets[k]), int(lengths[k])
             frac = fracs[k] if fracs is not None and length > 0 else 0  # (a voice of length 0 takes no part)
@@ -135,10 +150,7 @@ def _chain(rows, n_ch, n_total, onsets, lengths, gains, fracs, init, raw, noun="
             else:
                 for c in range(n_ch):
                     acc[c, t0:t1] = acc[c, t0:t1] + term[c]
-        assert acc.dtype == np.float32
-        if not raw:
-            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
-    return acc
+    return _chain_end(acc, raw)
 
 
 def check_fracs(fracs, n):
@@ -230,6 +242,14 @@ def pan_comp(pans):
     return np.array([math.pow(10, ((1 - abs(float(p))) * 1.5) / 20) for p in np.asarray(pans, dtype=np.float32).ravel()], dtype=np.float64)
 
 
+def _pan_unit(x, p, comp):
+    """The reference's Pan unit (Pan.js:21-22) over mono samples x float32 [len], panned to p with the compensation comp -> float32
+    [2, len]: float64 operations, each rounded by itself; one rounding to f32"""
+    xd, p = x.astype(np.float64), np.float64(p)
+    return np.stack([(((xd * (np.float64(1) - p)) / np.float64(2)) * comp).astype(np.float32),
+                     (((xd * (np.float64(1) + p)) / np.float64(2)) * comp).astype(np.float32)])
+
+
 def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=None, init=None, raw=False, comp=None, fracs=None):
     """rows: a list of MONO float32 arrays [1, samples_k], onsets int64 [voices], pans float32 [voices] (finite, NOT clamped) -> float32
     [2, n_total]: the contract of dusp_score_rows_pan_device.  It is score_chain_rows with the reference's Pan unit (Pan.js:21-22) applied
@@ -260,19 +280,9 @@ def score_chain_rows_panned(rows, onsets, pans, n_total, lengths=None, gains=Non
         raise ValueError("dusp-hip: pans must have shape (voices=%d,)" % n)
     if not np.all(np.isfinite(pans)):
         raise ValueError("dusp-hip: pans must be finite")
-    if comp is None:
-        comp = pan_comp(pans)
-    else:
-        comp = np.asarray(comp, dtype=np.float64)
-        if comp.shape != (n,):
-            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
+    comp = _comp_array(comp, n, lambda: pan_comp(pans))
 
-    def pan(k, x):  # the Pan unit: float64 operations, each rounded by itself; one rounding to f32
-        xd, p = x[0].astype(np.float64), np.float64(pans[k])
-        return np.stack([(((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32),
-                         (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)])
-
-    return _chain(rows, 2, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw, place=pan)
+    return _chain(rows, 2, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw, place=lambda k, x: _pan_unit(x[0], pans[k], comp[k]))
 
 
 def stereo_pans(pans, n):
@@ -324,21 +334,12 @@ def score_chain_rows_stereo(rows, onsets, pans, n_total, lengths=None, gains=Non
     onsets = _whole(onsets, n, "onsets")
     pans = stereo_pans(pans, n)
     check_stereo_kinds([r.shape[0] for r in rows], pans)
-    if comp is None:
-        comp = pan_comp(np.where(np.isnan(pans), np.float32(0), pans))
-    else:
-        comp = np.asarray(comp, dtype=np.float64)
-        if comp.shape != (n,):
-            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
+    comp = _comp_array(comp, n, lambda: pan_comp(np.where(np.isnan(pans), np.float32(0), pans)))
 
     def place(k, x):
         if x.shape[0] == 2:
             return x
-        if np.isnan(pans[k]):
-            return np.concatenate([x, x])
-        xd, p = x[0].astype(np.float64), np.float64(pans[k])  # the Pan unit: float64 operations, each rounded by itself; one rounding to f32
-        return np.stack([(((xd * (np.float64(1) - p)) / np.float64(2)) * comp[k]).astype(np.float32),
-                         (((xd * (np.float64(1) + p)) / np.float64(2)) * comp[k]).astype(np.float32)])
+        return np.concatenate([x, x]) if np.isnan(pans[k]) else _pan_unit(x[0], pans[k], comp[k])
 
     return _chain(rows, 2, n_total, onsets, _row_lengths(rows, lengths), gains, fracs, init, raw, place=place)
 
@@ -396,16 +397,9 @@ def score_chain_rows_placed(rows, onsets, delays, tap_gains, n_total, lengths=No
     delays, tap_gains = check_taps(delays, tap_gains, n)
     n_ch = delays.shape[1]
     lengths = _row_lengths(rows, lengths)
-    if gains is not None:
-        gains = np.asarray(gains, dtype=np.float32)
-        if gains.shape != (n,):
-            raise ValueError("dusp-hip: gains must have shape (voices=%d,)" % n)
-    if init is not None:
-        init = np.asarray(init, dtype=np.float32)
-        if init.shape != (n_ch, n_total):
-            raise ValueError("dusp-hip: init must have shape (channels=%d, n_total=%d)" % (n_ch, n_total))
+    gains = _gains_table(gains, n)
+    acc = _chain_start(init, n_ch, n_total)
     with np.errstate(all="ignore"):
-        acc = init.copy() if init is not None else np.zeros((n_ch, n_total), dtype=np.float32)
         for k, row in enumerate(rows):
             length = int(lengths[k])
             if length == 0:
@@ -423,10 +417,7 @@ def score_chain_rows_placed(rows, onsets, delays, tap_gains, n_total, lengths=No
                 t0, t1 = max(onset, 0), min(onset + len(term), n_total)
                 if t1 > t0:
                     acc[c, t0:t1] = acc[c, t0:t1] + term[t0 - onset:t1 - onset]  # float32 + float32: one f32 rounding
-        assert acc.dtype == np.float32
-        if not raw:
-            acc = np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
-    return acc
+    return _chain_end(acc, raw)
 
 
 def check_places(places, n, speakers=None):
@@ -492,3 +483,148 @@ def space_taps(places, speakers=None, decibels_per_metre=-3, sample_delay_per_me
                 delays[k, c] = f64(f32(f64(dist) * f64(sdpm)))
                 gains[k, c] = math.pow(10, float(db) / 20) if np.isfinite(db) else np.nan
     return check_taps(delays, gains, n)
+
+
+# ---- the placement of a call's voices: its keywords as one checked thing ----
+
+STEREO_NO_PLACES = "dusp-hip: places and stereo do not go together: a placed voice is mono and the speakers are the channels"
+SPACE_ALONE = "dusp-hip: places stand alone: together with pans or fracs they are refused (a sub-sample onset in front of a Space would be a second two-tap stage)"
+
+
+def pan_arrays(pans, n, comp=None):
+    """pans of n voices -> (float32 [n], float64 [n] compensation): checked — one finite pan a voice, not clamped — with the reference Pan
+    unit's compensation 10^((1 - |pan|) * 1.5 / 20) by math.pow where comp is None (pan_comp).  Needs no device."""
+    with np.errstate(all="ignore"):
+        pans = np.ascontiguousarray(pans, dtype=np.float32)
+    if pans.shape != (n,):
+        raise ValueError("dusp-hip: pans must have shape (voices=%d,)" % n)
+    if not np.all(np.isfinite(pans)):
+        raise ValueError("dusp-hip: the pan of voice %d is not finite" % int(np.argmax(~np.isfinite(pans))))
+    return pans, _comp_array(comp, n, lambda: pan_comp(pans))
+
+
+def stereo_pan_arrays(pans, n, comp=None):
+    """pans of n voices of a stereo piece -> (float32 [n] with NaN for "not placed", float64 [n] compensation): None (nothing placed)
+    or one entry a voice, a number, None or NaN; an infinite pan is refused (stereo_pans).  The compensation is pan_arrays'; an
+    unplaced voice's is 1 and is not read.  Needs no device."""
+    pans = stereo_pans(pans, n)
+
+    def made():
+        comp, placed = np.ones(n, dtype=np.float64), ~np.isnan(pans)
+        comp[placed] = pan_comp(pans[placed])
+        return comp
+
+    return pans, _comp_array(comp, n, made)
+
+
+def _comp_array(comp, n, made):
+    """the compensation of n voices -> float64 [n]: the caller's, checked, or made()"""
+    if comp is None:
+        return made()
+    comp = np.ascontiguousarray(comp, dtype=np.float64)
+    if comp.shape != (n,):
+        raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
+    return comp
+
+
+frac_arrays = check_fracs  # (the name the hosts know it by)
+
+
+def tap_arrays(taps, n):
+    """taps = (delays, gains) of n voices -> float64 (delays [n, C], gains [n, C]): checked — 1 .. 8 speakers, finite delays in
+    [0, 2^24] samples, finite gains — by the strings the library uses (check_taps).  Needs no device."""
+    try:
+        delays, gains = taps
+    except (TypeError, ValueError):
+        raise ValueError("dusp-hip: taps are a pair (delays, gains), each of shape (voices=%d, speakers)" % n)
+    return check_taps(delays, gains, n)
+
+
+def check_piece_channels(channels):
+    """channels[p]: the output channels of part p's circuit.  A piece has one channel count: refused by string otherwise."""
+    for p, c in enumerate(channels):
+        if c != channels[0]:
+            raise DuspError("dusp-hip: the voices of a piece must have one number of output channels: part %d has %d, part 0 has %d" % (p, c, channels[0]))
+    return channels[0]
+
+
+def check_pan_channels(channels):
+    """channels[p]: the output channels of part p's circuit.  A panned voice is mono: refused by string otherwise."""
+    for p, c in enumerate(channels):
+        if c != 1:
+            raise DuspError("dusp-hip: a panned voice is mono: part %d has %d output channels" % (p, c))
+    return 2
+
+
+def check_space_channels(channels, speakers):
+    """channels[p]: the output channels of part p's circuit.  A placed voice is mono: refused by string otherwise."""
+    for p, c in enumerate(channels):
+        if c != 1:
+            raise DuspError("dusp-hip: a placed voice is mono: part %d has %d output channels" % (p, c))
+    return speakers
+
+
+def check_stereo_channels(channels, part_of, pans):
+    """channels[p]: the output channels of part p's circuit; part_of[k]: voice k's part; pans: float32 with NaN for "not placed".  A
+    voice of a stereo piece has one or two channels, and one of two is not placed: refused by string otherwise."""
+    check_stereo_kinds([channels[p] for p in part_of], pans)
+    return 2
+
+
+class Placement:
+    """How the n voices of a score or piece are placed where they are added to the timeline: the keywords of a call — pans (with comp),
+    fracs, taps = (delays, gains) or, at sample_rate, a space = (places, speakers, decibels_per_metre, sample_delay_per_metre), and
+    stereo — checked once, by the strings the library uses.  Needs no device.
+        kind    "rows", "pan", "space" or "stereo": which chain the voices are held to (chain) and which entry of the library renders them
+        pans    float32 [n] — stereo: with NaN for a voice that is not placed — and comp, float64 [n]; both None without pans
+        fracs   float64 [n], or None
+        taps    (delays, gains), float64 [n, speakers] each, or None
+    fracs_first: the fractions are looked at before the pans, Context.render_score_parts' order of refusal (a piece's is pans first)."""
+
+    def __init__(self, n, pans=None, comp=None, fracs=None, taps=None, stereo=False, space=None, sample_rate=None, fracs_first=False):
+        self.refuse_together(pans, fracs, taps if space is None else space, stereo)
+        self.kind = "stereo" if stereo else "space" if taps is not None or space is not None else "pan" if pans is not None else "rows"
+        self.pans = self.comp = self.fracs = self.taps = None
+        if fracs is not None and fracs_first:
+            self.fracs = frac_arrays(fracs, n)
+        if stereo:
+            self.pans, self.comp = stereo_pan_arrays(pans, n, comp)
+        elif pans is not None:
+            self.pans, self.comp = pan_arrays(pans, n, comp)
+        if fracs is not None and not fracs_first:
+            self.fracs = frac_arrays(fracs, n)
+        if space is not None:
+            check_places(space[0], n, space[1])
+            self.taps = space_taps(*space, sample_rate=sample_rate)
+        elif taps is not None:
+            self.taps = tap_arrays(taps, n)
+
+    @staticmethod
+    def refuse_together(pans, fracs, places, stereo):
+        """what does not go together, refused before anything else of a call is looked at (places: taps or a space, whichever the call has)"""
+        if places is not None and stereo:
+            raise ValueError(STEREO_NO_PLACES)
+        if places is not None and (pans is not None or fracs is not None):
+            raise ValueError(SPACE_ALONE)
+
+    def keywords(self):
+        """-> the keywords of Context.render_score_parts that say the same"""
+        return dict(pans=self.pans, fracs=self.fracs, taps=self.taps, stereo=self.kind == "stereo")
+
+    def channels(self, voice_channels):
+        """the timeline's channels where a voice has voice_channels, unchecked: voices that do not fit are the library's to refuse"""
+        return self.taps[0].shape[1] if self.kind == "space" else voice_channels if self.kind == "rows" else 2
+
+    def timeline_channels(self, part_channels, part_of):
+        """part_channels[p]: the output channels of part p's circuit; part_of[k]: voice k's part -> the timeline's channels; parts that
+        do not fit the placement are refused by string"""
+        if self.kind == "stereo":
+            return check_stereo_channels(part_channels, part_of, self.pans)
+        if self.kind == "space":
+            return check_space_channels(part_channels, self.channels(1))
+        return check_pan_channels(part_channels) if self.kind == "pan" else check_piece_channels(part_channels)
+
+    @property
+    def chain(self):
+        """the contract the placed voices are held to, which takes the arrays held here beside the rows and onsets"""
+        return {"rows": score_chain_rows, "pan": score_chain_rows_panned, "space": score_chain_rows_placed, "stereo": score_chain_rows_stereo}[self.kind]

@@ -12,6 +12,7 @@ program with a per-instance parameter table.
 import numpy as np
 
 from . import descriptor, mix, runtime, wav
+from .mix import check_pan_channels, check_piece_channels, check_space_channels, check_stereo_channels  # noqa: F401 (what a piece's parts are held to)
 
 _contexts = {}
 
@@ -262,14 +263,14 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
 
     stereo=True: as render_piece's — voices of one or two channels, two channels out, pans optional and None / NaN for a voice that is
     not placed; the piece's call with the score as its one part, as with pans."""
-    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre),
-                         stereo=stereo)
+    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo))
 
 
-def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, pcm=None, space=None, stereo=False):
+def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if pans is not None or fracs is not None or space is not None or stereo:
-        return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, pans, True, fracs, pcm, space, stereo)
+    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space")):
+        return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
     uni, n_voice, n_total, onsets, lengths, gains, prog = _score_program(outlets, onsets, voice_duration, duration, lengths, gains, engine, device)
@@ -283,8 +284,8 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
                      tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
-    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, pans, fracs, (bit_depth, normalise),
-                         _space(places, speakers, decibels_per_metre, sample_delay_per_metre), stereo)
+    return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
@@ -335,52 +336,17 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def check_piece_channels(channels):
-    """channels[p]: the output channels of part p's circuit.  A piece has one channel count: refused by string otherwise."""
-    for p, c in enumerate(channels):
-        if c != channels[0]:
-            raise descriptor.DuspError("dusp-hip: the voices of a piece must have one number of output channels: part %d has %d, part 0 has %d" % (p, c, channels[0]))
-    return channels[0]
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo):
+    """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
+    known.  The Space keywords are one thing too, None without places (the other three alone say nothing)"""
+    return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo)
 
 
-def check_pan_channels(channels):
-    """channels[p]: the output channels of part p's circuit.  A panned voice is mono: refused by string otherwise."""
-    for p, c in enumerate(channels):
-        if c != 1:
-            raise descriptor.DuspError("dusp-hip: a panned voice is mono: part %d has %d output channels" % (p, c))
-    return 2
-
-
-def check_space_channels(channels, speakers):
-    """channels[p]: the output channels of part p's circuit.  A placed voice is mono: refused by string otherwise."""
-    for p, c in enumerate(channels):
-        if c != 1:
-            raise descriptor.DuspError("dusp-hip: a placed voice is mono: part %d has %d output channels" % (p, c))
-    return speakers
-
-
-def _space(places, speakers, decibels_per_metre, sample_delay_per_metre):
-    """the Space keywords of a call as one thing, None without places (the other three alone say nothing)"""
-    return None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre)
-
-
-def check_stereo_channels(channels, part_of, pans):
-    """channels[p]: the output channels of part p's circuit; part_of[k]: voice k's part; pans: float32 with NaN for "not placed".  A
-    voice of a stereo piece has one or two channels, and one of two is not placed: refused by string otherwise."""
-    mix.check_stereo_kinds([channels[p] for p in part_of], pans)
-    return 2
-
-
-def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None, one_part=False, fracs=None, space=None, stereo=False):
-    """-> PieceParts, samples of timeline, onsets, lengths, gains, channels, pans, fracs, taps (all checked: nothing is built yet).  With
-    pans the voices are mono and channels is the timeline's two; with a space (_space) they are mono, channels is the speakers' number
-    and taps the (delays, gains) of mix.space_taps at the voices' sample rate; pans, fracs and taps come back as None where none were
-    given.  stereo: the voices have one or two channels, channels is the timeline's two, and pans come back as float32 with NaN
-    for a voice that is not placed."""
-    if space is not None and stereo:
-        raise ValueError(runtime.STEREO_NO_PLACES)
-    if space is not None and (pans is not None or fracs is not None):
-        raise ValueError(runtime.SPACE_ALONE)
+def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, one_part=False):
+    """-> PieceParts, samples of timeline, onsets, lengths, gains, the timeline's channels, the voices' mix.Placement (all checked:
+    nothing is built yet).  placing: the call's placement keywords (_placing); a space becomes the taps of mix.space_taps at the
+    voices' sample rate, and parts whose channels do not fit the placement are refused (Placement.timeline_channels)."""
+    mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
     if n == 0:
@@ -396,35 +362,22 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans=None
         raise descriptor.DuspError("dusp-hip: voice_duration must cover at least one sample")
     n_total = _n_samples(duration, rate)
     onsets, lengths, gains = _voice_arrays(onsets, lengths, gains, n, np.array(voice_samples), "voices", "the voice's own samples")
-    if stereo:
-        pans, _ = runtime.stereo_pan_arrays(pans, n)
-    elif pans is not None:
-        pans, _ = runtime.pan_arrays(pans, n)
-    if fracs is not None:
-        fracs = runtime.frac_arrays(fracs, n)
-    taps = None
-    if space is not None:
-        mix.check_places(space[0], n, space[1])
-        taps = mix.space_taps(space[0], space[1], space[2], space[3], sample_rate=rate)
+    place = mix.Placement(n, sample_rate=rate, **placing)
     grouped = piece_parts(extractions, voice_samples)
     if one_part and len(grouped.parts) != 1:  # (render_score with pans or fracs)
         raise descriptor.DuspError("dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments")
     channels = [runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts]
-    if stereo:
-        return grouped, n_total, onsets, lengths, gains, check_stereo_channels(channels, grouped.part_of, pans), pans, fracs, taps
-    if taps is not None:
-        return grouped, n_total, onsets, lengths, gains, check_space_channels(channels, taps[0].shape[1]), pans, fracs, taps
-    return grouped, n_total, onsets, lengths, gains, check_pan_channels(channels) if pans is not None else check_piece_channels(channels), pans, fracs, taps
+    return grouped, n_total, onsets, lengths, gains, place.timeline_channels(channels, grouped.part_of), place
 
 
-def _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format=None, normalise=0, pans=None, fracs=None, taps=None, stereo=False):
+def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format=None, normalise=0):
     ctx = context(grouped.sample_rate, device)
     programs = []
     try:
         for uni, _ in grouped.parts:
             programs.append(ctx.build(uni.words, engine))
         parts = [(prog, n_voice, uni.n_instances, uni.params) for prog, (uni, n_voice) in zip(programs, grouped.parts)]
-        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps, stereo=stereo)
+        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, **place.keywords())
     finally:
         for prog in programs:
             prog.close()
@@ -462,24 +415,24 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     reads a mono input for every channel of a wider one), a voice of two channels keeps its channels and takes no pan (the Pan unit's
     inlet is mono).  What the reference renders for Sum.many over such voices behind their Delays, bit for bit
     (mix.score_chain_rows_stereo).  fracs work as above; places are refused."""
-    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs,
-                                space=_space(places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo)
+    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo), _one_part)
 
 
-def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, one_part, fracs, pcm=None, space=None, stereo=False):
+def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
     """render_piece (pcm None) and render_piece_pcm (pcm = (bit_depth, normalise))"""
     if pcm is not None:
         _check_pcm(*pcm)
-    grouped, n_total, onsets, lengths, gains, channels, pans, fracs, taps = _piece(outlets, onsets, voice_durations, duration, lengths, gains, pans, one_part, fracs, space, stereo)
+    grouped, n_total, onsets, lengths, gains, channels, place = _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, one_part)
     return _delivered(pcm, grouped.sample_rate, n_total, channels,
-                      lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, engine, device, tile_bytes, format, normalise, pans=pans, fracs=fracs, taps=taps, stereo=stereo))
+                      lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format, normalise))
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
                      tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
-    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, pans, _one_part, fracs, (bit_depth, normalise),
-                                _space(places, speakers, decibels_per_metre, sample_delay_per_metre), stereo)
+    return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import _whole, check_fracs, check_stereo_kinds, check_taps, pan_comp, stereo_pans
+from .mix import SPACE_ALONE, STEREO_NO_PLACES, Placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -132,60 +132,6 @@ class ScorePart(ctypes.Structure):
     _fields_ = [("prog", ctypes.c_void_p), ("n_instances", ctypes.c_size_t), ("n_voice_samples", ctypes.c_size_t), ("h_params", ctypes.c_void_p)]
 
 
-def pan_arrays(pans, n, comp=None):
-    """pans of n voices -> (float32 [n], float64 [n] compensation): checked — one finite pan a voice, not clamped — with the reference Pan
-    unit's compensation 10^((1 - |pan|) * 1.5 / 20) by math.pow where comp is None (dusp_amd/mix.py pan_comp).  Needs no device."""
-    with np.errstate(all="ignore"):
-        pans = np.ascontiguousarray(pans, dtype=np.float32)
-    if pans.shape != (n,):
-        raise ValueError("dusp-hip: pans must have shape (voices=%d,)" % n)
-    if not np.all(np.isfinite(pans)):
-        raise ValueError("dusp-hip: the pan of voice %d is not finite" % int(np.argmax(~np.isfinite(pans))))
-    if comp is None:
-        comp = pan_comp(pans)
-    else:
-        comp = np.ascontiguousarray(comp, dtype=np.float64)
-        if comp.shape != (n,):
-            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
-    return pans, comp
-
-
-def stereo_pan_arrays(pans, n, comp=None):
-    """pans of n voices of a stereo piece -> (float32 [n] with NaN for "not placed", float64 [n] compensation): None (nothing placed)
-    or one entry a voice, a number, None or NaN; an infinite pan is refused (dusp_amd/mix.py stereo_pans).  The compensation is
-    pan_arrays'; an unplaced voice's is 1 and is not read.  Needs no device."""
-    pans = stereo_pans(pans, n)
-    placed = ~np.isnan(pans)
-    if comp is None:
-        comp = np.ones(n, dtype=np.float64)
-        comp[placed] = pan_comp(pans[placed])
-    else:
-        comp = np.ascontiguousarray(comp, dtype=np.float64)
-        if comp.shape != (n,):
-            raise ValueError("dusp-hip: comp must have shape (voices=%d,)" % n)
-    return pans, comp
-
-
-STEREO_NO_PLACES = "dusp-hip: places and stereo do not go together: a placed voice is mono and the speakers are the channels"
-SPACE_ALONE = "dusp-hip: places stand alone: together with pans or fracs they are refused (a sub-sample onset in front of a Space would be a second two-tap stage)"
-
-
-def frac_arrays(fracs, n):
-    """fracs of n voices -> float64 [n]: checked — one finite fraction of a sample a voice, 0 <= f < 1 — by the strings the library uses
-    (dusp_amd/mix.py check_fracs).  Needs no device."""
-    return check_fracs(fracs, n)
-
-
-def tap_arrays(taps, n):
-    """taps = (delays, gains) of n voices -> float64 (delays [n, C], gains [n, C]): checked — 1 .. 8 speakers, finite delays in
-    [0, 2^24] samples, finite gains — by the strings the library uses (dusp_amd/mix.py check_taps).  Needs no device."""
-    try:
-        delays, gains = taps
-    except (TypeError, ValueError):
-        raise ValueError("dusp-hip: taps are a pair (delays, gains), each of shape (voices=%d, speakers)" % n)
-    return check_taps(delays, gains, n)
-
-
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
 # Page-locked memory is a machine-wide resource: results a caller keeps alive stay pinned, so beyond this many bytes in use per
 # context new results are ordinary (pageable) numpy arrays again (the staged download).  `render(..., pinned=False)` opts out per call.
@@ -258,15 +204,6 @@ def _score_rows(rows, row_samples, onsets, lengths):
 def _ptr(a, some=True):
     """the address of a host array for the library: NULL for None, and where the caller has nothing to be read (a call without voices)"""
     return a.ctypes.data if a is not None and some else None
-
-
-def _gains_table(gains, n, noun):
-    """gains -> contiguous float32 [n], checked, or None; noun: what the caller counts (n_instances, voices)"""
-    if gains is not None:
-        gains = np.ascontiguousarray(gains, dtype=np.float32)
-        if gains.shape != (n,):
-            raise ValueError("dusp-hip: gains must have shape (%s=%d,)" % (noun, n))
-    return gains
 
 
 def _pcm_out(ctx, format, normalise, frames, pinned, batch=None):
@@ -396,21 +333,24 @@ class Context:
         contract): rows are the voices' DEVICE pointers (ints; None or 0 for a voice of no samples), voice k planar f32
         [n_channels][row_samples[k]].  onsets and lengths are HOST arrays of whole numbers of samples, lengths in 0 .. row_samples[k].
         Everything else as score_device; score_last_ms() reports the call."""
+        self._score_rows_call(rows, row_samples, onsets, lengths, lambda n: (), lambda n, rows, samples, onsets, lengths: self._L.dusp_score_rows_device(
+            self._h, rows, samples, n, n_channels, onsets, lengths, d_gains, n_total_samples, d_init, int(bool(raw)), d_out, stream))
+
+    def _score_rows_call(self, rows, row_samples, onsets, lengths, placed, call):
+        """What the score_rows_* methods do alike: the rows' arrays, checked (_score_rows); what places the voices, checked — placed(n) ->
+        host arrays, alive across the call; and the library's entry, call(n, rows, samples, onsets, lengths as addresses, *those arrays)."""
         n = len(rows)
         pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
-        self._check(self._L.dusp_score_rows_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, n_channels, _ptr(onsets, n), _ptr(lengths), d_gains, n_total_samples,
-                                                   d_init, int(bool(raw)), d_out, stream))
+        arrays = placed(n)
+        self._check(call(n, _ptr(pointers, n), _ptr(samples, n), _ptr(onsets, n), _ptr(lengths), *arrays))
 
     def score_rows_pan(self, rows, row_samples, onsets, pans, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, comp=None, stream=None):
         """score_rows_device over MONO rows, voice k panned to pans[k] where it is added to a timeline of TWO channels
         (dusp_score_rows_pan_device; dusp_amd/mix.py score_chain_rows_panned is the contract): rows are the voices' DEVICE pointers, voice
         k f32 [row_samples[k]]; pans a HOST array of finite f32, not clamped; comp the f64 compensation per voice (None: math.pow's, the
         reference's formula); d_init (which may be d_out) and d_out f32 [2][n_total_samples].  score_last_ms() reports the call."""
-        n = len(rows)
-        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
-        pans, comp = pan_arrays(pans, n, comp)
-        self._check(self._L.dusp_score_rows_pan_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, _ptr(onsets, n), _ptr(lengths), d_gains, _ptr(pans, n), _ptr(comp, n),
-                                                       n_total_samples, d_init, int(bool(raw)), d_out, stream))
+        self._score_rows_call(rows, row_samples, onsets, lengths, lambda n: pan_arrays(pans, n, comp), lambda n, rows, samples, onsets, lengths, pans, comp: self._L.dusp_score_rows_pan_device(
+            self._h, rows, samples, n, onsets, lengths, d_gains, _ptr(pans, n), _ptr(comp, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def score_rows_frac(self, rows, row_samples, n_channels, onsets, fracs, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, pans=None,
                         comp=None, stream=None):
@@ -419,18 +359,14 @@ class Context:
         the contract): fracs a HOST array of finite f64 in [0, 1), None for all zero.  A voice with a fraction is heard through the
         reference Delay's two taps and covers one more sample; one without is the voice of those calls, and a call without any fraction
         launches their kernels.  score_last_ms() reports the call."""
-        n = len(rows)
-        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
-        if fracs is not None:
-            fracs = frac_arrays(fracs, n)
-        if pans is not None:
-            pans, comp = pan_arrays(pans, n, comp)
-            if n == 0:  # (no voices: `|| 0`, or a copy, of both channels of d_init; the pointer only says "two channels")
-                pans, comp = np.zeros(1, dtype=np.float32), np.ones(1, dtype=np.float64)
-        else:
-            comp = None
-        self._check(self._L.dusp_score_rows_frac_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, n_channels, _ptr(onsets, n), _ptr(fracs, n), _ptr(lengths), d_gains,
-                                                        _ptr(pans), _ptr(comp), n_total_samples, d_init, int(bool(raw)), d_out, stream))
+        def placed(n):
+            place = Placement(n, pans, comp, fracs, fracs_first=True)
+            if place.kind == "pan" and n == 0:  # (no voices: `|| 0`, or a copy, of both channels of d_init; the pointer only says "two channels")
+                return place.fracs, np.zeros(1, dtype=np.float32), np.ones(1, dtype=np.float64)
+            return place.fracs, place.pans, place.comp
+
+        self._score_rows_call(rows, row_samples, onsets, lengths, placed, lambda n, rows, samples, onsets, lengths, fracs, pans, comp: self._L.dusp_score_rows_frac_device(
+            self._h, rows, samples, n, n_channels, onsets, _ptr(fracs, n), lengths, d_gains, _ptr(pans), _ptr(comp), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def score_rows_space(self, rows, row_samples, onsets, delays, tap_gains, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, stream=None):
         """score_rows_device over MONO rows, voice k heard by speaker c — channel c of a timeline of C — through the gain tap_gains[k][c]
@@ -438,11 +374,8 @@ class Context:
         are the voices' DEVICE pointers, voice k f32 [row_samples[k]]; delays and tap_gains HOST arrays of f64 [voices][C], 1 <= C <= 8,
         the delays finite in [0, 2^24] and the gains finite (dusp_amd.space_taps makes both from places and speakers); d_init (which may
         be d_out) and d_out f32 [C][n_total_samples].  score_last_ms() reports the call."""
-        n = len(rows)
-        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
-        delays, tap_gains = tap_arrays((delays, tap_gains), n)
-        self._check(self._L.dusp_score_rows_space_device(self._h, _ptr(pointers, n), _ptr(samples, n), n, delays.shape[1], _ptr(onsets, n), _ptr(lengths), d_gains,
-                                                         _ptr(delays, n), _ptr(tap_gains, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
+        self._score_rows_call(rows, row_samples, onsets, lengths, lambda n: tap_arrays((delays, tap_gains), n), lambda n, rows, samples, onsets, lengths, delays, tap_gains: self._L.dusp_score_rows_space_device(
+            self._h, rows, samples, n, delays.shape[1], onsets, lengths, d_gains, _ptr(delays, n), _ptr(tap_gains, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def score_rows_stereo(self, rows, row_samples, row_channels, onsets, pans, n_total_samples, d_out, lengths=None, d_gains=None, d_init=None, raw=False, comp=None,
                           fracs=None, stream=None):
@@ -451,18 +384,16 @@ class Context:
         pans a HOST array of f32 with NaN (or None) for a voice that is not placed (None: nothing placed) — a mono voice with a finite
         pan is score_rows_pan's voice, one without feeds both channels, a voice of two channels is not placed; fracs as score_rows_frac's
         (None: all zero); d_init (which may be d_out) and d_out f32 [2][n_total_samples].  score_last_ms() reports the call."""
-        n = len(rows)
-        pointers, samples, onsets, lengths = _score_rows(rows, row_samples, onsets, lengths)
-        channels = np.asarray(row_channels) if n else np.zeros(0, dtype=np.uint32)
-        if channels.shape != (n,) or channels.dtype.kind not in "iu":
-            raise ValueError("dusp-hip: row_channels must be whole numbers of shape (voices=%d,)" % n)
-        pans, comp = stereo_pan_arrays(pans, n, comp)
-        check_stereo_kinds(channels.tolist(), pans)
-        channels = np.ascontiguousarray(channels, dtype=np.uint32)
-        if fracs is not None:
-            fracs = frac_arrays(fracs, n)
-        self._check(self._L.dusp_score_rows_stereo_device(self._h, _ptr(pointers, n), _ptr(samples, n), _ptr(channels, n), n, _ptr(onsets, n), _ptr(fracs, n), _ptr(lengths),
-                                                          d_gains, _ptr(pans, n), _ptr(comp, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
+        def placed(n):
+            channels = np.asarray(row_channels) if n else np.zeros(0, dtype=np.uint32)
+            if channels.shape != (n,) or channels.dtype.kind not in "iu":
+                raise ValueError("dusp-hip: row_channels must be whole numbers of shape (voices=%d,)" % n)
+            place = stereo_pan_arrays(pans, n, comp)
+            check_stereo_kinds(channels.tolist(), place[0])
+            return (np.ascontiguousarray(channels, dtype=np.uint32), frac_arrays(fracs, n) if fracs is not None else None) + place
+
+        self._score_rows_call(rows, row_samples, onsets, lengths, placed, lambda n, rows, samples, onsets, lengths, channels, fracs, pans, comp: self._L.dusp_score_rows_stereo_device(
+            self._h, rows, samples, _ptr(channels, n), n, onsets, _ptr(fracs, n), lengths, d_gains, _ptr(pans, n), _ptr(comp, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
                            pans=None, fracs=None, taps=None, stereo=False):
@@ -481,10 +412,7 @@ class Context:
         stereo=True: the parts have ONE OR TWO output channels and the result has two (dusp_render_host_score_parts_stereo;
         mix.score_chain_rows_stereo): pans may be None (nothing placed) or hold None / NaN for a voice that is not placed, and a voice
         of a two-channel part is not placed; fracs as above.  Not together with taps."""
-        if taps is not None and stereo:
-            raise ValueError(STEREO_NO_PLACES)
-        if taps is not None and (pans is not None or fracs is not None):
-            raise ValueError(SPACE_ALONE)
+        Placement.refuse_together(pans, fracs, taps, stereo)
         if not parts:
             raise ValueError("dusp-hip: a piece has at least one part")
         n = len(part_of)
@@ -503,35 +431,22 @@ class Context:
         for p, (prog, n_voice_samples, n_instances, params) in enumerate(parts):
             keep.append(prog._params_table(params, n_instances, "dusp-hip: the params of part %d must have shape" % p))
             table[p] = ScorePart(prog._h, n_instances, n_voice_samples, _ptr(keep[-1]))
-        n_ch = parts[0][0].n_out_channels
-        entry = self._L.dusp_render_host_score_parts
-        args = [table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data, _ptr(lengths), _ptr(gains), n_total_samples, int(tile_bytes)]
-        if fracs is not None:
-            fracs = frac_arrays(fracs, n)
-        comp = None
-        if taps is not None:  # (the speakers and the taps behind the gains)
-            delays, tap_gains = tap_arrays(taps, n)
-            n_ch = delays.shape[1]  # (parts that are not mono: the library refuses them)
-            entry = self._L.dusp_render_host_score_parts_space
-            args[7:7] = (n_ch, delays.ctypes.data, tap_gains.ctypes.data)
-        if stereo:
-            pans, comp = stereo_pan_arrays(pans, n)
-            check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], pans)
-            n_ch = 2
-        elif pans is not None:
-            pans, comp = pan_arrays(pans, n)
-            n_ch = 2  # (parts that are not mono: the library refuses them)
-        if stereo:  # (the fractions, or NULL, behind the onsets; the pans and their compensation behind the gains)
-            entry = self._L.dusp_render_host_score_parts_stereo
-            args[7:7] = (pans.ctypes.data, comp.ctypes.data)
-            args[5:5] = (_ptr(fracs),)
-        elif fracs is not None:  # (the fractions behind the onsets; the pans and their compensation, or two NULLs, behind the gains)
-            entry = self._L.dusp_render_host_score_parts_frac
-            args[7:7] = (_ptr(pans), _ptr(comp))
-            args[5:5] = (fracs.ctypes.data,)
-        elif pans is not None:  # (the pans and their compensation behind the gains)
-            entry = self._L.dusp_render_host_score_parts_pan
-            args[7:7] = (_ptr(pans), _ptr(comp))
+        place = Placement(n, pans, None, fracs, taps, stereo, fracs_first=True)
+        if place.kind == "stereo":
+            check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], place.pans)
+        n_ch = place.channels(parts[0][0].n_out_channels)  # (parts that do not fit the placement: the library refuses them)
+        voices = (table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data)
+        scaled, placed, timeline = (_ptr(lengths), _ptr(gains)), (_ptr(place.pans), _ptr(place.comp)), (n_total_samples, int(tile_bytes))
+        if place.kind == "space":
+            entry, args = self._L.dusp_render_host_score_parts_space, voices + scaled + (n_ch, place.taps[0].ctypes.data, place.taps[1].ctypes.data) + timeline
+        elif place.kind == "stereo":
+            entry, args = self._L.dusp_render_host_score_parts_stereo, voices + (_ptr(place.fracs),) + scaled + placed + timeline
+        elif place.fracs is not None:  # (with the pans and their compensation, or two NULLs)
+            entry, args = self._L.dusp_render_host_score_parts_frac, voices + (_ptr(place.fracs),) + scaled + placed + timeline
+        elif place.kind == "pan":
+            entry, args = self._L.dusp_render_host_score_parts_pan, voices + scaled + placed + timeline
+        else:
+            entry, args = self._L.dusp_render_host_score_parts, voices + scaled + timeline
         fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
         self._check(entry(*args, fmt, normalise, out.ctypes.data, _ptr(peak)))
         return out if peak is None else (out, peak[0])

@@ -100,7 +100,7 @@ int main() {
             dusp::ScoreRowsPlan P;
             const bool whole = layout != 2 || init != 2;  // a window only in place: outside it nothing is written
             const int64_t rc = dusp::score_rows_plan(onsets.data(), with_lens ? lens.data() : nullptr, samples.data(), addr.data(), (size_t)N, NT, whole,
-                                                     layout == 3 ? 600 : dusp::kScorePlanBytes, P, fracs.data());
+                                                     layout == 3 ? 600 : dusp::kScorePlanBytes, P, {fracs.data()});
             if (rc != -1) { bad++; continue; }
             if (P.n_entries() == 0) continue;  // (no listed voice: the launch is the existing kernels')
             doubled += P.block_shift > dusp::kScoreGroupShift;
@@ -144,7 +144,7 @@ int main() {
             }
             {
                 std::vector<unsigned char> packed;
-                const size_t at = dusp::score_rows_plan_pack(P, packed);
+                const size_t at = dusp::score_plan_pack(P, packed);
                 void *image = nullptr, *coeff = nullptr, *weights = nullptr;  // exact sizes, on the boundaries the device's buffer gives them
                 if (at != 0 || posix_memalign(&image, 32, std::max<size_t>(packed.size(), 1)) != 0) { bad++; continue; }
                 if (posix_memalign(&coeff, 32, (size_t)N * sizeof(dusp::ScorePan)) != 0) { bad++; free(image); continue; }

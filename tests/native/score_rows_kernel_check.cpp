@@ -68,7 +68,7 @@ int main() {
             dusp::ScoreRowsPlan P;
             const bool whole = layout != 2 || init != 2;  // a window only in place: outside it nothing is written
             const int64_t rc = dusp::score_rows_plan(onsets.data(), with_lens ? lens.data() : nullptr, samples.data(), addr.data(), (size_t)N, NT, whole,
-                                                     layout == 3 ? 600 : dusp::kScorePlanBytes, P);
+                                                     layout == 3 ? 600 : dusp::kScorePlanBytes, P, {});
             if (rc != -1) { bad++; continue; }
             doubled += P.block_shift > dusp::kScoreGroupShift;
             windows += !whole && P.w_hi > P.w_lo && (P.w_lo > 0 || P.w_hi < NT);
@@ -91,7 +91,7 @@ int main() {
             }
             if (P.w_hi > P.w_lo) {
                 std::vector<unsigned char> packed;
-                const size_t at = dusp::score_rows_plan_pack(P, packed);
+                const size_t at = dusp::score_plan_pack(P, packed);
                 void *image = nullptr;  // exact size, on the 32-byte boundary the device's buffer gives it
                 if (at != 0 || posix_memalign(&image, 32, std::max<size_t>(packed.size(), 1)) != 0) { bad++; continue; }
                 memcpy(image, packed.data(), packed.size());

@@ -41,7 +41,7 @@ int main() {
             lengths[k] = lk == 0 ? 0 : lk == 1 ? std::min<int64_t>(1, samples[k]) : lk == 2 ? (int64_t)samples[k] : pick(0, (int64_t)samples[k]);
         }
         ScoreRowsPlan P;
-        const int64_t rc = score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, P);
+        const int64_t rc = score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, P, {});
         cases++;
         bool ok = rc == -1;
         auto span = [&](size_t k, int64_t &lo, int64_t &hi) {  // brute force, in __int128 so that the check itself cannot overflow
@@ -86,7 +86,7 @@ int main() {
                       std::vector<uint32_t>(P.entries.begin() + P.block_first[b], P.entries.begin() + P.block_first[b + 1]) == want;
             }
             std::vector<unsigned char> image(3);  // the packed image: 32-byte aligned, the three arrays one behind the other
-            const size_t at = score_rows_plan_pack(P, image);
+            const size_t at = score_plan_pack(P, image);
             ok &= at == 32 && image.size() == at + P.bytes();
             for (size_t k = 0; k < kScoreEntryPad; k++) ok &= P.entries[P.n_entries() + k] == 0;
             if (equal_rows && budget == kScorePlanBytes) {  // rows of one length: score_plan's lists and window
@@ -104,13 +104,13 @@ int main() {
         uint32_t samples[3] = {4, 8, 2};
         ScoreRowsPlan P;
         cases += 4;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P) != 1;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {}) != 1;
         len[1] = -1;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P) != 1;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {}) != 1;
         len[1] = 8;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P) != -1;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {}) != -1;
         len[2] = 3;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P) != 2;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {}) != 2;
     }
     printf("{\"cases\": %ld, \"bad\": %ld, \"doubled\": %ld, \"far_onsets\": %ld, \"empty_tiles\": %ld, \"empty_rows\": %ld}\n", cases, bad, doubled, far_onsets, empty_tiles, empty_rows);
     return bad != 0;

@@ -52,7 +52,7 @@ int main() {
         }
         zero_fracs += all_zero;
         ScoreRowsPlan P;
-        const int64_t rc = score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, P, fracs.data());
+        const int64_t rc = score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, P, {fracs.data()});
         cases++;
         bool ok = rc == -1;
         auto length = [&](size_t k) { return with_lengths ? lengths[k] : (int64_t)samples[k]; };
@@ -108,7 +108,7 @@ int main() {
         }
         if (all_zero) {  // all fractions zero: the plan made without fractions, record for record
             ScoreRowsPlan Q;
-            ok &= score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, Q) == -1;
+            ok &= score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, Q, {}) == -1;
             ok &= Q.block_first == P.block_first && Q.entries == P.entries && Q.w_lo == P.w_lo && Q.w_hi == P.w_hi && Q.t_lo == P.t_lo && Q.t_hi == P.t_hi &&
                   Q.block_shift == P.block_shift && Q.first_block == P.first_block && Q.voices.size() == P.voices.size() &&
                   (n == 0 || memcmp(Q.voices.data(), P.voices.data(), n * sizeof(ScoreRow)) == 0);
@@ -123,9 +123,9 @@ int main() {
         uint32_t samples[3] = {4, 8, 2};
         double fr[3] = {0.25, 0.5, 0.75};
         ScoreRowsPlan P;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, fr) != 1;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {fr}) != 1;
         len[1] = 8;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, fr) != -1;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {fr}) != -1;
         bad += !(P.voices[0].hi == 5 && P.voices[0].pad == 4 && P.voices[1].hi == 14 && P.voices[2].hi == 0 && P.t_hi == 14);
     }
     printf("{\"cases\": %ld, \"bad\": %ld, \"doubled\": %ld, \"far_onsets\": %ld, \"tail_only\": %ld, \"two_taps\": %ld, \"zero_fracs\": %ld}\n", cases, bad, doubled, far_onsets,

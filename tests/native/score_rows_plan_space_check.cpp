@@ -65,7 +65,7 @@ int main() {
         }
         zero_taps += all_zero;
         ScoreRowsPlan P;
-        const int64_t rc = score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, P, nullptr, taps.data(), C);
+        const int64_t rc = score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, P, {nullptr, taps.data(), C});
         cases++;
         bool ok = rc == -1;
         auto length = [&](size_t k) { return with_lengths ? lengths[k] : (int64_t)samples[k]; };
@@ -141,7 +141,7 @@ int main() {
         }
         if (all_zero) {  // no shift and no fraction anywhere: the lists of the plan made without taps; only pad differs (len, not 0)
             ScoreRowsPlan Q;
-            ok &= score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, Q) == -1;
+            ok &= score_rows_plan(onsets.data(), with_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, n_total, whole, budget, Q, {}) == -1;
             ok &= Q.block_first == P.block_first && Q.entries == P.entries && Q.w_lo == P.w_lo && Q.w_hi == P.w_hi && Q.t_lo == P.t_lo && Q.t_hi == P.t_hi &&
                   Q.block_shift == P.block_shift && Q.first_block == P.first_block && Q.voices.size() == P.voices.size();
             for (size_t k = 0; ok && k < n; k++)
@@ -160,9 +160,9 @@ int main() {
         uint32_t samples[3] = {4, 8, 2};
         const ScoreSpaceTap T[6] = {score_space_tap(0.0, 1.0), score_space_tap(10.5, 1.0), score_space_tap(1.0, 1.0), score_space_tap(2.0, 1.0), score_space_tap(0.0, 1.0), score_space_tap(16777216.0, 1.0)};
         ScoreRowsPlan P;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, nullptr, T, 2) != 1;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {nullptr, T, 2}) != 1;
         len[1] = 8;
-        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, nullptr, T, 2) != -1;
+        bad += score_rows_plan(on, len, samples, nullptr, 3, 100, true, kScorePlanBytes, P, {nullptr, T, 2}) != -1;
         bad += !(P.voices[0].lo == 0 && P.voices[0].hi == 15 && P.voices[0].pad == 4 && P.voices[1].lo == 6 && P.voices[1].hi == 15 && P.voices[2].hi == 0 && P.t_hi == 15);
     }
     printf("{\"cases\": %ld, \"bad\": %ld, \"doubled\": %ld, \"far_onsets\": %ld, \"disjoint\": %ld, \"two_taps\": %ld, \"zero_taps\": %ld}\n", cases, bad, doubled, far_onsets,

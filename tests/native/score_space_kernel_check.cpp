@@ -95,7 +95,7 @@ int main() {
             dusp::ScoreRowsPlan P;
             const bool whole = layout != 2 || init != 2;  // a window only in place: outside it nothing is written
             const int64_t rc = dusp::score_rows_plan(onsets.data(), with_lens ? lens.data() : nullptr, samples.data(), addr.data(), (size_t)N, NT, whole,
-                                                     layout == 3 ? 600 : dusp::kScorePlanBytes, P, nullptr, taps, (size_t)C);
+                                                     layout == 3 ? 600 : dusp::kScorePlanBytes, P, {nullptr, taps, (size_t)C});
             if (rc != -1) { bad++; free(tapmem); continue; }
             if (P.n_entries() == 0) { free(tapmem); continue; }  // (no listed voice: the launch is the rows kernel's)
             doubled += P.block_shift > dusp::kScoreGroupShift;
@@ -149,7 +149,7 @@ int main() {
             }
             {
                 std::vector<unsigned char> packed;
-                const size_t at = dusp::score_rows_plan_pack(P, packed);
+                const size_t at = dusp::score_plan_pack(P, packed);
                 void *image = nullptr;
                 if (at != 0 || posix_memalign(&image, 32, std::max<size_t>(packed.size(), 1)) != 0) { bad++; free(tapmem); continue; }
                 memcpy(image, packed.data(), packed.size());

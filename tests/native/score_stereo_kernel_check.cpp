@@ -96,11 +96,11 @@ int main() {
             const bool whole = layout != 2 || init != 2;  // a window only in place: outside it nothing is written
             const size_t budget = layout == 3 ? 600 : dusp::kScorePlanBytes;
             const int64_t rc = dusp::score_rows_plan(onsets.data(), with_lens ? lens.data() : nullptr, samples.data(), addr.data(), (size_t)N, NT, whole, budget, P,
-                                                     with_fracs ? fracs.data() : nullptr, nullptr, 0, channels.data(), pans.data());
+                                                     {with_fracs ? fracs.data() : nullptr, nullptr, 0, channels.data(), pans.data()});
             if (rc != -1) { bad++; continue; }
             {   // the same call without row_channels: the plan it always was, but for the strides of the mono rows
                 dusp::ScoreRowsPlan Q;
-                dusp::score_rows_plan(onsets.data(), with_lens ? lens.data() : nullptr, samples.data(), addr.data(), (size_t)N, NT, whole, budget, Q, with_fracs ? fracs.data() : nullptr);
+                dusp::score_rows_plan(onsets.data(), with_lens ? lens.data() : nullptr, samples.data(), addr.data(), (size_t)N, NT, whole, budget, Q, {with_fracs ? fracs.data() : nullptr});
                 bool same = Q.block_first == P.block_first && Q.entries == P.entries && Q.w_lo == P.w_lo && Q.w_hi == P.w_hi && Q.block_shift == P.block_shift && Q.voices.size() == P.voices.size();
                 for (int k = 0; same && k < N; k++) {
                     const dusp::ScoreRow &a = P.voices[k], &b = Q.voices[k];
@@ -162,7 +162,7 @@ int main() {
             }
             if (P.w_hi > P.w_lo && P.n_entries() > 0) {  // (as the ABI: no listed voice, no plan, and the launch is the pan kernel's)
                 std::vector<unsigned char> packed;
-                const size_t at = dusp::score_rows_plan_pack(P, packed);
+                const size_t at = dusp::score_plan_pack(P, packed);
                 void *image = nullptr, *coeff = nullptr, *weights = nullptr;  // exact sizes, on the boundaries the device's buffer gives them
                 if (at != 0 || posix_memalign(&image, 32, std::max<size_t>(packed.size(), 1)) != 0) { bad++; continue; }
                 if (posix_memalign(&coeff, 32, (size_t)N * sizeof(dusp::ScorePan)) != 0) { bad++; free(image); continue; }
