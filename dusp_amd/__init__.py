@@ -10,7 +10,7 @@ from .mix import space_taps, split_onsets  # noqa: F401
 from .graph import (Abs, AllPass, Circuit, CircleBuffer, CircleBufferReader, CircleBufferWriter, Clip, CombFilter, DecibelToScaler, Delay,  # noqa: F401
                     Divide, Filter, FixedDelay, FixedMultiply, Gain, MonoDelay, MultiChannelOsc, ReadBackDelay, HardClipAbove, HardClipBelow, Multiply, Osc, PolarityInvert, Pow,
                     Ramp, Repeater, SecondsToSamples, SemitoneToRatio, Subtract, Sum, Unit,
-                    AHD, ConcatChannels, CrossFader, HostSource, MidiToFrequency, Pan, PickChannel, Rescale, SampleRateRedux, Shape, Timer, VectorMagnitude)
+                    AHD, ConcatChannels, CrossFader, HostSource, MasterInput, MidiToFrequency, Pan, PickChannel, Rescale, SampleRateRedux, Shape, Timer, VectorMagnitude)
 from .render import ChannelData, render_many, render_mix, render_mix_pcm, render_mix_wav, render_piece, render_piece_pcm, render_piece_wav, render_score, render_score_pcm, render_score_wav, renderChannelData  # noqa: F401
 from .runtime import Context, DuspHipError, Program  # noqa: F401
 

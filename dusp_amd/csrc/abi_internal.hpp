@@ -429,8 +429,9 @@ struct TiledBatch {
     TiledBatch(dusp_program *prog, size_t n_instances, const float *h_params, const float *h_gains, size_t tile);  // tiles of `tile` instances
     TiledBatch(dusp_program *prog, size_t n_instances, const float *h_params, const std::vector<size_t> &starts);  // tiles [starts[i], starts[i + 1])
     ~TiledBatch();
-    // instances [lo, lo + n): their columns and gains to the device, their PCM into d_host_out
-    int render_tile(size_t lo, size_t n, size_t n_samples);
+    // instances [lo, lo + n): their columns and gains to the device, their PCM into d_host_out.  d_inputs: the input streams of a
+    // program that has some, [n_inputs][n][n_samples] in device memory (the master of a piece reads the timeline: abi_score.hip)
+    int render_tile(size_t lo, size_t n, size_t n_samples, const float *d_inputs = nullptr);
 
 private:
     void gather(const float *h_params, size_t lo, size_t n);

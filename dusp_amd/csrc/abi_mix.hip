@@ -70,14 +70,14 @@ TiledBatch::~TiledBatch() {
     prog->param_bound.clear();
     prog->mixed = true;  // (whichever tile was the last to render, the whole batch it was not)
 }
-int TiledBatch::render_tile(size_t lo, size_t n, size_t n_samples) {
+int TiledBatch::render_tile(size_t lo, size_t n, size_t n_samples, const float *d_inputs) {
     dusp_ctx *ctx = prog->ctx;
     if (n_params) {
         HIP_TRY(ctx, hipMemcpyAsync(prog->d_host_par.p, &cols[n_params * lo], n_params * n * sizeof(float), hipMemcpyHostToDevice, stream));
         staged = true;
     }
     if (h_gains) HIP_TRY(ctx, hipMemcpyAsync(prog->d_mix_gains.p, h_gains + lo, n * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (int rc = render_device_unguarded(prog, n, n_samples, n_params ? prog->d_host_par.p : nullptr, nullptr, prog->d_host_out.p, stream)) return rc;
+    if (int rc = render_device_unguarded(prog, n, n_samples, n_params ? prog->d_host_par.p : nullptr, d_inputs, prog->d_host_out.p, stream)) return rc;
     return check_guards(prog, stream);
 }
 

@@ -1,7 +1,8 @@
 // abi_score.hip — the C ABI (include/dusp_hip.h): voices mixed at per-voice onsets into a timeline (score_plan.hpp and the six score
 // engines): the plans' image on the device, the placement of a rows call, the one launch path, the device entries (dusp_score_device;
 // dusp_score_rows_device and its pan, frac, space and stereo forms) and the host round trips (dusp_render_host_score;
-// dusp_render_host_score_parts and its pan, frac, space and stereo forms).
+// dusp_render_host_score_parts and its pan, frac, space and stereo forms; dusp_render_host_score_piece, which is all of them and takes
+// the master of a piece).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -307,6 +308,48 @@ static int score_deliver_host(dusp_program *prog, const char *who, ScoreKind kin
     return DUSP_OK;
 }
 
+// ---- the master of a piece: one mono circuit over every channel of the timeline ----
+
+// What a piece's master is held to before anything renders; n_ch: the timeline's channels, each an instance of the master
+static int score_master_check(dusp_ctx *ctx, const std::string &w, const dusp_score_master *master, const dusp_score_part *parts, size_t n_parts, size_t n_ch, size_t n_total) {
+    dusp_program *m = master->prog;
+    if (!m) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master's program is NULL");
+    if (m->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master was built on another context: it shares the one of the piece's parts");
+    for (size_t p = 0; p < n_parts; p++)
+        if (parts[p].prog == m)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master is also part " + std::to_string(p) + ": its buffers would be used twice; build it on its own");
+    if (m->P.g.n_inputs != 1)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a master reads exactly one input stream (the timeline's channel), this program has " + std::to_string(m->P.g.n_inputs));
+    if (m->P.out_bufs.size() != 1)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a master has one output channel, this program has " + std::to_string(m->P.out_bufs.size()) +
+                                        ": it is applied to every channel of the timeline by itself");
+    if (m->resumable) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, w + ": a resumable program (DUSP_ENGINE_RESUMABLE) is not a master: every call renders it from its initial state");
+    if (m->P.g.n_params > 0 && !master->h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master has parameters but its h_params is NULL");
+    if (!samples_in_range(n_total) || n_ch * n_total > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master renders channels x timeline samples, which must not exceed 2^31: render such a piece in windows of the timeline without a master");
+    return DUSP_OK;
+}
+
+// What a host render with a master ends with once its tiles are added to the running sums (prog->d_mix, [n_ch][n_total]): the RAW sums —
+// no `|| 0`: a unit behind a Sum hears the Sum's own values — are the master's input block as they stand, channel c the one input stream
+// of instance c; its render from its initial state, deciding as a tile of a mix decides (it waits for its compiled kernel), applies
+// `|| 0` at its own copy-out; then the delivery from the master's buffer, which waits for the stream, and the guard checks
+static int score_master_deliver_host(dusp_program *prog, const char *who, const dusp_score_master *master, size_t n_ch, size_t n_total, int format, int normalise, float *h_peak,
+                                     void *h_out) {
+    dusp_ctx *ctx = prog->ctx;
+    dusp_program *m = master->prog;
+    {
+        TiledBatch channels(m, n_ch, master->h_params, nullptr, n_ch);  // (one tile: all channels; what changes bits is decided as for a mix)
+        if (int rc = channels.render_tile(0, n_ch, n_total, prog->d_mix.p)) return rc;
+        if (int rc = deliver_host(prog, m->d_host_out.p, nullptr, 1, n_ch, n_total, format, normalise, h_peak, h_out)) return rc;
+        channels.staged = false;  // (the delivery has waited for the stream)
+    }
+    if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
+    if (int rc = check_guards(m, ctx->stream)) return rc;
+    return DUSP_OK;
+}
+
 // ---- device entries ----
 
 extern "C" {
@@ -454,10 +497,11 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
 
 // dusp_render_host_score_parts and its pan, frac, space and stereo forms: the parts' voices placed as `given` says (pan, space: mono
 // parts; stereo: parts of one and of two output channels, and the voices' channels, given.h_row_channels, are made here from the
-// parts') into a timeline of given.timeline_channels(a voice's)
+// parts') into a timeline of given.timeline_channels(a voice's).  master (optional; dusp_render_host_score_piece): a mono circuit with one
+// input stream, rendered over every channel of the raw timeline before the delivery (score_master_deliver_host)
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const ScorePlacement &given, size_t n_total_samples, size_t tile_bytes, int format,
-                                   int normalise, void *h_out, float *h_peak) {
+                                   int normalise, void *h_out, float *h_peak, const dusp_score_master *master = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
@@ -492,6 +536,8 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
                 CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": parts " + std::to_string(q) + " and " + std::to_string(p) + " are the same program: its tile buffer would be used twice; make them one part or build it twice");
         n_listed += parts[p].n_instances;
     }
+    if (master)
+        if (int rc = score_master_check(ctx, w, master, parts, n_parts, n_out_ch, n_total_samples)) return rc;
     if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
     if (int rc = place.check_values(ctx, who, n_voices)) return rc;
@@ -572,6 +618,10 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         fprintf(stderr, "[dusp host piece] %zu plans over %zu voices of %zu parts in %.0f us on the host: %zu bytes\n", n_tiles, n_voices, n_parts,
                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count(), ctx->h_score_plan.size());
     HIP_TRY(ctx, prog0->d_mix.ensure(n_out_ch * n_total_samples));  // the timeline's running sums
+    if (master) {  // (... and what the master makes of them: one more [channels][n_total], and its columns)
+        HIP_TRY(ctx, master->prog->d_host_out.ensure(n_out_ch * n_total_samples));
+        if (master->prog->P.g.n_params) HIP_TRY(ctx, master->prog->d_host_par.ensure((size_t)master->prog->P.g.n_params * n_out_ch));
+    }
     if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once)
         HIP_TRY(ctx, prog0->d_mix_gains.ensure(n_voices));
         HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -591,8 +641,10 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         const float *d_gains = h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr;
         if (int rc = score_launch(ctx, launches[i], n_out_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream, nullptr, 0)) return rc;
     }
-    // (`|| 0` is the rows kernel's over the timeline's channels, panned or not)
-    if (int rc = score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)) return rc;
+    // (`|| 0` is the rows kernel's over the timeline's channels, panned or not; behind a master it is the master's own copy-out's)
+    if (int rc = master ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
+                        : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out))
+        return rc;
     waited();  // (the delivery has waited for the stream)
     return DUSP_OK;
     });
@@ -663,6 +715,35 @@ int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_p
     if (!h_pans) CTX_FAIL(parts[0].prog->ctx, DUSP_ERR_ARG, "dusp_render_host_score_parts_stereo: h_pans is NULL");
     return render_host_score_parts("dusp_render_host_score_parts_stereo", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains,
                                    ScorePlacement(ScoreKind::stereo, h_fracs, h_pans, h_comp), n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
+}
+
+// One entry for every placement, with or without a master: the placement as a record (dusp_score_placement; NULL: plain rows)
+int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                 const float *h_gains, const dusp_score_placement *placement, const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes,
+                                 int format, int normalise, void *h_out, float *h_peak) {
+    if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
+    const char *who = "dusp_render_host_score_piece";
+    dusp_ctx *ctx = parts[0].prog->ctx;
+    const dusp_score_placement plain{DUSP_PLACE_ROWS, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+    const dusp_score_placement &by = placement ? *placement : plain;
+    ScorePlacement place(ScoreKind::rows);
+    switch (by.kind) {
+    case DUSP_PLACE_ROWS:
+        place = ScorePlacement(ScoreKind::rows, by.h_fracs, nullptr, nullptr);
+        break;
+    case DUSP_PLACE_PAN:
+    case DUSP_PLACE_STEREO:
+        if (!by.h_pans) CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": h_pans is NULL");
+        place = ScorePlacement(by.kind == DUSP_PLACE_PAN ? ScoreKind::pan : ScoreKind::stereo, by.h_fracs, by.h_pans, by.h_comp);
+        break;
+    case DUSP_PLACE_SPACE:
+        place = ScorePlacement(by.n_speakers, by.h_delays, by.h_tap_gains);
+        break;
+    default:
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the placement's kind must be DUSP_PLACE_ROWS (0), DUSP_PLACE_PAN (1), DUSP_PLACE_SPACE (2) or DUSP_PLACE_STEREO (3)");
+    }
+    return render_host_score_parts(who, parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, place, n_total_samples, tile_bytes, format, normalise, h_out, h_peak,
+                                   master);
 }
 
 }  // extern "C"

@@ -67,6 +67,7 @@ UNITS = {
     "Shape": (OP_SHAPE, ["duration", "min", "max"]),
     "AHD": (OP_AHD, ["attack", "hold", "decay"]),
     "HostSource": (OP_INPUT, []),
+    "MasterInput": (OP_INPUT, []),  # the timeline of a score or piece, where its master reads it (graph.MasterInput): stream 0, no samples
 }
 DATA_OUTLET = {"MidiToFrequency": "frequency"}  # every other unit's data outlet is "out" (MidiToFrequency.js:6)
 

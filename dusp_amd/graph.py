@@ -816,6 +816,18 @@ class HostSource(Unit):
         self.samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
 
 
+class MasterInput(Unit):
+    """Where the mix enters the master of a score or piece (`master=` of render_score / render_piece): a mono outlet that stands for
+    one channel of the timeline.  It is extracted as INPUT stream 0 like a HostSource, but carries no samples — the device reads the
+    timeline where it stands — and is never ticked on the host.  No counterpart class in the reference, where the master is
+    `fx(Sum.many(...))`."""
+    isMasterInput = True
+
+    def __init__(self):
+        super().__init__()
+        self.addOutlet("out", mono=True)
+
+
 class SampleRateRedux(Unit):
     """reference src/components/SampleRateRedux.js:3-16 — sample & hold every `ammount` samples"""
 

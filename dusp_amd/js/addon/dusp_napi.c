@@ -9,6 +9,7 @@
  *         (runs dusp_render_host on the libuv pool so the event loop stays live)
  *   stateDownload(prog, instance, unit) -> Float64Array
  *   renderPiece(progs[], ...) -> Promise: a piece of several instruments (dusp_render_host_score_parts; see fn_render_piece)
+ *   renderPieceMaster(progs[], ..., master, masterParams) -> Promise: the same through a master (dusp_render_host_score_piece)
  *   descriptorChannels(Float64Array words) -> the circuit's output channels (host code only: no context)
  *   programDestroy(prog), ctxDestroy(ctx), version(), abiVersion()
  * Failures surface the way the reference's do: synchronous calls THROW A STRING, render() REJECTS
@@ -757,6 +758,9 @@ typedef struct {
     size_t n_speakers;
     float peak;
     int stereo;       /* renderPieceStereo: parts of one or two channels, pans with NaN for "not placed", fracs or NULL */
+    prog_box *master_pb; /* renderPieceMaster: the program the mix goes through (dusp_render_host_score_piece), else NULL ... */
+    napi_ref master_ref;
+    float *master_params; /* ... and a host copy of its table [nParams][timeline channels], or NULL */
     int format, normalise, rc;
     char err[512];
 } piece_job;
@@ -766,6 +770,8 @@ static void piece_free(napi_env env, piece_job *j) {
         if (j->params) free(j->params[p]);
         if (j->refs && j->refs[p]) napi_delete_reference(env, j->refs[p]);
     }
+    if (j->master_ref) napi_delete_reference(env, j->master_ref);
+    free(j->master_params);
     free(j->params);
     free(j->refs);
     free(j->pbs);
@@ -795,8 +801,18 @@ static void piece_execute(napi_env env, void *data) {
         }
         j->parts[p].prog = j->pbs[p]->prog;
     }
+    if (j->master_pb && !j->master_pb->prog) {
+        j->rc = DUSP_ERR_STATE;
+        snprintf(j->err, sizeof j->err, "dusp-hip: renderPiece: a program has been destroyed");
+    }
     if (j->rc == DUSP_OK) {
-        if (j->stereo)
+        if (j->master_pb) { /* one entry for every placement */
+            dusp_score_placement place = {j->stereo ? DUSP_PLACE_STEREO : j->delays ? DUSP_PLACE_SPACE : j->pans ? DUSP_PLACE_PAN : DUSP_PLACE_ROWS,
+                                          j->fracs, j->pans, j->comp, j->n_speakers, j->delays, j->tap_gains};
+            dusp_score_master master = {j->master_pb->prog, j->master_params};
+            j->rc = dusp_render_host_score_piece(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, &master, j->n_total, j->tile_bytes,
+                                                 j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+        } else if (j->stereo)
             j->rc = dusp_render_host_score_parts_stereo(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->fracs, j->lengths, j->gains, j->pans, j->comp, j->n_total,
                                                         j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
         else if (j->delays)
@@ -849,6 +865,7 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
     }
     for (size_t p = 0; p < j->n_parts; p++)
         if (--j->pbs[p]->in_flight == 0 && j->pbs[p]->destroy_deferred) prog_destroy_now(j->pbs[p]);
+    if (j->master_pb && --j->master_pb->in_flight == 0 && j->master_pb->destroy_deferred) prog_destroy_now(j->master_pb);
     napi_delete_async_work(env, j->work);
     piece_free(env, j);
 }
@@ -866,23 +883,39 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *      tapGains[k * nSpeakers + c] and a delay of delays[k * nSpeakers + c] samples; the gains computed by the caller with Math.pow)
  * renderPieceStereo(the same twelve, fracs Float64Array | null, pans Float32Array, comp Float64Array)
  *   -> the first over parts of ONE OR TWO output channels, two channels out (dusp_render_host_score_parts_stereo: a mono voice panned to
- *      pans[k], or heard alike on both channels where pans[k] is NaN; a voice of two channels, whose pan is NaN, keeps its channels) */
-static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo */
-    napi_value argv[15];
+ *      pans[k], or heard alike on both channels where pans[k] is NaN; a voice of two channels, whose pan is NaN, keeps its channels)
+ * renderPieceMaster(the same twelve, kind, fracs | null, pans | null, comp | null, nSpeakers, delays | null, tapGains | null, master, masterParams | null)
+ *   -> any of the five — kind 0 plain rows, 1 panned, 2 in a space, 3 stereo, each with the arrays of its kind as above — with the mix
+ *      put through the program `master` before it is delivered (dusp_render_host_score_piece: a program with one input stream and one
+ *      output channel, channel c of the timeline instance c of it; masterParams its table, nParams * timeline channels values) */
+static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master */
+    napi_value argv[21];
     char msg[256];
-    if (!get_args(env, info, form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    if (!get_args(env, info, form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    const int with_master = form == 5;
+    int fracs_at = 12, space_at = 12, pans_at = form == 2 || form == 4 ? 13 : 12;
+    if (with_master) { /* the placement's kind says which of the four other forms this is */
+        double kind = -1;
+        if (napi_get_value_double(env, argv[12], &kind) != napi_ok || !(kind == 0 || kind == 1 || kind == 2 || kind == 3)) {
+            throw_string(env, "dusp-hip: renderPiece: kind must be 0 (rows), 1 (pan), 2 (space) or 3 (stereo)");
+            return NULL;
+        }
+        form = kind == 1 ? 1 : kind == 2 ? 3 : kind == 3 ? 4 : 2; /* (plain rows: the form with fractions, whose pans may be null) */
+        fracs_at = 13, pans_at = 14, space_at = 16;
+    }
     int panned = form == 1 || form == 4;
     int with_fracs = form == 2;
-    const int pans_at = form == 2 || form == 4 ? 13 : 12;
-    if (form == 4) {
+    if (form == 4 || (with_master && form == 1)) {
         napi_valuetype ft = napi_undefined;
-        napi_typeof(env, argv[12], &ft);
+        napi_typeof(env, argv[fracs_at], &ft);
         with_fracs = ft != napi_null && ft != napi_undefined;
     }
     if (form == 2) {
-        napi_valuetype pt = napi_undefined;
-        napi_typeof(env, argv[13], &pt);
+        napi_valuetype pt = napi_undefined, ft = napi_undefined;
+        napi_typeof(env, argv[pans_at], &pt);
         panned = pt != napi_null && pt != napi_undefined;
+        napi_typeof(env, argv[fracs_at], &ft);
+        if (with_master) with_fracs = ft != napi_null && ft != napi_undefined;
     }
     uint32_t n_parts = 0;
     bool is_array = false;
@@ -1005,7 +1038,7 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
     if (!bad && with_fracs) {
         void *fd;
         size_t n_f = 0;
-        if (!typed_array(env, argv[12], napi_float64_array, &fd, &n_f) || n_f != n_voices) bad = "fracs must be a Float64Array of one value per voice";
+        if (!typed_array(env, argv[fracs_at], napi_float64_array, &fd, &n_f) || n_f != n_voices) bad = "fracs must be a Float64Array of one value per voice";
         else if (!(j->fracs = (double *)malloc(n_f * sizeof(double)))) bad = "out of host memory for the fractions";
         else memcpy(j->fracs, fd, n_f * sizeof(double));
     }
@@ -1013,9 +1046,9 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         void *dd, *gd;
         size_t n_d = 0, n_g = 0;
         double speakers = 0;
-        if (napi_get_value_double(env, argv[12], &speakers) != napi_ok || !(speakers >= 1 && speakers <= 8 && speakers == (double)(size_t)speakers)) bad = "a Space has 1 .. 8 speakers";
-        else if (!typed_array(env, argv[13], napi_float64_array, &dd, &n_d) || n_d != n_voices * (size_t)speakers) bad = "delays must be a Float64Array of one value per voice and speaker";
-        else if (!typed_array(env, argv[14], napi_float64_array, &gd, &n_g) || n_g != n_d) bad = "tapGains must be a Float64Array of one value per voice and speaker";
+        if (napi_get_value_double(env, argv[space_at], &speakers) != napi_ok || !(speakers >= 1 && speakers <= 8 && speakers == (double)(size_t)speakers)) bad = "a Space has 1 .. 8 speakers";
+        else if (!typed_array(env, argv[space_at + 1], napi_float64_array, &dd, &n_d) || n_d != n_voices * (size_t)speakers) bad = "delays must be a Float64Array of one value per voice and speaker";
+        else if (!typed_array(env, argv[space_at + 2], napi_float64_array, &gd, &n_g) || n_g != n_d) bad = "tapGains must be a Float64Array of one value per voice and speaker";
         else if (!(j->delays = (double *)malloc(n_d * sizeof(double))) || !(j->tap_gains = (double *)malloc(n_g * sizeof(double)))) bad = "out of host memory for the taps";
         else {
             memcpy(j->delays, dd, n_d * sizeof(double));
@@ -1023,6 +1056,24 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
             j->n_speakers = (size_t)speakers;
             n_channels = (uint32_t)speakers; /* the timeline's */
         }
+    }
+    if (!bad && with_master) { /* the master: a program of the parts' context; its table has one column a channel of the timeline */
+        napi_valuetype mt = napi_undefined;
+        if (!(j->master_pb = as_prog(env, argv[19]))) { /* (as_prog has thrown) */
+            piece_free(env, j);
+            return NULL;
+        }
+        dusp_program_info mi;
+        dusp_program_info_get(j->master_pb->prog, &mi);
+        napi_typeof(env, argv[20], &mt);
+        if (j->master_pb->cb != j->pbs[0]->cb) bad = "the master is built on the context of the piece's parts";
+        else if (mt != napi_null && mt != napi_undefined) {
+            void *data;
+            size_t len;
+            if (!typed_array(env, argv[20], napi_float32_array, &data, &len) || len != (size_t)mi.n_params * n_channels) bad = "masterParams must be a Float32Array of nParams * timeline channels values";
+            else if (!(j->master_params = (float *)malloc(len * sizeof(float) + 1))) bad = "out of host memory for a parameter table";
+            else memcpy(j->master_params, data, len * sizeof(float));
+        } else if (mi.n_params) bad = "the master's program needs a parameter table";
     }
     j->n_floats = (size_t)n_channels * j->n_total;
     j->n_bytes = j->n_floats * (size_t)(!j->format || j->format == DUSP_PCM_F32 ? 4 : j->format == DUSP_PCM_S16 ? 2 : 3);
@@ -1040,15 +1091,19 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         napi_value prog_v;
         queued = napi_get_element(env, argv[0], p, &prog_v) == napi_ok && napi_create_reference(env, prog_v, 1, &j->refs[p]) == napi_ok;
     }
+    if (queued && j->master_pb) queued = napi_create_reference(env, argv[19], 1, &j->master_ref) == napi_ok;
     queued = queued && napi_create_async_work(env, NULL, name, piece_execute, piece_complete, j, &j->work) == napi_ok;
     if (queued) {
         for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight++;
+        if (j->master_pb) j->master_pb->in_flight++;
         if (napi_queue_async_work(env, j->work) != napi_ok) {
             for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight--;
+            if (j->master_pb) j->master_pb->in_flight--;
             queued = 0;
         }
     }
     if (!queued) {
+        j->master_pb = NULL;
         piece_free(env, j);
         throw_string(env, "dusp-hip: renderPiece: could not queue the render");
         return NULL;
@@ -1061,6 +1116,7 @@ static napi_value fn_render_piece_pan(napi_env env, napi_callback_info info) { r
 static napi_value fn_render_piece_frac(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 2); }
 static napi_value fn_render_piece_space(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 3); }
 static napi_value fn_render_piece_stereo(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 4); }
+static napi_value fn_render_piece_master(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 5); }
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1094,7 +1150,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"render", fn_render},            {"programContinue", fn_program_continue}, {"deviceCount", fn_device_count},
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
-        {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo},
+        {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo}, {"renderPieceMaster", fn_render_piece_master},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

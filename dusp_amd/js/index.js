@@ -24,6 +24,7 @@ module.exports = {
   renderPieceWav: renderChannelData.renderPieceWav,
   splitOnsets: renderChannelData.splitOnsets,
   spaceTaps: renderChannelData.spaceTaps,
+  masterProgram: renderChannelData.masterProgram,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

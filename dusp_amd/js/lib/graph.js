@@ -880,6 +880,15 @@ class HostSignal extends Unit {
   }
 }
 
+/* Where the mix enters the master of a score or piece (the `master` option of renderScore / renderPiece): a mono outlet that stands for
+ * one channel of the timeline.  It is extracted as INPUT stream 0 like every HostSignal, but it is never ticked: it carries no samples,
+ * the device reads the timeline where it stands (twin of graph.py MasterInput; no counterpart class in the reference). */
+class MasterInput extends HostSignal {
+  get isMasterInput() { return true }
+  hostChunk() { throw MasterInput.ALONE }
+}
+MasterInput.ALONE = 'dusp-hip: a MasterInput carries no samples: it stands for the timeline inside the master of a score or piece'
+
 /* Noise.js:3-27 — a sample-and-hold of Math.random() at rate f (default: a fresh number every sample).  The numbers can
  * only be drawn by the JavaScript engine, in tick order, so the unit is a HostSignal; with a seeded Math.random a render
  * is reproducible, here as in the reference. */
@@ -903,7 +912,7 @@ class Noise extends HostSignal {
   }
 }
 
-module.exports = { Retriggerer, SporadicRetriggerer, HostSignal, Noise, Shape, AHD, Pan, MidiToFrequency, Rescale, CrossFader, VectorMagnitude, Timer, SampleRateRedux, ConcatChannels, PickChannel,
+module.exports = { Retriggerer, SporadicRetriggerer, HostSignal, MasterInput, Noise, Shape, AHD, Pan, MidiToFrequency, Rescale, CrossFader, VectorMagnitude, Timer, SampleRateRedux, ConcatChannels, PickChannel,
   FixedDelay, CombFilter, AllPass, MonoDelay, ReadBackDelay, MultiChannelOsc, Event, Subtract, Divide, Pow, PolarityInvert, Abs, DecibelToScaler, SemitoneToRatio, SecondsToSamples,
   FixedMultiply, Clip, HardClipAbove, HardClipBelow, Gain,
   Unit, Inlet, Outlet, Circuit, Osc, Ramp, Multiply, Sum, Filter, Delay,

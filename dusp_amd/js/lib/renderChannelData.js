@@ -15,6 +15,7 @@ const config = require('./config')
 const { extract, unify, deviceRetrigger } = require('./extract')
 const { makeTables } = require('./wavetables')
 const { OP, UNITS } = require('./ops')
+const { MasterInput } = require('./graph')
 const { encodeWav, encodeFrames } = require('./wav')
 
 const contexts = new Map() // "sampleRate|device|slot" -> native context with that rate's wave tables
@@ -452,9 +453,10 @@ function wholeSamples(who, name, values, count) {
  * places (with speakers, decibelsPerMetre, sampleDelayPerMetre): as renderPiece's — mono voices, one channel a speaker — through the
  * piece's call too.
  * stereo: true — as renderPiece's: voices of one or two channels, two channels out, pans optional and null / NaN for a voice that is not
- * placed — through the piece's call too. */
+ * placed — through the piece's call too.
+ * master: as renderPiece's — the mix through a mono circuit, channel by channel, on the device — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
-const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true
+const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -668,6 +670,44 @@ function spaceTaps(places, { speakers, decibelsPerMetre = -3, sampleDelayPerMetr
   return { nSpeakers, delays, gains }
 }
 
+/* The refusals of a master, in the words of mix.py (MASTER_*) */
+const MASTER = {
+  inputAlone: MasterInput.ALONE,
+  notCallable: 'dusp-hip: master is a function fx(x) of the mix, or a list of one function a channel of the timeline',
+  count: (have, channels) => 'dusp-hip: master lists ' + have + ' circuits, the timeline has ' + channels + ' channels: one a channel',
+  oneInput: (c, have) => 'dusp-hip: the master of channel ' + c + ' holds ' + have + ' MasterInput units: a master reads the mix through exactly one, the one it is given',
+  hostSource: (c) => 'dusp-hip: the master of channel ' + c + " holds a HostSource: the timeline is a master's only input",
+  events: (c) => 'dusp-hip: the master of channel ' + c + ' has scheduled events: a master is rendered in one piece',
+  channels: (c, have) => 'dusp-hip: the master of channel ' + c + ' has ' + have + ' output channels: a master is a mono circuit, applied to every channel by itself',
+  notIsomorphic: (c) => 'dusp-hip: the masters of channels 0 and ' + c + ' are not isomorphic circuits: they are one program and may differ in constants only',
+  rate: (have, want) => "dusp-hip: the master's sample rate is " + have + ", the voices' is " + want,
+}
+
+/* The master of a score or piece -> unify's result over `channels` instances, one a channel of the timeline (twin of render.py
+ * master_program).  master: a function fx(x), called once per channel with a fresh MasterInput and returning the master's outlet, or an
+ * array of one function a channel.  The circuits are isomorphic; what differs between them is constants, which become the program's
+ * parameter table [nParams][channels].  Refused by string: what is no function, an array of the wrong length, a circuit that holds no
+ * or several MasterInput, another host-computed signal or a scheduled event, one with more than one output channel, circuits that are
+ * not isomorphic. */
+function masterProgram(master, channels, sampleRate) {
+  const fxs = Array.isArray(master) ? master : new Array(channels).fill(master)
+  if (!fxs.length || !fxs.every((fx) => typeof fx === 'function')) throw MASTER.notCallable
+  if (fxs.length !== channels) throw MASTER.count(fxs.length, channels)
+  const extractions = []
+  fxs.forEach((fx, c) => {
+    const ex = extract(fx(new MasterInput()), { allowEvents: true })
+    if (ex.circuit.events && ex.circuit.events.length) throw MASTER.events(c)
+    if (ex.sources.some((u) => !u.isMasterInput)) throw MASTER.hostSource(c)
+    if (ex.sources.length !== 1) throw MASTER.oneInput(c, ex.sources.length)
+    if (ex.sampleRate !== sampleRate) throw MASTER.rate(ex.sampleRate, sampleRate)
+    const nOut = native().descriptorChannels(ex.words)
+    if (nOut !== 1) throw MASTER.channels(c, nOut)
+    if (c && structureKey(ex) !== structureKey(extractions[0])) throw MASTER.notIsomorphic(c)
+    extractions.push(ex)
+  })
+  return unify(extractions)
+}
+
 async function pieceCall(who, outlets, opts, format, normalise, onePart = false) {
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
   const stereo = opts.stereo === true
@@ -709,19 +749,25 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   const n = native()
   const channels = grouped.parts.map((part) => n.descriptorChannels(part.uni.words))
   const nChannels = stereo ? checkStereoKinds(Array.from(grouped.partOf, (p) => channels[p]), panned.pans) : taps ? checkSpaceChannels(channels, taps.nSpeakers) : panned ? checkPanChannels(channels) : checkPieceChannels(channels)
+  const master = given(opts.master) ? masterProgram(opts.master, nChannels, sampleRate) : null // (behind every other check of the call)
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
   const progs = []
+  let masterProg = null
   try {
     for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
+    if (master) masterProg = n.programBuild(contextFor(sampleRate), master.words, engine)
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
-    const result = stereo ? await n.renderPieceStereo(...args, fracs, panned.pans, panned.comp)
+    const result = master ? await n.renderPieceMaster(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+      taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master.nParams ? master.params : null)
+      : stereo ? await n.renderPieceStereo(...args, fracs, panned.pans, panned.comp)
       : taps ? await n.renderPieceSpace(...args, taps.nSpeakers, taps.delays, taps.gains)
       : fracs ? await n.renderPieceFrac(...args, fracs, panned ? panned.pans : null, panned ? panned.comp : null)
       : panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
     return { nSamples, nChannels, sampleRate, result }
   } finally {
     for (const prog of progs) n.programDestroy(prog)
+    if (masterProg) n.programDestroy(masterProg)
   }
 }
 
@@ -748,7 +794,13 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * mono voice with a pan is the panned voice above, a mono voice without one is heard alike on both channels (the reference's Sum reads
  * a mono input for every channel of a wider one), a voice of two channels keeps its channels and takes no pan (the Pan unit's inlet is
  * mono).  What the reference renders for Sum.many over such voices behind their Delays, bit for bit.  fracs work as above; places are
- * refused.  Without the option every call is what it was. */
+ * refused.  Without the option every call is what it was.
+ * master: the mix through a circuit before it is delivered — an EQ, an echo, a comb or all-pass, a clip on the sum — on the device,
+ * whatever the placement (dusp_render_host_score_piece).  A function fx(x), given a fresh MasterInput once per channel of the timeline
+ * and returning a MONO circuit over it, or an array of one function a channel; the circuits are isomorphic and may differ in constants
+ * (masterProgram).  Channel c of the result is the render of the master over the timeline's channel c as the chain left it — before
+ * `|| 0`, as a unit behind Sum.many hears it — from the master's initial state (DESIGN.md 6.14 says where that is the reference's
+ * fx(Sum.many(...)) bit for bit and where it is not).  The call's engine is the master's too. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   const channelData = []
@@ -816,6 +868,8 @@ module.exports.splitOnsets = splitOnsets
 module.exports.spaceTaps = spaceTaps
 module.exports.checkPlaces = checkPlaces
 module.exports.checkSpaceChannels = checkSpaceChannels
+module.exports.masterProgram = masterProgram
+module.exports.MASTER = MASTER
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

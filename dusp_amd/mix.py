@@ -628,3 +628,35 @@ class Placement:
     def chain(self):
         """the contract the placed voices are held to, which takes the arrays held here beside the rows and onsets"""
         return {"rows": score_chain_rows, "pan": score_chain_rows_panned, "space": score_chain_rows_placed, "stereo": score_chain_rows_stereo}[self.kind]
+
+
+# ---- the master of a score or piece: one mono circuit over every channel of the timeline (DESIGN.md 6.14) ----
+
+MASTER_INPUT_ALONE = "dusp-hip: a MasterInput carries no samples: it stands for the timeline inside the master of a score or piece"
+MASTER_NOT_CALLABLE = "dusp-hip: master is a function fx(x) of the mix, or a list of one function a channel of the timeline"
+MASTER_COUNT = "dusp-hip: master lists %d circuits, the timeline has %d channels: one a channel"
+MASTER_ONE_INPUT = "dusp-hip: the master of channel %d holds %d MasterInput units: a master reads the mix through exactly one, the one it is given"
+MASTER_HOST_SOURCE = "dusp-hip: the master of channel %d holds a HostSource: the timeline is a master's only input"
+MASTER_EVENTS = "dusp-hip: the master of channel %d has scheduled events: a master is rendered in one piece"
+MASTER_CHANNELS = "dusp-hip: the master of channel %d has %d output channels: a master is a mono circuit, applied to every channel by itself"
+MASTER_NOT_ISOMORPHIC = "dusp-hip: the masters of channels 0 and %d are not isomorphic circuits: they are one program and may differ in constants only"
+MASTER_RATE = "dusp-hip: the master's sample rate is %d, the voices' is %d"
+
+
+def master_chain(raw, render_channel):
+    """The master stage of a score or piece, over its raw timeline: the contract of dusp_render_host_score_piece with a master, needs no
+    GPU.  raw float32 [channels, n_total]: the chain's running sums as they stand behind the last voice (score_chain* with raw=True:
+    NaN, Inf and -0 kept — in the reference a unit behind a Sum hears the Sum's own values, `|| 0` is renderChannelData's copy-out's).
+    render_channel(c, samples) -> float32 [n_total]: the render of the master's instance c over n_total samples from its initial
+    state with `samples`, float32 [n_total], as its one input stream, `|| 0` applied at ITS copy-out as every render does (the tests
+    pass the CPU oracle).  -> float32 [channels, n_total]: channel c is render_channel(c, raw[c]); no channel hears another."""
+    raw = np.asarray(raw)
+    if raw.dtype != np.float32 or raw.ndim != 2:
+        raise ValueError("dusp-hip: the raw timeline is float32 of shape (channels, n_total)")
+    out = np.empty_like(raw)
+    for c in range(raw.shape[0]):
+        y = np.asarray(render_channel(c, np.ascontiguousarray(raw[c])), dtype=np.float32)
+        if y.shape != (raw.shape[1],):
+            raise ValueError("dusp-hip: the master's render of channel %d must have shape (n_total=%d,)" % (c, raw.shape[1]))
+        out[c] = y
+    return out

@@ -75,6 +75,13 @@ def write_back(prog, circuit, chunk_size, n_samples, instance=0):
     circuit.clock += ((n_samples + chunk_size - 1) // chunk_size) * chunk_size
 
 
+def _no_master_input(extraction):
+    """a circuit rendered by itself holds no MasterInput: that unit stands for the timeline of a score or piece (refused before a device is asked for)"""
+    if any(getattr(src, "isMasterInput", False) for src in extraction.sources):
+        raise descriptor.DuspError(mix.MASTER_INPUT_ALONE)
+    return extraction
+
+
 def _host_inputs(sources, clock, length):
     """This segment's samples of the circuit's HostSource units -> float32 [n_sources, 1, length] (zeros past a source's end)."""
     if not sources:
@@ -93,7 +100,7 @@ def renderChannelData(outlet, duration=1, TypedArray=np.float32, engine=runtime.
     ONE device program is continued from segment to segment (dusp_program_continue), so delay lines, CircleBuffers
     and feedback chunks stay resident on the device.  Afterwards the circuit is consumed like the reference's:
     circuit.clock has advanced and the unit objects hold their post-render state."""
-    return _render_extracted(outlet, descriptor.extract(outlet, allow_events=True), duration, TypedArray, engine, device)
+    return _render_extracted(outlet, _no_master_input(descriptor.extract(outlet, allow_events=True)), duration, TypedArray, engine, device)
 
 
 def _render_extracted(outlet, first, duration, TypedArray, engine, device):
@@ -244,7 +251,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -262,14 +269,17 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     piece's call with the score as its one part, as with pans.
 
     stereo=True: as render_piece's — voices of one or two channels, two channels out, pans optional and None / NaN for a voice that is
-    not placed; the piece's call with the score as its one part, as with pans."""
+    not placed; the piece's call with the score as its one part, as with pans.
+
+    master: as render_piece's — the mix through a mono circuit, channel by channel, on the device; the piece's call with the score as
+    its one part, as with pans."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master))
 
 
 def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space")):
+    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master")):
         return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
@@ -282,17 +292,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo), (bit_depth, normalise))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre, stereo), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo, master), bit_depth)
 
 
 class PieceParts:
@@ -336,16 +346,52 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo):
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None):
     """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
-    known.  The Space keywords are one thing too, None without places (the other three alone say nothing)"""
-    return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo)
+    known.  The Space keywords are one thing too, None without places (the other three alone say nothing).  master: what the mix goes
+    through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it"""
+    return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master)
+
+
+def master_program(master, channels, sample_rate):
+    """The master of a score or piece -> descriptor.Unified of `channels` instances, one a channel of the timeline; needs no device.
+    master: a callable fx(x), called once per channel with a fresh graph.MasterInput and returning the master's outlet, or a list of one
+    callable a channel (an echo of another length left and right).  The circuits are extracted and unified: they are isomorphic, what
+    differs between them is constants, which become the program's parameter table [n_params][channels].  Refused by string: a master
+    that is not callable, a list of the wrong length, a circuit that holds no or several MasterInput, a HostSource or a scheduled
+    event, one with more than one output channel, circuits that are not isomorphic."""
+    from . import graph
+    fxs = list(master) if isinstance(master, (list, tuple)) else [master] * channels
+    if not fxs or not all(callable(fx) for fx in fxs):
+        raise descriptor.DuspError(mix.MASTER_NOT_CALLABLE)
+    if len(fxs) != channels:
+        raise descriptor.DuspError(mix.MASTER_COUNT % (len(fxs), channels))
+    extractions = []
+    for c, fx in enumerate(fxs):
+        ex = descriptor.extract(fx(graph.MasterInput()), allow_events=True)
+        if ex.circuit.events:
+            raise descriptor.DuspError(mix.MASTER_EVENTS % c)
+        if any(not getattr(src, "isMasterInput", False) for src in ex.sources):
+            raise descriptor.DuspError(mix.MASTER_HOST_SOURCE % c)
+        if len(ex.sources) != 1:
+            raise descriptor.DuspError(mix.MASTER_ONE_INPUT % (c, len(ex.sources)))
+        if ex.sample_rate != sample_rate:
+            raise descriptor.DuspError(mix.MASTER_RATE % (ex.sample_rate, sample_rate))
+        n_out = runtime.descriptor_channels(ex.words)
+        if n_out != 1:
+            raise descriptor.DuspError(mix.MASTER_CHANNELS % (c, n_out))
+        if c and structure_key(ex) != structure_key(extractions[0]):
+            raise descriptor.DuspError(mix.MASTER_NOT_ISOMORPHIC % c)
+        extractions.append(ex)
+    return descriptor.unify(extractions)
 
 
 def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, one_part=False):
-    """-> PieceParts, samples of timeline, onsets, lengths, gains, the timeline's channels, the voices' mix.Placement (all checked:
-    nothing is built yet).  placing: the call's placement keywords (_placing); a space becomes the taps of mix.space_taps at the
+    """-> PieceParts, samples of timeline, onsets, lengths, gains, the timeline's channels, the voices' mix.Placement — with the call's
+    master as place.master, a descriptor.Unified of one instance a channel, or None (all checked: nothing is built yet).  placing: the call's placement keywords (_placing); a space becomes the taps of mix.space_taps at the
     voices' sample rate, and parts whose channels do not fit the placement are refused (Placement.timeline_channels)."""
+    placing = dict(placing)
+    master = placing.pop("master", None)
     mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
@@ -366,8 +412,9 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     grouped = piece_parts(extractions, voice_samples)
     if one_part and len(grouped.parts) != 1:  # (render_score with pans or fracs)
         raise descriptor.DuspError("dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments")
-    channels = [runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts]
-    return grouped, n_total, onsets, lengths, gains, place.timeline_channels(channels, grouped.part_of), place
+    channels = place.timeline_channels([runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts], grouped.part_of)
+    place.master = None if master is None else master_program(master, channels, rate)  # (behind every other check of the call)
+    return grouped, n_total, onsets, lengths, gains, channels, place
 
 
 def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format=None, normalise=0):
@@ -377,14 +424,18 @@ def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, devic
         for uni, _ in grouped.parts:
             programs.append(ctx.build(uni.words, engine))
         parts = [(prog, n_voice, uni.n_instances, uni.params) for prog, (uni, n_voice) in zip(programs, grouped.parts)]
-        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, **place.keywords())
+        master = getattr(place, "master", None)
+        if master is not None:
+            programs.append(ctx.build(master.words, engine))
+            master = (programs[-1], master.params)
+        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, master=master, **place.keywords())
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -414,9 +465,16 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     a mono voice with a pan is the panned voice above, a mono voice without one is heard alike on both channels (the reference's Sum
     reads a mono input for every channel of a wider one), a voice of two channels keeps its channels and takes no pan (the Pan unit's
     inlet is mono).  What the reference renders for Sum.many over such voices behind their Delays, bit for bit
-    (mix.score_chain_rows_stereo).  fracs work as above; places are refused."""
+    (mix.score_chain_rows_stereo).  fracs work as above; places are refused.
+
+    master: the mix through a circuit before it is delivered — an EQ, an echo, a comb or all-pass, a clip on the sum — on the device,
+    whatever the placement.  A callable fx(x), given a fresh MasterInput once per channel of the timeline and returning a MONO circuit
+    over it, or a list of one callable a channel; the circuits are isomorphic and may differ in constants (master_program).  Channel c
+    of the result is the render of the master over the timeline's channel c as the chain left it — before `|| 0`, as a unit behind
+    Sum.many hears it — from the master's initial state (mix.master_chain; DESIGN.md 6.14 says where that is the reference's
+    `fx(Sum.many(...))` bit for bit and where it is not).  The call's engine is the master's too."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo), _one_part)
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master), _one_part)
 
 
 def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
@@ -429,17 +487,17 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo), _one_part, (bit_depth, normalise))
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master), bit_depth)
 
 
 class PcmData:
@@ -463,7 +521,7 @@ def render_pcm(outlet, duration=1, bit_depth=16, normalise=0, engine=runtime.ENG
     (renderChannelData); those are encoded here by the same contract (wav.encode_frames), the peak taken over the whole render.  The
     bytes are the same either way.  Like renderChannelData this consumes the circuit."""
     _check_pcm(bit_depth, normalise)
-    first = descriptor.extract(outlet, allow_events=True)
+    first = _no_master_input(descriptor.extract(outlet, allow_events=True))
     n = _n_samples(duration, first.sample_rate)
     if n > 0 and not first.circuit.events:
         prog = context(first.sample_rate, device).build(first.words, engine)

@@ -33,6 +33,7 @@ EXPORTS = [
     "dusp_score_rows_frac_device", "dusp_render_host_score_parts_frac",
     "dusp_score_rows_space_device", "dusp_render_host_score_parts_space",
     "dusp_score_rows_stereo_device", "dusp_render_host_score_parts_stereo",
+    "dusp_render_host_score_piece",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -112,6 +113,7 @@ def load():
     L.dusp_render_host_score_parts_space.argtypes = [vp, sz, sz, vp, vp, vp, vp, sz, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_score_rows_stereo_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
     L.dusp_render_host_score_parts_stereo.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    L.dusp_render_host_score_piece.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -130,6 +132,21 @@ def load():
 class ScorePart(ctypes.Structure):
     """dusp_score_part: one instrument of a piece (dusp_render_host_score_parts)"""
     _fields_ = [("prog", ctypes.c_void_p), ("n_instances", ctypes.c_size_t), ("n_voice_samples", ctypes.c_size_t), ("h_params", ctypes.c_void_p)]
+
+
+PLACE_ROWS, PLACE_PAN, PLACE_SPACE, PLACE_STEREO = 0, 1, 2, 3  # dusp_score_place_kind
+PLACE_KINDS = {"rows": PLACE_ROWS, "pan": PLACE_PAN, "space": PLACE_SPACE, "stereo": PLACE_STEREO}
+
+
+class ScorePlacement(ctypes.Structure):
+    """dusp_score_placement: how the voices of a piece are placed, as one record (dusp_render_host_score_piece)"""
+    _fields_ = [("kind", ctypes.c_int), ("h_fracs", ctypes.c_void_p), ("h_pans", ctypes.c_void_p), ("h_comp", ctypes.c_void_p), ("n_speakers", ctypes.c_size_t),
+                ("h_delays", ctypes.c_void_p), ("h_tap_gains", ctypes.c_void_p)]
+
+
+class ScoreMaster(ctypes.Structure):
+    """dusp_score_master: the mono circuit a piece's mix goes through, and its parameter table [n_params][timeline channels]"""
+    _fields_ = [("prog", ctypes.c_void_p), ("h_params", ctypes.c_void_p)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -396,7 +413,7 @@ class Context:
             self._h, rows, samples, _ptr(channels, n), n, onsets, _ptr(fracs, n), lengths, d_gains, _ptr(pans, n), _ptr(comp, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None, taps=None, stereo=False):
+                           pans=None, fracs=None, taps=None, stereo=False, master=None):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -411,7 +428,11 @@ class Context:
         Not together with pans or fracs.
         stereo=True: the parts have ONE OR TWO output channels and the result has two (dusp_render_host_score_parts_stereo;
         mix.score_chain_rows_stereo): pans may be None (nothing placed) or hold None / NaN for a voice that is not placed, and a voice
-        of a two-channel part is not placed; fracs as above.  Not together with taps."""
+        of a two-channel part is not placed; fracs as above.  Not together with taps.
+        master = (program, params): the mix goes through that program before it is delivered (dusp_render_host_score_piece, the one
+        entry that takes every placement above as a record; mix.master_chain is the contract) — a program of this context with ONE
+        input stream and ONE output channel, channel c of the timeline instance c of it, params its table [n_params][timeline
+        channels] (None without parameters).  The library refuses what is no master, before anything renders."""
         Placement.refuse_together(pans, fracs, taps, stereo)
         if not parts:
             raise ValueError("dusp-hip: a piece has at least one part")
@@ -436,6 +457,16 @@ class Context:
             check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], place.pans)
         n_ch = place.channels(parts[0][0].n_out_channels)  # (parts that do not fit the placement: the library refuses them)
         voices = (table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data)
+        if master is not None:
+            prog, params = master
+            params = prog._params_table(params, n_ch, "dusp-hip: the params of the master must have shape")  # (n_instances: the timeline's channels)
+            how = ScorePlacement(PLACE_KINDS[place.kind], _ptr(place.fracs), _ptr(place.pans), _ptr(place.comp), n_ch if place.kind == "space" else 0,
+                                 _ptr(place.taps[0]) if place.taps else None, _ptr(place.taps[1]) if place.taps else None)
+            through = ScoreMaster(prog._h, _ptr(params))
+            fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
+            self._check(self._L.dusp_render_host_score_piece(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(through),
+                                                             n_total_samples, int(tile_bytes), fmt, normalise, out.ctypes.data, _ptr(peak)))
+            return out if peak is None else (out, peak[0])
         scaled, placed, timeline = (_ptr(lengths), _ptr(gains)), (_ptr(place.pans), _ptr(place.comp)), (n_total_samples, int(tile_bytes))
         if place.kind == "space":
             entry, args = self._L.dusp_render_host_score_parts_space, voices + scaled + (n_ch, place.taps[0].ctypes.data, place.taps[1].ctypes.data) + timeline

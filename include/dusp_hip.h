@@ -559,6 +559,50 @@ int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_p
                                         const float *h_pans, const double *h_comp, size_t n_total_samples, size_t tile_bytes, int format,
                                         int normalise, void *h_out, float *h_peak);
 
+/* Master bus: the mix of a piece through a circuit, on the device (additions to ABI v7, detected by symbol).
+ * dusp_render_host_score_piece is ONE entry for every placement — the five dusp_render_host_score_parts* calls above are this call
+ * with the matching dusp_score_placement and no master, bit for bit and refusal for refusal (under this entry's name) — and the only one
+ * that takes a master.
+ *
+ * A MASTER is a program with exactly one input stream (opcode INPUT, stream 0) and one output channel, built on the parts' context.
+ * It is applied to every channel of the timeline by itself: channel c is instance c of the master, so its slot-major parameter table
+ * is h_params [n_params][timeline channels] (an echo of 300.25 samples left and 411.5 right is one program with one parameter).
+ * After the last tile the timeline's RAW running sums — no `|| 0`: in the reference a unit behind a Sum hears the Sum's own values,
+ * and `|| 0` is applied at renderChannelData's copy-out only — are the master's input block as they stand ([1 stream][C instances]
+ * [n_total_samples]: no copy, no transpose), the master is rendered over n_total_samples from its initial state, its own copy-out
+ * applies `|| 0`, and the delivery (planar f32, or peak and encoded frames) is taken from the master's buffer:
+ *     h_out = render(master, n_instances = C, n_samples = n_total_samples, input 0 of instance c = raw timeline channel c)
+ * The master render decides as a tile of dusp_render_host_mix decides: it waits for its compiled kernel (two calls give the same
+ * bits), and what changes bits is decided from its whole parameter table.  A stateless master is cut into time segments as any
+ * render is; segments that warm up stay refused for programs with inputs, so a Filter master runs as one chain per channel.
+ * Device memory: one more f32 [C][n_total_samples] (the master's output) beside the timeline.
+ * The documented divergences of the chain (a NaN voice sample, Inf, the sign of a zero) reach the master unchanged.
+ *   placement   NULL: plain rows.  Else its kind and the arrays of that kind, per voice in chain order, as the matching
+ *               dusp_render_host_score_parts* call takes them (h_fracs with ROWS, PAN and STEREO; NULL: none)
+ *   master      NULL: no master, the call is the matching dusp_render_host_score_parts* call.
+ * Refused with a message before anything renders, beside what those calls refuse: a master with no input stream or more than one;
+ * with more than one output channel; a resumable master; a master built on another context; a master that is also one of the parts;
+ * NULL h_params where the master has parameters; C x n_total_samples beyond 2^31.  Afterwards the master's state is a mix's
+ * (dusp_state_download refuses), like every part's. */
+typedef enum { DUSP_PLACE_ROWS = 0, DUSP_PLACE_PAN = 1, DUSP_PLACE_SPACE = 2, DUSP_PLACE_STEREO = 3 } dusp_score_place_kind;
+typedef struct dusp_score_placement {
+    int kind;                    /* dusp_score_place_kind */
+    const double *h_fracs;       /* ROWS, PAN, STEREO: f64 [n_voices] in [0, 1), or NULL */
+    const float *h_pans;         /* PAN: finite f32 [n_voices].  STEREO: NaN for a voice that is not placed */
+    const double *h_comp;        /* PAN, STEREO: f64 [n_voices], or NULL for the host's pow */
+    size_t n_speakers;           /* SPACE: 1 .. 8 */
+    const double *h_delays;      /* SPACE: f64 [n_voices][n_speakers] */
+    const double *h_tap_gains;   /* SPACE: f64 [n_voices][n_speakers] */
+} dusp_score_placement;
+typedef struct dusp_score_master {
+    dusp_program *prog;
+    const float *h_params; /* f32 [n_params][timeline channels] or NULL */
+} dusp_score_master;
+int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                 const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                 const dusp_score_placement *placement, const dusp_score_master *master, size_t n_total_samples,
+                                 size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

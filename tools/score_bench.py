@@ -27,6 +27,10 @@
           notes alone (render_device into a preallocated buffer) and against the same piece with the onsets shuffled — every tile's
           union window is then the whole timeline, which is what the window is worth.  One run under DUSP_JIT_LOG=2 prints the plans'
           host time and block (stderr).
+  master  (--master; profiles/score_master.txt) the piece above — 8192 notes of 0.5 s over 60 s in onset order — through
+          Context.render_score_parts without a master and with a Clip master, an echo master and a Filter master
+          (dusp_render_host_score_piece): the call on the host's clock, and the master's render alone
+          (dusp_last_kernel_ms on the master program).  A report: no ratio is fixed in advance.
 
 Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
 """
@@ -311,6 +315,45 @@ def piece(scale, ctxs, reps):
     logged.close()
 
 
+def master(scale, ctxs, reps):
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
+    d.configure(SR)
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    ctx = ctxs["default"]
+    prog = ctx.build(uni.words)
+
+    def clip(x):
+        c = d.Clip(0.8)
+        c.IN = d.Multiply(x, 1.7)
+        return c
+
+    def echo(x):
+        s = d.Sum(x, 0)
+        s.B = d.Multiply(d.Delay(s, 300.25, 2048), 0.5)
+        return s
+
+    print("master: %d notes of %d samples over %d samples, one channel (%.1f MB of timeline, as much again for the master's output), engine %s" % (V, nv, nt, nt * 4 / 1e6, prog.engine),
+          flush=True)
+    for label, fx in [("no master", None), ("Clip(0.8) behind Multiply(x, 1.7)", clip), ("feedback echo, 300.25 samples", echo), ("Filter(x, 1200)", lambda x: d.Filter(x, 1200))]:
+        through = ctx.build(descriptor.extract(fx(d.MasterInput())).words) if fx else None
+        times, kernel = [], []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, master=(through, None) if through else None)
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+            if through:
+                kernel.append(through.last_kernel_ms())
+        shape = "   master render alone median %9.3f ms  fastest %9.3f   [%s]" % (float(np.median(kernel[1:])), min(kernel[1:]), through.read_shape()) if through else ""
+        print("  render_score_parts, host clock, %-36s median %9.2f ms  fastest %9.2f%s" % (label, float(np.median(times[1:])), min(times[1:]), shape), flush=True)
+        if through:
+            through.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -320,9 +363,12 @@ def main():
     ap.add_argument("--frac", action="store_true", help="the sub-sample-onset leg alone, over the dense cases named by --cases")
     ap.add_argument("--space", action="store_true", help="the Space-placement leg alone, over the dense cases named by --cases")
     ap.add_argument("--stereo", action="store_true", help="the stereo-piece leg alone, over the dense cases named by --cases")
+    ap.add_argument("--master", action="store_true", help="the master-bus leg alone: the piece with and without a master")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
+    if a.master:
+        return master(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
