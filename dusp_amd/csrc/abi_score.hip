@@ -2,7 +2,8 @@
 // engines): the plans' image on the device, the placement of a rows call, the one launch path, the device entries (dusp_score_device;
 // dusp_score_rows_device and its pan, frac, space and stereo forms) and the host round trips (dusp_render_host_score;
 // dusp_render_host_score_parts and its pan, frac, space and stereo forms; dusp_render_host_score_piece, which is all of them and takes
-// the master of a piece).
+// the master of a piece; dusp_render_host_score_piece_buses, which adds effect sends: per-voice levels into bus circuits, DESIGN.md 6.15,
+// with the device entries dusp_score_rows_send_device and dusp_score_return_device).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -30,6 +31,9 @@ struct ScorePlacement {
     size_t n_speakers = 0;             // space: the taps, f64 [voice][speaker] each
     const double *h_delays = nullptr, *h_tap_gains = nullptr;
     const uint32_t *h_row_channels = nullptr;  // stereo: voice k is a row of h_row_channels[k] channels, one or two
+    // rows, pan, with buses (score_send_engine.hip): what voice k gives to bus b is h_sends[b * sends_stride + k], finite
+    size_t n_buses = 0, sends_stride = 0;
+    const float *h_sends = nullptr;
     explicit ScorePlacement(ScoreKind kind_) : kind(kind_) {}
     ScorePlacement(ScoreKind kind_, const double *fracs, const float *pans, const double *comp) : kind(kind_), h_fracs(fracs), h_pans(pans), h_comp(comp) {}
     ScorePlacement(size_t speakers, const double *delays, const double *tap_gains) : kind(ScoreKind::space), n_speakers(speakers), h_delays(delays), h_tap_gains(tap_gains) {}
@@ -43,7 +47,22 @@ struct ScorePlacement {
         if (h_delays) t.h_delays += lo * n_speakers;
         if (h_tap_gains) t.h_tap_gains += lo * n_speakers;
         if (h_row_channels) t.h_row_channels += lo;
+        if (h_sends) t.h_sends += lo;
         return t;
+    }
+
+    // buses: how many, the levels, and what sends do not go with (fractions, a space, a stereo piece: later changes); n voices
+    int check_sends(dusp_ctx *ctx, const char *who, size_t n) const {
+        const std::string w(who);
+        if (n_buses < 1 || n_buses > dusp::kScoreBusMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 1 .. 4 buses, not " + std::to_string(n_buses));
+        if (!h_sends) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buses' h_sends is NULL: every bus needs a send level a voice");
+        if (h_fracs || kind == ScoreKind::space || kind == ScoreKind::stereo)
+            CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, w + ": sends go with plain rows and with pans at whole-sample onsets: together with fracs, places or stereo they are refused");
+        for (size_t b = 0; b < n_buses; b++)
+            for (size_t k = 0; k < n; k++)
+                if (!std::isfinite(h_sends[b * sends_stride + k]))
+                    CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the send level of voice " + std::to_string(k) + " into bus " + std::to_string(b) + " is not finite");
+        return DUSP_OK;
     }
 
     // The checks of n voices, before anything renders; each holds where the kind has nothing of its sort.  The two entry families run
@@ -110,6 +129,7 @@ struct ScoreLaunch {
     bool frac = false;   // some listed voice starts between samples: the launch is score_frac_engine.hip's, plain rows or panned ...
     size_t frac_at = 0;  // ... and this the byte offset of its voices' weights (dusp::ScoreFrac), behind the plan
     size_t space_at = 0;  // a space launch: byte offset of its voices' taps (dusp::ScoreSpaceTap, [voice][speaker]), behind the plan
+    size_t n_buses = 0, send_at = 0;  // a launch with sends (score_send_engine.hip): how many buses, and the byte offset of its voices' levels (dusp::ScoreSend), behind the plan
     explicit ScoreLaunch(ScoreKind kind_, uint64_t n_total = 0) : kind(kind_), w_hi(n_total) {}  // (n_total: over the whole timeline)
 };
 
@@ -208,6 +228,13 @@ static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onset
     for (size_t k = 0; k < n && L.any && !L.frac && !taps; k++) L.frac = P.voices[k].hi > P.voices[k].lo && P.voices[k].pad != 0;
     if (L.frac) L.frac_at = score_image_append<dusp::ScoreFrac>(ctx, n, [&](size_t k) { return dusp::score_frac_weights(h_fracs[k]); });
     score_pans_add(ctx, place, n, L);
+    L.n_buses = place.n_buses;
+    if (L.any && place.n_buses)  // (16 bytes a voice on top of the budget, as the weights are)
+        L.send_at = score_image_append<dusp::ScoreSend>(ctx, n, [&](size_t k) {
+            dusp::ScoreSend r{{0.0f, 0.0f, 0.0f, 0.0f}};
+            for (size_t b = 0; b < place.n_buses; b++) r.level[b] = place.h_sends[b * place.sends_stride + k];
+            return r;
+        });
     if (listed) {
         listed->resize(n);
         for (size_t k = 0; k < n; k++) (*listed)[k] = P.voices[k].hi > P.voices[k].lo;
@@ -240,9 +267,10 @@ static bool score_plan_intact(dusp_ctx *ctx) { return !ctx->d_score_plan || !g_g
 
 // The launch L describes, over its window of a timeline [n_channels][n_total] (pan: mono rows, [2][n_total]).  Its plan is in the image
 // on the device (the buffer and L.at: both on 32-byte boundaries); a launch without voices has none and hands the kernel of its kind NULLs.
-// d_planar, n_voice: the batch of a contiguous launch (else NULL and 0).
+// d_planar, n_voice: the batch of a contiguous launch (else NULL and 0).  d_send_init, d_send_out: the send timelines
+// [L.n_buses][n_channels][n_total] of a rows or pan launch with buses (d_send_out NULL: a launch without).
 static int score_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, size_t n_total, const float *d_gains, const float *d_init, int raw, float *d_out,
-                        hipStream_t stream, const float *d_planar, size_t n_voice) {
+                        hipStream_t stream, const float *d_planar, size_t n_voice, const float *d_send_init = nullptr, float *d_send_out = nullptr) {
     if (L.w_hi <= L.w_lo) return DUSP_OK;
     const unsigned char *d_image = ctx->d_score_plan;
     const unsigned char *d_voices = L.any ? d_image + L.at : nullptr;
@@ -250,7 +278,11 @@ static int score_launch(dusp_ctx *ctx, const ScoreLaunch &L, size_t n_channels, 
     const uint32_t *d_block_first = L.any ? (const uint32_t *)(d_voices + L.n_voices * record) : nullptr, *d_entries = L.any ? d_block_first + L.n_block_first : nullptr;
     const dusp::ScoreRow *d_rows = (const dusp::ScoreRow *)d_voices;
     const dusp::ScorePan *d_pans = L.any && (L.kind == ScoreKind::pan || L.kind == ScoreKind::stereo) ? (const dusp::ScorePan *)(d_image + L.pan_at) : nullptr;
-    if (L.any && L.kind == ScoreKind::stereo)  // (score_stereo_engine.hip: rows of one and of two channels into a timeline of two)
+    if (d_send_out)  // (score_send_engine.hip: the rows or the pan chain, and every bus's beside it; without voices a copy of both inits)
+        HIP_TRY(ctx, dusp::launch_score_send(d_gains, L.any ? (const dusp::ScoreSend *)(d_image + L.send_at) : nullptr, d_pans, d_rows, d_block_first, d_entries, d_init, d_out,
+                                             d_send_init, d_send_out, (uint32_t)L.n_buses, (uint32_t)n_channels, n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw,
+                                             L.kind == ScoreKind::pan, stream));
+    else if (L.any && L.kind == ScoreKind::stereo)  // (score_stereo_engine.hip: rows of one and of two channels into a timeline of two)
         HIP_TRY(ctx, dusp::launch_score_stereo(d_gains, d_pans, L.frac ? (const dusp::ScoreFrac *)(d_image + L.frac_at) : nullptr, d_rows, d_block_first, d_entries, d_init, d_out,
                                                n_total, L.w_lo, L.w_hi, L.block_shift, L.first_block, raw, stream));
     else if (L.any && L.kind == ScoreKind::space)  // (score_space_engine.hip: mono rows into a timeline of n_channels speakers)
@@ -310,23 +342,72 @@ static int score_deliver_host(dusp_program *prog, const char *who, ScoreKind kin
 
 // ---- the master of a piece: one mono circuit over every channel of the timeline ----
 
-// What a piece's master is held to before anything renders; n_ch: the timeline's channels, each an instance of the master
-static int score_master_check(dusp_ctx *ctx, const std::string &w, const dusp_score_master *master, const dusp_score_part *parts, size_t n_parts, size_t n_ch, size_t n_total) {
+// What a piece's master is held to before anything renders; n_ch: the timeline's channels, each an instance of the master.  A bus is
+// held to the same rules in the same words but for the noun: the = "bus 2", a = "a bus" (a master: "the master", "a master")
+static int score_master_check(dusp_ctx *ctx, const std::string &w, const dusp_score_master *master, const dusp_score_part *parts, size_t n_parts, size_t n_ch, size_t n_total,
+                              const std::string &the = "the master", const std::string &a = "a master") {
     dusp_program *m = master->prog;
-    if (!m) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master's program is NULL");
-    if (m->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master was built on another context: it shares the one of the piece's parts");
+    const bool bus = a != "a master";
+    if (!m) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + "'s program is NULL");
+    if (m->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " was built on another context: it shares the one of the piece's parts");
     for (size_t p = 0; p < n_parts; p++)
         if (parts[p].prog == m)
-            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master is also part " + std::to_string(p) + ": its buffers would be used twice; build it on its own");
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " is also part " + std::to_string(p) + ": its buffers would be used twice; build it on its own");
     if (m->P.g.n_inputs != 1)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a master reads exactly one input stream (the timeline's channel), this program has " + std::to_string(m->P.g.n_inputs));
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + a + " reads exactly one input stream (the " + (bus ? "send " : "") + "timeline's channel), this program has " + std::to_string(m->P.g.n_inputs));
     if (m->P.out_bufs.size() != 1)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a master has one output channel, this program has " + std::to_string(m->P.out_bufs.size()) +
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + a + " has one output channel, this program has " + std::to_string(m->P.out_bufs.size()) +
                                         ": it is applied to every channel of the timeline by itself");
-    if (m->resumable) CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, w + ": a resumable program (DUSP_ENGINE_RESUMABLE) is not a master: every call renders it from its initial state");
-    if (m->P.g.n_params > 0 && !master->h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master has parameters but its h_params is NULL");
+    if (m->resumable)
+        CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, w + ": a resumable program (DUSP_ENGINE_RESUMABLE) is not " + a + ": every call renders it from its initial state");
+    if (m->P.g.n_params > 0 && !master->h_params) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " has parameters but its h_params is NULL");
     if (!samples_in_range(n_total) || n_ch * n_total > dusp::kScoreRowMax)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the master renders channels x timeline samples, which must not exceed 2^31: render such a piece in windows of the timeline without a master");
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " renders channels x timeline samples, which must not exceed 2^31: render such a piece in windows of the timeline without " + a);
+    return DUSP_OK;
+}
+
+// What the buses of a piece are held to before anything renders: their number and levels (and what sends do not go with), every
+// rule of a master per bus, and a bus that is also the master or another bus
+static int score_buses_check(dusp_ctx *ctx, const std::string &w, const dusp_score_buses *buses, const ScorePlacement &place, size_t n_voices, const dusp_score_part *parts,
+                             size_t n_parts, const dusp_score_master *master, size_t n_ch, size_t n_total) {
+    if (int rc = place.check_sends(ctx, w.c_str(), n_voices)) return rc;
+    if (!buses->buses) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buses' programs are NULL");
+    for (size_t b = 0; b < buses->n_buses; b++) {
+        const std::string the = "bus " + std::to_string(b);
+        if (int rc = score_master_check(ctx, w, &buses->buses[b], parts, n_parts, n_ch, n_total, the, "a bus")) return rc;
+        if (master && master->prog == buses->buses[b].prog)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " is also the master: its buffers would be used twice; build it on its own");
+        for (size_t q = 0; q < b; q++)
+            if (buses->buses[q].prog == buses->buses[b].prog)
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": buses " + std::to_string(q) + " and " + std::to_string(b) + " are the same program: its buffers would be used twice; build it twice");
+    }
+    return DUSP_OK;
+}
+
+// What a host render with buses does between its last tile and its delivery: every bus in turn rendered over its RAW send timeline
+// (d_mix_sends [b], [n_ch][n_total]: channel c the one input stream of instance c) from its initial state into its own d_host_out, as a
+// master is (`|| 0` at its own copy-out), then ONE return launch that adds the buses' outputs onto the dry sums in d_mix, left-deep:
+// raw where a master follows (which reads the sums as they stand), else with the `|| 0` a delivery without buses applies by a launch
+// of its own.  rendered: the buses' batches, which stand until the delivery has waited for the stream.
+static int score_buses_return(dusp_program *prog, const dusp_score_buses *buses, size_t n_ch, size_t n_total, int raw, std::vector<std::unique_ptr<TiledBatch>> &rendered) {
+    dusp_ctx *ctx = prog->ctx;
+    const float *wets[dusp::kScoreBusMax] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t b = 0; b < buses->n_buses; b++) {
+        rendered.emplace_back(new TiledBatch(buses->buses[b].prog, n_ch, buses->buses[b].h_params, nullptr, n_ch));  // (one tile: all channels)
+        if (int rc = rendered.back()->render_tile(0, n_ch, n_total, prog->d_mix_sends.p + b * n_ch * n_total)) return rc;
+        wets[b] = buses->buses[b].prog->d_host_out.p;
+    }
+    HIP_TRY(ctx, dusp::launch_score_return(prog->d_mix.p, wets, (uint32_t)buses->n_buses, prog->d_mix.p, (uint64_t)n_ch * n_total, raw, ctx->stream));
+    return DUSP_OK;
+}
+
+// ... and what it ends with behind its delivery: the guard bytes of what the send and return kernels wrote, and every bus's own
+static int score_buses_guards(dusp_program *prog, const char *who, const dusp_score_buses *buses) {
+    dusp_ctx *ctx = prog->ctx;
+    if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_sends.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
+    for (size_t b = 0; b < buses->n_buses; b++)
+        if (int rc = check_guards(buses->buses[b].prog, ctx->stream)) return rc;
     return DUSP_OK;
 }
 
@@ -384,13 +465,20 @@ int dusp_score_device(dusp_ctx *ctx, const float *d_planar, size_t n_instances, 
 // channel; stereo: n_channels is 1 and every row has place.h_row_channels[k]), into a timeline of place.timeline_channels(n_channels)
 static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
                              const int64_t *h_lengths, const float *d_gains, const ScorePlacement &place, size_t n_total_samples, const float *d_init, int raw, float *d_out,
-                             void *stream_) {
+                             void *stream_, const float *d_send_init = nullptr, float *d_send_out = nullptr, bool sends = false) {
     if (!ctx) return DUSP_ERR_ARG;
     return guarded(ctx->err, who, [&]() -> int {
     const std::string w(who);
     if (int rc = place.check_taps(ctx, who, n_voices, n_total_samples)) return rc;  // (first: the timeline's channel count is theirs)
     const size_t n_out_channels = place.timeline_channels(n_channels);
     if (!d_out || (n_voices && (!h_rows || !h_row_samples || !h_onsets))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (sends) {  // (dusp_score_rows_send_device)
+        if (n_voices || place.n_buses < 1 || place.n_buses > dusp::kScoreBusMax) {
+            if (int rc = place.check_sends(ctx, who, n_voices)) return rc;
+        }
+        if (!d_send_out) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+        if ((((uintptr_t)d_send_init | (uintptr_t)d_send_out) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
+    }
     const bool stereo = place.kind == ScoreKind::stereo;
     if (stereo && n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 0..2^24 voices");
     if (int rc = place.check_kinds(ctx, who, n_voices)) return rc;  // (before the rows' sizes are looked at: they are channels x samples)
@@ -409,6 +497,7 @@ static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_of(ctx, stream_);
     ScoreLaunch L(place.kind, n_total_samples);  // (no voices: `|| 0`, or a copy, of d_init alone)
+    L.n_buses = place.n_buses;
     return score_device_call(
         ctx, stream, n_voices != 0, L,
         [&]() {
@@ -416,7 +505,7 @@ static int score_rows_device(dusp_ctx *ctx, const char *who, const float *const 
             return score_rows_add(ctx, who, h_onsets, h_lengths, h_row_samples, (const uint64_t *)h_rows, n_voices, 0, n_total_samples, /*whole_timeline=*/true,
                                   score_plan_budget(ctx), place, L, nullptr);
         },
-        [&]() { return score_launch(ctx, L, n_out_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream, nullptr, 0); });
+        [&]() { return score_launch(ctx, L, n_out_channels, n_total_samples, d_gains, d_init, raw != 0, d_out, stream, nullptr, 0, d_send_init, d_send_out); });
     });
 }
 
@@ -501,7 +590,7 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
 // input stream, rendered over every channel of the raw timeline before the delivery (score_master_deliver_host)
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const ScorePlacement &given, size_t n_total_samples, size_t tile_bytes, int format,
-                                   int normalise, void *h_out, float *h_peak, const dusp_score_master *master = nullptr) {
+                                   int normalise, void *h_out, float *h_peak, const dusp_score_master *master = nullptr, const dusp_score_buses *buses = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
@@ -509,6 +598,11 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     const std::string w(who);
     const size_t n_ch = prog0->P.out_bufs.size();  // (a voice's)
     ScorePlacement place = given;
+    if (buses) {  // (the levels travel with the placement: a tile's are its voices')
+        place.n_buses = buses->n_buses;
+        place.sends_stride = n_voices;
+        place.h_sends = buses->h_sends;
+    }
     const bool stereo = place.kind == ScoreKind::stereo, panned = place.kind == ScoreKind::pan, taps = place.kind == ScoreKind::space;
     if (!h_part_of || !h_onsets) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_part_of or h_onsets is NULL");
     if (n_voices < 1 || n_voices > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^24 voices");
@@ -538,6 +632,8 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     }
     if (master)
         if (int rc = score_master_check(ctx, w, master, parts, n_parts, n_out_ch, n_total_samples)) return rc;
+    if (buses)
+        if (int rc = score_buses_check(ctx, w, buses, place, n_voices, parts, n_parts, master, n_out_ch, n_total_samples)) return rc;
     if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
     if (int rc = place.check_values(ctx, who, n_voices)) return rc;
@@ -622,12 +718,22 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         HIP_TRY(ctx, master->prog->d_host_out.ensure(n_out_ch * n_total_samples));
         if (master->prog->P.g.n_params) HIP_TRY(ctx, master->prog->d_host_par.ensure((size_t)master->prog->P.g.n_params * n_out_ch));
     }
+    if (buses) {  // (... the send timelines, and what every bus makes of its own: 2 x n_buses more [channels][n_total], and the buses' columns)
+        HIP_TRY(ctx, prog0->d_mix_sends.ensure(buses->n_buses * n_out_ch * n_total_samples));
+        for (size_t b = 0; b < buses->n_buses; b++) {
+            dusp_program *bus = buses->buses[b].prog;
+            HIP_TRY(ctx, bus->d_host_out.ensure(n_out_ch * n_total_samples));
+            if (bus->P.g.n_params) HIP_TRY(ctx, bus->d_host_par.ensure((size_t)bus->P.g.n_params * n_out_ch));
+        }
+    }
     if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once)
         HIP_TRY(ctx, prog0->d_mix_gains.ensure(n_voices));
         HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
     if (int rc = score_image_upload(ctx, ctx->stream)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix.p, 0, n_out_ch * n_total_samples * sizeof(float), ctx->stream));
+    float *d_sends = buses ? prog0->d_mix_sends.p : nullptr;
+    if (buses) HIP_TRY(ctx, hipMemsetAsync(d_sends, 0, buses->n_buses * n_out_ch * n_total_samples * sizeof(float), ctx->stream));
     std::vector<std::unique_ptr<TiledBatch>> whole;  // what changes bits is decided from the WHOLE part
     for (size_t p = 0; p < n_parts; p++) whole.emplace_back(new TiledBatch(parts[p].prog, parts[p].n_instances, parts[p].h_params, share[p]));
     auto waited = [&]() {
@@ -639,13 +745,22 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
             if (renders[i][p])
                 if (int rc = whole[p]->render_tile(share[p][i], share[p][i + 1] - share[p][i], parts[p].n_voice_samples)) return rc;
         const float *d_gains = h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr;
-        if (int rc = score_launch(ctx, launches[i], n_out_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream, nullptr, 0)) return rc;
+        if (int rc = score_launch(ctx, launches[i], n_out_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream, nullptr, 0, d_sends, d_sends))
+            return rc;
     }
-    // (`|| 0` is the rows kernel's over the timeline's channels, panned or not; behind a master it is the master's own copy-out's)
-    if (int rc = master ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
-                        : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out))
+    std::vector<std::unique_ptr<TiledBatch>> returned;  // (the buses' renders)
+    if (buses)
+        if (int rc = score_buses_return(prog0, buses, n_out_ch, n_total_samples, /*raw=*/master != nullptr, returned)) return rc;
+    // (`|| 0` is the rows kernel's over the timeline's channels, panned or not; behind a master it is the master's own copy-out's; behind
+    // buses without a master the return kernel has applied it)
+    if (int rc = master  ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
+                 : buses ? deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
+                         : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out))
         return rc;
     waited();  // (the delivery has waited for the stream)
+    for (auto &b : returned) b->staged = false;
+    if (buses)
+        if (int rc = score_buses_guards(prog0, who, buses)) return rc;
     return DUSP_OK;
     });
 }
@@ -717,12 +832,11 @@ int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_p
                                    ScorePlacement(ScoreKind::stereo, h_fracs, h_pans, h_comp), n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
 }
 
-// One entry for every placement, with or without a master: the placement as a record (dusp_score_placement; NULL: plain rows)
-int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
-                                 const float *h_gains, const dusp_score_placement *placement, const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes,
-                                 int format, int normalise, void *h_out, float *h_peak) {
+// One entry for every placement, with or without a master and buses: the placement as a record (dusp_score_placement; NULL: plain rows)
+static int render_host_score_piece(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                   const int64_t *h_lengths, const float *h_gains, const dusp_score_placement *placement, const dusp_score_buses *buses,
+                                   const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
-    const char *who = "dusp_render_host_score_piece";
     dusp_ctx *ctx = parts[0].prog->ctx;
     const dusp_score_placement plain{DUSP_PLACE_ROWS, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
     const dusp_score_placement &by = placement ? *placement : plain;
@@ -743,7 +857,64 @@ int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, s
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the placement's kind must be DUSP_PLACE_ROWS (0), DUSP_PLACE_PAN (1), DUSP_PLACE_SPACE (2) or DUSP_PLACE_STEREO (3)");
     }
     return render_host_score_parts(who, parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, place, n_total_samples, tile_bytes, format, normalise, h_out, h_peak,
-                                   master);
+                                   master, buses);
+}
+
+int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                 const float *h_gains, const dusp_score_placement *placement, const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes,
+                                 int format, int normalise, void *h_out, float *h_peak) {
+    return render_host_score_piece("dusp_render_host_score_piece", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, nullptr, master, n_total_samples,
+                                   tile_bytes, format, normalise, h_out, h_peak);
+}
+
+// ... and with effect sends (buses NULL: dusp_render_host_score_piece under this entry's name)
+int dusp_render_host_score_piece_buses(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                       const float *h_gains, const dusp_score_placement *placement, const dusp_score_buses *buses, const dusp_score_master *master,
+                                       size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
+    return render_host_score_piece("dusp_render_host_score_piece_buses", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, buses, master,
+                                   n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
+}
+
+// The send chain alone (score_send_engine.hip): dusp_score_rows_device — h_pans: dusp_score_rows_pan_device, mono rows into two
+// channels — whose every term also goes, times the voice's level, to n_buses send timelines
+int dusp_score_rows_send_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices, size_t n_channels, const int64_t *h_onsets,
+                                const int64_t *h_lengths, const float *d_gains, const float *h_pans, const double *h_comp, size_t n_buses, const float *h_sends,
+                                size_t n_total_samples, const float *d_init, int raw, float *d_out, const float *d_send_init, float *d_send_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    if (h_pans && n_channels != 1) CTX_FAIL(ctx, DUSP_ERR_ARG, "dusp_score_rows_send_device: a panned voice is mono: n_channels must be 1 with h_pans");
+    ScorePlacement place(h_pans ? ScoreKind::pan : ScoreKind::rows, nullptr, h_pans, h_comp);
+    place.n_buses = n_buses;
+    place.sends_stride = n_voices;
+    place.h_sends = h_sends;
+    return score_rows_device(ctx, "dusp_score_rows_send_device", h_rows, h_row_samples, n_voices, n_channels, h_onsets, h_lengths, d_gains, place, n_total_samples, d_init, raw,
+                             d_out, stream_, d_send_init, d_send_out, /*sends=*/true);
+}
+
+// The return of the buses alone: d_out[j] = d_dry[j] + h_wets[0][j] + ... over n_floats floats, left-deep, `|| 0` unless raw
+int dusp_score_return_device(dusp_ctx *ctx, const float *d_dry, const float *const *h_wets, size_t n_buses, size_t n_floats, int raw, float *d_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    const char *who = "dusp_score_return_device";
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    if (n_buses < 1 || n_buses > dusp::kScoreBusMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 1 .. 4 buses, not " + std::to_string(n_buses));
+    if (!d_dry || !d_out || !h_wets) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (n_floats < 1 || n_floats > dusp::kScoreRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^31 floats");
+    uintptr_t low = (uintptr_t)d_dry | (uintptr_t)d_out;
+    for (size_t b = 0; b < n_buses; b++) {
+        if (!h_wets[b]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+        low |= (uintptr_t)h_wets[b];
+    }
+    if (low & 3) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    const ScoreLaunch none(ScoreKind::rows);  // (no plan: timed like any other launch)
+    return score_device_call(
+        ctx, stream, false, none, []() { return DUSP_OK; },
+        [&]() {
+            HIP_TRY(ctx, dusp::launch_score_return(d_dry, h_wets, (uint32_t)n_buses, d_out, n_floats, raw != 0, stream));
+            return DUSP_OK;
+        });
+    });
 }
 
 }  // extern "C"

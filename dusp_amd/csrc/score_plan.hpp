@@ -297,4 +297,16 @@ static_assert(sizeof(ScoreFrac) == 16, "one four-dword scalar load");
 
 inline ScoreFrac score_frac_weights(double frac) { return ScoreFrac{1.0 - frac, frac}; }
 
+// ---- sends: a level per voice and bus (score_send_engine.hip; dusp_amd/mix.py score_chain_sends) ----
+
+// What a voice gives to each of up to kScoreBusMax buses: the f32 factor of its dry term.  One record a voice of the plan, a parallel
+// array behind the plan in the context's image and on top of its byte budget, as ScorePan and ScoreFrac; the levels of buses the call
+// does not have are 0 and are not read.
+// (16 bytes on a 16-byte boundary: one four-dword scalar load a voice)
+constexpr size_t kScoreBusMax = 4;
+struct alignas(16) ScoreSend {
+    float level[kScoreBusMax];
+};
+static_assert(sizeof(ScoreSend) == 16, "one four-dword scalar load");
+
 }  // namespace dusp

@@ -10,6 +10,8 @@
  *   stateDownload(prog, instance, unit) -> Float64Array
  *   renderPiece(progs[], ...) -> Promise: a piece of several instruments (dusp_render_host_score_parts; see fn_render_piece)
  *   renderPieceMaster(progs[], ..., master, masterParams) -> Promise: the same through a master (dusp_render_host_score_piece)
+ *   renderPieceBuses(progs[], ..., master | null, masterParams, buses[], busParams[], sends) -> Promise: the same with effect sends
+ *         (dusp_render_host_score_piece_buses)
  *   descriptorChannels(Float64Array words) -> the circuit's output channels (host code only: no context)
  *   programDestroy(prog), ctxDestroy(ctx), version(), abiVersion()
  * Failures surface the way the reference's do: synchronous calls THROW A STRING, render() REJECTS
@@ -761,6 +763,11 @@ typedef struct {
     prog_box *master_pb; /* renderPieceMaster: the program the mix goes through (dusp_render_host_score_piece), else NULL ... */
     napi_ref master_ref;
     float *master_params; /* ... and a host copy of its table [nParams][timeline channels], or NULL */
+    size_t n_buses;       /* renderPieceBuses: the bus programs (dusp_render_host_score_piece_buses), each kept as the master is ... */
+    prog_box *bus_pb[4];
+    napi_ref bus_ref[4];
+    float *bus_params[4];
+    float *sends;         /* ... and a host copy of the voices' levels [nBuses][nVoices] */
     int format, normalise, rc;
     char err[512];
 } piece_job;
@@ -772,6 +779,11 @@ static void piece_free(napi_env env, piece_job *j) {
     }
     if (j->master_ref) napi_delete_reference(env, j->master_ref);
     free(j->master_params);
+    for (size_t b = 0; b < 4; b++) {
+        if (j->bus_ref[b]) napi_delete_reference(env, j->bus_ref[b]);
+        free(j->bus_params[b]);
+    }
+    free(j->sends);
     free(j->params);
     free(j->refs);
     free(j->pbs);
@@ -805,8 +817,24 @@ static void piece_execute(napi_env env, void *data) {
         j->rc = DUSP_ERR_STATE;
         snprintf(j->err, sizeof j->err, "dusp-hip: renderPiece: a program has been destroyed");
     }
+    for (size_t b = 0; b < j->n_buses; b++)
+        if (!j->bus_pb[b]->prog) {
+            j->rc = DUSP_ERR_STATE;
+            snprintf(j->err, sizeof j->err, "dusp-hip: renderPiece: a program has been destroyed");
+        }
     if (j->rc == DUSP_OK) {
-        if (j->master_pb) { /* one entry for every placement */
+        if (j->n_buses) { /* one entry for every placement, which refuses what sends do not go with */
+            dusp_score_placement place = {j->stereo ? DUSP_PLACE_STEREO : j->delays ? DUSP_PLACE_SPACE : j->pans ? DUSP_PLACE_PAN : DUSP_PLACE_ROWS,
+                                          j->fracs, j->pans, j->comp, j->n_speakers, j->delays, j->tap_gains};
+            dusp_score_master master = {j->master_pb ? j->master_pb->prog : NULL, j->master_params}, circuits[4];
+            for (size_t b = 0; b < j->n_buses; b++) {
+                circuits[b].prog = j->bus_pb[b]->prog;
+                circuits[b].h_params = j->bus_params[b];
+            }
+            dusp_score_buses buses = {j->n_buses, circuits, j->sends};
+            j->rc = dusp_render_host_score_piece_buses(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, &buses, j->master_pb ? &master : NULL,
+                                                       j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+        } else if (j->master_pb) { /* one entry for every placement */
             dusp_score_placement place = {j->stereo ? DUSP_PLACE_STEREO : j->delays ? DUSP_PLACE_SPACE : j->pans ? DUSP_PLACE_PAN : DUSP_PLACE_ROWS,
                                           j->fracs, j->pans, j->comp, j->n_speakers, j->delays, j->tap_gains};
             dusp_score_master master = {j->master_pb->prog, j->master_params};
@@ -866,6 +894,8 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
     for (size_t p = 0; p < j->n_parts; p++)
         if (--j->pbs[p]->in_flight == 0 && j->pbs[p]->destroy_deferred) prog_destroy_now(j->pbs[p]);
     if (j->master_pb && --j->master_pb->in_flight == 0 && j->master_pb->destroy_deferred) prog_destroy_now(j->master_pb);
+    for (size_t b = 0; b < j->n_buses; b++)
+        if (--j->bus_pb[b]->in_flight == 0 && j->bus_pb[b]->destroy_deferred) prog_destroy_now(j->bus_pb[b]);
     napi_delete_async_work(env, j->work);
     piece_free(env, j);
 }
@@ -887,12 +917,16 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  * renderPieceMaster(the same twelve, kind, fracs | null, pans | null, comp | null, nSpeakers, delays | null, tapGains | null, master, masterParams | null)
  *   -> any of the five — kind 0 plain rows, 1 panned, 2 in a space, 3 stereo, each with the arrays of its kind as above — with the mix
  *      put through the program `master` before it is delivered (dusp_render_host_score_piece: a program with one input stream and one
- *      output channel, channel c of the timeline instance c of it; masterParams its table, nParams * timeline channels values) */
-static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master */
-    napi_value argv[21];
+ *      output channel, channel c of the timeline instance c of it; masterParams its table, nParams * timeline channels values)
+ * renderPieceBuses(the same twenty-one — master and masterParams may be null —, buses[] (programs), busParams[] (Float32Array | null each), sends Float32Array)
+ *   -> the same with effect sends (dusp_render_host_score_piece_buses): 1 .. 4 bus programs, each what a master is, with its table, and
+ *      sends[b * nVoices + k] what voice k gives to bus b; the library refuses the kinds and arrays sends do not go with */
+static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master, 6 ... and buses */
+    napi_value argv[24];
     char msg[256];
-    if (!get_args(env, info, form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
-    const int with_master = form == 5;
+    if (!get_args(env, info, form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    const int with_buses = form == 6;
+    int with_master = form == 5 || form == 6; /* (the placement as a record; with buses the master itself may be null) */
     int fracs_at = 12, space_at = 12, pans_at = form == 2 || form == 4 ? 13 : 12;
     if (with_master) { /* the placement's kind says which of the four other forms this is */
         double kind = -1;
@@ -1057,6 +1091,47 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
             n_channels = (uint32_t)speakers; /* the timeline's */
         }
     }
+    if (with_buses) { /* (a call with buses may have no master) */
+        napi_valuetype mv = napi_undefined;
+        napi_typeof(env, argv[19], &mv);
+        if (mv == napi_null || mv == napi_undefined) with_master = 0;
+    }
+    if (!bad && with_buses) { /* the buses: programs of the parts' context, each with its table; and the levels */
+        uint32_t n_buses = 0, n_tables = 0;
+        bool arrays = false, tables = false;
+        void *sd;
+        size_t n_s = 0;
+        if (napi_is_array(env, argv[21], &arrays) != napi_ok || !arrays || napi_get_array_length(env, argv[21], &n_buses) != napi_ok || n_buses < 1 || n_buses > 4)
+            bad = "buses must be an array of 1 .. 4 programs";
+        else if (napi_is_array(env, argv[22], &tables) != napi_ok || !tables || napi_get_array_length(env, argv[22], &n_tables) != napi_ok || n_tables != n_buses)
+            bad = "busParams must be an array of one entry per bus";
+        else if (!typed_array(env, argv[23], napi_float32_array, &sd, &n_s) || n_s != (size_t)n_buses * n_voices) bad = "sends must be a Float32Array of one value per bus and voice";
+        else if (!(j->sends = (float *)malloc(n_s * sizeof(float) + 1))) bad = "out of host memory for the send levels";
+        else memcpy(j->sends, sd, n_s * sizeof(float));
+        for (uint32_t b = 0; b < n_buses && !bad; b++) {
+            napi_value prog_v, table_v;
+            napi_valuetype tt = napi_undefined;
+            prog_box *pb = NULL;
+            if (napi_get_element(env, argv[21], b, &prog_v) != napi_ok || napi_get_element(env, argv[22], b, &table_v) != napi_ok) { bad = "could not read a bus"; break; }
+            if (!(pb = as_prog(env, prog_v))) { /* (as_prog has thrown) */
+                piece_free(env, j);
+                return NULL;
+            }
+            j->bus_pb[b] = pb;
+            j->n_buses = b + 1;
+            dusp_program_info bi;
+            dusp_program_info_get(pb->prog, &bi);
+            napi_typeof(env, table_v, &tt);
+            if (pb->cb != j->pbs[0]->cb) bad = "a bus is built on the context of the piece's parts";
+            else if (tt != napi_null && tt != napi_undefined) {
+                void *data;
+                size_t len;
+                if (!typed_array(env, table_v, napi_float32_array, &data, &len) || len != (size_t)bi.n_params * n_channels) bad = "busParams holds Float32Arrays of nParams * timeline channels values";
+                else if (!(j->bus_params[b] = (float *)malloc(len * sizeof(float) + 1))) bad = "out of host memory for a parameter table";
+                else memcpy(j->bus_params[b], data, len * sizeof(float));
+            } else if (bi.n_params) bad = "a bus's program needs a parameter table";
+        }
+    }
     if (!bad && with_master) { /* the master: a program of the parts' context; its table has one column a channel of the timeline */
         napi_valuetype mt = napi_undefined;
         if (!(j->master_pb = as_prog(env, argv[19]))) { /* (as_prog has thrown) */
@@ -1092,18 +1167,25 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         queued = napi_get_element(env, argv[0], p, &prog_v) == napi_ok && napi_create_reference(env, prog_v, 1, &j->refs[p]) == napi_ok;
     }
     if (queued && j->master_pb) queued = napi_create_reference(env, argv[19], 1, &j->master_ref) == napi_ok;
+    for (size_t b = 0; b < j->n_buses && queued; b++) {
+        napi_value prog_v;
+        queued = napi_get_element(env, argv[21], (uint32_t)b, &prog_v) == napi_ok && napi_create_reference(env, prog_v, 1, &j->bus_ref[b]) == napi_ok;
+    }
     queued = queued && napi_create_async_work(env, NULL, name, piece_execute, piece_complete, j, &j->work) == napi_ok;
     if (queued) {
         for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight++;
         if (j->master_pb) j->master_pb->in_flight++;
+        for (size_t b = 0; b < j->n_buses; b++) j->bus_pb[b]->in_flight++;
         if (napi_queue_async_work(env, j->work) != napi_ok) {
             for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight--;
             if (j->master_pb) j->master_pb->in_flight--;
+            for (size_t b = 0; b < j->n_buses; b++) j->bus_pb[b]->in_flight--;
             queued = 0;
         }
     }
     if (!queued) {
         j->master_pb = NULL;
+        j->n_buses = 0;
         piece_free(env, j);
         throw_string(env, "dusp-hip: renderPiece: could not queue the render");
         return NULL;
@@ -1117,6 +1199,7 @@ static napi_value fn_render_piece_frac(napi_env env, napi_callback_info info) { 
 static napi_value fn_render_piece_space(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 3); }
 static napi_value fn_render_piece_stereo(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 4); }
 static napi_value fn_render_piece_master(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 5); }
+static napi_value fn_render_piece_buses(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 6); }
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1151,6 +1234,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
         {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo}, {"renderPieceMaster", fn_render_piece_master},
+        {"renderPieceBuses", fn_render_piece_buses},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -454,9 +454,10 @@ function wholeSamples(who, name, values, count) {
  * piece's call too.
  * stereo: true — as renderPiece's: voices of one or two channels, two channels out, pans optional and null / NaN for a voice that is not
  * placed — through the piece's call too.
- * master: as renderPiece's — the mix through a mono circuit, channel by channel, on the device — through the piece's call too. */
+ * master: as renderPiece's — the mix through a mono circuit, channel by channel, on the device — through the piece's call too.
+ * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
-const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master)
+const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -689,28 +690,75 @@ const MASTER = {
  * parameter table [nParams][channels].  Refused by string: what is no function, an array of the wrong length, a circuit that holds no
  * or several MasterInput, another host-computed signal or a scheduled event, one with more than one output channel, circuits that are
  * not isomorphic. */
-function masterProgram(master, channels, sampleRate) {
+function masterProgram(master, channels, sampleRate, bus = null) {
+  // bus (null: a master): the circuit is bus number `bus` of the call's buses — given and checked as a master is, refused in BUS's words
+  const refuse = (name, ...args) => (bus === null ? MASTER[name] : BUS[name]).apply(null, bus === null ? args : [bus].concat(args))
   const fxs = Array.isArray(master) ? master : new Array(channels).fill(master)
-  if (!fxs.length || !fxs.every((fx) => typeof fx === 'function')) throw MASTER.notCallable
-  if (fxs.length !== channels) throw MASTER.count(fxs.length, channels)
+  if (!fxs.length || !fxs.every((fx) => typeof fx === 'function')) throw (bus === null ? MASTER.notCallable : BUS.notCallable(bus))
+  if (fxs.length !== channels) throw refuse('count', fxs.length, channels)
   const extractions = []
   fxs.forEach((fx, c) => {
     const ex = extract(fx(new MasterInput()), { allowEvents: true })
-    if (ex.circuit.events && ex.circuit.events.length) throw MASTER.events(c)
-    if (ex.sources.some((u) => !u.isMasterInput)) throw MASTER.hostSource(c)
-    if (ex.sources.length !== 1) throw MASTER.oneInput(c, ex.sources.length)
-    if (ex.sampleRate !== sampleRate) throw MASTER.rate(ex.sampleRate, sampleRate)
+    if (ex.circuit.events && ex.circuit.events.length) throw refuse('events', c)
+    if (ex.sources.some((u) => !u.isMasterInput)) throw refuse('hostSource', c)
+    if (ex.sources.length !== 1) throw refuse('oneInput', c, ex.sources.length)
+    if (ex.sampleRate !== sampleRate) throw refuse('rate', ex.sampleRate, sampleRate)
     const nOut = native().descriptorChannels(ex.words)
-    if (nOut !== 1) throw MASTER.channels(c, nOut)
-    if (c && structureKey(ex) !== structureKey(extractions[0])) throw MASTER.notIsomorphic(c)
+    if (nOut !== 1) throw refuse('channels', c, nOut)
+    if (c && structureKey(ex) !== structureKey(extractions[0])) throw refuse('notIsomorphic', c)
     extractions.push(ex)
   })
   return unify(extractions)
 }
 
+/* Effect sends (DESIGN.md 6.15): the refusals of a bus and of the levels, in the words of mix.py (BUS_*, SENDS_*) */
+const BUS = {
+  notCallable: (b) => 'dusp-hip: bus ' + b + ' is a function fx(x) of its send timeline, or a list of one function a channel of the timeline',
+  count: (b, have, channels) => 'dusp-hip: bus ' + b + ' lists ' + have + ' circuits, the timeline has ' + channels + ' channels: one a channel',
+  oneInput: (b, c, have) => 'dusp-hip: bus ' + b + ', channel ' + c + ', holds ' + have + ' MasterInput units: a bus reads its sends through exactly one, the one it is given',
+  hostSource: (b, c) => 'dusp-hip: bus ' + b + ', channel ' + c + ", holds a HostSource: the send timeline is a bus's only input",
+  events: (b, c) => 'dusp-hip: bus ' + b + ', channel ' + c + ', has scheduled events: a bus is rendered in one piece',
+  channels: (b, c, have) => 'dusp-hip: bus ' + b + ', channel ' + c + ', has ' + have + ' output channels: a bus is a mono circuit, applied to every channel by itself',
+  notIsomorphic: (b, c) => 'dusp-hip: the circuits of bus ' + b + ' at channels 0 and ' + c + ' are not isomorphic: they are one program and may differ in constants only',
+  rate: (b, have, want) => 'dusp-hip: the sample rate of bus ' + b + ' is ' + have + ", the voices' is " + want,
+}
+const SENDS = {
+  withoutBuses: 'dusp-hip: sends without buses: a send level is what a voice gives to a bus',
+  withoutSends: 'dusp-hip: buses without sends: every bus needs a send level a voice (sends of shape (buses, voices))',
+  busCount: (have) => 'dusp-hip: a call has 1 .. 4 buses, not ' + have,
+  placement: 'dusp-hip: sends go with plain rows and with pans at whole-sample onsets: together with fracs, places or stereo they are refused',
+  shape: (buses, voices) => 'dusp-hip: sends must have shape (buses=' + buses + ', voices=' + voices + ')',
+  notFinite: (k, b) => 'dusp-hip: the send level of voice ' + k + ' into bus ' + b + ' is not finite',
+}
+
+/* the send levels of `count` voices into nBuses buses -> Float32Array [nBuses * count], bus by bus (twin of mix.py check_sends): an
+ * array of nBuses arrays of `count` numbers, or — one bus — `count` numbers; every level finite as a float32 */
+function checkSends(sends, count, nBuses) {
+  if (!(nBuses >= 1 && nBuses <= 4)) throw SENDS.busCount(nBuses)
+  const isList = (x) => Array.isArray(x) || ArrayBuffer.isView(x)
+  if (!isList(sends)) throw SENDS.shape(nBuses, count)
+  let rows = Array.from(sends)
+  if (nBuses === 1 && rows.length === count && !rows.some(isList) && !(count === 1 && isList(sends[0]))) rows = [rows]
+  if (rows.length !== nBuses || !rows.every((r) => isList(r) && r.length === count && !Array.from(r).some(isList))) throw SENDS.shape(nBuses, count)
+  const out = new Float32Array(nBuses * count)
+  rows.forEach((r, b) => out.set(Float32Array.from(r, Number), b * count))
+  for (let b = 0; b < nBuses; b++) for (let k = 0; k < count; k++) if (!Number.isFinite(out[b * count + k])) throw SENDS.notFinite(k, b)
+  return out
+}
+
+/* what sends do not go with, refused before anything else of a call is looked at (twin of render.py _placing) */
+function refuseSends(opts) {
+  if (!given(opts.buses) && given(opts.sends)) throw SENDS.withoutBuses
+  if (!given(opts.buses)) return
+  if (!given(opts.sends)) throw SENDS.withoutSends
+  if (given(opts.fracs) || given(opts.places) || opts.stereo === true) throw SENDS.placement
+  if (!Array.isArray(opts.buses) || opts.buses.length < 1 || opts.buses.length > 4) throw SENDS.busCount(Array.isArray(opts.buses) ? opts.buses.length : 0)
+}
+
 async function pieceCall(who, outlets, opts, format, normalise, onePart = false) {
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
   const stereo = opts.stereo === true
+  refuseSends(opts)
   if (given(opts.places) && stereo) throw STEREO_NO_PLACES
   if (given(opts.places) && (given(opts.pans) || given(opts.fracs))) throw SPACE_ALONE
   const extractions = outlets.map((o) => extract(o))
@@ -750,15 +798,23 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   const channels = grouped.parts.map((part) => n.descriptorChannels(part.uni.words))
   const nChannels = stereo ? checkStereoKinds(Array.from(grouped.partOf, (p) => channels[p]), panned.pans) : taps ? checkSpaceChannels(channels, taps.nSpeakers) : panned ? checkPanChannels(channels) : checkPieceChannels(channels)
   const master = given(opts.master) ? masterProgram(opts.master, nChannels, sampleRate) : null // (behind every other check of the call)
+  let buses = null, sends = null // (... the buses behind the master: the levels, then each bus as a master is made)
+  if (given(opts.buses)) {
+    sends = checkSends(opts.sends, count, opts.buses.length)
+    buses = opts.buses.map((fx, b) => masterProgram(fx, nChannels, sampleRate, b))
+  }
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
-  const progs = []
+  const progs = [], busProgs = []
   let masterProg = null
   try {
     for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
     if (master) masterProg = n.programBuild(contextFor(sampleRate), master.words, engine)
+    if (buses) for (const bus of buses) busProgs.push(n.programBuild(contextFor(sampleRate), bus.words, engine))
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
-    const result = master ? await n.renderPieceMaster(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+    const result = buses ? await n.renderPieceBuses(...args, panned ? 1 : 0, null, panned ? panned.pans : null, panned ? panned.comp : null, 0, null, null,
+      masterProg, master && master.nParams ? master.params : null, busProgs, buses.map((bus) => (bus.nParams ? bus.params : null)), sends)
+      : master ? await n.renderPieceMaster(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master.nParams ? master.params : null)
       : stereo ? await n.renderPieceStereo(...args, fracs, panned.pans, panned.comp)
       : taps ? await n.renderPieceSpace(...args, taps.nSpeakers, taps.delays, taps.gains)
@@ -768,6 +824,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   } finally {
     for (const prog of progs) n.programDestroy(prog)
     if (masterProg) n.programDestroy(masterProg)
+    for (const prog of busProgs) n.programDestroy(prog)
   }
 }
 
@@ -800,7 +857,13 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * and returning a MONO circuit over it, or an array of one function a channel; the circuits are isomorphic and may differ in constants
  * (masterProgram).  Channel c of the result is the render of the master over the timeline's channel c as the chain left it — before
  * `|| 0`, as a unit behind Sum.many hears it — from the master's initial state (DESIGN.md 6.14 says where that is the reference's
- * fx(Sum.many(...)) bit for bit and where it is not).  The call's engine is the master's too. */
+ * fx(Sum.many(...)) bit for bit and where it is not).  The call's engine is the master's too.
+ * buses, sends: effect sends — some notes, at a level of their own, into an effect such as an echo, and its return beside the dry mix
+ * (dusp_render_host_score_piece_buses; DESIGN.md 6.15).  buses: an array of 1 .. 4 circuits, each given as a master is; sends: an array
+ * of one array of levels a bus (one bus: the levels themselves will do), sends[b][k] what voice k gives to bus b.  Bus b hears the chain
+ * of every voice's dry term — after its gain and its pan — times its level, is rendered over that timeline as a master is over the mix,
+ * and the buses' outputs are added to the dry mix in order, in front of the master where there is one.  A level of 0 is a
+ * multiplication by 0, not a voice left out.  With plain voices and with pans; fracs, places and stereo are refused with sends. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   const channelData = []
@@ -870,6 +933,9 @@ module.exports.checkPlaces = checkPlaces
 module.exports.checkSpaceChannels = checkSpaceChannels
 module.exports.masterProgram = masterProgram
 module.exports.MASTER = MASTER
+module.exports.BUS = BUS
+module.exports.SENDS = SENDS
+module.exports.checkSends = checkSends
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

@@ -120,15 +120,19 @@ def _chain_end(acc, raw):
         return acc if raw else np.where(np.isnan(acc) | (acc == 0), np.float32(0), acc)
 
 
-def _chain(rows, n_ch, n_total, onsets, lengths, gains, fracs, init, raw, noun="voices", place=None):
+def _chain(rows, n_ch, n_total, onsets, lengths, gains, fracs, init, raw, noun="voices", place=None, sends=None):
     """The one chain behind score_chain, score_chain_rows and score_chain_rows_panned.  rows: a list of float32 [channels, samples_k];
     onsets, lengths: int64 [voices], checked by the caller; gains, fracs and init are checked here, in that order (they are refused in
     the same words by all three, but for the noun of the gains' shape).  place(k, x): what becomes of voice k's samples after the gain
-    before they are added, float32 [channels, len] -> float32 [n_ch, len] (None: x itself)."""
+    before they are added, float32 [channels, len] -> float32 [n_ch, len] (None: x itself).
+    sends (None: the chain as it always was, operation for operation): float32 [B, voices], checked by the caller (check_sends), without
+    fracs — the term every add of the chain adds is also multiplied by sends[b][k], a plain f32 product, and added to bus b's send
+    timeline by a plain f32 add, for every bus and every voice (score_chain_sends).  Then -> (sums, send timelines [B, n_ch, n_total])."""
     gains = _gains_table(gains, len(rows), noun)
     if fracs is not None:
         fracs = check_fracs(fracs, len(rows))
     acc = _chain_start(init, n_ch, n_total)
+    send = None if sends is None else np.zeros((len(sends), n_ch, n_total), dtype=np.float32)
     with np.errstate(all="ignore"):
         for k, row in enumerate(rows):
             onset, length = int(onsets[k]), int(lengths[k])
@@ -150,7 +154,11 @@ def _chain(rows, n_ch, n_total, onsets, lengths, gains, fracs, init, raw, noun="
             else:
                 for c in range(n_ch):
                     acc[c, t0:t1] = acc[c, t0:t1] + term[c]
-    return _chain_end(acc, raw)
+            if send is not None:  # (term: float32 [n_ch, t1 - t0], the very values added above)
+                for b in range(len(sends)):
+                    for c in range(n_ch):
+                        send[b, c, t0:t1] = send[b, c, t0:t1] + term[c] * sends[b, k]  # one f32 product, one f32 add
+    return _chain_end(acc, raw) if send is None else (_chain_end(acc, raw), send)
 
 
 def check_fracs(fracs, n):
@@ -660,3 +668,104 @@ def master_chain(raw, render_channel):
             raise ValueError("dusp-hip: the master's render of channel %d must have shape (n_total=%d,)" % (c, raw.shape[1]))
         out[c] = y
     return out
+
+
+# ---- effect sends: per-voice levels into bus circuits beside the dry mix ----
+
+BUS_MAX = 4
+BUS_NOT_CALLABLE = "dusp-hip: bus %d is a function fx(x) of its send timeline, or a list of one function a channel of the timeline"
+BUS_CIRCUITS = "dusp-hip: bus %d lists %d circuits, the timeline has %d channels: one a channel"
+BUS_ONE_INPUT = "dusp-hip: bus %d, channel %d, holds %d MasterInput units: a bus reads its sends through exactly one, the one it is given"
+BUS_HOST_SOURCE = "dusp-hip: bus %d, channel %d, holds a HostSource: the send timeline is a bus's only input"
+BUS_EVENTS = "dusp-hip: bus %d, channel %d, has scheduled events: a bus is rendered in one piece"
+BUS_CHANNELS = "dusp-hip: bus %d, channel %d, has %d output channels: a bus is a mono circuit, applied to every channel by itself"
+BUS_NOT_ISOMORPHIC = "dusp-hip: the circuits of bus %d at channels 0 and %d are not isomorphic: they are one program and may differ in constants only"
+BUS_RATE = "dusp-hip: the sample rate of bus %d is %d, the voices' is %d"
+SENDS_WITHOUT_BUSES = "dusp-hip: sends without buses: a send level is what a voice gives to a bus"
+BUSES_WITHOUT_SENDS = "dusp-hip: buses without sends: every bus needs a send level a voice (sends of shape (buses, voices))"
+BUS_COUNT = "dusp-hip: a call has 1 .. 4 buses, not %d"
+SENDS_PLACEMENT = "dusp-hip: sends go with plain rows and with pans at whole-sample onsets: together with fracs, places or stereo they are refused"
+SENDS_SHAPE = "dusp-hip: sends must have shape (buses=%d, voices=%d)"
+SENDS_NOT_FINITE = "dusp-hip: the send level of voice %d into bus %d is not finite"
+
+
+def check_sends(sends, n, n_buses):
+    """the send levels of n voices into n_buses buses -> contiguous float32 [n_buses, n]: one finite level a bus and voice; a 1-D array
+    of n levels is accepted for one bus.  Refused by the strings the library uses: a number of buses outside 1 .. 4, another shape, a
+    level that is not finite as float32.  Needs no device."""
+    if not 1 <= n_buses <= BUS_MAX:
+        raise ValueError(BUS_COUNT % n_buses)
+    with np.errstate(all="ignore"):
+        sends = np.asarray(sends, dtype=np.float32)
+    if sends.ndim == 1 and n_buses == 1:
+        sends = sends.reshape(1, -1)
+    if sends.shape != (n_buses, n):
+        raise ValueError(SENDS_SHAPE % (n_buses, n))
+    sends = np.ascontiguousarray(sends)
+    if not np.all(np.isfinite(sends)):
+        b, k = np.argwhere(~np.isfinite(sends))[0]
+        raise ValueError(SENDS_NOT_FINITE % (int(k), int(b)))
+    return sends
+
+
+def refuse_sends_placement(fracs, places, stereo):
+    """what sends do not go with, refused on every surface before anything renders"""
+    if fracs is not None or places is not None or stereo:
+        raise ValueError(SENDS_PLACEMENT)
+
+
+def score_chain_sends(rows, onsets, n_total, sends, lengths=None, gains=None, pans=None, comp=None):
+    """The chain of a score or piece with effect sends: the contract of dusp_score_rows_send_device, needs no GPU.  rows, onsets,
+    lengths, gains: as score_chain_rows takes them, or — with pans (and comp) — as score_chain_rows_panned does (mono rows, two
+    channels); sends: float32 [B, voices], 1 <= B <= 4 (check_sends) -> (dry_raw float32 [C, n_total], send_raw float32 [B, C, n_total]).
+
+        dry[c][t]    : score_chain_rows / score_chain_rows_panned with raw=True, untouched
+        send_b[c][t] = +0; for k in index order, where voice k covers t:
+                           send_b = f32(send_b + f32(dry_term_k[c][t] * sends[b][k]))
+
+    dry_term_k[c][t] is exactly the f32 value the dry chain adds for voice k at channel c — the row's sample, f32(row * g_k), or the
+    Pan unit's two f32 values — so a send is post-fader and post-pan: Multiply(Multiply(Delay(v_k, onset_k), g_k), s_bk) in the
+    reference, for a panned voice behind its Pan.  The product and the add are plain f32 operations, each rounded by itself: the send
+    term is f32(f32(x * g) * s), never f32(x * (g * s)).
+
+    EVERY voice is in EVERY bus's chain: a level of 0 is a multiplication by 0, as the reference's would be, and there is no skipped
+    add — NaN * 0 poisons the bus where the voice sounds, and -x * 0 is -0.  Both timelines are raw: NaN, Inf and -0 kept."""
+    rows = [np.asarray(r, dtype=np.float32) for r in rows]
+    if sends is None:
+        raise ValueError(BUSES_WITHOUT_SENDS)
+    s = np.asarray(sends)
+    sends = check_sends(s, len(rows), 1 if s.ndim == 1 else s.shape[0])
+    if pans is not None:
+        dry = score_chain_rows_panned(rows, onsets, pans, n_total, lengths, gains, None, True, comp)  # (its checks, in its order)
+        pans = np.asarray(pans, dtype=np.float32)
+        comp = _comp_array(comp, len(rows), lambda: pan_comp(pans))
+        both = _chain(rows, 2, _timeline(n_total), _whole(onsets, len(rows), "onsets"), _row_lengths(rows, lengths), gains, None, None, True,
+                      place=lambda k, x: _pan_unit(x[0], pans[k], comp[k]), sends=sends)
+    else:
+        dry = score_chain_rows(rows, onsets, n_total, lengths, gains, None, True)
+        both = _chain(rows, dry.shape[0], _timeline(n_total), _whole(onsets, len(rows), "onsets"), _row_lengths(rows, lengths), gains, None, None, True, sends=sends)
+    assert dry.tobytes() == both[0].tobytes()  # (the dry half IS today's chain)
+    return dry, both[1]
+
+
+def bus_return(dry_raw, wets, raw=False):
+    """The return of the buses onto the dry mix: dry_raw float32 [C, n_total] (the raw dry timeline), wets a list of B float32
+    [C, n_total] (bus b's render over its raw send timeline: master_chain(send_raw[b], ...), `|| 0` applied at the bus's own copy-out)
+    -> float32 [C, n_total]:
+
+        mix = f32(...f32(f32(dry + wet_0) + wet_1)... + wet_{B-1})        (Sum.many([dry, wet_0, ...]): left-deep, one rounding an add)
+
+    and `mix || 0` unless raw (raw: what a master behind the buses reads).  One divergence from the reference's one circuit comes
+    from rendering a bus as a program of its own: where a bus's output is NaN its copy-out has made it 0 already, so the dry sample
+    survives, where the reference's final Sum would be NaN and leave as 0."""
+    dry_raw = np.asarray(dry_raw)
+    if dry_raw.dtype != np.float32 or dry_raw.ndim != 2:
+        raise ValueError("dusp-hip: the raw timeline is float32 of shape (channels, n_total)")
+    acc = dry_raw.copy()
+    with np.errstate(all="ignore"):
+        for b, wet in enumerate(wets):
+            wet = np.asarray(wet, dtype=np.float32)
+            if wet.shape != dry_raw.shape:
+                raise ValueError("dusp-hip: the output of bus %d must have shape (channels=%d, n_total=%d)" % ((b,) + dry_raw.shape))
+            acc = acc + wet
+    return _chain_end(acc, raw)

@@ -251,7 +251,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -274,12 +274,12 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     master: as render_piece's — the mix through a mono circuit, channel by channel, on the device; the piece's call with the score as
     its one part, as with pans."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends))
 
 
 def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master")):
+    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses")):
         return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
@@ -292,17 +292,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master), (bit_depth, normalise))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre, stereo, master), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), bit_depth)
 
 
 class PieceParts:
@@ -346,42 +346,60 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None):
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None):
     """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
     known.  The Space keywords are one thing too, None without places (the other three alone say nothing).  master: what the mix goes
-    through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it"""
-    return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master)
+    through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it;
+    buses, sends: the effect buses beside the mix and the voices' levels into them, which travel with it too.  What sends do not go
+    with is refused here, before anything else of the call is looked at"""
+    if buses is None and sends is not None:
+        raise ValueError(mix.SENDS_WITHOUT_BUSES)
+    if buses is not None:
+        if sends is None:
+            raise ValueError(mix.BUSES_WITHOUT_SENDS)
+        if fracs is not None or places is not None or stereo:
+            raise ValueError(mix.SENDS_PLACEMENT)
+        if not isinstance(buses, (list, tuple)) or not 1 <= len(buses) <= mix.BUS_MAX:
+            raise ValueError(mix.BUS_COUNT % (len(buses) if isinstance(buses, (list, tuple)) else 0))
+    return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master,
+                buses=buses, sends=sends)
 
 
-def master_program(master, channels, sample_rate):
+def master_program(master, channels, sample_rate, bus=None):
     """The master of a score or piece -> descriptor.Unified of `channels` instances, one a channel of the timeline; needs no device.
     master: a callable fx(x), called once per channel with a fresh graph.MasterInput and returning the master's outlet, or a list of one
     callable a channel (an echo of another length left and right).  The circuits are extracted and unified: they are isomorphic, what
     differs between them is constants, which become the program's parameter table [n_params][channels].  Refused by string: a master
     that is not callable, a list of the wrong length, a circuit that holds no or several MasterInput, a HostSource or a scheduled
-    event, one with more than one output channel, circuits that are not isomorphic."""
+    event, one with more than one output channel, circuits that are not isomorphic.
+    bus (None: a master): the circuit is bus number `bus` of the call's `buses=` — what a master is to the mix it is to its send
+    timeline, given and checked alike, and refused by the BUS_* strings, which name it."""
     from . import graph
+
+    def refuse(name, *args):
+        raise descriptor.DuspError(getattr(mix, "MASTER_" + name) % args if bus is None else getattr(mix, "BUS_" + name) % ((bus,) + args))
+
     fxs = list(master) if isinstance(master, (list, tuple)) else [master] * channels
     if not fxs or not all(callable(fx) for fx in fxs):
-        raise descriptor.DuspError(mix.MASTER_NOT_CALLABLE)
+        refuse("NOT_CALLABLE")
     if len(fxs) != channels:
-        raise descriptor.DuspError(mix.MASTER_COUNT % (len(fxs), channels))
+        refuse("COUNT" if bus is None else "CIRCUITS", len(fxs), channels)
     extractions = []
     for c, fx in enumerate(fxs):
         ex = descriptor.extract(fx(graph.MasterInput()), allow_events=True)
         if ex.circuit.events:
-            raise descriptor.DuspError(mix.MASTER_EVENTS % c)
+            refuse("EVENTS", c)
         if any(not getattr(src, "isMasterInput", False) for src in ex.sources):
-            raise descriptor.DuspError(mix.MASTER_HOST_SOURCE % c)
+            refuse("HOST_SOURCE", c)
         if len(ex.sources) != 1:
-            raise descriptor.DuspError(mix.MASTER_ONE_INPUT % (c, len(ex.sources)))
+            refuse("ONE_INPUT", c, len(ex.sources))
         if ex.sample_rate != sample_rate:
-            raise descriptor.DuspError(mix.MASTER_RATE % (ex.sample_rate, sample_rate))
+            refuse("RATE", ex.sample_rate, sample_rate)
         n_out = runtime.descriptor_channels(ex.words)
         if n_out != 1:
-            raise descriptor.DuspError(mix.MASTER_CHANNELS % (c, n_out))
+            refuse("CHANNELS", c, n_out)
         if c and structure_key(ex) != structure_key(extractions[0]):
-            raise descriptor.DuspError(mix.MASTER_NOT_ISOMORPHIC % c)
+            refuse("NOT_ISOMORPHIC", c)
         extractions.append(ex)
     return descriptor.unify(extractions)
 
@@ -392,6 +410,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     voices' sample rate, and parts whose channels do not fit the placement are refused (Placement.timeline_channels)."""
     placing = dict(placing)
     master = placing.pop("master", None)
+    buses, sends = placing.pop("buses", None), placing.pop("sends", None)
     mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
@@ -414,6 +433,10 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
         raise descriptor.DuspError("dusp-hip: the voices of a score are isomorphic circuits: a piece renders several instruments")
     channels = place.timeline_channels([runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts], grouped.part_of)
     place.master = None if master is None else master_program(master, channels, rate)  # (behind every other check of the call)
+    place.buses = place.sends = None  # (... and the buses, each a descriptor.Unified of one instance a channel, with the levels [buses, voices])
+    if buses is not None:
+        place.sends = mix.check_sends(sends, n, len(buses))
+        place.buses = [master_program(fx, channels, rate, bus=b) for b, fx in enumerate(buses)]
     return grouped, n_total, onsets, lengths, gains, channels, place
 
 
@@ -428,14 +451,19 @@ def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, devic
         if master is not None:
             programs.append(ctx.build(master.words, engine))
             master = (programs[-1], master.params)
-        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, master=master, **place.keywords())
+        buses = getattr(place, "buses", None)
+        if buses is not None:
+            programs.extend(ctx.build(bus.words, engine) for bus in buses)
+            buses = [(prog, bus.params) for prog, bus in zip(programs[-len(buses):], buses)]
+        return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, master=master, buses=buses,
+                                      sends=getattr(place, "sends", None), **place.keywords())
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -472,9 +500,17 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     over it, or a list of one callable a channel; the circuits are isomorphic and may differ in constants (master_program).  Channel c
     of the result is the render of the master over the timeline's channel c as the chain left it — before `|| 0`, as a unit behind
     Sum.many hears it — from the master's initial state (mix.master_chain; DESIGN.md 6.14 says where that is the reference's
-    `fx(Sum.many(...))` bit for bit and where it is not).  The call's engine is the master's too."""
+    `fx(Sum.many(...))` bit for bit and where it is not).  The call's engine is the master's too.
+
+    buses, sends: effect sends — some notes, at a level of their own, into an effect such as an echo, and its return beside the dry
+    mix.  buses is a list of 1 .. 4 circuits, each given as a master is (a callable fx(x) over a fresh MasterInput, or a list of one
+    a channel); sends is float32 [buses, voices] (one bus: [voices] will do), sends[b][k] what voice k gives to bus b.  Bus b hears
+    the chain of every voice's dry term — after its gain and its pan — times its level, is rendered over that timeline as a master is
+    over the mix, and the buses' outputs are added to the dry mix in order: Sum.many([dry, bus_0(...), bus_1(...), ...]), in front
+    of the master where there is one (mix.score_chain_sends, mix.master_chain, mix.bus_return).  A level of 0 is a
+    multiplication by 0, not a voice left out.  With plain voices and with pans; fracs, places and stereo are refused with sends."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master), _one_part)
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), _one_part)
 
 
 def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
@@ -487,17 +523,17 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master), _one_part, (bit_depth, normalise))
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends), bit_depth)
 
 
 class PcmData:

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import SPACE_ALONE, STEREO_NO_PLACES, Placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
+from .mix import BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -34,6 +34,7 @@ EXPORTS = [
     "dusp_score_rows_space_device", "dusp_render_host_score_parts_space",
     "dusp_score_rows_stereo_device", "dusp_render_host_score_parts_stereo",
     "dusp_render_host_score_piece",
+    "dusp_render_host_score_piece_buses", "dusp_score_rows_send_device", "dusp_score_return_device",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -114,6 +115,9 @@ def load():
     L.dusp_score_rows_stereo_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, ci, vp, vp]
     L.dusp_render_host_score_parts_stereo.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_render_host_score_piece.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    L.dusp_render_host_score_piece_buses.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    L.dusp_score_rows_send_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, sz, vp, ci, vp, vp, vp, vp]
+    L.dusp_score_return_device.argtypes = [vp, vp, vp, sz, sz, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -147,6 +151,11 @@ class ScorePlacement(ctypes.Structure):
 class ScoreMaster(ctypes.Structure):
     """dusp_score_master: the mono circuit a piece's mix goes through, and its parameter table [n_params][timeline channels]"""
     _fields_ = [("prog", ctypes.c_void_p), ("h_params", ctypes.c_void_p)]
+
+
+class ScoreBuses(ctypes.Structure):
+    """dusp_score_buses: the bus circuits of a piece, each given as a master is, and the voices' send levels f32 [n_buses][n_voices]"""
+    _fields_ = [("n_buses", ctypes.c_size_t), ("buses", ctypes.c_void_p), ("h_sends", ctypes.c_void_p)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -412,8 +421,30 @@ class Context:
         self._score_rows_call(rows, row_samples, onsets, lengths, placed, lambda n, rows, samples, onsets, lengths, channels, fracs, pans, comp: self._L.dusp_score_rows_stereo_device(
             self._h, rows, samples, _ptr(channels, n), n, onsets, _ptr(fracs, n), lengths, d_gains, _ptr(pans, n), _ptr(comp, n), n_total_samples, d_init, int(bool(raw)), d_out, stream))
 
+    def score_rows_send(self, rows, row_samples, n_channels, onsets, sends, n_total_samples, d_out, d_send_out, lengths=None, d_gains=None, d_init=None, d_send_init=None,
+                        raw=False, pans=None, comp=None, stream=None):
+        """score_rows_device — or, with pans, score_rows_pan (n_channels must be 1, the timelines have two) — with effect sends
+        (dusp_score_rows_send_device; dusp_amd/mix.py score_chain_sends is the contract): sends a HOST array of finite f32
+        [buses][voices], 1 .. 4 buses (one bus: [voices] will do); every term the dry chain adds also goes, times the voice's level,
+        to bus b's send timeline.  d_send_init (None: +0; may be d_send_out) and d_send_out: f32 [buses][C][n_total_samples], always
+        raw.  score_last_ms() reports the call."""
+        def placed(n):
+            a = np.asarray(sends)
+            levels = check_sends(a, n, 1 if a.ndim == 1 else a.shape[0])
+            return (levels,) + (pan_arrays(pans, n, comp) if pans is not None else (None, None))
+
+        self._score_rows_call(rows, row_samples, onsets, lengths, placed, lambda n, rows, samples, onsets, lengths, levels, pans, comp: self._L.dusp_score_rows_send_device(
+            self._h, rows, samples, n, n_channels, onsets, lengths, d_gains, _ptr(pans), _ptr(comp), levels.shape[0], _ptr(levels), n_total_samples, d_init, int(bool(raw)), d_out,
+            d_send_init, d_send_out, stream))
+
+    def score_return(self, d_dry, d_wets, n_floats, d_out, raw=False, stream=None):
+        """Device pointers: d_out[j] = d_dry[j] + d_wets[0][j] + ... over n_floats floats, left-deep with one f32 rounding an add, `|| 0`
+        unless raw (dusp_score_return_device; dusp_amd/mix.py bus_return is the contract).  d_wets: 1 .. 4 pointers; d_out may be d_dry."""
+        wets = (ctypes.c_void_p * max(len(d_wets), 1))(*d_wets)
+        self._check(self._L.dusp_score_return_device(self._h, d_dry, ctypes.addressof(wets), len(d_wets), n_floats, int(bool(raw)), d_out, stream))
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None, taps=None, stereo=False, master=None):
+                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -432,7 +463,18 @@ class Context:
         master = (program, params): the mix goes through that program before it is delivered (dusp_render_host_score_piece, the one
         entry that takes every placement above as a record; mix.master_chain is the contract) — a program of this context with ONE
         input stream and ONE output channel, channel c of the timeline instance c of it, params its table [n_params][timeline
-        channels] (None without parameters).  The library refuses what is no master, before anything renders."""
+        channels] (None without parameters).  The library refuses what is no master, before anything renders.
+        buses = [(program, params), ...] with sends, f32 [buses][voices]: effect sends (dusp_render_host_score_piece_buses;
+        mix.score_chain_sends, mix.master_chain and mix.bus_return are the contract) — 1 .. 4 programs, each what a master is; voice k
+        gives sends[b][k] of what it adds to the mix to bus b, every bus is rendered over its send timeline, and their outputs are
+        added to the dry mix in order, in front of the master where there is one.  With plain rows and with pans; fracs, taps and
+        stereo are refused together with sends."""
+        if buses is None and sends is not None:
+            raise ValueError(SENDS_WITHOUT_BUSES)
+        if buses is not None:
+            if sends is None:
+                raise ValueError(BUSES_WITHOUT_SENDS)
+            refuse_sends_placement(fracs, taps, stereo)
         Placement.refuse_together(pans, fracs, taps, stereo)
         if not parts:
             raise ValueError("dusp-hip: a piece has at least one part")
@@ -457,12 +499,28 @@ class Context:
             check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], place.pans)
         n_ch = place.channels(parts[0][0].n_out_channels)  # (parts that do not fit the placement: the library refuses them)
         voices = (table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data)
-        if master is not None:
-            prog, params = master
-            params = prog._params_table(params, n_ch, "dusp-hip: the params of the master must have shape")  # (n_instances: the timeline's channels)
+        if master is not None or buses is not None:
             how = ScorePlacement(PLACE_KINDS[place.kind], _ptr(place.fracs), _ptr(place.pans), _ptr(place.comp), n_ch if place.kind == "space" else 0,
                                  _ptr(place.taps[0]) if place.taps else None, _ptr(place.taps[1]) if place.taps else None)
-            through = ScoreMaster(prog._h, _ptr(params))
+            through = None
+            if master is not None:
+                prog, params = master
+                params = prog._params_table(params, n_ch, "dusp-hip: the params of the master must have shape")  # (n_instances: the timeline's channels)
+                through = ScoreMaster(prog._h, _ptr(params))
+        if buses is not None:
+            buses = list(buses)
+            levels = check_sends(sends, n, len(buses))
+            circuits = (ScoreMaster * len(buses))()
+            for b, (prog, params) in enumerate(buses):
+                keep.append(prog._params_table(params, n_ch, "dusp-hip: the params of bus %d must have shape" % b))
+                circuits[b] = ScoreMaster(prog._h, _ptr(keep[-1]))
+            into = ScoreBuses(len(buses), ctypes.addressof(circuits), levels.ctypes.data)
+            fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
+            self._check(self._L.dusp_render_host_score_piece_buses(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(into),
+                                                                   ctypes.addressof(through) if through is not None else None, n_total_samples, int(tile_bytes), fmt,
+                                                                   normalise, out.ctypes.data, _ptr(peak)))
+            return out if peak is None else (out, peak[0])
+        if master is not None:
             fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
             self._check(self._L.dusp_render_host_score_piece(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(through),
                                                              n_total_samples, int(tile_bytes), fmt, normalise, out.ctypes.data, _ptr(peak)))

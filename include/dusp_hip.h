@@ -603,6 +603,52 @@ int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, s
                                  const dusp_score_placement *placement, const dusp_score_master *master, size_t n_total_samples,
                                  size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak);
 
+/* Effect sends: per-voice send levels into bus circuits, on the device (additions to ABI v7, detected by symbol; DESIGN.md 6.15;
+ * dusp_amd/mix.py score_chain_sends, master_chain and bus_return are the contract).
+ *
+ * A BUS is what a master is — a program with one input stream and one output channel on the parts' context, instance c of it for
+ * channel c of the timeline, h_params [n_params][timeline channels] — and a call has 1 .. 4 of them.  h_sends[b][k] is what voice k
+ * gives to bus b, a finite f32.  Beside the dry chain, which is untouched, every tile's launch (score_send_engine.hip: the voice's row
+ * is read once) keeps one send timeline a bus:
+ *     send_b[c][t] = +0; for k in chain order, where voice k covers t: send_b = f32(send_b + f32(dry_term_k[c][t] * h_sends[b][k]))
+ * dry_term being the very f32 the dry chain adds (the row's sample, f32(row * g_k), or the Pan unit's two values: a send is post-fader
+ * and post-pan), the product and the add plain f32 operations.  EVERY voice is in EVERY bus's chain: a level of 0 is a multiplication
+ * by 0, so NaN * 0 poisons the bus and -x * 0 is -0.  After the last tile each bus is rendered over its RAW send timeline from its
+ * initial state, as a master is over the mix (`|| 0` at its own copy-out), and one launch returns them:
+ *     mix = f32(...f32(f32(dry + wet_0) + wet_1)... + wet_{B-1})      (Sum.many([dry, wet_0, ...]): left-deep, one rounding an add)
+ * delivered as `mix || 0`, or handed raw to the master, which works as in dusp_render_host_score_piece.  Where a bus's output is NaN
+ * its copy-out has made it 0 and the dry sample survives (the reference's final Sum would give NaN, delivered as 0).
+ * Device memory: B send timelines and B bus outputs of f32 [C][n_total_samples], beside the timeline (and the master's output).
+ *   buses   NULL: no buses, the call is dusp_render_host_score_piece (under this entry's name).
+ * Refused with a message before anything renders, beside what that call refuses: every rule of a master, per bus ("bus b"); a bus
+ * that is also a part, the master or another bus; n_buses outside 1 .. 4; NULL h_sends; a level that is not finite (bus and voice
+ * named); h_fracs, DUSP_PLACE_SPACE or DUSP_PLACE_STEREO together with buses (DUSP_ERR_UNSUPPORTED). */
+typedef struct dusp_score_buses {
+    size_t n_buses;                 /* 1 .. 4 */
+    const dusp_score_master *buses; /* [n_buses] */
+    const float *h_sends;           /* f32 [n_buses][n_voices], HOST memory, finite */
+} dusp_score_buses;
+int dusp_render_host_score_piece_buses(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                       const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                       const dusp_score_placement *placement, const dusp_score_buses *buses,
+                                       const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format,
+                                       int normalise, void *h_out, float *h_peak);
+/* The send chain alone: dusp_score_rows_device (h_pans NULL; rows of n_channels) or dusp_score_rows_pan_device (h_pans; n_channels
+ * must be 1, the timelines have two channels) with n_buses send timelines beside the dry one.  h_sends: f32 [n_buses][n_voices], HOST
+ * memory.  d_send_init (NULL: +0) and d_send_out: f32 [n_buses][C][n_total_samples], always raw; d_send_init may be d_send_out as
+ * d_init may be d_out.  The levels (16 bytes a voice) go up with the plan, on top of its byte budget; dusp_score_last_ms reports this
+ * call too.  Refused as dusp_score_rows_device refuses, and: n_buses outside 1 .. 4, NULL h_sends, a level that is not finite. */
+int dusp_score_rows_send_device(dusp_ctx *ctx, const float *const *h_rows, const uint32_t *h_row_samples, size_t n_voices,
+                                size_t n_channels, const int64_t *h_onsets, const int64_t *h_lengths, const float *d_gains,
+                                const float *h_pans, const double *h_comp, size_t n_buses, const float *h_sends,
+                                size_t n_total_samples, const float *d_init, int raw, float *d_out, const float *d_send_init,
+                                float *d_send_out, void *stream);
+/* The return of the buses alone: d_out[j] = f32(...f32(d_dry[j] + h_wets[0][j])... + h_wets[n_buses - 1][j]) over n_floats floats
+ * (1 .. 2^31), `|| 0` unless raw.  h_wets: a HOST array of n_buses device addresses.  d_out may be d_dry.  Four floats a lane where
+ * every buffer is on a 16-byte boundary, one a lane otherwise.  dusp_score_last_ms reports this call too. */
+int dusp_score_return_device(dusp_ctx *ctx, const float *d_dry, const float *const *h_wets, size_t n_buses, size_t n_floats, int raw,
+                             float *d_out, void *stream);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

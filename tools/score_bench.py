@@ -31,6 +31,11 @@
           Context.render_score_parts without a master and with a Clip master, an echo master and a Filter master
           (dusp_render_host_score_piece): the call on the host's clock, and the master's render alone
           (dusp_last_kernel_ms on the master program).  A report: no ratio is fixed in advance.
+  sends   (--sends; profiles/score_sends.txt) the same piece's notes, rendered once into device rows, one channel and panned: the
+          send kernel (dusp_score_rows_send_device) at 1, 2 and 4 buses against the rows (resp. pan) kernel with
+          gains over the same plan — launched once, the floor: what the dry chain alone costs; and 1 + B times into distinct
+          buffers, what reading every row once is meant to beat.  The return kernel against dusp_fill_device.  The whole call on
+          the host's clock with an echo bus and without.  A report: no ratio is fixed in advance.
 
 Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
 """
@@ -354,6 +359,88 @@ def master(scale, ctxs, reps):
     prog.close()
 
 
+def sends(scale, ctxs, reps):
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
+    d.configure(SR)
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    ctx = ctxs["default"]
+    prog = ctx.build(uni.words)
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    rows = torch.empty((V, 1, nv), dtype=torch.float32, device="cuda")
+    dp = torch.from_numpy(params).cuda()
+    prog.render_device(nv, V, dp.data_ptr(), rows.data_ptr(), s)
+    torch.cuda.synchronize()
+    pointers, samples = [rows.data_ptr() + 4 * nv * k for k in range(V)], np.full(V, nv, dtype=np.uint32)
+    rs = np.random.RandomState(3)
+    d_gains = torch.from_numpy((0.05 + 1.9 * rs.random_sample(V)).astype(np.float32)).cuda()
+    pans = (rs.random_sample(V) * 2 - 1).astype(np.float32)
+    levels = rs.random_sample((4, V)).astype(np.float32)
+
+    def median_of(call, launches=1):
+        kernel = []
+        for r in range(reps + 1):
+            total = 0.0
+            for i in range(launches):
+                call(i)
+                total += ctx.score_last_ms()[0]
+            if r:
+                kernel.append(total)
+        return float(np.median(kernel)), min(kernel)
+
+    print("sends: %d notes of %d samples over %d samples (%.0f MB of notes, %.1f MB a timeline and channel), kernels alone by HIP events (dusp_score_last_ms), median and fastest of %d after a warm-up"
+          % (V, nv, nt, V * nv * 4 / 1e6, nt * 4 / 1e6, reps), flush=True)
+    line = "  %-58s median %8.3f ms  fastest %8.3f%s"
+    for label, C, pan in (("rows, one channel", 1, None), ("panned, two channels", 2, pans)):
+        bufs = [torch.zeros((C, nt), dtype=torch.float32, device="cuda") for _ in range(5)]
+        snd = torch.zeros((4, C, nt), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        if pan is None:
+            old = lambda i: ctx.score_rows_device(pointers, samples, 1, onsets, nt, bufs[i].data_ptr(), d_gains=d_gains.data_ptr(), raw=True, stream=s)
+        else:
+            old = lambda i: ctx.score_rows_pan(pointers, samples, onsets, pan, nt, bufs[i].data_ptr(), d_gains=d_gains.data_ptr(), raw=True, stream=s)
+        floor = median_of(old)
+        print(line % ((label + ": the kernel that stands, with gains, once (the floor)",) + floor + ("",)), flush=True)
+        for B in (1, 2, 4):
+            again = median_of(old, 1 + B)
+            fused = median_of(lambda i: ctx.score_rows_send(pointers, samples, 1, onsets, levels[:B], nt, bufs[0].data_ptr(), snd.data_ptr(), d_gains=d_gains.data_ptr(), raw=True,
+                                                            pans=pan, stream=s))
+            print(line % ((label + ": the kernel that stands, %d launches into distinct buffers" % (1 + B),) + again + ("",)), flush=True)
+            print(line % ((label + ": the send kernel, B = %d" % B,) + fused + ("   x%.2f of the floor, x%.2f of %d launches" % (fused[0] / floor[0], fused[0] / again[0], 1 + B),)), flush=True)
+        n = C * nt
+        for B in (1, 2, 4):
+            back = median_of(lambda i: ctx.score_return(bufs[0].data_ptr(), [snd.data_ptr() + 4 * n * b for b in range(B)], n, bufs[1].data_ptr(), stream=s))
+            print(line % ((label + ": the return kernel, B = %d (%.0f MB read, %.0f MB written)" % (B, (1 + B) * n * 4 / 1e6, n * 4 / 1e6),) + back + ("",)), flush=True)
+        med, best = timed(lambda: ctx.fill(bufs[1].data_ptr(), n, 0.0, s), stream, reps)
+        print(line % (label + ": dusp_fill_device over %.0f MB" % (n * 4 / 1e6), med, best, ""), flush=True)
+        del bufs, snd
+    del rows
+
+    def echo(x):
+        e = d.Sum(x, 0)
+        e.B = d.Multiply(d.Delay(e, 300.25, 2048), 0.5)
+        return e
+
+    bus = ctx.build(descriptor.extract(echo(d.MasterInput())).words)
+    for label, kw in (("no buses", {}), ("one echo bus, 300.25 samples", dict(buses=[(bus, None)], sends=levels[:1]))):
+        times, kernel = [], []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, **kw)
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+            if kw:
+                kernel.append(bus.last_kernel_ms())
+        shape = "   bus render alone median %8.3f ms   [%s]" % (float(np.median(kernel[1:])), bus.read_shape()) if kw else ""
+        print("  render_score_parts, host clock, %-30s median %9.2f ms  fastest %9.2f%s" % (label, float(np.median(times[1:])), min(times[1:]), shape), flush=True)
+    bus.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -364,11 +451,14 @@ def main():
     ap.add_argument("--space", action="store_true", help="the Space-placement leg alone, over the dense cases named by --cases")
     ap.add_argument("--stereo", action="store_true", help="the stereo-piece leg alone, over the dense cases named by --cases")
     ap.add_argument("--master", action="store_true", help="the master-bus leg alone: the piece with and without a master")
+    ap.add_argument("--sends", action="store_true", help="the effect-send leg alone: the send and return kernels, and the piece with and without a bus")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
     if a.master:
         return master(a.scale, ctxs, a.reps)
+    if a.sends:
+        return sends(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
