@@ -68,6 +68,8 @@ hipError_t launch_score_send(const float *d_gains, const ScoreSend *d_sends, con
                              const uint32_t *d_entries, const float *d_init, float *d_out, const float *d_send_init, float *d_send_out, uint32_t n_buses, uint32_t n_channels,
                              uint64_t n_total, uint64_t w_lo, uint64_t w_hi, uint32_t block_shift, uint64_t first_block, int raw, bool pan, hipStream_t stream);
 hipError_t launch_score_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, uint64_t n, int raw, hipStream_t stream);
+hipError_t launch_score_tracks(const float *d_direct, const float *const *d_tracks, const float *h_faders, const float *h_levels, uint32_t n_tracks, uint32_t n_buses,
+                               float *d_out, const float *d_feed_init, float *d_feed_out, uint64_t n, int raw, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -177,6 +179,7 @@ struct dusp_workspaces {
     DevBuf<float> d_host_peaks;                                      // ... and the instances' peaks
     DevBuf<float> d_mix, d_mix_gains;                                // dusp_render_host_mix: the running sums [n_out_channels][n_samples]; one tile's gains
     DevBuf<float> d_mix_sends;                                       // a piece with buses: the send timelines [n_buses][n_out_channels][n_total] (abi_score.hip)
+    DevBuf<float> d_mix_tracks;                                      // a piece with tracks: the track timelines [n_tracks][n_out_channels][n_total], in the order of the track programs (abi_score.hip)
     DevBuf<float> d_saved_bufs, d_rings_wave;  // wave engine, resumable: outlets' last chunk; rings parked during a migration
     // WAVE programs the circuit compiler takes (jit_codegen.hpp): the generated text's constants
     DevBuf<float> d_jit_fk;
@@ -188,7 +191,7 @@ struct dusp_workspaces {
     DevBuf<float> d_handoff_out;     // the two parts' PCM before they are put side by side
     DevBuf<int64_t> d_jit_regime;  // per-instance delays: [slot, ring length, mono] per unit, then the verdicts (render_jit)
 
-    static constexpr size_t kCount = 29;
+    static constexpr size_t kCount = 30;
 
     template <class F>
     void for_each_workspace(F &&f) {  // f(name, buffer); buffers that share a name are reported together
@@ -208,6 +211,7 @@ struct dusp_workspaces {
         f("mix sums / gains", d_mix);
         f("mix sums / gains", d_mix_gains);
         f("send timelines", d_mix_sends);
+        f("track timelines", d_mix_tracks);
         f("staging parameters", d_host_par);
         f("staging inputs", d_host_in);
         f("hand-off buffers", d_handoff_init);

@@ -3,7 +3,8 @@
 // dusp_score_rows_device and its pan, frac, space and stereo forms) and the host round trips (dusp_render_host_score;
 // dusp_render_host_score_parts and its pan, frac, space and stereo forms; dusp_render_host_score_piece, which is all of them and takes
 // the master of a piece; dusp_render_host_score_piece_buses, which adds effect sends: per-voice levels into bus circuits, DESIGN.md 6.15,
-// with the device entries dusp_score_rows_send_device and dusp_score_return_device).
+// with the device entries dusp_score_rows_send_device and dusp_score_return_device; dusp_render_host_score_piece_tracks, which adds
+// tracks: sub-mixes of the piece through circuits of their own, DESIGN.md 6.16, with the device entry dusp_score_tracks_mix_device).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -23,6 +24,12 @@ enum class ScoreKind { contiguous, rows, pan, space, stereo };
 
 // What places the voices of a rows call: its kind and the host arrays that go with it, one entry a voice, which the caller owns.  An
 // entry fills one in (nothing but the kind set: plain rows) and everything between it and the launch takes it by reference.
+struct ScoreGathered {  // what a gathered placement points into
+    std::vector<double> fracs, comp, delays, tap_gains;
+    std::vector<float> pans;
+    std::vector<uint32_t> row_channels;
+};
+
 struct ScorePlacement {
     ScoreKind kind;                    // what the call is, whether or not it has voices: the entry says it, once
     const double *h_fracs = nullptr;   // rows, pan, stereo: the voices' fractions of a sample (NULL: none)
@@ -48,6 +55,25 @@ struct ScorePlacement {
         if (h_tap_gains) t.h_tap_gains += lo * n_speakers;
         if (h_row_channels) t.h_row_channels += lo;
         if (h_sends) t.h_sends += lo;
+        return t;
+    }
+    // the same placement for the n voices which[0], which[1], ... alone (a track's of a tile), its arrays copied into `into`; a call
+    // with tracks has no per-voice levels (h_sends)
+    ScorePlacement gather(const size_t *which, size_t n, ScoreGathered &into) const {
+        ScorePlacement t = *this;
+        auto take = [&](auto &v, const auto *&h, size_t width) {
+            if (!h) return;
+            v.resize(n * width);
+            for (size_t k = 0; k < n; k++)
+                for (size_t c = 0; c < width; c++) v[k * width + c] = h[which[k] * width + c];
+            h = v.data();
+        };
+        take(into.fracs, t.h_fracs, 1);
+        take(into.pans, t.h_pans, 1);
+        take(into.comp, t.h_comp, 1);
+        take(into.delays, t.h_delays, n_speakers);
+        take(into.tap_gains, t.h_tap_gains, n_speakers);
+        take(into.row_channels, t.h_row_channels, 1);
         return t;
     }
 
@@ -209,7 +235,7 @@ static void score_pans_add(dusp_ctx *ctx, const ScorePlacement &place, size_t n,
 // else the image and the launch are as without.  Behind them the pan coefficients, where the call has pans (score_pans_add).
 static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onsets, const int64_t *h_lengths, const uint32_t *row_samples, const uint64_t *rows, size_t n,
                           size_t first_voice, uint64_t n_total, bool whole_timeline, size_t budget_bytes, const ScorePlacement &place, ScoreLaunch &L,
-                          std::vector<unsigned char> *listed) {
+                          std::vector<unsigned char> *listed, const size_t *voice_ids = nullptr) {  // (voice_ids: gathered voices' own numbers, for the refusal)
     const bool taps = place.kind == ScoreKind::space;
     const double *h_fracs = place.h_fracs;
     dusp::ScoreRowsPlan P;
@@ -221,8 +247,8 @@ static int score_rows_add(dusp_ctx *ctx, const char *who, const int64_t *h_onset
     const dusp::ScorePlacing by{h_fracs, taps ? T.data() : nullptr, place.n_speakers, place.h_row_channels, place.h_pans};  // (row_channels with pans: every voice's kind)
     const int64_t bad = dusp::score_rows_plan(h_onsets, h_lengths, row_samples, rows, n, n_total, whole_timeline, budget_bytes, P, by);
     if (bad >= 0)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(first_voice + (size_t)bad) + " is " + std::to_string(h_lengths[bad]) +
-                                        ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
+        CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the length of voice " + std::to_string(voice_ids ? voice_ids[bad] : first_voice + (size_t)bad) + " is " +
+                                        std::to_string(h_lengths[bad]) + ": lengths must lie in 0 .. the voice's own row samples (" + std::to_string(row_samples[bad]) + ")");
     score_image_add(ctx, P, n, L);
     if (taps && L.any) L.space_at = score_image_append<dusp::ScoreSpaceTap>(ctx, T.size(), [&](size_t j) { return T[j]; });
     for (size_t k = 0; k < n && L.any && !L.frac && !taps; k++) L.frac = P.voices[k].hi > P.voices[k].lo && P.voices[k].pad != 0;
@@ -345,16 +371,15 @@ static int score_deliver_host(dusp_program *prog, const char *who, ScoreKind kin
 // What a piece's master is held to before anything renders; n_ch: the timeline's channels, each an instance of the master.  A bus is
 // held to the same rules in the same words but for the noun: the = "bus 2", a = "a bus" (a master: "the master", "a master")
 static int score_master_check(dusp_ctx *ctx, const std::string &w, const dusp_score_master *master, const dusp_score_part *parts, size_t n_parts, size_t n_ch, size_t n_total,
-                              const std::string &the = "the master", const std::string &a = "a master") {
+                              const std::string &the = "the master", const std::string &a = "a master", const std::string &heard = "") {  // (heard: whose timeline it reads, "send " for a bus, "track " for a track program)
     dusp_program *m = master->prog;
-    const bool bus = a != "a master";
     if (!m) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + "'s program is NULL");
     if (m->ctx != ctx) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " was built on another context: it shares the one of the piece's parts");
     for (size_t p = 0; p < n_parts; p++)
         if (parts[p].prog == m)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " is also part " + std::to_string(p) + ": its buffers would be used twice; build it on its own");
     if (m->P.g.n_inputs != 1)
-        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + a + " reads exactly one input stream (the " + (bus ? "send " : "") + "timeline's channel), this program has " + std::to_string(m->P.g.n_inputs));
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + a + " reads exactly one input stream (the " + heard + "timeline's channel), this program has " + std::to_string(m->P.g.n_inputs));
     if (m->P.out_bufs.size() != 1)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + a + " has one output channel, this program has " + std::to_string(m->P.out_bufs.size()) +
                                         ": it is applied to every channel of the timeline by itself");
@@ -369,12 +394,16 @@ static int score_master_check(dusp_ctx *ctx, const std::string &w, const dusp_sc
 // What the buses of a piece are held to before anything renders: their number and levels (and what sends do not go with), every
 // rule of a master per bus, and a bus that is also the master or another bus
 static int score_buses_check(dusp_ctx *ctx, const std::string &w, const dusp_score_buses *buses, const ScorePlacement &place, size_t n_voices, const dusp_score_part *parts,
-                             size_t n_parts, const dusp_score_master *master, size_t n_ch, size_t n_total) {
-    if (int rc = place.check_sends(ctx, w.c_str(), n_voices)) return rc;
+                             size_t n_parts, const dusp_score_master *master, size_t n_ch, size_t n_total, bool voice_levels = true) {
+    if (voice_levels) {
+        if (int rc = place.check_sends(ctx, w.c_str(), n_voices)) return rc;
+    } else if (buses->n_buses < 1 || buses->n_buses > dusp::kScoreBusMax) {  // (a call with tracks: the levels are the tracks', score_tracks_check)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 1 .. 4 buses, not " + std::to_string(buses->n_buses));
+    }
     if (!buses->buses) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buses' programs are NULL");
     for (size_t b = 0; b < buses->n_buses; b++) {
         const std::string the = "bus " + std::to_string(b);
-        if (int rc = score_master_check(ctx, w, &buses->buses[b], parts, n_parts, n_ch, n_total, the, "a bus")) return rc;
+        if (int rc = score_master_check(ctx, w, &buses->buses[b], parts, n_parts, n_ch, n_total, the, "a bus", "send ")) return rc;
         if (master && master->prog == buses->buses[b].prog)
             CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " is also the master: its buffers would be used twice; build it on its own");
         for (size_t q = 0; q < b; q++)
@@ -408,6 +437,96 @@ static int score_buses_guards(dusp_program *prog, const char *who, const dusp_sc
         CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
     for (size_t b = 0; b < buses->n_buses; b++)
         if (int rc = check_guards(buses->buses[b].prog, ctx->stream)) return rc;
+    return DUSP_OK;
+}
+
+// ---- the tracks of a piece: sub-mixes through circuits of their own (dusp_amd/mix.py track_mix) ----
+
+// What the tracks of a piece are held to before anything renders: their number, where every voice goes, the faders and levels, what
+// tracks do not go with, every rule of a master per track program ("track program p"), a program that is used twice, and the tracks
+// every program lists.  slot_of[g]: where track g's timeline lies in d_mix_tracks — the tracks of one program adjacent, in the
+// program's order, the tracks without a circuit behind them
+static int score_tracks_check(dusp_ctx *ctx, const std::string &w, const dusp_score_tracks *tracks, const dusp_score_buses *buses, size_t n_voices, const dusp_score_part *parts,
+                              size_t n_parts, const dusp_score_master *master, size_t n_ch, size_t n_total, std::vector<size_t> &slot_of) {
+    const size_t T = tracks->n_tracks;
+    if (T < 1 || T > dusp::kScoreTrackMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 1 .. 8 tracks, not " + std::to_string(T));
+    if (!tracks->h_track_of) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the tracks' h_track_of is NULL: every voice goes to a track or, with -1, straight to the mix");
+    for (size_t k = 0; k < n_voices; k++)
+        if (tracks->h_track_of[k] < -1 || tracks->h_track_of[k] >= (int64_t)T)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": voice " + std::to_string(k) + " names track " + std::to_string(tracks->h_track_of[k]) + " of " + std::to_string(T) +
+                                            ": track_of holds -1 (straight to the mix) or a track, 0 .. " + std::to_string(T - 1));
+    for (size_t g = 0; tracks->h_faders && g < T; g++)
+        if (!std::isfinite(tracks->h_faders[g])) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the fader of track " + std::to_string(g) + " is not finite");
+    if (tracks->h_track_sends && !buses) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": track_sends without buses: a level is what a track gives to a bus");
+    if (buses && !tracks->h_track_sends)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": buses without track_sends: with tracks every bus needs a level a track (track_sends of shape (buses, tracks))");
+    if (buses && buses->h_sends)
+        CTX_FAIL(ctx, DUSP_ERR_UNSUPPORTED, w + ": sends and tracks do not go together: with tracks the buses are fed by track_sends, a level a track");
+    for (size_t b = 0; buses && b < buses->n_buses; b++)
+        for (size_t g = 0; g < T; g++)
+            if (!std::isfinite(tracks->h_track_sends[b * T + g]))
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the level of track " + std::to_string(g) + " into bus " + std::to_string(b) + " is not finite");
+    if (tracks->n_programs > T) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + std::to_string(tracks->n_programs) + " track programs for " + std::to_string(T) + " tracks: a program serves at least one track");
+    if (tracks->n_programs && !tracks->programs) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the tracks' programs are NULL");
+    slot_of.assign(T, T);
+    size_t slot = 0;
+    for (size_t p = 0; p < tracks->n_programs; p++) {
+        const dusp_score_track_program &tp = tracks->programs[p];
+        const std::string the = "track program " + std::to_string(p);
+        const dusp_score_master as_master{tp.prog, tp.h_params};
+        if (int rc = score_master_check(ctx, w, &as_master, parts, n_parts, n_ch, n_total, the, "a track program", "track ")) return rc;
+        if (master && master->prog == tp.prog) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " is also the master: its buffers would be used twice; build it on its own");
+        for (size_t b = 0; buses && b < buses->n_buses; b++)
+            if (buses->buses[b].prog == tp.prog)
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " is also bus " + std::to_string(b) + ": its buffers would be used twice; build it on its own");
+        for (size_t q = 0; q < p; q++)
+            if (tracks->programs[q].prog == tp.prog)
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": track programs " + std::to_string(q) + " and " + std::to_string(p) + " are the same program: its buffers would be used twice; build it twice");
+        if (tp.n_tracks < 1 || !tp.h_tracks) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " lists no tracks: a track program serves at least one");
+        for (size_t j = 0; j < tp.n_tracks; j++) {
+            const size_t g = tp.h_tracks[j];
+            if (g >= T) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " lists track " + std::to_string(g) + " of " + std::to_string(T));
+            if (slot_of[g] != T) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " lists track " + std::to_string(g) + ", which has a circuit already: a track goes through one");
+            slot_of[g] = slot++;
+        }
+        if (tp.n_tracks * n_ch * n_total > dusp::kScoreRowMax)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + the + " renders (tracks x channels) x timeline samples, which must not exceed 2^31: give tracks of one circuit programs of their own, or render such a piece in windows of the timeline");
+    }
+    for (size_t g = 0; g < T; g++)
+        if (slot_of[g] == T) slot_of[g] = slot++;
+    return DUSP_OK;
+}
+
+// What a host render with tracks does between its last tile and its buses: every track program rendered ONCE over the adjacent RAW
+// timelines of its tracks (d_mix_tracks: instance j * n_ch + c hears channel c of its j-th track) from its initial state into its own
+// d_host_out, as a master is (`|| 0` at its own copy-out); then ONE launch of the mix kernel: the direct timeline in d_mix and every
+// track's output — its program's, or its raw timeline where it has no circuit — times its fader, left-deep into d_mix in place, and
+// times its levels into the buses' feeds (d_mix_sends, from +0).  raw: buses or a master follow, which read the sums as they stand.
+static int score_tracks_mix(dusp_program *prog, const dusp_score_tracks *tracks, const dusp_score_buses *buses, const std::vector<size_t> &slot_of, size_t n_ch, size_t n_total,
+                            int raw, std::vector<std::unique_ptr<TiledBatch>> &rendered) {
+    dusp_ctx *ctx = prog->ctx;
+    const size_t row = n_ch * n_total;
+    const float *y[dusp::kScoreTrackMax] = {};
+    for (size_t g = 0; g < tracks->n_tracks; g++) y[g] = prog->d_mix_tracks.p + slot_of[g] * row;
+    for (size_t p = 0; p < tracks->n_programs; p++) {
+        const dusp_score_track_program &tp = tracks->programs[p];
+        const size_t n_inst = tp.n_tracks * n_ch;
+        rendered.emplace_back(new TiledBatch(tp.prog, n_inst, tp.h_params, nullptr, n_inst));  // (one tile: every track and channel)
+        if (int rc = rendered.back()->render_tile(0, n_inst, n_total, prog->d_mix_tracks.p + slot_of[tp.h_tracks[0]] * row)) return rc;
+        for (size_t j = 0; j < tp.n_tracks; j++) y[tp.h_tracks[j]] = tp.prog->d_host_out.p + j * row;
+    }
+    HIP_TRY(ctx, dusp::launch_score_tracks(prog->d_mix.p, y, tracks->h_faders, tracks->h_track_sends, (uint32_t)tracks->n_tracks, buses ? (uint32_t)buses->n_buses : 0u, prog->d_mix.p,
+                                           nullptr, buses ? prog->d_mix_sends.p : nullptr, (uint64_t)row, raw, ctx->stream));
+    return DUSP_OK;
+}
+
+// ... and what it ends with behind its delivery: the guard bytes of the track timelines, and every track program's own
+static int score_tracks_guards(dusp_program *prog, const char *who, const dusp_score_tracks *tracks) {
+    dusp_ctx *ctx = prog->ctx;
+    if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_tracks.intact() || !prog->d_mix_sends.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
+    for (size_t p = 0; p < tracks->n_programs; p++)
+        if (int rc = check_guards(tracks->programs[p].prog, ctx->stream)) return rc;
     return DUSP_OK;
 }
 
@@ -590,7 +709,8 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
 // input stream, rendered over every channel of the raw timeline before the delivery (score_master_deliver_host)
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const ScorePlacement &given, size_t n_total_samples, size_t tile_bytes, int format,
-                                   int normalise, void *h_out, float *h_peak, const dusp_score_master *master = nullptr, const dusp_score_buses *buses = nullptr) {
+                                   int normalise, void *h_out, float *h_peak, const dusp_score_master *master = nullptr, const dusp_score_buses *buses = nullptr,
+                                   const dusp_score_tracks *tracks = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
@@ -598,7 +718,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     const std::string w(who);
     const size_t n_ch = prog0->P.out_bufs.size();  // (a voice's)
     ScorePlacement place = given;
-    if (buses) {  // (the levels travel with the placement: a tile's are its voices')
+    if (buses && !tracks) {  // (the levels travel with the placement: a tile's are its voices'; with tracks the levels are the tracks')
         place.n_buses = buses->n_buses;
         place.sends_stride = n_voices;
         place.h_sends = buses->h_sends;
@@ -633,7 +753,10 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     if (master)
         if (int rc = score_master_check(ctx, w, master, parts, n_parts, n_out_ch, n_total_samples)) return rc;
     if (buses)
-        if (int rc = score_buses_check(ctx, w, buses, place, n_voices, parts, n_parts, master, n_out_ch, n_total_samples)) return rc;
+        if (int rc = score_buses_check(ctx, w, buses, place, n_voices, parts, n_parts, master, n_out_ch, n_total_samples, /*voice_levels=*/!tracks)) return rc;
+    std::vector<size_t> slot_of;  // (with tracks: where track g's timeline lies in d_mix_tracks)
+    if (tracks)
+        if (int rc = score_tracks_check(ctx, w, tracks, buses, n_voices, parts, n_parts, master, n_out_ch, n_total_samples, slot_of)) return rc;
     if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
     if (int rc = place.check_values(ctx, who, n_voices)) return rc;
@@ -687,80 +810,151 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         if (int rc = tiled_batch_prepare(parts[p].prog, who, parts[p].n_instances, parts[p].n_voice_samples, parts[p].h_params, nullptr, most, format, normalise, h_out, &unused)) return rc;
     }
     // every tile's plan, over the tile's union window, made up front under the call's one budget and uploaded once: the rows' addresses
-    // are known, since the tile buffers stand
-    std::vector<ScoreLaunch> launches(n_tiles, ScoreLaunch(place.kind));
+    // are known, since the tile buffers stand.  With tracks a tile has one plan a DESTINATION that has voices in it — the direct
+    // timeline (0) and every track's (1 + g) — over that destination's voices alone, gathered; tiles ascend, so every destination's
+    // chain is in index order.  first_launch[i] .. first_launch[i + 1]: tile i's launches
+    struct TileLaunch {
+        ScoreLaunch L;
+        size_t dest, gains_at;  // which timeline; where its voices' gains begin in d_mix_gains
+    };
+    std::vector<TileLaunch> launches;
+    std::vector<size_t> first_launch(n_tiles + 1, 0);
+    std::vector<std::vector<size_t>> members;  // (with tracks: the voices of every launch, by their numbers in the call)
+    if (tracks)
+        for (size_t i = 0; i < n_tiles; i++) {
+            for (size_t dest = 0; dest <= tracks->n_tracks; dest++) {
+                std::vector<size_t> which;
+                for (size_t k = starts[i]; k < starts[i + 1]; k++)
+                    if ((size_t)(tracks->h_track_of[k] + 1) == dest) which.push_back(k);
+                if (which.empty()) continue;
+                launches.push_back(TileLaunch{ScoreLaunch(place.kind), dest, 0});
+                members.push_back(std::move(which));
+            }
+            first_launch[i + 1] = launches.size();
+        }
+    else
+        for (size_t i = 0; i < n_tiles; i++) {
+            launches.push_back(TileLaunch{ScoreLaunch(place.kind), 0, starts[i]});
+            first_launch[i + 1] = launches.size();
+        }
     std::vector<std::vector<unsigned char>> renders(n_tiles, std::vector<unsigned char>(n_parts, 0));  // does part p render in tile i?
+    std::vector<float> ordered_gains;  // (with tracks: the gains in launch order, uploaded once)
+    // (the call's one budget, shared out over the tiles; with tracks a tile's share is shared out over its launches by their voices)
     const size_t tile_budget = score_plan_budget(ctx) / n_tiles;
     if (int rc = score_image_begin(ctx)) return rc;
     const auto t_plan = std::chrono::steady_clock::now();
     {
         std::vector<uint64_t> rows;
         std::vector<unsigned char> listed;
-        for (size_t i = 0; i < n_tiles; i++) {
+        auto row_of = [&](size_t i, size_t k) {  // voice k, of tile i, in its part's tile buffer
+            const size_t p = h_part_of[k];
+            return (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[k] - share[p][i]) * part_ch[p] * parts[p].n_voice_samples);
+        };
+        for (size_t i = 0; i < n_tiles && !tracks; i++) {
             const size_t lo = starts[i], n = starts[i + 1] - lo;
             rows.resize(n);
-            for (size_t k = 0; k < n; k++) {
-                const size_t p = h_part_of[lo + k];
-                rows[k] = (uint64_t)(uintptr_t)(parts[p].prog->d_host_out.p + (instance_of[lo + k] - share[p][i]) * part_ch[p] * parts[p].n_voice_samples);
-            }
+            for (size_t k = 0; k < n; k++) rows[k] = row_of(i, lo + k);
             if (int rc = score_rows_add(ctx, who, h_onsets + lo, h_lengths ? h_lengths + lo : nullptr, row_samples.data() + lo, rows.data(), n, lo, n_total_samples,
-                                        /*whole_timeline=*/false, tile_budget, place.tile(lo), launches[i], &listed))
+                                        /*whole_timeline=*/false, tile_budget, place.tile(lo), launches[i].L, &listed))
                 return rc;
             for (size_t k = 0; k < n; k++)
                 if (listed[k]) renders[i][h_part_of[lo + k]] = 1;
         }
+        std::vector<int64_t> onsets, lengths;
+        std::vector<uint32_t> samples;
+        ScoreGathered gathered;
+        for (size_t i = 0; i < n_tiles && tracks; i++)
+            for (size_t j = first_launch[i]; j < first_launch[i + 1]; j++) {
+                const std::vector<size_t> &which = members[j];
+                const size_t n = which.size();
+                rows.resize(n);
+                onsets.resize(n);
+                lengths.resize(n);
+                samples.resize(n);
+                launches[j].gains_at = ordered_gains.size();
+                for (size_t k = 0; k < n; k++) {
+                    rows[k] = row_of(i, which[k]);
+                    onsets[k] = h_onsets[which[k]];
+                    if (h_lengths) lengths[k] = h_lengths[which[k]];
+                    samples[k] = row_samples[which[k]];
+                    if (h_gains) ordered_gains.push_back(h_gains[which[k]]);
+                }
+                if (int rc = score_rows_add(ctx, who, onsets.data(), h_lengths ? lengths.data() : nullptr, samples.data(), rows.data(), n, 0, n_total_samples,
+                                            /*whole_timeline=*/false, tile_budget * n / (starts[i + 1] - starts[i]), place.gather(which.data(), n, gathered), launches[j].L, &listed,
+                                            which.data()))
+                    return rc;
+                for (size_t k = 0; k < n; k++)
+                    if (listed[k]) renders[i][h_part_of[which[k]]] = 1;
+            }
     }
     if (ctx->knobs.jit_log >= 2)  // (DUSP_JIT_LOG=2: what the plans cost the host)
-        fprintf(stderr, "[dusp host piece] %zu plans over %zu voices of %zu parts in %.0f us on the host: %zu bytes\n", n_tiles, n_voices, n_parts,
+        fprintf(stderr, "[dusp host piece] %zu plans over %zu voices of %zu parts in %.0f us on the host: %zu bytes\n", launches.size(), n_voices, n_parts,
                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count(), ctx->h_score_plan.size());
-    HIP_TRY(ctx, prog0->d_mix.ensure(n_out_ch * n_total_samples));  // the timeline's running sums
+    const size_t timeline = n_out_ch * n_total_samples;
+    HIP_TRY(ctx, prog0->d_mix.ensure(timeline));  // the timeline's running sums
     if (master) {  // (... and what the master makes of them: one more [channels][n_total], and its columns)
-        HIP_TRY(ctx, master->prog->d_host_out.ensure(n_out_ch * n_total_samples));
+        HIP_TRY(ctx, master->prog->d_host_out.ensure(timeline));
         if (master->prog->P.g.n_params) HIP_TRY(ctx, master->prog->d_host_par.ensure((size_t)master->prog->P.g.n_params * n_out_ch));
     }
     if (buses) {  // (... the send timelines, and what every bus makes of its own: 2 x n_buses more [channels][n_total], and the buses' columns)
-        HIP_TRY(ctx, prog0->d_mix_sends.ensure(buses->n_buses * n_out_ch * n_total_samples));
+        HIP_TRY(ctx, prog0->d_mix_sends.ensure(buses->n_buses * timeline));
         for (size_t b = 0; b < buses->n_buses; b++) {
             dusp_program *bus = buses->buses[b].prog;
-            HIP_TRY(ctx, bus->d_host_out.ensure(n_out_ch * n_total_samples));
+            HIP_TRY(ctx, bus->d_host_out.ensure(timeline));
             if (bus->P.g.n_params) HIP_TRY(ctx, bus->d_host_par.ensure((size_t)bus->P.g.n_params * n_out_ch));
         }
     }
-    if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once)
+    if (tracks) {  // (... the tracks' timelines, and what every track program makes of its own: one [channels][n_total] a track each, and its columns)
+        HIP_TRY(ctx, prog0->d_mix_tracks.ensure(tracks->n_tracks * timeline));
+        for (size_t p = 0; p < tracks->n_programs; p++) {
+            const dusp_score_track_program &tp = tracks->programs[p];
+            HIP_TRY(ctx, tp.prog->d_host_out.ensure(tp.n_tracks * timeline));
+            if (tp.prog->P.g.n_params) HIP_TRY(ctx, tp.prog->d_host_par.ensure((size_t)tp.prog->P.g.n_params * tp.n_tracks * n_out_ch));
+        }
+    }
+    if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once; with tracks in launch order)
         HIP_TRY(ctx, prog0->d_mix_gains.ensure(n_voices));
-        HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, tracks ? ordered_gains.data() : h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
     if (int rc = score_image_upload(ctx, ctx->stream)) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix.p, 0, n_out_ch * n_total_samples * sizeof(float), ctx->stream));
-    float *d_sends = buses ? prog0->d_mix_sends.p : nullptr;
-    if (buses) HIP_TRY(ctx, hipMemsetAsync(d_sends, 0, buses->n_buses * n_out_ch * n_total_samples * sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix.p, 0, timeline * sizeof(float), ctx->stream));
+    float *d_sends = buses && !tracks ? prog0->d_mix_sends.p : nullptr;  // (with tracks the mix kernel writes the buses' feeds, from +0)
+    if (d_sends) HIP_TRY(ctx, hipMemsetAsync(d_sends, 0, buses->n_buses * timeline * sizeof(float), ctx->stream));
+    if (tracks) HIP_TRY(ctx, hipMemsetAsync(prog0->d_mix_tracks.p, 0, tracks->n_tracks * timeline * sizeof(float), ctx->stream));
     std::vector<std::unique_ptr<TiledBatch>> whole;  // what changes bits is decided from the WHOLE part
     for (size_t p = 0; p < n_parts; p++) whole.emplace_back(new TiledBatch(parts[p].prog, parts[p].n_instances, parts[p].h_params, share[p]));
     auto waited = [&]() {
         for (auto &b : whole) b->staged = false;
     };
     for (size_t i = 0; i < n_tiles; i++) {
-        if (launches[i].w_hi <= launches[i].w_lo) continue;  // (no voice of the tile reaches the timeline: nothing to render)
-        for (size_t p = 0; p < n_parts; p++)
+        for (size_t p = 0; p < n_parts; p++)  // (no voice of the tile reaches a timeline: nothing to render)
             if (renders[i][p])
                 if (int rc = whole[p]->render_tile(share[p][i], share[p][i + 1] - share[p][i], parts[p].n_voice_samples)) return rc;
-        const float *d_gains = h_gains ? prog0->d_mix_gains.p + starts[i] : nullptr;
-        if (int rc = score_launch(ctx, launches[i], n_out_ch, n_total_samples, d_gains, prog0->d_mix.p, /*raw=*/1, prog0->d_mix.p, ctx->stream, nullptr, 0, d_sends, d_sends))
-            return rc;
+        for (size_t j = first_launch[i]; j < first_launch[i + 1]; j++) {
+            if (launches[j].L.w_hi <= launches[j].L.w_lo) continue;
+            const float *d_gains = h_gains ? prog0->d_mix_gains.p + launches[j].gains_at : nullptr;
+            float *d_into = launches[j].dest ? prog0->d_mix_tracks.p + slot_of[launches[j].dest - 1] * timeline : prog0->d_mix.p;  // (in place and raw)
+            if (int rc = score_launch(ctx, launches[j].L, n_out_ch, n_total_samples, d_gains, d_into, /*raw=*/1, d_into, ctx->stream, nullptr, 0, d_sends, d_sends)) return rc;
+        }
     }
-    std::vector<std::unique_ptr<TiledBatch>> returned;  // (the buses' renders)
+    std::vector<std::unique_ptr<TiledBatch>> tracked, returned;  // (the track programs' renders, and the buses')
+    if (tracks)  // (raw where buses or a master follow; else the mix kernel applies the `|| 0` of the delivery)
+        if (int rc = score_tracks_mix(prog0, tracks, buses, slot_of, n_out_ch, n_total_samples, /*raw=*/buses != nullptr || master != nullptr, tracked)) return rc;
     if (buses)
         if (int rc = score_buses_return(prog0, buses, n_out_ch, n_total_samples, /*raw=*/master != nullptr, returned)) return rc;
     // (`|| 0` is the rows kernel's over the timeline's channels, panned or not; behind a master it is the master's own copy-out's; behind
-    // buses without a master the return kernel has applied it)
-    if (int rc = master  ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
-                 : buses ? deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
-                         : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out))
+    // buses without a master the return kernel has applied it, behind tracks without either the mix kernel)
+    if (int rc = master            ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
+                 : buses || tracks ? deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
+                                   : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out))
         return rc;
     waited();  // (the delivery has waited for the stream)
     for (auto &b : returned) b->staged = false;
+    for (auto &b : tracked) b->staged = false;
     if (buses)
         if (int rc = score_buses_guards(prog0, who, buses)) return rc;
+    if (tracks)
+        if (int rc = score_tracks_guards(prog0, who, tracks)) return rc;
     return DUSP_OK;
     });
 }
@@ -835,7 +1029,8 @@ int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_p
 // One entry for every placement, with or without a master and buses: the placement as a record (dusp_score_placement; NULL: plain rows)
 static int render_host_score_piece(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const dusp_score_placement *placement, const dusp_score_buses *buses,
-                                   const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
+                                   const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak,
+                                   const dusp_score_tracks *tracks = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_ctx *ctx = parts[0].prog->ctx;
     const dusp_score_placement plain{DUSP_PLACE_ROWS, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
@@ -857,7 +1052,7 @@ static int render_host_score_piece(const char *who, const dusp_score_part *parts
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the placement's kind must be DUSP_PLACE_ROWS (0), DUSP_PLACE_PAN (1), DUSP_PLACE_SPACE (2) or DUSP_PLACE_STEREO (3)");
     }
     return render_host_score_parts(who, parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, place, n_total_samples, tile_bytes, format, normalise, h_out, h_peak,
-                                   master, buses);
+                                   master, buses, tracks);
 }
 
 int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
@@ -873,6 +1068,14 @@ int dusp_render_host_score_piece_buses(const dusp_score_part *parts, size_t n_pa
                                        size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
     return render_host_score_piece("dusp_render_host_score_piece_buses", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, buses, master,
                                    n_total_samples, tile_bytes, format, normalise, h_out, h_peak);
+}
+
+// ... and with tracks (tracks NULL: dusp_render_host_score_piece_buses under this entry's name)
+int dusp_render_host_score_piece_tracks(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                        const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks, const dusp_score_buses *buses,
+                                        const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
+    return render_host_score_piece("dusp_render_host_score_piece_tracks", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, buses, master,
+                                   n_total_samples, tile_bytes, format, normalise, h_out, h_peak, tracks);
 }
 
 // The send chain alone (score_send_engine.hip): dusp_score_rows_device — h_pans: dusp_score_rows_pan_device, mono rows into two
@@ -912,6 +1115,41 @@ int dusp_score_return_device(dusp_ctx *ctx, const float *d_dry, const float *con
         ctx, stream, false, none, []() { return DUSP_OK; },
         [&]() {
             HIP_TRY(ctx, dusp::launch_score_return(d_dry, h_wets, (uint32_t)n_buses, d_out, n_floats, raw != 0, stream));
+            return DUSP_OK;
+        });
+    });
+}
+
+// The mix of the tracks alone (score_tracks_engine.hip): d_out = d_direct + the tracks' outputs times their faders, left-deep, `|| 0`
+// unless raw, and the buses' feeds [n_buses][n_floats] = d_feed_init (NULL: +0) + every term times its level
+int dusp_score_tracks_mix_device(dusp_ctx *ctx, const float *d_direct, const float *const *h_tracks, size_t n_tracks, const float *h_faders, size_t n_buses, const float *h_levels,
+                                 size_t n_floats, int raw, float *d_out, const float *d_feed_init, float *d_feed_out, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    const char *who = "dusp_score_tracks_mix_device";
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    if (n_tracks < 1 || n_tracks > dusp::kScoreTrackMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 1 .. 8 tracks, not " + std::to_string(n_tracks));
+    if (n_buses > dusp::kScoreBusMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 0 .. 4 buses, not " + std::to_string(n_buses));
+    if (!d_direct || !d_out || !h_tracks || (n_buses && (!h_levels || !d_feed_out))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (n_floats < 1 || n_floats > dusp::kScoreRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^31 floats");
+    uintptr_t low = (uintptr_t)d_direct | (uintptr_t)d_out | (n_buses ? (uintptr_t)d_feed_init | (uintptr_t)d_feed_out : 0);
+    for (size_t g = 0; g < n_tracks; g++) {
+        if (!h_tracks[g]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+        low |= (uintptr_t)h_tracks[g];
+        if (h_faders && !std::isfinite(h_faders[g])) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the fader of track " + std::to_string(g) + " is not finite");
+        for (size_t b = 0; b < n_buses; b++)
+            if (!std::isfinite(h_levels[b * n_tracks + g]))
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the level of track " + std::to_string(g) + " into bus " + std::to_string(b) + " is not finite");
+    }
+    if (low & 3) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    const ScoreLaunch none(ScoreKind::rows);  // (no plan: timed like any other launch)
+    return score_device_call(
+        ctx, stream, false, none, []() { return DUSP_OK; },
+        [&]() {
+            HIP_TRY(ctx, dusp::launch_score_tracks(d_direct, h_tracks, h_faders, n_buses ? h_levels : nullptr, (uint32_t)n_tracks, (uint32_t)n_buses, d_out,
+                                                   n_buses ? d_feed_init : nullptr, n_buses ? d_feed_out : nullptr, n_floats, raw != 0, stream));
             return DUSP_OK;
         });
     });

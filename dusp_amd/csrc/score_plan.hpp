@@ -309,4 +309,7 @@ struct alignas(16) ScoreSend {
 };
 static_assert(sizeof(ScoreSend) == 16, "one four-dword scalar load");
 
+// ---- tracks: sub-mixes of a piece through circuits of their own (score_tracks_engine.hip; dusp_amd/mix.py track_mix) ----
+constexpr size_t kScoreTrackMax = 8;
+
 }  // namespace dusp

@@ -12,6 +12,8 @@
  *   renderPieceMaster(progs[], ..., master, masterParams) -> Promise: the same through a master (dusp_render_host_score_piece)
  *   renderPieceBuses(progs[], ..., master | null, masterParams, buses[], busParams[], sends) -> Promise: the same with effect sends
  *         (dusp_render_host_score_piece_buses)
+ *   renderPieceTracks(the same — buses[] may be null —, nTracks, trackOf, trackProgs[], trackLists[], trackParams[], faders | null, trackSends | null)
+ *         -> Promise: the same with tracks, sub-mixes through circuits of their own (dusp_render_host_score_piece_tracks)
  *   descriptorChannels(Float64Array words) -> the circuit's output channels (host code only: no context)
  *   programDestroy(prog), ctxDestroy(ctx), version(), abiVersion()
  * Failures surface the way the reference's do: synchronous calls THROW A STRING, render() REJECTS
@@ -768,6 +770,15 @@ typedef struct {
     napi_ref bus_ref[4];
     float *bus_params[4];
     float *sends;         /* ... and a host copy of the voices' levels [nBuses][nVoices] */
+    int with_tracks;      /* renderPieceTracks (dusp_render_host_score_piece_tracks): where every voice goes, the track programs, each kept as the master is ... */
+    size_t n_tracks, n_tprogs;
+    int32_t *track_of;
+    prog_box *tprog_pb[8];
+    napi_ref tprog_ref[8];
+    float *tprog_params[8];
+    uint32_t *tprog_tracks[8]; /* ... with the tracks each serves, */
+    size_t tprog_n[8];
+    float *faders, *track_sends; /* ... the faders [nTracks] or NULL, and the tracks' levels [nBuses][nTracks] or NULL */
     int format, normalise, rc;
     char err[512];
 } piece_job;
@@ -784,6 +795,14 @@ static void piece_free(napi_env env, piece_job *j) {
         free(j->bus_params[b]);
     }
     free(j->sends);
+    for (size_t t = 0; t < 8; t++) {
+        if (j->tprog_ref[t]) napi_delete_reference(env, j->tprog_ref[t]);
+        free(j->tprog_params[t]);
+        free(j->tprog_tracks[t]);
+    }
+    free(j->track_of);
+    free(j->faders);
+    free(j->track_sends);
     free(j->params);
     free(j->refs);
     free(j->pbs);
@@ -822,8 +841,32 @@ static void piece_execute(napi_env env, void *data) {
             j->rc = DUSP_ERR_STATE;
             snprintf(j->err, sizeof j->err, "dusp-hip: renderPiece: a program has been destroyed");
         }
+    for (size_t t = 0; t < j->n_tprogs; t++)
+        if (!j->tprog_pb[t]->prog) {
+            j->rc = DUSP_ERR_STATE;
+            snprintf(j->err, sizeof j->err, "dusp-hip: renderPiece: a program has been destroyed");
+        }
     if (j->rc == DUSP_OK) {
-        if (j->n_buses) { /* one entry for every placement, which refuses what sends do not go with */
+        if (j->with_tracks) { /* one entry for every placement, with or without buses and a master */
+            dusp_score_placement place = {j->stereo ? DUSP_PLACE_STEREO : j->delays ? DUSP_PLACE_SPACE : j->pans ? DUSP_PLACE_PAN : DUSP_PLACE_ROWS,
+                                          j->fracs, j->pans, j->comp, j->n_speakers, j->delays, j->tap_gains};
+            dusp_score_master master = {j->master_pb ? j->master_pb->prog : NULL, j->master_params}, circuits[4];
+            dusp_score_track_program served[8];
+            for (size_t b = 0; b < j->n_buses; b++) {
+                circuits[b].prog = j->bus_pb[b]->prog;
+                circuits[b].h_params = j->bus_params[b];
+            }
+            for (size_t t = 0; t < j->n_tprogs; t++) {
+                served[t].prog = j->tprog_pb[t]->prog;
+                served[t].n_tracks = j->tprog_n[t];
+                served[t].h_tracks = j->tprog_tracks[t];
+                served[t].h_params = j->tprog_params[t];
+            }
+            dusp_score_buses buses = {j->n_buses, circuits, j->sends};
+            dusp_score_tracks tracks = {j->n_tracks, j->track_of, j->n_tprogs, served, j->faders, j->track_sends};
+            j->rc = dusp_render_host_score_piece_tracks(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, &tracks, j->n_buses ? &buses : NULL,
+                                                        j->master_pb ? &master : NULL, j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+        } else if (j->n_buses) { /* one entry for every placement, which refuses what sends do not go with */
             dusp_score_placement place = {j->stereo ? DUSP_PLACE_STEREO : j->delays ? DUSP_PLACE_SPACE : j->pans ? DUSP_PLACE_PAN : DUSP_PLACE_ROWS,
                                           j->fracs, j->pans, j->comp, j->n_speakers, j->delays, j->tap_gains};
             dusp_score_master master = {j->master_pb ? j->master_pb->prog : NULL, j->master_params}, circuits[4];
@@ -896,6 +939,8 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
     if (j->master_pb && --j->master_pb->in_flight == 0 && j->master_pb->destroy_deferred) prog_destroy_now(j->master_pb);
     for (size_t b = 0; b < j->n_buses; b++)
         if (--j->bus_pb[b]->in_flight == 0 && j->bus_pb[b]->destroy_deferred) prog_destroy_now(j->bus_pb[b]);
+    for (size_t t = 0; t < j->n_tprogs; t++)
+        if (--j->tprog_pb[t]->in_flight == 0 && j->tprog_pb[t]->destroy_deferred) prog_destroy_now(j->tprog_pb[t]);
     napi_delete_async_work(env, j->work);
     piece_free(env, j);
 }
@@ -920,12 +965,19 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *      output channel, channel c of the timeline instance c of it; masterParams its table, nParams * timeline channels values)
  * renderPieceBuses(the same twenty-one — master and masterParams may be null —, buses[] (programs), busParams[] (Float32Array | null each), sends Float32Array)
  *   -> the same with effect sends (dusp_render_host_score_piece_buses): 1 .. 4 bus programs, each what a master is, with its table, and
- *      sends[b * nVoices + k] what voice k gives to bus b; the library refuses the kinds and arrays sends do not go with */
+ *      sends[b * nVoices + k] what voice k gives to bus b; the library refuses the kinds and arrays sends do not go with
+ * renderPieceTracks(the same twenty-four — buses[] and busParams[] may be null (no buses), sends is null —, nTracks, trackOf Int32Array, trackProgs[] (programs),
+ *                   trackLists[] (Uint32Array each), trackParams[] (Float32Array | null each), faders Float32Array | null, trackSends Float32Array | null)
+ *   -> the same with tracks (dusp_render_host_score_piece_tracks): voice k goes to track trackOf[k], or with -1 straight to the mix; track program t
+ *      serves the tracks trackLists[t], its table one column a (track, channel); faders[g] scales track g, trackSends[b * nTracks + g] is what
+ *      track g gives to bus b; the library refuses the rest */
 static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master, 6 ... and buses */
-    napi_value argv[24];
+    napi_value argv[31];
     char msg[256];
-    if (!get_args(env, info, form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
-    const int with_buses = form == 6;
+    const int with_tracks = form == 7;
+    if (with_tracks) form = 6;
+    if (!get_args(env, info, with_tracks ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    int with_buses = form == 6;
     int with_master = form == 5 || form == 6; /* (the placement as a record; with buses the master itself may be null) */
     int fracs_at = 12, space_at = 12, pans_at = form == 2 || form == 4 ? 13 : 12;
     if (with_master) { /* the placement's kind says which of the four other forms this is */
@@ -1095,6 +1147,8 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         napi_valuetype mv = napi_undefined;
         napi_typeof(env, argv[19], &mv);
         if (mv == napi_null || mv == napi_undefined) with_master = 0;
+        napi_typeof(env, argv[21], &mv);
+        if (with_tracks && (mv == napi_null || mv == napi_undefined)) with_buses = 0; /* (a call with tracks may have no buses) */
     }
     if (!bad && with_buses) { /* the buses: programs of the parts' context, each with its table; and the levels */
         uint32_t n_buses = 0, n_tables = 0;
@@ -1105,7 +1159,11 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
             bad = "buses must be an array of 1 .. 4 programs";
         else if (napi_is_array(env, argv[22], &tables) != napi_ok || !tables || napi_get_array_length(env, argv[22], &n_tables) != napi_ok || n_tables != n_buses)
             bad = "busParams must be an array of one entry per bus";
-        else if (!typed_array(env, argv[23], napi_float32_array, &sd, &n_s) || n_s != (size_t)n_buses * n_voices) bad = "sends must be a Float32Array of one value per bus and voice";
+        else if (with_tracks) { /* (the levels are the tracks': trackSends) */
+            napi_valuetype st = napi_undefined;
+            napi_typeof(env, argv[23], &st);
+            if (st != napi_null && st != napi_undefined) bad = "sends must be null with tracks: the buses are fed by trackSends";
+        } else if (!typed_array(env, argv[23], napi_float32_array, &sd, &n_s) || n_s != (size_t)n_buses * n_voices) bad = "sends must be a Float32Array of one value per bus and voice";
         else if (!(j->sends = (float *)malloc(n_s * sizeof(float) + 1))) bad = "out of host memory for the send levels";
         else memcpy(j->sends, sd, n_s * sizeof(float));
         for (uint32_t b = 0; b < n_buses && !bad; b++) {
@@ -1130,6 +1188,72 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
                 else if (!(j->bus_params[b] = (float *)malloc(len * sizeof(float) + 1))) bad = "out of host memory for a parameter table";
                 else memcpy(j->bus_params[b], data, len * sizeof(float));
             } else if (bi.n_params) bad = "a bus's program needs a parameter table";
+        }
+    }
+    if (!bad && with_tracks) { /* the tracks: where the voices go, the track programs with their lists and tables, the faders and levels */
+        double n_tracks = 0;
+        uint32_t n_tp = 0, n_lists = 0, n_tables = 0;
+        bool a0 = false, a1 = false, a2 = false;
+        void *od;
+        size_t n_o = 0;
+        napi_valuetype ft = napi_undefined, lt = napi_undefined;
+        j->with_tracks = 1;
+        if (napi_get_value_double(env, argv[24], &n_tracks) != napi_ok || !(n_tracks >= 1 && n_tracks <= 8 && n_tracks == (double)(size_t)n_tracks)) bad = "a call has 1 .. 8 tracks";
+        else if (!typed_array(env, argv[25], napi_int32_array, &od, &n_o) || n_o != n_voices) bad = "trackOf must be an Int32Array of one value per voice";
+        else if (!(j->track_of = (int32_t *)malloc(n_o * sizeof(int32_t)))) bad = "out of host memory for trackOf";
+        else if (napi_is_array(env, argv[26], &a0) != napi_ok || !a0 || napi_get_array_length(env, argv[26], &n_tp) != napi_ok || n_tp > 8) bad = "trackProgs must be an array of 0 .. 8 programs";
+        else if (napi_is_array(env, argv[27], &a1) != napi_ok || !a1 || napi_get_array_length(env, argv[27], &n_lists) != napi_ok || n_lists != n_tp) bad = "trackLists must be an array of one entry per track program";
+        else if (napi_is_array(env, argv[28], &a2) != napi_ok || !a2 || napi_get_array_length(env, argv[28], &n_tables) != napi_ok || n_tables != n_tp) bad = "trackParams must be an array of one entry per track program";
+        else {
+            memcpy(j->track_of, od, n_o * sizeof(int32_t));
+            j->n_tracks = (size_t)n_tracks;
+        }
+        for (uint32_t t = 0; t < n_tp && !bad; t++) {
+            napi_value prog_v, list_v, table_v;
+            napi_valuetype tt = napi_undefined;
+            prog_box *pb = NULL;
+            void *ld;
+            size_t n_l = 0;
+            if (napi_get_element(env, argv[26], t, &prog_v) != napi_ok || napi_get_element(env, argv[27], t, &list_v) != napi_ok || napi_get_element(env, argv[28], t, &table_v) != napi_ok) { bad = "could not read a track program"; break; }
+            if (!(pb = as_prog(env, prog_v))) { /* (as_prog has thrown) */
+                piece_free(env, j);
+                return NULL;
+            }
+            j->tprog_pb[t] = pb;
+            j->n_tprogs = t + 1;
+            dusp_program_info ti;
+            dusp_program_info_get(pb->prog, &ti);
+            napi_typeof(env, table_v, &tt);
+            if (pb->cb != j->pbs[0]->cb) bad = "a track program is built on the context of the piece's parts";
+            else if (!typed_array(env, list_v, napi_uint32_array, &ld, &n_l) || n_l < 1 || n_l > 8) bad = "trackLists holds Uint32Arrays of 1 .. 8 tracks";
+            else if (!(j->tprog_tracks[t] = (uint32_t *)malloc(n_l * sizeof(uint32_t)))) bad = "out of host memory for a track list";
+            else {
+                memcpy(j->tprog_tracks[t], ld, n_l * sizeof(uint32_t));
+                j->tprog_n[t] = n_l;
+                if (tt != napi_null && tt != napi_undefined) {
+                    void *data;
+                    size_t len;
+                    if (!typed_array(env, table_v, napi_float32_array, &data, &len) || len != (size_t)ti.n_params * n_l * n_channels) bad = "trackParams holds Float32Arrays of nParams * tracks * timeline channels values";
+                    else if (!(j->tprog_params[t] = (float *)malloc(len * sizeof(float) + 1))) bad = "out of host memory for a parameter table";
+                    else memcpy(j->tprog_params[t], data, len * sizeof(float));
+                } else if (ti.n_params) bad = "a track program needs a parameter table";
+            }
+        }
+        napi_typeof(env, argv[29], &ft);
+        if (!bad && ft != napi_null && ft != napi_undefined) {
+            void *data;
+            size_t len;
+            if (!typed_array(env, argv[29], napi_float32_array, &data, &len) || len != j->n_tracks) bad = "faders must be a Float32Array of one value per track";
+            else if (!(j->faders = (float *)malloc(len * sizeof(float)))) bad = "out of host memory for the faders";
+            else memcpy(j->faders, data, len * sizeof(float));
+        }
+        napi_typeof(env, argv[30], &lt);
+        if (!bad && lt != napi_null && lt != napi_undefined) {
+            void *data;
+            size_t len;
+            if (!typed_array(env, argv[30], napi_float32_array, &data, &len) || len != j->n_buses * j->n_tracks || !len) bad = "trackSends must be a Float32Array of one value per bus and track";
+            else if (!(j->track_sends = (float *)malloc(len * sizeof(float)))) bad = "out of host memory for the tracks' levels";
+            else memcpy(j->track_sends, data, len * sizeof(float));
         }
     }
     if (!bad && with_master) { /* the master: a program of the parts' context; its table has one column a channel of the timeline */
@@ -1171,21 +1295,28 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         napi_value prog_v;
         queued = napi_get_element(env, argv[21], (uint32_t)b, &prog_v) == napi_ok && napi_create_reference(env, prog_v, 1, &j->bus_ref[b]) == napi_ok;
     }
+    for (size_t t = 0; t < j->n_tprogs && queued; t++) {
+        napi_value prog_v;
+        queued = napi_get_element(env, argv[26], (uint32_t)t, &prog_v) == napi_ok && napi_create_reference(env, prog_v, 1, &j->tprog_ref[t]) == napi_ok;
+    }
     queued = queued && napi_create_async_work(env, NULL, name, piece_execute, piece_complete, j, &j->work) == napi_ok;
     if (queued) {
         for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight++;
         if (j->master_pb) j->master_pb->in_flight++;
         for (size_t b = 0; b < j->n_buses; b++) j->bus_pb[b]->in_flight++;
+        for (size_t t = 0; t < j->n_tprogs; t++) j->tprog_pb[t]->in_flight++;
         if (napi_queue_async_work(env, j->work) != napi_ok) {
             for (uint32_t p = 0; p < n_parts; p++) j->pbs[p]->in_flight--;
             if (j->master_pb) j->master_pb->in_flight--;
             for (size_t b = 0; b < j->n_buses; b++) j->bus_pb[b]->in_flight--;
+            for (size_t t = 0; t < j->n_tprogs; t++) j->tprog_pb[t]->in_flight--;
             queued = 0;
         }
     }
     if (!queued) {
         j->master_pb = NULL;
         j->n_buses = 0;
+        j->n_tprogs = 0;
         piece_free(env, j);
         throw_string(env, "dusp-hip: renderPiece: could not queue the render");
         return NULL;
@@ -1200,6 +1331,7 @@ static napi_value fn_render_piece_space(napi_env env, napi_callback_info info) {
 static napi_value fn_render_piece_stereo(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 4); }
 static napi_value fn_render_piece_master(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 5); }
 static napi_value fn_render_piece_buses(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 6); }
+static napi_value fn_render_piece_tracks(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 7); }
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1234,7 +1366,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
         {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo}, {"renderPieceMaster", fn_render_piece_master},
-        {"renderPieceBuses", fn_render_piece_buses},
+        {"renderPieceBuses", fn_render_piece_buses}, {"renderPieceTracks", fn_render_piece_tracks},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

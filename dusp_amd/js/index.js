@@ -25,6 +25,8 @@ module.exports = {
   splitOnsets: renderChannelData.splitOnsets,
   spaceTaps: renderChannelData.spaceTaps,
   masterProgram: renderChannelData.masterProgram,
+  checkTracks: renderChannelData.checkTracks,
+  trackPrograms: renderChannelData.trackPrograms,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

@@ -457,7 +457,8 @@ function wholeSamples(who, name, values, count) {
  * master: as renderPiece's — the mix through a mono circuit, channel by channel, on the device — through the piece's call too.
  * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
-const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends)
+const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends) ||
+  given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -691,10 +692,17 @@ const MASTER = {
  * or several MasterInput, another host-computed signal or a scheduled event, one with more than one output channel, circuits that are
  * not isomorphic. */
 function masterProgram(master, channels, sampleRate, bus = null) {
-  // bus (null: a master): the circuit is bus number `bus` of the call's buses — given and checked as a master is, refused in BUS's words
-  const refuse = (name, ...args) => (bus === null ? MASTER[name] : BUS[name]).apply(null, bus === null ? args : [bus].concat(args))
+  return unify(channelCircuits(master, channels, sampleRate, bus))
+}
+
+/* masterProgram's circuits, extracted and checked, one a channel, before they are unified (twin of render.py _channel_circuits) */
+function channelCircuits(master, channels, sampleRate, bus = null, track = null) {
+  // bus (null: a master): the circuit is bus number `bus` of the call's buses — given and checked as a master is, refused in BUS's words;
+  // track: the circuit is track number `track` of the call's tracks, refused in TRACK's words
+  const words = track !== null ? TRACK : bus !== null ? BUS : MASTER, named = track !== null ? [track] : bus !== null ? [bus] : []
+  const refuse = (name, ...args) => words[name].apply(null, named.concat(args))
   const fxs = Array.isArray(master) ? master : new Array(channels).fill(master)
-  if (!fxs.length || !fxs.every((fx) => typeof fx === 'function')) throw (bus === null ? MASTER.notCallable : BUS.notCallable(bus))
+  if (!fxs.length || !fxs.every((fx) => typeof fx === 'function')) throw (named.length ? words.notCallable(named[0]) : MASTER.notCallable)
   if (fxs.length !== channels) throw refuse('count', fxs.length, channels)
   const extractions = []
   fxs.forEach((fx, c) => {
@@ -708,7 +716,7 @@ function masterProgram(master, channels, sampleRate, bus = null) {
     if (c && structureKey(ex) !== structureKey(extractions[0])) throw refuse('notIsomorphic', c)
     extractions.push(ex)
   })
-  return unify(extractions)
+  return extractions
 }
 
 /* Effect sends (DESIGN.md 6.15): the refusals of a bus and of the levels, in the words of mix.py (BUS_*, SENDS_*) */
@@ -746,12 +754,109 @@ function checkSends(sends, count, nBuses) {
   return out
 }
 
-/* what sends do not go with, refused before anything else of a call is looked at (twin of render.py _placing) */
+/* Tracks (DESIGN.md 6.16): the refusals of a track's circuit and of what says where the voices go, in the words of mix.py (TRACK_*, TRACKS_*) */
+const TRACK = {
+  notCallable: (g) => 'dusp-hip: track ' + g + ' is None (a fader group), a function fx(x) of its sub-mix, or a list of one function a channel of the timeline',
+  count: (g, have, channels) => 'dusp-hip: track ' + g + ' lists ' + have + ' circuits, the timeline has ' + channels + ' channels: one a channel',
+  oneInput: (g, c, have) => 'dusp-hip: track ' + g + ', channel ' + c + ', holds ' + have + ' MasterInput units: a track reads its sub-mix through exactly one, the one it is given',
+  hostSource: (g, c) => 'dusp-hip: track ' + g + ', channel ' + c + ", holds a HostSource: the track's timeline is its circuit's only input",
+  events: (g, c) => 'dusp-hip: track ' + g + ', channel ' + c + ', has scheduled events: a track is rendered in one piece',
+  channels: (g, c, have) => 'dusp-hip: track ' + g + ', channel ' + c + ', has ' + have + " output channels: a track's circuit is mono, applied to every channel by itself",
+  notIsomorphic: (g, c) => 'dusp-hip: the circuits of track ' + g + ' at channels 0 and ' + c + ' are not isomorphic: they are one program and may differ in constants only',
+  rate: (g, have, want) => 'dusp-hip: the sample rate of track ' + g + ' is ' + have + ", the voices' is " + want,
+}
+const TRACKS = {
+  withoutTrackOf: 'dusp-hip: tracks without track_of: every voice goes to a track or, with -1, straight to the mix',
+  trackOfAlone: 'dusp-hip: track_of without tracks: a track is what a voice goes to',
+  needTracks: (name) => 'dusp-hip: ' + name + ' without tracks: it says something about every track',
+  count: (have) => 'dusp-hip: a call has 1 .. 8 tracks, not ' + have,
+  trackOfShape: (voices) => 'dusp-hip: track_of must have shape (voices=' + voices + ',) and hold whole numbers',
+  trackOfRange: (k, g, tracks) => 'dusp-hip: voice ' + k + ' names track ' + g + ' of ' + tracks + ': track_of holds -1 (straight to the mix) or a track, 0 .. ' + (tracks - 1),
+  fadersShape: (tracks) => 'dusp-hip: faders must have shape (tracks=' + tracks + ',)',
+  faderNotFinite: (g) => 'dusp-hip: the fader of track ' + g + ' is not finite',
+  sendsShape: (buses, tracks) => 'dusp-hip: track_sends must have shape (buses=' + buses + ', tracks=' + tracks + ')',
+  levelNotFinite: (g, b) => 'dusp-hip: the level of track ' + g + ' into bus ' + b + ' is not finite',
+  sendsWithoutBuses: 'dusp-hip: track_sends without buses: a level is what a track gives to a bus',
+  busesWithoutSends: 'dusp-hip: buses without track_sends: with tracks every bus needs a level a track (track_sends of shape (buses, tracks))',
+  withSends: 'dusp-hip: sends and tracks do not go together: with tracks the buses are fed by track_sends, a level a track',
+}
+
+/* What says where the `count` voices of a call with nTracks tracks go, and what the tracks give -> { trackOf Int32Array [count], faders
+ * Float32Array [nTracks] | null, trackSends Float32Array [nBuses * nTracks] | null } (twin of mix.py check_tracks: the same checks in
+ * the same order, the same strings).  nTracks null: the call has no tracks, and every other option of theirs is refused. */
+function checkTracks(count, nTracks, trackOf, faders = null, trackSends = null, nBuses = 0, sends = null) {
+  const isList = (x) => Array.isArray(x) || ArrayBuffer.isView(x)
+  if (!given(nTracks)) {
+    if (given(trackOf)) throw TRACKS.trackOfAlone
+    if (given(faders)) throw TRACKS.needTracks('faders')
+    if (given(trackSends)) throw TRACKS.needTracks('track_sends')
+    return { trackOf: null, faders: null, trackSends: null }
+  }
+  if (!given(trackOf)) throw TRACKS.withoutTrackOf
+  if (!(nTracks >= 1 && nTracks <= 8)) throw TRACKS.count(nTracks)
+  if (!isList(trackOf) || trackOf.length !== count || Array.from(trackOf).some((x) => typeof x !== 'number' || !Number.isInteger(x))) throw TRACKS.trackOfShape(count)
+  const of = Array.from(trackOf)
+  for (let k = 0; k < count; k++) if (of[k] < -1 || of[k] >= nTracks) throw TRACKS.trackOfRange(k, of[k], nTracks)
+  let f = null, levels = null
+  if (given(faders)) {
+    if (!isList(faders) || faders.length !== nTracks || Array.from(faders).some(isList)) throw TRACKS.fadersShape(nTracks)
+    f = Float32Array.from(faders, Number)
+    for (let g = 0; g < nTracks; g++) if (!Number.isFinite(f[g])) throw TRACKS.faderNotFinite(g)
+  }
+  if (given(sends)) throw TRACKS.withSends
+  if (given(trackSends) && !nBuses) throw TRACKS.sendsWithoutBuses
+  if (nBuses && !given(trackSends)) throw TRACKS.busesWithoutSends
+  if (given(trackSends)) {
+    if (!(nBuses >= 1 && nBuses <= 4)) throw SENDS.busCount(nBuses)
+    if (!isList(trackSends)) throw TRACKS.sendsShape(nBuses, nTracks)
+    let rows = Array.from(trackSends)
+    if (nBuses === 1 && !rows.some(isList)) rows = [rows]
+    if (rows.length !== nBuses || !rows.every((r) => isList(r) && r.length === nTracks && !Array.from(r).some(isList))) throw TRACKS.sendsShape(nBuses, nTracks)
+    levels = new Float32Array(nBuses * nTracks)
+    rows.forEach((r, b) => levels.set(Float32Array.from(r, Number), b * nTracks))
+    for (let b = 0; b < nBuses; b++) for (let g = 0; g < nTracks; g++) if (!Number.isFinite(levels[b * nTracks + g])) throw TRACKS.levelNotFinite(g, b)
+  }
+  return { trackOf: Int32Array.from(of), faders: f, trackSends: levels }
+}
+
+/* The tracks of a score or piece -> [{ uni, tracks }]: the tracks' circuits grouped by structure in the order their first track comes,
+ * every group ONE program whose instances are (track, channel), instance j * channels + c the circuit of the group's j-th track over
+ * channel c (twin of render.py track_programs).  tracks: an array of 1 .. 8 entries, each null (a track without a circuit) or given as
+ * a master is. */
+function trackPrograms(tracks, channels, sampleRate) {
+  const index = new Map(), members = []
+  tracks.forEach((fx, g) => {
+    if (!given(fx)) return
+    const extractions = channelCircuits(fx, channels, sampleRate, null, g)
+    const key = structureKey(extractions[0])
+    if (!index.has(key)) {
+      index.set(key, members.length)
+      members.push({ extractions: [], tracks: [] })
+    }
+    const m = members[index.get(key)]
+    m.extractions.push(...extractions)
+    m.tracks.push(g)
+  })
+  return members.map((m) => ({ uni: unify(m.extractions), tracks: m.tracks }))
+}
+
+/* what sends and tracks do not go with, refused before anything else of a call is looked at (twin of render.py _placing) */
 function refuseSends(opts) {
-  if (!given(opts.buses) && given(opts.sends)) throw SENDS.withoutBuses
+  if (!given(opts.tracks)) {
+    checkTracks(0, null, opts.trackOf, opts.faders, opts.trackSends)
+    if (!given(opts.buses) && given(opts.sends)) throw SENDS.withoutBuses
+  } else {
+    if (!Array.isArray(opts.tracks) || opts.tracks.length < 1 || opts.tracks.length > 8) throw TRACKS.count(Array.isArray(opts.tracks) ? opts.tracks.length : 0)
+    if (!given(opts.trackOf)) throw TRACKS.withoutTrackOf
+    if (given(opts.sends)) throw TRACKS.withSends
+    if (given(opts.trackSends) && !given(opts.buses)) throw TRACKS.sendsWithoutBuses
+    if (given(opts.buses) && !given(opts.trackSends)) throw TRACKS.busesWithoutSends
+  }
   if (!given(opts.buses)) return
-  if (!given(opts.sends)) throw SENDS.withoutSends
-  if (given(opts.fracs) || given(opts.places) || opts.stereo === true) throw SENDS.placement
+  if (!given(opts.tracks)) {
+    if (!given(opts.sends)) throw SENDS.withoutSends
+    if (given(opts.fracs) || given(opts.places) || opts.stereo === true) throw SENDS.placement
+  }
   if (!Array.isArray(opts.buses) || opts.buses.length < 1 || opts.buses.length > 4) throw SENDS.busCount(Array.isArray(opts.buses) ? opts.buses.length : 0)
 }
 
@@ -798,13 +903,18 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   const channels = grouped.parts.map((part) => n.descriptorChannels(part.uni.words))
   const nChannels = stereo ? checkStereoKinds(Array.from(grouped.partOf, (p) => channels[p]), panned.pans) : taps ? checkSpaceChannels(channels, taps.nSpeakers) : panned ? checkPanChannels(channels) : checkPieceChannels(channels)
   const master = given(opts.master) ? masterProgram(opts.master, nChannels, sampleRate) : null // (behind every other check of the call)
+  let routed = null, groups = null // (... the tracks: the arrays, then the track circuits grouped into programs)
+  if (given(opts.tracks)) {
+    routed = checkTracks(count, opts.tracks.length, opts.trackOf, opts.faders, opts.trackSends, given(opts.buses) ? opts.buses.length : 0, opts.sends)
+    groups = trackPrograms(opts.tracks, nChannels, sampleRate)
+  }
   let buses = null, sends = null // (... the buses behind the master: the levels, then each bus as a master is made)
   if (given(opts.buses)) {
-    sends = checkSends(opts.sends, count, opts.buses.length)
+    sends = routed ? null : checkSends(opts.sends, count, opts.buses.length)
     buses = opts.buses.map((fx, b) => masterProgram(fx, nChannels, sampleRate, b))
   }
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
-  const progs = [], busProgs = []
+  const progs = [], busProgs = [], trackProgs = []
   let masterProg = null
   try {
     for (const part of grouped.parts) progs.push(n.programBuild(contextFor(sampleRate), part.uni.words, engine))
@@ -812,7 +922,12 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     if (buses) for (const bus of buses) busProgs.push(n.programBuild(contextFor(sampleRate), bus.words, engine))
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
-    const result = buses ? await n.renderPieceBuses(...args, panned ? 1 : 0, null, panned ? panned.pans : null, panned ? panned.comp : null, 0, null, null,
+    if (groups) for (const group of groups) trackProgs.push(n.programBuild(contextFor(sampleRate), group.uni.words, engine))
+    const result = routed ? await n.renderPieceTracks(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+      taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
+      buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, null, opts.tracks.length, routed.trackOf, trackProgs,
+      groups.map((group) => Uint32Array.from(group.tracks)), groups.map((group) => (group.uni.nParams ? group.uni.params : null)), routed.faders, routed.trackSends)
+      : buses ? await n.renderPieceBuses(...args, panned ? 1 : 0, null, panned ? panned.pans : null, panned ? panned.comp : null, 0, null, null,
       masterProg, master && master.nParams ? master.params : null, busProgs, buses.map((bus) => (bus.nParams ? bus.params : null)), sends)
       : master ? await n.renderPieceMaster(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master.nParams ? master.params : null)
@@ -825,6 +940,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     for (const prog of progs) n.programDestroy(prog)
     if (masterProg) n.programDestroy(masterProg)
     for (const prog of busProgs) n.programDestroy(prog)
+    for (const prog of trackProgs) n.programDestroy(prog)
   }
 }
 
@@ -863,7 +979,14 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * of one array of levels a bus (one bus: the levels themselves will do), sends[b][k] what voice k gives to bus b.  Bus b hears the chain
  * of every voice's dry term — after its gain and its pan — times its level, is rendered over that timeline as a master is over the mix,
  * and the buses' outputs are added to the dry mix in order, in front of the master where there is one.  A level of 0 is a
- * multiplication by 0, not a voice left out.  With plain voices and with pans; fracs, places and stereo are refused with sends. */
+ * multiplication by 0, not a voice left out.  With plain voices and with pans; fracs, places and stereo are refused with sends.
+ * tracks, trackOf, faders, trackSends: sub-mixes — some of the voices through a circuit of their own before they reach the mix
+ * (dusp_render_host_score_piece_tracks; DESIGN.md 6.16).  tracks: an array of 1 .. 8 entries, each given as a master is or null for a
+ * track without a circuit, a fader group; trackOf: one whole number a voice, the track it goes to or -1 for straight to the mix.  Track
+ * g hears the chain of ITS voices — the call's placement over them alone, raw — and is rendered over it as a master is over the mix;
+ * tracks with isomorphic circuits are ONE program (trackPrograms).  faders (one finite number a track) scale the tracks' outputs, which
+ * are added to the direct voices' chain in order; with buses, trackSends[b][g] is what track g gives to bus b, and sends is refused.
+ * Whatever the placement, with or without a master. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   const channelData = []
@@ -936,6 +1059,10 @@ module.exports.MASTER = MASTER
 module.exports.BUS = BUS
 module.exports.SENDS = SENDS
 module.exports.checkSends = checkSends
+module.exports.TRACK = TRACK
+module.exports.TRACKS = TRACKS
+module.exports.checkTracks = checkTracks
+module.exports.trackPrograms = trackPrograms
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

@@ -769,3 +769,118 @@ def bus_return(dry_raw, wets, raw=False):
                 raise ValueError("dusp-hip: the output of bus %d must have shape (channels=%d, n_total=%d)" % ((b,) + dry_raw.shape))
             acc = acc + wet
     return _chain_end(acc, raw)
+
+
+# ---- tracks: sub-mixes of a piece through insert circuits ----
+
+TRACK_MAX = 8
+TRACK_NOT_CALLABLE = "dusp-hip: track %d is None (a fader group), a function fx(x) of its sub-mix, or a list of one function a channel of the timeline"
+TRACK_CIRCUITS = "dusp-hip: track %d lists %d circuits, the timeline has %d channels: one a channel"
+TRACK_ONE_INPUT = "dusp-hip: track %d, channel %d, holds %d MasterInput units: a track reads its sub-mix through exactly one, the one it is given"
+TRACK_HOST_SOURCE = "dusp-hip: track %d, channel %d, holds a HostSource: the track's timeline is its circuit's only input"
+TRACK_EVENTS = "dusp-hip: track %d, channel %d, has scheduled events: a track is rendered in one piece"
+TRACK_CHANNELS = "dusp-hip: track %d, channel %d, has %d output channels: a track's circuit is mono, applied to every channel by itself"
+TRACK_NOT_ISOMORPHIC = "dusp-hip: the circuits of track %d at channels 0 and %d are not isomorphic: they are one program and may differ in constants only"
+TRACK_RATE = "dusp-hip: the sample rate of track %d is %d, the voices' is %d"
+TRACKS_WITHOUT_TRACK_OF = "dusp-hip: tracks without track_of: every voice goes to a track or, with -1, straight to the mix"
+TRACKS_TRACK_OF_ALONE = "dusp-hip: track_of without tracks: a track is what a voice goes to"
+TRACKS_NEED_TRACKS = "dusp-hip: %s without tracks: it says something about every track"
+TRACKS_COUNT = "dusp-hip: a call has 1 .. 8 tracks, not %d"
+TRACKS_TRACK_OF_SHAPE = "dusp-hip: track_of must have shape (voices=%d,) and hold whole numbers"
+TRACKS_TRACK_OF_RANGE = "dusp-hip: voice %d names track %d of %d: track_of holds -1 (straight to the mix) or a track, 0 .. %d"
+TRACKS_FADERS_SHAPE = "dusp-hip: faders must have shape (tracks=%d,)"
+TRACKS_FADER_NOT_FINITE = "dusp-hip: the fader of track %d is not finite"
+TRACKS_SENDS_SHAPE = "dusp-hip: track_sends must have shape (buses=%d, tracks=%d)"
+TRACKS_LEVEL_NOT_FINITE = "dusp-hip: the level of track %d into bus %d is not finite"
+TRACKS_SENDS_WITHOUT_BUSES = "dusp-hip: track_sends without buses: a level is what a track gives to a bus"
+TRACKS_BUSES_WITHOUT_SENDS = "dusp-hip: buses without track_sends: with tracks every bus needs a level a track (track_sends of shape (buses, tracks))"
+TRACKS_WITH_SENDS = "dusp-hip: sends and tracks do not go together: with tracks the buses are fed by track_sends, a level a track"
+
+
+def check_tracks(n, n_tracks, track_of, faders=None, track_sends=None, n_buses=0, sends=None):
+    """What says where the n voices of a call with n_tracks tracks go, and what the tracks give -> (track_of int32 [n], faders float32
+    [n_tracks] or None, track_sends float32 [n_buses, n_tracks] or None), contiguous.  n_tracks None: the call has no `tracks=`, and
+    every other keyword of theirs is refused.  n_buses: the call's buses (0: none); sends: its per-voice `sends=`, which do not go
+    with tracks.  Refused by the strings the library uses, in this order: a keyword without tracks; tracks without track_of; a number of
+    tracks outside 1 .. 8; another shape of track_of or an entry that is no whole number; an entry outside -1 .. n_tracks - 1 (the voice
+    named); another shape of faders; a fader that is not finite as float32 (the track named); sends together with tracks; track_sends
+    without buses and buses without track_sends; another shape; a level that is not finite (bus and track named).  Needs no device."""
+    if n_tracks is None:
+        if track_of is not None:
+            raise ValueError(TRACKS_TRACK_OF_ALONE)
+        for name, value in (("faders", faders), ("track_sends", track_sends)):
+            if value is not None:
+                raise ValueError(TRACKS_NEED_TRACKS % name)
+        return None, None, None
+    if track_of is None:
+        raise ValueError(TRACKS_WITHOUT_TRACK_OF)
+    if not 1 <= n_tracks <= TRACK_MAX:
+        raise ValueError(TRACKS_COUNT % n_tracks)
+    of = np.asarray(track_of)
+    if of.shape != (n,) or (of.dtype.kind not in "iu" and (of.dtype.kind != "f" or not np.all(np.isfinite(of)) or np.any(of != np.floor(of)))):
+        raise ValueError(TRACKS_TRACK_OF_SHAPE % n)
+    of = of.astype(np.int64)
+    wrong = (of < -1) | (of >= n_tracks)
+    if wrong.any():
+        k = int(np.argmax(wrong))
+        raise ValueError(TRACKS_TRACK_OF_RANGE % (k, int(of[k]), n_tracks, n_tracks - 1))
+    of = np.ascontiguousarray(of, dtype=np.int32)
+    if faders is not None:
+        with np.errstate(all="ignore"):
+            faders = np.ascontiguousarray(faders, dtype=np.float32)
+        if faders.shape != (n_tracks,):
+            raise ValueError(TRACKS_FADERS_SHAPE % n_tracks)
+        if not np.all(np.isfinite(faders)):
+            raise ValueError(TRACKS_FADER_NOT_FINITE % int(np.argmax(~np.isfinite(faders))))
+    if sends is not None:
+        raise ValueError(TRACKS_WITH_SENDS)
+    if track_sends is not None and not n_buses:
+        raise ValueError(TRACKS_SENDS_WITHOUT_BUSES)
+    if n_buses and track_sends is None:
+        raise ValueError(TRACKS_BUSES_WITHOUT_SENDS)
+    if track_sends is not None:
+        if not 1 <= n_buses <= BUS_MAX:
+            raise ValueError(BUS_COUNT % n_buses)
+        with np.errstate(all="ignore"):
+            track_sends = np.asarray(track_sends, dtype=np.float32)
+        if track_sends.ndim == 1 and n_buses == 1:
+            track_sends = track_sends.reshape(1, -1)
+        if track_sends.shape != (n_buses, n_tracks):
+            raise ValueError(TRACKS_SENDS_SHAPE % (n_buses, n_tracks))
+        track_sends = np.ascontiguousarray(track_sends)
+        if not np.all(np.isfinite(track_sends)):
+            b, g = np.argwhere(~np.isfinite(track_sends))[0]
+            raise ValueError(TRACKS_LEVEL_NOT_FINITE % (int(g), int(b)))
+    return of, faders, track_sends
+
+
+def track_mix(direct, ys, faders=None, track_sends=None):
+    """The mix of a piece's tracks: the contract of dusp_score_tracks_mix_device and of the stage of dusp_render_host_score_piece_tracks
+    behind its track renders, needs no GPU.  direct: float32 [C, n_total], the raw chain over the voices that go straight to the mix
+    (zeros where there are none); ys: a list of T float32 [C, n_total], track g's output — master_chain(raw sub_g, ...) where the track
+    has a circuit (`|| 0` applied at the circuit's own copy-out), the raw sub-mix sub_g where it has none (NaN, Inf and -0 kept);
+    faders: float32 [T] or None; track_sends: float32 [B, T] or None -> (mix float32 [C, n_total], feeds float32 [B, C, n_total]), both
+    raw (bus_return makes `|| 0` of the mix, or hands it raw to the master):
+
+        term_g = faders given ? f32(y_g * f_g) : y_g
+        mix    = direct; for g in order: mix = f32(mix + term_g)                                  (left-deep, one rounding an add)
+        feed_b = +0;     for g in order: feed_b = f32(feed_b + f32(term_g * track_sends[b][g]))
+
+    EVERY track is in EVERY bus's chain: a level of 0 is a multiplication by 0, as in score_chain_sends — NaN * 0 poisons the feed and
+    -x * 0 is -0.  A track without a circuit passes a NaN on; a track with one has none to pass (its copy-out made it 0)."""
+    direct = np.asarray(direct)
+    if direct.dtype != np.float32 or direct.ndim != 2:
+        raise ValueError("dusp-hip: the raw timeline is float32 of shape (channels, n_total)")
+    ys = [np.asarray(y, dtype=np.float32) for y in ys]
+    _, faders, track_sends = check_tracks(0, len(ys), np.zeros(0, dtype=np.int32), faders, track_sends, 0 if track_sends is None else (1 if np.ndim(track_sends) == 1 else len(track_sends)))
+    acc = direct.copy()
+    feeds = np.zeros((0 if track_sends is None else track_sends.shape[0],) + direct.shape, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for g, y in enumerate(ys):
+            if y.shape != direct.shape:
+                raise ValueError("dusp-hip: the output of track %d must have shape (channels=%d, n_total=%d)" % ((g,) + direct.shape))
+            term = y if faders is None else y * faders[g]
+            acc = acc + term
+            for b in range(feeds.shape[0]):
+                feeds[b] = feeds[b] + term * track_sends[b, g]
+    return acc, feeds

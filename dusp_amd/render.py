@@ -251,7 +251,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -272,14 +272,17 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     not placed; the piece's call with the score as its one part, as with pans.
 
     master: as render_piece's — the mix through a mono circuit, channel by channel, on the device; the piece's call with the score as
-    its one part, as with pans."""
+    its one part, as with pans.
+
+    tracks, track_of, faders, track_sends: as render_piece's — some of the voices through a circuit of their own before they reach
+    the mix; the piece's call with the score as its one part, as with pans."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends))
 
 
 def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses")):
+    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
         return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
@@ -292,17 +295,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), (bit_depth, normalise))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), bit_depth)
 
 
 class PieceParts:
@@ -346,23 +349,39 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None):
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
     """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
     known.  The Space keywords are one thing too, None without places (the other three alone say nothing).  master: what the mix goes
     through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it;
     buses, sends: the effect buses beside the mix and the voices' levels into them, which travel with it too.  What sends do not go
-    with is refused here, before anything else of the call is looked at"""
-    if buses is None and sends is not None:
-        raise ValueError(mix.SENDS_WITHOUT_BUSES)
+    with is refused here, before anything else of the call is looked at.  tracks, track_of, faders, track_sends: the tracks some
+    voices go through, which travel with it as well; with tracks the buses are fed by track_sends, whatever the placement, and what
+    does not go with tracks is refused here too (mix.check_tracks holds the arrays once the voices are counted)"""
+    if tracks is None:
+        mix.check_tracks(0, None, track_of, faders, track_sends)
+        if buses is None and sends is not None:
+            raise ValueError(mix.SENDS_WITHOUT_BUSES)
+    else:
+        if not isinstance(tracks, (list, tuple)) or not 1 <= len(tracks) <= mix.TRACK_MAX:
+            raise ValueError(mix.TRACKS_COUNT % (len(tracks) if isinstance(tracks, (list, tuple)) else 0))
+        if track_of is None:
+            raise ValueError(mix.TRACKS_WITHOUT_TRACK_OF)
+        if sends is not None:
+            raise ValueError(mix.TRACKS_WITH_SENDS)
+        if track_sends is not None and buses is None:
+            raise ValueError(mix.TRACKS_SENDS_WITHOUT_BUSES)
+        if buses is not None and track_sends is None:
+            raise ValueError(mix.TRACKS_BUSES_WITHOUT_SENDS)
     if buses is not None:
-        if sends is None:
-            raise ValueError(mix.BUSES_WITHOUT_SENDS)
-        if fracs is not None or places is not None or stereo:
-            raise ValueError(mix.SENDS_PLACEMENT)
+        if tracks is None:
+            if sends is None:
+                raise ValueError(mix.BUSES_WITHOUT_SENDS)
+            if fracs is not None or places is not None or stereo:
+                raise ValueError(mix.SENDS_PLACEMENT)
         if not isinstance(buses, (list, tuple)) or not 1 <= len(buses) <= mix.BUS_MAX:
             raise ValueError(mix.BUS_COUNT % (len(buses) if isinstance(buses, (list, tuple)) else 0))
     return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master,
-                buses=buses, sends=sends)
+                buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends)
 
 
 def master_program(master, channels, sample_rate, bus=None):
@@ -374,16 +393,24 @@ def master_program(master, channels, sample_rate, bus=None):
     event, one with more than one output channel, circuits that are not isomorphic.
     bus (None: a master): the circuit is bus number `bus` of the call's `buses=` — what a master is to the mix it is to its send
     timeline, given and checked alike, and refused by the BUS_* strings, which name it."""
+    return descriptor.unify(_channel_circuits(master, channels, sample_rate, bus))
+
+
+def _channel_circuits(master, channels, sample_rate, bus=None, track=None):
+    """master_program's circuits, extracted and checked, one a channel, before they are unified; track: the circuit is track number
+    `track` of the call's `tracks=`, refused by the TRACK_* strings, which name it."""
     from . import graph
 
     def refuse(name, *args):
+        if track is not None:
+            raise descriptor.DuspError(getattr(mix, "TRACK_" + name) % ((track,) + args))
         raise descriptor.DuspError(getattr(mix, "MASTER_" + name) % args if bus is None else getattr(mix, "BUS_" + name) % ((bus,) + args))
 
     fxs = list(master) if isinstance(master, (list, tuple)) else [master] * channels
     if not fxs or not all(callable(fx) for fx in fxs):
         refuse("NOT_CALLABLE")
     if len(fxs) != channels:
-        refuse("COUNT" if bus is None else "CIRCUITS", len(fxs), channels)
+        refuse("COUNT" if bus is None and track is None else "CIRCUITS", len(fxs), channels)
     extractions = []
     for c, fx in enumerate(fxs):
         ex = descriptor.extract(fx(graph.MasterInput()), allow_events=True)
@@ -401,7 +428,28 @@ def master_program(master, channels, sample_rate, bus=None):
         if c and structure_key(ex) != structure_key(extractions[0]):
             refuse("NOT_ISOMORPHIC", c)
         extractions.append(ex)
-    return descriptor.unify(extractions)
+    return extractions
+
+
+def track_programs(tracks, channels, sample_rate):
+    """The tracks of a score or piece -> a list of (descriptor.Unified, [track numbers]): the tracks' circuits grouped by structure
+    (structure_key) in the order their first track comes, every group ONE program whose instances are (track, channel) — instance
+    j * channels + c the circuit of the group's j-th track over channel c — and whose parameter table has one column an instance:
+    eight tracks with one EQ are one render, not eight.  tracks: a list of 1 .. 8 entries, each None (a track without a circuit: a
+    fader group, in no program) or given as a master is, a callable fx(x) over a fresh graph.MasterInput or a list of one a channel.
+    Refused by the TRACK_* strings, which name the track, as a master's circuits are.  Needs no device."""
+    index, members = {}, []
+    for g, fx in enumerate(tracks):
+        if fx is None:
+            continue
+        extractions = _channel_circuits(fx, channels, sample_rate, track=g)
+        key = structure_key(extractions[0])
+        if key not in index:
+            index[key] = len(members)
+            members.append(([], []))
+        members[index[key]][0].extend(extractions)
+        members[index[key]][1].append(g)
+    return [(descriptor.unify(extractions), which) for extractions, which in members]
 
 
 def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, one_part=False):
@@ -411,6 +459,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     placing = dict(placing)
     master = placing.pop("master", None)
     buses, sends = placing.pop("buses", None), placing.pop("sends", None)
+    tracks, track_of, faders, track_sends = (placing.pop(k, None) for k in ("tracks", "track_of", "faders", "track_sends"))
     mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
@@ -434,8 +483,12 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     channels = place.timeline_channels([runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts], grouped.part_of)
     place.master = None if master is None else master_program(master, channels, rate)  # (behind every other check of the call)
     place.buses = place.sends = None  # (... and the buses, each a descriptor.Unified of one instance a channel, with the levels [buses, voices])
+    place.tracks = None  # (... and the tracks: (how many, track_of, track_programs' groups, faders, levels [buses, tracks]))
+    if tracks is not None:
+        track_of, faders, track_sends = mix.check_tracks(n, len(tracks), track_of, faders, track_sends, 0 if buses is None else len(buses), sends)
+        place.tracks = (len(tracks), track_of, track_programs(tracks, channels, rate), faders, track_sends)
     if buses is not None:
-        place.sends = mix.check_sends(sends, n, len(buses))
+        place.sends = None if tracks is not None else mix.check_sends(sends, n, len(buses))
         place.buses = [master_program(fx, channels, rate, bus=b) for b, fx in enumerate(buses)]
     return grouped, n_total, onsets, lengths, gains, channels, place
 
@@ -455,15 +508,21 @@ def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, devic
         if buses is not None:
             programs.extend(ctx.build(bus.words, engine) for bus in buses)
             buses = [(prog, bus.params) for prog, bus in zip(programs[-len(buses):], buses)]
+        tracks = getattr(place, "tracks", None)
+        if tracks is not None:
+            n_tracks, track_of, groups, faders, track_sends = tracks
+            programs.extend(ctx.build(uni.words, engine) for uni, _ in groups)
+            circuits = [(prog, which, uni.params) for prog, (uni, which) in zip(programs[len(programs) - len(groups):], groups)]
+            tracks = dict(n_tracks=n_tracks, track_of=track_of, programs=circuits, faders=faders, track_sends=track_sends)
         return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, master=master, buses=buses,
-                                      sends=getattr(place, "sends", None), **place.keywords())
+                                      sends=getattr(place, "sends", None), tracks=tracks, **place.keywords())
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -508,9 +567,19 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     the chain of every voice's dry term — after its gain and its pan — times its level, is rendered over that timeline as a master is
     over the mix, and the buses' outputs are added to the dry mix in order: Sum.many([dry, bus_0(...), bus_1(...), ...]), in front
     of the master where there is one (mix.score_chain_sends, mix.master_chain, mix.bus_return).  A level of 0 is a
-    multiplication by 0, not a voice left out.  With plain voices and with pans; fracs, places and stereo are refused with sends."""
+    multiplication by 0, not a voice left out.  With plain voices and with pans; fracs, places and stereo are refused with sends.
+
+    tracks, track_of, faders, track_sends: sub-mixes — the drums through one Clip, the pad through one Filter, the bass straight to
+    the mix, a fader on each group, the group and not each note sent to the echo.  tracks is a list of 1 .. 8 entries, each given as
+    a master is (a callable fx(x) over a fresh MasterInput, or a list of one a channel) or None for a track without a circuit;
+    track_of holds one whole number a voice, the track it goes to or -1 for straight to the mix.  Track g hears the chain of ITS
+    voices — the call's placement over them alone, in index order, raw — and is rendered over that timeline as a master is over the
+    mix; tracks with isomorphic circuits are rendered as ONE program (track_programs).  faders (one finite number a track) scale the
+    tracks' outputs, which are added to the direct voices' chain in order; with buses=, track_sends (float32 [buses, tracks]) is what
+    each track gives to each bus, and sends= is refused: the buses hear the tracks, not the notes (mix.track_mix).
+    Whatever the placement, with or without a master."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), _one_part)
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), _one_part)
 
 
 def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
@@ -523,17 +592,17 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends), _one_part, (bit_depth, normalise))
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends), bit_depth)
 
 
 class PcmData:

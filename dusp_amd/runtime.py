@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
+from .mix import BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -35,6 +35,7 @@ EXPORTS = [
     "dusp_score_rows_stereo_device", "dusp_render_host_score_parts_stereo",
     "dusp_render_host_score_piece",
     "dusp_render_host_score_piece_buses", "dusp_score_rows_send_device", "dusp_score_return_device",
+    "dusp_render_host_score_piece_tracks", "dusp_score_tracks_mix_device",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -118,6 +119,9 @@ def load():
     L.dusp_render_host_score_piece_buses.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_score_rows_send_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, sz, vp, ci, vp, vp, vp, vp]
     L.dusp_score_return_device.argtypes = [vp, vp, vp, sz, sz, ci, vp, vp]
+    if hasattr(L, "dusp_render_host_score_piece_tracks"):  # (detected by symbol: DUSP_HIP_LIB may name a build from before tracks, for A/B runs)
+        L.dusp_render_host_score_piece_tracks.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+        L.dusp_score_tracks_mix_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, ci, vp, vp, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -156,6 +160,19 @@ class ScoreMaster(ctypes.Structure):
 class ScoreBuses(ctypes.Structure):
     """dusp_score_buses: the bus circuits of a piece, each given as a master is, and the voices' send levels f32 [n_buses][n_voices]"""
     _fields_ = [("n_buses", ctypes.c_size_t), ("buses", ctypes.c_void_p), ("h_sends", ctypes.c_void_p)]
+
+
+class ScoreTrackProgram(ctypes.Structure):
+    """dusp_score_track_program: the one program of tracks with isomorphic circuits, the tracks it serves, and its parameter table
+    [n_params][tracks x timeline channels]"""
+    _fields_ = [("prog", ctypes.c_void_p), ("n_tracks", ctypes.c_size_t), ("h_tracks", ctypes.c_void_p), ("h_params", ctypes.c_void_p)]
+
+
+class ScoreTracks(ctypes.Structure):
+    """dusp_score_tracks: where every voice of a piece goes (int32 [n_voices], -1: straight to the mix), the track programs, the faders
+    f32 [n_tracks] and the tracks' levels into the buses f32 [n_buses][n_tracks]"""
+    _fields_ = [("n_tracks", ctypes.c_size_t), ("h_track_of", ctypes.c_void_p), ("n_programs", ctypes.c_size_t), ("programs", ctypes.c_void_p),
+                ("h_faders", ctypes.c_void_p), ("h_track_sends", ctypes.c_void_p)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -443,8 +460,28 @@ class Context:
         wets = (ctypes.c_void_p * max(len(d_wets), 1))(*d_wets)
         self._check(self._L.dusp_score_return_device(self._h, d_dry, ctypes.addressof(wets), len(d_wets), n_floats, int(bool(raw)), d_out, stream))
 
+    def score_tracks_mix(self, d_direct, d_tracks, n_floats, d_out, faders=None, levels=None, d_feed_out=None, d_feed_init=None, raw=False, stream=None):
+        """Device pointers: d_out[j] = d_direct[j] + term_0[j] + ... over n_floats floats, term_g = d_tracks[g][j] times faders[g] (None:
+        as it stands), left-deep with one f32 rounding an add, `|| 0` unless raw; with levels, HOST f32 [buses][tracks] (0 .. 4 buses),
+        d_feed_out[b][j] = (d_feed_init ? d_feed_init[b][j] : +0) + f32(term_0[j] * levels[b][0]) + ..., f32 [buses][n_floats], always raw
+        (dusp_score_tracks_mix_device; dusp_amd/mix.py track_mix is the contract).  d_tracks: 1 .. 8 pointers; d_out may be d_direct,
+        d_feed_out may be d_feed_init.  score_last_ms() reports the call."""
+        tracks = (ctypes.c_void_p * max(len(d_tracks), 1))(*d_tracks)
+        if faders is not None:
+            faders = np.ascontiguousarray(faders, dtype=np.float32)
+            if faders.shape != (len(d_tracks),):
+                raise ValueError(TRACKS_FADERS_SHAPE % len(d_tracks))
+        n_buses = 0
+        if levels is not None:
+            levels = np.ascontiguousarray(levels, dtype=np.float32)
+            if levels.ndim != 2 or levels.shape[1] != len(d_tracks):
+                raise ValueError(TRACKS_SENDS_SHAPE % (levels.shape[0] if levels.ndim == 2 else 0, len(d_tracks)))
+            n_buses = levels.shape[0]
+        self._check(self._L.dusp_score_tracks_mix_device(self._h, d_direct, ctypes.addressof(tracks), len(d_tracks), _ptr(faders), n_buses, _ptr(levels, n_buses), n_floats,
+                                                         int(bool(raw)), d_out, d_feed_init, d_feed_out, stream))
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None):
+                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -468,10 +505,18 @@ class Context:
         mix.score_chain_sends, mix.master_chain and mix.bus_return are the contract) — 1 .. 4 programs, each what a master is; voice k
         gives sends[b][k] of what it adds to the mix to bus b, every bus is rendered over its send timeline, and their outputs are
         added to the dry mix in order, in front of the master where there is one.  With plain rows and with pans; fracs, taps and
-        stereo are refused together with sends."""
-        if buses is None and sends is not None:
+        stereo are refused together with sends.
+        tracks = dict(n_tracks, track_of, programs, faders=None, track_sends=None): sub-mixes (dusp_render_host_score_piece_tracks;
+        mix.track_mix is the contract) — voice k goes to track track_of[k], or with -1 straight to the mix; programs is a list of
+        (program, [track numbers], params), each what a master is and ONE program for the tracks it lists, params its table
+        [n_params][tracks x timeline channels]; a track in no program has no circuit.  faders: one finite f32 a track; track_sends:
+        f32 [buses][tracks], with buses, whose sends are then None.  Whatever the placement."""
+        if tracks is not None:
+            track_of, faders, track_sends = check_tracks(len(part_of), tracks["n_tracks"], tracks["track_of"], tracks.get("faders"), tracks.get("track_sends"),
+                                                         0 if buses is None else len(buses), sends)
+        elif buses is None and sends is not None:
             raise ValueError(SENDS_WITHOUT_BUSES)
-        if buses is not None:
+        if buses is not None and tracks is None:
             if sends is None:
                 raise ValueError(BUSES_WITHOUT_SENDS)
             refuse_sends_placement(fracs, taps, stereo)
@@ -499,7 +544,7 @@ class Context:
             check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], place.pans)
         n_ch = place.channels(parts[0][0].n_out_channels)  # (parts that do not fit the placement: the library refuses them)
         voices = (table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data)
-        if master is not None or buses is not None:
+        if master is not None or buses is not None or tracks is not None:
             how = ScorePlacement(PLACE_KINDS[place.kind], _ptr(place.fracs), _ptr(place.pans), _ptr(place.comp), n_ch if place.kind == "space" else 0,
                                  _ptr(place.taps[0]) if place.taps else None, _ptr(place.taps[1]) if place.taps else None)
             through = None
@@ -509,12 +554,28 @@ class Context:
                 through = ScoreMaster(prog._h, _ptr(params))
         if buses is not None:
             buses = list(buses)
-            levels = check_sends(sends, n, len(buses))
+            levels = check_sends(sends, n, len(buses)) if tracks is None else None
             circuits = (ScoreMaster * len(buses))()
             for b, (prog, params) in enumerate(buses):
                 keep.append(prog._params_table(params, n_ch, "dusp-hip: the params of bus %d must have shape" % b))
                 circuits[b] = ScoreMaster(prog._h, _ptr(keep[-1]))
-            into = ScoreBuses(len(buses), ctypes.addressof(circuits), levels.ctypes.data)
+            into = ScoreBuses(len(buses), ctypes.addressof(circuits), _ptr(levels))
+        if tracks is not None:
+            served = list(tracks["programs"])
+            table_t = (ScoreTrackProgram * max(len(served), 1))()
+            for p, (prog, which, params) in enumerate(served):
+                which = np.ascontiguousarray(which, dtype=np.uint32)
+                keep.append(which)
+                keep.append(prog._params_table(params, len(which) * n_ch, "dusp-hip: the params of track program %d must have shape" % p))
+                table_t[p] = ScoreTrackProgram(prog._h, len(which), which.ctypes.data, _ptr(keep[-1]))
+            routed = ScoreTracks(tracks["n_tracks"], track_of.ctypes.data, len(served), ctypes.addressof(table_t), _ptr(faders), _ptr(track_sends))
+            fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
+            self._check(self._L.dusp_render_host_score_piece_tracks(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(routed),
+                                                                    ctypes.addressof(into) if buses is not None else None,
+                                                                    ctypes.addressof(through) if through is not None else None, n_total_samples, int(tile_bytes), fmt,
+                                                                    normalise, out.ctypes.data, _ptr(peak)))
+            return out if peak is None else (out, peak[0])
+        if buses is not None:
             fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
             self._check(self._L.dusp_render_host_score_piece_buses(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(into),
                                                                    ctypes.addressof(through) if through is not None else None, n_total_samples, int(tile_bytes), fmt,

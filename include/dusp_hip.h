@@ -649,6 +649,59 @@ int dusp_score_rows_send_device(dusp_ctx *ctx, const float *const *h_rows, const
 int dusp_score_return_device(dusp_ctx *ctx, const float *d_dry, const float *const *h_wets, size_t n_buses, size_t n_floats, int raw,
                              float *d_out, void *stream);
 
+/* Tracks: sub-mixes of a piece through insert circuits, on the device (additions to ABI v7, detected by symbol; DESIGN.md 6.16;
+ * dusp_amd/mix.py track_mix is the contract).
+ *
+ * Voice k goes to track h_track_of[k] (0 .. n_tracks - 1) or, with -1, straight to the mix.  Every destination that has voices is the
+ * chain of today's placement over ITS voices, in index order, raw, in a timeline of its own [C][n_total_samples]; a track without
+ * voices hears zeros.  A TRACK PROGRAM is what a master is, and serves the tracks listed in h_tracks, which have isomorphic circuits:
+ * its instances are (track, channel), instance j * C + c the circuit of track h_tracks[j] over channel c of that track's timeline,
+ * h_params [n_params][n_tracks x C] one column an instance.  It is rendered ONCE, from its initial state, over its tracks' raw
+ * timelines (`|| 0` at its own copy-out).  A track that no program lists has no circuit — a fader group — and its output is its raw
+ * timeline.  Then one launch (score_tracks_engine.hip) mixes:
+ *     term_g = h_faders ? f32(y_g * h_faders[g]) : y_g
+ *     mix    = direct; for g in order: mix = f32(mix + term_g)                                   (left-deep, one rounding an add)
+ *     feed_b = +0;     for g in order: feed_b = f32(feed_b + f32(term_g * h_track_sends[b][g]))   (with buses: every track is in every
+ *                                                                                                   bus's chain, a level of 0 included)
+ * and the call goes on as dusp_render_host_score_piece_buses does behind its last tile: every bus rendered over its feed, the return,
+ * the master, the delivery.  With tracks the buses' h_sends must be NULL: the levels are h_track_sends.
+ * Device memory on top of that call's: n_tracks timelines and the track programs' outputs, f32 [C][n_total_samples] each.
+ *   tracks   NULL: the call is dusp_render_host_score_piece_buses (under this entry's name).
+ * Refused with a message before anything renders, beside what that call refuses: n_tracks outside 1 .. 8; NULL h_track_of; an entry of
+ * h_track_of outside -1 .. n_tracks - 1 (the voice named); a fader that is not finite (the track named); h_track_sends without buses,
+ * buses without h_track_sends, buses with h_sends; a level that is not finite (bus and track named); every rule of a master, per
+ * program ("track program p"); a track program that is also a part, a bus, the master or another track program; a program that lists
+ * no track, a track out of range, or a track that another program (or itself) lists already; (tracks x channels) x timeline samples of
+ * a program above 2^31 floats. */
+typedef struct dusp_score_track_program {
+    dusp_program *prog;       /* one input stream, one output channel, on the parts' context */
+    size_t n_tracks;          /* how many tracks it serves, >= 1 */
+    const uint32_t *h_tracks; /* [n_tracks]: which, each 0 .. the call's n_tracks - 1 */
+    const float *h_params;    /* [n_params][n_tracks x timeline channels], HOST memory; NULL without parameters */
+} dusp_score_track_program;
+typedef struct dusp_score_tracks {
+    size_t n_tracks;                          /* 1 .. 8 */
+    const int32_t *h_track_of;                /* [n_voices]: -1 (straight to the mix) .. n_tracks - 1 */
+    size_t n_programs;                        /* 0 .. n_tracks */
+    const dusp_score_track_program *programs; /* [n_programs] */
+    const float *h_faders;                    /* f32 [n_tracks], finite; NULL: none */
+    const float *h_track_sends;               /* f32 [n_buses][n_tracks], finite; NULL exactly when the call has no buses */
+} dusp_score_tracks;
+int dusp_render_host_score_piece_tracks(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                        const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                        const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                        const dusp_score_buses *buses, const dusp_score_master *master, size_t n_total_samples,
+                                        size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak);
+/* The mix of the tracks alone, over flat buffers of n_floats floats (1 .. 2^31): d_out[j] = d_direct[j] + term_0[j] + ... as above,
+ * `|| 0` unless raw, and d_feed_out[b][j] = (d_feed_init ? d_feed_init[b][j] : +0) + f32(term_0[j] * h_levels[b][0]) + ..., always raw.
+ * h_tracks: a HOST array of n_tracks (1 .. 8) device addresses; h_faders: f32 [n_tracks] or NULL; h_levels: f32 [n_buses][n_tracks],
+ * n_buses 0 .. 4 (0: no feeds; the three feed arguments are ignored); the feeds are f32 [n_buses][n_floats].  d_out may be d_direct,
+ * d_feed_out may be d_feed_init.  Four floats a lane where every buffer (each feed included) is on a 16-byte boundary, one a lane
+ * otherwise.  dusp_score_last_ms reports this call too. */
+int dusp_score_tracks_mix_device(dusp_ctx *ctx, const float *d_direct, const float *const *h_tracks, size_t n_tracks,
+                                 const float *h_faders, size_t n_buses, const float *h_levels, size_t n_floats, int raw, float *d_out,
+                                 const float *d_feed_init, float *d_feed_out, void *stream);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

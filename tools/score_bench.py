@@ -36,6 +36,11 @@
           gains over the same plan — launched once, the floor: what the dry chain alone costs; and 1 + B times into distinct
           buffers, what reading every row once is meant to beat.  The return kernel against dusp_fill_device.  The whole call on
           the host's clock with an echo bus and without.  A report: no ratio is fixed in advance.
+  tracks  (--tracks; profiles/score_tracks.txt) the mix kernel (dusp_score_tracks_mix_device) over one channel of
+          the piece's timeline at T = 2, 4, 8 tracks and B = 0, 2 buses, with faders, against dusp_fill_device over one timeline
+          and against the return kernel over as many input buffers (T <= 4).  Then the piece with eight Filter tracks as ONE
+          program of eight instances on the host's clock, beside the piece with the same Filter as its master, the piece
+          alone, and eight calls with the Filter as the master one after the other.  A report: no ratio is fixed in advance.
 
 Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
 """
@@ -441,6 +446,77 @@ def sends(scale, ctxs, reps):
     prog.close()
 
 
+def tracks(scale, ctxs, reps):
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
+    d.configure(SR)
+    ctx = ctxs["default"]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+
+    def median_of(call):
+        kernel = []
+        for r in range(reps + 1):
+            call()
+            if r:
+                kernel.append(ctx.score_last_ms()[0])
+        return float(np.median(kernel)), min(kernel)
+
+    print("tracks: one channel of %d samples (%.1f MB a timeline), kernels alone by HIP events (dusp_score_last_ms), median and fastest of %d after a warm-up"
+          % (nt, nt * 4 / 1e6, reps), flush=True)
+    line = "  %-66s median %8.3f ms  fastest %8.3f%s"
+    bufs = [torch.randn(nt, dtype=torch.float32, device="cuda") for _ in range(9)]
+    out, feeds = torch.empty(nt, dtype=torch.float32, device="cuda"), torch.empty((2, nt), dtype=torch.float32, device="cuda")
+    rs = np.random.RandomState(4)
+    faders, levels = rs.random_sample(8).astype(np.float32), rs.random_sample((2, 8)).astype(np.float32)
+    torch.cuda.synchronize()
+    fill = timed(lambda: ctx.fill(out.data_ptr(), nt, 0.0, s), stream, reps)
+    print(line % (("dusp_fill_device over one timeline (%.1f MB written)" % (nt * 4 / 1e6),) + fill + ("",)), flush=True)
+    for T in (2, 4, 8):
+        ys = [b.data_ptr() for b in bufs[1:1 + T]]
+        if T <= 4:
+            back = median_of(lambda: ctx.score_return(bufs[0].data_ptr(), ys, nt, out.data_ptr(), stream=s))
+            print(line % (("dusp_score_return_kernel, %d inputs (%.0f MB read, %.0f MB written)" % (1 + T, (1 + T) * nt * 4 / 1e6, nt * 4 / 1e6),) + back + ("",)), flush=True)
+        for B in (0, 2):
+            mixed = median_of(lambda: ctx.score_tracks_mix(bufs[0].data_ptr(), ys, nt, out.data_ptr(), faders[:T], levels[:B, :T] if B else None, feeds.data_ptr() if B else None, stream=s))
+            mb = ((1 + T) * nt * 4 / 1e6, (1 + B) * nt * 4 / 1e6)
+            print(line % (("the mix kernel, T = %d, B = %d, with faders (%.0f MB read, %.0f MB written)" % ((T, B) + mb),) + mixed +
+                          ("   %.0f GB/s, x%.2f of the fill" % ((mb[0] + mb[1]) / mixed[0], mixed[0] / fill[0]),)), flush=True)
+    del bufs, out, feeds
+    # eight Filter tracks as ONE program of eight instances, beside the same Filter as a master (one instance a channel: the master
+    # path is the parent commit's, unchanged)
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    prog = ctx.build(uni.words)
+    lowpass = ctx.build(descriptor.extract(d.Filter(d.MasterInput(), 1200)).words)
+    track_of = (np.arange(V) % 8).astype(np.int32)
+    print("  %d notes of %d samples over %d samples, one channel, host clock, median and fastest of %d after a warm-up" % (V, nv, nt, reps), flush=True)
+    for label, kw in (("no tracks, no master", {}), ("Filter(x, 1200) as the master (one instance)", dict(master=(lowpass, None))),
+                      ("eight Filter(x, 1200) tracks, ONE program of eight instances", dict(tracks=dict(n_tracks=8, track_of=track_of, programs=[(lowpass, list(range(8)), None)])))):
+        times, kernel = [], []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, **kw)
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+            if kw:
+                kernel.append(lowpass.last_kernel_ms())
+        shape = "   Filter render alone median %8.3f ms   [%s]" % (float(np.median(kernel[1:])), lowpass.read_shape()) if kw else ""
+        print("  render_score_parts, %-62s median %9.2f ms  fastest %9.2f%s" % (label, float(np.median(times[1:])), min(times[1:]), shape), flush=True)
+    times = []
+    for r in range(reps + 1):  # the way round without track programs: eight renders of the piece's timeline through the Filter as a master, one after the other
+        t0 = time.perf_counter()
+        for g in range(8):
+            res = ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, master=(lowpass, None))
+            del res
+        times.append((time.perf_counter() - t0) * 1e3)
+    print("  render_score_parts, %-62s median %9.2f ms  fastest %9.2f" % ("eight calls with the Filter as the master, one after the other", float(np.median(times[1:])), min(times[1:])), flush=True)
+    lowpass.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -452,6 +528,7 @@ def main():
     ap.add_argument("--stereo", action="store_true", help="the stereo-piece leg alone, over the dense cases named by --cases")
     ap.add_argument("--master", action="store_true", help="the master-bus leg alone: the piece with and without a master")
     ap.add_argument("--sends", action="store_true", help="the effect-send leg alone: the send and return kernels, and the piece with and without a bus")
+    ap.add_argument("--tracks", action="store_true", help="the tracks leg alone: the mix kernel beside the fill and the return kernel, and eight Filter tracks as one program")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
@@ -459,6 +536,8 @@ def main():
         return master(a.scale, ctxs, a.reps)
     if a.sends:
         return sends(a.scale, ctxs, a.reps)
+    if a.tracks:
+        return tracks(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
