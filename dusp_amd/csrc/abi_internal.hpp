@@ -70,6 +70,12 @@ hipError_t launch_score_send(const float *d_gains, const ScoreSend *d_sends, con
 hipError_t launch_score_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, uint64_t n, int raw, hipStream_t stream);
 hipError_t launch_score_tracks(const float *d_direct, const float *const *d_tracks, const float *h_faders, const float *h_levels, uint32_t n_tracks, uint32_t n_buses,
                                float *d_out, const float *d_feed_init, float *d_feed_out, uint64_t n, int raw, hipStream_t stream);
+hipError_t launch_score_stems_mix(const float *d_direct, const float *const *d_tracks, const float *h_faders, const float *h_levels, uint32_t n_tracks, uint32_t n_buses,
+                                  float *d_out, const float *d_feed_init, float *d_feed_out, float *d_stem_direct, float *const *d_stem_tracks, uint64_t n, int raw,
+                                  hipStream_t stream);
+hipError_t launch_score_stems_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, float *d_stem_direct, float *const *d_stem_buses, uint64_t n,
+                                     int raw, hipStream_t stream);
+hipError_t launch_pcm_peak_common(const float *d_peaks, float *d_common, uint32_t n, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -177,9 +183,11 @@ struct dusp_workspaces {
     DevBuf<float> d_host_out, d_host_par, d_host_frames, d_host_in;  // dusp_render_host staging, grown on demand
     DevBuf<unsigned char> d_host_pcm;                                // dusp_render_host_pcm: the encoded frames ...
     DevBuf<float> d_host_peaks;                                      // ... and the instances' peaks
+    DevBuf<float> d_host_peak_common;                                // ... a call with stems: the one peak of all its signals, once a signal (score_stems_engine.hip)
     DevBuf<float> d_mix, d_mix_gains;                                // dusp_render_host_mix: the running sums [n_out_channels][n_samples]; one tile's gains
     DevBuf<float> d_mix_sends;                                       // a piece with buses: the send timelines [n_buses][n_out_channels][n_total] (abi_score.hip)
     DevBuf<float> d_mix_tracks;                                      // a piece with tracks: the track timelines [n_tracks][n_out_channels][n_total], in the order of the track programs (abi_score.hip)
+    DevBuf<float> d_stems;                                           // a piece with stems: the signals [1 + n_tracks + n_buses + 1][n_out_channels][n_total], the mix last (abi_score.hip)
     DevBuf<float> d_saved_bufs, d_rings_wave;  // wave engine, resumable: outlets' last chunk; rings parked during a migration
     // WAVE programs the circuit compiler takes (jit_codegen.hpp): the generated text's constants
     DevBuf<float> d_jit_fk;
@@ -191,7 +199,7 @@ struct dusp_workspaces {
     DevBuf<float> d_handoff_out;     // the two parts' PCM before they are put side by side
     DevBuf<int64_t> d_jit_regime;  // per-instance delays: [slot, ring length, mono] per unit, then the verdicts (render_jit)
 
-    static constexpr size_t kCount = 30;
+    static constexpr size_t kCount = 32;
 
     template <class F>
     void for_each_workspace(F &&f) {  // f(name, buffer); buffers that share a name are reported together
@@ -208,10 +216,12 @@ struct dusp_workspaces {
         f("staging frames", d_host_frames);
         f("staging PCM frames / peaks", d_host_pcm);
         f("staging PCM frames / peaks", d_host_peaks);
+        f("staging PCM frames / peaks", d_host_peak_common);
         f("mix sums / gains", d_mix);
         f("mix sums / gains", d_mix_gains);
         f("send timelines", d_mix_sends);
         f("track timelines", d_mix_tracks);
+        f("stems", d_stems);
         f("staging parameters", d_host_par);
         f("staging inputs", d_host_in);
         f("hand-off buffers", d_handoff_init);
@@ -400,9 +410,10 @@ inline int check_planar_pcm(dusp_ctx *ctx, const char *who, size_t n_instances, 
 
 // abi_deliver.hip
 // What a host render ends with: d_planar f32 [n_instances][n_ch][n_samples] (or, already transposed, d_frames) reaches h_out — as it is,
-// or (pcm_format != 0) through the peak and encode kernels; waits for the stream.
+// or (pcm_format != 0) through the peak and encode kernels; waits for the stream.  common_peak (a call with stems): the instances are
+// the signals of one call — their peaks are taken whatever the format (h_peaks: all of them), and what normalises is the largest.
 int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
-                 int normalise, float *h_peaks, void *h_out);
+                 int normalise, float *h_peaks, void *h_out, bool common_peak = false);
 
 // abi_mix.hip
 constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)

@@ -4,7 +4,9 @@
 // dusp_render_host_score_parts and its pan, frac, space and stereo forms; dusp_render_host_score_piece, which is all of them and takes
 // the master of a piece; dusp_render_host_score_piece_buses, which adds effect sends: per-voice levels into bus circuits, DESIGN.md 6.15,
 // with the device entries dusp_score_rows_send_device and dusp_score_return_device; dusp_render_host_score_piece_tracks, which adds
-// tracks: sub-mixes of the piece through circuits of their own, DESIGN.md 6.16, with the device entry dusp_score_tracks_mix_device).
+// tracks: sub-mixes of the piece through circuits of their own, DESIGN.md 6.16, with the device entry dusp_score_tracks_mix_device;
+// dusp_render_host_score_piece_stems, which delivers the direct mix, every track and every bus return beside the mix, DESIGN.md 6.17,
+// with the device entries dusp_score_stems_mix_device, dusp_score_stems_return_device and dusp_peak_common_device).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -418,13 +420,23 @@ static int score_buses_check(dusp_ctx *ctx, const std::string &w, const dusp_sco
 // master is (`|| 0` at its own copy-out), then ONE return launch that adds the buses' outputs onto the dry sums in d_mix, left-deep:
 // raw where a master follows (which reads the sums as they stand), else with the `|| 0` a delivery without buses applies by a launch
 // of its own.  rendered: the buses' batches, which stand until the delivery has waited for the stream.
-static int score_buses_return(dusp_program *prog, const dusp_score_buses *buses, size_t n_ch, size_t n_total, int raw, std::vector<std::unique_ptr<TiledBatch>> &rendered) {
+// With stems (d_stem_buses given; score_stems_engine.hip): the same sum into d_out (nullptr: d_mix in place), every bus's output kept in
+// its slot, d_stem_buses + b * the timeline, and — d_stem_direct given: per-note sends, whose dry timeline has no slot yet — dry || 0.
+static int score_buses_return(dusp_program *prog, const dusp_score_buses *buses, size_t n_ch, size_t n_total, int raw, std::vector<std::unique_ptr<TiledBatch>> &rendered,
+                              float *d_out = nullptr, float *d_stem_direct = nullptr, float *d_stem_buses = nullptr) {
     dusp_ctx *ctx = prog->ctx;
     const float *wets[dusp::kScoreBusMax] = {nullptr, nullptr, nullptr, nullptr};
     for (size_t b = 0; b < buses->n_buses; b++) {
         rendered.emplace_back(new TiledBatch(buses->buses[b].prog, n_ch, buses->buses[b].h_params, nullptr, n_ch));  // (one tile: all channels)
         if (int rc = rendered.back()->render_tile(0, n_ch, n_total, prog->d_mix_sends.p + b * n_ch * n_total)) return rc;
         wets[b] = buses->buses[b].prog->d_host_out.p;
+    }
+    if (d_stem_buses) {
+        float *slots[dusp::kScoreBusMax] = {nullptr, nullptr, nullptr, nullptr};
+        for (size_t b = 0; b < buses->n_buses; b++) slots[b] = d_stem_buses + b * n_ch * n_total;
+        HIP_TRY(ctx, dusp::launch_score_stems_return(prog->d_mix.p, wets, (uint32_t)buses->n_buses, d_out ? d_out : prog->d_mix.p, d_stem_direct, slots, (uint64_t)n_ch * n_total, raw,
+                                                     ctx->stream));
+        return DUSP_OK;
     }
     HIP_TRY(ctx, dusp::launch_score_return(prog->d_mix.p, wets, (uint32_t)buses->n_buses, prog->d_mix.p, (uint64_t)n_ch * n_total, raw, ctx->stream));
     return DUSP_OK;
@@ -502,8 +514,10 @@ static int score_tracks_check(dusp_ctx *ctx, const std::string &w, const dusp_sc
 // d_host_out, as a master is (`|| 0` at its own copy-out); then ONE launch of the mix kernel: the direct timeline in d_mix and every
 // track's output — its program's, or its raw timeline where it has no circuit — times its fader, left-deep into d_mix in place, and
 // times its levels into the buses' feeds (d_mix_sends, from +0).  raw: buses or a master follow, which read the sums as they stand.
+// With stems (d_stems given; score_stems_engine.hip): the same mix into d_out (nullptr: d_mix in place), direct || 0 kept in slot 0 of
+// d_stems and every track's term || 0 in slot 1 + g, a slot the timeline's floats.
 static int score_tracks_mix(dusp_program *prog, const dusp_score_tracks *tracks, const dusp_score_buses *buses, const std::vector<size_t> &slot_of, size_t n_ch, size_t n_total,
-                            int raw, std::vector<std::unique_ptr<TiledBatch>> &rendered) {
+                            int raw, std::vector<std::unique_ptr<TiledBatch>> &rendered, float *d_out = nullptr, float *d_stems = nullptr) {
     dusp_ctx *ctx = prog->ctx;
     const size_t row = n_ch * n_total;
     const float *y[dusp::kScoreTrackMax] = {};
@@ -514,6 +528,13 @@ static int score_tracks_mix(dusp_program *prog, const dusp_score_tracks *tracks,
         rendered.emplace_back(new TiledBatch(tp.prog, n_inst, tp.h_params, nullptr, n_inst));  // (one tile: every track and channel)
         if (int rc = rendered.back()->render_tile(0, n_inst, n_total, prog->d_mix_tracks.p + slot_of[tp.h_tracks[0]] * row)) return rc;
         for (size_t j = 0; j < tp.n_tracks; j++) y[tp.h_tracks[j]] = tp.prog->d_host_out.p + j * row;
+    }
+    if (d_stems) {
+        float *slots[dusp::kScoreTrackMax] = {};
+        for (size_t g = 0; g < tracks->n_tracks; g++) slots[g] = d_stems + (1 + g) * row;
+        HIP_TRY(ctx, dusp::launch_score_stems_mix(prog->d_mix.p, y, tracks->h_faders, tracks->h_track_sends, (uint32_t)tracks->n_tracks, buses ? (uint32_t)buses->n_buses : 0u,
+                                                  d_out ? d_out : prog->d_mix.p, nullptr, buses ? prog->d_mix_sends.p : nullptr, d_stems, slots, (uint64_t)row, raw, ctx->stream));
+        return DUSP_OK;
     }
     HIP_TRY(ctx, dusp::launch_score_tracks(prog->d_mix.p, y, tracks->h_faders, tracks->h_track_sends, (uint32_t)tracks->n_tracks, buses ? (uint32_t)buses->n_buses : 0u, prog->d_mix.p,
                                            nullptr, buses ? prog->d_mix_sends.p : nullptr, (uint64_t)row, raw, ctx->stream));
@@ -547,6 +568,31 @@ static int score_master_deliver_host(dusp_program *prog, const char *who, const 
     if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
         CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
     if (int rc = check_guards(m, ctx->stream)) return rc;
+    return DUSP_OK;
+}
+
+// ---- the stems of a piece: the direct mix, every track and bus return beside the mix (dusp_amd/mix.py stems) ----
+
+// What a host render with stems ends with: the block prog->d_stems, [n_signals][n_ch][n_total], holds every stem, written on the way by
+// the mix of the tracks and the return of the buses, and — without a master — the mix in its last slot.  With a master the RAW mix is in
+// d_mix as ever: the master's render over it (score_master_deliver_host says how) is copied device to device into the last slot.  Then
+// ONE delivery of the block as n_signals instances of n_ch channels, under one gain (deliver_host's common_peak), and the guard checks.
+static int score_stems_deliver_host(dusp_program *prog, const char *who, const dusp_score_master *master, size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise,
+                                    float *h_peaks, void *h_out) {
+    dusp_ctx *ctx = prog->ctx;
+    const size_t timeline = n_ch * n_total;
+    std::unique_ptr<TiledBatch> channels;
+    if (master) {
+        channels.reset(new TiledBatch(master->prog, n_ch, master->h_params, nullptr, n_ch));  // (one tile: all channels)
+        if (int rc = channels->render_tile(0, n_ch, n_total, prog->d_mix.p)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(prog->d_stems.p + (n_signals - 1) * timeline, master->prog->d_host_out.p, timeline * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (int rc = deliver_host(prog, prog->d_stems.p, nullptr, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, /*common_peak=*/true)) return rc;
+    if (channels) channels->staged = false;  // (the delivery has waited for the stream)
+    if (g_guard_bytes && (!prog->d_stems.intact() || !prog->d_host_peak_common.intact() || !prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
+        CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
+    if (master)
+        if (int rc = check_guards(master->prog, ctx->stream)) return rc;
     return DUSP_OK;
 }
 
@@ -706,11 +752,12 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
 // dusp_render_host_score_parts and its pan, frac, space and stereo forms: the parts' voices placed as `given` says (pan, space: mono
 // parts; stereo: parts of one and of two output channels, and the voices' channels, given.h_row_channels, are made here from the
 // parts') into a timeline of given.timeline_channels(a voice's).  master (optional; dusp_render_host_score_piece): a mono circuit with one
-// input stream, rendered over every channel of the raw timeline before the delivery (score_master_deliver_host)
+// input stream, rendered over every channel of the raw timeline before the delivery (score_master_deliver_host).  stems (optional;
+// dusp_render_host_score_piece_stems): h_out takes 1 + tracks + buses + 1 signals and h_peak as many peaks (score_stems_deliver_host)
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const ScorePlacement &given, size_t n_total_samples, size_t tile_bytes, int format,
                                    int normalise, void *h_out, float *h_peak, const dusp_score_master *master = nullptr, const dusp_score_buses *buses = nullptr,
-                                   const dusp_score_tracks *tracks = nullptr) {
+                                   const dusp_score_tracks *tracks = nullptr, const dusp_score_stems *stems = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
@@ -757,8 +804,16 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
     std::vector<size_t> slot_of;  // (with tracks: where track g's timeline lies in d_mix_tracks)
     if (tracks)
         if (int rc = score_tracks_check(ctx, w, tracks, buses, n_voices, parts, n_parts, master, n_out_ch, n_total_samples, slot_of)) return rc;
+    // (with stems: the direct mix, the tracks, the buses' returns, and the mix last)
+    const size_t n_stem_tracks = tracks ? tracks->n_tracks : 0, n_stem_buses = buses ? buses->n_buses : 0, n_signals = 1 + n_stem_tracks + n_stem_buses + 1;
+    if (stems && stems->n_signals != n_signals)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the stems' n_signals is " + std::to_string(stems->n_signals) + ", the call delivers " + std::to_string(n_signals) + ": the direct mix, " +
+                                        std::to_string(n_stem_tracks) + " tracks, " + std::to_string(n_stem_buses) + " buses and the mix");
+    if (stems && !h_out) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_out is NULL: a call with stems delivers its " + std::to_string(n_signals) + " signals there");
     if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
+    if (stems && n_signals * n_out_ch * n_total_samples > dusp::kScoreRowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": signals x channels x timeline samples must not exceed 2^31 with stems (" + std::to_string(n_signals) + " signals): render such a piece in windows of the timeline");
     if (int rc = place.check_values(ctx, who, n_voices)) return rc;
     // voice k of the chain: the next unused instance of part h_part_of[k]
     std::vector<size_t> instance_of(n_voices), used(n_parts, 0);
@@ -912,6 +967,7 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
             if (tp.prog->P.g.n_params) HIP_TRY(ctx, tp.prog->d_host_par.ensure((size_t)tp.prog->P.g.n_params * tp.n_tracks * n_out_ch));
         }
     }
+    if (stems) HIP_TRY(ctx, prog0->d_stems.ensure(n_signals * timeline));  // (... and with stems every signal of the delivery: one more [channels][n_total] each)
     if (h_gains) {  // (4 bytes a voice, where the plans take 32 and more: the whole piece's at once; with tracks in launch order)
         HIP_TRY(ctx, prog0->d_mix_gains.ensure(n_voices));
         HIP_TRY(ctx, hipMemcpyAsync(prog0->d_mix_gains.p, tracks ? ordered_gains.data() : h_gains, n_voices * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -938,13 +994,23 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         }
     }
     std::vector<std::unique_ptr<TiledBatch>> tracked, returned;  // (the track programs' renders, and the buses')
+    // (with stems: the kernel that makes the mix last keeps the stems on the way, and without a master it writes the mix into the last
+    // slot itself; with a master the raw mix stays in d_mix for it.  slot s: d_stems + s timelines)
+    float *d_slots = stems ? prog0->d_stems.p : nullptr, *d_last = stems && !master ? d_slots + (n_signals - 1) * timeline : nullptr;
     if (tracks)  // (raw where buses or a master follow; else the mix kernel applies the `|| 0` of the delivery)
-        if (int rc = score_tracks_mix(prog0, tracks, buses, slot_of, n_out_ch, n_total_samples, /*raw=*/buses != nullptr || master != nullptr, tracked)) return rc;
-    if (buses)
-        if (int rc = score_buses_return(prog0, buses, n_out_ch, n_total_samples, /*raw=*/master != nullptr, returned)) return rc;
+        if (int rc = score_tracks_mix(prog0, tracks, buses, slot_of, n_out_ch, n_total_samples, /*raw=*/buses != nullptr || master != nullptr, tracked, buses ? nullptr : d_last, d_slots))
+            return rc;
+    if (buses)  // (per-note sends: the dry timeline gets its slot here)
+        if (int rc = score_buses_return(prog0, buses, n_out_ch, n_total_samples, /*raw=*/master != nullptr, returned, d_last, stems && !tracks ? d_slots : nullptr,
+                                        stems ? d_slots + (1 + n_stem_tracks) * timeline : nullptr))
+            return rc;
+    if (stems && !tracks && !buses)  // (one timeline: its stem and — `|| 0`, as a delivery without stems applies it — the mix; raw and in place in front of a master)
+        HIP_TRY(ctx, dusp::launch_score_stems_mix(prog0->d_mix.p, nullptr, nullptr, nullptr, 0, 0, d_last ? d_last : prog0->d_mix.p, nullptr, nullptr, d_slots, nullptr, (uint64_t)timeline,
+                                                  /*raw=*/master != nullptr, ctx->stream));
     // (`|| 0` is the rows kernel's over the timeline's channels, panned or not; behind a master it is the master's own copy-out's; behind
     // buses without a master the return kernel has applied it, behind tracks without either the mix kernel)
-    if (int rc = master            ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
+    if (int rc = stems             ? score_stems_deliver_host(prog0, who, master, n_signals, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
+                 : master          ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
                  : buses || tracks ? deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
                                    : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out))
         return rc;
@@ -1030,7 +1096,7 @@ int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_p
 static int render_host_score_piece(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const dusp_score_placement *placement, const dusp_score_buses *buses,
                                    const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak,
-                                   const dusp_score_tracks *tracks = nullptr) {
+                                   const dusp_score_tracks *tracks = nullptr, const dusp_score_stems *stems = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_ctx *ctx = parts[0].prog->ctx;
     const dusp_score_placement plain{DUSP_PLACE_ROWS, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
@@ -1052,7 +1118,7 @@ static int render_host_score_piece(const char *who, const dusp_score_part *parts
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the placement's kind must be DUSP_PLACE_ROWS (0), DUSP_PLACE_PAN (1), DUSP_PLACE_SPACE (2) or DUSP_PLACE_STEREO (3)");
     }
     return render_host_score_parts(who, parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, place, n_total_samples, tile_bytes, format, normalise, h_out, h_peak,
-                                   master, buses, tracks);
+                                   master, buses, tracks, stems);
 }
 
 int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
@@ -1076,6 +1142,15 @@ int dusp_render_host_score_piece_tracks(const dusp_score_part *parts, size_t n_p
                                         const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak) {
     return render_host_score_piece("dusp_render_host_score_piece_tracks", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, buses, master,
                                    n_total_samples, tile_bytes, format, normalise, h_out, h_peak, tracks);
+}
+
+// ... and with stems (stems NULL: dusp_render_host_score_piece_tracks under this entry's name)
+int dusp_render_host_score_piece_stems(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                       const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks, const dusp_score_buses *buses,
+                                       const dusp_score_master *master, const dusp_score_stems *stems, size_t n_total_samples, size_t tile_bytes, int format, int normalise,
+                                       void *h_out, float *h_peaks) {
+    return render_host_score_piece("dusp_render_host_score_piece_stems", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, buses, master,
+                                   n_total_samples, tile_bytes, format, normalise, h_out, h_peaks, tracks, stems);
 }
 
 // The send chain alone (score_send_engine.hip): dusp_score_rows_device — h_pans: dusp_score_rows_pan_device, mono rows into two
@@ -1150,6 +1225,95 @@ int dusp_score_tracks_mix_device(dusp_ctx *ctx, const float *d_direct, const flo
         [&]() {
             HIP_TRY(ctx, dusp::launch_score_tracks(d_direct, h_tracks, h_faders, n_buses ? h_levels : nullptr, (uint32_t)n_tracks, (uint32_t)n_buses, d_out,
                                                    n_buses ? d_feed_init : nullptr, n_buses ? d_feed_out : nullptr, n_floats, raw != 0, stream));
+            return DUSP_OK;
+        });
+    });
+}
+
+// dusp_score_tracks_mix_device with 0 .. 8 tracks, which keeps the stems (score_stems_engine.hip): d_stems [1 + n_tracks][n_floats], slot 0
+// d_direct || 0 and slot 1 + g term g || 0
+int dusp_score_stems_mix_device(dusp_ctx *ctx, const float *d_direct, const float *const *h_tracks, size_t n_tracks, const float *h_faders, size_t n_buses, const float *h_levels,
+                                size_t n_floats, int raw, float *d_out, const float *d_feed_init, float *d_feed_out, float *d_stems, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    const char *who = "dusp_score_stems_mix_device";
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    if (n_tracks > dusp::kScoreTrackMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 0 .. 8 tracks, not " + std::to_string(n_tracks));
+    if (n_buses > dusp::kScoreBusMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 0 .. 4 buses, not " + std::to_string(n_buses));
+    if (!d_direct || !d_out || !d_stems || (n_tracks && !h_tracks) || (n_buses && ((n_tracks && !h_levels) || !d_feed_out))) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (n_floats < 1 || n_floats > dusp::kScoreRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^31 floats");
+    uintptr_t low = (uintptr_t)d_direct | (uintptr_t)d_out | (uintptr_t)d_stems | (n_buses ? (uintptr_t)d_feed_init | (uintptr_t)d_feed_out : 0);
+    float *slots[dusp::kScoreTrackMax] = {};
+    for (size_t g = 0; g < n_tracks; g++) {
+        if (!h_tracks[g]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+        low |= (uintptr_t)h_tracks[g];
+        slots[g] = d_stems + (1 + g) * n_floats;
+        if (h_faders && !std::isfinite(h_faders[g])) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the fader of track " + std::to_string(g) + " is not finite");
+        for (size_t b = 0; b < n_buses; b++)
+            if (!std::isfinite(h_levels[b * n_tracks + g]))
+                CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the level of track " + std::to_string(g) + " into bus " + std::to_string(b) + " is not finite");
+    }
+    if (low & 3) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    const ScoreLaunch none(ScoreKind::rows);  // (no plan: timed like any other launch)
+    return score_device_call(
+        ctx, stream, false, none, []() { return DUSP_OK; },
+        [&]() {
+            HIP_TRY(ctx, dusp::launch_score_stems_mix(d_direct, h_tracks, h_faders, n_buses ? h_levels : nullptr, (uint32_t)n_tracks, (uint32_t)n_buses, d_out,
+                                                      n_buses ? d_feed_init : nullptr, n_buses ? d_feed_out : nullptr, d_stems, slots, n_floats, raw != 0, stream));
+            return DUSP_OK;
+        });
+    });
+}
+
+// dusp_score_return_device which keeps the stems: wet b into d_stem_buses + b * n_floats and, d_stem_direct given, d_dry || 0 there
+int dusp_score_stems_return_device(dusp_ctx *ctx, const float *d_dry, const float *const *h_wets, size_t n_buses, size_t n_floats, int raw, float *d_out, float *d_stem_direct,
+                                   float *d_stem_buses, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    const char *who = "dusp_score_stems_return_device";
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    if (n_buses < 1 || n_buses > dusp::kScoreBusMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": a call has 1 .. 4 buses, not " + std::to_string(n_buses));
+    if (!d_dry || !d_out || !h_wets || !d_stem_buses) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (n_floats < 1 || n_floats > dusp::kScoreRowMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^31 floats");
+    uintptr_t low = (uintptr_t)d_dry | (uintptr_t)d_out | (uintptr_t)d_stem_direct | (uintptr_t)d_stem_buses;
+    float *slots[dusp::kScoreBusMax] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t b = 0; b < n_buses; b++) {
+        if (!h_wets[b]) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+        low |= (uintptr_t)h_wets[b];
+        slots[b] = d_stem_buses + b * n_floats;
+    }
+    if (low & 3) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    const ScoreLaunch none(ScoreKind::rows);  // (no plan: timed like any other launch)
+    return score_device_call(
+        ctx, stream, false, none, []() { return DUSP_OK; },
+        [&]() {
+            HIP_TRY(ctx, dusp::launch_score_stems_return(d_dry, h_wets, (uint32_t)n_buses, d_out, d_stem_direct, slots, n_floats, raw != 0, stream));
+            return DUSP_OK;
+        });
+    });
+}
+
+// One peak for n_peaks instances: d_common[i] = the largest of d_peaks, as unsigned words (score_stems_engine.hip)
+int dusp_peak_common_device(dusp_ctx *ctx, const float *d_peaks, size_t n_peaks, float *d_common, void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    const char *who = "dusp_peak_common_device";
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    if (!d_peaks || !d_common) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (n_peaks < 1 || n_peaks > (1u << 24)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": need 1..2^24 peaks");
+    if ((((uintptr_t)d_peaks | (uintptr_t)d_common) & 3) != 0) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the buffers must be 4-byte aligned");
+    if (d_peaks == d_common) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": d_common must not be d_peaks: every lane reads all the peaks");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    const ScoreLaunch none(ScoreKind::rows);  // (no plan: timed like any other launch)
+    return score_device_call(
+        ctx, stream, false, none, []() { return DUSP_OK; },
+        [&]() {
+            HIP_TRY(ctx, dusp::launch_pcm_peak_common(d_peaks, d_common, (uint32_t)n_peaks, stream));
             return DUSP_OK;
         });
     });

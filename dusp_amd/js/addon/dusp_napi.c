@@ -14,6 +14,8 @@
  *         (dusp_render_host_score_piece_buses)
  *   renderPieceTracks(the same — buses[] may be null —, nTracks, trackOf, trackProgs[], trackLists[], trackParams[], faders | null, trackSends | null)
  *         -> Promise: the same with tracks, sub-mixes through circuits of their own (dusp_render_host_score_piece_tracks)
+ *   renderPieceStems(the same thirty-one — nTracks may be 0 and what follows it null: no tracks)
+ *         -> Promise<{ data, peaks }>: the same, delivering the stems beside the mix (dusp_render_host_score_piece_stems)
  *   descriptorChannels(Float64Array words) -> the circuit's output channels (host code only: no context)
  *   programDestroy(prog), ctxDestroy(ctx), version(), abiVersion()
  * Failures surface the way the reference's do: synchronous calls THROW A STRING, render() REJECTS
@@ -779,6 +781,9 @@ typedef struct {
     uint32_t *tprog_tracks[8]; /* ... with the tracks each serves, */
     size_t tprog_n[8];
     float *faders, *track_sends; /* ... the faders [nTracks] or NULL, and the tracks' levels [nBuses][nTracks] or NULL */
+    int with_stems;       /* renderPieceStems (dusp_render_host_score_piece_stems): out holds n_signals signals, the mix last, and every one has a peak */
+    size_t n_signals;
+    float peaks[16];      /* (1 + 8 tracks + 4 buses + 1 at the most) */
     int format, normalise, rc;
     char err[512];
 } piece_job;
@@ -847,7 +852,7 @@ static void piece_execute(napi_env env, void *data) {
             snprintf(j->err, sizeof j->err, "dusp-hip: renderPiece: a program has been destroyed");
         }
     if (j->rc == DUSP_OK) {
-        if (j->with_tracks) { /* one entry for every placement, with or without buses and a master */
+        if (j->with_tracks || j->with_stems) { /* one entry for every placement, with or without buses and a master */
             dusp_score_placement place = {j->stereo ? DUSP_PLACE_STEREO : j->delays ? DUSP_PLACE_SPACE : j->pans ? DUSP_PLACE_PAN : DUSP_PLACE_ROWS,
                                           j->fracs, j->pans, j->comp, j->n_speakers, j->delays, j->tap_gains};
             dusp_score_master master = {j->master_pb ? j->master_pb->prog : NULL, j->master_params}, circuits[4];
@@ -864,8 +869,14 @@ static void piece_execute(napi_env env, void *data) {
             }
             dusp_score_buses buses = {j->n_buses, circuits, j->sends};
             dusp_score_tracks tracks = {j->n_tracks, j->track_of, j->n_tprogs, served, j->faders, j->track_sends};
-            j->rc = dusp_render_host_score_piece_tracks(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, &tracks, j->n_buses ? &buses : NULL,
-                                                        j->master_pb ? &master : NULL, j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
+            dusp_score_stems stems = {j->n_signals};
+            if (j->with_stems)
+                j->rc = dusp_render_host_score_piece_stems(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, j->with_tracks ? &tracks : NULL,
+                                                           j->n_buses ? &buses : NULL, j->master_pb ? &master : NULL, &stems, j->n_total, j->tile_bytes, j->format, j->normalise,
+                                                           j->out, j->peaks);
+            else
+                j->rc = dusp_render_host_score_piece_tracks(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, &tracks, j->n_buses ? &buses : NULL,
+                                                            j->master_pb ? &master : NULL, j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->format ? &j->peak : NULL);
         } else if (j->n_buses) { /* one entry for every placement, which refuses what sends do not go with */
             dusp_score_placement place = {j->stereo ? DUSP_PLACE_STEREO : j->delays ? DUSP_PLACE_SPACE : j->pans ? DUSP_PLACE_PAN : DUSP_PLACE_ROWS,
                                           j->fracs, j->pans, j->comp, j->n_speakers, j->delays, j->tap_gains};
@@ -910,7 +921,21 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
         snprintf(j->err, sizeof j->err, "dusp-hip: render was cancelled");
     }
     int ok = 0;
-    if (j->rc == DUSP_OK && j->format) { /* { data: Buffer over the encoded frames, peaks: Float32Array(1) } */
+    if (j->rc == DUSP_OK && j->with_stems) { /* { data: Buffer over the encoded frames or Float32Array of planar f32, all signals; peaks: Float32Array(nSignals) } */
+        napi_value data, ab, peaks_ab, peaks;
+        void *peaks_mem;
+        int wrapped = j->format ? napi_create_external_buffer(env, j->n_bytes, j->out, free_pcm, NULL, &data) == napi_ok
+                                : napi_create_external_arraybuffer(env, j->out, j->n_floats * sizeof(float), free_pcm, NULL, &ab) == napi_ok &&
+                                      napi_create_typedarray(env, napi_float32_array, j->n_floats, ab, 0, &data) == napi_ok;
+        if (wrapped) j->out = NULL; /* owned by the Buffer or ArrayBuffer now */
+        if (wrapped && napi_create_arraybuffer(env, j->n_signals * sizeof(float), &peaks_mem, &peaks_ab) == napi_ok &&
+            napi_create_typedarray(env, napi_float32_array, j->n_signals, peaks_ab, 0, &peaks) == napi_ok && napi_create_object(env, &result) == napi_ok) {
+            memcpy(peaks_mem, j->peaks, j->n_signals * sizeof(float));
+            napi_set_named_property(env, result, "data", data);
+            napi_set_named_property(env, result, "peaks", peaks);
+            ok = 1;
+        }
+    } else if (j->rc == DUSP_OK && j->format) { /* { data: Buffer over the encoded frames, peaks: Float32Array(1) } */
         napi_value buf, peaks_ab, peaks;
         void *peaks_mem;
         if (napi_create_arraybuffer(env, sizeof(float), &peaks_mem, &peaks_ab) == napi_ok && napi_create_typedarray(env, napi_float32_array, 1, peaks_ab, 0, &peaks) == napi_ok &&
@@ -970,13 +995,23 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *                   trackLists[] (Uint32Array each), trackParams[] (Float32Array | null each), faders Float32Array | null, trackSends Float32Array | null)
  *   -> the same with tracks (dusp_render_host_score_piece_tracks): voice k goes to track trackOf[k], or with -1 straight to the mix; track program t
  *      serves the tracks trackLists[t], its table one column a (track, channel); faders[g] scales track g, trackSends[b * nTracks + g] is what
- *      track g gives to bus b; the library refuses the rest */
+ *      track g gives to bus b; the library refuses the rest
+ * renderPieceStems(the same thirty-one — nTracks may be 0 with trackOf, trackProgs, trackLists, trackParams, faders and trackSends null (no tracks); with buses and no tracks
+ *                  sends holds the voices' levels —)
+ *   -> the same, delivering the stems beside the mix (dusp_render_host_score_piece_stems): resolves to { data, peaks } whatever the format, data the
+ *      1 + nTracks + nBuses + 1 signals one behind the other (a Float32Array of planar f32, or a Buffer of frames under ONE gain), the mix last, peaks a
+ *      Float32Array of every signal's own peak */
 static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master, 6 ... and buses */
     napi_value argv[31];
     char msg[256];
-    const int with_tracks = form == 7;
-    if (with_tracks) form = 6;
-    if (!get_args(env, info, with_tracks ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    const int with_stems = form == 8; /* (renderPieceStems: renderPieceTracks' arguments, the tracks among them or not) */
+    int with_tracks = form == 7;
+    if (with_tracks || with_stems) form = 6;
+    if (!get_args(env, info, with_tracks || with_stems ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    if (with_stems) { /* (nTracks 0: a call without tracks) */
+        double n_tracks = 0;
+        with_tracks = napi_get_value_double(env, argv[24], &n_tracks) != napi_ok || n_tracks != 0;
+    }
     int with_buses = form == 6;
     int with_master = form == 5 || form == 6; /* (the placement as a record; with buses the master itself may be null) */
     int fracs_at = 12, space_at = 12, pans_at = form == 2 || form == 4 ? 13 : 12;
@@ -1148,7 +1183,7 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         napi_typeof(env, argv[19], &mv);
         if (mv == napi_null || mv == napi_undefined) with_master = 0;
         napi_typeof(env, argv[21], &mv);
-        if (with_tracks && (mv == napi_null || mv == napi_undefined)) with_buses = 0; /* (a call with tracks may have no buses) */
+        if ((with_tracks || with_stems) && (mv == napi_null || mv == napi_undefined)) with_buses = 0; /* (a call with tracks or stems may have no buses) */
     }
     if (!bad && with_buses) { /* the buses: programs of the parts' context, each with its table; and the levels */
         uint32_t n_buses = 0, n_tables = 0;
@@ -1274,7 +1309,9 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
             else memcpy(j->master_params, data, len * sizeof(float));
         } else if (mi.n_params) bad = "the master's program needs a parameter table";
     }
-    j->n_floats = (size_t)n_channels * j->n_total;
+    j->with_stems = with_stems;
+    j->n_signals = with_stems ? 1 + j->n_tracks + j->n_buses + 1 : 1;
+    j->n_floats = j->n_signals * (size_t)n_channels * j->n_total;
     j->n_bytes = j->n_floats * (size_t)(!j->format || j->format == DUSP_PCM_F32 ? 4 : j->format == DUSP_PCM_S16 ? 2 : 3);
     if (!bad && !(j->out = (float *)malloc(j->n_bytes + 1))) bad = "out of host memory for the PCM buffer";
     if (bad) {
@@ -1332,6 +1369,7 @@ static napi_value fn_render_piece_stereo(napi_env env, napi_callback_info info) 
 static napi_value fn_render_piece_master(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 5); }
 static napi_value fn_render_piece_buses(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 6); }
 static napi_value fn_render_piece_tracks(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 7); }
+static napi_value fn_render_piece_stems(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 8); }
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1366,7 +1404,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderPcm", fn_render_pcm},     {"renderMix", fn_render_mix},       {"renderScore", fn_render_score},
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
         {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo}, {"renderPieceMaster", fn_render_piece_master},
-        {"renderPieceBuses", fn_render_piece_buses}, {"renderPieceTracks", fn_render_piece_tracks},
+        {"renderPieceBuses", fn_render_piece_buses}, {"renderPieceTracks", fn_render_piece_tracks}, {"renderPieceStems", fn_render_piece_stems},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -27,6 +27,7 @@ module.exports = {
   masterProgram: renderChannelData.masterProgram,
   checkTracks: renderChannelData.checkTracks,
   trackPrograms: renderChannelData.trackPrograms,
+  stemNames: renderChannelData.stemNames,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

@@ -455,10 +455,11 @@ function wholeSamples(who, name, values, count) {
  * stereo: true — as renderPiece's: voices of one or two channels, two channels out, pans optional and null / NaN for a voice that is not
  * placed — through the piece's call too.
  * master: as renderPiece's — the mix through a mono circuit, channel by channel, on the device — through the piece's call too.
- * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too. */
+ * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too.
+ * stems: true — as renderPiece's: the direct mix, every track and every bus return beside the mix — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
 const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends) ||
-  given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends)
+  given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends) || (opts.stems !== undefined && opts.stems !== false)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -466,9 +467,10 @@ function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the pie
 
 async function renderScore(outlets, opts = {}) {
   const { duration = 1 } = opts
-  const { nSamples, nChannels, sampleRate, result } = asPiece(opts)
+  const { nSamples, nChannels, sampleRate, result, names } = asPiece(opts)
     ? await pieceCall('renderScore', outlets, scoreAsPiece(opts), 0, 0, true)
     : await mixCall('renderScore', outlets, duration, opts, 0, 0, true)
+  if (names) return planarStems(names, nSamples, nChannels, sampleRate, result)
   const channelData = []
   channelData.sampleRate = sampleRate
   if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
@@ -479,15 +481,16 @@ async function renderScorePcm(outlets, opts = {}) {
   const { duration = 1, bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderScorePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderScorePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result } = asPiece(opts)
+  const { nChannels, sampleRate, result, names } = asPiece(opts)
     ? await pieceCall('renderScorePcm', outlets, scoreAsPiece(opts), PCM_FORMAT[bitDepth], normalise, true)
     : await mixCall('renderScorePcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise, true)
+  if (names) return pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise)
   if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
   return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
 }
 
 async function renderScoreWav(outlets, opts = {}) {
-  return encodeWav(await renderScorePcm(outlets, opts))
+  return wavOf(await renderScorePcm(outlets, opts))
 }
 
 /* What two extractions have in common exactly when unify takes them as instances of one program: the descriptor's words with the
@@ -840,6 +843,57 @@ function trackPrograms(tracks, channels, sampleRate) {
   return members.map((m) => ({ uni: unify(m.extractions), tracks: m.tracks }))
 }
 
+/* Stems (DESIGN.md 6.17): the refusal and the names, in the words of mix.py (STEMS_NOT_BOOL, stem_names) */
+const STEMS_NOT_BOOL = 'dusp-hip: stems is True or False: with True a call delivers the direct mix, every track and every bus return beside the mix'
+function checkStems(stems) {
+  if (stems === undefined) return false
+  if (typeof stems !== 'boolean') throw STEMS_NOT_BOOL
+  return stems
+}
+function stemNames(nTracks, nBuses) {
+  const names = ['direct']
+  for (let g = 0; g < nTracks; g++) names.push('track' + g)
+  for (let b = 0; b < nBuses; b++) names.push('bus' + b)
+  return names.concat(['mix'])
+}
+/* the one peak of several signals: the largest of their peaks compared as unsigned bit patterns, a NaN wins (twin of wav.py common_peak) */
+function commonPeak(peaks) {
+  const f = Float32Array.from(peaks), bits = new Uint32Array(f.buffer)
+  let top = 0
+  for (const b of bits) if (b > top) top = b
+  return new Float32Array(new Uint32Array([top]).buffer)[0]
+}
+/* What a call with stems: true resolves to (twin of render.py Stems): names, the signals in the order they were delivered; mix, exactly
+ * what the call resolves to without stems; direct, tracks (one a track) and buses (one a bus), each of the mix's kind; peaks, name ->
+ * the signal's own peak; peak, the largest of them; for PCM gain, the one gain all frames were encoded under. */
+function stemsOf(names, signals, peaks, extra = {}) {
+  const nTracks = names.filter((name) => name.startsWith('track')).length
+  const out = { names, direct: signals[0], tracks: signals.slice(1, 1 + nTracks), buses: signals.slice(1 + nTracks, -1), mix: signals[signals.length - 1], peaks: {}, peak: commonPeak(peaks) }
+  names.forEach((name, s) => { out.peaks[name] = peaks[s] })
+  return Object.assign(out, extra)
+}
+function planarStems(names, nSamples, nChannels, sampleRate, result) {
+  const signals = names.map((name, s) => {
+    const channelData = []
+    channelData.sampleRate = sampleRate
+    if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.data.subarray((s * nChannels + c) * nSamples, (s * nChannels + c + 1) * nSamples))
+    return channelData
+  })
+  return stemsOf(names, signals, result ? result.peaks : new Float32Array(names.length))
+}
+function pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise) {
+  const peaks = result ? result.peaks : new Float32Array(names.length), each = result ? result.data.length / names.length : 0
+  const signals = names.map((name, s) => ({ data: result ? result.data.subarray(s * each, (s + 1) * each) : Buffer.alloc(0), bitDepth, numberOfChannels: result ? nChannels : 0, sampleRate, peak: peaks[s] }))
+  const peak = commonPeak(peaks)
+  return stemsOf(names, signals, peaks, { gain: normalise && Number.isFinite(peak) && peak > (normalise === 1 ? 1 : 0) ? 1 / peak : 1 })
+}
+/* PCM -> a WAV file; the stems of a call -> a file a signal */
+function wavOf(pcm) {
+  if (!pcm.names) return encodeWav(pcm)
+  const files = pcm.names.map((name, s) => encodeWav(s === 0 ? pcm.direct : s === pcm.names.length - 1 ? pcm.mix : s <= pcm.tracks.length ? pcm.tracks[s - 1] : pcm.buses[s - 1 - pcm.tracks.length]))
+  return stemsOf(pcm.names, files, pcm.names.map((name) => pcm.peaks[name]), { gain: pcm.gain })
+}
+
 /* what sends and tracks do not go with, refused before anything else of a call is looked at (twin of render.py _placing) */
 function refuseSends(opts) {
   if (!given(opts.tracks)) {
@@ -863,6 +917,7 @@ function refuseSends(opts) {
 async function pieceCall(who, outlets, opts, format, normalise, onePart = false) {
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
   const stereo = opts.stereo === true
+  const stems = checkStems(opts.stems) // (what is no boolean is refused first)
   refuseSends(opts)
   if (given(opts.places) && stereo) throw STEREO_NO_PLACES
   if (given(opts.places) && (given(opts.pans) || given(opts.fracs))) throw SPACE_ALONE
@@ -913,7 +968,8 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     sends = routed ? null : checkSends(opts.sends, count, opts.buses.length)
     buses = opts.buses.map((fx, b) => masterProgram(fx, nChannels, sampleRate, b))
   }
-  if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null }
+  const names = stems ? stemNames(routed ? opts.tracks.length : 0, buses ? buses.length : 0) : null
+  if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null, names }
   const progs = [], busProgs = [], trackProgs = []
   let masterProg = null
   try {
@@ -923,7 +979,12 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
     if (groups) for (const group of groups) trackProgs.push(n.programBuild(contextFor(sampleRate), group.uni.words, engine))
-    const result = routed ? await n.renderPieceTracks(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+    const result = stems ? await n.renderPieceStems(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+      taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
+      buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
+      routed ? trackProgs : null, routed ? groups.map((group) => Uint32Array.from(group.tracks)) : null, routed ? groups.map((group) => (group.uni.nParams ? group.uni.params : null)) : null,
+      routed ? routed.faders : null, routed ? routed.trackSends : null)
+      : routed ? await n.renderPieceTracks(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, null, opts.tracks.length, routed.trackOf, trackProgs,
       groups.map((group) => Uint32Array.from(group.tracks)), groups.map((group) => (group.uni.nParams ? group.uni.params : null)), routed.faders, routed.trackSends)
@@ -935,7 +996,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
       : taps ? await n.renderPieceSpace(...args, taps.nSpeakers, taps.delays, taps.gains)
       : fracs ? await n.renderPieceFrac(...args, fracs, panned ? panned.pans : null, panned ? panned.comp : null)
       : panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
-    return { nSamples, nChannels, sampleRate, result }
+    return { nSamples, nChannels, sampleRate, result, names }
   } finally {
     for (const prog of progs) n.programDestroy(prog)
     if (masterProg) n.programDestroy(masterProg)
@@ -986,9 +1047,15 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * g hears the chain of ITS voices — the call's placement over them alone, raw — and is rendered over it as a master is over the mix;
  * tracks with isomorphic circuits are ONE program (trackPrograms).  faders (one finite number a track) scale the tracks' outputs, which
  * are added to the direct voices' chain in order; with buses, trackSends[b][g] is what track g gives to bus b, and sends is refused.
- * Whatever the placement, with or without a master. */
+ * Whatever the placement, with or without a master.
+ * stems: true — the call resolves to its stems beside the mix (dusp_render_host_score_piece_stems; DESIGN.md 6.17; stemsOf says what
+ * it holds): the direct mix (with tracks the voices that go straight to the mix, else the dry mix of all voices), every track after
+ * its fader and every bus's return, each as the mix is delivered, and the mix itself, bit for bit the call's result without stems.  The
+ * stems are taken in front of the master; without a master they add up to the mix.  Every signal has its peak, and PCM frames get ONE
+ * gain from the largest of them.  One addon call, one delivery.  What is no boolean is refused. */
 async function renderPiece(outlets, opts = {}) {
-  const { nSamples, nChannels, sampleRate, result } = await pieceCall('renderPiece', outlets, opts, 0, 0)
+  const { nSamples, nChannels, sampleRate, result, names } = await pieceCall('renderPiece', outlets, opts, 0, 0)
+  if (names) return planarStems(names, nSamples, nChannels, sampleRate, result)
   const channelData = []
   channelData.sampleRate = sampleRate
   if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
@@ -999,13 +1066,14 @@ async function renderPiecePcm(outlets, opts = {}) {
   const { bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderPiecePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderPiecePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result } = await pieceCall('renderPiecePcm', outlets, opts, PCM_FORMAT[bitDepth], normalise)
+  const { nChannels, sampleRate, result, names } = await pieceCall('renderPiecePcm', outlets, opts, PCM_FORMAT[bitDepth], normalise)
+  if (names) return pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise)
   if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
   return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
 }
 
 async function renderPieceWav(outlets, opts = {}) {
-  return encodeWav(await renderPiecePcm(outlets, opts))
+  return wavOf(await renderPiecePcm(outlets, opts))
 }
 
 /* A flat descriptor (what lib/extract.js produces — from this package's graph classes or from the reference's own objects,
@@ -1063,6 +1131,9 @@ module.exports.TRACK = TRACK
 module.exports.TRACKS = TRACKS
 module.exports.checkTracks = checkTracks
 module.exports.trackPrograms = trackPrograms
+module.exports.STEMS_NOT_BOOL = STEMS_NOT_BOOL
+module.exports.stemNames = stemNames
+module.exports.commonPeak = commonPeak
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

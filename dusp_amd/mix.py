@@ -875,12 +875,85 @@ def track_mix(direct, ys, faders=None, track_sends=None):
     _, faders, track_sends = check_tracks(0, len(ys), np.zeros(0, dtype=np.int32), faders, track_sends, 0 if track_sends is None else (1 if np.ndim(track_sends) == 1 else len(track_sends)))
     acc = direct.copy()
     feeds = np.zeros((0 if track_sends is None else track_sends.shape[0],) + direct.shape, dtype=np.float32)
+    terms = track_terms(ys, faders)
     with np.errstate(all="ignore"):
         for g, y in enumerate(ys):
             if y.shape != direct.shape:
                 raise ValueError("dusp-hip: the output of track %d must have shape (channels=%d, n_total=%d)" % ((g,) + direct.shape))
-            term = y if faders is None else y * faders[g]
+            term = terms[g]
             acc = acc + term
             for b in range(feeds.shape[0]):
                 feeds[b] = feeds[b] + term * track_sends[b, g]
     return acc, feeds
+
+
+# ---- stems: the direct mix, every track and every bus return beside the mix ----
+
+STEMS_NOT_BOOL = "dusp-hip: stems is True or False: with True a call delivers the direct mix, every track and every bus return beside the mix"
+
+
+def check_stems(stems):
+    """`stems=` of a score or piece call -> bool; what is no bool is refused by string (a list of names, a count: later changes)"""
+    if not isinstance(stems, (bool, np.bool_)):
+        raise ValueError(STEMS_NOT_BOOL)
+    return bool(stems)
+
+
+def stem_names(n_tracks, n_buses):
+    """the names of the S + 1 signals of a call with stems, in the order they are delivered: direct, track0 .., bus0 .., mix"""
+    return ["direct"] + ["track%d" % g for g in range(n_tracks)] + ["bus%d" % b for b in range(n_buses)] + ["mix"]
+
+
+def track_terms(ys, faders=None):
+    """What every track adds to the mix, as track_mix forms it: ys a list of T float32 arrays, faders float32 [T] or None -> a list of T
+    float32 arrays, term_g = faders given ? f32(y_g * f_g) : y_g — raw: NaN, Inf and -0 kept.  The faders are held as check_tracks
+    holds them."""
+    ys = [np.asarray(y, dtype=np.float32) for y in ys]
+    if faders is None or not ys:
+        return ys
+    _, faders, _ = check_tracks(0, len(ys), np.zeros(0, dtype=np.int32), faders)
+    with np.errstate(all="ignore"):
+        return [y * faders[g] for g, y in enumerate(ys)]
+
+
+def stems(direct_raw, terms, wets, out):
+    """The signals of a call with stems: the contract of dusp_render_host_score_piece_stems, needs no GPU.  direct_raw: float32
+    [C, n_total], the raw chain over the voices that go straight to the mix (with tracks), or the raw dry chain over all voices
+    (without); terms: track_terms' list of T; wets: a list of B float32 [C, n_total], every bus's render as its own copy-out left it
+    (`|| 0` applied there); out: the call's output as it is without stems, behind the master where there is one
+    -> float32 [S + 1, C, n_total], S = 1 + T + B, named by stem_names(T, B):
+
+        0           direct || 0
+        1 .. T      term_g || 0
+        T+1 .. T+B  wet_b
+        S           out
+
+    `|| 0`: NaN -> +0 and -0 -> +0.  The stems are in front of the master.  THE PROPERTY THAT MAKES THESE STEMS: in a call without a
+    master whose raw signals hold no NaN, or0(f32(...f32(f32(stem_0 + stem_1) + stem_2)... + stem_{S-1})), left-deep in this order, is
+    `out` bit for bit — `|| 0` on a stem only changes the sign of a zero, which changes a sum only where the sum is a zero, and the
+    last `|| 0` removes that.  A NaN breaks it: a fader group (a track without a circuit) passes a NaN of its voices on, its stem is
+    0 there and the mix is 0 there, but the other stems add up to something else."""
+    direct_raw = np.asarray(direct_raw)
+    if direct_raw.dtype != np.float32 or direct_raw.ndim != 2:
+        raise ValueError("dusp-hip: the raw timeline is float32 of shape (channels, n_total)")
+    signals = [_chain_end(direct_raw, False)]
+    for name, group, raw in (("track", terms, False), ("bus", wets, True)):
+        for j, x in enumerate(group):
+            x = np.asarray(x, dtype=np.float32)
+            if x.shape != direct_raw.shape:
+                raise ValueError("dusp-hip: the output of %s %d must have shape (channels=%d, n_total=%d)" % ((name, j) + direct_raw.shape))
+            signals.append(_chain_end(x, raw))
+    out = np.asarray(out, dtype=np.float32)
+    if out.shape != direct_raw.shape:
+        raise ValueError("dusp-hip: the mix must have shape (channels=%d, n_total=%d)" % direct_raw.shape)
+    signals.append(out)
+    return np.stack(signals)
+
+
+def stems_sum(stack):
+    """or0 of the left-deep f32 sum of the stems of a stack (all but its last signal): what stems' property compares with the mix"""
+    acc = np.asarray(stack[0], dtype=np.float32).copy()
+    with np.errstate(all="ignore"):
+        for x in stack[1:-1]:
+            acc = acc + np.asarray(x, dtype=np.float32)
+    return _chain_end(acc, False)

@@ -177,7 +177,9 @@ def _check_pcm(bit_depth, normalise):
 
 
 def _wav(pcm, bit_depth):
-    """PcmData -> a complete RIFF/WAVE file (bytes)"""
+    """PcmData -> a complete RIFF/WAVE file (bytes); a Stems of PcmData -> a Stems of files"""
+    if isinstance(pcm, Stems):
+        return pcm.each(lambda one: _wav(one, bit_depth))
     if bit_depth == 32:
         return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
     return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
@@ -199,6 +201,51 @@ def _delivered(pcm, sample_rate, n, channels, run):
     else:
         data, peak = run(_PCM_FORMAT[bit_depth], normalise)
     return PcmData(data, bit_depth, sample_rate, peak)
+
+
+class Stems:
+    """What a score or piece call with stems=True hands back (mix.stems is the contract): `names`, the signals in the
+    order they were delivered (mix.stem_names: direct, track0 .., bus0 .., mix); `mix`, exactly what the call returns without stems;
+    `direct`, `tracks` (a list, one a track) and `buses` (a list, one a bus), each of the mix's type — ChannelData, PcmData, or the
+    bytes of a WAV file; `peaks`, name -> numpy.float32, every signal's own max |x| over all its channels; `peak`, the largest of them
+    (wav.common_peak); and for PCM `gain`, the one gain all the frames were encoded under (wav.gain(peak, normalise))."""
+
+    def __init__(self, names, signals, peaks, gain=None):
+        self.names, self._signals = list(names), list(signals)
+        n_tracks = sum(1 for name in self.names if name.startswith("track"))
+        self.direct, self.tracks, self.buses, self.mix = self._signals[0], self._signals[1:1 + n_tracks], self._signals[1 + n_tracks:-1], self._signals[-1]
+        self.peaks = {name: np.float32(p) for name, p in zip(self.names, peaks)}
+        self.peak = wav.common_peak(np.asarray(peaks, dtype=np.float32))
+        if gain is not None:
+            self.gain = gain
+
+    def __getitem__(self, name):
+        return self._signals[self.names.index(name)]
+
+    def each(self, make):
+        """the same Stems with make(signal) for every signal"""
+        return Stems(self.names, [make(one) for one in self._signals], [self.peaks[name] for name in self.names], getattr(self, "gain", None))
+
+
+def _delivered_stems(pcm, sample_rate, n, channels, names, run):
+    """_delivered for a call with stems: run(format, normalise) -> (signals [S + 1, ...], peaks [S + 1]) -> Stems"""
+    def channel_data(planar):
+        result = ChannelData()
+        result.sampleRate = sample_rate
+        result.extend(planar)
+        return result
+
+    if pcm is None:
+        if n == 0:
+            return Stems(names, [channel_data([]) for _ in names], np.zeros(len(names), dtype=np.float32))
+        signals, peaks = run(None, 0)
+        return Stems(names, [channel_data(one) for one in signals], peaks)
+    bit_depth, normalise = pcm
+    if n == 0:
+        signals, peaks = wav.encode_stems(np.zeros((len(names), channels, 0), dtype=np.float32), bit_depth, normalise)
+    else:
+        signals, peaks = run(_PCM_FORMAT[bit_depth], normalise)
+    return Stems(names, [PcmData(one, bit_depth, sample_rate, p) for one, p in zip(signals, peaks)], peaks, wav.gain(wav.common_peak(peaks), normalise))
 
 
 def _render_mix(outlets, duration, gains, engine, device, tile_instances, pcm=None):
@@ -251,7 +298,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -275,14 +322,17 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     its one part, as with pans.
 
     tracks, track_of, faders, track_sends: as render_piece's — some of the voices through a circuit of their own before they reach
-    the mix; the piece's call with the score as its one part, as with pans."""
+    the mix; the piece's call with the score as its one part, as with pans.
+
+    stems=True: as render_piece's — the direct mix, every track and every bus return beside the mix, as a Stems; the piece's call with
+    the score as its one part, as with a master."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems))
 
 
 def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if placing["stereo"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
+    if placing["stereo"] or placing["stems"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
         return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
@@ -295,17 +345,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
-    """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+    """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), (bit_depth, normalise))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
-    """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav)."""
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+    """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), bit_depth)
 
 
 class PieceParts:
@@ -349,14 +399,16 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
     """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
     known.  The Space keywords are one thing too, None without places (the other three alone say nothing).  master: what the mix goes
     through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it;
     buses, sends: the effect buses beside the mix and the voices' levels into them, which travel with it too.  What sends do not go
     with is refused here, before anything else of the call is looked at.  tracks, track_of, faders, track_sends: the tracks some
     voices go through, which travel with it as well; with tracks the buses are fed by track_sends, whatever the placement, and what
-    does not go with tracks is refused here too (mix.check_tracks holds the arrays once the voices are counted)"""
+    does not go with tracks is refused here too (mix.check_tracks holds the arrays once the voices are counted).  stems: whether the
+    call delivers its stems beside the mix, which travels with it too; what is no bool is refused here, first"""
+    stems = mix.check_stems(stems)
     if tracks is None:
         mix.check_tracks(0, None, track_of, faders, track_sends)
         if buses is None and sends is not None:
@@ -381,7 +433,7 @@ def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per
         if not isinstance(buses, (list, tuple)) or not 1 <= len(buses) <= mix.BUS_MAX:
             raise ValueError(mix.BUS_COUNT % (len(buses) if isinstance(buses, (list, tuple)) else 0))
     return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master,
-                buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends)
+                buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems)
 
 
 def master_program(master, channels, sample_rate, bus=None):
@@ -460,6 +512,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     master = placing.pop("master", None)
     buses, sends = placing.pop("buses", None), placing.pop("sends", None)
     tracks, track_of, faders, track_sends = (placing.pop(k, None) for k in ("tracks", "track_of", "faders", "track_sends"))
+    stems = placing.pop("stems", False)
     mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
@@ -483,6 +536,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     channels = place.timeline_channels([runtime.descriptor_channels(uni.words) for uni, _ in grouped.parts], grouped.part_of)
     place.master = None if master is None else master_program(master, channels, rate)  # (behind every other check of the call)
     place.buses = place.sends = None  # (... and the buses, each a descriptor.Unified of one instance a channel, with the levels [buses, voices])
+    place.stems = stems  # (... whether the call delivers its stems)
     place.tracks = None  # (... and the tracks: (how many, track_of, track_programs' groups, faders, levels [buses, tracks]))
     if tracks is not None:
         track_of, faders, track_sends = mix.check_tracks(n, len(tracks), track_of, faders, track_sends, 0 if buses is None else len(buses), sends)
@@ -515,14 +569,14 @@ def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, devic
             circuits = [(prog, which, uni.params) for prog, (uni, which) in zip(programs[len(programs) - len(groups):], groups)]
             tracks = dict(n_tracks=n_tracks, track_of=track_of, programs=circuits, faders=faders, track_sends=track_sends)
         return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, master=master, buses=buses,
-                                      sends=getattr(place, "sends", None), tracks=tracks, **place.keywords())
+                                      sends=getattr(place, "sends", None), tracks=tracks, stems=getattr(place, "stems", False), **place.keywords())
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -577,9 +631,15 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     mix; tracks with isomorphic circuits are rendered as ONE program (track_programs).  faders (one finite number a track) scale the
     tracks' outputs, which are added to the direct voices' chain in order; with buses=, track_sends (float32 [buses, tracks]) is what
     each track gives to each bus, and sends= is refused: the buses hear the tracks, not the notes (mix.track_mix).
-    Whatever the placement, with or without a master."""
+    Whatever the placement, with or without a master.
+
+    stems=True: the call delivers a Stems — the direct mix (with tracks the voices that go straight to the mix, else the dry mix of
+    all voices), every track after its fader and every bus's return, each as the mix is delivered, beside the mix itself, which is
+    bit for bit the call's result without stems.  The stems are taken in front of the master; without a master they add up to the mix
+    (mix.stems says exactly how).  Every signal comes with its peak, and PCM frames get ONE gain from the largest of
+    them, so the files still add up.  One call, one delivery; every signal takes a timeline of device memory."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), _one_part)
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), _one_part)
 
 
 def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
@@ -587,22 +647,26 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
     if pcm is not None:
         _check_pcm(*pcm)
     grouped, n_total, onsets, lengths, gains, channels, place = _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, one_part)
+    run = lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format, normalise)
+    if place.stems:
+        names = mix.stem_names(place.tracks[0] if place.tracks is not None else 0, len(place.buses) if place.buses is not None else 0)
+        return _delivered_stems(pcm, grouped.sample_rate, n_total, channels, names, run)
     return _delivered(pcm, grouped.sample_rate, n_total, channels,
                       lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format, normalise))
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
-    """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData."""
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+    """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends), _one_part, (bit_depth, normalise))
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None):
-    """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav)."""
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+    """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems), bit_depth)
 
 
 class PcmData:

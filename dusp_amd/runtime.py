@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
+from .mix import check_stems, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,6 +36,7 @@ EXPORTS = [
     "dusp_render_host_score_piece",
     "dusp_render_host_score_piece_buses", "dusp_score_rows_send_device", "dusp_score_return_device",
     "dusp_render_host_score_piece_tracks", "dusp_score_tracks_mix_device",
+    "dusp_render_host_score_piece_stems", "dusp_score_stems_mix_device", "dusp_score_stems_return_device", "dusp_peak_common_device",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -122,6 +123,11 @@ def load():
     if hasattr(L, "dusp_render_host_score_piece_tracks"):  # (detected by symbol: DUSP_HIP_LIB may name a build from before tracks, for A/B runs)
         L.dusp_render_host_score_piece_tracks.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
         L.dusp_score_tracks_mix_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, ci, vp, vp, vp, vp]
+    if hasattr(L, "dusp_render_host_score_piece_stems"):  # (detected by symbol, as the tracks are)
+        L.dusp_render_host_score_piece_stems.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+        L.dusp_score_stems_mix_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, ci, vp, vp, vp, vp, vp]
+        L.dusp_score_stems_return_device.argtypes = [vp, vp, vp, sz, sz, ci, vp, vp, vp, vp]
+        L.dusp_peak_common_device.argtypes = [vp, vp, sz, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -173,6 +179,11 @@ class ScoreTracks(ctypes.Structure):
     f32 [n_tracks] and the tracks' levels into the buses f32 [n_buses][n_tracks]"""
     _fields_ = [("n_tracks", ctypes.c_size_t), ("h_track_of", ctypes.c_void_p), ("n_programs", ctypes.c_size_t), ("programs", ctypes.c_void_p),
                 ("h_faders", ctypes.c_void_p), ("h_track_sends", ctypes.c_void_p)]
+
+
+class ScoreStems(ctypes.Structure):
+    """dusp_score_stems: how many signals the caller has sized h_out and h_peaks for, 1 + tracks + buses + 1"""
+    _fields_ = [("n_signals", ctypes.c_size_t)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -480,8 +491,36 @@ class Context:
         self._check(self._L.dusp_score_tracks_mix_device(self._h, d_direct, ctypes.addressof(tracks), len(d_tracks), _ptr(faders), n_buses, _ptr(levels, n_buses), n_floats,
                                                          int(bool(raw)), d_out, d_feed_init, d_feed_out, stream))
 
+    def score_stems_mix(self, d_direct, d_tracks, n_floats, d_out, d_stems, faders=None, levels=None, d_feed_out=None, d_feed_init=None, raw=False, stream=None):
+        """score_tracks_mix with 0 .. 8 tracks, which also writes d_stems, f32 [1 + tracks][n_floats]: slot 0 d_direct || 0, slot 1 + g
+        term g || 0 (dusp_score_stems_mix_device; mix.track_terms and mix.stems are the contract).  d_stems aliases no other buffer."""
+        tracks = (ctypes.c_void_p * max(len(d_tracks), 1))(*d_tracks)
+        if faders is not None:
+            faders = np.ascontiguousarray(faders, dtype=np.float32)
+            if faders.shape != (len(d_tracks),):
+                raise ValueError(TRACKS_FADERS_SHAPE % len(d_tracks))
+        n_buses = 0
+        if levels is not None:
+            levels = np.ascontiguousarray(levels, dtype=np.float32)
+            if levels.ndim != 2 or levels.shape[1] != len(d_tracks):
+                raise ValueError(TRACKS_SENDS_SHAPE % (levels.shape[0] if levels.ndim == 2 else 0, len(d_tracks)))
+            n_buses = levels.shape[0]
+        self._check(self._L.dusp_score_stems_mix_device(self._h, d_direct, ctypes.addressof(tracks), len(d_tracks), _ptr(faders, len(d_tracks)), n_buses,
+                                                        _ptr(levels, n_buses and len(d_tracks)), n_floats, int(bool(raw)), d_out, d_feed_init, d_feed_out, d_stems, stream))
+
+    def score_stems_return(self, d_dry, d_wets, n_floats, d_out, d_stem_buses, d_stem_direct=None, raw=False, stream=None):
+        """score_return which also copies wet b into d_stem_buses + b * n_floats floats and, d_stem_direct given, writes d_dry || 0 there
+        (dusp_score_stems_return_device; mix.bus_return and mix.stems are the contract).  The slots alias no other buffer."""
+        wets = (ctypes.c_void_p * max(len(d_wets), 1))(*d_wets)
+        self._check(self._L.dusp_score_stems_return_device(self._h, d_dry, ctypes.addressof(wets), len(d_wets), n_floats, int(bool(raw)), d_out, d_stem_direct, d_stem_buses, stream))
+
+    def peak_common(self, d_peaks, n_peaks, d_common, stream=None):
+        """Device pointers: d_common[i] = the largest of d_peaks[0 .. n_peaks), compared as unsigned words, for every i < n_peaks
+        (dusp_peak_common_device; wav.common_peak): what encode() reads as d_peaks to give all instances one gain."""
+        self._check(self._L.dusp_peak_common_device(self._h, d_peaks, n_peaks, d_common, stream))
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None):
+                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None, stems=False):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -510,7 +549,12 @@ class Context:
         mix.track_mix is the contract) — voice k goes to track track_of[k], or with -1 straight to the mix; programs is a list of
         (program, [track numbers], params), each what a master is and ONE program for the tracks it lists, params its table
         [n_params][tracks x timeline channels]; a track in no program has no circuit.  faders: one finite f32 a track; track_sends:
-        f32 [buses][tracks], with buses, whose sends are then None.  Whatever the placement."""
+        f32 [buses][tracks], with buses, whose sends are then None.  Whatever the placement.
+        stems=True: the direct mix, every track and every bus return beside the mix (dusp_render_host_score_piece_stems; mix.stems is
+        the contract, mix.stem_names the order) -> (signals, peaks): signals [S + 1, channels, n_total] float32 without a format, else
+        [S + 1, n_total, channels(, 3)] frames under ONE gain (wav.encode_stems), the mix last and exactly what the call returns
+        without stems; peaks float32 [S + 1], every signal's own, whatever the format."""
+        stems = check_stems(stems)
         if tracks is not None:
             track_of, faders, track_sends = check_tracks(len(part_of), tracks["n_tracks"], tracks["track_of"], tracks.get("faders"), tracks.get("track_sends"),
                                                          0 if buses is None else len(buses), sends)
@@ -544,7 +588,7 @@ class Context:
             check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], place.pans)
         n_ch = place.channels(parts[0][0].n_out_channels)  # (parts that do not fit the placement: the library refuses them)
         voices = (table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data)
-        if master is not None or buses is not None or tracks is not None:
+        if master is not None or buses is not None or tracks is not None or stems:
             how = ScorePlacement(PLACE_KINDS[place.kind], _ptr(place.fracs), _ptr(place.pans), _ptr(place.comp), n_ch if place.kind == "space" else 0,
                                  _ptr(place.taps[0]) if place.taps else None, _ptr(place.taps[1]) if place.taps else None)
             through = None
@@ -569,6 +613,19 @@ class Context:
                 keep.append(prog._params_table(params, len(which) * n_ch, "dusp-hip: the params of track program %d must have shape" % p))
                 table_t[p] = ScoreTrackProgram(prog._h, len(which), which.ctypes.data, _ptr(keep[-1]))
             routed = ScoreTracks(tracks["n_tracks"], track_of.ctypes.data, len(served), ctypes.addressof(table_t), _ptr(faders), _ptr(track_sends))
+        if stems:
+            n_signals = 1 + (tracks["n_tracks"] if tracks is not None else 0) + (len(buses) if buses is not None else 0) + 1
+            if format is None:
+                fmt, normalise, out = 0, 0, self.host_empty((n_signals, n_ch, n_total_samples), pinned)
+            else:
+                fmt, normalise, out, _ = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned, batch=n_signals)
+            peaks, asked = np.empty(n_signals, dtype=np.float32), ScoreStems(n_signals)
+            self._check(self._L.dusp_render_host_score_piece_stems(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(routed) if tracks is not None else None,
+                                                                   ctypes.addressof(into) if buses is not None else None,
+                                                                   ctypes.addressof(through) if through is not None else None, ctypes.addressof(asked), n_total_samples,
+                                                                   int(tile_bytes), fmt, normalise, out.ctypes.data, peaks.ctypes.data))
+            return out, peaks
+        if tracks is not None:
             fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
             self._check(self._L.dusp_render_host_score_piece_tracks(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(routed),
                                                                     ctypes.addressof(into) if buses is not None else None,

@@ -149,3 +149,27 @@ def decode_wav(buf):
         raise WavError("dusp-hip: unsupported WAV sample format")
     fmt["channelData"] = np.ascontiguousarray(fr.reshape(-1, n_channels).T)
     return fmt
+
+
+def common_peak(peaks):
+    """The one peak of several signals: the largest of their peaks compared as unsigned bit patterns (a NaN wins) -> float32"""
+    peaks = np.ascontiguousarray(peaks, dtype=np.float32)
+    if peaks.size == 0:
+        return np.float32(0)
+    return np.array([np.max(peaks.view(np.uint32))], dtype=np.uint32).view(np.float32)[0]
+
+
+def encode_stems(stack, bit_depth=16, normalise=NORMALISE_NONE):
+    """The signals of a call with stems (mix.stems: float32 [S + 1, channels, samples]) -> (frames [S + 1, samples, channels] as
+    encode_frames makes them — int16, uint8 [.., 3] or float32 — and peaks float32 [S + 1], every signal's own over all its channels)
+    under ONE gain for all of them: gain(common_peak(peaks), normalise).  Delivered stems then still add up to the delivered mix, and
+    none clips where the mix does not.  normalise 0 is the quantiser a signal.  The device's bytes (dusp_render_host_score_piece_stems)."""
+    stack = np.ascontiguousarray(stack, dtype=np.float32)
+    if stack.ndim != 3:
+        raise WavError("dusp-hip: the stems are float32 of shape (signals, channels, samples)")
+    peaks = np.array([peak(x) for x in stack], dtype=np.float32)
+    g = gain(common_peak(peaks), normalise)
+    frames = np.transpose(stack, (0, 2, 1))
+    if bit_depth == 32:
+        return np.ascontiguousarray(scale_f32(frames, g)), peaks
+    return np.ascontiguousarray(pack(quantise(frames, g, bit_depth), bit_depth)), peaks

@@ -702,6 +702,42 @@ int dusp_score_tracks_mix_device(dusp_ctx *ctx, const float *d_direct, const flo
                                  const float *h_faders, size_t n_buses, const float *h_levels, size_t n_floats, int raw, float *d_out,
                                  const float *d_feed_init, float *d_feed_out, void *stream);
 
+/* Stems: the direct mix, every track and every bus return beside the mix, in the call's one delivery (additions to ABI v7, detected by
+ * symbol; dusp_amd/mix.py stems is the contract).  With T tracks (0 without `tracks`) and B buses (0 without `buses`)
+ * a call with stems delivers S + 1 = 1 + T + B + 1 signals of [C][n_total] f32, in this order:
+ *     0            direct   direct || 0: with tracks the raw chain over the voices that go straight to the mix, else the raw dry chain
+ *     1 .. T       track g  term_g || 0, term_g = faders ? f32(y_g * f_g) : y_g as the mix of the tracks forms it
+ *     T+1 .. T+B   bus b    the bus's output as its own copy-out left it
+ *     S            mix      the call's output exactly as without stems (behind the master where there is one; the stems are in front)
+ * `|| 0`: NaN and -0 leave as +0.  Without a master and without NaN in the raw signals the first S, added left-deep in f32, `|| 0`, are
+ * the mix bit for bit.  h_out: n_signals instances of what the call delivers without stems (planar f32 [C][n_total], or frames
+ * [n_total][C] of `format`).  With normalise 1 or 2 ALL signals get the gain of the largest of their peaks, so delivered stems still
+ * add up to the delivered mix; normalise 0 is the quantiser a signal.  h_peaks (f32 [n_signals] or NULL): every signal's own peak,
+ * whatever the format, planar f32 included.  The signals take n_signals x C x n_total floats of device memory on top of the call's,
+ * and as much staging for encoded frames.
+ * stems NULL: dusp_render_host_score_piece_tracks under this entry's name.  Refused before anything renders, on top of that entry's
+ * refusals: n_signals that is not 1 + n_tracks + n_buses + 1 (both numbers named), h_out NULL, n_signals x C x n_total beyond 2^31. */
+typedef struct dusp_score_stems {
+    size_t n_signals; /* must be 1 + n_tracks + n_buses + 1: the caller has sized h_out and h_peaks */
+} dusp_score_stems;
+int dusp_render_host_score_piece_stems(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                       const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                       const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                       const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems,
+                                       size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks);
+/* dusp_score_tracks_mix_device with n_tracks 0 .. 8, which also writes d_stems, f32 [1 + n_tracks][n_floats]: slot 0 = d_direct || 0,
+ * slot 1 + g = term_g || 0.  d_stems aliases no other buffer; the wide path needs every slot on a 16-byte boundary too. */
+int dusp_score_stems_mix_device(dusp_ctx *ctx, const float *d_direct, const float *const *h_tracks, size_t n_tracks,
+                                const float *h_faders, size_t n_buses, const float *h_levels, size_t n_floats, int raw, float *d_out,
+                                const float *d_feed_init, float *d_feed_out, float *d_stems, void *stream);
+/* dusp_score_return_device which also copies wet b into d_stem_buses + b * n_floats (f32 [n_buses][n_floats]) and, d_stem_direct
+ * given, writes d_dry || 0 there.  The slots alias no other buffer. */
+int dusp_score_stems_return_device(dusp_ctx *ctx, const float *d_dry, const float *const *h_wets, size_t n_buses, size_t n_floats, int raw,
+                                   float *d_out, float *d_stem_direct, float *d_stem_buses, void *stream);
+/* d_common[i] = the largest of d_peaks[0 .. n_peaks) for every i (dusp_peak_device's words, compared as unsigned bit patterns: any NaN
+ * wins), 1 <= n_peaks <= 2^24: what dusp_encode_device reads as d_peaks to give n_peaks instances one gain.  d_common is not d_peaks. */
+int dusp_peak_common_device(dusp_ctx *ctx, const float *d_peaks, size_t n_peaks, float *d_common, void *stream);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

@@ -41,6 +41,11 @@
           and against the return kernel over as many input buffers (T <= 4).  Then the piece with eight Filter tracks as ONE
           program of eight instances on the host's clock, beside the piece with the same Filter as its master, the piece
           alone, and eight calls with the Filter as the master one after the other.  A report: no ratio is fixed in advance.
+  stems   (--stems; profiles/score_stems.txt) the stems mix kernel (dusp_score_stems_mix_device) over one channel of
+          the piece's timeline at T = 8 tracks with faders and B = 2 buses against the mix kernel of the tracks over the same inputs,
+          and the stems return kernel against the return kernel.  Then the piece with eight fader groups and two stateless buses
+          on the host's clock: with stems, without, and the eleven single-stem calls (all faders but one 0) the call with stems
+          replaces, one after the other.  A report: no ratio is fixed in advance.
 
 Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
 """
@@ -517,6 +522,83 @@ def tracks(scale, ctxs, reps):
     prog.close()
 
 
+def stems(scale, ctxs, reps):
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR
+    T, B = 8, 2
+    d.configure(SR)
+    ctx = ctxs["default"]
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+
+    def median_of(call):
+        kernel = []
+        for r in range(reps + 1):
+            call()
+            if r:
+                kernel.append(ctx.score_last_ms()[0])
+        return float(np.median(kernel)), min(kernel), max(kernel)
+
+    print("stems: one channel of %d samples (%.1f MB a timeline), T = %d tracks with faders, B = %d buses; kernels alone by HIP events (dusp_score_last_ms), median, fastest and slowest of %d after a warm-up"
+          % (nt, nt * 4 / 1e6, T, B, reps), flush=True)
+    line = "  %-78s median %8.3f ms  fastest %8.3f  slowest %8.3f%s"
+    bufs = [torch.randn(nt, dtype=torch.float32, device="cuda") for _ in range(1 + T)]
+    out, feeds = torch.empty(nt, dtype=torch.float32, device="cuda"), torch.empty((B, nt), dtype=torch.float32, device="cuda")
+    slots = torch.empty((1 + T, nt), dtype=torch.float32, device="cuda")
+    rs = np.random.RandomState(4)
+    faders, levels = rs.random_sample(T).astype(np.float32), rs.random_sample((B, T)).astype(np.float32)
+    ys = [b.data_ptr() for b in bufs[1:]]
+    torch.cuda.synchronize()
+    mb = lambda read, written: (read * nt * 4 / 1e6, written * nt * 4 / 1e6)
+    old = median_of(lambda: ctx.score_tracks_mix(bufs[0].data_ptr(), ys, nt, out.data_ptr(), faders, levels, feeds.data_ptr(), stream=s))
+    print(line % (("dusp_score_tracks_kernel (%.0f MB read, %.0f MB written)" % mb(1 + T, 1 + B),) + old + ("",)), flush=True)
+    new = median_of(lambda: ctx.score_stems_mix(bufs[0].data_ptr(), ys, nt, out.data_ptr(), slots.data_ptr(), faders, levels, feeds.data_ptr(), stream=s))
+    print(line % (("dusp_score_stems_mix_kernel, 1 + T slots more (%.0f MB read, %.0f MB written)" % mb(1 + T, 1 + B + 1 + T),) + new + ("   x%.2f of the mix kernel" % (new[0] / old[0]),)), flush=True)
+    wets = ys[:B]
+    old = median_of(lambda: ctx.score_return(bufs[0].data_ptr(), wets, nt, out.data_ptr(), stream=s))
+    print(line % (("dusp_score_return_kernel (%.0f MB read, %.0f MB written)" % mb(1 + B, 1),) + old + ("",)), flush=True)
+    new = median_of(lambda: ctx.score_stems_return(bufs[0].data_ptr(), wets, nt, out.data_ptr(), slots.data_ptr() + 4 * nt, stream=s))
+    print(line % (("dusp_score_stems_return_kernel, B slots more (%.0f MB read, %.0f MB written)" % mb(1 + B, 1 + B),) + new + ("   x%.2f of the return kernel" % (new[0] / old[0]),)), flush=True)
+    new = median_of(lambda: ctx.score_stems_return(bufs[0].data_ptr(), wets, nt, out.data_ptr(), slots.data_ptr() + 4 * nt, slots.data_ptr(), stream=s))
+    print(line % (("dusp_score_stems_return_kernel, the direct slot too (%.0f MB read, %.0f MB written)" % mb(1 + B, 2 + B),) + new + ("   x%.2f of the return kernel" % (new[0] / old[0]),)), flush=True)
+    del bufs, out, feeds, slots
+    # the whole call: eight fader groups, two stateless buses (a gain each), no master
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    prog = ctx.build(uni.words)
+    buses = [ctx.build(descriptor.extract(d.Multiply(d.MasterInput(), g)).words) for g in (0.5, 0.25)]
+    track_of = (np.arange(V) % T).astype(np.int32)
+    S = 1 + T + B
+
+    def call(f, **kw):
+        res = ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, buses=[(b, None) for b in buses],
+                                     tracks=dict(n_tracks=T, track_of=track_of, programs=[], faders=f, track_sends=levels), **kw)
+        del res
+
+    def host_clock(run):
+        times = []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            run()
+            times.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(times[1:])), min(times[1:]), max(times[1:])
+
+    print("  %d notes of %d samples over %d samples, one channel, planar f32 into pinned memory, host clock, median, fastest and slowest of %d after a warm-up" % (V, nv, nt, reps), flush=True)
+    row = "  render_score_parts, %-70s median %9.2f ms  fastest %9.2f  slowest %9.2f%s"
+    plain = host_clock(lambda: call(faders))
+    print(row % (("eight fader groups, two buses, no stems (%.0f MB delivered)" % (nt * 4 / 1e6),) + plain + ("",)), flush=True)
+    with_stems = host_clock(lambda: call(faders, stems=True))
+    print(row % (("the same with stems: %d signals (%.0f MB delivered)" % (S + 1, (S + 1) * nt * 4 / 1e6),) + with_stems + ("   x%.2f of the call without" % (with_stems[0] / plain[0]),)), flush=True)
+    single = [np.where(np.arange(T) == g, faders, 0).astype(np.float32) for g in range(T)] + [np.zeros(T, dtype=np.float32)] * (1 + B)  # (a track alone; the direct mix and each bus alone: no track)
+    apart = host_clock(lambda: [call(f) for f in single])
+    print(row % (("the %d single-stem calls it replaces, one after the other" % S,) + apart + ("   x%.2f of the call with stems" % (apart[0] / with_stems[0]),)), flush=True)
+    for b in buses:
+        b.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -529,6 +611,7 @@ def main():
     ap.add_argument("--master", action="store_true", help="the master-bus leg alone: the piece with and without a master")
     ap.add_argument("--sends", action="store_true", help="the effect-send leg alone: the send and return kernels, and the piece with and without a bus")
     ap.add_argument("--tracks", action="store_true", help="the tracks leg alone: the mix kernel beside the fill and the return kernel, and eight Filter tracks as one program")
+    ap.add_argument("--stems", action="store_true", help="the stems leg alone: the stems mix and return kernels beside the kernels they extend, and the piece with and without stems")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
@@ -538,6 +621,8 @@ def main():
         return sends(a.scale, ctxs, a.reps)
     if a.tracks:
         return tracks(a.scale, ctxs, a.reps)
+    if a.stems:
+        return stems(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
