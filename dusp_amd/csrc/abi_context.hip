@@ -123,6 +123,9 @@ void dusp_ctx_destroy(dusp_ctx *ctx) {
     }
     if (ctx->d_tables) (void)hipFree(ctx->d_tables);
     if (ctx->d_score_plan) (void)hipFree(ctx->d_score_plan);
+    if (ctx->d_meter) (void)hipFree(ctx->d_meter);
+    for (hipEvent_t ev : ctx->meter_marks)
+        if (ev) (void)hipEventDestroy(ev);
     if (ctx->score_uploaded) (void)hipEventDestroy(ctx->score_uploaded);
     if (ctx->score_done) (void)hipEventDestroy(ctx->score_done);
     for (hipEvent_t ev : {ctx->score_up0, ctx->score_t0, ctx->score_t1})

@@ -7,6 +7,7 @@
 //   abi_deliver.hip     interleave / peak / encode, host renders and their delivery
 //   abi_mix.hip         mix of a batch on the device, the tiles of a large batch, the host render of a mix
 //   abi_score.hip       scores: plans' image, the one launch path, device entries and host renders of scores and pieces
+//   abi_meter.hip       meters: RMS and BS.1770 loudness of signals on the device, and the gates on the host
 #pragma once
 #include <limits>
 #include <cmath>
@@ -28,6 +29,7 @@
 #include "device_types.hpp"
 #include "fused_plan.hpp"
 #include "jit_codegen.hpp"
+#include "meter_plan.hpp"
 #include "program.hpp"
 #include "score_plan.hpp"
 
@@ -76,6 +78,8 @@ hipError_t launch_score_stems_mix(const float *d_direct, const float *const *d_t
 hipError_t launch_score_stems_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, float *d_stem_direct, float *const *d_stem_buses, uint64_t n,
                                      int raw, hipStream_t stream);
 hipError_t launch_pcm_peak_common(const float *d_peaks, float *d_common, uint32_t n, hipStream_t stream);
+hipError_t launch_meter(const float *d_planar, uint32_t n_signals, uint32_t n_channels, uint64_t n, uint32_t hop, const MeterCoef &k, double *d_scratch, double *d_sumsq,
+                        double *d_hops, hipStream_t stream, hipEvent_t *marks);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -122,6 +126,12 @@ struct dusp_ctx {
     hipEvent_t score_up0 = nullptr, score_t0 = nullptr, score_t1 = nullptr;
     double score_plan_ms = 0;
     bool score_timed = false, score_upload_timed = false;
+    // the meters' scratch (abi_meter.hip; meter_plan.hpp MeterGeometry says what lies where), grown on demand, with the call's sums
+    // behind it where the caller gave no device memory for them; and the events around the passes of the last dusp_meter_device call
+    double *d_meter = nullptr;
+    size_t meter_cap = 0;  // doubles
+    hipEvent_t meter_marks[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool meter_timed = false;
 };
 
 // DUSP_GUARD=1 (tests): every device allocation of the library carries guard bytes behind its end, filled with a pattern and
@@ -414,6 +424,18 @@ inline int check_planar_pcm(dusp_ctx *ctx, const char *who, size_t n_instances, 
 // the signals of one call — their peaks are taken whatever the format (h_peaks: all of them), and what normalises is the largest.
 int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
                  int normalise, float *h_peaks, void *h_out, bool common_peak = false);
+
+// abi_meter.hip
+// What a call may be metered at: refuses a sample rate below 8000 and shapes the kernels do not take, in `who`'s name
+int meter_check(dusp_ctx *ctx, const char *who, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate);
+// The meters of d_planar [n_signals][n_channels][n_samples] on `stream`: the sums stay on the device, in the context's scratch, until
+// meter_finish — which waits for the stream — turns them into h_rms [n_signals][n_channels], h_lufs [n_signals] and (optional)
+// h_momentary [n_signals][n_blocks].  The caller has run meter_check.
+int meter_launch(dusp_ctx *ctx, const float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, hipStream_t stream);
+int meter_finish(dusp_ctx *ctx, const char *who, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, hipStream_t stream, double *h_rms, double *h_lufs,
+                 double *h_momentary);
+// the scratch of a call, grown on demand: `extra` doubles behind what the kernels take
+int meter_scratch(dusp_ctx *ctx, size_t rows, size_t n_samples, uint32_t hop, size_t extra, dusp::MeterGeometry &G);
 
 // abi_mix.hip
 constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)

@@ -6,7 +6,9 @@
 // with the device entries dusp_score_rows_send_device and dusp_score_return_device; dusp_render_host_score_piece_tracks, which adds
 // tracks: sub-mixes of the piece through circuits of their own, DESIGN.md 6.16, with the device entry dusp_score_tracks_mix_device;
 // dusp_render_host_score_piece_stems, which delivers the direct mix, every track and every bus return beside the mix, DESIGN.md 6.17,
-// with the device entries dusp_score_stems_mix_device, dusp_score_stems_return_device and dusp_peak_common_device).
+// with the device entries dusp_score_stems_mix_device, dusp_score_stems_return_device and dusp_peak_common_device;
+// dusp_render_host_score_piece_meters, which also meters what it delivers, DESIGN.md 6.18, with the device entry dusp_meter_device —
+// abi_meter.hip has the rest of the meters).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -357,12 +359,34 @@ static int score_device_call(dusp_ctx *ctx, hipStream_t stream, bool voices, con
     return DUSP_OK;
 }
 
+// ---- the meters of a delivery (abi_meter.hip) ----
+
+struct ScoreMetered {  // what a call with meters asked for, and the rate its signals are metered at
+    const dusp_score_meters *ask;
+    uint32_t sample_rate;
+};
+
+// deliver_host of a block that no kernel writes any more, [n_signals][n_ch][n_total] — metered on the way where the call has meters: the
+// meter kernels run on the context's stream in front of the peak and encode kernels, over the f32 signals in front of the PCM gain, and
+// what they leave is gated once the delivery has waited for the stream
+static int deliver_metered(dusp_program *prog, const char *who, const ScoreMetered *metered, const float *d_block, size_t n_signals, size_t n_ch, size_t n_total, int format,
+                           int normalise, float *h_peaks, void *h_out, bool common_peak) {
+    dusp_ctx *ctx = prog->ctx;
+    if (metered)
+        if (int rc = meter_launch(ctx, d_block, n_signals, n_ch, n_total, metered->sample_rate, ctx->stream)) return rc;
+    if (int rc = deliver_host(prog, d_block, nullptr, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak)) return rc;
+    if (metered)
+        if (int rc = meter_finish(ctx, who, n_signals, n_ch, n_total, metered->sample_rate, ctx->stream, metered->ask->h_rms, metered->ask->h_lufs, metered->ask->h_momentary)) return rc;
+    return DUSP_OK;
+}
+
 // What a host render ends with once its tiles are added to the timeline's running sums (prog->d_mix, [n_ch][n_total]): `|| 0` over the
 // whole timeline — a launch of `kind` without voices — the delivery, which waits for the stream, and the guard check
-static int score_deliver_host(dusp_program *prog, const char *who, ScoreKind kind, size_t n_ch, size_t n_total, int format, int normalise, float *h_peak, void *h_out) {
+static int score_deliver_host(dusp_program *prog, const char *who, ScoreKind kind, size_t n_ch, size_t n_total, int format, int normalise, float *h_peak, void *h_out,
+                              const ScoreMetered *metered = nullptr) {
     dusp_ctx *ctx = prog->ctx;
     if (int rc = score_launch(ctx, ScoreLaunch(kind, n_total), n_ch, n_total, nullptr, prog->d_mix.p, /*raw=*/0, prog->d_mix.p, ctx->stream, nullptr, 0)) return rc;
-    if (int rc = deliver_host(prog, prog->d_mix.p, nullptr, 1, n_ch, n_total, format, normalise, h_peak, h_out)) return rc;
+    if (int rc = deliver_metered(prog, who, metered, prog->d_mix.p, 1, n_ch, n_total, format, normalise, h_peak, h_out, false)) return rc;
     if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
         CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
     return DUSP_OK;
@@ -556,13 +580,13 @@ static int score_tracks_guards(dusp_program *prog, const char *who, const dusp_s
 // of instance c; its render from its initial state, deciding as a tile of a mix decides (it waits for its compiled kernel), applies
 // `|| 0` at its own copy-out; then the delivery from the master's buffer, which waits for the stream, and the guard checks
 static int score_master_deliver_host(dusp_program *prog, const char *who, const dusp_score_master *master, size_t n_ch, size_t n_total, int format, int normalise, float *h_peak,
-                                     void *h_out) {
+                                     void *h_out, const ScoreMetered *metered = nullptr) {
     dusp_ctx *ctx = prog->ctx;
     dusp_program *m = master->prog;
     {
         TiledBatch channels(m, n_ch, master->h_params, nullptr, n_ch);  // (one tile: all channels; what changes bits is decided as for a mix)
         if (int rc = channels.render_tile(0, n_ch, n_total, prog->d_mix.p)) return rc;
-        if (int rc = deliver_host(prog, m->d_host_out.p, nullptr, 1, n_ch, n_total, format, normalise, h_peak, h_out)) return rc;
+        if (int rc = deliver_metered(prog, who, metered, m->d_host_out.p, 1, n_ch, n_total, format, normalise, h_peak, h_out, false)) return rc;
         channels.staged = false;  // (the delivery has waited for the stream)
     }
     if (g_guard_bytes && (!prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
@@ -578,7 +602,7 @@ static int score_master_deliver_host(dusp_program *prog, const char *who, const 
 // d_mix as ever: the master's render over it (score_master_deliver_host says how) is copied device to device into the last slot.  Then
 // ONE delivery of the block as n_signals instances of n_ch channels, under one gain (deliver_host's common_peak), and the guard checks.
 static int score_stems_deliver_host(dusp_program *prog, const char *who, const dusp_score_master *master, size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise,
-                                    float *h_peaks, void *h_out) {
+                                    float *h_peaks, void *h_out, const ScoreMetered *metered = nullptr) {
     dusp_ctx *ctx = prog->ctx;
     const size_t timeline = n_ch * n_total;
     std::unique_ptr<TiledBatch> channels;
@@ -587,7 +611,7 @@ static int score_stems_deliver_host(dusp_program *prog, const char *who, const d
         if (int rc = channels->render_tile(0, n_ch, n_total, prog->d_mix.p)) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(prog->d_stems.p + (n_signals - 1) * timeline, master->prog->d_host_out.p, timeline * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    if (int rc = deliver_host(prog, prog->d_stems.p, nullptr, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, /*common_peak=*/true)) return rc;
+    if (int rc = deliver_metered(prog, who, metered, prog->d_stems.p, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, /*common_peak=*/true)) return rc;
     if (channels) channels->staged = false;  // (the delivery has waited for the stream)
     if (g_guard_bytes && (!prog->d_stems.intact() || !prog->d_host_peak_common.intact() || !prog->d_mix.intact() || !prog->d_mix_gains.intact() || !score_plan_intact(ctx)))
         CTX_FAIL(ctx, DUSP_ERR_HIP, std::string(who) + ": the score kernel wrote past the end of a device buffer: guard bytes overwritten");
@@ -757,7 +781,7 @@ int dusp_score_rows_pan_device(dusp_ctx *ctx, const float *const *h_rows, const 
 static int render_host_score_parts(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const ScorePlacement &given, size_t n_total_samples, size_t tile_bytes, int format,
                                    int normalise, void *h_out, float *h_peak, const dusp_score_master *master = nullptr, const dusp_score_buses *buses = nullptr,
-                                   const dusp_score_tracks *tracks = nullptr, const dusp_score_stems *stems = nullptr) {
+                                   const dusp_score_tracks *tracks = nullptr, const dusp_score_stems *stems = nullptr, const dusp_score_meters *meters = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_program *prog0 = parts[0].prog;  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx = prog0->ctx;
@@ -810,6 +834,21 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the stems' n_signals is " + std::to_string(stems->n_signals) + ", the call delivers " + std::to_string(n_signals) + ": the direct mix, " +
                                         std::to_string(n_stem_tracks) + " tracks, " + std::to_string(n_stem_buses) + " buses and the mix");
     if (stems && !h_out) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": h_out is NULL: a call with stems delivers its " + std::to_string(n_signals) + " signals there");
+    // (with meters: every signal of the delivery, at the parts' sample rate)
+    const ScoreMetered metered_as{meters, (uint32_t)prog0->P.g.sample_rate}, *metered = meters ? &metered_as : nullptr;
+    if (meters) {
+        const size_t n_metered = stems ? n_signals : 1, n_blocks = dusp::meter_blocks(n_total_samples, metered_as.sample_rate);
+        if (metered_as.sample_rate < dusp::kMeterRateMin)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": meters need a sample rate of at least 8000 Hz, not " + std::to_string(metered_as.sample_rate) + ": the K-weighting's shelf lies at 1682 Hz");
+        if (meters->n_signals != n_metered)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the meters' n_signals is " + std::to_string(meters->n_signals) + ", the call delivers " + std::to_string(n_metered) +
+                                            (stems ? ": its stems and the mix" : ": the mix"));
+        if (meters->n_blocks != n_blocks)
+            CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the meters' n_blocks is " + std::to_string(meters->n_blocks) + ", a timeline of " + std::to_string(n_total_samples) + " samples at " +
+                                            std::to_string(metered_as.sample_rate) + " Hz has " + std::to_string(n_blocks) + " blocks (dusp_meter_blocks)");
+        if (!meters->h_rms) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the meters' h_rms is NULL: every signal's RMS a channel goes there");
+        if (!meters->h_lufs) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the meters' h_lufs is NULL: every signal's loudness goes there");
+    }
     if (!samples_in_range(n_total_samples) || n_out_ch * n_total_samples > dusp::kScoreRowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the timeline must have 1..2^31 samples and channels x timeline samples must not exceed 2^31: render such a piece in windows of the timeline");
     if (stems && n_signals * n_out_ch * n_total_samples > dusp::kScoreRowMax)
@@ -1009,10 +1048,10 @@ static int render_host_score_parts(const char *who, const dusp_score_part *parts
                                                   /*raw=*/master != nullptr, ctx->stream));
     // (`|| 0` is the rows kernel's over the timeline's channels, panned or not; behind a master it is the master's own copy-out's; behind
     // buses without a master the return kernel has applied it, behind tracks without either the mix kernel)
-    if (int rc = stems             ? score_stems_deliver_host(prog0, who, master, n_signals, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
-                 : master          ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
-                 : buses || tracks ? deliver_host(prog0, prog0->d_mix.p, nullptr, 1, n_out_ch, n_total_samples, format, normalise, h_peak, h_out)
-                                   : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out))
+    if (int rc = stems             ? score_stems_deliver_host(prog0, who, master, n_signals, n_out_ch, n_total_samples, format, normalise, h_peak, h_out, metered)
+                 : master          ? score_master_deliver_host(prog0, who, master, n_out_ch, n_total_samples, format, normalise, h_peak, h_out, metered)
+                 : buses || tracks ? deliver_metered(prog0, who, metered, prog0->d_mix.p, 1, n_out_ch, n_total_samples, format, normalise, h_peak, h_out, false)
+                                   : score_deliver_host(prog0, who, ScoreKind::rows, n_out_ch, n_total_samples, format, normalise, h_peak, h_out, metered))
         return rc;
     waited();  // (the delivery has waited for the stream)
     for (auto &b : returned) b->staged = false;
@@ -1096,7 +1135,7 @@ int dusp_render_host_score_parts_stereo(const dusp_score_part *parts, size_t n_p
 static int render_host_score_piece(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
                                    const int64_t *h_lengths, const float *h_gains, const dusp_score_placement *placement, const dusp_score_buses *buses,
                                    const dusp_score_master *master, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peak,
-                                   const dusp_score_tracks *tracks = nullptr, const dusp_score_stems *stems = nullptr) {
+                                   const dusp_score_tracks *tracks = nullptr, const dusp_score_stems *stems = nullptr, const dusp_score_meters *meters = nullptr) {
     if (!parts || !n_parts || !parts[0].prog) return DUSP_ERR_ARG;
     dusp_ctx *ctx = parts[0].prog->ctx;
     const dusp_score_placement plain{DUSP_PLACE_ROWS, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
@@ -1118,7 +1157,7 @@ static int render_host_score_piece(const char *who, const dusp_score_part *parts
         CTX_FAIL(ctx, DUSP_ERR_ARG, std::string(who) + ": the placement's kind must be DUSP_PLACE_ROWS (0), DUSP_PLACE_PAN (1), DUSP_PLACE_SPACE (2) or DUSP_PLACE_STEREO (3)");
     }
     return render_host_score_parts(who, parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, place, n_total_samples, tile_bytes, format, normalise, h_out, h_peak,
-                                   master, buses, tracks, stems);
+                                   master, buses, tracks, stems, meters);
 }
 
 int dusp_render_host_score_piece(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
@@ -1151,6 +1190,16 @@ int dusp_render_host_score_piece_stems(const dusp_score_part *parts, size_t n_pa
                                        void *h_out, float *h_peaks) {
     return render_host_score_piece("dusp_render_host_score_piece_stems", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, buses, master,
                                    n_total_samples, tile_bytes, format, normalise, h_out, h_peaks, tracks, stems);
+}
+
+// ... and with meters: the RMS and the loudness of every signal the call delivers (meters NULL: dusp_render_host_score_piece_stems under
+// this entry's name)
+int dusp_render_host_score_piece_meters(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                        const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks, const dusp_score_buses *buses,
+                                        const dusp_score_master *master, const dusp_score_stems *stems, const dusp_score_meters *meters, size_t n_total_samples, size_t tile_bytes,
+                                        int format, int normalise, void *h_out, float *h_peaks) {
+    return render_host_score_piece("dusp_render_host_score_piece_meters", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, buses, master,
+                                   n_total_samples, tile_bytes, format, normalise, h_out, h_peaks, tracks, stems, meters);
 }
 
 // The send chain alone (score_send_engine.hip): dusp_score_rows_device — h_pans: dusp_score_rows_pan_device, mono rows into two
@@ -1316,6 +1365,36 @@ int dusp_peak_common_device(dusp_ctx *ctx, const float *d_peaks, size_t n_peaks,
             HIP_TRY(ctx, dusp::launch_pcm_peak_common(d_peaks, d_common, (uint32_t)n_peaks, stream));
             return DUSP_OK;
         });
+    });
+}
+
+// The meter kernels alone (meter_engine.hip): the sums of squares and the K-weighted hop sums of signals on the device
+int dusp_meter_device(dusp_ctx *ctx, const float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double *d_sumsq, double *d_hops,
+                      void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    const char *who = "dusp_meter_device";
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    if (!d_planar || !d_sumsq || !d_hops) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (int rc = meter_check(ctx, who, n_signals, n_channels, n_samples, sample_rate)) return rc;
+    if (((uintptr_t)d_planar & 3) || (((uintptr_t)d_sumsq | (uintptr_t)d_hops) & 7)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": d_planar must be 4-byte aligned, d_sumsq and d_hops 8-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_of(ctx, stream_);
+    dusp::MeterGeometry G;
+    if (int rc = meter_scratch(ctx, n_signals * n_channels, n_samples, dusp::meter_hop(sample_rate), 0, G)) return rc;
+    for (hipEvent_t &ev : ctx->meter_marks)
+        if (!ev) HIP_TRY(ctx, hipEventCreate(&ev));
+    ctx->meter_timed = false;
+    const ScoreLaunch none(ScoreKind::rows);  // (no plan: timed like any other launch)
+    const int rc = score_device_call(
+        ctx, stream, false, none, []() { return DUSP_OK; },
+        [&]() {
+            HIP_TRY(ctx, dusp::launch_meter(d_planar, (uint32_t)n_signals, (uint32_t)n_channels, n_samples, dusp::meter_hop(sample_rate), dusp::meter_k_weighting(sample_rate),
+                                            ctx->d_meter, d_sumsq, d_hops, stream, ctx->meter_marks));
+            return DUSP_OK;
+        });
+    ctx->meter_timed = rc == DUSP_OK;
+    return rc;
     });
 }
 

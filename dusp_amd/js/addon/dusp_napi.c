@@ -16,6 +16,11 @@
  *         -> Promise: the same with tracks, sub-mixes through circuits of their own (dusp_render_host_score_piece_tracks)
  *   renderPieceStems(the same thirty-one — nTracks may be 0 and what follows it null: no tracks)
  *         -> Promise<{ data, peaks }>: the same, delivering the stems beside the mix (dusp_render_host_score_piece_stems)
+ *   renderPieceMeters(the same thirty-one, stems, nBlocks)
+ *         -> Promise<{ data, peaks, rms, lufs, momentary }>: the same, with stems or without, metering what it delivers
+ *            (dusp_render_host_score_piece_meters)
+ *   meter(ctx, Float32Array planar, nSignals, nChannels, nSamples, sampleRate) -> { rms, lufs, momentary }: the meters of signals in host
+ *         memory (dusp_meter_host)
  *   descriptorChannels(Float64Array words) -> the circuit's output channels (host code only: no context)
  *   programDestroy(prog), ctxDestroy(ctx), version(), abiVersion()
  * Failures surface the way the reference's do: synchronous calls THROW A STRING, render() REJECTS
@@ -784,6 +789,9 @@ typedef struct {
     int with_stems;       /* renderPieceStems (dusp_render_host_score_piece_stems): out holds n_signals signals, the mix last, and every one has a peak */
     size_t n_signals;
     float peaks[16];      /* (1 + 8 tracks + 4 buses + 1 at the most) */
+    int with_meters, stems_asked; /* renderPieceMeters (dusp_render_host_score_piece_meters): the result is boxed as with stems, of one signal where stems_asked is 0; */
+    size_t n_blocks, n_channels;  /* ... what the caller says the timeline's blocks are (the library checks), the timeline's channels, */
+    double *m_rms, *m_lufs, *m_momentary; /* ... and the meters: [n_signals][n_channels], [n_signals], [n_signals][n_blocks] */
     int format, normalise, rc;
     char err[512];
 } piece_job;
@@ -822,6 +830,9 @@ static void piece_free(napi_env env, piece_job *j) {
     free(j->delays);
     free(j->tap_gains);
     free(j->out);
+    free(j->m_rms);
+    free(j->m_lufs);
+    free(j->m_momentary);
     free(j);
 }
 static void piece_execute(napi_env env, void *data) {
@@ -870,7 +881,12 @@ static void piece_execute(napi_env env, void *data) {
             dusp_score_buses buses = {j->n_buses, circuits, j->sends};
             dusp_score_tracks tracks = {j->n_tracks, j->track_of, j->n_tprogs, served, j->faders, j->track_sends};
             dusp_score_stems stems = {j->n_signals};
-            if (j->with_stems)
+            dusp_score_meters meters = {j->n_signals, j->n_blocks, j->m_rms, j->m_lufs, j->m_momentary};
+            if (j->with_meters)
+                j->rc = dusp_render_host_score_piece_meters(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, j->with_tracks ? &tracks : NULL,
+                                                            j->n_buses ? &buses : NULL, j->master_pb ? &master : NULL, j->stems_asked ? &stems : NULL, &meters, j->n_total, j->tile_bytes,
+                                                            j->format, j->normalise, j->out, j->peaks);
+            else if (j->with_stems)
                 j->rc = dusp_render_host_score_piece_stems(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, j->with_tracks ? &tracks : NULL,
                                                            j->n_buses ? &buses : NULL, j->master_pb ? &master : NULL, &stems, j->n_total, j->tile_bytes, j->format, j->normalise,
                                                            j->out, j->peaks);
@@ -934,6 +950,18 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
             napi_set_named_property(env, result, "data", data);
             napi_set_named_property(env, result, "peaks", peaks);
             ok = 1;
+            if (j->with_meters) { /* ... and rms, lufs, momentary: Float64Arrays */
+                const char *names[3] = {"rms", "lufs", "momentary"};
+                const double *from[3] = {j->m_rms, j->m_lufs, j->m_momentary};
+                const size_t counts[3] = {j->n_signals * j->n_channels, j->n_signals, j->n_signals * j->n_blocks};
+                for (int m = 0; m < 3 && ok; m++) {
+                    napi_value mab, arr;
+                    void *mem;
+                    ok = napi_create_arraybuffer(env, counts[m] * sizeof(double), &mem, &mab) == napi_ok &&
+                         napi_create_typedarray(env, napi_float64_array, counts[m], mab, 0, &arr) == napi_ok && napi_set_named_property(env, result, names[m], arr) == napi_ok;
+                    if (ok && counts[m]) memcpy(mem, from[m], counts[m] * sizeof(double));
+                }
+            }
         }
     } else if (j->rc == DUSP_OK && j->format) { /* { data: Buffer over the encoded frames, peaks: Float32Array(1) } */
         napi_value buf, peaks_ab, peaks;
@@ -1002,12 +1030,13 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *      1 + nTracks + nBuses + 1 signals one behind the other (a Float32Array of planar f32, or a Buffer of frames under ONE gain), the mix last, peaks a
  *      Float32Array of every signal's own peak */
 static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master, 6 ... and buses */
-    napi_value argv[31];
+    napi_value argv[33];
     char msg[256];
-    const int with_stems = form == 8; /* (renderPieceStems: renderPieceTracks' arguments, the tracks among them or not) */
+    const int with_meters = form == 9; /* (renderPieceMeters: renderPieceStems' arguments, then whether the stems are asked for and the blocks of the timeline) */
+    const int with_stems = form == 8 || with_meters; /* (renderPieceStems: renderPieceTracks' arguments, the tracks among them or not) */
     int with_tracks = form == 7;
     if (with_tracks || with_stems) form = 6;
-    if (!get_args(env, info, with_tracks || with_stems ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    if (!get_args(env, info, with_meters ? 33 : with_tracks || with_stems ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
     if (with_stems) { /* (nTracks 0: a call without tracks) */
         double n_tracks = 0;
         with_tracks = napi_get_value_double(env, argv[24], &n_tracks) != napi_ok || n_tracks != 0;
@@ -1310,7 +1339,23 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         } else if (mi.n_params) bad = "the master's program needs a parameter table";
     }
     j->with_stems = with_stems;
-    j->n_signals = with_stems ? 1 + j->n_tracks + j->n_buses + 1 : 1;
+    j->with_meters = with_meters;
+    j->stems_asked = with_stems;
+    if (with_meters) {
+        bool asked = false;
+        double n_blocks = -1;
+        if (napi_get_value_bool(env, argv[31], &asked) != napi_ok || napi_get_value_double(env, argv[32], &n_blocks) != napi_ok || !(n_blocks >= 0 && n_blocks <= 4294967295.0) ||
+            n_blocks != (double)(size_t)n_blocks)
+            bad = bad ? bad : "stems is a boolean and nBlocks a whole number";
+        else
+            j->stems_asked = asked, j->n_blocks = (size_t)n_blocks;
+    }
+    j->n_signals = j->stems_asked ? 1 + j->n_tracks + j->n_buses + 1 : 1;
+    j->n_channels = (size_t)n_channels;
+    if (!bad && with_meters &&
+        (!(j->m_rms = (double *)calloc(j->n_signals * j->n_channels + 1, sizeof(double))) || !(j->m_lufs = (double *)calloc(j->n_signals + 1, sizeof(double))) ||
+         !(j->m_momentary = (double *)calloc(j->n_signals * j->n_blocks + 1, sizeof(double)))))
+        bad = "out of host memory for the meters";
     j->n_floats = j->n_signals * (size_t)n_channels * j->n_total;
     j->n_bytes = j->n_floats * (size_t)(!j->format || j->format == DUSP_PCM_F32 ? 4 : j->format == DUSP_PCM_S16 ? 2 : 3);
     if (!bad && !(j->out = (float *)malloc(j->n_bytes + 1))) bad = "out of host memory for the PCM buffer";
@@ -1370,6 +1415,53 @@ static napi_value fn_render_piece_master(napi_env env, napi_callback_info info) 
 static napi_value fn_render_piece_buses(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 6); }
 static napi_value fn_render_piece_tracks(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 7); }
 static napi_value fn_render_piece_stems(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 8); }
+static napi_value fn_render_piece_meters(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 9); }
+
+/* meter(ctx, planar, nSignals, nChannels, nSamples, sampleRate) -> { rms: Float64Array [nSignals * nChannels], lufs: Float64Array [nSignals],
+ * momentary: Float64Array [nSignals * blocks] }: the meters of f32 signals in host memory, on the device, gated in the library
+ * (dusp_meter_host).  Throws the library's message. */
+static napi_value fn_meter(napi_env env, napi_callback_info info) {
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return NULL;
+    ctx_box *b = as_ctx(env, argv[0]);
+    if (!b) return NULL;
+    void *data;
+    size_t len;
+    double dims[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) napi_get_value_double(env, argv[2 + i], &dims[i]);
+    for (int i = 0; i < 4; i++)
+        if (!(dims[i] >= 1 && dims[i] <= 4294967295.0) || dims[i] != (double)(size_t)dims[i]) {
+            throw_string(env, "dusp-hip: meter: nSignals, nChannels, nSamples and sampleRate are whole numbers of at least 1");
+            return NULL;
+        }
+    const size_t n_signals = (size_t)dims[0], n_channels = (size_t)dims[1], n_samples = (size_t)dims[2];
+    const uint32_t rate = (uint32_t)dims[3];
+    if (!typed_array(env, argv[1], napi_float32_array, &data, &len) || (double)len != dims[0] * dims[1] * dims[2]) {
+        throw_string(env, "dusp-hip: meter: planar must be a Float32Array of nSignals * nChannels * nSamples values");
+        return NULL;
+    }
+    const size_t n_blocks = dusp_meter_blocks(n_samples, rate), counts[3] = {n_signals * n_channels, n_signals, n_signals * n_blocks};
+    const char *names[3] = {"rms", "lufs", "momentary"};
+    napi_value result, arrs[3];
+    void *mem[3];
+    NAPI_OK(napi_create_object(env, &result));
+    for (int m = 0; m < 3; m++) {
+        napi_value ab;
+        NAPI_OK(napi_create_arraybuffer(env, counts[m] * sizeof(double), &mem[m], &ab));
+        NAPI_OK(napi_create_typedarray(env, napi_float64_array, counts[m], ab, 0, &arrs[m]));
+        NAPI_OK(napi_set_named_property(env, result, names[m], arrs[m]));
+    }
+    pthread_mutex_lock(&b->lock);
+    int rc = dusp_meter_host(b->ctx, (const float *)data, n_signals, n_channels, n_samples, rate, (double *)mem[0], (double *)mem[1], n_blocks ? (double *)mem[2] : NULL);
+    char msg[512];
+    if (rc != DUSP_OK) snprintf(msg, sizeof msg, "dusp-hip: %s", dusp_last_error(b->ctx));
+    pthread_mutex_unlock(&b->lock);
+    if (rc != DUSP_OK) {
+        throw_string(env, msg);
+        return NULL;
+    }
+    return result;
+}
 
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
@@ -1405,6 +1497,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
         {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo}, {"renderPieceMaster", fn_render_piece_master},
         {"renderPieceBuses", fn_render_piece_buses}, {"renderPieceTracks", fn_render_piece_tracks}, {"renderPieceStems", fn_render_piece_stems},
+        {"renderPieceMeters", fn_render_piece_meters}, {"meter", fn_meter},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -28,6 +28,8 @@ module.exports = {
   checkTracks: renderChannelData.checkTracks,
   trackPrograms: renderChannelData.trackPrograms,
   stemNames: renderChannelData.stemNames,
+  meter: renderChannelData.meter,
+  meterBlocks: renderChannelData.meterBlocks,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,
   quick: require('./lib/quick'),

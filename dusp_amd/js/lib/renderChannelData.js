@@ -456,10 +456,12 @@ function wholeSamples(who, name, values, count) {
  * placed — through the piece's call too.
  * master: as renderPiece's — the mix through a mono circuit, channel by channel, on the device — through the piece's call too.
  * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too.
- * stems: true — as renderPiece's: the direct mix, every track and every bus return beside the mix — through the piece's call too. */
+ * stems: true — as renderPiece's: the direct mix, every track and every bus return beside the mix — through the piece's call too.
+ * meters: true — as renderPiece's: the RMS and the BS.1770 loudness of every signal the call delivers — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
 const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends) ||
-  given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends) || (opts.stems !== undefined && opts.stems !== false)
+  given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends) || (opts.stems !== undefined && opts.stems !== false) ||
+  (opts.meters !== undefined && opts.meters !== false)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -467,26 +469,26 @@ function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the pie
 
 async function renderScore(outlets, opts = {}) {
   const { duration = 1 } = opts
-  const { nSamples, nChannels, sampleRate, result, names } = asPiece(opts)
+  const { nSamples, nChannels, sampleRate, result, names, metered } = asPiece(opts)
     ? await pieceCall('renderScore', outlets, scoreAsPiece(opts), 0, 0, true)
     : await mixCall('renderScore', outlets, duration, opts, 0, 0, true)
-  if (names) return planarStems(names, nSamples, nChannels, sampleRate, result)
+  if (names) return withMeters(planarStems(names, nSamples, nChannels, sampleRate, result), metered)
   const channelData = []
   channelData.sampleRate = sampleRate
   if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
-  return channelData
+  return withMeters(channelData, metered)
 }
 
 async function renderScorePcm(outlets, opts = {}) {
   const { duration = 1, bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderScorePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderScorePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result, names } = asPiece(opts)
+  const { nChannels, sampleRate, result, names, metered } = asPiece(opts)
     ? await pieceCall('renderScorePcm', outlets, scoreAsPiece(opts), PCM_FORMAT[bitDepth], normalise, true)
     : await mixCall('renderScorePcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise, true)
-  if (names) return pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise)
-  if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
-  return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
+  if (names) return withMeters(pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise), metered)
+  if (!result) return withMeters({ data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }, metered)
+  return withMeters({ data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }, metered)
 }
 
 async function renderScoreWav(outlets, opts = {}) {
@@ -889,9 +891,61 @@ function pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise) {
 }
 /* PCM -> a WAV file; the stems of a call -> a file a signal */
 function wavOf(pcm) {
+  if (pcm.meters && !pcm.names) return { mix: encodeWav(pcm.mix), meters: pcm.meters } // (meters without stems)
+  if (pcm.meters) return Object.assign(wavOf(Object.assign({}, pcm, { meters: undefined })), { meters: pcm.meters })
   if (!pcm.names) return encodeWav(pcm)
   const files = pcm.names.map((name, s) => encodeWav(s === 0 ? pcm.direct : s === pcm.names.length - 1 ? pcm.mix : s <= pcm.tracks.length ? pcm.tracks[s - 1] : pcm.buses[s - 1 - pcm.tracks.length]))
   return stemsOf(pcm.names, files, pcm.names.map((name) => pcm.peaks[name]), { gain: pcm.gain })
+}
+
+/* Meters (DESIGN.md 6.18): the refusals, the hop and the block count, in the words of mix.py (METERS_NOT_BOOL, METER_RATE_LOW, meter_hop,
+ * meter_blocks) */
+const METERS_NOT_BOOL = 'dusp-hip: meters is True or False: with True a call also delivers the RMS and the BS.1770 loudness of every signal it delivers'
+const METER_RATE_LOW = (rate) => 'dusp-hip: meters need a sample rate of at least 8000 Hz, not ' + rate + ": the K-weighting's shelf lies at 1682 Hz"
+function checkMeters(meters) {
+  if (meters === undefined) return false
+  if (typeof meters !== 'boolean') throw METERS_NOT_BOOL
+  return meters
+}
+const meterHop = (sampleRate) => Math.floor((sampleRate + 5) / 10)
+function meterBlocks(n, sampleRate) {
+  const hop = meterHop(sampleRate), block = 4 * hop
+  return n < block ? 0 : Math.floor((n - block) / hop) + 1
+}
+/* What a call with meters: true holds as `meters` (twin of render.py Meters): names, the signals in the order they were delivered
+ * (stemNames with stems, else ['mix']); rms, name -> Float64Array [channels]; lufs, name -> the gated integrated loudness of ITU-R
+ * BS.1770-4 (-Infinity: no block above the gates, NaN: a sample that is not finite); momentary, name -> Float64Array [blocks], the
+ * loudness of every 400 ms block, 100 ms apart; hop and block in samples.  Taken on the f32 signals in front of the PCM gain: the
+ * loudness of an encoded file is lufs + 20 log10(gain).  got (the addon's doubles; null: a timeline of no samples, no energy, no block). */
+function metersOf(names, got, nChannels, nBlocks, sampleRate) {
+  const out = { names, rms: {}, lufs: {}, momentary: {}, hop: meterHop(sampleRate), block: 4 * meterHop(sampleRate) }
+  names.forEach((name, s) => {
+    out.rms[name] = got ? got.rms.slice(s * nChannels, (s + 1) * nChannels) : new Float64Array(nChannels)
+    out.lufs[name] = got ? got.lufs[s] : -Infinity
+    out.momentary[name] = got ? got.momentary.slice(s * nBlocks, (s + 1) * nBlocks) : new Float64Array(0)
+  })
+  return out
+}
+/* what a call resolves to, with its meters where it has some: the stems gain `.meters`; without stems { mix, meters } (twin of render.py Metered) */
+function withMeters(delivered, metered) {
+  if (!metered) return delivered
+  return delivered && delivered.names ? Object.assign(delivered, { meters: metered }) : { mix: delivered, meters: metered }
+}
+/* The meters of any signals a user has (twin of render.py meter): channelData — an array of Float32Arrays, the channels of one signal, or
+ * an array of such arrays, several signals of the same shape — at sampleRate -> what metersOf makes, the names '0', '1', ...; metered on
+ * the device and gated in the library (dusp_meter_host). */
+function meter(channelData, sampleRate) {
+  const signals = channelData.length && !ArrayBuffer.isView(channelData[0]) ? Array.from(channelData) : [channelData]
+  const nChannels = signals[0].length, nSamples = nChannels ? signals[0][0].length : 0
+  if (!(sampleRate >= 8000)) throw METER_RATE_LOW(sampleRate)
+  if (!nChannels || signals.some((sig) => sig.length !== nChannels || Array.from(sig).some((ch) => !(ch instanceof Float32Array) || ch.length !== nSamples)))
+    throw 'dusp-hip: meter: the signals to meter are Float32Arrays of one length, the same number a signal'
+  const names = signals.map((sig, s) => String(s))
+  if (nSamples === 0) return metersOf(names, null, nChannels, 0, sampleRate)
+  const planar = new Float32Array(signals.length * nChannels * nSamples)
+  signals.forEach((sig, s) => Array.from(sig).forEach((ch, c) => planar.set(ch, (s * nChannels + c) * nSamples)))
+  const got = native().meter(contextFor(sampleRate), planar, signals.length, nChannels, nSamples, sampleRate)
+  return metersOf(names, got, nChannels, meterBlocks(nSamples, sampleRate), sampleRate)
 }
 
 /* what sends and tracks do not go with, refused before anything else of a call is looked at (twin of render.py _placing) */
@@ -918,6 +972,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
   const stereo = opts.stereo === true
   const stems = checkStems(opts.stems) // (what is no boolean is refused first)
+  const meters = checkMeters(opts.meters) // (... and next to it)
   refuseSends(opts)
   if (given(opts.places) && stereo) throw STEREO_NO_PLACES
   if (given(opts.places) && (given(opts.pans) || given(opts.fracs))) throw SPACE_ALONE
@@ -969,7 +1024,9 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     buses = opts.buses.map((fx, b) => masterProgram(fx, nChannels, sampleRate, b))
   }
   const names = stems ? stemNames(routed ? opts.tracks.length : 0, buses ? buses.length : 0) : null
-  if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null, names }
+  if (meters && !(sampleRate >= 8000)) throw METER_RATE_LOW(sampleRate)
+  const nBlocks = meterBlocks(nSamples, sampleRate)
+  if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null, names, metered: meters ? metersOf(names || ['mix'], null, nChannels, 0, sampleRate) : null }
   const progs = [], busProgs = [], trackProgs = []
   let masterProg = null
   try {
@@ -979,7 +1036,12 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
     if (groups) for (const group of groups) trackProgs.push(n.programBuild(contextFor(sampleRate), group.uni.words, engine))
-    const result = stems ? await n.renderPieceStems(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+    const result = meters ? await n.renderPieceMeters(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+      taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
+      buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
+      routed ? trackProgs : null, routed ? groups.map((group) => Uint32Array.from(group.tracks)) : null, routed ? groups.map((group) => (group.uni.nParams ? group.uni.params : null)) : null,
+      routed ? routed.faders : null, routed ? routed.trackSends : null, stems, nBlocks)
+      : stems ? await n.renderPieceStems(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
       routed ? trackProgs : null, routed ? groups.map((group) => Uint32Array.from(group.tracks)) : null, routed ? groups.map((group) => (group.uni.nParams ? group.uni.params : null)) : null,
@@ -996,7 +1058,9 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
       : taps ? await n.renderPieceSpace(...args, taps.nSpeakers, taps.delays, taps.gains)
       : fracs ? await n.renderPieceFrac(...args, fracs, panned ? panned.pans : null, panned ? panned.comp : null)
       : panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
-    return { nSamples, nChannels, sampleRate, result, names }
+    if (!meters) return { nSamples, nChannels, sampleRate, result, names }
+    // (one addon call: { data, peaks, rms, lufs, momentary }; without stems what is delivered is the call's without meters)
+    return { nSamples, nChannels, sampleRate, result: stems || format ? result : result.data, names, metered: metersOf(names || ['mix'], result, nChannels, nBlocks, sampleRate) }
   } finally {
     for (const prog of progs) n.programDestroy(prog)
     if (masterProg) n.programDestroy(masterProg)
@@ -1052,24 +1116,29 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * it holds): the direct mix (with tracks the voices that go straight to the mix, else the dry mix of all voices), every track after
  * its fader and every bus's return, each as the mix is delivered, and the mix itself, bit for bit the call's result without stems.  The
  * stems are taken in front of the master; without a master they add up to the mix.  Every signal has its peak, and PCM frames get ONE
- * gain from the largest of them.  One addon call, one delivery.  What is no boolean is refused. */
+ * gain from the largest of them.  One addon call, one delivery.  What is no boolean is refused.
+ * meters: true — the call also meters what it delivers, on the device, in front of the PCM gain (dusp_render_host_score_piece_meters;
+ * DESIGN.md 6.18; metersOf says what `meters` holds): the RMS a channel, the gated integrated loudness in LUFS (ITU-R BS.1770-4) and the
+ * momentary loudness of every 400 ms block, of the mix and — with stems — of every stem.  With stems the result gains `.meters`; without,
+ * the call resolves to { mix, meters }, mix what it resolves to without meters bit for bit.  One addon call.  What is no boolean is
+ * refused, next to stems. */
 async function renderPiece(outlets, opts = {}) {
-  const { nSamples, nChannels, sampleRate, result, names } = await pieceCall('renderPiece', outlets, opts, 0, 0)
-  if (names) return planarStems(names, nSamples, nChannels, sampleRate, result)
+  const { nSamples, nChannels, sampleRate, result, names, metered } = await pieceCall('renderPiece', outlets, opts, 0, 0)
+  if (names) return withMeters(planarStems(names, nSamples, nChannels, sampleRate, result), metered)
   const channelData = []
   channelData.sampleRate = sampleRate
   if (result) for (let c = 0; c < nChannels; c++) channelData.push(result.subarray(c * nSamples, (c + 1) * nSamples))
-  return channelData
+  return withMeters(channelData, metered)
 }
 
 async function renderPiecePcm(outlets, opts = {}) {
   const { bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderPiecePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderPiecePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result, names } = await pieceCall('renderPiecePcm', outlets, opts, PCM_FORMAT[bitDepth], normalise)
-  if (names) return pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise)
-  if (!result) return { data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }
-  return { data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }
+  const { nChannels, sampleRate, result, names, metered } = await pieceCall('renderPiecePcm', outlets, opts, PCM_FORMAT[bitDepth], normalise)
+  if (names) return withMeters(pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise), metered)
+  if (!result) return withMeters({ data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }, metered)
+  return withMeters({ data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }, metered)
 }
 
 async function renderPieceWav(outlets, opts = {}) {
@@ -1134,6 +1203,11 @@ module.exports.trackPrograms = trackPrograms
 module.exports.STEMS_NOT_BOOL = STEMS_NOT_BOOL
 module.exports.stemNames = stemNames
 module.exports.commonPeak = commonPeak
+module.exports.METERS_NOT_BOOL = METERS_NOT_BOOL
+module.exports.METER_RATE_LOW = METER_RATE_LOW
+module.exports.meterHop = meterHop
+module.exports.meterBlocks = meterBlocks
+module.exports.meter = meter
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

@@ -957,3 +957,136 @@ def stems_sum(stack):
         for x in stack[1:-1]:
             acc = acc + np.asarray(x, dtype=np.float32)
     return _chain_end(acc, False)
+
+
+# ---- meters: RMS and ITU-R BS.1770-4 loudness of the mix and of every stem ----
+
+METERS_NOT_BOOL = "dusp-hip: meters is True or False: with True a call also delivers the RMS and the BS.1770 loudness of every signal it delivers"
+METER_RATE_MIN = 8000  # (the shelf's tan needs sample_rate > 2 * 1682 Hz; 8000 is the lowest rate the project tests)
+METER_RATE_LOW = "dusp-hip: meters need a sample rate of at least 8000 Hz, not %d: the K-weighting's shelf lies at 1682 Hz"
+LUFS_OFFSET, LUFS_ABSOLUTE_GATE, LUFS_RELATIVE_GATE = -0.691, -70.0, -10.0
+
+
+def check_meters(meters):
+    """`meters=` of a score or piece call -> bool; what is no bool is refused by string, as stems= is"""
+    if not isinstance(meters, (bool, np.bool_)):
+        raise ValueError(METERS_NOT_BOOL)
+    return bool(meters)
+
+
+def k_weighting(sample_rate):
+    """The K-weighting of ITU-R BS.1770-4 at any sample rate: two biquad sections (b0, b1, b2, a1, a2) in f64, the high shelf and the
+    RLB high-pass, by the bilinear re-derivation libebur128 uses; at 48 kHz the standard's table to its last printed digit."""
+    import math
+    fs = float(sample_rate)
+    if not fs >= METER_RATE_MIN:
+        raise ValueError(METER_RATE_LOW % sample_rate)
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / fs)
+    Vh = math.pow(10.0, G / 20.0)
+    Vb = math.pow(Vh, 0.4996667741545416)
+    a0 = 1.0 + K / Q + K * K
+    shelf = ((Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0)
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / fs)
+    den = 1.0 + K / Q + K * K
+    rlb = (1.0, -2.0, 1.0, 2.0 * (K * K - 1.0) / den, (1.0 - K / Q + K * K) / den)
+    return shelf, rlb
+
+
+def meter_hop(sample_rate):
+    """100 ms as a whole number of samples (libebur128's rule); a block is four of them"""
+    return (int(sample_rate) + 5) // 10
+
+
+def meter_blocks(n, sample_rate):
+    """how many 400 ms blocks, 100 ms apart, lie in n samples (dusp_meter_blocks)"""
+    hop = meter_hop(sample_rate)
+    block = 4 * hop
+    return 0 if n < block else (n - block) // hop + 1
+
+
+def k_weighted(rows, sample_rate):
+    """rows float32 or float64 [R, n] -> float64 [R, n]: every row through both sections of k_weighting from rest, each section direct
+    form I, y = b0 x + b1 x1 + b2 x2 - a1 y1 - a2 y2 left to right, every operation rounded by itself in f64.  THE sequential loop the
+    device's cut in time is held to."""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2:
+        raise ValueError("dusp-hip: the rows to weight have shape (rows, samples)")
+    (b0, b1, b2, a1, a2), (c0, c1, c2, d1, d2) = k_weighting(sample_rate)
+    out = np.empty_like(rows)
+    if rows.shape[0] >= 16:  # (many rows: one numpy operation a step over all of them — the same operations in the same order)
+        r = rows.shape[0]
+        x1, x2, y1, y2, z1, z2 = (np.zeros(r) for _ in range(6))
+        cols = np.ascontiguousarray(rows.T)
+        res = np.empty_like(cols)
+        with np.errstate(all="ignore"):
+            for t in range(cols.shape[0]):
+                x = cols[t]
+                y = b0 * x + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2
+                z = c0 * y + c1 * y1 + c2 * y2 - d1 * z1 - d2 * z2
+                x2, x1, y2, y1, z2, z1 = x1, x, y1, y, z1, z
+                res[t] = z
+        return np.ascontiguousarray(res.T)
+    for k in range(rows.shape[0]):  # (few rows: Python's own doubles, which round every operation by itself as well)
+        x1 = x2 = y1 = y2 = z1 = z2 = 0.0
+        zs = []
+        for x in rows[k].tolist():
+            y = b0 * x + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2
+            z = c0 * y + c1 * y1 + c2 * y2 - d1 * z1 - d2 * z2
+            x2, x1, y2, y1, z2, z1 = x1, x, y1, y, z1, z
+            zs.append(z)
+        out[k] = zs
+    return out
+
+
+def loudness(e):
+    """energies float64 [n_blocks] -> (momentary float64 [n_blocks], lufs): momentary = -0.691 + 10 log10(e), -inf for 0; lufs the
+    gated integrated loudness of BS.1770-4 — the blocks above -70, then above their mean's loudness - 10 as well; -inf when no block
+    is left, NaN as soon as one energy is not finite.  (What dusp_meter_host computes from the hop sums, in the library.)"""
+    e = np.asarray(e, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        momentary = LUFS_OFFSET + 10.0 * np.log10(e)
+        if not np.all(np.isfinite(e)):
+            return momentary, float("nan")
+        kept = momentary > LUFS_ABSOLUTE_GATE
+        if not kept.any():
+            return momentary, float("-inf")
+        gamma = LUFS_OFFSET + 10.0 * np.log10(np.mean(e[kept])) + LUFS_RELATIVE_GATE
+        kept &= momentary > gamma
+        if not kept.any():
+            return momentary, float("-inf")
+        return momentary, float(LUFS_OFFSET + 10.0 * np.log10(np.mean(e[kept])))
+
+
+def meters(signals, sample_rate):
+    """The meters of a delivery: the contract of dusp_meter_host and of meters=True, in f64 throughout, needs no GPU.  signals float32
+    [S, C, n] -> dict(rms float64 [S, C], energies float64 [S, n_blocks], momentary float64 [S, n_blocks], lufs float64 [S], hop, block):
+
+        rms[s][c]       sqrt(sum_t f64(x)^2 / n)
+        energies[s][j]  sum over c of mean(z_c[j hop : j hop + block]^2), z_c = k_weighted(channel c): EVERY channel has weight 1 —
+                        the standard for mono and stereo; a Space timeline's speakers are no 5.1 layout and get weight 1 too
+        momentary, lufs loudness(energies[s])
+
+    hop = meter_hop(sample_rate), block = 4 hop, n_blocks = meter_blocks(n, sample_rate).  A block that holds or follows a sample that is
+    not finite has an energy that is not finite.  The meters are taken on the f32 signals in front of the PCM gain: the loudness of an
+    encoded file is lufs + 20 log10(gain)."""
+    signals = np.asarray(signals, dtype=np.float32)
+    if signals.ndim != 3:
+        raise ValueError("dusp-hip: the signals to meter are float32 of shape (signals, channels, samples)")
+    k_weighting(sample_rate)  # (refuses a rate that is too low)
+    S, C, n = signals.shape
+    hop = meter_hop(sample_rate)
+    block, n_blocks = 4 * hop, meter_blocks(n, sample_rate)
+    x = signals.astype(np.float64)
+    with np.errstate(all="ignore"):
+        rms = np.sqrt(np.sum(x * x, axis=2) / n) if n else np.zeros((S, C))
+        z = k_weighted(x.reshape(S * C, n), sample_rate).reshape(S, C, n) if n_blocks else x
+        energies = np.zeros((S, n_blocks))
+        for j in range(n_blocks):
+            w = z[:, :, j * hop:j * hop + block]
+            energies[:, j] = np.sum(np.mean(w * w, axis=2), axis=1)
+    momentary, lufs = np.zeros((S, n_blocks)), np.zeros(S)
+    for s in range(S):
+        momentary[s], lufs[s] = loudness(energies[s])
+    return dict(rms=rms, energies=energies, momentary=momentary, lufs=lufs, hop=hop, block=block)

@@ -180,6 +180,8 @@ def _wav(pcm, bit_depth):
     """PcmData -> a complete RIFF/WAVE file (bytes); a Stems of PcmData -> a Stems of files"""
     if isinstance(pcm, Stems):
         return pcm.each(lambda one: _wav(one, bit_depth))
+    if isinstance(pcm, Metered):
+        return Metered(_wav(pcm.mix, bit_depth), pcm.meters)
     if bit_depth == 32:
         return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
     return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
@@ -224,7 +226,48 @@ class Stems:
 
     def each(self, make):
         """the same Stems with make(signal) for every signal"""
-        return Stems(self.names, [make(one) for one in self._signals], [self.peaks[name] for name in self.names], getattr(self, "gain", None))
+        made = Stems(self.names, [make(one) for one in self._signals], [self.peaks[name] for name in self.names], getattr(self, "gain", None))
+        if hasattr(self, "meters"):
+            made.meters = self.meters
+        return made
+
+
+class Meters:
+    """The meters of a call with meters=True (mix.meters is the contract), taken on the f32 signals in front of the PCM
+    gain: `names`, the signals in the order they were delivered (mix.stem_names with stems, else ["mix"]); `rms`, name -> float64
+    [channels]; `lufs`, name -> float, the gated integrated loudness of ITU-R BS.1770-4 (-inf: no block above the gates, NaN: a sample
+    that is not finite); `momentary`, name -> float64 [n_blocks], the loudness of every 400 ms block, 100 ms apart; `hop` and `block`
+    in samples.  The loudness of an encoded file is lufs + 20 log10(gain)."""
+
+    def __init__(self, names, got):
+        self.names = list(names)
+        self.rms = {name: np.array(got["rms"][k], dtype=np.float64) for k, name in enumerate(self.names)}
+        self.lufs = {name: float(got["lufs"][k]) for k, name in enumerate(self.names)}
+        self.momentary = {name: np.array(got["momentary"][k], dtype=np.float64) for k, name in enumerate(self.names)}
+        self.hop, self.block = int(got["hop"]), int(got["block"])
+
+
+class Metered:
+    """What a score or piece call with meters=True and without stems hands back: `mix`, exactly what the call returns without meters,
+    and `meters`, a Meters of the one signal "mix"."""
+
+    def __init__(self, mix_, meters):
+        self.mix, self.meters = mix_, meters
+
+
+def _empty_meters(n_signals, channels, sample_rate):
+    """the meters of a timeline of no samples, which renders nothing: no energy, no block"""
+    if not sample_rate >= mix.METER_RATE_MIN:
+        raise ValueError(mix.METER_RATE_LOW % sample_rate)
+    hop = mix.meter_hop(sample_rate)
+    return dict(rms=np.zeros((n_signals, channels)), lufs=np.full(n_signals, -np.inf), momentary=np.zeros((n_signals, 0)), hop=hop, block=4 * hop)
+
+
+def meter(planar, sample_rate, device=-1):
+    """The meters of any signals a user has: planar float32 [signals, channels, samples] (or [channels, samples]: one signal) -> a
+    Meters whose names are "0", "1", ..., metered on the device and gated in the library (Context.meter; mix.meters is the contract)."""
+    got = context(sample_rate, device).meter(planar, sample_rate)
+    return Meters([str(k) for k in range(len(got["lufs"]))], got)
 
 
 def _delivered_stems(pcm, sample_rate, n, channels, names, run):
@@ -298,7 +341,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -327,12 +370,12 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     stems=True: as render_piece's — the direct mix, every track and every bus return beside the mix, as a Stems; the piece's call with
     the score as its one part, as with a master."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters))
 
 
 def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if placing["stereo"] or placing["stems"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
+    if placing["stereo"] or placing["stems"] or placing["meters"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
         return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
@@ -345,17 +388,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), (bit_depth, normalise))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), bit_depth)
 
 
 class PieceParts:
@@ -399,7 +442,7 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
     """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
     known.  The Space keywords are one thing too, None without places (the other three alone say nothing).  master: what the mix goes
     through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it;
@@ -407,8 +450,9 @@ def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per
     with is refused here, before anything else of the call is looked at.  tracks, track_of, faders, track_sends: the tracks some
     voices go through, which travel with it as well; with tracks the buses are fed by track_sends, whatever the placement, and what
     does not go with tracks is refused here too (mix.check_tracks holds the arrays once the voices are counted).  stems: whether the
-    call delivers its stems beside the mix, which travels with it too; what is no bool is refused here, first"""
-    stems = mix.check_stems(stems)
+    call delivers its stems beside the mix, which travels with it too; what is no bool is refused here, first.  meters: whether
+    the call also meters what it delivers, which travels with it as stems does and is refused next to it"""
+    stems, meters = mix.check_stems(stems), mix.check_meters(meters)
     if tracks is None:
         mix.check_tracks(0, None, track_of, faders, track_sends)
         if buses is None and sends is not None:
@@ -433,7 +477,7 @@ def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per
         if not isinstance(buses, (list, tuple)) or not 1 <= len(buses) <= mix.BUS_MAX:
             raise ValueError(mix.BUS_COUNT % (len(buses) if isinstance(buses, (list, tuple)) else 0))
     return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master,
-                buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems)
+                buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters)
 
 
 def master_program(master, channels, sample_rate, bus=None):
@@ -512,7 +556,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     master = placing.pop("master", None)
     buses, sends = placing.pop("buses", None), placing.pop("sends", None)
     tracks, track_of, faders, track_sends = (placing.pop(k, None) for k in ("tracks", "track_of", "faders", "track_sends"))
-    stems = placing.pop("stems", False)
+    stems, meters = placing.pop("stems", False), placing.pop("meters", False)
     mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
@@ -537,6 +581,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     place.master = None if master is None else master_program(master, channels, rate)  # (behind every other check of the call)
     place.buses = place.sends = None  # (... and the buses, each a descriptor.Unified of one instance a channel, with the levels [buses, voices])
     place.stems = stems  # (... whether the call delivers its stems)
+    place.meters = meters  # (... and whether it meters what it delivers)
     place.tracks = None  # (... and the tracks: (how many, track_of, track_programs' groups, faders, levels [buses, tracks]))
     if tracks is not None:
         track_of, faders, track_sends = mix.check_tracks(n, len(tracks), track_of, faders, track_sends, 0 if buses is None else len(buses), sends)
@@ -569,14 +614,14 @@ def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, devic
             circuits = [(prog, which, uni.params) for prog, (uni, which) in zip(programs[len(programs) - len(groups):], groups)]
             tracks = dict(n_tracks=n_tracks, track_of=track_of, programs=circuits, faders=faders, track_sends=track_sends)
         return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, master=master, buses=buses,
-                                      sends=getattr(place, "sends", None), tracks=tracks, stems=getattr(place, "stems", False), **place.keywords())
+                                      sends=getattr(place, "sends", None), tracks=tracks, stems=getattr(place, "stems", False), **(dict(meters=True) if getattr(place, "meters", False) else {}), **place.keywords())
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -637,9 +682,14 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     all voices), every track after its fader and every bus's return, each as the mix is delivered, beside the mix itself, which is
     bit for bit the call's result without stems.  The stems are taken in front of the master; without a master they add up to the mix
     (mix.stems says exactly how).  Every signal comes with its peak, and PCM frames get ONE gain from the largest of
-    them, so the files still add up.  One call, one delivery; every signal takes a timeline of device memory."""
+    them, so the files still add up.  One call, one delivery; every signal takes a timeline of device memory.
+
+    meters=True: the call also meters what it delivers, on the device, in front of the PCM gain (mix.meters says exactly what;
+    DESIGN.md 6.18): the RMS a channel, the gated integrated loudness in LUFS (ITU-R BS.1770-4) and the momentary loudness of every
+    400 ms block, of the mix and — with stems — of every stem.  With stems the Stems gains `.meters`; without, the call returns a
+    Metered: `.mix`, what it returns without meters bit for bit, and `.meters`."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), _one_part)
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), _one_part)
 
 
 def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
@@ -648,25 +698,40 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
         _check_pcm(*pcm)
     grouped, n_total, onsets, lengths, gains, channels, place = _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, one_part)
     run = lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format, normalise)
+    names = mix.stem_names(place.tracks[0] if place.tracks is not None else 0, len(place.buses) if place.buses is not None else 0) if place.stems else ["mix"]
+    if place.meters:  # (the run hands back what it does without meters, and the meters beside it)
+        got = _empty_meters(len(names), channels, grouped.sample_rate)
+        render = run
+
+        def run(format, normalise):
+            result, metered = render(format, normalise)
+            got.update(metered)
+            return result
+
+        delivered = (_delivered_stems(pcm, grouped.sample_rate, n_total, channels, names, run) if place.stems else
+                     _delivered(pcm, grouped.sample_rate, n_total, channels, run))
+        if not place.stems:
+            return Metered(delivered, Meters(names, got))
+        delivered.meters = Meters(names, got)
+        return delivered
     if place.stems:
-        names = mix.stem_names(place.tracks[0] if place.tracks is not None else 0, len(place.buses) if place.buses is not None else 0)
         return _delivered_stems(pcm, grouped.sample_rate, n_total, channels, names, run)
     return _delivered(pcm, grouped.sample_rate, n_total, channels,
                       lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format, normalise))
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems), _one_part, (bit_depth, normalise))
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters), bit_depth)
 
 
 class PcmData:

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import check_stems, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
+from .mix import check_meters, check_stems, meter_blocks, meter_hop, METER_RATE_LOW, METER_RATE_MIN, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,6 +37,7 @@ EXPORTS = [
     "dusp_render_host_score_piece_buses", "dusp_score_rows_send_device", "dusp_score_return_device",
     "dusp_render_host_score_piece_tracks", "dusp_score_tracks_mix_device",
     "dusp_render_host_score_piece_stems", "dusp_score_stems_mix_device", "dusp_score_stems_return_device", "dusp_peak_common_device",
+    "dusp_meter_blocks", "dusp_meter_device", "dusp_meter_last_ms", "dusp_meter_host", "dusp_render_host_score_piece_meters",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -128,6 +129,12 @@ def load():
         L.dusp_score_stems_mix_device.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, ci, vp, vp, vp, vp, vp]
         L.dusp_score_stems_return_device.argtypes = [vp, vp, vp, sz, sz, ci, vp, vp, vp, vp]
         L.dusp_peak_common_device.argtypes = [vp, vp, sz, vp, vp]
+    if hasattr(L, "dusp_render_host_score_piece_meters"):  # (detected by symbol, as the stems are)
+        L.dusp_meter_blocks.argtypes, L.dusp_meter_blocks.restype = [sz, ctypes.c_uint32], sz
+        L.dusp_meter_device.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, vp, vp, vp]
+        L.dusp_meter_last_ms.argtypes = [vp, vp]
+        L.dusp_meter_host.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, vp, vp, vp]
+        L.dusp_render_host_score_piece_meters.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -184,6 +191,11 @@ class ScoreTracks(ctypes.Structure):
 class ScoreStems(ctypes.Structure):
     """dusp_score_stems: how many signals the caller has sized h_out and h_peaks for, 1 + tracks + buses + 1"""
     _fields_ = [("n_signals", ctypes.c_size_t)]
+
+
+class ScoreMeters(ctypes.Structure):
+    """dusp_score_meters: how many signals and blocks the caller has sized the three arrays for, and the arrays"""
+    _fields_ = [("n_signals", ctypes.c_size_t), ("n_blocks", ctypes.c_size_t), ("h_rms", ctypes.c_void_p), ("h_lufs", ctypes.c_void_p), ("h_momentary", ctypes.c_void_p)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -519,8 +531,38 @@ class Context:
         (dusp_peak_common_device; wav.common_peak): what encode() reads as d_peaks to give all instances one gain."""
         self._check(self._L.dusp_peak_common_device(self._h, d_peaks, n_peaks, d_common, stream))
 
+    def meter_device(self, d_planar, n_signals, n_channels, n_samples, sample_rate, d_sumsq, d_hops, stream=None):
+        """Device pointers: the meter kernels alone (dusp_meter_device; mix.meters is the contract) over f32 [n_signals][n_channels]
+        [n_samples] -> d_sumsq f64 [n_signals][n_channels], the sums of squares, and d_hops f64 [n_signals][ceil(n_samples / hop)], per
+        hop of 100 ms the sum over the channels of the K-weighted squares.  Timed by score_last_ms; meter_last_ms has the passes."""
+        self._check(self._L.dusp_meter_device(self._h, d_planar, n_signals, n_channels, n_samples, int(sample_rate), d_sumsq, d_hops, stream))
+
+    def meter_last_ms(self):
+        """-> the four passes of the most recent meter_device call in ms, by HIP events (dusp_meter_last_ms; waits for that call): the
+        segments from rest, the walk over their states, the segments from their true states, the reduction"""
+        ms = (ctypes.c_float * 4)()
+        self._check(self._L.dusp_meter_last_ms(self._h, ctypes.addressof(ms)))
+        return tuple(ms)
+
+    def meter(self, planar, sample_rate):
+        """planar float32 [signals, channels, samples] (or [channels, samples]: one signal) in host memory -> what mix.meters returns
+        but the energies: dict(rms [S, C], lufs [S], momentary [S, n_blocks], hop, block), float64, metered on the device and gated in
+        the library (dusp_meter_host)."""
+        planar = np.ascontiguousarray(planar, dtype=np.float32)
+        if planar.ndim == 2:
+            planar = planar[None]
+        if planar.ndim != 3:
+            raise ValueError("dusp-hip: the signals to meter are float32 of shape (signals, channels, samples)")
+        if not int(sample_rate) >= METER_RATE_MIN:
+            raise ValueError(METER_RATE_LOW % sample_rate)
+        S, C, n = planar.shape
+        rms, lufs, momentary = np.zeros((S, C)), np.full(S, -np.inf), np.zeros((S, meter_blocks(n, sample_rate)))
+        if n:
+            self._check(self._L.dusp_meter_host(self._h, planar.ctypes.data, S, C, n, int(sample_rate), rms.ctypes.data, lufs.ctypes.data, _ptr(momentary)))
+        return dict(rms=rms, lufs=lufs, momentary=momentary, hop=meter_hop(sample_rate), block=4 * meter_hop(sample_rate))
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None, stems=False):
+                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None, stems=False, meters=False):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -553,8 +595,11 @@ class Context:
         stems=True: the direct mix, every track and every bus return beside the mix (dusp_render_host_score_piece_stems; mix.stems is
         the contract, mix.stem_names the order) -> (signals, peaks): signals [S + 1, channels, n_total] float32 without a format, else
         [S + 1, n_total, channels(, 3)] frames under ONE gain (wav.encode_stems), the mix last and exactly what the call returns
-        without stems; peaks float32 [S + 1], every signal's own, whatever the format."""
-        stems = check_stems(stems)
+        without stems; peaks float32 [S + 1], every signal's own, whatever the format.
+        meters=True: the RMS and the BS.1770 loudness of every signal the call delivers — its S + 1 signals with stems, else the mix —
+        at the parts' sample rate (dusp_render_host_score_piece_meters; mix.meters is the contract) -> (what the call returns without
+        meters, dict(rms [signals, channels], lufs [signals], momentary [signals, n_blocks], hop, block)), all float64."""
+        stems, meters = check_stems(stems), check_meters(meters)
         if tracks is not None:
             track_of, faders, track_sends = check_tracks(len(part_of), tracks["n_tracks"], tracks["track_of"], tracks.get("faders"), tracks.get("track_sends"),
                                                          0 if buses is None else len(buses), sends)
@@ -588,7 +633,7 @@ class Context:
             check_stereo_kinds([parts[p][0].n_out_channels for p in part_of], place.pans)
         n_ch = place.channels(parts[0][0].n_out_channels)  # (parts that do not fit the placement: the library refuses them)
         voices = (table, len(parts), n, part_of.ctypes.data, onsets.ctypes.data)
-        if master is not None or buses is not None or tracks is not None or stems:
+        if master is not None or buses is not None or tracks is not None or stems or meters:
             how = ScorePlacement(PLACE_KINDS[place.kind], _ptr(place.fracs), _ptr(place.pans), _ptr(place.comp), n_ch if place.kind == "space" else 0,
                                  _ptr(place.taps[0]) if place.taps else None, _ptr(place.taps[1]) if place.taps else None)
             through = None
@@ -613,6 +658,27 @@ class Context:
                 keep.append(prog._params_table(params, len(which) * n_ch, "dusp-hip: the params of track program %d must have shape" % p))
                 table_t[p] = ScoreTrackProgram(prog._h, len(which), which.ctypes.data, _ptr(keep[-1]))
             routed = ScoreTracks(tracks["n_tracks"], track_of.ctypes.data, len(served), ctypes.addressof(table_t), _ptr(faders), _ptr(track_sends))
+        if meters:  # (one entry for every call: with or without stems, tracks, buses and a master)
+            rate = parts[0][0].sample_rate
+            if not rate >= METER_RATE_MIN:
+                raise ValueError(METER_RATE_LOW % rate)
+            n_signals = 1 + (tracks["n_tracks"] if tracks is not None else 0) + (len(buses) if buses is not None else 0) + 1 if stems else 1
+            n_blocks = meter_blocks(n_total_samples, rate)
+            got = dict(rms=np.zeros((n_signals, n_ch)), lufs=np.zeros(n_signals), momentary=np.zeros((n_signals, n_blocks)), hop=meter_hop(rate), block=4 * meter_hop(rate))
+            want = ScoreMeters(n_signals, n_blocks, got["rms"].ctypes.data, got["lufs"].ctypes.data, _ptr(got["momentary"]))
+            if stems:
+                if format is None:
+                    fmt, normalise, out = 0, 0, self.host_empty((n_signals, n_ch, n_total_samples), pinned)
+                else:
+                    fmt, normalise, out, _ = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned, batch=n_signals)
+                peak, asked = np.empty(n_signals, dtype=np.float32), ScoreStems(n_signals)
+            else:
+                fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
+            self._check(self._L.dusp_render_host_score_piece_meters(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(routed) if tracks is not None else None,
+                                                                    ctypes.addressof(into) if buses is not None else None,
+                                                                    ctypes.addressof(through) if through is not None else None, ctypes.addressof(asked) if stems else None,
+                                                                    ctypes.addressof(want), n_total_samples, int(tile_bytes), fmt, normalise, out.ctypes.data, _ptr(peak)))
+            return ((out, peak) if stems else out if peak is None else (out, peak[0])), got
         if stems:
             n_signals = 1 + (tracks["n_tracks"] if tracks is not None else 0) + (len(buses) if buses is not None else 0) + 1
             if format is None:

@@ -738,6 +738,50 @@ int dusp_score_stems_return_device(dusp_ctx *ctx, const float *d_dry, const floa
  * wins), 1 <= n_peaks <= 2^24: what dusp_encode_device reads as d_peaks to give n_peaks instances one gain.  d_common is not d_peaks. */
 int dusp_peak_common_device(dusp_ctx *ctx, const float *d_peaks, size_t n_peaks, float *d_common, void *stream);
 
+/* Meters: RMS and ITU-R BS.1770-4 loudness of the mix and of every stem (additions to ABI v7, detected by symbol; DESIGN.md 6.18;
+ * dusp_amd/mix.py meters is the contract).  Signals are planar f32 [n_signals][n_channels][n_samples].  Per (signal, channel) the RMS,
+ * sqrt(sum f64(x)^2 / n).  Per signal the K-weighted loudness: every channel through the standard's two biquads (made for the sample
+ * rate by the bilinear re-derivation libebur128 uses) in f64, EVERY channel with weight 1 (the standard for mono and stereo; a Space
+ * timeline's speakers are no 5.1 layout and get weight 1 too); hop = (sample_rate + 5) / 10 samples, a block is 4 hops, block j begins
+ * at sample j * hop; momentary[j] = -0.691 + 10 log10(e_j), -inf for 0; lufs the gated integrated loudness (-70 absolute, -10 relative),
+ * -inf when no block is left, NaN as soon as one block's energy is not finite — which every block is that holds or follows a sample
+ * that is not finite.  The meters are taken on the f32 signals in front of the PCM gain: an encoded file's loudness is
+ * lufs + 20 log10(gain).  Not built: true peak, loudness range, short-term loudness, surround weights, delivery to a loudness target.
+ * The sums are formed in a fixed order without floating-point atomics: two runs give the same bits.  A sample rate below 8000 is
+ * refused (the shelf lies at 1682 Hz). */
+/* how many blocks n_samples hold: 0 below a block, else (n_samples - block) / hop + 1; 0 for a sample rate below 8000 */
+size_t dusp_meter_blocks(size_t n_samples, uint32_t sample_rate);
+/* The kernels alone, on device pointers: d_sumsq f64 [n_signals][n_channels] = the sums of squares, d_hops f64
+ * [n_signals][ceil(n_samples / hop)] = per hop of 100 ms the sum over the channels of the K-weighted squares (the last hop may be
+ * shorter).  Both 8-byte aligned, d_planar 4-byte aligned.  Timed by dusp_score_last_ms; dusp_meter_last_ms has the four passes.  The
+ * scratch is the context's: calls on one context are ordered on one stream.  n_signals x n_channels x n_samples <= 2^33. */
+int dusp_meter_device(dusp_ctx *ctx, const float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate,
+                      double *d_sumsq, double *d_hops, void *stream);
+/* the last dusp_meter_device call pass by pass, by events: ms[0] the segments from rest, ms[1] the walk over the segments' states,
+ * ms[2] the segments from their true states, ms[3] the reduction.  Waits for the call. */
+int dusp_meter_last_ms(dusp_ctx *ctx, float ms[4]);
+/* Host round trip: uploads h_planar, meters it, and gates in the library: h_rms f64 [n_signals][n_channels], h_lufs f64 [n_signals],
+ * h_momentary f64 [n_signals][dusp_meter_blocks(n_samples, sample_rate)] or NULL. */
+int dusp_meter_host(dusp_ctx *ctx, const float *h_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate,
+                    double *h_rms, double *h_lufs, double *h_momentary);
+/* dusp_render_host_score_piece_stems which also meters what it delivers: n_signals signals (1 + n_tracks + n_buses + 1 with stems, 1 —
+ * the mix — without) of the timeline's channels, at the parts' sample rate, after the last kernel that writes them and before the
+ * encode.  meters NULL: that entry under this entry's name.  Refused before anything renders, each in its own words: n_signals or
+ * n_blocks that is not what the call gives (both numbers named), NULL h_rms or h_lufs, a sample rate below 8000. */
+typedef struct dusp_score_meters {
+    size_t n_signals;    /* must be what the call delivers */
+    size_t n_blocks;     /* must be dusp_meter_blocks(n_total_samples, the parts' sample rate) */
+    double *h_rms;       /* [n_signals][channels] */
+    double *h_lufs;      /* [n_signals] */
+    double *h_momentary; /* [n_signals][n_blocks], or NULL */
+} dusp_score_meters;
+int dusp_render_host_score_piece_meters(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                        const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                        const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                        const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems,
+                                        const dusp_score_meters *meters, size_t n_total_samples, size_t tile_bytes, int format, int normalise,
+                                        void *h_out, float *h_peaks);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

@@ -46,6 +46,10 @@
           and the stems return kernel against the return kernel.  Then the piece with eight fader groups and two stateless buses
           on the host's clock: with stems, without, and the eleven single-stem calls (all faders but one 0) the call with stems
           replaces, one after the other.  A report: no ratio is fixed in advance.
+  meters  (--meters; profiles/score_meters.txt) the meter kernels (dusp_meter_device) over the twelve signals of the
+          stems' case, one channel and two, pass by pass by HIP events (dusp_meter_last_ms), beside dusp_pcm_peak_kernel over the same
+          block; then the piece with stems on the host's clock with and without meters=True, one channel and panned into two.  With
+          DUSP_HIP_LIB naming a library from before the meters the call with stems alone.  A report: no ratio is fixed in advance.
 
 Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
 """
@@ -599,6 +603,93 @@ def stems(scale, ctxs, reps):
     prog.close()
 
 
+def meters(scale, ctxs, reps):
+    """--meters: the meter kernels alone, pass by pass, beside the peak kernel over the same block; the call with stems
+    with and without meters.  Under DUSP_HIP_LIB naming a library from before the meters only the call with stems runs."""
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR // (1 if scale == 1 else 8)
+    T, B = 8, 2
+    S = 1 + T + B
+    d.configure(SR)
+    ctx = ctxs["default"]
+    has = hasattr(ctx._L, "dusp_meter_device")
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    three = lambda xs: (float(np.median(xs)), min(xs), max(xs))
+    line = "  %-78s median %8.3f ms  fastest %8.3f  slowest %8.3f%s"
+    for C in ((1, 2) if has else ()):
+        block = torch.randn((S + 1, C, nt), dtype=torch.float32, device="cuda") * 0.1
+        n_hops = -(-nt // ((SR + 5) // 10))
+        sumsq, hops, peaks = torch.empty((S + 1, C), dtype=torch.float64, device="cuda"), torch.empty((S + 1, n_hops), dtype=torch.float64, device="cuda"), torch.empty(S + 1, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        print("meters: %d signals of %d channel(s) of %d samples (%.0f MB), hop %d, segments of %d samples; kernels alone by HIP events, median, fastest and slowest of %d after a warm-up"
+              % (S + 1, C, nt, block.numel() * 4 / 1e6, (SR + 5) // 10, 480 if SR == 48000 else -1, reps), flush=True)
+        whole, passes, peak = [], [], []
+        for r in range(reps + 1):
+            ctx.meter_device(block.data_ptr(), S + 1, C, nt, SR, sumsq.data_ptr(), hops.data_ptr(), stream=s)
+            if r:
+                whole.append(ctx.score_last_ms()[0])
+                passes.append(ctx.meter_last_ms())
+        for r in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(stream):
+                e0.record()
+                ctx.peak(block.data_ptr(), S + 1, C, nt, peaks.data_ptr(), stream=s)
+                e1.record()
+            e1.synchronize()
+            if r:
+                peak.append(e0.elapsed_time(e1))
+        print(line % (("the meter kernels, all passes (dusp_meter_device)",) + three(whole) + ("",)), flush=True)
+        for k, name in enumerate(("pass A: every segment from rest", "combine: one lane a row over its segments' states", "pass B: every segment from its true state, z^2 and x^2",
+                                  "reduce: segments -> hops -> d_hops, d_sumsq")):
+            print(line % (("  " + name,) + three([p[k] for p in passes]) + ("",)), flush=True)
+        print(line % (("dusp_pcm_peak_kernel over the same block (reads the same bytes once)",) + three(peak) + ("   the meters are x%.1f of it" % (np.median(whole) / np.median(peak)),)), flush=True)
+        again = hops.clone()
+        ctx.meter_device(block.data_ptr(), S + 1, C, nt, SR, sumsq.data_ptr(), hops.data_ptr(), stream=s)
+        stream.synchronize()
+        print("  two runs, the same bits: %s" % bool(torch.equal(again.view(torch.int64), hops.view(torch.int64))), flush=True)
+        del block, sumsq, hops, peaks
+    # the whole call: stems' piece — eight fader groups, two stateless buses (a gain each), no master — at one channel, and panned into two
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    prog = ctx.build(uni.words)
+    buses = [ctx.build(descriptor.extract(d.Multiply(d.MasterInput(), g)).words) for g in (0.5, 0.25)]
+    track_of = (np.arange(V) % T).astype(np.int32)
+    rs = np.random.RandomState(4)
+    faders, levels = rs.random_sample(T).astype(np.float32), rs.random_sample((B, T)).astype(np.float32)
+
+    def call(**kw):
+        res = ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, buses=[(b, None) for b in buses],
+                                     tracks=dict(n_tracks=T, track_of=track_of, programs=[], faders=faders, track_sends=levels), stems=True, **kw)
+        return res
+
+    def host_clock(run):
+        times = []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = run()
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+        return three(times[1:])
+
+    row = "  render_score_parts with stems, %-58s median %9.2f ms  fastest %9.2f  slowest %9.2f%s"
+    print("  %d notes of %d samples over %d samples, %d signals, planar f32 into pinned memory, host clock, median, fastest and slowest of %d after a warm-up; library: %s"
+          % (V, nv, nt, S + 1, reps, os.environ.get("DUSP_HIP_LIB") or "this tree's"), flush=True)
+    for name, kw in (("one channel", {}), ("two channels (pans)", dict(pans=np.linspace(-1, 1, V)))):
+        plain = host_clock(lambda: call(**kw))
+        print(row % ((name + ", no meters",) + plain + ("",)), flush=True)
+        if has:
+            metered = host_clock(lambda: call(meters=True, **kw))
+            print(row % ((name + ", meters=True",) + metered + ("   +%.2f ms, x%.2f" % (metered[0] - plain[0], metered[0] / plain[0]),)), flush=True)
+            _, got = call(meters=True, **kw)
+            print("    lufs of the mix %.2f, of track0 %.2f; %d blocks" % (got["lufs"][-1], got["lufs"][1], got["momentary"].shape[1]), flush=True)
+    for b in buses:
+        b.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -612,6 +703,7 @@ def main():
     ap.add_argument("--sends", action="store_true", help="the effect-send leg alone: the send and return kernels, and the piece with and without a bus")
     ap.add_argument("--tracks", action="store_true", help="the tracks leg alone: the mix kernel beside the fill and the return kernel, and eight Filter tracks as one program")
     ap.add_argument("--stems", action="store_true", help="the stems leg alone: the stems mix and return kernels beside the kernels they extend, and the piece with and without stems")
+    ap.add_argument("--meters", action="store_true", help="the meters leg alone: the meter kernels pass by pass beside the peak kernel, and the piece with stems with and without meters")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
@@ -623,6 +715,8 @@ def main():
         return tracks(a.scale, ctxs, a.reps)
     if a.stems:
         return stems(a.scale, ctxs, a.reps)
+    if a.meters:
+        return meters(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
