@@ -6,7 +6,10 @@
 //   abi_render_jit.hip  ... the render on a compiled circuit kernel
 //   abi_deliver.hip     interleave / peak / encode, host renders and their delivery
 //   abi_mix.hip         mix of a batch on the device, the tiles of a large batch, the host render of a mix
-//   abi_score.hip       scores: plans' image, the one launch path, device entries and host renders of scores and pieces
+//   abi_score.hip       scores: plans' image, the one launch path, device entries with a plan, the host render of a score (abi_score.hpp: what
+//                       the files that launch score kernels share)
+//   abi_piece.hip       pieces: the host renders of several instruments, with a master, buses, tracks, stems and meters
+//   abi_score_sweep.hip device entries without a plan: the buses' return, the tracks' mix, the common peak
 //   abi_meter.hip       meters: RMS and BS.1770 loudness of signals on the device, and the gates on the host
 #pragma once
 #include <limits>
@@ -69,14 +72,11 @@ hipError_t launch_score_stereo(const float *d_gains, const ScorePan *d_pans, con
 hipError_t launch_score_send(const float *d_gains, const ScoreSend *d_sends, const ScorePan *d_pans, const ScoreRow *d_voices, const uint32_t *d_block_first,
                              const uint32_t *d_entries, const float *d_init, float *d_out, const float *d_send_init, float *d_send_out, uint32_t n_buses, uint32_t n_channels,
                              uint64_t n_total, uint64_t w_lo, uint64_t w_hi, uint32_t block_shift, uint64_t first_block, int raw, bool pan, hipStream_t stream);
-hipError_t launch_score_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, uint64_t n, int raw, hipStream_t stream);
+hipError_t launch_score_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, float *d_stem_direct, float *const *d_stem_buses, uint64_t n, int raw,
+                               hipStream_t stream);
 hipError_t launch_score_tracks(const float *d_direct, const float *const *d_tracks, const float *h_faders, const float *h_levels, uint32_t n_tracks, uint32_t n_buses,
-                               float *d_out, const float *d_feed_init, float *d_feed_out, uint64_t n, int raw, hipStream_t stream);
-hipError_t launch_score_stems_mix(const float *d_direct, const float *const *d_tracks, const float *h_faders, const float *h_levels, uint32_t n_tracks, uint32_t n_buses,
-                                  float *d_out, const float *d_feed_init, float *d_feed_out, float *d_stem_direct, float *const *d_stem_tracks, uint64_t n, int raw,
-                                  hipStream_t stream);
-hipError_t launch_score_stems_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, float *d_stem_direct, float *const *d_stem_buses, uint64_t n,
-                                     int raw, hipStream_t stream);
+                               float *d_out, const float *d_feed_init, float *d_feed_out, float *d_stem_direct, float *const *d_stem_tracks, uint64_t n, int raw,
+                               hipStream_t stream);
 hipError_t launch_pcm_peak_common(const float *d_peaks, float *d_common, uint32_t n, hipStream_t stream);
 hipError_t launch_meter(const float *d_planar, uint32_t n_signals, uint32_t n_channels, uint64_t n, uint32_t hop, const MeterCoef &k, double *d_scratch, double *d_sumsq,
                         double *d_hops, hipStream_t stream, hipEvent_t *marks);
@@ -193,11 +193,11 @@ struct dusp_workspaces {
     DevBuf<float> d_host_out, d_host_par, d_host_frames, d_host_in;  // dusp_render_host staging, grown on demand
     DevBuf<unsigned char> d_host_pcm;                                // dusp_render_host_pcm: the encoded frames ...
     DevBuf<float> d_host_peaks;                                      // ... and the instances' peaks
-    DevBuf<float> d_host_peak_common;                                // ... a call with stems: the one peak of all its signals, once a signal (score_stems_engine.hip)
+    DevBuf<float> d_host_peak_common;                                // ... a call with stems: the one peak of all its signals, once a signal (pcm_peak_common.hpp)
     DevBuf<float> d_mix, d_mix_gains;                                // dusp_render_host_mix: the running sums [n_out_channels][n_samples]; one tile's gains
-    DevBuf<float> d_mix_sends;                                       // a piece with buses: the send timelines [n_buses][n_out_channels][n_total] (abi_score.hip)
-    DevBuf<float> d_mix_tracks;                                      // a piece with tracks: the track timelines [n_tracks][n_out_channels][n_total], in the order of the track programs (abi_score.hip)
-    DevBuf<float> d_stems;                                           // a piece with stems: the signals [1 + n_tracks + n_buses + 1][n_out_channels][n_total], the mix last (abi_score.hip)
+    DevBuf<float> d_mix_sends;                                       // a piece with buses: the send timelines [n_buses][n_out_channels][n_total] (abi_piece.hip)
+    DevBuf<float> d_mix_tracks;                                      // a piece with tracks: the track timelines [n_tracks][n_out_channels][n_total], in the order of the track programs (abi_piece.hip)
+    DevBuf<float> d_stems;                                           // a piece with stems: the signals [1 + n_tracks + n_buses + 1][n_out_channels][n_total], the mix last (abi_piece.hip)
     DevBuf<float> d_saved_bufs, d_rings_wave;  // wave engine, resumable: outlets' last chunk; rings parked during a migration
     // WAVE programs the circuit compiler takes (jit_codegen.hpp): the generated text's constants
     DevBuf<float> d_jit_fk;
@@ -473,7 +473,7 @@ struct TiledBatch {
     TiledBatch(dusp_program *prog, size_t n_instances, const float *h_params, const std::vector<size_t> &starts);  // tiles [starts[i], starts[i + 1])
     ~TiledBatch();
     // instances [lo, lo + n): their columns and gains to the device, their PCM into d_host_out.  d_inputs: the input streams of a
-    // program that has some, [n_inputs][n][n_samples] in device memory (the master of a piece reads the timeline: abi_score.hip)
+    // program that has some, [n_inputs][n][n_samples] in device memory (the master of a piece reads the timeline: abi_piece.hip)
     int render_tile(size_t lo, size_t n, size_t n_samples, const float *d_inputs = nullptr);
 
 private:

@@ -1,13 +1,13 @@
 // abi_meter.hip — the C ABI (include/dusp_hip.h): the meters of signals on the device (meter_engine.hip: sums of squares and K-weighted hop
 // sums, the K-weighting cut in time) and what the library makes of the few thousand doubles that come down, on the host in f64
-// (meter_plan.hpp: blocks from hops, the two gates, log10) — dusp_meter_blocks, dusp_meter_host, dusp_meter_last_ms, and what
-// dusp_meter_device and dusp_render_host_score_piece_meters (abi_score.hip) are made of.  DESIGN.md 6.18; dusp_amd/mix.py meters is the
+// (meter_plan.hpp: blocks from hops, the two gates, log10) — dusp_meter_blocks, dusp_meter_device, dusp_meter_host, dusp_meter_last_ms,
+// and what dusp_render_host_score_piece_meters (abi_piece.hip) meters its delivery with.  DESIGN.md 6.18; dusp_amd/mix.py meters is the
 // contract.
 #include <cmath>
 #include <string>
 #include <vector>
 
-#include "abi_internal.hpp"
+#include "abi_score.hpp"
 
 int meter_check(dusp_ctx *ctx, const char *who, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate) {
     const std::string w(who);
@@ -72,6 +72,32 @@ int dusp_meter_last_ms(dusp_ctx *ctx, float ms[4]) {
     HIP_TRY(ctx, hipEventSynchronize(ctx->meter_marks[4]));
     for (int i = 0; i < 4; i++) HIP_TRY(ctx, hipEventElapsedTime(&ms[i], ctx->meter_marks[i], ctx->meter_marks[i + 1]));
     return DUSP_OK;
+}
+
+// The meter kernels alone (meter_engine.hip): the sums of squares and the K-weighted hop sums of signals on the device
+int dusp_meter_device(dusp_ctx *ctx, const float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double *d_sumsq, double *d_hops,
+                      void *stream_) {
+    if (!ctx) return DUSP_ERR_ARG;
+    const char *who = "dusp_meter_device";
+    return guarded(ctx->err, who, [&]() -> int {
+    const std::string w(who);
+    if (!d_planar || !d_sumsq || !d_hops) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": NULL buffer");
+    if (int rc = meter_check(ctx, who, n_signals, n_channels, n_samples, sample_rate)) return rc;
+    if (((uintptr_t)d_planar & 3) || (((uintptr_t)d_sumsq | (uintptr_t)d_hops) & 7)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": d_planar must be 4-byte aligned, d_sumsq and d_hops 8-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    dusp::MeterGeometry G;
+    if (int rc = meter_scratch(ctx, n_signals * n_channels, n_samples, dusp::meter_hop(sample_rate), 0, G)) return rc;
+    for (hipEvent_t &ev : ctx->meter_marks)
+        if (!ev) HIP_TRY(ctx, hipEventCreate(&ev));
+    ctx->meter_timed = false;
+    const int rc = score_unplanned_call(ctx, stream_, [&](hipStream_t stream) {  // (timed like a score launch too: dusp_score_last_ms)
+        HIP_TRY(ctx, dusp::launch_meter(d_planar, (uint32_t)n_signals, (uint32_t)n_channels, n_samples, dusp::meter_hop(sample_rate), dusp::meter_k_weighting(sample_rate),
+                                        ctx->d_meter, d_sumsq, d_hops, stream, ctx->meter_marks));
+        return DUSP_OK;
+    });
+    ctx->meter_timed = rc == DUSP_OK;
+    return rc;
+    });
 }
 
 int dusp_meter_host(dusp_ctx *ctx, const float *h_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double *h_rms, double *h_lufs,

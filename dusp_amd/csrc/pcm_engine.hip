@@ -18,10 +18,14 @@
 // transpose: 8 samples go from two 16-byte loads to one 16-byte store of 8 shorts (24 bytes for s24, 32 for f32).
 //
 // Gains are derived here, on the device, from the peaks (pcm_gain): no host round trip between the two kernels.
+//
+// One peak for all signals of a block (a call with stems): pcm_peak_common.hpp, a kernel of this object over the peak kernel's words, in
+// a header of its own because its text also compiles for the host under tests/native/hip_host_stub, which the kernels here do not.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "pcm_peak_common.hpp"
 #include "pcm_quant.hpp"
 
 namespace dusp {

@@ -17,6 +17,11 @@ namespace dusp {
 // NaN and -0 leave as +0 (`x || 0`)
 static __device__ __forceinline__ float score_or0(float a) { return (a != a || a == 0.0f) ? 0.0f : a; }
 
+// the one argument the STEMS instance of a kernel takes beyond the plain one's, as a parameter pack of one float * or of nothing
+// (score_tracks_engine.hip, score_send_engine.hip's return): the pointer, or nullptr where the pack is empty
+static __device__ __forceinline__ float *score_stem_direct() { return nullptr; }
+static __device__ __forceinline__ float *score_stem_direct(float *stem_direct) { return stem_direct; }
+
 // a record of 32 bytes (ScoreRow, ScorePan) or of 16 (ScoreFrac) as ONE load: its words as a vector (field by field the compiler splits
 // a ScoreRow into four, two and one dwords)
 typedef uint32_t ScoreWords8 __attribute__((vector_size(32), may_alias));

@@ -27,7 +27,8 @@
 //
 // dusp_score_return_kernel: out = dry; for b: out = f32(out + wet_b); `|| 0` unless raw — Sum.many([dry, wet_0, ...]), left-deep.  All
 // buffers are [C][n_total], taken as flat arrays of n floats: four floats a lane as one 16-byte load and store where every buffer is on
-// a 16-byte boundary, and the n % 4 floats behind them (or, where one is not, all n) one a lane.  out may be dry.
+// a 16-byte boundary, and the n % 4 floats behind them (or, where one is not, all n) one a lane.  out may be dry.  Its STEMS instance
+// also copies every wet_b it reads into the bus's slot and, where asked, dry || 0 into the direct slot.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -247,17 +248,30 @@ hipError_t launch_score_send(const float *d_gains, const ScoreSend *d_sends, con
 
 // ---- the return of the buses ----
 
+template <bool STEMS>
 struct ScoreWets {  // the buses' outputs, each [n] floats; the first n_buses are read
     const float *p[kScoreBusMax];
 };
+template <>
+struct ScoreWets<true> {  // ... and the buses' slots, each [n] floats
+    const float *p[kScoreBusMax];
+    float *stem[kScoreBusMax];
+};
 
-// n_vec lanes take four floats each, the n - 4 * n_vec floats behind them one lane each
-__global__ void __launch_bounds__(256) dusp_score_return_kernel(const float *dry, ScoreWets wets, uint32_t n_buses, float *out, uint64_t n, uint64_t n_vec, int raw) {
+// n_vec lanes take four floats each, the n - 4 * n_vec floats behind them one lane each.  StemDirect: with STEMS one float *, nullptr
+// or where dry || 0 goes; without, nothing — the arguments of that instance hold no stem pointer at all
+template <bool STEMS, class... StemDirect>
+__global__ void __launch_bounds__(256) dusp_score_return_kernel(const float *dry, ScoreWets<STEMS> wets, uint32_t n_buses, float *out, StemDirect... stem_direct_, uint64_t n,
+                                                                 uint64_t n_vec, int raw) {
+    static_assert(sizeof...(StemDirect) == (STEMS ? 1 : 0), "stem_direct is an argument of the STEMS instance alone");
+    float *stem_direct = score_stem_direct(stem_direct_...);
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_vec) {
         float4 a = ((const float4 *)dry)[i];
+        if (STEMS && stem_direct) ((float4 *)stem_direct)[i] = make_float4(score_or0(a.x), score_or0(a.y), score_or0(a.z), score_or0(a.w));
         for (uint32_t b = 0; b < n_buses; b++) {
             const float4 w = ((const float4 *)wets.p[b])[i];
+            if constexpr (STEMS) ((float4 *)wets.stem[b])[i] = w;
             a.x = a.x + w.x;
             a.y = a.y + w.y;
             a.z = a.z + w.z;
@@ -270,22 +284,45 @@ __global__ void __launch_bounds__(256) dusp_score_return_kernel(const float *dry
     const uint64_t j = 4 * n_vec + (i - n_vec);
     if (j >= n) return;
     float a = dry[j];
-    for (uint32_t b = 0; b < n_buses; b++) a = a + wets.p[b][j];
+    if (STEMS && stem_direct) stem_direct[j] = score_or0(a);
+    for (uint32_t b = 0; b < n_buses; b++) {
+        const float w = wets.p[b][j];
+        if constexpr (STEMS) wets.stem[b][j] = w;
+        a = a + w;
+    }
     out[j] = raw ? a : score_or0(a);
 }
 
-// out[j] = dry[j] + wets[0][j] + ... (left-deep), `|| 0` unless raw, over n floats, 1 <= n <= 2^31; n_buses <= kScoreBusMax (0: dry -> out)
-hipError_t launch_score_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, uint64_t n, int raw, hipStream_t stream) {
-    if (n_buses > kScoreBusMax) return (hipError_t)1;  // (hipErrorInvalidValue: the callers have checked)
-    ScoreWets wets{};
-    uintptr_t low = (uintptr_t)d_dry | (uintptr_t)d_out;
+template <bool STEMS>
+static void launch_score_return_as(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, float *d_stem_direct, float *const *d_stem_buses, uint64_t n, int raw,
+                                   hipStream_t stream) {
+    ScoreWets<STEMS> wets{};
+    uintptr_t low = (uintptr_t)d_dry | (uintptr_t)d_out | (uintptr_t)d_stem_direct;
     for (uint32_t b = 0; b < n_buses; b++) {
         wets.p[b] = d_wets[b];
         low |= (uintptr_t)d_wets[b];
+        if constexpr (STEMS) {
+            wets.stem[b] = d_stem_buses[b];
+            low |= (uintptr_t)d_stem_buses[b];
+        }
     }
     const uint64_t n_vec = (low & 15) ? 0 : n / 4, lanes = n_vec + (n - 4 * n_vec);
     const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-    hipLaunchKernelGGL(dusp_score_return_kernel, grid, block, 0, stream, d_dry, wets, n_buses, d_out, n, n_vec, raw);
+    if constexpr (STEMS)
+        hipLaunchKernelGGL((dusp_score_return_kernel<true, float *>), grid, block, 0, stream, d_dry, wets, n_buses, d_out, d_stem_direct, n, n_vec, raw);
+    else
+        hipLaunchKernelGGL((dusp_score_return_kernel<false>), grid, block, 0, stream, d_dry, wets, n_buses, d_out, n, n_vec, raw);
+}
+
+// out[j] = dry[j] + wets[0][j] + ... (left-deep), `|| 0` unless raw, over n floats, 1 <= n <= 2^31; n_buses <= kScoreBusMax (0: dry -> out).
+// d_stem_buses given (the stems of a piece): the launch also writes d_stem_buses[b][j] = d_wets[b][j], as it is (the
+// bus's copy-out has made it `|| 0`), and, d_stem_direct given — the dry timeline has no slot yet: per-note sends without tracks —
+// d_stem_direct[j] = d_dry[j] || 0.  The slots are n floats each and alias nothing.  d_stem_buses nullptr: d_stem_direct is not looked at.
+hipError_t launch_score_return(const float *d_dry, const float *const *d_wets, uint32_t n_buses, float *d_out, float *d_stem_direct, float *const *d_stem_buses, uint64_t n, int raw,
+                               hipStream_t stream) {
+    if (n_buses > kScoreBusMax) return (hipError_t)1;  // (hipErrorInvalidValue: the callers have checked)
+    d_stem_buses ? launch_score_return_as<true>(d_dry, d_wets, n_buses, d_out, d_stem_direct, d_stem_buses, n, raw, stream)
+                 : launch_score_return_as<false>(d_dry, d_wets, n_buses, d_out, nullptr, nullptr, n, raw, stream);
     return hipGetLastError();
 }
 

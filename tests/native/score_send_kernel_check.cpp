@@ -208,7 +208,7 @@ int main() {
             }
             float *out = in_place ? buf[0] : buf[5];
             const float *wets[4] = {buf[1], buf[2], buf[3], buf[4]};
-            const hipError_t err = dusp::launch_score_return(buf[0], wets, (uint32_t)B, out, n, raw, nullptr);
+            const hipError_t err = dusp::launch_score_return(buf[0], wets, (uint32_t)B, out, nullptr, nullptr, n, raw, nullptr);
             const bool ok = err == hipSuccess && same_bits(out, want.data(), n);
             returns++;
             if (!ok) { bad++; if (bad < 20) printf("RETURN MISMATCH n %zu B %d raw %d in_place %d aligned %d\n", n, B, raw, in_place, aligned); }

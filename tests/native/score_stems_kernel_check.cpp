@@ -1,8 +1,9 @@
-// score_stems_kernel_check.cpp — the text of dusp_amd/csrc/score_stems_engine.hip compiled for the HOST (hip_host_stub/: lanes one
-// after the other) and held on bit patterns
+// score_stems_kernel_check.cpp — the text of the STEMS instances of dusp_amd/csrc/score_tracks_engine.hip's mix kernel and of
+// score_send_engine.hip's return kernel, and of pcm_peak_common.hpp, compiled for the HOST (hip_host_stub/: lanes one after the other)
+// and held on bit patterns
 //   * to a plain loop over the contract (dusp_amd/mix.py track_terms, track_mix, bus_return, stems): the slots are direct || 0,
 //     term_g || 0 and every wet as it is, the mix and the feeds what they were;
-//   * to the OLD kernels' text (score_tracks_engine.hip, score_send_engine.hip's return) over the same inputs: mix and feeds bit for bit.
+//   * to the instances WITHOUT stems of the same two templates (a launch without slots) over the same inputs: mix and feeds bit for bit.
 // EVERY BUFFER IS A HEAP ALLOCATION OF EXACTLY ITS SIZE behind its offset, so under AddressSanitizer one float read or written outside
 // a buffer is reported.
 // Covered, mix kernel: n = 1, 3, 4, 5, 1027, 4636 floats; T = 0 .. 8; B = 0 .. 4; with and without faders; raw and not; out of place
@@ -15,7 +16,7 @@
 // Prints {"cases": n, "bad": m, "wide": w, "narrow": s, "strided": g, "old": o}.
 #include "../../dusp_amd/csrc/score_tracks_engine.hip"
 #include "../../dusp_amd/csrc/score_send_engine.hip"
-#include "../../dusp_amd/csrc/score_stems_engine.hip"
+#include "../../dusp_amd/csrc/pcm_peak_common.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -91,13 +92,13 @@ static void mix_case(size_t n, int T, int B, int faders, int raw, int in_place, 
     float *slots[8];
     for (int g = 0; g < T; g++) ptrs[g] = tracks[g].p, slots[g] = stems.p + (size_t)(1 + g) * n;
     float *o = in_place ? direct.p : out.p;
-    const hipError_t err = dusp::launch_score_stems_mix(direct.p, ptrs, faders ? fader : nullptr, B ? level : nullptr, (uint32_t)T, (uint32_t)B, o, nullptr, B ? feed_out.p : nullptr,
-                                                        stems.p, slots, n, raw, nullptr);
+    const hipError_t err = dusp::launch_score_tracks(direct.p, ptrs, faders ? fader : nullptr, B ? level : nullptr, (uint32_t)T, (uint32_t)B, o, nullptr, B ? feed_out.p : nullptr,
+                                                     stems.p, slots, n, raw, nullptr);
     const unsigned grid = g_last_grid;
     bool ok = err == hipSuccess && same_bits(o, want.data(), n) && (B == 0 || same_bits(feed_out.p, fwant.data(), (size_t)B * n)) && same_bits(stems.p, swant.data(), (size_t)(1 + T) * n);
-    if (T > 0) {  // the old kernel's text over the same inputs: its mix and feeds, bit for bit (memcmp: NaN payloads too)
+    if (T > 0) {  // the instance without stems over the same inputs: its mix and feeds, bit for bit (memcmp: NaN payloads too)
         float *oo = in_place ? direct_old.p : out_old.p;
-        const hipError_t e2 = dusp::launch_score_tracks(direct_old.p, ptrs, faders ? fader : nullptr, B ? level : nullptr, (uint32_t)T, (uint32_t)B, oo, nullptr, B ? feed_old.p : nullptr, n, raw, nullptr);
+        const hipError_t e2 = dusp::launch_score_tracks(direct_old.p, ptrs, faders ? fader : nullptr, B ? level : nullptr, (uint32_t)T, (uint32_t)B, oo, nullptr, B ? feed_old.p : nullptr, nullptr, nullptr, n, raw, nullptr);
         ok &= e2 == hipSuccess && memcmp(oo, o, n * 4) == 0 && (B == 0 || memcmp(feed_old.p, feed_out.p, (size_t)B * n * 4) == 0);
         old_held++;
     }
@@ -129,8 +130,8 @@ static void return_case(size_t n, int B, int with_direct, int raw, int in_place,
     float *slots[4];
     for (int b = 0; b < B; b++) ptrs[b] = wets[b].p, slots[b] = slot_buses.p + (size_t)b * n;
     float *o = in_place ? dry.p : out.p, *oo = in_place ? dry_old.p : out_old.p;
-    const hipError_t err = dusp::launch_score_stems_return(dry.p, ptrs, (uint32_t)B, o, with_direct ? slot_direct.p : nullptr, slots, n, raw, nullptr);
-    const hipError_t e2 = dusp::launch_score_return(dry_old.p, ptrs, (uint32_t)B, oo, n, raw, nullptr);
+    const hipError_t err = dusp::launch_score_return(dry.p, ptrs, (uint32_t)B, o, with_direct ? slot_direct.p : nullptr, slots, n, raw, nullptr);
+    const hipError_t e2 = dusp::launch_score_return(dry_old.p, ptrs, (uint32_t)B, oo, nullptr, nullptr, n, raw, nullptr);
     bool ok = err == hipSuccess && e2 == hipSuccess && same_bits(o, want.data(), n) && memcmp(o, oo, n * 4) == 0 && (!with_direct || same_bits(slot_direct.p, dwant.data(), n));
     for (int b = 0; b < B; b++) ok &= memcmp(slots[b], wets[b].p, n * 4) == 0;  // (a copy: NaN payloads and -0 as they are)
     old_held++;

@@ -84,7 +84,7 @@ static void one_case(size_t n, int T, int B, int faders, int raw, int in_place, 
     float *o = in_place ? direct.p : out.p;
     const float *fi = feed_mode == 0 ? nullptr : feed_in.p;
     float *fo = B == 0 ? nullptr : feed_mode == 2 ? feed_in.p : feed_out.p;
-    const hipError_t err = dusp::launch_score_tracks(direct.p, ptrs, faders ? fader : nullptr, B ? level : nullptr, (uint32_t)T, (uint32_t)B, o, B ? fi : nullptr, fo, n, raw, nullptr);
+    const hipError_t err = dusp::launch_score_tracks(direct.p, ptrs, faders ? fader : nullptr, B ? level : nullptr, (uint32_t)T, (uint32_t)B, o, B ? fi : nullptr, fo, nullptr, nullptr, n, raw, nullptr);
     const bool ok = err == hipSuccess && same_bits(o, want.data(), n) && (B == 0 || same_bits(fo, fwant.data(), (size_t)B * n));
     checked++;
     // which path the launch took: the wide one needs every buffer, each feed included, on a 16-byte boundary

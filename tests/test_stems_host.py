@@ -234,8 +234,9 @@ def test_stems_travel_with_the_placement_to_the_piece():
 # ---- the kernels' text, under sanitizers ------------------------------------------------------------------------------------------------
 
 def test_score_stems_kernel_text_on_the_host_under_sanitizers(tmp_path):
-    """dusp_amd/csrc/score_stems_engine.hip itself, compiled for the host with its lanes run one after the other, every buffer a heap
-    allocation of exactly its size, under AddressSanitizer and UBSan, against a brute-force loop and against the old kernels' text
+    """the STEMS instances of the mix and return kernels (dusp_amd/csrc/score_tracks_engine.hip, score_send_engine.hip) and
+    pcm_peak_common.hpp themselves, compiled for the host with their lanes run one after the other, every buffer a heap allocation of
+    exactly its size, under AddressSanitizer and UBSan, against a brute-force loop and against the instances without stems
     (tests/native/score_stems_kernel_check.cpp lists what it covers).  A stand-alone program, run as a subprocess."""
     native = os.path.join(ROOT, "tests", "native")
     exe = str(tmp_path / "score_stems_kernel_check")
