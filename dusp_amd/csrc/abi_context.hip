@@ -124,6 +124,7 @@ void dusp_ctx_destroy(dusp_ctx *ctx) {
     if (ctx->d_tables) (void)hipFree(ctx->d_tables);
     if (ctx->d_score_plan) (void)hipFree(ctx->d_score_plan);
     if (ctx->d_meter) (void)hipFree(ctx->d_meter);
+    if (ctx->d_true_peak) (void)hipFree(ctx->d_true_peak);
     for (hipEvent_t ev : ctx->meter_marks)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->score_uploaded) (void)hipEventDestroy(ctx->score_uploaded);

@@ -163,37 +163,9 @@ static hipError_t download_staged(dusp_program *prog, void *h_out_, const void *
 
 }  // extern "C"
 
-// What a host render ends with: d_planar f32 [n_instances][n_ch][n_samples] (or, already transposed, d_frames) reaches h_out — as it is,
-// or (pcm_format != 0) through the peak and encode kernels — by the delivery paths above; waits for the stream.
-int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
-                 int normalise, float *h_peaks, void *h_out, bool common_peak) {
+// d_src, n_bytes of device memory, reaches h_out by the delivery paths above; waits for the stream
+static int deliver_download(dusp_program *prog, const void *d_src, size_t n_bytes, void *h_out) {
     dusp_ctx *ctx = prog->ctx;
-    const size_t n_out = n_instances * n_ch * n_samples;
-    const void *d_src = d_frames ? d_frames : d_planar;
-    size_t n_bytes = n_out * sizeof(float);
-    const float *d_peaks = nullptr;
-    if ((pcm_format && (normalise || h_peaks)) || (common_peak && h_peaks)) {  // (the signals of a call with stems are metered whatever the format)
-        HIP_TRY(ctx, prog->d_host_peaks.ensure(n_instances));
-        d_peaks = prog->d_host_peaks.p;
-        if (int rc = dusp_peak_device(ctx, d_planar, n_instances, n_ch, n_samples, prog->d_host_peaks.p, ctx->stream)) return rc;
-        if (h_peaks) HIP_TRY(ctx, hipMemcpyAsync(h_peaks, d_peaks, n_instances * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (pcm_format) {  // peak, gain, quantisation and interleave on the device: 2 or 3 bytes a sample cross the link
-        if (common_peak && normalise) {  // (one gain for all: the encoder reads peaks[inst], every one of them the largest)
-            HIP_TRY(ctx, prog->d_host_peak_common.ensure(n_instances));
-            HIP_TRY(ctx, dusp::launch_pcm_peak_common(d_peaks, prog->d_host_peak_common.p, (uint32_t)n_instances, ctx->stream));
-            d_peaks = prog->d_host_peak_common.p;
-        }
-        n_bytes = n_out * (size_t)dusp::pcm_bytes_per_sample(pcm_format);
-        HIP_TRY(ctx, prog->d_host_pcm.ensure(n_bytes));
-        if (int rc = dusp_encode_device(ctx, d_planar, n_instances, n_ch, n_samples, pcm_format, normalise, d_peaks, prog->d_host_pcm.p, ctx->stream)) return rc;
-        if (g_guard_bytes) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact() || !prog->d_host_peak_common.intact())
-                CTX_FAIL(ctx, DUSP_ERR_HIP, "render: the PCM encoder wrote past the end of a device buffer: guard bytes overwritten");
-        }
-        d_src = prog->d_host_pcm.p;
-    }
     if (n_bytes >= kStagedMinBytes && !is_pinned_host(h_out)) {
         HIP_TRY(ctx, download_staged(prog, h_out, d_src, n_bytes));
     } else {  // pinned destination: one DMA at link speed; small output: not worth more
@@ -201,6 +173,65 @@ int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frame
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return DUSP_OK;
+}
+
+// gain, quantisation and interleave on the device, into the program's d_host_pcm: 2 or 3 bytes a sample cross the link.  -> its bytes
+static int deliver_encode(dusp_program *prog, const float *d_planar, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format, int normalise, const float *d_peaks,
+                          size_t &n_bytes) {
+    dusp_ctx *ctx = prog->ctx;
+    n_bytes = n_instances * n_ch * n_samples * (size_t)dusp::pcm_bytes_per_sample(pcm_format);
+    HIP_TRY(ctx, prog->d_host_pcm.ensure(n_bytes));
+    if (int rc = dusp_encode_device(ctx, d_planar, n_instances, n_ch, n_samples, pcm_format, normalise, d_peaks, prog->d_host_pcm.p, ctx->stream)) return rc;
+    if (g_guard_bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (!prog->d_host_pcm.intact() || !prog->d_host_peaks.intact() || !prog->d_host_peak_common.intact())
+            CTX_FAIL(ctx, DUSP_ERR_HIP, "render: the PCM encoder wrote past the end of a device buffer: guard bytes overwritten");
+    }
+    return DUSP_OK;
+}
+
+int deliver_peaks(dusp_program *prog, const float *d_planar, size_t n_instances, size_t n_ch, size_t n_samples, float *h_peaks) {
+    dusp_ctx *ctx = prog->ctx;
+    HIP_TRY(ctx, prog->d_host_peaks.ensure(n_instances));
+    if (int rc = dusp_peak_device(ctx, d_planar, n_instances, n_ch, n_samples, prog->d_host_peaks.p, ctx->stream)) return rc;
+    if (h_peaks) HIP_TRY(ctx, hipMemcpyAsync(h_peaks, prog->d_host_peaks.p, n_instances * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return DUSP_OK;
+}
+
+int deliver_at_level(dusp_program *prog, const float *d_planar, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format, float level, void *h_out) {
+    dusp_ctx *ctx = prog->ctx;
+    const std::vector<float> levels(n_instances, level);  // (the upload has read it once the delivery has waited for the stream)
+    HIP_TRY(ctx, prog->d_host_peak_common.ensure(n_instances));
+    HIP_TRY(ctx, hipMemcpyAsync(prog->d_host_peak_common.p, levels.data(), n_instances * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    size_t n_bytes = 0;
+    int rc = deliver_encode(prog, d_planar, n_instances, n_ch, n_samples, pcm_format, DUSP_NORMALISE_FULL, prog->d_host_peak_common.p, n_bytes);
+    if (!rc) rc = deliver_download(prog, prog->d_host_pcm.p, n_bytes, h_out);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+// What a host render ends with: d_planar f32 [n_instances][n_ch][n_samples] (or, already transposed, d_frames) reaches h_out — as it is,
+// or (pcm_format != 0) through the peak and encode kernels — by the delivery paths above; waits for the stream.
+int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
+                 int normalise, float *h_peaks, void *h_out, bool common_peak) {
+    dusp_ctx *ctx = prog->ctx;
+    const void *d_src = d_frames ? d_frames : d_planar;
+    size_t n_bytes = n_instances * n_ch * n_samples * sizeof(float);
+    const float *d_peaks = nullptr;
+    if ((pcm_format && (normalise || h_peaks)) || (common_peak && h_peaks)) {  // (the signals of a call with stems are metered whatever the format)
+        if (int rc = deliver_peaks(prog, d_planar, n_instances, n_ch, n_samples, h_peaks)) return rc;
+        d_peaks = prog->d_host_peaks.p;
+    }
+    if (pcm_format) {
+        if (common_peak && normalise) {  // (one gain for all: the encoder reads peaks[inst], every one of them the largest)
+            HIP_TRY(ctx, prog->d_host_peak_common.ensure(n_instances));
+            HIP_TRY(ctx, dusp::launch_pcm_peak_common(d_peaks, prog->d_host_peak_common.p, (uint32_t)n_instances, ctx->stream));
+            d_peaks = prog->d_host_peak_common.p;
+        }
+        if (int rc = deliver_encode(prog, d_planar, n_instances, n_ch, n_samples, pcm_format, normalise, d_peaks, n_bytes)) return rc;
+        d_src = prog->d_host_pcm.p;
+    }
+    return deliver_download(prog, d_src, n_bytes, h_out);
 }
 
 extern "C" {

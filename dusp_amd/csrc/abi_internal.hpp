@@ -35,6 +35,7 @@
 #include "meter_plan.hpp"
 #include "program.hpp"
 #include "score_plan.hpp"
+#include "truepeak_plan.hpp"
 
 namespace dusp {
 hipError_t launch_chunk_engine(const ChunkArgs &a, hipStream_t stream);
@@ -80,6 +81,7 @@ hipError_t launch_score_tracks(const float *d_direct, const float *const *d_trac
 hipError_t launch_pcm_peak_common(const float *d_peaks, float *d_common, uint32_t n, hipStream_t stream);
 hipError_t launch_meter(const float *d_planar, uint32_t n_signals, uint32_t n_channels, uint64_t n, uint32_t hop, const MeterCoef &k, double *d_scratch, double *d_sumsq,
                         double *d_hops, hipStream_t stream, hipEvent_t *marks);
+hipError_t launch_true_peak(const float *d_planar, uint64_t rows, uint64_t n, uint32_t F, const TruePeakTaps &taps, int n_cus, uint64_t *d_words, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -132,6 +134,9 @@ struct dusp_ctx {
     size_t meter_cap = 0;  // doubles
     hipEvent_t meter_marks[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool meter_timed = false;
+    // the true peaks' words (abi_loudness.hip; truepeak_engine.hip), one a (signal, channel), grown on demand
+    uint64_t *d_true_peak = nullptr;
+    size_t true_peak_cap = 0;  // words
 };
 
 // DUSP_GUARD=1 (tests): every device allocation of the library carries guard bytes behind its end, filled with a pattern and
@@ -424,6 +429,12 @@ inline int check_planar_pcm(dusp_ctx *ctx, const char *who, size_t n_instances, 
 // the signals of one call — their peaks are taken whatever the format (h_peaks: all of them), and what normalises is the largest.
 int deliver_host(dusp_program *prog, const float *d_planar, const float *d_frames, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format,
                  int normalise, float *h_peaks, void *h_out, bool common_peak = false);
+// ... and its two halves, for a delivery that decides between them (abi_piece.hip, a delivery at a loudness target).  deliver_peaks: the
+// instances' sample peaks into the program's d_host_peaks and, asynchronously, into h_peaks (NULL: not asked for).  deliver_at_level:
+// every instance's frames encoded under pcm_gain(bits(level), FULL) — `level` goes into the word array the encoder reads, once an
+// instance — and downloaded; waits for the stream
+int deliver_peaks(dusp_program *prog, const float *d_planar, size_t n_instances, size_t n_ch, size_t n_samples, float *h_peaks);
+int deliver_at_level(dusp_program *prog, const float *d_planar, size_t n_instances, size_t n_ch, size_t n_samples, int pcm_format, float level, void *h_out);
 
 // abi_meter.hip
 // What a call may be metered at: refuses a sample rate below 8000 and shapes the kernels do not take, in `who`'s name
@@ -436,6 +447,14 @@ int meter_finish(dusp_ctx *ctx, const char *who, size_t n_signals, size_t n_chan
                  double *h_momentary);
 // the scratch of a call, grown on demand: `extra` doubles behind what the kernels take
 int meter_scratch(dusp_ctx *ctx, size_t rows, size_t n_samples, uint32_t hop, size_t extra, dusp::MeterGeometry &G);
+
+// abi_loudness.hip
+// The true peaks of d_planar [n_signals][n_channels][n_samples] on `stream`, into the context's words; true_peak_download copies them
+// down behind what the stream holds (asynchronously: the caller waits for the stream, then calls true_peak_values)
+int true_peak_launch(dusp_ctx *ctx, const float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, hipStream_t stream);
+int true_peak_download(dusp_ctx *ctx, size_t rows, std::vector<uint64_t> &h_words, hipStream_t stream);
+// the words of a call, once the stream has been waited for -> h_true_peak [rows]; the largest of them, a NaN winning; the guard checked
+int true_peak_values(dusp_ctx *ctx, const char *who, const std::vector<uint64_t> &h_words, double *h_true_peak, double *largest);
 
 // abi_mix.hip
 constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)

@@ -1,7 +1,7 @@
 // abi_piece.hip — the C ABI (include/dusp_hip.h): the host renders of a PIECE — the voices of several instruments (parts) placed into one
 // timeline: dusp_render_host_score_parts and its pan, frac, space and stereo forms, and dusp_render_host_score_piece, which is all of
 // them and takes a master, with _buses (effect sends, 6.15), _tracks (sub-mixes, 6.16), _stems (every signal beside the
-// mix, 6.17) and _meters (6.18).  One record of the call (PieceCall) and one driver, render_host_score_parts, that reads as its stages:
+// mix, 6.17), _meters (6.18) and _loudness (true peaks, and a delivery at a loudness target: 6.19).  One record of the call (PieceCall) and one driver, render_host_score_parts, that reads as its stages:
 // check, tiles, plans, buffers, render, finish.  Behind them what a master, the buses, the tracks and the stems are held to and do.
 #include <chrono>
 #include <cmath>
@@ -33,6 +33,7 @@ struct PieceCall {
     const dusp_score_tracks *tracks = nullptr;  // ..._tracks
     const dusp_score_stems *stems = nullptr;    // ..._stems: h_out takes 1 + tracks + buses + 1 signals and h_peak as many peaks
     const dusp_score_meters *meters = nullptr;  // ..._meters
+    const dusp_score_loudness *loud = nullptr;  // ..._loudness: the true peak of every delivered (signal, channel), and with deliver the one gain
 
     dusp_program *prog0() const { return parts[0].prog; }  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx() const { return parts[0].prog->ctx; }
@@ -348,6 +349,27 @@ static int piece_check(PieceCall &call, PieceFacts &F) {
     return DUSP_OK;
 }
 
+// check, behind every other refusal of the call (the tiles' included: a format or normalise that is none): what a call with a
+// loudness record is held to
+static int piece_check_loudness(const PieceCall &call, const PieceFacts &F) {
+    const dusp_score_loudness *loud = call.loud;
+    if (!loud) return DUSP_OK;
+    dusp_ctx *ctx = call.ctx();
+    const std::string w(call.who);
+    if (!loud->h_true_peak) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the loudness record's h_true_peak is NULL: the true peak of every signal and channel goes there");
+    if (loud->deliver && !call.meters) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": deliver at a loudness target needs meters: the gain comes from the loudness of the mix");
+    if (loud->deliver && !call.format)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": deliver at a loudness target needs a PCM format, not 0: frames of DUSP_PCM_F32 are the f32 delivery at a target");
+    if (loud->deliver && call.normalise != 0)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": deliver at a loudness target does not go with normalise " + std::to_string(call.normalise) + ": the target decides the gain, normalise must be 0");
+    if (loud->deliver && !std::isfinite(loud->target_lufs)) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the loudness target must be a finite number of LUFS, not " + std::to_string(loud->target_lufs));
+    if (loud->deliver && !(std::isfinite(loud->ceiling_dbtp) && loud->ceiling_dbtp <= 0.0))
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": the true-peak ceiling must be a finite number of dBTP at most 0, not " + std::to_string(loud->ceiling_dbtp));
+    if (F.sample_rate < dusp::kMeterRateMin)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": meters need a sample rate of at least 8000 Hz, not " + std::to_string(F.sample_rate) + ": the K-weighting's shelf lies at 1682 Hz");
+    return DUSP_OK;
+}
+
 // The tiles of a call: runs of the chain's voices whose rows together fit tile_bytes.  A part's share of tile i is its instances
 // [share[p][i], share[p][i + 1]), one contiguous range since its instances enter the chain in their own order; its tile buffer holds the
 // largest share
@@ -532,15 +554,42 @@ static int piece_render(const PieceCall &call, const PieceFacts &F, const PieceT
 // deliver_host of a block that no kernel writes any more, [n_signals][n_ch][n_total] — metered on the way where the call has meters: the
 // meter kernels run on the context's stream in front of the peak and encode kernels, over the f32 signals in front of the PCM gain, and
 // what they leave is gated once the delivery has waited for the stream
-static int deliver_metered(dusp_program *prog, const char *who, const dusp_score_meters *meters, uint32_t sample_rate, const float *d_block, size_t n_signals, size_t n_ch,
-                           size_t n_total, int format, int normalise, float *h_peaks, void *h_out, bool common_peak) {
+//
+// With a loudness record the true-peak kernel runs behind the meter kernels and in front of the peak kernel.  Without
+// deliver its words come down where the meters' sums do, behind a delivery that is the call's without the record.  With deliver the
+// peak kernel follows, then the ONE wait for the stream: the gates, the largest true peak of any signal and channel and the loudness of
+// the MIX — the last signal — give the level (truepeak_plan.hpp true_peak_loudness_gain, f64 on the host), which the encoders read as
+// every signal's peak word under DUSP_NORMALISE_FULL: one gain for all, the encode kernels unchanged
+static int deliver_metered(dusp_program *prog, const char *who, const dusp_score_meters *meters, const dusp_score_loudness *loud, uint32_t sample_rate, const float *d_block,
+                           size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise, float *h_peaks, void *h_out, bool common_peak) {
     dusp_ctx *ctx = prog->ctx;
+    std::vector<uint64_t> words;
     if (meters)
         if (int rc = meter_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, ctx->stream)) return rc;
-    if (int rc = deliver_host(prog, d_block, nullptr, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak)) return rc;
-    if (meters)
+    if (loud)
+        if (int rc = true_peak_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, ctx->stream)) return rc;
+    const bool at_target = loud && loud->deliver;
+    if (at_target) {
+        if (h_peaks)
+            if (int rc = deliver_peaks(prog, d_block, n_signals, n_ch, n_total, h_peaks)) return rc;
+    } else {
+        if (int rc = deliver_host(prog, d_block, nullptr, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak)) return rc;
+    }
+    if (loud)
+        if (int rc = true_peak_download(ctx, n_signals * n_ch, words, ctx->stream)) return rc;
+    if (meters) {  // (waits for the stream)
         if (int rc = meter_finish(ctx, who, n_signals, n_ch, n_total, sample_rate, ctx->stream, meters->h_rms, meters->h_lufs, meters->h_momentary)) return rc;
-    return DUSP_OK;
+    } else if (loud) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (!loud) return DUSP_OK;
+    double largest = 0.0, gain = 1.0;
+    float level = 1.0f;
+    if (int rc = true_peak_values(ctx, who, words, loud->h_true_peak, &largest)) return rc;
+    if (at_target) dusp::true_peak_loudness_gain(meters->h_lufs[n_signals - 1], largest, loud->target_lufs, loud->ceiling_dbtp, gain, level);
+    if (loud->h_gain) *loud->h_gain = gain;
+    if (loud->h_level) *loud->h_level = level;
+    return at_target ? deliver_at_level(prog, d_block, n_signals, n_ch, n_total, format, level, h_out) : DUSP_OK;
 }
 
 // The one delivery: n_signals signals from d_block, under one gain where common_peak says so; it waits for the stream.  With a master
@@ -557,7 +606,7 @@ static int piece_deliver(const PieceCall &call, const PieceFacts &F, const float
         if (call.stems)
             HIP_TRY(ctx, hipMemcpyAsync(prog0->d_stems.p + (n_signals - 1) * F.timeline, call.master->prog->d_host_out.p, F.timeline * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    return deliver_metered(prog0, call.who, call.meters, F.sample_rate, d_block, n_signals, F.n_out_ch, call.n_total, call.format, call.normalise, call.h_peak, call.h_out, common_peak);
+    return deliver_metered(prog0, call.who, call.meters, call.loud, F.sample_rate, d_block, n_signals, F.n_out_ch, call.n_total, call.format, call.normalise, call.h_peak, call.h_out, common_peak);
 }
 
 // guards, behind the delivery: the buffers of the piece that the call used, then every auxiliary program's own
@@ -615,6 +664,7 @@ static int render_host_score_parts(PieceCall call) {
         if (int rc = piece_check(call, facts)) return rc;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         if (int rc = piece_tiles(call, facts, tiles)) return rc;
+        if (int rc = piece_check_loudness(call, facts)) return rc;
         if (int rc = piece_plans(call, facts, tiles, plans)) return rc;
         if (int rc = piece_buffers(call, facts, plans)) return rc;
         PieceBatches batches;  // (behind the plans and tiles: a batch whose vectors are still on their way waits for the stream as it goes)
@@ -755,6 +805,18 @@ int dusp_render_host_score_piece_meters(const dusp_score_part *parts, size_t n_p
     PieceCall call = piece_call("dusp_render_host_score_piece_meters", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, n_total_samples, tile_bytes, format, normalise,
                                 h_out, h_peaks);
     call.master = master, call.buses = buses, call.tracks = tracks, call.stems = stems, call.meters = meters;
+    return render_host_score_piece(call, placement);
+}
+
+// ... and with a loudness record: the true peak of every signal and channel the call delivers and, with deliver, PCM frames at a loudness
+// target under a true-peak ceiling (loudness NULL: dusp_render_host_score_piece_meters under this entry's name)
+int dusp_render_host_score_piece_loudness(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                          const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks, const dusp_score_buses *buses,
+                                          const dusp_score_master *master, const dusp_score_stems *stems, const dusp_score_meters *meters, const dusp_score_loudness *loudness,
+                                          size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks) {
+    PieceCall call = piece_call("dusp_render_host_score_piece_loudness", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, n_total_samples, tile_bytes, format, normalise,
+                                h_out, h_peaks);
+    call.master = master, call.buses = buses, call.tracks = tracks, call.stems = stems, call.meters = meters, call.loud = loudness;
     return render_host_score_piece(call, placement);
 }
 

@@ -19,8 +19,13 @@
  *   renderPieceMeters(the same thirty-one, stems, nBlocks)
  *         -> Promise<{ data, peaks, rms, lufs, momentary }>: the same, with stems or without, metering what it delivers
  *            (dusp_render_host_score_piece_meters)
+ *   renderPieceLoudness(the same thirty-three, deliver, targetLufs, ceilingDbtp)
+ *         -> Promise<{ data, peaks, rms, lufs, momentary, truePeak, gain, level }>: the same, with the true peak of every signal and channel
+ *            and — deliver true — the frames encoded at the loudness target (dusp_render_host_score_piece_loudness)
  *   meter(ctx, Float32Array planar, nSignals, nChannels, nSamples, sampleRate) -> { rms, lufs, momentary }: the meters of signals in host
  *         memory (dusp_meter_host)
+ *   truePeak(ctx, Float32Array planar, nSignals, nChannels, nSamples, sampleRate) -> Float64Array [nSignals * nChannels]: the true peaks
+ *         of signals in host memory, linear (dusp_true_peak_host)
  *   descriptorChannels(Float64Array words) -> the circuit's output channels (host code only: no context)
  *   programDestroy(prog), ctxDestroy(ctx), version(), abiVersion()
  * Failures surface the way the reference's do: synchronous calls THROW A STRING, render() REJECTS
@@ -792,6 +797,9 @@ typedef struct {
     int with_meters, stems_asked; /* renderPieceMeters (dusp_render_host_score_piece_meters): the result is boxed as with stems, of one signal where stems_asked is 0; */
     size_t n_blocks, n_channels;  /* ... what the caller says the timeline's blocks are (the library checks), the timeline's channels, */
     double *m_rms, *m_lufs, *m_momentary; /* ... and the meters: [n_signals][n_channels], [n_signals], [n_signals][n_blocks] */
+    int with_loud, deliver;       /* renderPieceLoudness (dusp_render_host_score_piece_loudness): renderPieceMeters with the true peaks, and with deliver at the target */
+    double target, ceiling, *m_tp, l_gain; /* ... the target in LUFS and the ceiling in dBTP, the true peaks [n_signals][n_channels], the gain */
+    float l_level;                /* ... and the level it came from */
     int format, normalise, rc;
     char err[512];
 } piece_job;
@@ -831,6 +839,7 @@ static void piece_free(napi_env env, piece_job *j) {
     free(j->tap_gains);
     free(j->out);
     free(j->m_rms);
+    free(j->m_tp);
     free(j->m_lufs);
     free(j->m_momentary);
     free(j);
@@ -882,7 +891,12 @@ static void piece_execute(napi_env env, void *data) {
             dusp_score_tracks tracks = {j->n_tracks, j->track_of, j->n_tprogs, served, j->faders, j->track_sends};
             dusp_score_stems stems = {j->n_signals};
             dusp_score_meters meters = {j->n_signals, j->n_blocks, j->m_rms, j->m_lufs, j->m_momentary};
-            if (j->with_meters)
+            dusp_score_loudness loud = {j->deliver, j->target, j->ceiling, j->m_tp, &j->l_gain, &j->l_level};
+            if (j->with_loud)
+                j->rc = dusp_render_host_score_piece_loudness(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, j->with_tracks ? &tracks : NULL,
+                                                              j->n_buses ? &buses : NULL, j->master_pb ? &master : NULL, j->stems_asked ? &stems : NULL, &meters, &loud, j->n_total,
+                                                              j->tile_bytes, j->format, j->normalise, j->out, j->peaks);
+            else if (j->with_meters)
                 j->rc = dusp_render_host_score_piece_meters(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, j->with_tracks ? &tracks : NULL,
                                                             j->n_buses ? &buses : NULL, j->master_pb ? &master : NULL, j->stems_asked ? &stems : NULL, &meters, j->n_total, j->tile_bytes,
                                                             j->format, j->normalise, j->out, j->peaks);
@@ -962,6 +976,16 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
                     if (ok && counts[m]) memcpy(mem, from[m], counts[m] * sizeof(double));
                 }
             }
+            if (j->with_loud && ok) { /* ... and truePeak: Float64Array; gain, level: numbers */
+                napi_value mab, arr, gain, level;
+                void *mem;
+                const size_t count = j->n_signals * j->n_channels;
+                ok = napi_create_arraybuffer(env, count * sizeof(double), &mem, &mab) == napi_ok && napi_create_typedarray(env, napi_float64_array, count, mab, 0, &arr) == napi_ok &&
+                     napi_set_named_property(env, result, "truePeak", arr) == napi_ok && napi_create_double(env, j->l_gain, &gain) == napi_ok &&
+                     napi_create_double(env, (double)j->l_level, &level) == napi_ok && napi_set_named_property(env, result, "gain", gain) == napi_ok &&
+                     napi_set_named_property(env, result, "level", level) == napi_ok;
+                if (ok && count) memcpy(mem, j->m_tp, count * sizeof(double));
+            }
         }
     } else if (j->rc == DUSP_OK && j->format) { /* { data: Buffer over the encoded frames, peaks: Float32Array(1) } */
         napi_value buf, peaks_ab, peaks;
@@ -1030,13 +1054,14 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *      1 + nTracks + nBuses + 1 signals one behind the other (a Float32Array of planar f32, or a Buffer of frames under ONE gain), the mix last, peaks a
  *      Float32Array of every signal's own peak */
 static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master, 6 ... and buses */
-    napi_value argv[33];
+    napi_value argv[36];
     char msg[256];
-    const int with_meters = form == 9; /* (renderPieceMeters: renderPieceStems' arguments, then whether the stems are asked for and the blocks of the timeline) */
+    const int with_loud = form == 10; /* (renderPieceLoudness: renderPieceMeters' arguments, then deliver, the target and the ceiling) */
+    const int with_meters = form == 9 || with_loud; /* (renderPieceMeters: renderPieceStems' arguments, then whether the stems are asked for and the blocks of the timeline) */
     const int with_stems = form == 8 || with_meters; /* (renderPieceStems: renderPieceTracks' arguments, the tracks among them or not) */
     int with_tracks = form == 7;
     if (with_tracks || with_stems) form = 6;
-    if (!get_args(env, info, with_meters ? 33 : with_tracks || with_stems ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    if (!get_args(env, info, with_loud ? 36 : with_meters ? 33 : with_tracks || with_stems ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
     if (with_stems) { /* (nTracks 0: a call without tracks) */
         double n_tracks = 0;
         with_tracks = napi_get_value_double(env, argv[24], &n_tracks) != napi_ok || n_tracks != 0;
@@ -1350,8 +1375,17 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         else
             j->stems_asked = asked, j->n_blocks = (size_t)n_blocks;
     }
+    j->with_loud = with_loud;
+    j->l_gain = 1.0, j->l_level = 1.0f;
+    if (with_loud) {
+        bool deliver = false;
+        if (napi_get_value_bool(env, argv[33], &deliver) != napi_ok || napi_get_value_double(env, argv[34], &j->target) != napi_ok || napi_get_value_double(env, argv[35], &j->ceiling) != napi_ok)
+            bad = bad ? bad : "deliver is a boolean, targetLufs and ceilingDbtp are numbers";
+        j->deliver = deliver ? 1 : 0;
+    }
     j->n_signals = j->stems_asked ? 1 + j->n_tracks + j->n_buses + 1 : 1;
     j->n_channels = (size_t)n_channels;
+    if (!bad && with_loud && !(j->m_tp = (double *)calloc(j->n_signals * j->n_channels + 1, sizeof(double)))) bad = "out of host memory for the true peaks";
     if (!bad && with_meters &&
         (!(j->m_rms = (double *)calloc(j->n_signals * j->n_channels + 1, sizeof(double))) || !(j->m_lufs = (double *)calloc(j->n_signals + 1, sizeof(double))) ||
          !(j->m_momentary = (double *)calloc(j->n_signals * j->n_blocks + 1, sizeof(double)))))
@@ -1416,6 +1450,7 @@ static napi_value fn_render_piece_buses(napi_env env, napi_callback_info info) {
 static napi_value fn_render_piece_tracks(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 7); }
 static napi_value fn_render_piece_stems(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 8); }
 static napi_value fn_render_piece_meters(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 9); }
+static napi_value fn_render_piece_loudness(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 10); }
 
 /* meter(ctx, planar, nSignals, nChannels, nSamples, sampleRate) -> { rms: Float64Array [nSignals * nChannels], lufs: Float64Array [nSignals],
  * momentary: Float64Array [nSignals * blocks] }: the meters of f32 signals in host memory, on the device, gated in the library
@@ -1463,6 +1498,42 @@ static napi_value fn_meter(napi_env env, napi_callback_info info) {
     return result;
 }
 
+/* truePeak(ctx, planar, nSignals, nChannels, nSamples, sampleRate) -> Float64Array [nSignals * nChannels]: the true peaks of f32 signals in
+ * host memory, on the device, linear (dusp_true_peak_host).  Throws the library's message. */
+static napi_value fn_true_peak(napi_env env, napi_callback_info info) {
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return NULL;
+    ctx_box *b = as_ctx(env, argv[0]);
+    if (!b) return NULL;
+    void *data, *mem;
+    size_t len;
+    double dims[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) napi_get_value_double(env, argv[2 + i], &dims[i]);
+    for (int i = 0; i < 4; i++)
+        if (!(dims[i] >= 1 && dims[i] <= 4294967295.0) || dims[i] != (double)(size_t)dims[i]) {
+            throw_string(env, "dusp-hip: truePeak: nSignals, nChannels, nSamples and sampleRate are whole numbers of at least 1");
+            return NULL;
+        }
+    const size_t n_signals = (size_t)dims[0], n_channels = (size_t)dims[1], n_samples = (size_t)dims[2];
+    if (!typed_array(env, argv[1], napi_float32_array, &data, &len) || (double)len != dims[0] * dims[1] * dims[2]) {
+        throw_string(env, "dusp-hip: truePeak: planar must be a Float32Array of nSignals * nChannels * nSamples values");
+        return NULL;
+    }
+    napi_value ab, result;
+    NAPI_OK(napi_create_arraybuffer(env, n_signals * n_channels * sizeof(double), &mem, &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_signals * n_channels, ab, 0, &result));
+    pthread_mutex_lock(&b->lock);
+    int rc = dusp_true_peak_host(b->ctx, (const float *)data, n_signals, n_channels, n_samples, (uint32_t)dims[3], (double *)mem);
+    char msg[512];
+    if (rc != DUSP_OK) snprintf(msg, sizeof msg, "dusp-hip: %s", dusp_last_error(b->ctx));
+    pthread_mutex_unlock(&b->lock);
+    if (rc != DUSP_OK) {
+        throw_string(env, msg);
+        return NULL;
+    }
+    return result;
+}
+
 /* descriptorChannels(words) -> the output channels of the descriptor's circuit (dusp_descriptor_channels: host code only, no context) */
 static napi_value fn_descriptor_channels(napi_env env, napi_callback_info info) {
     napi_value argv[1], out;
@@ -1497,7 +1568,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderPiece", fn_render_piece}, {"descriptorChannels", fn_descriptor_channels}, {"renderPiecePan", fn_render_piece_pan},
         {"renderPieceFrac", fn_render_piece_frac}, {"renderPieceSpace", fn_render_piece_space}, {"renderPieceStereo", fn_render_piece_stereo}, {"renderPieceMaster", fn_render_piece_master},
         {"renderPieceBuses", fn_render_piece_buses}, {"renderPieceTracks", fn_render_piece_tracks}, {"renderPieceStems", fn_render_piece_stems},
-        {"renderPieceMeters", fn_render_piece_meters}, {"meter", fn_meter},
+        {"renderPieceMeters", fn_render_piece_meters}, {"meter", fn_meter}, {"renderPieceLoudness", fn_render_piece_loudness}, {"truePeak", fn_true_peak},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -29,6 +29,7 @@ module.exports = {
   trackPrograms: renderChannelData.trackPrograms,
   stemNames: renderChannelData.stemNames,
   meter: renderChannelData.meter,
+  truePeak: renderChannelData.truePeak,
   meterBlocks: renderChannelData.meterBlocks,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,

@@ -457,11 +457,12 @@ function wholeSamples(who, name, values, count) {
  * master: as renderPiece's — the mix through a mono circuit, channel by channel, on the device — through the piece's call too.
  * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too.
  * stems: true — as renderPiece's: the direct mix, every track and every bus return beside the mix — through the piece's call too.
- * meters: true — as renderPiece's: the RMS and the BS.1770 loudness of every signal the call delivers — through the piece's call too. */
+ * meters: true — as renderPiece's: the RMS and the BS.1770 loudness of every signal the call delivers — through the piece's call too.
+ * truePeak: true, and on the Pcm / Wav forms loudness, truePeakMax — as renderPiece's — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
 const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends) ||
   given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends) || (opts.stems !== undefined && opts.stems !== false) ||
-  (opts.meters !== undefined && opts.meters !== false)
+  (opts.meters !== undefined && opts.meters !== false) || (opts.truePeak !== undefined && opts.truePeak !== false) || given(opts.loudness)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -483,12 +484,12 @@ async function renderScorePcm(outlets, opts = {}) {
   const { duration = 1, bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderScorePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderScorePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result, names, metered } = asPiece(opts)
+  const { nChannels, sampleRate, result, names, metered, loud } = asPiece(opts)
     ? await pieceCall('renderScorePcm', outlets, scoreAsPiece(opts), PCM_FORMAT[bitDepth], normalise, true)
     : await mixCall('renderScorePcm', outlets, duration, opts, PCM_FORMAT[bitDepth], normalise, true)
-  if (names) return withMeters(pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise), metered)
-  if (!result) return withMeters({ data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }, metered)
-  return withMeters({ data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }, metered)
+  if (names) return withMeters(pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise), metered, loud)
+  if (!result) return withMeters({ data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }, metered, loud)
+  return withMeters({ data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }, metered, loud)
 }
 
 async function renderScoreWav(outlets, opts = {}) {
@@ -891,11 +892,11 @@ function pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise) {
 }
 /* PCM -> a WAV file; the stems of a call -> a file a signal */
 function wavOf(pcm) {
-  if (pcm.meters && !pcm.names) return { mix: encodeWav(pcm.mix), meters: pcm.meters } // (meters without stems)
+  if (pcm.meters && !pcm.names) return Object.assign({ mix: encodeWav(pcm.mix), meters: pcm.meters }, pcm.level === undefined ? {} : { gain: pcm.gain, level: pcm.level }) // (meters without stems)
   if (pcm.meters) return Object.assign(wavOf(Object.assign({}, pcm, { meters: undefined })), { meters: pcm.meters })
   if (!pcm.names) return encodeWav(pcm)
   const files = pcm.names.map((name, s) => encodeWav(s === 0 ? pcm.direct : s === pcm.names.length - 1 ? pcm.mix : s <= pcm.tracks.length ? pcm.tracks[s - 1] : pcm.buses[s - 1 - pcm.tracks.length]))
-  return stemsOf(pcm.names, files, pcm.names.map((name) => pcm.peaks[name]), { gain: pcm.gain })
+  return stemsOf(pcm.names, files, pcm.names.map((name) => pcm.peaks[name]), Object.assign({ gain: pcm.gain }, pcm.level === undefined ? {} : { level: pcm.level }))
 }
 
 /* Meters (DESIGN.md 6.18): the refusals, the hop and the block count, in the words of mix.py (METERS_NOT_BOOL, METER_RATE_LOW, meter_hop,
@@ -907,6 +908,30 @@ function checkMeters(meters) {
   if (typeof meters !== 'boolean') throw METERS_NOT_BOOL
   return meters
 }
+/* Loudness delivery (DESIGN.md 6.19): the refusals in the words of mix.py (TRUE_PEAK_NOT_BOOL, LOUDNESS_NOT_NUMBER, TRUE_PEAK_MAX_BAD,
+ * LOUDNESS_WITH_NORMALISE, LOUDNESS_PLANAR; check_true_peak, check_loudness) */
+const TRUE_PEAK_NOT_BOOL = 'dusp-hip: true_peak is True or False: with True a call also delivers the true peak of every signal and channel it delivers'
+const LOUDNESS = {
+  notNumber: 'dusp-hip: loudness is None or a finite number, the target in LUFS (-14, -16, -23 ...): the frames are then encoded at that loudness',
+  ceiling: 'dusp-hip: true_peak_max is a finite number of dBTP at most 0 (default -1), the ceiling no delivered signal\'s true peak exceeds',
+  withNormalise: (normalise) => 'dusp-hip: loudness and normalise=' + normalise + ' do not go together: the target decides the gain, normalise must be 0',
+  planar: 'dusp-hip: loudness goes with the _pcm and _wav calls: 32-bit frames via bit_depth=32 are the f32 delivery at a target'
+}
+function checkTruePeak(truePeak) {
+  if (truePeak === undefined) return false
+  if (typeof truePeak !== 'boolean') throw TRUE_PEAK_NOT_BOOL
+  return truePeak
+}
+/* loudness:, truePeakMax: of a call -> { target (null: none), ceiling }; pcm: whether the call delivers frames */
+function checkLoudness(loudness, truePeakMax, normalise, pcm) {
+  const ceiling = truePeakMax === undefined ? -1 : truePeakMax
+  if (typeof ceiling !== 'number' || !Number.isFinite(ceiling) || ceiling > 0) throw LOUDNESS.ceiling
+  if (!given(loudness)) return { target: null, ceiling }
+  if (typeof loudness !== 'number' || !Number.isFinite(loudness)) throw LOUDNESS.notNumber
+  if (!pcm) throw LOUDNESS.planar
+  if (normalise !== 0) throw LOUDNESS.withNormalise(normalise)
+  return { target: loudness, ceiling }
+}
 const meterHop = (sampleRate) => Math.floor((sampleRate + 5) / 10)
 function meterBlocks(n, sampleRate) {
   const hop = meterHop(sampleRate), block = 4 * hop
@@ -916,10 +941,13 @@ function meterBlocks(n, sampleRate) {
  * (stemNames with stems, else ['mix']); rms, name -> Float64Array [channels]; lufs, name -> the gated integrated loudness of ITU-R
  * BS.1770-4 (-Infinity: no block above the gates, NaN: a sample that is not finite); momentary, name -> Float64Array [blocks], the
  * loudness of every 400 ms block, 100 ms apart; hop and block in samples.  Taken on the f32 signals in front of the PCM gain: the
- * loudness of an encoded file is lufs + 20 log10(gain).  got (the addon's doubles; null: a timeline of no samples, no energy, no block). */
-function metersOf(names, got, nChannels, nBlocks, sampleRate) {
+ * loudness of an encoded file is lufs + 20 log10(gain).  got (the addon's doubles; null: a timeline of no samples, no energy, no block).
+ * truePeak (a call with truePeak: true or loudness:): also truePeak, name -> Float64Array [channels], linear: dBTP is 20 log10. */
+function metersOf(names, got, nChannels, nBlocks, sampleRate, truePeak = false) {
   const out = { names, rms: {}, lufs: {}, momentary: {}, hop: meterHop(sampleRate), block: 4 * meterHop(sampleRate) }
+  if (truePeak) out.truePeak = {}
   names.forEach((name, s) => {
+    if (truePeak) out.truePeak[name] = got ? got.truePeak.slice(s * nChannels, (s + 1) * nChannels) : new Float64Array(nChannels)
     out.rms[name] = got ? got.rms.slice(s * nChannels, (s + 1) * nChannels) : new Float64Array(nChannels)
     out.lufs[name] = got ? got.lufs[s] : -Infinity
     out.momentary[name] = got ? got.momentary.slice(s * nBlocks, (s + 1) * nBlocks) : new Float64Array(0)
@@ -927,9 +955,10 @@ function metersOf(names, got, nChannels, nBlocks, sampleRate) {
   return out
 }
 /* what a call resolves to, with its meters where it has some: the stems gain `.meters`; without stems { mix, meters } (twin of render.py Metered) */
-function withMeters(delivered, metered) {
+function withMeters(delivered, metered, loud = null) {
   if (!metered) return delivered
-  return delivered && delivered.names ? Object.assign(delivered, { meters: metered }) : { mix: delivered, meters: metered }
+  const out = delivered && delivered.names ? Object.assign(delivered, { meters: metered }) : { mix: delivered, meters: metered }
+  return loud ? Object.assign(out, loud) : out // (a call with loudness: the one gain the frames were encoded under, and the level it came from)
 }
 /* The meters of any signals a user has (twin of render.py meter): channelData — an array of Float32Arrays, the channels of one signal, or
  * an array of such arrays, several signals of the same shape — at sampleRate -> what metersOf makes, the names '0', '1', ...; metered on
@@ -946,6 +975,20 @@ function meter(channelData, sampleRate) {
   signals.forEach((sig, s) => Array.from(sig).forEach((ch, c) => planar.set(ch, (s * nChannels + c) * nSamples)))
   const got = native().meter(contextFor(sampleRate), planar, signals.length, nChannels, nSamples, sampleRate)
   return metersOf(names, got, nChannels, meterBlocks(nSamples, sampleRate), sampleRate)
+}
+/* The true peak of any signals a user has (twin of render.py true_peak): channelData as meter takes it -> an array, one Float64Array
+ * [channels] a signal, linear; taken on the device (dusp_true_peak_host). */
+function truePeak(channelData, sampleRate) {
+  const signals = channelData.length && !ArrayBuffer.isView(channelData[0]) ? Array.from(channelData) : [channelData]
+  const nChannels = signals[0].length, nSamples = nChannels ? signals[0][0].length : 0
+  if (!(sampleRate > 0)) throw 'dusp-hip: truePeak: the true peak needs a sample rate: it decides the oversampling'
+  if (!nChannels || signals.some((sig) => sig.length !== nChannels || Array.from(sig).some((ch) => !(ch instanceof Float32Array) || ch.length !== nSamples)))
+    throw 'dusp-hip: truePeak: the signals are Float32Arrays of one length, the same number a signal'
+  if (nSamples === 0) return signals.map(() => new Float64Array(nChannels))
+  const planar = new Float32Array(signals.length * nChannels * nSamples)
+  signals.forEach((sig, s) => Array.from(sig).forEach((ch, c) => planar.set(ch, (s * nChannels + c) * nSamples)))
+  const got = native().truePeak(contextFor(sampleRate), planar, signals.length, nChannels, nSamples, sampleRate)
+  return signals.map((sig, s) => got.slice(s * nChannels, (s + 1) * nChannels))
 }
 
 /* what sends and tracks do not go with, refused before anything else of a call is looked at (twin of render.py _placing) */
@@ -972,7 +1015,10 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   const { gains, engine = 0, tileBytes = 0, duration = 1, voiceDurations = 1 } = opts
   const stereo = opts.stereo === true
   const stems = checkStems(opts.stems) // (what is no boolean is refused first)
-  const meters = checkMeters(opts.meters) // (... and next to it)
+  const metersAsked = checkMeters(opts.meters) // (... and next to it)
+  const truePeakAsked = checkTruePeak(opts.truePeak) // (... and next to that)
+  const loud = checkLoudness(opts.loudness, opts.truePeakMax, normalise, format !== 0) // (... then what the loudness target does not go with)
+  const truePeaks = truePeakAsked || loud.target !== null, meters = metersAsked || truePeaks // (a target implies true peaks, true peaks imply meters)
   refuseSends(opts)
   if (given(opts.places) && stereo) throw STEREO_NO_PLACES
   if (given(opts.places) && (given(opts.pans) || given(opts.fracs))) throw SPACE_ALONE
@@ -1026,7 +1072,8 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   const names = stems ? stemNames(routed ? opts.tracks.length : 0, buses ? buses.length : 0) : null
   if (meters && !(sampleRate >= 8000)) throw METER_RATE_LOW(sampleRate)
   const nBlocks = meterBlocks(nSamples, sampleRate)
-  if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null, names, metered: meters ? metersOf(names || ['mix'], null, nChannels, 0, sampleRate) : null }
+  const delivered = loud.target !== null ? (got) => ({ gain: got ? got.gain : 1, level: got ? got.level : 1 }) : () => null
+  if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null, names, metered: meters ? metersOf(names || ['mix'], null, nChannels, 0, sampleRate, truePeaks) : null, loud: delivered(null) }
   const progs = [], busProgs = [], trackProgs = []
   let masterProg = null
   try {
@@ -1036,11 +1083,11 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
     if (groups) for (const group of groups) trackProgs.push(n.programBuild(contextFor(sampleRate), group.uni.words, engine))
-    const result = meters ? await n.renderPieceMeters(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+    const result = meters ? await (truePeaks ? n.renderPieceLoudness : n.renderPieceMeters)(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
       routed ? trackProgs : null, routed ? groups.map((group) => Uint32Array.from(group.tracks)) : null, routed ? groups.map((group) => (group.uni.nParams ? group.uni.params : null)) : null,
-      routed ? routed.faders : null, routed ? routed.trackSends : null, stems, nBlocks)
+      routed ? routed.faders : null, routed ? routed.trackSends : null, stems, nBlocks, ...(truePeaks ? [loud.target !== null, loud.target === null ? 0 : loud.target, loud.ceiling] : []))
       : stems ? await n.renderPieceStems(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
@@ -1060,7 +1107,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
       : panned ? await n.renderPiecePan(...args, panned.pans, panned.comp) : await n.renderPiece(...args)
     if (!meters) return { nSamples, nChannels, sampleRate, result, names }
     // (one addon call: { data, peaks, rms, lufs, momentary }; without stems what is delivered is the call's without meters)
-    return { nSamples, nChannels, sampleRate, result: stems || format ? result : result.data, names, metered: metersOf(names || ['mix'], result, nChannels, nBlocks, sampleRate) }
+    return { nSamples, nChannels, sampleRate, result: stems || format ? result : result.data, names, metered: metersOf(names || ['mix'], result, nChannels, nBlocks, sampleRate, truePeaks), loud: delivered(result) }
   } finally {
     for (const prog of progs) n.programDestroy(prog)
     if (masterProg) n.programDestroy(masterProg)
@@ -1121,7 +1168,13 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
  * DESIGN.md 6.18; metersOf says what `meters` holds): the RMS a channel, the gated integrated loudness in LUFS (ITU-R BS.1770-4) and the
  * momentary loudness of every 400 ms block, of the mix and — with stems — of every stem.  With stems the result gains `.meters`; without,
  * the call resolves to { mix, meters }, mix what it resolves to without meters bit for bit.  One addon call.  What is no boolean is
- * refused, next to stems. */
+ * refused, next to stems.
+ * truePeak: true (implies meters) — `meters.truePeak`, name -> Float64Array [channels]: the true peak of every channel of every delivered
+ * signal, oversampled on the device (dusp_render_host_score_piece_loudness; DESIGN.md 6.19), linear: dBTP is 20 log10.
+ * loudness, truePeakMax (renderPiecePcm and renderPieceWav; here loudness is refused): the target in LUFS and the ceiling in dBTP
+ * (default -1): the frames of every signal are encoded under ONE gain that brings the mix to the target, lowered where the largest true
+ * peak of any signal would exceed the ceiling.  The result gains `gain` and `level`; every `peak` stays the sample peak.  Not together
+ * with normalise != 0. */
 async function renderPiece(outlets, opts = {}) {
   const { nSamples, nChannels, sampleRate, result, names, metered } = await pieceCall('renderPiece', outlets, opts, 0, 0)
   if (names) return withMeters(planarStems(names, nSamples, nChannels, sampleRate, result), metered)
@@ -1135,10 +1188,10 @@ async function renderPiecePcm(outlets, opts = {}) {
   const { bitDepth = 16, normalise = 0 } = opts
   if (bitDepth !== 16 && bitDepth !== 24 && bitDepth !== 32) throw 'dusp-hip: renderPiecePcm: bitDepth must be 16, 24 or 32'
   if (normalise !== 0 && normalise !== 1 && normalise !== 2) throw 'dusp-hip: renderPiecePcm: normalise must be 0 (none), 1 (shrink only what clips) or 2 (to full scale)'
-  const { nChannels, sampleRate, result, names, metered } = await pieceCall('renderPiecePcm', outlets, opts, PCM_FORMAT[bitDepth], normalise)
-  if (names) return withMeters(pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise), metered)
-  if (!result) return withMeters({ data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }, metered)
-  return withMeters({ data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }, metered)
+  const { nChannels, sampleRate, result, names, metered, loud } = await pieceCall('renderPiecePcm', outlets, opts, PCM_FORMAT[bitDepth], normalise)
+  if (names) return withMeters(pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise), metered, loud)
+  if (!result) return withMeters({ data: Buffer.alloc(0), bitDepth, numberOfChannels: 0, sampleRate, peak: 0 }, metered, loud)
+  return withMeters({ data: result.data, bitDepth, numberOfChannels: nChannels, sampleRate, peak: result.peaks[0] }, metered, loud)
 }
 
 async function renderPieceWav(outlets, opts = {}) {
@@ -1208,6 +1261,9 @@ module.exports.METER_RATE_LOW = METER_RATE_LOW
 module.exports.meterHop = meterHop
 module.exports.meterBlocks = meterBlocks
 module.exports.meter = meter
+module.exports.truePeak = truePeak
+module.exports.TRUE_PEAK_NOT_BOOL = TRUE_PEAK_NOT_BOOL
+module.exports.LOUDNESS = LOUDNESS
 module.exports.instanceRange = instanceRange
 module.exports.deviceCount = () => native().deviceCount()
 module.exports.SegmentRenderer = SegmentRenderer

@@ -1090,3 +1090,119 @@ def meters(signals, sample_rate):
     for s in range(S):
         momentary[s], lufs[s] = loudness(energies[s])
     return dict(rms=rms, energies=energies, momentary=momentary, lufs=lufs, hop=hop, block=block)
+
+
+# ---- loudness delivery: the true peak, and the one gain of a delivery at a loudness target ----
+
+TRUE_PEAK_NOT_BOOL = "dusp-hip: true_peak is True or False: with True a call also delivers the true peak of every signal and channel it delivers"
+LOUDNESS_NOT_NUMBER = "dusp-hip: loudness is None or a finite number, the target in LUFS (-14, -16, -23 ...): the frames are then encoded at that loudness"
+TRUE_PEAK_MAX_BAD = "dusp-hip: true_peak_max is a finite number of dBTP at most 0 (default -1), the ceiling no delivered signal's true peak exceeds"
+LOUDNESS_WITH_NORMALISE = "dusp-hip: loudness and normalise=%d do not go together: the target decides the gain, normalise must be 0"
+LOUDNESS_PLANAR = "dusp-hip: loudness goes with the _pcm and _wav calls: 32-bit frames via bit_depth=32 are the f32 delivery at a target"
+TRUE_PEAK_TAPS = 49
+
+
+def check_true_peak(true_peak):
+    """`true_peak=` of a score or piece call -> bool; what is no bool is refused by string, as meters= is"""
+    if not isinstance(true_peak, (bool, np.bool_)):
+        raise ValueError(TRUE_PEAK_NOT_BOOL)
+    return bool(true_peak)
+
+
+def check_loudness(loudness, true_peak_max=-1.0, normalise=0, pcm=True):
+    """`loudness=` and `true_peak_max=` of a _pcm or _wav call -> (target in LUFS or None, ceiling in dBTP), floats.  Refused by string:
+    a loudness that is no finite number, a ceiling that is not finite or above 0, loudness together with normalise != 0, and loudness
+    on a call that delivers planar f32 (pcm False)"""
+    def number(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and np.isfinite(v)
+    if not number(true_peak_max) or true_peak_max > 0:
+        raise ValueError(TRUE_PEAK_MAX_BAD)
+    if loudness is None:
+        return None, float(true_peak_max)
+    if not number(loudness):
+        raise ValueError(LOUDNESS_NOT_NUMBER)
+    if not pcm:
+        raise ValueError(LOUDNESS_PLANAR)
+    if normalise != 0:
+        raise ValueError(LOUDNESS_WITH_NORMALISE % normalise)
+    return float(loudness), float(true_peak_max)
+
+
+def true_peak_taps(sample_rate):
+    """The interpolator of the true peak at a sample rate -> (F, h): F = 4 below 96 kHz, 2 below 192 kHz, else 1 — then h = [1.0] and
+    the true peak is the sample peak.  F > 1: the windowed sinc libebur128 interpolates with, re-derived here: 49 taps, m = j - 24,
+    h[j] = sin(m pi / F) / (m pi / F) — 1 at m = 0, exactly 0 where F divides m — times the Hann window 0.5 (1 - cos(2 pi j / 48)), in
+    f64.  Phase p owns h[p::F]: K = ceil(49 / F) taps (13 or 25), a shorter phase padded with a zero tap (dusp_true_peak_taps)."""
+    import math
+    if not sample_rate > 0:
+        raise ValueError("dusp-hip: the true peak needs a sample rate, not %r: it decides the oversampling" % (sample_rate,))
+    F = 4 if sample_rate < 96000 else 2 if sample_rate < 192000 else 1
+    if F == 1:
+        return 1, np.array([1.0])
+    h = np.zeros(TRUE_PEAK_TAPS)
+    for j in range(TRUE_PEAK_TAPS):
+        m = j - 24
+        v = 1.0 if m == 0 else 0.0 if m % F == 0 else math.sin(m * math.pi / F) / (m * math.pi / F)
+        h[j] = v * (0.5 * (1.0 - math.cos(2.0 * math.pi * j / 48.0)))
+    return F, h
+
+
+def true_peak(signals, sample_rate, taps=None):
+    """The true peak of a delivery: the contract of dusp_true_peak_host and of true_peak=True, in f64 throughout, needs no GPU.
+    signals float32 [S, C, n] -> float64 [S, C], LINEAR (dBTP is 20 log10).  taps: (F, h) as true_peak_taps makes them (None: its own).
+
+    Per row, x zero outside [0, n): for u in [0, n + K - 1) and every phase p in [0, F), acc = 0.0, then acc = acc + h[p + F k] *
+    f64(x[u - k]) for k = 0 .. K - 1 in that order — every product and every sum rounded by itself, no fma, a padded phase's zero tap
+    multiplied like the rest.  The peak is the largest |acc| over every u and p, the filter's tail behind the last sample included;
+    NaN as soon as any acc is not finite; 0 for n = 0."""
+    signals = np.asarray(signals, dtype=np.float32)
+    if signals.ndim != 3:
+        raise ValueError("dusp-hip: the signals to take the true peak of are float32 of shape (signals, channels, samples)")
+    F, h = true_peak_taps(sample_rate) if taps is None else (int(taps[0]), np.asarray(taps[1], dtype=np.float64))
+    K = -(-len(h) // F)
+    phases = np.zeros((F, K))
+    for p in range(F):
+        own = h[p::F]
+        phases[p, :len(own)] = own
+    S, C, n = signals.shape
+    if n == 0:
+        return np.zeros((S, C))
+    x = np.zeros((S * C, n + 2 * (K - 1)))
+    x[:, K - 1:K - 1 + n] = signals.reshape(S * C, n).astype(np.float64)
+    n_out = n + K - 1
+    largest, finite = np.zeros(S * C), np.ones(S * C, dtype=bool)
+    with np.errstate(all="ignore"):
+        for p in range(F):
+            acc = np.zeros((S * C, n_out))
+            for k in range(K):
+                acc = acc + phases[p, k] * x[:, K - 1 - k:K - 1 - k + n_out]  # (x[u - k]; a product and a sum, each rounded by itself)
+            finite &= np.all(np.isfinite(acc), axis=1)
+            largest = np.maximum(largest, np.max(np.abs(np.where(np.isfinite(acc), acc, 0.0)), axis=1))
+    return np.where(finite, largest, np.nan).reshape(S, C)
+
+
+def loudness_gain(lufs, true_peaks, target_lufs, ceiling_dbtp):
+    """The one gain of a delivery at a loudness target under a true-peak ceiling -> (gain, level): with tp the largest of true_peaks (a
+    NaN wins), G = min(10^((target - lufs) / 20), 10^(ceiling / 20) / tp); level = float32(1 / G), the sample magnitude that is
+    brought to full scale — what the encoders read as the peak under NORMALISE_FULL — and gain = 1.0 / float64(level), what they
+    apply.  Unity, (1.0, float32(1.0)): lufs -inf or NaN; tp 0, NaN or Inf; a level that comes out zero, subnormal or not finite.
+    Unity leaves the samples as they are, as pcm_gain leaves an instance whose peak is NaN.  (truepeak_plan.hpp true_peak_loudness_gain.)"""
+    import math
+    unity = (1.0, np.float32(1.0))
+    tps = np.asarray(true_peaks, dtype=np.float64).ravel()
+    lufs = float(lufs)
+    if math.isnan(lufs) or lufs == -math.inf or tps.size == 0:
+        return unity
+    tp = float("nan") if np.any(np.isnan(tps)) else float(np.max(tps))
+    if not tp > 0.0 or not math.isfinite(tp):
+        return unity
+    with np.errstate(all="ignore"):
+        try:
+            by_loudness = math.pow(10.0, (float(target_lufs) - lufs) / 20.0)
+        except OverflowError:
+            by_loudness = math.inf
+        G = min(by_loudness, math.pow(10.0, float(ceiling_dbtp) / 20.0) / tp)
+        level = np.float32(np.float64(1.0) / np.float64(G))
+    if not np.isfinite(level) or level < np.finfo(np.float32).tiny:
+        return unity
+    return 1.0 / float(np.float64(level)), level

@@ -181,7 +181,7 @@ def _wav(pcm, bit_depth):
     if isinstance(pcm, Stems):
         return pcm.each(lambda one: _wav(one, bit_depth))
     if isinstance(pcm, Metered):
-        return Metered(_wav(pcm.mix, bit_depth), pcm.meters)
+        return Metered(_wav(pcm.mix, bit_depth), pcm.meters, getattr(pcm, "gain", None), getattr(pcm, "level", None))
     if bit_depth == 32:
         return wav.encode_wav(pcm.data, pcm.sampleRate, 32, frames=True)
     return wav.encode_wav(pcm.data, pcm.sampleRate, bit_depth)
@@ -210,7 +210,8 @@ class Stems:
     order they were delivered (mix.stem_names: direct, track0 .., bus0 .., mix); `mix`, exactly what the call returns without stems;
     `direct`, `tracks` (a list, one a track) and `buses` (a list, one a bus), each of the mix's type — ChannelData, PcmData, or the
     bytes of a WAV file; `peaks`, name -> numpy.float32, every signal's own max |x| over all its channels; `peak`, the largest of them
-    (wav.common_peak); and for PCM `gain`, the one gain all the frames were encoded under (wav.gain(peak, normalise))."""
+    (wav.common_peak); and for PCM `gain`, the one gain all the frames were encoded under (wav.gain(peak, normalise)) — with loudness=
+    the gain of mix.loudness_gain, and `level` beside it."""
 
     def __init__(self, names, signals, peaks, gain=None):
         self.names, self._signals = list(names), list(signals)
@@ -227,8 +228,9 @@ class Stems:
     def each(self, make):
         """the same Stems with make(signal) for every signal"""
         made = Stems(self.names, [make(one) for one in self._signals], [self.peaks[name] for name in self.names], getattr(self, "gain", None))
-        if hasattr(self, "meters"):
-            made.meters = self.meters
+        for extra in ("meters", "level"):
+            if hasattr(self, extra):
+                setattr(made, extra, getattr(self, extra))
         return made
 
 
@@ -237,7 +239,8 @@ class Meters:
     gain: `names`, the signals in the order they were delivered (mix.stem_names with stems, else ["mix"]); `rms`, name -> float64
     [channels]; `lufs`, name -> float, the gated integrated loudness of ITU-R BS.1770-4 (-inf: no block above the gates, NaN: a sample
     that is not finite); `momentary`, name -> float64 [n_blocks], the loudness of every 400 ms block, 100 ms apart; `hop` and `block`
-    in samples.  The loudness of an encoded file is lufs + 20 log10(gain)."""
+    in samples.  The loudness of an encoded file is lufs + 20 log10(gain).  With true_peak=True (or loudness=): `true_peak`, name ->
+    float64 [channels], the true peak of every channel (mix.true_peak is the contract), LINEAR: dBTP is 20 log10."""
 
     def __init__(self, names, got):
         self.names = list(names)
@@ -245,14 +248,19 @@ class Meters:
         self.lufs = {name: float(got["lufs"][k]) for k, name in enumerate(self.names)}
         self.momentary = {name: np.array(got["momentary"][k], dtype=np.float64) for k, name in enumerate(self.names)}
         self.hop, self.block = int(got["hop"]), int(got["block"])
+        if "true_peak" in got:
+            self.true_peak = {name: np.array(got["true_peak"][k], dtype=np.float64) for k, name in enumerate(self.names)}
 
 
 class Metered:
     """What a score or piece call with meters=True and without stems hands back: `mix`, exactly what the call returns without meters,
-    and `meters`, a Meters of the one signal "mix"."""
+    and `meters`, a Meters of the one signal "mix".  A call with loudness= adds `gain`, the gain the frames were encoded under, and
+    `level`, the numpy.float32 sample magnitude that was brought to full scale (mix.loudness_gain); `mix.peak` stays the sample peak."""
 
-    def __init__(self, mix_, meters):
+    def __init__(self, mix_, meters, gain=None, level=None):
         self.mix, self.meters = mix_, meters
+        if gain is not None:
+            self.gain, self.level = gain, level
 
 
 def _empty_meters(n_signals, channels, sample_rate):
@@ -268,6 +276,12 @@ def meter(planar, sample_rate, device=-1):
     Meters whose names are "0", "1", ..., metered on the device and gated in the library (Context.meter; mix.meters is the contract)."""
     got = context(sample_rate, device).meter(planar, sample_rate)
     return Meters([str(k) for k in range(len(got["lufs"]))], got)
+
+
+def true_peak(planar, sample_rate, device=-1):
+    """The true peak of any signals a user has: planar float32 [signals, channels, samples] (or [channels, samples]: one signal) ->
+    float64 [signals, channels], linear (dBTP is 20 log10), taken on the device (Context.true_peak; mix.true_peak is the contract)."""
+    return context(sample_rate, device).true_peak(planar, sample_rate)
 
 
 def _delivered_stems(pcm, sample_rate, n, channels, names, run):
@@ -341,7 +355,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -368,14 +382,17 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     the mix; the piece's call with the score as its one part, as with pans.
 
     stems=True: as render_piece's — the direct mix, every track and every bus return beside the mix, as a Stems; the piece's call with
-    the score as its one part, as with a master."""
+    the score as its one part, as with a master.
+
+    meters=True, true_peak=True: as render_piece's — the RMS, the loudness and the true peak of every signal the call delivers; the
+    piece's call too.  loudness belongs to render_score_pcm and render_score_wav and is refused here."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness))
 
 
 def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if placing["stereo"] or placing["stems"] or placing["meters"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
+    if placing["stereo"] or placing["stems"] or placing["meters"] or placing["true_peak"] or placing["loudness"] is not None or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
         return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
@@ -388,17 +405,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), (bit_depth, normalise))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max), bit_depth)
 
 
 class PieceParts:
@@ -442,7 +459,7 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0):
     """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
     known.  The Space keywords are one thing too, None without places (the other three alone say nothing).  master: what the mix goes
     through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it;
@@ -451,8 +468,10 @@ def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per
     voices go through, which travel with it as well; with tracks the buses are fed by track_sends, whatever the placement, and what
     does not go with tracks is refused here too (mix.check_tracks holds the arrays once the voices are counted).  stems: whether the
     call delivers its stems beside the mix, which travels with it too; what is no bool is refused here, first.  meters: whether
-    the call also meters what it delivers, which travels with it as stems does and is refused next to it"""
-    stems, meters = mix.check_stems(stems), mix.check_meters(meters)
+    the call also meters what it delivers, which travels with it as stems does and is refused next to it.  true_peak: whether it also
+    takes the true peaks, refused next to meters; loudness, true_peak_max: the target and ceiling of a delivery at a loudness target,
+    which travel with it as they are (_render_piece_voices holds them to mix.check_loudness once it knows what the call delivers)"""
+    stems, meters, true_peak = mix.check_stems(stems), mix.check_meters(meters), mix.check_true_peak(true_peak)
     if tracks is None:
         mix.check_tracks(0, None, track_of, faders, track_sends)
         if buses is None and sends is not None:
@@ -477,7 +496,8 @@ def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per
         if not isinstance(buses, (list, tuple)) or not 1 <= len(buses) <= mix.BUS_MAX:
             raise ValueError(mix.BUS_COUNT % (len(buses) if isinstance(buses, (list, tuple)) else 0))
     return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master,
-                buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters)
+                buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters, true_peak=true_peak, loudness=loudness,
+                true_peak_max=true_peak_max)
 
 
 def master_program(master, channels, sample_rate, bus=None):
@@ -557,6 +577,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     buses, sends = placing.pop("buses", None), placing.pop("sends", None)
     tracks, track_of, faders, track_sends = (placing.pop(k, None) for k in ("tracks", "track_of", "faders", "track_sends"))
     stems, meters = placing.pop("stems", False), placing.pop("meters", False)
+    true_peak, loudness, true_peak_max = placing.pop("true_peak", False), placing.pop("loudness", None), placing.pop("true_peak_max", -1.0)
     mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
@@ -582,6 +603,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     place.buses = place.sends = None  # (... and the buses, each a descriptor.Unified of one instance a channel, with the levels [buses, voices])
     place.stems = stems  # (... whether the call delivers its stems)
     place.meters = meters  # (... and whether it meters what it delivers)
+    place.true_peak, place.loudness, place.true_peak_max = true_peak, loudness, true_peak_max  # (... takes its true peaks, and delivers at a loudness target)
     place.tracks = None  # (... and the tracks: (how many, track_of, track_programs' groups, faders, levels [buses, tracks]))
     if tracks is not None:
         track_of, faders, track_sends = mix.check_tracks(n, len(tracks), track_of, faders, track_sends, 0 if buses is None else len(buses), sends)
@@ -614,14 +636,14 @@ def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, devic
             circuits = [(prog, which, uni.params) for prog, (uni, which) in zip(programs[len(programs) - len(groups):], groups)]
             tracks = dict(n_tracks=n_tracks, track_of=track_of, programs=circuits, faders=faders, track_sends=track_sends)
         return ctx.render_score_parts(parts, grouped.part_of, onsets, n_total, lengths, gains, tile_bytes, format, normalise, master=master, buses=buses,
-                                      sends=getattr(place, "sends", None), tracks=tracks, stems=getattr(place, "stems", False), **(dict(meters=True) if getattr(place, "meters", False) else {}), **place.keywords())
+                                      sends=getattr(place, "sends", None), tracks=tracks, stems=getattr(place, "stems", False), **(dict(meters=True) if getattr(place, "meters", False) else {}), **getattr(place, "loud", {}), **place.keywords())
     finally:
         for prog in programs:
             prog.close()
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -687,9 +709,19 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     meters=True: the call also meters what it delivers, on the device, in front of the PCM gain (mix.meters says exactly what;
     DESIGN.md 6.18): the RMS a channel, the gated integrated loudness in LUFS (ITU-R BS.1770-4) and the momentary loudness of every
     400 ms block, of the mix and — with stems — of every stem.  With stems the Stems gains `.meters`; without, the call returns a
-    Metered: `.mix`, what it returns without meters bit for bit, and `.meters`."""
+    Metered: `.mix`, what it returns without meters bit for bit, and `.meters`.
+
+    true_peak=True (implies meters): `.meters.true_peak` has the true peak of every channel of every delivered signal — the signal
+    oversampled four times (twice from 96 kHz, not at all from 192 kHz) by libebur128's windowed sinc, on the device (mix.true_peak;
+    DESIGN.md 6.19) — linear: dBTP is 20 log10.  Everything else is the call with meters=True bit for bit.
+
+    loudness (render_piece_pcm and render_piece_wav; here it is refused): the target in LUFS (-14, -16, -23 ...), with true_peak_max
+    the ceiling in dBTP (default -1).  The frames of the mix — and with stems of every stem — are encoded under ONE gain that brings
+    the MIX to the target, lowered where the largest true peak of any delivered signal would exceed the ceiling (mix.loudness_gain;
+    there is no limiter).  The result gains `.gain` and `.level`; every PcmData.peak stays the signal's sample peak.  Not together
+    with normalise != 0."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), _one_part)
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness), _one_part)
 
 
 def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
@@ -699,8 +731,14 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
     grouped, n_total, onsets, lengths, gains, channels, place = _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, one_part)
     run = lambda format, normalise: _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, device, tile_bytes, format, normalise)
     names = mix.stem_names(place.tracks[0] if place.tracks is not None else 0, len(place.buses) if place.buses is not None else 0) if place.stems else ["mix"]
-    if place.meters:  # (the run hands back what it does without meters, and the meters beside it)
+    loudness, ceiling = mix.check_loudness(place.loudness, place.true_peak_max, pcm[1] if pcm is not None else 0, pcm is not None)
+    place.loud = dict(true_peak=True, loudness=loudness, true_peak_max=ceiling) if place.true_peak or loudness is not None else {}
+    if place.meters or place.loud:  # (the run hands back what it does without meters, and the meters beside it)
         got = _empty_meters(len(names), channels, grouped.sample_rate)
+        if place.loud:  # (a timeline of no samples: true peaks 0, gain 1)
+            got["true_peak"] = np.zeros((len(names), channels))
+        if loudness is not None:
+            got["gain"], got["level"] = 1.0, np.float32(1.0)
         render = run
 
         def run(format, normalise):
@@ -711,8 +749,10 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
         delivered = (_delivered_stems(pcm, grouped.sample_rate, n_total, channels, names, run) if place.stems else
                      _delivered(pcm, grouped.sample_rate, n_total, channels, run))
         if not place.stems:
-            return Metered(delivered, Meters(names, got))
+            return Metered(delivered, Meters(names, got), got.get("gain"), got.get("level"))
         delivered.meters = Meters(names, got)
+        if loudness is not None:  # (the one gain all the frames were encoded under, and the level it came from)
+            delivered.gain, delivered.level = got["gain"], got["level"]
         return delivered
     if place.stems:
         return _delivered_stems(pcm, grouped.sample_rate, n_total, channels, names, run)
@@ -721,17 +761,17 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters), _one_part, (bit_depth, normalise))
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters, true_peak=true_peak, loudness=loudness, true_peak_max=true_peak_max), bit_depth)
 
 
 class PcmData:

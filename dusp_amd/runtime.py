@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import check_meters, check_stems, meter_blocks, meter_hop, METER_RATE_LOW, METER_RATE_MIN, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
+from .mix import check_loudness, check_meters, check_stems, check_true_peak, meter_blocks, meter_hop, METER_RATE_LOW, METER_RATE_MIN, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -38,6 +38,7 @@ EXPORTS = [
     "dusp_render_host_score_piece_tracks", "dusp_score_tracks_mix_device",
     "dusp_render_host_score_piece_stems", "dusp_score_stems_mix_device", "dusp_score_stems_return_device", "dusp_peak_common_device",
     "dusp_meter_blocks", "dusp_meter_device", "dusp_meter_last_ms", "dusp_meter_host", "dusp_render_host_score_piece_meters",
+    "dusp_true_peak_taps", "dusp_true_peak_tile", "dusp_true_peak_device", "dusp_true_peak_host", "dusp_render_host_score_piece_loudness",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -135,6 +136,12 @@ def load():
         L.dusp_meter_last_ms.argtypes = [vp, vp]
         L.dusp_meter_host.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, vp, vp, vp]
         L.dusp_render_host_score_piece_meters.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    if hasattr(L, "dusp_render_host_score_piece_loudness"):  # (detected by symbol, as the meters are)
+        L.dusp_true_peak_taps.argtypes = [ctypes.c_uint32, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
+        L.dusp_true_peak_tile.argtypes, L.dusp_true_peak_tile.restype = [vp, sz, sz, sz, ctypes.c_uint32], sz
+        L.dusp_true_peak_device.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, vp, vp]
+        L.dusp_true_peak_host.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, vp]
+        L.dusp_render_host_score_piece_loudness.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -196,6 +203,13 @@ class ScoreStems(ctypes.Structure):
 class ScoreMeters(ctypes.Structure):
     """dusp_score_meters: how many signals and blocks the caller has sized the three arrays for, and the arrays"""
     _fields_ = [("n_signals", ctypes.c_size_t), ("n_blocks", ctypes.c_size_t), ("h_rms", ctypes.c_void_p), ("h_lufs", ctypes.c_void_p), ("h_momentary", ctypes.c_void_p)]
+
+
+class ScoreLoudness(ctypes.Structure):
+    """dusp_score_loudness: whether the call encodes at a loudness target, the target and the true-peak ceiling, and where the true peaks
+    [signals][channels], the gain and the level go"""
+    _fields_ = [("deliver", ctypes.c_int), ("target_lufs", ctypes.c_double), ("ceiling_dbtp", ctypes.c_double), ("h_true_peak", ctypes.c_void_p), ("h_gain", ctypes.c_void_p),
+                ("h_level", ctypes.c_void_p)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -561,8 +575,35 @@ class Context:
             self._check(self._L.dusp_meter_host(self._h, planar.ctypes.data, S, C, n, int(sample_rate), rms.ctypes.data, lufs.ctypes.data, _ptr(momentary)))
         return dict(rms=rms, lufs=lufs, momentary=momentary, hop=meter_hop(sample_rate), block=4 * meter_hop(sample_rate))
 
+    def true_peak_device(self, d_planar, n_signals, n_channels, n_samples, sample_rate, d_words, stream=None):
+        """Device pointers: the true-peak kernel alone (dusp_true_peak_device; mix.true_peak is the contract) over f32 [n_signals]
+        [n_channels][n_samples] -> d_words uint64 [n_signals][n_channels], the bits of every row's true peak as a double.  Timed by
+        score_last_ms."""
+        self._check(self._L.dusp_true_peak_device(self._h, d_planar, n_signals, n_channels, n_samples, int(sample_rate), d_words, stream))
+
+    def true_peak_tile(self, n_signals, n_channels, n_samples, sample_rate):
+        """-> the output positions a workgroup of that true-peak call owns on this context's device (dusp_true_peak_tile)"""
+        return int(self._L.dusp_true_peak_tile(self._h, n_signals, n_channels, n_samples, int(sample_rate)))
+
+    def true_peak(self, planar, sample_rate):
+        """planar float32 [signals, channels, samples] (or [channels, samples]: one signal) in host memory -> what mix.true_peak
+        returns: float64 [signals, channels], linear, taken on the device (dusp_true_peak_host)."""
+        planar = np.ascontiguousarray(planar, dtype=np.float32)
+        if planar.ndim == 2:
+            planar = planar[None]
+        if planar.ndim != 3:
+            raise ValueError("dusp-hip: the signals to take the true peak of are float32 of shape (signals, channels, samples)")
+        if not int(sample_rate) > 0:
+            raise ValueError("dusp-hip: the true peak needs a sample rate, not %r: it decides the oversampling" % (sample_rate,))
+        S, C, n = planar.shape
+        got = np.zeros((S, C))
+        if n and S and C:
+            self._check(self._L.dusp_true_peak_host(self._h, planar.ctypes.data, S, C, n, int(sample_rate), got.ctypes.data))
+        return got
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
-                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None, stems=False, meters=False):
+                           pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None, stems=False, meters=False, true_peak=False,
+                           loudness=None, true_peak_max=-1.0):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -598,8 +639,17 @@ class Context:
         without stems; peaks float32 [S + 1], every signal's own, whatever the format.
         meters=True: the RMS and the BS.1770 loudness of every signal the call delivers — its S + 1 signals with stems, else the mix —
         at the parts' sample rate (dusp_render_host_score_piece_meters; mix.meters is the contract) -> (what the call returns without
-        meters, dict(rms [signals, channels], lufs [signals], momentary [signals, n_blocks], hop, block)), all float64."""
-        stems, meters = check_stems(stems), check_meters(meters)
+        meters, dict(rms [signals, channels], lufs [signals], momentary [signals, n_blocks], hop, block)), all float64.
+        true_peak=True (implies meters): the dict gains true_peak [signals, channels], linear, the true peak of every signal and
+        channel the call delivers (dusp_render_host_score_piece_loudness; mix.true_peak is the contract).
+        loudness (a finite number of LUFS; implies true_peak; with a format, normalise 0) and true_peak_max (dBTP, at most 0): the
+        frames of every signal are encoded under ONE gain that brings the MIX to that loudness unless the largest true peak of any
+        signal would then exceed the ceiling (mix.loudness_gain; wav.encode_at_level has the bytes); the dict gains gain (a float) and
+        level (numpy.float32)."""
+        stems, meters, true_peak = check_stems(stems), check_meters(meters), check_true_peak(true_peak)
+        loudness, true_peak_max = check_loudness(loudness, true_peak_max, normalise, format is not None)
+        true_peak = true_peak or loudness is not None
+        meters = meters or true_peak
         if tracks is not None:
             track_of, faders, track_sends = check_tracks(len(part_of), tracks["n_tracks"], tracks["track_of"], tracks.get("faders"), tracks.get("track_sends"),
                                                          0 if buses is None else len(buses), sends)
@@ -666,6 +716,13 @@ class Context:
             n_blocks = meter_blocks(n_total_samples, rate)
             got = dict(rms=np.zeros((n_signals, n_ch)), lufs=np.zeros(n_signals), momentary=np.zeros((n_signals, n_blocks)), hop=meter_hop(rate), block=4 * meter_hop(rate))
             want = ScoreMeters(n_signals, n_blocks, got["rms"].ctypes.data, got["lufs"].ctypes.data, _ptr(got["momentary"]))
+            entry, loud = self._L.dusp_render_host_score_piece_meters, ()
+            if true_peak:  # (the same entry with one more record)
+                got["true_peak"] = np.zeros((n_signals, n_ch))
+                gain, level = ctypes.c_double(1.0), ctypes.c_float(1.0)
+                asked_loud = ScoreLoudness(int(loudness is not None), 0.0 if loudness is None else loudness, true_peak_max, got["true_peak"].ctypes.data, ctypes.addressof(gain),
+                                           ctypes.addressof(level))
+                entry, loud = self._L.dusp_render_host_score_piece_loudness, (ctypes.addressof(asked_loud),)
             if stems:
                 if format is None:
                     fmt, normalise, out = 0, 0, self.host_empty((n_signals, n_ch, n_total_samples), pinned)
@@ -674,10 +731,11 @@ class Context:
                 peak, asked = np.empty(n_signals, dtype=np.float32), ScoreStems(n_signals)
             else:
                 fmt, normalise, out, peak = _pcm_out(self, format, normalise, (n_total_samples, n_ch), pinned)
-            self._check(self._L.dusp_render_host_score_piece_meters(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(routed) if tracks is not None else None,
-                                                                    ctypes.addressof(into) if buses is not None else None,
-                                                                    ctypes.addressof(through) if through is not None else None, ctypes.addressof(asked) if stems else None,
-                                                                    ctypes.addressof(want), n_total_samples, int(tile_bytes), fmt, normalise, out.ctypes.data, _ptr(peak)))
+            self._check(entry(*voices, _ptr(lengths), _ptr(gains), ctypes.addressof(how), ctypes.addressof(routed) if tracks is not None else None,
+                              ctypes.addressof(into) if buses is not None else None, ctypes.addressof(through) if through is not None else None,
+                              ctypes.addressof(asked) if stems else None, ctypes.addressof(want), *loud, n_total_samples, int(tile_bytes), fmt, normalise, out.ctypes.data, _ptr(peak)))
+            if loudness is not None:
+                got["gain"], got["level"] = float(gain.value), np.float32(level.value)
             return ((out, peak) if stems else out if peak is None else (out, peak[0])), got
         if stems:
             n_signals = 1 + (tracks["n_tracks"] if tracks is not None else 0) + (len(buses) if buses is not None else 0) + 1

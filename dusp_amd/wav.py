@@ -173,3 +173,19 @@ def encode_stems(stack, bit_depth=16, normalise=NORMALISE_NONE):
     if bit_depth == 32:
         return np.ascontiguousarray(scale_f32(frames, g)), peaks
     return np.ascontiguousarray(pack(quantise(frames, g, bit_depth), bit_depth)), peaks
+
+
+def encode_at_level(stack, bit_depth=16, level=1.0):
+    """encode_stems' byte contract with every signal under gain(level, NORMALISE_FULL) — 1 / float64(float32(level)), or 1 for a level
+    that is 0, NaN or Inf: `level` is the sample magnitude that is brought to full scale (mix.loudness_gain makes it from a loudness
+    target).  At level = the common peak these are the bytes of encode_stems(stack, bit_depth, NORMALISE_FULL).  -> (frames, peaks),
+    the peaks every signal's own sample peak.  The device's bytes with deliver = 1 (dusp_render_host_score_piece_loudness)."""
+    stack = np.ascontiguousarray(stack, dtype=np.float32)
+    if stack.ndim != 3:
+        raise WavError("dusp-hip: the stems are float32 of shape (signals, channels, samples)")
+    peaks = np.array([peak(x) for x in stack], dtype=np.float32)
+    g = gain(level, NORMALISE_FULL)
+    frames = np.transpose(stack, (0, 2, 1))
+    if bit_depth == 32:
+        return np.ascontiguousarray(scale_f32(frames, g)), peaks
+    return np.ascontiguousarray(pack(quantise(frames, g, bit_depth), bit_depth)), peaks

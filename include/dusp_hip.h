@@ -746,7 +746,8 @@ int dusp_peak_common_device(dusp_ctx *ctx, const float *d_peaks, size_t n_peaks,
  * at sample j * hop; momentary[j] = -0.691 + 10 log10(e_j), -inf for 0; lufs the gated integrated loudness (-70 absolute, -10 relative),
  * -inf when no block is left, NaN as soon as one block's energy is not finite — which every block is that holds or follows a sample
  * that is not finite.  The meters are taken on the f32 signals in front of the PCM gain: an encoded file's loudness is
- * lufs + 20 log10(gain).  Not built: true peak, loudness range, short-term loudness, surround weights, delivery to a loudness target.
+ * lufs + 20 log10(gain).  Not built: loudness range, short-term loudness, surround weights (true peak and the delivery at a loudness
+ * target: the next section).
  * The sums are formed in a fixed order without floating-point atomics: two runs give the same bits.  A sample rate below 8000 is
  * refused (the shelf lies at 1682 Hz). */
 /* how many blocks n_samples hold: 0 below a block, else (n_samples - block) / hop + 1; 0 for a sample rate below 8000 */
@@ -781,6 +782,54 @@ int dusp_render_host_score_piece_meters(const dusp_score_part *parts, size_t n_p
                                         const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems,
                                         const dusp_score_meters *meters, size_t n_total_samples, size_t tile_bytes, int format, int normalise,
                                         void *h_out, float *h_peaks);
+
+/* Loudness delivery: the true peak of signals, and PCM frames at a loudness target under a true-peak ceiling (additions to ABI v7,
+ * detected by symbol; dusp_amd/mix.py true_peak_taps, true_peak and loudness_gain are the contract).
+ * The true peak of a row of n f32 samples at a sample rate: the row oversampled F times — F = 4 below 96000 Hz, 2 below 192000 Hz, else
+ * 1 — by the Hann-windowed sinc of 49 taps libebur128 interpolates with, h[j] = sinc((j - 24) / F) x 0.5 (1 - cos(2 pi j / 48)), exactly
+ * 0 where F divides j - 24 != 0; phase p owns h[p], h[p + F], ..: K = ceil(49 / F) taps, a shorter phase padded with a zero tap.  With
+ * x zero outside [0, n), for u in [0, n + K - 1) and every phase: acc = 0.0, acc = acc + h[p + F k] * f64(x[u - k]), k = 0 .. K - 1 in
+ * that order, every product and sum rounded by itself in f64 (no FMA).  The true peak is the largest |acc| — the filter's tail behind
+ * the last sample included — and NaN as soon as one acc is not finite.  F = 1: h = [1], the sample peak.  LINEAR; dBTP is 20 log10.
+ * One 64-bit unsigned maximum a workgroup, no floating-point atomic: two runs give the same bits. */
+/* the factor and the 49 taps at a sample rate (F = 1: h49[0] = 1, the rest 0); a rate of 0 is refused */
+int dusp_true_peak_taps(uint32_t sample_rate, int *factor, double *h49);
+/* the kernel alone, on device pointers: d_words [n_signals][n_channels], 8-byte aligned, one word a row: the bits of its true peak as
+ * a double (the quiet NaN where an accumulator was not finite).  d_planar 4-byte aligned; rows may start on any 4-byte boundary.  The
+ * shapes of dusp_meter_device, any sample rate but 0.  Timed by dusp_score_last_ms. */
+int dusp_true_peak_device(dusp_ctx *ctx, const float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate,
+                          uint64_t *d_words, void *stream);
+/* the output positions a workgroup of that call owns (256 x 1, 2, 4 or 8: what fills the context's device), for tests and profiles; 0
+ * for a call that would be refused */
+size_t dusp_true_peak_tile(dusp_ctx *ctx, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate);
+/* Host round trip: uploads h_planar, runs the kernel and downloads h_true_peak f64 [n_signals][n_channels]. */
+int dusp_true_peak_host(dusp_ctx *ctx, const float *h_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate,
+                        double *h_true_peak);
+/* dusp_render_host_score_piece_meters which also takes the true peak of every signal and channel it delivers, behind the meter kernels
+ * and in front of the peak kernel, and — deliver = 1 — encodes at a loudness target: with lufs the loudness of the MIX (the last
+ * signal) and tp the largest true peak of ANY delivered signal and channel,
+ *     G = min(10^((target_lufs - lufs) / 20), 10^(ceiling_dbtp / 20) / tp),  level = (float)(1 / G),  gain = 1 / (double)level
+ * and every signal's frames are what dusp_encode_device makes of it with `level` as its peak under DUSP_NORMALISE_FULL: ONE gain for all
+ * signals, so the files still add up and none exceeds the ceiling.  The gain is unity (gain 1, level 1.0f: the samples stay as they
+ * are) where lufs is -inf or NaN, where tp is 0, NaN or Inf, and where level comes out zero, subnormal or not finite.  The ceiling only
+ * lowers the gain: there is no limiter.  h_peaks stay the sample peaks.  deliver = 1 waits for the stream once between the meters and
+ * the encode; deliver = 0 waits no more than the _meters entry and delivers its bytes.  loudness NULL: that entry under this entry's
+ * name.  Refused before anything renders, behind every refusal of that entry, each in its own words: NULL h_true_peak; deliver without
+ * meters, with format 0 or with normalise != 0; a target that is not finite; a ceiling that is not finite or above 0; a sample rate
+ * below 8000. */
+typedef struct dusp_score_loudness {
+    int deliver;         /* 0: true peaks only; 1: encode at the loudness target */
+    double target_lufs, ceiling_dbtp;
+    double *h_true_peak; /* [n_signals][channels], required */
+    double *h_gain;      /* 1, may be NULL */
+    float *h_level;      /* 1, may be NULL */
+} dusp_score_loudness;
+int dusp_render_host_score_piece_loudness(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                          const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                          const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                          const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems,
+                                          const dusp_score_meters *meters, const dusp_score_loudness *loudness, size_t n_total_samples,
+                                          size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks);
 
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's

@@ -50,6 +50,10 @@
           stems' case, one channel and two, pass by pass by HIP events (dusp_meter_last_ms), beside dusp_pcm_peak_kernel over the same
           block; then the piece with stems on the host's clock with and without meters=True, one channel and panned into two.  With
           DUSP_HIP_LIB naming a library from before the meters the call with stems alone.  A report: no ratio is fixed in advance.
+  loudness (--loudness; profiles/score_loudness.txt) the true-peak kernel (dusp_true_peak_device) over the same twelve
+          signals, beside the peak kernel and the meter passes; then the piece with stems as s16 frames with meters=True,
+          normalise=2, with true_peak=True and with loudness=-16, and without any new option — the only leg under DUSP_HIP_LIB
+          naming the parent's library.  A report: no ratio is fixed in advance.
 
 Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
 """
@@ -690,6 +694,108 @@ def meters(scale, ctxs, reps):
     prog.close()
 
 
+def loudness(scale, ctxs, reps):
+    """--loudness: the true-peak kernel alone beside the peak kernel and the meter passes over the same block; the
+    call with stems and s16 frames with loudness=-16 beside the same call with meters=True, normalise=2; and the call with stems
+    without any new option, which under DUSP_HIP_LIB naming the parent's library is the only leg that runs."""
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR // (1 if scale == 1 else 8)
+    T, B = 8, 2
+    S = 1 + T + B
+    d.configure(SR)
+    ctx = ctxs["default"]
+    has = hasattr(ctx._L, "dusp_true_peak_device")
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    three = lambda xs: (float(np.median(xs)), min(xs), max(xs))
+    line = "  %-78s median %8.3f ms  fastest %8.3f  slowest %8.3f%s"
+    for C in ((1, 2) if has else ()):
+        block = torch.randn((S + 1, C, nt), dtype=torch.float32, device="cuda") * 0.1
+        n_hops = -(-nt // ((SR + 5) // 10))
+        sumsq, hops, peaks = torch.empty((S + 1, C), dtype=torch.float64, device="cuda"), torch.empty((S + 1, n_hops), dtype=torch.float64, device="cuda"), torch.empty(S + 1, dtype=torch.float32, device="cuda")
+        words = torch.empty((S + 1, C), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        print("loudness: %d signals of %d channel(s) of %d samples (%.0f MB) at %d Hz, F = 4, tiles of %d positions; kernels alone by HIP events, median, fastest and slowest of %d after a warm-up"
+              % (S + 1, C, nt, block.numel() * 4 / 1e6, SR, ctx.true_peak_tile(S + 1, C, nt, SR), reps), flush=True)
+        tp, whole, passes, peak = [], [], [], []
+        for r in range(reps + 1):
+            ctx.true_peak_device(block.data_ptr(), S + 1, C, nt, SR, words.data_ptr(), stream=s)
+            if r:
+                tp.append(ctx.score_last_ms()[0])
+        for r in range(reps + 1):
+            ctx.meter_device(block.data_ptr(), S + 1, C, nt, SR, sumsq.data_ptr(), hops.data_ptr(), stream=s)
+            if r:
+                whole.append(ctx.score_last_ms()[0])
+                passes.append(ctx.meter_last_ms())
+        for r in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(stream):
+                e0.record()
+                ctx.peak(block.data_ptr(), S + 1, C, nt, peaks.data_ptr(), stream=s)
+                e1.record()
+            e1.synchronize()
+            if r:
+                peak.append(e0.elapsed_time(e1))
+        flops = 2.0 * 52 * block.numel()
+        print(line % (("dusp_true_peak_kernel<4> (dusp_true_peak_device; memset of the words included)",) + three(tp) +
+                      ("   %.2f GFLOP of unfused f64: %.1f TFLOP/s; %.0f GB/s read" % (flops / 1e9, flops / np.median(tp) / 1e9, block.numel() * 4 / np.median(tp) / 1e6),)), flush=True)
+        print(line % (("dusp_pcm_peak_kernel over the same block (reads the same bytes once)",) + three(peak) + ("   the true peak is x%.1f of it" % (np.median(tp) / np.median(peak)),)), flush=True)
+        print(line % (("the meter kernels, all passes (dusp_meter_device)",) + three(whole) + ("   the true peak is x%.2f of them" % (np.median(tp) / np.median(whole)),)), flush=True)
+        for k, name in ((0, "pass A: every segment from rest"), (2, "pass B: every segment from its true state, z^2 and x^2")):
+            print(line % (("  " + name,) + three([p[k] for p in passes]) + ("",)), flush=True)
+        again = words.clone()
+        ctx.true_peak_device(block.data_ptr(), S + 1, C, nt, SR, words.data_ptr(), stream=s)
+        stream.synchronize()
+        print("  two runs, the same bits: %s; the largest true peak %.4f, the largest sample %.4f" % (bool(torch.equal(again, words)), float(words.view(torch.float64).max()), float(block.abs().max())),
+              flush=True)
+        del block, sumsq, hops, peaks, words
+    # the whole call: stems' piece — eight fader groups, two stateless buses (a gain each), no master — at one channel, and panned into two
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    prog = ctx.build(uni.words)
+    buses = [ctx.build(descriptor.extract(d.Multiply(d.MasterInput(), g)).words) for g in (0.5, 0.25)]
+    track_of = (np.arange(V) % T).astype(np.int32)
+    rs = np.random.RandomState(4)
+    faders, levels = rs.random_sample(T).astype(np.float32), rs.random_sample((B, T)).astype(np.float32)
+
+    def call(**kw):
+        return ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, buses=[(b, None) for b in buses],
+                                      tracks=dict(n_tracks=T, track_of=track_of, programs=[], faders=faders, track_sends=levels), stems=True, **kw)
+
+    def host_clock(run):
+        times = []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = run()
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+        return three(times[1:])
+
+    row = "  render_score_parts with stems, %-66s median %9.2f ms  fastest %9.2f  slowest %9.2f%s"
+    print("  %d notes of %d samples over %d samples, %d signals, into pinned memory, host clock, median, fastest and slowest of %d after a warm-up; library: %s"
+          % (V, nv, nt, S + 1, reps, os.environ.get("DUSP_HIP_LIB") or "this tree's"), flush=True)
+    for name, kw in (("one channel", {}), ("two channels (pans)", dict(pans=np.linspace(-1, 1, V)))):
+        plain = host_clock(lambda: call(**kw))
+        print(row % ((name + ", planar f32, no new option",) + plain + ("",)), flush=True)
+        frames = host_clock(lambda: call(format="s16", normalise=2, **kw))
+        print(row % ((name + ", s16, normalise=2, no new option",) + frames + ("",)), flush=True)
+        if has:
+            metered = host_clock(lambda: call(format="s16", normalise=2, meters=True, **kw))
+            print(row % ((name + ", s16, normalise=2, meters=True",) + metered + ("",)), flush=True)
+            peaked = host_clock(lambda: call(format="s16", normalise=2, true_peak=True, **kw))
+            print(row % ((name + ", s16, normalise=2, true_peak=True",) + peaked + ("   +%.2f ms, x%.3f of meters=True" % (peaked[0] - metered[0], peaked[0] / metered[0]),)), flush=True)
+            loud = host_clock(lambda: call(format="s16", loudness=-16.0, **kw))
+            print(row % ((name + ", s16, loudness=-16",) + loud + ("   +%.2f ms, x%.3f of meters=True, normalise=2" % (loud[0] - metered[0], loud[0] / metered[0]),)), flush=True)
+            _, got = call(format="s16", loudness=-16.0, **kw)
+            print("    lufs of the mix %.2f, largest true peak %.4f, level %r, gain %.6f: the mix leaves at %.2f LUFS, the largest true peak at %.2f dBTP"
+                  % (got["lufs"][-1], got["true_peak"].max(), got["level"], got["gain"], got["lufs"][-1] + 20 * np.log10(got["gain"]), 20 * np.log10(got["true_peak"].max() * got["gain"])), flush=True)
+    for b in buses:
+        b.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -704,6 +810,7 @@ def main():
     ap.add_argument("--tracks", action="store_true", help="the tracks leg alone: the mix kernel beside the fill and the return kernel, and eight Filter tracks as one program")
     ap.add_argument("--stems", action="store_true", help="the stems leg alone: the stems mix and return kernels beside the kernels they extend, and the piece with and without stems")
     ap.add_argument("--meters", action="store_true", help="the meters leg alone: the meter kernels pass by pass beside the peak kernel, and the piece with stems with and without meters")
+    ap.add_argument("--loudness", action="store_true", help="the loudness leg alone: the true-peak kernel beside the peak kernel and the meter passes, and the piece with stems delivered at a loudness target")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
@@ -717,6 +824,8 @@ def main():
         return stems(a.scale, ctxs, a.reps)
     if a.meters:
         return meters(a.scale, ctxs, a.reps)
+    if a.loudness:
+        return loudness(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
