@@ -11,7 +11,7 @@ from .graph import (Abs, AllPass, Circuit, CircleBuffer, CircleBufferReader, Cir
                     Divide, Filter, FixedDelay, FixedMultiply, Gain, MonoDelay, MultiChannelOsc, ReadBackDelay, HardClipAbove, HardClipBelow, Multiply, Osc, PolarityInvert, Pow,
                     Ramp, Repeater, SecondsToSamples, SemitoneToRatio, Subtract, Sum, Unit,
                     AHD, ConcatChannels, CrossFader, HostSource, MasterInput, MidiToFrequency, Pan, PickChannel, Rescale, SampleRateRedux, Shape, Timer, VectorMagnitude)
-from .render import ChannelData, Metered, Meters, Stems, meter, render_many, render_mix, render_mix_pcm, render_mix_wav, render_piece, render_piece_pcm, render_piece_wav, render_score, render_score_pcm, render_score_wav, renderChannelData, true_peak  # noqa: F401
+from .render import ChannelData, Limiter, Metered, Meters, Stems, limit, meter, render_many, render_mix, render_mix_pcm, render_mix_wav, render_piece, render_piece_pcm, render_piece_wav, render_score, render_score_pcm, render_score_wav, renderChannelData, true_peak  # noqa: F401
 from .runtime import Context, DuspHipError, Program  # noqa: F401
 
 

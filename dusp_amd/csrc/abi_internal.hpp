@@ -11,6 +11,8 @@
 //   abi_piece.hip       pieces: the host renders of several instruments, with a master, buses, tracks, stems and meters
 //   abi_score_sweep.hip device entries without a plan: the buses' return, the tracks' mix, the common peak
 //   abi_meter.hip       meters: RMS and BS.1770 loudness of signals on the device, and the gates on the host
+//   abi_loudness.hip    the true peak of signals on the device
+//   abi_limiter.hip     the linked look-ahead true-peak limiter of signals on the device
 #pragma once
 #include <limits>
 #include <cmath>
@@ -32,6 +34,7 @@
 #include "device_types.hpp"
 #include "fused_plan.hpp"
 #include "jit_codegen.hpp"
+#include "limiter_plan.hpp"
 #include "meter_plan.hpp"
 #include "program.hpp"
 #include "score_plan.hpp"
@@ -82,6 +85,9 @@ hipError_t launch_pcm_peak_common(const float *d_peaks, float *d_common, uint32_
 hipError_t launch_meter(const float *d_planar, uint32_t n_signals, uint32_t n_channels, uint64_t n, uint32_t hop, const MeterCoef &k, double *d_scratch, double *d_sumsq,
                         double *d_hops, hipStream_t stream, hipEvent_t *marks);
 hipError_t launch_true_peak(const float *d_planar, uint64_t rows, uint64_t n, uint32_t F, const TruePeakTaps &taps, int n_cus, uint64_t *d_words, hipStream_t stream);
+hipError_t launch_limit_envelope(const float *d_planar, uint64_t rows, uint64_t n, uint32_t F, const TruePeakTaps &taps, double T, uint32_t L, int n_cus, uint32_t *d_q,
+                                 uint64_t *d_smallest, hipStream_t stream);
+hipError_t launch_limit_apply(float *d_planar, uint64_t rows, uint64_t n, uint32_t L, int n_cus, const uint32_t *d_q, uint64_t *d_smallest, double *d_gain, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -137,6 +143,12 @@ struct dusp_ctx {
     // the true peaks' words (abi_loudness.hip; truepeak_engine.hip), one a (signal, channel), grown on demand
     uint64_t *d_true_peak = nullptr;
     size_t true_peak_cap = 0;  // words
+    // the limiter's scratch (abi_limiter.hip; limiter_engine.hip): the word that takes the smallest window sum, then one 32-bit word a
+    // sample of the timeline, grown on demand
+    uint64_t *d_limit = nullptr;
+    size_t limit_cap = 0;  // samples
+    hipEvent_t limit_marks[3] = {nullptr, nullptr, nullptr};  // around the two kernels of the last dusp_limit_device call
+    bool limit_timed = false;
 };
 
 // DUSP_GUARD=1 (tests): every device allocation of the library carries guard bytes behind its end, filled with a pattern and
@@ -455,6 +467,16 @@ int true_peak_launch(dusp_ctx *ctx, const float *d_planar, size_t n_signals, siz
 int true_peak_download(dusp_ctx *ctx, size_t rows, std::vector<uint64_t> &h_words, hipStream_t stream);
 // the words of a call, once the stream has been waited for -> h_true_peak [rows]; the largest of them, a NaN winning; the guard checked
 int true_peak_values(dusp_ctx *ctx, const char *who, const std::vector<uint64_t> &h_words, double *h_true_peak, double *largest);
+
+// abi_limiter.hip
+// The limiter over d_planar [n_signals][n_channels][n_samples], in place, on `stream`: the envelope kernel against `threshold`, then the
+// gain / apply kernel over a window of L samples; the smallest window sum stays in the context's scratch.  limit_download copies it
+// down behind what the stream holds (asynchronously: the caller waits for the stream, then calls limit_reduction, which also checks
+// the scratch's guard).  The caller has checked the shapes, threshold and L (limit_check)
+int limit_check(dusp_ctx *ctx, const char *who, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold, size_t window_samples);
+int limit_launch(dusp_ctx *ctx, float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold, uint32_t L, hipStream_t stream);
+int limit_download(dusp_ctx *ctx, uint64_t *h_smallest, hipStream_t stream);
+int limit_reduction(dusp_ctx *ctx, const char *who, uint64_t smallest, uint32_t L, double *reduction);
 
 // abi_mix.hip
 constexpr size_t kMixRowMax = (size_t)1 << 31;  // floats in one voice's PCM that the mix kernel's grid covers (mix_engine.hip launch_mix)

@@ -34,6 +34,7 @@ struct PieceCall {
     const dusp_score_stems *stems = nullptr;    // ..._stems: h_out takes 1 + tracks + buses + 1 signals and h_peak as many peaks
     const dusp_score_meters *meters = nullptr;  // ..._meters
     const dusp_score_loudness *loud = nullptr;  // ..._loudness: the true peak of every delivered (signal, channel), and with deliver the one gain
+    const dusp_score_limiter *limiter = nullptr;  // ..._limiter: the delivered signals limited to the ceiling in front of that gain
 
     dusp_program *prog0() const { return parts[0].prog; }  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx() const { return parts[0].prog->ctx; }
@@ -370,6 +371,18 @@ static int piece_check_loudness(const PieceCall &call, const PieceFacts &F) {
     return DUSP_OK;
 }
 
+// check, behind the loudness record's: what a call with a limiter is held to
+static int piece_check_limiter(const PieceCall &call) {
+    const dusp_score_limiter *limiter = call.limiter;
+    if (!limiter) return DUSP_OK;
+    dusp_ctx *ctx = call.ctx();
+    const std::string w(call.who);
+    if (!call.loud || !call.loud->deliver) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + dusp::kLimiterNeedsDeliver);
+    if (limiter->window_samples < 1 || limiter->window_samples > dusp::kLimiterWindowMax)
+        CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + dusp::kLimiterWindowRange + std::to_string(limiter->window_samples));
+    return DUSP_OK;
+}
+
 // The tiles of a call: runs of the chain's voices whose rows together fit tile_bytes.  A part's share of tile i is its instances
 // [share[p][i], share[p][i + 1]), one contiguous range since its instances enter the chain in their own order; its tile buffer holds the
 // largest share
@@ -560,21 +573,63 @@ static int piece_render(const PieceCall &call, const PieceFacts &F, const PieceT
 // peak kernel follows, then the ONE wait for the stream: the gates, the largest true peak of any signal and channel and the loudness of
 // the MIX — the last signal — give the level (truepeak_plan.hpp true_peak_loudness_gain, f64 on the host), which the encoders read as
 // every signal's peak word under DUSP_NORMALISE_FULL: one gain for all, the encode kernels unchanged
-static int deliver_metered(dusp_program *prog, const char *who, const dusp_score_meters *meters, const dusp_score_loudness *loud, uint32_t sample_rate, const float *d_block,
-                           size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise, float *h_peaks, void *h_out, bool common_peak) {
+//
+// With a limiter the host then decides, in f64, whether it is engaged.  Not engaged: nothing more is launched.  Engaged:
+// the limiter's kernels over the block IN PLACE — nothing reads the block behind the delivery — then the same measurement again over the
+// limited block with a second wait, and the gain comes from that second measurement
+//
+// words, smallest: where the true peaks' words and the limiter's smallest sum come down, asynchronously — the CALLER's (deliver_metered),
+// who waits for the stream before they go out of scope where a step in between has failed
+static int deliver_metered_steps(dusp_program *prog, const char *who, const dusp_score_meters *meters, const dusp_score_loudness *loud, const dusp_score_limiter *limiter,
+                                 uint32_t sample_rate, float *d_block, size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise, float *h_peaks, void *h_out,
+                                 bool common_peak, std::vector<uint64_t> &words, uint64_t &smallest) {
     dusp_ctx *ctx = prog->ctx;
-    std::vector<uint64_t> words;
+    const bool at_target = loud && loud->deliver;
+    if (at_target) {
+        double largest = 0.0, gain = 1.0, threshold = 0.0, reduction = 1.0;
+        float level = 1.0f;
+        // one measurement of the block as it stands: the meter kernels, the true-peak kernel, the peak kernel, the ONE wait -> the gain
+        auto measure = [&]() -> int {
+            if (int rc = meter_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, ctx->stream)) return rc;
+            if (int rc = true_peak_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, ctx->stream)) return rc;
+            if (h_peaks)
+                if (int rc = deliver_peaks(prog, d_block, n_signals, n_ch, n_total, h_peaks)) return rc;
+            if (int rc = true_peak_download(ctx, n_signals * n_ch, words, ctx->stream)) return rc;
+            if (int rc = meter_finish(ctx, who, n_signals, n_ch, n_total, sample_rate, ctx->stream, meters->h_rms, meters->h_lufs, meters->h_momentary)) return rc;  // (waits)
+            if (int rc = true_peak_values(ctx, who, words, loud->h_true_peak, &largest)) return rc;
+            dusp::true_peak_loudness_gain(meters->h_lufs[n_signals - 1], largest, loud->target_lufs, loud->ceiling_dbtp, gain, level);
+            return DUSP_OK;
+        };
+        if (int rc = measure()) return rc;
+        const double lufs_in = meters->h_lufs[n_signals - 1], true_peak_in = largest;
+        bool engaged = false;
+        if (limiter) {  // (engaged where the gain is not unity and some true peak lies above the ceiling seen from the target)
+            threshold = dusp::limiter_threshold(lufs_in, loud->target_lufs, loud->ceiling_dbtp);
+            engaged = level != 1.0f && threshold > 0.0 && std::isfinite(threshold) && largest > threshold;
+        }
+        if (engaged) {
+            const uint32_t L = (uint32_t)limiter->window_samples;
+            if (int rc = limit_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, threshold, L, ctx->stream)) return rc;
+            if (int rc = limit_download(ctx, &smallest, ctx->stream)) return rc;
+            if (int rc = measure()) return rc;  // (the limited block; its wait is the download's too)
+            if (int rc = limit_reduction(ctx, who, smallest, L, &reduction)) return rc;
+        }
+        if (limiter) {
+            if (limiter->h_engaged) *limiter->h_engaged = engaged;
+            if (limiter->h_threshold) *limiter->h_threshold = threshold;
+            if (limiter->h_reduction) *limiter->h_reduction = reduction;
+            if (limiter->h_lufs_in) *limiter->h_lufs_in = lufs_in;
+            if (limiter->h_true_peak_in) *limiter->h_true_peak_in = true_peak_in;
+        }
+        if (loud->h_gain) *loud->h_gain = gain;
+        if (loud->h_level) *loud->h_level = level;
+        return deliver_at_level(prog, d_block, n_signals, n_ch, n_total, format, level, h_out);
+    }
     if (meters)
         if (int rc = meter_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, ctx->stream)) return rc;
     if (loud)
         if (int rc = true_peak_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, ctx->stream)) return rc;
-    const bool at_target = loud && loud->deliver;
-    if (at_target) {
-        if (h_peaks)
-            if (int rc = deliver_peaks(prog, d_block, n_signals, n_ch, n_total, h_peaks)) return rc;
-    } else {
-        if (int rc = deliver_host(prog, d_block, nullptr, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak)) return rc;
-    }
+    if (int rc = deliver_host(prog, d_block, nullptr, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak)) return rc;
     if (loud)
         if (int rc = true_peak_download(ctx, n_signals * n_ch, words, ctx->stream)) return rc;
     if (meters) {  // (waits for the stream)
@@ -583,13 +638,19 @@ static int deliver_metered(dusp_program *prog, const char *who, const dusp_score
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (!loud) return DUSP_OK;
-    double largest = 0.0, gain = 1.0;
-    float level = 1.0f;
-    if (int rc = true_peak_values(ctx, who, words, loud->h_true_peak, &largest)) return rc;
-    if (at_target) dusp::true_peak_loudness_gain(meters->h_lufs[n_signals - 1], largest, loud->target_lufs, loud->ceiling_dbtp, gain, level);
-    if (loud->h_gain) *loud->h_gain = gain;
-    if (loud->h_level) *loud->h_level = level;
-    return at_target ? deliver_at_level(prog, d_block, n_signals, n_ch, n_total, format, level, h_out) : DUSP_OK;
+    if (int rc = true_peak_values(ctx, who, words, loud->h_true_peak, nullptr)) return rc;
+    if (loud->h_gain) *loud->h_gain = 1.0;
+    if (loud->h_level) *loud->h_level = 1.0f;
+    return DUSP_OK;
+}
+
+static int deliver_metered(dusp_program *prog, const char *who, const dusp_score_meters *meters, const dusp_score_loudness *loud, const dusp_score_limiter *limiter, uint32_t sample_rate,
+                           float *d_block, size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise, float *h_peaks, void *h_out, bool common_peak) {
+    std::vector<uint64_t> words;
+    uint64_t smallest = 0;
+    const int rc = deliver_metered_steps(prog, who, meters, loud, limiter, sample_rate, d_block, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak, words, smallest);
+    if (rc) (void)hipStreamSynchronize(prog->ctx->stream);  // (a copy into `words` or `smallest` may still be on its way)
+    return rc;
 }
 
 // The one delivery: n_signals signals from d_block, under one gain where common_peak says so; it waits for the stream.  With a master
@@ -597,7 +658,7 @@ static int deliver_metered(dusp_program *prog, const char *who, const dusp_score
 // the one input stream of instance c: its render from its initial state, deciding as a tile of a mix decides (it waits for its compiled
 // kernel), applies `|| 0` at its own copy-out into its d_host_out — which the caller delivers from or, with stems, has copied device to
 // device into the last slot of the block
-static int piece_deliver(const PieceCall &call, const PieceFacts &F, const float *d_block, size_t n_signals, bool common_peak, PieceBatches &batches) {
+static int piece_deliver(const PieceCall &call, const PieceFacts &F, float *d_block, size_t n_signals, bool common_peak, PieceBatches &batches) {
     dusp_ctx *ctx = call.ctx();
     dusp_program *prog0 = call.prog0();
     if (call.master) {
@@ -606,7 +667,7 @@ static int piece_deliver(const PieceCall &call, const PieceFacts &F, const float
         if (call.stems)
             HIP_TRY(ctx, hipMemcpyAsync(prog0->d_stems.p + (n_signals - 1) * F.timeline, call.master->prog->d_host_out.p, F.timeline * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    return deliver_metered(prog0, call.who, call.meters, call.loud, F.sample_rate, d_block, n_signals, F.n_out_ch, call.n_total, call.format, call.normalise, call.h_peak, call.h_out, common_peak);
+    return deliver_metered(prog0, call.who, call.meters, call.loud, call.limiter, F.sample_rate, d_block, n_signals, F.n_out_ch, call.n_total, call.format, call.normalise, call.h_peak, call.h_out, common_peak);
 }
 
 // guards, behind the delivery: the buffers of the piece that the call used, then every auxiliary program's own
@@ -647,7 +708,7 @@ static int piece_finish(const PieceCall &call, const PieceFacts &F, PieceBatches
     if (!stems && !master && !buses && !tracks)
         if (int rc = score_launch(ctx, ScoreLaunch(ScoreKind::rows, call.n_total), F.n_out_ch, call.n_total, nullptr, prog0->d_mix.p, /*raw=*/0, prog0->d_mix.p, ctx->stream, nullptr, 0))
             return rc;
-    const float *d_block = stems ? d_slots : master ? call.master->prog->d_host_out.p : prog0->d_mix.p;
+    float *d_block = stems ? d_slots : master ? call.master->prog->d_host_out.p : prog0->d_mix.p;
     if (int rc = piece_deliver(call, F, d_block, stems ? F.n_signals : 1, /*common_peak=*/stems, batches)) return rc;
     for (auto &batch : batches) batch->staged = false;  // (the delivery has waited for the stream)
     return piece_guards(call);
@@ -665,6 +726,7 @@ static int render_host_score_parts(PieceCall call) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         if (int rc = piece_tiles(call, facts, tiles)) return rc;
         if (int rc = piece_check_loudness(call, facts)) return rc;
+        if (int rc = piece_check_limiter(call)) return rc;
         if (int rc = piece_plans(call, facts, tiles, plans)) return rc;
         if (int rc = piece_buffers(call, facts, plans)) return rc;
         PieceBatches batches;  // (behind the plans and tiles: a batch whose vectors are still on their way waits for the stream as it goes)
@@ -809,15 +871,32 @@ int dusp_render_host_score_piece_meters(const dusp_score_part *parts, size_t n_p
 }
 
 // ... and with a loudness record: the true peak of every signal and channel the call delivers and, with deliver, PCM frames at a loudness
-// target under a true-peak ceiling (loudness NULL: dusp_render_host_score_piece_meters under this entry's name)
+// target under a true-peak ceiling (loudness NULL: dusp_render_host_score_piece_meters under this entry's name); with a limiter the
+// delivered signals are limited to the ceiling in front of the gain.  One body for the two entries, each under its own name
+static int render_host_score_piece_limiter(const char *who, const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                           const int64_t *h_lengths, const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                           const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems, const dusp_score_meters *meters,
+                                           const dusp_score_loudness *loudness, const dusp_score_limiter *limiter, size_t n_total_samples, size_t tile_bytes, int format, int normalise,
+                                           void *h_out, float *h_peaks) {
+    PieceCall call = piece_call(who, parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, n_total_samples, tile_bytes, format, normalise, h_out, h_peaks);
+    call.master = master, call.buses = buses, call.tracks = tracks, call.stems = stems, call.meters = meters, call.loud = loudness, call.limiter = limiter;
+    return render_host_score_piece(call, placement);
+}
+
 int dusp_render_host_score_piece_loudness(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
                                           const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks, const dusp_score_buses *buses,
                                           const dusp_score_master *master, const dusp_score_stems *stems, const dusp_score_meters *meters, const dusp_score_loudness *loudness,
                                           size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks) {
-    PieceCall call = piece_call("dusp_render_host_score_piece_loudness", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, n_total_samples, tile_bytes, format, normalise,
-                                h_out, h_peaks);
-    call.master = master, call.buses = buses, call.tracks = tracks, call.stems = stems, call.meters = meters, call.loud = loudness;
-    return render_host_score_piece(call, placement);
+    return render_host_score_piece_limiter("dusp_render_host_score_piece_loudness", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, tracks, buses, master, stems,
+                                           meters, loudness, nullptr, n_total_samples, tile_bytes, format, normalise, h_out, h_peaks);
+}
+
+int dusp_render_host_score_piece_limiter(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets, const int64_t *h_lengths,
+                                         const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks, const dusp_score_buses *buses,
+                                         const dusp_score_master *master, const dusp_score_stems *stems, const dusp_score_meters *meters, const dusp_score_loudness *loudness,
+                                         const dusp_score_limiter *limiter, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks) {
+    return render_host_score_piece_limiter("dusp_render_host_score_piece_limiter", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, tracks, buses, master, stems,
+                                           meters, loudness, limiter, n_total_samples, tile_bytes, format, normalise, h_out, h_peaks);
 }
 
 }  // extern "C"

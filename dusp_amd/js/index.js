@@ -30,6 +30,7 @@ module.exports = {
   stemNames: renderChannelData.stemNames,
   meter: renderChannelData.meter,
   truePeak: renderChannelData.truePeak,
+  limit: renderChannelData.limit,
   meterBlocks: renderChannelData.meterBlocks,
   deviceCount: renderChannelData.deviceCount,
   renderDescriptor: renderChannelData.renderDescriptor,

@@ -458,11 +458,11 @@ function wholeSamples(who, name, values, count) {
  * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too.
  * stems: true — as renderPiece's: the direct mix, every track and every bus return beside the mix — through the piece's call too.
  * meters: true — as renderPiece's: the RMS and the BS.1770 loudness of every signal the call delivers — through the piece's call too.
- * truePeak: true, and on the Pcm / Wav forms loudness, truePeakMax — as renderPiece's — through the piece's call too. */
+ * truePeak: true, and on the Pcm / Wav forms loudness, truePeakMax, limiter, limiterWindow — as renderPiece's — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
 const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends) ||
   given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends) || (opts.stems !== undefined && opts.stems !== false) ||
-  (opts.meters !== undefined && opts.meters !== false) || (opts.truePeak !== undefined && opts.truePeak !== false) || given(opts.loudness)
+  (opts.meters !== undefined && opts.meters !== false) || (opts.truePeak !== undefined && opts.truePeak !== false) || given(opts.loudness) || (opts.limiter !== undefined && opts.limiter !== false)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -892,11 +892,11 @@ function pcmStems(names, nChannels, sampleRate, result, bitDepth, normalise) {
 }
 /* PCM -> a WAV file; the stems of a call -> a file a signal */
 function wavOf(pcm) {
-  if (pcm.meters && !pcm.names) return Object.assign({ mix: encodeWav(pcm.mix), meters: pcm.meters }, pcm.level === undefined ? {} : { gain: pcm.gain, level: pcm.level }) // (meters without stems)
+  if (pcm.meters && !pcm.names) return Object.assign({ mix: encodeWav(pcm.mix), meters: pcm.meters }, pcm.level === undefined ? {} : { gain: pcm.gain, level: pcm.level }, pcm.limiter === undefined ? {} : { limiter: pcm.limiter }) // (meters without stems)
   if (pcm.meters) return Object.assign(wavOf(Object.assign({}, pcm, { meters: undefined })), { meters: pcm.meters })
   if (!pcm.names) return encodeWav(pcm)
   const files = pcm.names.map((name, s) => encodeWav(s === 0 ? pcm.direct : s === pcm.names.length - 1 ? pcm.mix : s <= pcm.tracks.length ? pcm.tracks[s - 1] : pcm.buses[s - 1 - pcm.tracks.length]))
-  return stemsOf(pcm.names, files, pcm.names.map((name) => pcm.peaks[name]), Object.assign({ gain: pcm.gain }, pcm.level === undefined ? {} : { level: pcm.level }))
+  return stemsOf(pcm.names, files, pcm.names.map((name) => pcm.peaks[name]), Object.assign({ gain: pcm.gain }, pcm.level === undefined ? {} : { level: pcm.level }, pcm.limiter === undefined ? {} : { limiter: pcm.limiter }))
 }
 
 /* Meters (DESIGN.md 6.18): the refusals, the hop and the block count, in the words of mix.py (METERS_NOT_BOOL, METER_RATE_LOW, meter_hop,
@@ -916,6 +916,35 @@ const LOUDNESS = {
   ceiling: 'dusp-hip: true_peak_max is a finite number of dBTP at most 0 (default -1), the ceiling no delivered signal\'s true peak exceeds',
   withNormalise: (normalise) => 'dusp-hip: loudness and normalise=' + normalise + ' do not go together: the target decides the gain, normalise must be 0',
   planar: 'dusp-hip: loudness goes with the _pcm and _wav calls: 32-bit frames via bit_depth=32 are the f32 delivery at a target'
+}
+/* The limiter of a loudness delivery (DESIGN.md 6.20): the refusals in the words of mix.py (LIMITER_NOT_BOOL, LIMITER_NEEDS_LOUDNESS,
+ * LIMITER_WINDOW_BAD, LIMITER_WINDOW_LONG; check_limiter) */
+const LIMITER = {
+  notBool: 'dusp-hip: limiter is True or False: with True a delivery at a loudness target is limited to the true-peak ceiling before the one gain is taken',
+  needsLoudness: "dusp-hip: limiter without loudness: the limiter's threshold is the ceiling seen from the loudness target, so it needs loudness=",
+  windowBad: "dusp-hip: limiter_window is a finite positive number of seconds (default 0.005), the limiter's look-ahead, attack and release",
+  windowLong: (samples, sampleRate) => 'dusp-hip: limiter_window is ' + samples + ' samples at ' + sampleRate + " Hz: the limiter's window is at most 4096 samples",
+  threshold: "dusp-hip: the limiter's threshold is a finite number above 0, linear",
+  windowSamples: "dusp-hip: the limiter's window is a whole number of samples, 1 .. 4096"
+}
+function checkLimiterBool(limiter) {
+  if (limiter === undefined) return false
+  if (typeof limiter !== 'boolean') throw LIMITER.notBool
+  return limiter
+}
+/* limiter (a boolean already), limiterWindow: of a call with that loudness target at that sample rate -> the window in samples, 0 without a
+ * limiter: max(1, round(window x sampleRate)), halves to the even number as Python's round */
+function checkLimiter(limiter, limiterWindow, target, sampleRate) {
+  if (!limiter) return 0
+  if (target === null) throw LIMITER.needsLoudness
+  const w = limiterWindow === undefined ? 0.005 : limiterWindow
+  if (typeof w !== 'number' || !Number.isFinite(w) || !(w > 0)) throw LIMITER.windowBad
+  const exact = w * sampleRate
+  if (exact > 2 * 4096) throw LIMITER.windowLong(BigInt(Math.min(Math.trunc(exact), 2 ** 62)).toString(), sampleRate) // (Python's min(int(.), 2**62) through %d)
+  const down = Math.floor(exact), rounded = exact - down > 0.5 || (exact - down === 0.5 && down % 2 === 1) ? down + 1 : down
+  const L = Math.max(1, rounded)
+  if (L > 4096) throw LIMITER.windowLong(L, sampleRate)
+  return L
 }
 function checkTruePeak(truePeak) {
   if (truePeak === undefined) return false
@@ -991,6 +1020,27 @@ function truePeak(channelData, sampleRate) {
   return signals.map((sig, s) => got.slice(s * nChannels, (s + 1) * nChannels))
 }
 
+/* The linked look-ahead limiter over any signals a user has (twin of render.py limit): channelData as meter takes it, a threshold (linear,
+ * finite, above 0) and a window of 1 .. 4096 samples -> { data, gain, reduction }: data shaped as channelData, every row multiplied by ONE
+ * gain curve; gain the curve, a Float64Array [samples]; reduction its smallest value, 1 where nothing exceeds the threshold.  On the
+ * device (dusp_limit_host). */
+function limit(channelData, sampleRate, threshold, window) {
+  const nested = channelData.length && !ArrayBuffer.isView(channelData[0])
+  const signals = nested ? Array.from(channelData) : [channelData]
+  const nChannels = signals[0].length, nSamples = nChannels ? signals[0][0].length : 0
+  if (!(sampleRate > 0)) throw 'dusp-hip: limit: the limiter needs a sample rate: it decides the oversampling'
+  if (typeof threshold !== 'number' || !Number.isFinite(threshold) || !(threshold > 0)) throw LIMITER.threshold
+  if (!Number.isInteger(window) || window < 1 || window > 4096) throw LIMITER.windowSamples
+  if (!nChannels || signals.some((sig) => sig.length !== nChannels || Array.from(sig).some((ch) => !(ch instanceof Float32Array) || ch.length !== nSamples)))
+    throw 'dusp-hip: limit: the signals are Float32Arrays of one length, the same number a signal'
+  if (nSamples === 0) return { data: nested ? signals.map((sig) => Array.from(sig, () => new Float32Array(0))) : Array.from(signals[0], () => new Float32Array(0)), gain: new Float64Array(0), reduction: 1 }
+  const planar = new Float32Array(signals.length * nChannels * nSamples)
+  signals.forEach((sig, s) => Array.from(sig).forEach((ch, c) => planar.set(ch, (s * nChannels + c) * nSamples)))
+  const got = native().limit(contextFor(sampleRate), planar, signals.length, nChannels, nSamples, sampleRate, threshold, window)
+  const rows = signals.map((sig, s) => Array.from(sig, (ch, c) => got.data.subarray((s * nChannels + c) * nSamples, (s * nChannels + c + 1) * nSamples)))
+  return { data: nested ? rows : rows[0], gain: got.gain, reduction: got.reduction }
+}
+
 /* what sends and tracks do not go with, refused before anything else of a call is looked at (twin of render.py _placing) */
 function refuseSends(opts) {
   if (!given(opts.tracks)) {
@@ -1017,6 +1067,7 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   const stems = checkStems(opts.stems) // (what is no boolean is refused first)
   const metersAsked = checkMeters(opts.meters) // (... and next to it)
   const truePeakAsked = checkTruePeak(opts.truePeak) // (... and next to that)
+  const limiterAsked = checkLimiterBool(opts.limiter) // (... and next to that again)
   const loud = checkLoudness(opts.loudness, opts.truePeakMax, normalise, format !== 0) // (... then what the loudness target does not go with)
   const truePeaks = truePeakAsked || loud.target !== null, meters = metersAsked || truePeaks // (a target implies true peaks, true peaks imply meters)
   refuseSends(opts)
@@ -1070,9 +1121,11 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     buses = opts.buses.map((fx, b) => masterProgram(fx, nChannels, sampleRate, b))
   }
   const names = stems ? stemNames(routed ? opts.tracks.length : 0, buses ? buses.length : 0) : null
+  const window = checkLimiter(limiterAsked, opts.limiterWindow, loud.target, sampleRate) // (the limiter's window in samples, 0 without one)
   if (meters && !(sampleRate >= 8000)) throw METER_RATE_LOW(sampleRate)
   const nBlocks = meterBlocks(nSamples, sampleRate)
-  const delivered = loud.target !== null ? (got) => ({ gain: got ? got.gain : 1, level: got ? got.level : 1 }) : () => null
+  const idle = { engaged: false, threshold: 0, window, reduction: 1, lufsIn: -Infinity, truePeakIn: 0 } // (a timeline of no samples)
+  const delivered = loud.target !== null ? (got) => Object.assign({ gain: got ? got.gain : 1, level: got ? got.level : 1 }, window ? { limiter: got ? got.limiter : idle } : {}) : () => null
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null, names, metered: meters ? metersOf(names || ['mix'], null, nChannels, 0, sampleRate, truePeaks) : null, loud: delivered(null) }
   const progs = [], busProgs = [], trackProgs = []
   let masterProg = null
@@ -1083,11 +1136,11 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
     if (groups) for (const group of groups) trackProgs.push(n.programBuild(contextFor(sampleRate), group.uni.words, engine))
-    const result = meters ? await (truePeaks ? n.renderPieceLoudness : n.renderPieceMeters)(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+    const result = meters ? await (window ? n.renderPieceLimiter : truePeaks ? n.renderPieceLoudness : n.renderPieceMeters)(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
       routed ? trackProgs : null, routed ? groups.map((group) => Uint32Array.from(group.tracks)) : null, routed ? groups.map((group) => (group.uni.nParams ? group.uni.params : null)) : null,
-      routed ? routed.faders : null, routed ? routed.trackSends : null, stems, nBlocks, ...(truePeaks ? [loud.target !== null, loud.target === null ? 0 : loud.target, loud.ceiling] : []))
+      routed ? routed.faders : null, routed ? routed.trackSends : null, stems, nBlocks, ...(truePeaks ? [loud.target !== null, loud.target === null ? 0 : loud.target, loud.ceiling] : []), ...(window ? [window] : []))
       : stems ? await n.renderPieceStems(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
@@ -1262,6 +1315,9 @@ module.exports.meterHop = meterHop
 module.exports.meterBlocks = meterBlocks
 module.exports.meter = meter
 module.exports.truePeak = truePeak
+module.exports.limit = limit
+module.exports.LIMITER = LIMITER
+module.exports.checkLimiter = checkLimiter
 module.exports.TRUE_PEAK_NOT_BOOL = TRUE_PEAK_NOT_BOOL
 module.exports.LOUDNESS = LOUDNESS
 module.exports.instanceRange = instanceRange

@@ -1206,3 +1206,154 @@ def loudness_gain(lufs, true_peaks, target_lufs, ceiling_dbtp):
     if not np.isfinite(level) or level < np.finfo(np.float32).tiny:
         return unity
     return 1.0 / float(np.float64(level)), level
+
+
+# ---- the look-ahead true-peak limiter of a delivery at a loudness target ----
+
+LIMITER_NOT_BOOL = "dusp-hip: limiter is True or False: with True a delivery at a loudness target is limited to the true-peak ceiling before the one gain is taken"
+LIMITER_NEEDS_LOUDNESS = "dusp-hip: limiter without loudness: the limiter's threshold is the ceiling seen from the loudness target, so it needs loudness="
+LIMITER_WINDOW_BAD = "dusp-hip: limiter_window is a finite positive number of seconds (default 0.005), the limiter's look-ahead, attack and release"
+LIMITER_WINDOW_LONG = "dusp-hip: limiter_window is %d samples at %d Hz: the limiter's window is at most 4096 samples"
+LIMITER_THRESHOLD_BAD = "dusp-hip: the limiter's threshold is a finite number above 0, linear"
+LIMITER_WINDOW_SAMPLES = "dusp-hip: the limiter's window is a whole number of samples, 1 .. 4096"
+LIMITER_ONE = 1 << 30  # the gain curve's fixed point: 30 fractional bits
+LIMITER_WINDOW_MAX = 4096
+
+
+def check_limiter(limiter, limiter_window, loudness, sample_rate):
+    """`limiter=` and `limiter_window=` of a _pcm or _wav call -> L, the window in samples, max(1, round(window x sample_rate)); 0 for
+    limiter=False (the window is then not looked at).  Refused by string: a limiter that is no bool, limiter=True without loudness=,
+    a window that is no finite positive number, and one of more than 4096 samples"""
+    if not isinstance(limiter, (bool, np.bool_)):
+        raise ValueError(LIMITER_NOT_BOOL)
+    if not limiter:
+        return 0
+    if loudness is None:
+        raise ValueError(LIMITER_NEEDS_LOUDNESS)
+    w = limiter_window
+    if not isinstance(w, (int, float, np.integer, np.floating)) or isinstance(w, (bool, np.bool_)) or not np.isfinite(w) or not w > 0:
+        raise ValueError(LIMITER_WINDOW_BAD)
+    exact = float(w) * float(sample_rate)
+    if exact > 2.0 * LIMITER_WINDOW_MAX:  # (far too long, perhaps beyond what int() takes: the text says at most 2^62)
+        raise ValueError(LIMITER_WINDOW_LONG % (int(exact) if exact < 2.0 ** 62 else 2 ** 62, sample_rate))
+    L = max(1, int(round(float(w) * float(sample_rate))))
+    if L > LIMITER_WINDOW_MAX:
+        raise ValueError(LIMITER_WINDOW_LONG % (L, sample_rate))
+    return L
+
+
+def limiter_threshold(lufs, target_lufs, ceiling_dbtp):
+    """T, the true-peak magnitude that the gain of the loudness target brings exactly to the ceiling:
+    10^(ceiling / 20) / 10^((target - lufs) / 20), two powers and a division in f64 (limiter_plan.hpp limiter_threshold)."""
+    import math
+
+    def power(x):  # (C's pow: what overflows is inf, not an exception)
+        try:
+            return math.pow(10.0, x)
+        except OverflowError:
+            return math.inf
+    with np.errstate(all="ignore"):
+        return float(np.float64(power(float(ceiling_dbtp) / 20.0)) / np.float64(power((float(target_lufs) - float(lufs)) / 20.0)))
+
+
+def _limiter_taps(sample_rate, taps):
+    F, h = true_peak_taps(sample_rate) if taps is None else (int(taps[0]), np.asarray(taps[1], dtype=np.float64))
+    K = -(-len(h) // F)
+    phases = np.zeros((F, K))
+    for p in range(F):
+        own = h[p::F]
+        phases[p, :len(own)] = own
+    return F, K, phases
+
+
+def limiter_envelope(signals, sample_rate, taps=None):
+    """The limiter's envelope: signals float32 [S, C, n] -> e float64 [n], the largest oversampled magnitude of ANY row around sample
+    s.  With F, h, K those of true_peak_taps and D = (K - 1) / 2 (6 at F = 4, 12 at F = 2, 0 at F = 1) every row's accumulators
+    acc_p[u] are formed exactly as true_peak forms them; e[s] is the largest |acc_p[s + D]| over all rows and phases — the interpolator
+    delays by D samples, so these are the F oversampled points that belong to sample s.  An accumulator that is not finite counts as
+    0: the limiter does not react to a NaN or Inf sample.  The filter's head (u < D) and tail (u >= n + D) take no part."""
+    signals = np.asarray(signals, dtype=np.float32)
+    if signals.ndim != 3:
+        raise ValueError("dusp-hip: the signals to limit are float32 of shape (signals, channels, samples)")
+    F, K, phases = _limiter_taps(sample_rate, taps)
+    D = (K - 1) // 2
+    S, C, n = signals.shape
+    e = np.zeros(n)
+    if n == 0 or S * C == 0:
+        return e
+    x = np.zeros((S * C, n + 2 * (K - 1)))
+    x[:, K - 1:K - 1 + n] = signals.reshape(S * C, n).astype(np.float64)
+    with np.errstate(all="ignore"):
+        for p in range(F):
+            acc = np.zeros((S * C, n))
+            for k in range(K):  # u = s + D: x[u - k] lies at K - 1 + s + D - k
+                acc = acc + phases[p, k] * x[:, K - 1 + D - k:K - 1 + D - k + n]
+            e = np.maximum(e, np.max(np.abs(np.where(np.isfinite(acc), acc, 0.0)), axis=0))
+    return e
+
+
+def limiter_gain(e, threshold, window):
+    """The limiter's gain curve from its envelope -> (g float64 [n], q uint32 [n]).  T = threshold > 0, L = window, 1 .. 4096 samples:
+    r[s] = T / e[s] where e[s] > T, else 1 (one f64 division); q[s] = floor(r[s] x 2^30), ONE = 2^30 outside [0, n);
+    m[j] = min(q[j .. j + L - 1]) for j in [-(L - 1), n); sum[s] = m[s - L + 1] + .. + m[s], an exact integer; g[s] = f64(sum[s]) /
+    f64(L x ONE).  So g[s] <= r[s], exactly — every minimum in the mean holds q[s], and the floor and the integer mean only round down —
+    and g[s] is no lower than the smallest r within L samples of s less 2^-30.  The curve reaches a
+    peak's gain in a linear attack of L samples and leaves it in a release of L samples."""
+    import math
+    T, L = float(threshold), int(window)
+    if not (T > 0.0 and math.isfinite(T)):
+        raise ValueError(LIMITER_THRESHOLD_BAD)
+    if L != window or not 1 <= L <= LIMITER_WINDOW_MAX:
+        raise ValueError(LIMITER_WINDOW_SAMPLES)
+    e = np.asarray(e, dtype=np.float64)
+    n = len(e)
+    with np.errstate(all="ignore"):
+        r = np.where(e > T, T / np.where(e > T, e, 1.0), 1.0)
+    q = np.floor(r * float(LIMITER_ONE)).astype(np.uint32)
+    a = np.full(n + 2 * (L - 1), LIMITER_ONE, dtype=np.int64)  # a[j] = q[j - (L - 1)]
+    a[L - 1:L - 1 + n] = q
+    p, step = a.copy(), 1  # p[i] = min(a[i .. i + step - 1]) wherever that window lies inside a
+    while 2 * step <= L:
+        p[:len(p) - step] = np.minimum(p[:len(p) - step], p[step:])
+        step *= 2
+    m = np.minimum(p[:n + L - 1], p[L - step:L - step + n + L - 1])  # m[j'] = min(a[j' .. j' + L - 1]), j' = j + (L - 1)
+    c = np.concatenate(([0], np.cumsum(m)))
+    total = c[L:L + n] - c[:n]  # sum[s] = m[s] + .. + m[s + L - 1] in that indexing
+    return total.astype(np.float64) / float(L * LIMITER_ONE), q
+
+
+def limit(signals, sample_rate, threshold, window, taps=None):
+    """The linked look-ahead limiter: the contract of dusp_limit_host and of limiter=True, in f64 and integers, needs no GPU.
+    signals float32 [S, C, n] -> (limited float32 [S, C, n], g float64 [n], reduction): ONE curve g = limiter_gain(limiter_envelope(
+    signals)) for every row, limited = f32(f64(x) x g[s]); reduction = min(g), 1.0 exactly where nothing exceeds the threshold (the
+    output is then the input bit for bit).  A NaN sample stays a NaN."""
+    signals = np.asarray(signals, dtype=np.float32)
+    g, _ = limiter_gain(limiter_envelope(signals, sample_rate, taps), threshold, window)
+    with np.errstate(all="ignore"):
+        limited = (signals.astype(np.float64) * g).astype(np.float32)
+    return limited, g, (float(np.min(g)) if len(g) else 1.0)
+
+
+def deliver_limited(signals, sample_rate, target_lufs, ceiling_dbtp, window, taps=None):
+    """The whole chain of a delivery with limiter=True over the f32 signals the call delivers (the mix LAST), in f64, needs no GPU: the
+    contract of dusp_render_host_score_piece_limiter.  -> dict(signals, meters, true_peak, gain, level, limiter): the signals that are
+    encoded (wav.encode_at_level(signals, bit_depth, level) has the bytes), their meters and true peaks, the one gain and its level,
+    and the limiter's record — engaged, threshold, window, reduction, lufs_in, true_peak_in.
+
+    First meters, true_peak and loudness_gain as without a limiter.  T = limiter_threshold(lufs of the mix, target, ceiling).  The
+    limiter is engaged where that gain is not unity (level != 1), T is finite and above 0, and the largest true peak exceeds T;
+    otherwise the delivery is the one without a limiter.  Engaged: limit(signals, T, window), then meters, true_peak and loudness_gain
+    again over the limited signals — the ceiling is held by that gain, and what is returned describes the limited signals."""
+    import math
+    signals = np.asarray(signals, dtype=np.float32)
+    metered, tps = meters(signals, sample_rate), true_peak(signals, sample_rate, taps)
+    gain, level = loudness_gain(metered["lufs"][-1], tps, target_lufs, ceiling_dbtp)
+    lufs_in, tp_in = float(metered["lufs"][-1]), (float("nan") if np.any(np.isnan(tps)) else float(np.max(tps)))
+    record = dict(engaged=False, threshold=0.0, window=int(window), reduction=1.0, lufs_in=lufs_in, true_peak_in=tp_in)
+    T = record["threshold"] = limiter_threshold(lufs_in, target_lufs, ceiling_dbtp)
+    if level != np.float32(1.0) and T > 0.0 and math.isfinite(T) and tp_in > T:
+        signals, _, reduction = limit(signals, sample_rate, T, window, taps)
+        metered, tps = meters(signals, sample_rate), true_peak(signals, sample_rate, taps)
+        gain, level = loudness_gain(metered["lufs"][-1], tps, target_lufs, ceiling_dbtp)
+        record.update(engaged=True, reduction=reduction)
+    return dict(signals=signals, meters=metered, true_peak=tps, gain=gain, level=level, limiter=record)

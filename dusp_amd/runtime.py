@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import check_loudness, check_meters, check_stems, check_true_peak, meter_blocks, meter_hop, METER_RATE_LOW, METER_RATE_MIN, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
+from .mix import check_limiter, check_loudness, check_meters, check_stems, check_true_peak, meter_blocks, meter_hop, METER_RATE_LOW, METER_RATE_MIN, LIMITER_THRESHOLD_BAD, LIMITER_WINDOW_MAX, LIMITER_WINDOW_SAMPLES, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,6 +39,7 @@ EXPORTS = [
     "dusp_render_host_score_piece_stems", "dusp_score_stems_mix_device", "dusp_score_stems_return_device", "dusp_peak_common_device",
     "dusp_meter_blocks", "dusp_meter_device", "dusp_meter_last_ms", "dusp_meter_host", "dusp_render_host_score_piece_meters",
     "dusp_true_peak_taps", "dusp_true_peak_tile", "dusp_true_peak_device", "dusp_true_peak_host", "dusp_render_host_score_piece_loudness",
+    "dusp_limiter_threshold", "dusp_limit_tile", "dusp_limit_device", "dusp_limit_last_ms", "dusp_limit_host", "dusp_render_host_score_piece_limiter",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -142,6 +143,13 @@ def load():
         L.dusp_true_peak_device.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, vp, vp]
         L.dusp_true_peak_host.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, vp]
         L.dusp_render_host_score_piece_loudness.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    if hasattr(L, "dusp_render_host_score_piece_limiter"):  # (detected by symbol, as the loudness delivery is)
+        L.dusp_limiter_threshold.argtypes, L.dusp_limiter_threshold.restype = [ctypes.c_double] * 3, ctypes.c_double
+        L.dusp_limit_tile.argtypes, L.dusp_limit_tile.restype = [vp, sz, sz], sz
+        L.dusp_limit_device.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, ctypes.c_double, sz, vp, vp, vp, vp]
+        L.dusp_limit_last_ms.argtypes = [vp, vp]
+        L.dusp_limit_host.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, ctypes.c_double, sz, vp, vp, vp]
+        L.dusp_render_host_score_piece_limiter.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -210,6 +218,13 @@ class ScoreLoudness(ctypes.Structure):
     [signals][channels], the gain and the level go"""
     _fields_ = [("deliver", ctypes.c_int), ("target_lufs", ctypes.c_double), ("ceiling_dbtp", ctypes.c_double), ("h_true_peak", ctypes.c_void_p), ("h_gain", ctypes.c_void_p),
                 ("h_level", ctypes.c_void_p)]
+
+
+class ScoreLimiter(ctypes.Structure):
+    """dusp_score_limiter: the limiter's window in samples, and where what it did goes: whether it ran, its threshold, min(g), and the
+    mix's loudness and the largest true peak in front of it"""
+    _fields_ = [("window_samples", ctypes.c_size_t), ("h_engaged", ctypes.c_void_p), ("h_threshold", ctypes.c_void_p), ("h_reduction", ctypes.c_void_p),
+                ("h_lufs_in", ctypes.c_void_p), ("h_true_peak_in", ctypes.c_void_p)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -601,9 +616,49 @@ class Context:
             self._check(self._L.dusp_true_peak_host(self._h, planar.ctypes.data, S, C, n, int(sample_rate), got.ctypes.data))
         return got
 
+    def limit_device(self, d_planar, n_signals, n_channels, n_samples, sample_rate, threshold, window, d_q=None, d_gain=None, d_smallest=None, stream=None):
+        """Device pointers: the limiter's two kernels alone (dusp_limit_device; mix.limit is the contract), IN PLACE over f32 [n_signals]
+        [n_channels][n_samples].  Optional: d_q uint32 [n_samples], the words q; d_gain float64 [n_samples], the curve; d_smallest, one
+        uint64, the smallest window sum (reduction = word / (window x 2^30)).  Timed by score_last_ms; limit_last_ms has the two kernels."""
+        self._check(self._L.dusp_limit_device(self._h, d_planar, n_signals, n_channels, n_samples, int(sample_rate), float(threshold), int(window), d_q, d_gain, d_smallest, stream))
+
+    def limit_last_ms(self):
+        """-> the two kernels of the most recent limit_device call in ms, by HIP events (dusp_limit_last_ms; waits for that call): the
+        envelope kernel, the gain / apply kernel"""
+        ms = (ctypes.c_float * 2)()
+        self._check(self._L.dusp_limit_last_ms(self._h, ctypes.addressof(ms)))
+        return tuple(ms)
+
+    def limit_tile(self, n_samples, window):
+        """-> the samples a workgroup of that limiter call owns on this context's device (dusp_limit_tile)"""
+        return int(self._L.dusp_limit_tile(self._h, n_samples, int(window)))
+
+    def limit(self, planar, sample_rate, threshold, window):
+        """planar float32 [signals, channels, samples] (or [channels, samples]: one signal) in host memory -> what mix.limit returns:
+        (limited float32 of planar's shape, g float64 [samples], reduction), limited on the device under ONE curve
+        (dusp_limit_host).  threshold: linear, finite, above 0; window: 1 .. 4096 samples."""
+        planar = np.ascontiguousarray(planar, dtype=np.float32)
+        shape = planar.shape
+        if planar.ndim == 2:
+            planar = planar[None]
+        if planar.ndim != 3:
+            raise ValueError("dusp-hip: the signals to limit are float32 of shape (signals, channels, samples)")
+        if not int(sample_rate) > 0:
+            raise ValueError("dusp-hip: the limiter needs a sample rate, not %r: it decides the oversampling" % (sample_rate,))
+        if not (isinstance(threshold, (int, float, np.integer, np.floating)) and np.isfinite(threshold) and threshold > 0):
+            raise ValueError(LIMITER_THRESHOLD_BAD)
+        if not (isinstance(window, (int, np.integer)) and 1 <= window <= LIMITER_WINDOW_MAX):
+            raise ValueError(LIMITER_WINDOW_SAMPLES)
+        S, C, n = planar.shape
+        limited, g, reduction = np.empty_like(planar), np.ones(n), ctypes.c_double(1.0)
+        if n and S and C:
+            self._check(self._L.dusp_limit_host(self._h, planar.ctypes.data, S, C, n, int(sample_rate), float(threshold), int(window), limited.ctypes.data, g.ctypes.data,
+                                                ctypes.addressof(reduction)))
+        return limited.reshape(shape), g, float(reduction.value)
+
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
                            pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None, stems=False, meters=False, true_peak=False,
-                           loudness=None, true_peak_max=-1.0):
+                           loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -645,9 +700,15 @@ class Context:
         loudness (a finite number of LUFS; implies true_peak; with a format, normalise 0) and true_peak_max (dBTP, at most 0): the
         frames of every signal are encoded under ONE gain that brings the MIX to that loudness unless the largest true peak of any
         signal would then exceed the ceiling (mix.loudness_gain; wav.encode_at_level has the bytes); the dict gains gain (a float) and
-        level (numpy.float32)."""
+        level (numpy.float32).
+        limiter=True (with loudness) and limiter_window (seconds, default 0.005; at most 4096 samples): where the largest true peak
+        lies above the ceiling seen from the target, every delivered signal is first limited under ONE look-ahead gain curve
+        (dusp_render_host_score_piece_limiter; mix.deliver_limited is the contract), and what the call returns — the meters, the
+        peaks, gain and level — then describes the limited signals; the dict gains limiter, a dict of engaged, threshold, window (in
+        samples), reduction, lufs_in and true_peak_in."""
         stems, meters, true_peak = check_stems(stems), check_meters(meters), check_true_peak(true_peak)
         loudness, true_peak_max = check_loudness(loudness, true_peak_max, normalise, format is not None)
+        window = check_limiter(limiter, limiter_window, loudness, parts[0][0].sample_rate if parts else 1)
         true_peak = true_peak or loudness is not None
         meters = meters or true_peak
         if tracks is not None:
@@ -723,6 +784,13 @@ class Context:
                 asked_loud = ScoreLoudness(int(loudness is not None), 0.0 if loudness is None else loudness, true_peak_max, got["true_peak"].ctypes.data, ctypes.addressof(gain),
                                            ctypes.addressof(level))
                 entry, loud = self._L.dusp_render_host_score_piece_loudness, (ctypes.addressof(asked_loud),)
+                if window:  # (... and one more)
+                    if not hasattr(self._L, "dusp_render_host_score_piece_limiter"):
+                        raise DuspHipError(-3, "dusp-hip: this library has no limiter (dusp_render_host_score_piece_limiter is missing)")
+                    engaged, did = ctypes.c_int(0), (ctypes.c_double * 4)(0.0, 1.0, 0.0, 0.0)
+                    at = ctypes.addressof(did)
+                    asked_limiter = ScoreLimiter(window, ctypes.addressof(engaged), at, at + 8, at + 16, at + 24)
+                    entry, loud = self._L.dusp_render_host_score_piece_limiter, loud + (ctypes.addressof(asked_limiter),)
             if stems:
                 if format is None:
                     fmt, normalise, out = 0, 0, self.host_empty((n_signals, n_ch, n_total_samples), pinned)
@@ -736,6 +804,8 @@ class Context:
                               ctypes.addressof(asked) if stems else None, ctypes.addressof(want), *loud, n_total_samples, int(tile_bytes), fmt, normalise, out.ctypes.data, _ptr(peak)))
             if loudness is not None:
                 got["gain"], got["level"] = float(gain.value), np.float32(level.value)
+            if window:
+                got["limiter"] = dict(engaged=bool(engaged.value), threshold=float(did[0]), window=window, reduction=float(did[1]), lufs_in=float(did[2]), true_peak_in=float(did[3]))
             return ((out, peak) if stems else out if peak is None else (out, peak[0])), got
         if stems:
             n_signals = 1 + (tracks["n_tracks"] if tracks is not None else 0) + (len(buses) if buses is not None else 0) + 1

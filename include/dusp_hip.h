@@ -812,7 +812,7 @@ int dusp_true_peak_host(dusp_ctx *ctx, const float *h_planar, size_t n_signals, 
  * and every signal's frames are what dusp_encode_device makes of it with `level` as its peak under DUSP_NORMALISE_FULL: ONE gain for all
  * signals, so the files still add up and none exceeds the ceiling.  The gain is unity (gain 1, level 1.0f: the samples stay as they
  * are) where lufs is -inf or NaN, where tp is 0, NaN or Inf, and where level comes out zero, subnormal or not finite.  The ceiling only
- * lowers the gain: there is no limiter.  h_peaks stay the sample peaks.  deliver = 1 waits for the stream once between the meters and
+ * lowers the gain: this entry has no limiter (the _limiter entry below).  h_peaks stay the sample peaks.  deliver = 1 waits for the stream once between the meters and
  * the encode; deliver = 0 waits no more than the _meters entry and delivers its bytes.  loudness NULL: that entry under this entry's
  * name.  Refused before anything renders, behind every refusal of that entry, each in its own words: NULL h_true_peak; deliver without
  * meters, with format 0 or with normalise != 0; a target that is not finite; a ceiling that is not finite or above 0; a sample rate
@@ -830,6 +830,59 @@ int dusp_render_host_score_piece_loudness(const dusp_score_part *parts, size_t n
                                           const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems,
                                           const dusp_score_meters *meters, const dusp_score_loudness *loudness, size_t n_total_samples,
                                           size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks);
+
+/* The limiter of a delivery at a loudness target: a linked look-ahead true-peak limiter on the device (additions to ABI v7, detected by
+ * symbol; dusp_amd/mix.py limiter_envelope, limiter_gain, limit and limiter_threshold are the contract).
+ * Signals are planar f32 [n_signals][n_channels][n_samples]; F, h, K as for the true peak, D = (K - 1) / 2, ONE = 2^30, T the threshold
+ * (linear, finite, above 0), L the window (1 .. 4096 samples).  The envelope: e[s] = the largest |acc_p[s + D]| over ALL rows and
+ * phases, the accumulators formed as for the true peak; one that is not finite counts as 0.  The curve: r = T / e where e > T, else 1;
+ * q = floor(r x ONE); m[j] = min(q[j .. j + L - 1]), q = ONE outside [0, n); sum[s] = m[s - L + 1] + .. + m[s], an exact integer;
+ * g[s] = (double)sum[s] / (double)(L x ONE) — so g[s] <= r[s], exactly (every minimum in the mean holds q[s]), with a linear attack
+ * and release of L samples.  Every row becomes (float)((double)x x g[s]), ONE curve for all: the signals of a call still add up.  reduction = min(g), 1
+ * exactly where nothing exceeds T (the signals then stay bit for bit).  Integer between the two divisions: two runs, and any tiling,
+ * give the same bits. */
+/* 10^(ceiling_dbtp / 20) / 10^((target_lufs - lufs) / 20): the true-peak magnitude the gain of the target brings to the ceiling.  Needs
+ * no device. */
+double dusp_limiter_threshold(double lufs, double target_lufs, double ceiling_dbtp);
+/* the samples a workgroup of both kernels owns in a call over n_samples with that window (256 x 1, 2, 4 or 8; at most 1024 above a
+ * window of 512), for tests and profiles; 0 for a call that would be refused */
+size_t dusp_limit_tile(dusp_ctx *ctx, size_t n_samples, size_t window_samples);
+/* the two kernels alone, on device pointers, IN PLACE over d_planar (4-byte aligned; rows may start on any 4-byte boundary).  Optional,
+ * NULL to leave out: d_q uint32 [n_samples], the words q; d_gain f64 [n_samples], the curve; d_smallest, one 8-byte word, the smallest
+ * sum (reduction = word / (L x ONE)).  The scratch is the context's: calls on one context are ordered on one stream.  The shapes of
+ * dusp_true_peak_device.  Timed by dusp_score_last_ms; dusp_limit_last_ms has the two kernels. */
+int dusp_limit_device(dusp_ctx *ctx, float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold,
+                      size_t window_samples, uint32_t *d_q, double *d_gain, uint64_t *d_smallest, void *stream);
+/* the last dusp_limit_device call kernel by kernel, by events: ms[0] the envelope kernel, ms[1] the gain / apply kernel.  Waits for the
+ * call's kernels, and then checks the guard behind the context's scratch (DUSP_GUARD), which dusp_limit_device, not waiting, cannot. */
+int dusp_limit_last_ms(dusp_ctx *ctx, float ms[2]);
+/* Host round trip: uploads h_planar, limits it and downloads h_limited (may be h_planar); h_gain f64 [n_samples] or NULL; h_reduction
+ * one double or NULL. */
+int dusp_limit_host(dusp_ctx *ctx, const float *h_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold,
+                    size_t window_samples, float *h_limited, double *h_gain, double *h_reduction);
+/* dusp_render_host_score_piece_loudness with a limiter in front of the one gain (limiter NULL: that entry under this entry's name).
+ * After the meters, the true peaks and the one wait of a delivery at a target, on the host in f64: T = dusp_limiter_threshold(lufs of
+ * the MIX, target, ceiling).  The limiter is ENGAGED where that entry's gain is not unity (level != 1.0f), T is finite and above 0 and
+ * the largest true peak of any delivered signal and channel exceeds T; otherwise nothing more is launched and the delivery is that
+ * entry's byte for byte.  Engaged: the limiter's kernels over every delivered signal, in place; the meter, true-peak and peak kernels
+ * again over the limited signals; a second wait; then that entry's gain from the SECOND measurement and its encode.  The ceiling is
+ * therefore held by the static gain as before; the delivered loudness is the target less what limiting took from the mix.  What the
+ * call hands back then describes the LIMITED signals: the meters, h_true_peak, h_peaks, h_gain, h_level.  Refused behind every refusal
+ * of that entry, each in its own words: a limiter without a loudness record with deliver = 1; a window of 0 or above 4096. */
+typedef struct dusp_score_limiter {
+    size_t window_samples; /* L, 1 .. 4096 */
+    int *h_engaged;        /* each 1 value, may be NULL: whether the limiter ran ... */
+    double *h_threshold;   /* ... T ... */
+    double *h_reduction;   /* ... min(g), 1 when not engaged ... */
+    double *h_lufs_in;     /* ... the loudness of the mix in front of the limiter ... */
+    double *h_true_peak_in; /* ... and the largest true peak in front of it */
+} dusp_score_limiter;
+int dusp_render_host_score_piece_limiter(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                         const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                         const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                         const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems,
+                                         const dusp_score_meters *meters, const dusp_score_loudness *loudness, const dusp_score_limiter *limiter,
+                                         size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks);
 
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's

@@ -54,6 +54,11 @@
           signals, beside the peak kernel and the meter passes; then the piece with stems as s16 frames with meters=True,
           normalise=2, with true_peak=True and with loudness=-16, and without any new option — the only leg under DUSP_HIP_LIB
           naming the parent's library.  A report: no ratio is fixed in advance.
+  limiter (--limiter; profiles/score_limiter.txt) the limiter's two kernels (dusp_limit_device, kernel by kernel by HIP events:
+          dusp_limit_last_ms) over the same twelve signals with a window of 240 samples: the envelope kernel beside
+          the true-peak kernel, the gain / apply kernel beside the peak kernel; then the piece with stems as s16 frames at a
+          loudness target with the limiter engaged, with the limiter not engaged, and without it — the only leg under DUSP_HIP_LIB
+          naming the parent's library.  A report: no ratio is fixed in advance.
 
 Every variant is timed `--reps` times after a warm-up call; lines give the median and the fastest.
 """
@@ -796,6 +801,120 @@ def loudness(scale, ctxs, reps):
     prog.close()
 
 
+def limiter(scale, ctxs, reps):
+    """--limiter: the limiter's envelope kernel beside the true-peak kernel and its gain / apply kernel beside the peak
+    kernel over the same block, at a window of 5 ms and at the longest window; the call with stems and s16 frames at a loudness target
+    with the limiter engaged and not engaged beside the same call without it, which under DUSP_HIP_LIB naming the parent's library is
+    the only leg that runs."""
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR // (1 if scale == 1 else 8)
+    T, B = 8, 2
+    S = 1 + T + B
+    d.configure(SR)
+    ctx = ctxs["default"]
+    has = hasattr(ctx._L, "dusp_limit_device")
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    three = lambda xs: (float(np.median(xs)), min(xs), max(xs))
+    line = "  %-78s median %8.3f ms  fastest %8.3f  slowest %8.3f%s"
+    for C in ((1, 2) if has else ()):
+        source = torch.randn((S + 1, C, nt), dtype=torch.float32, device="cuda") * 0.1
+        block, peaks, words = source.clone(), torch.empty(S + 1, dtype=torch.float32, device="cuda"), torch.empty((S + 1, C), dtype=torch.int64, device="cuda")
+        word = torch.zeros(1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        print("limiter: %d signals of %d channel(s) of %d samples (%.0f MB) at %d Hz, F = 4; kernels alone by HIP events, median, fastest and slowest of %d after a warm-up"
+              % (S + 1, C, nt, block.numel() * 4 / 1e6, SR, reps), flush=True)
+        tp, peak = [], []
+        for r in range(reps + 1):
+            ctx.true_peak_device(source.data_ptr(), S + 1, C, nt, SR, words.data_ptr(), stream=s)
+            if r:
+                tp.append(ctx.score_last_ms()[0])
+        for r in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(stream):
+                e0.record()
+                ctx.peak(source.data_ptr(), S + 1, C, nt, peaks.data_ptr(), stream=s)
+                e1.record()
+            e1.synchronize()
+            if r:
+                peak.append(e0.elapsed_time(e1))
+        print(line % (("dusp_true_peak_kernel<4> over the block (the same f64 work, no division)",) + three(tp) + ("",)), flush=True)
+        print(line % (("dusp_pcm_peak_kernel over the block (reads it once)",) + three(peak) + ("",)), flush=True)
+        threshold = 0.2  # (two standard deviations of the noise: a few samples in a hundred lie above it)
+        for L in (240, 4096):
+            envelope, apply, first = [], [], None
+            for r in range(reps + 1):
+                with torch.cuda.stream(stream):
+                    block.copy_(source)  # (the limiter works in place: every run limits the same signals)
+                ctx.limit_device(block.data_ptr(), S + 1, C, nt, SR, threshold, L, d_smallest=word.data_ptr(), stream=s)
+                if r:
+                    ms = ctx.limit_last_ms()
+                    envelope.append(ms[0]), apply.append(ms[1])
+                if first is None:
+                    with torch.cuda.stream(stream):
+                        first = block.clone()
+                stream.synchronize()
+            flops = 2.0 * 52 * block.numel()
+            print("  window %d samples, tiles of %d samples, reduction %.4f, two runs the same bits: %s" % (L, ctx.limit_tile(nt, L), int(word.item()) / float(L * (1 << 30)), bool(torch.equal(first, block))),
+                  flush=True)
+            print(line % (("  dusp_limit_envelope_kernel<4>",) + three(envelope) +
+                          ("   %.1f TFLOP/s of unfused f64; x%.2f of the true-peak kernel" % (flops / np.median(envelope) / 1e9, np.median(envelope) / np.median(tp)),)), flush=True)
+            print(line % (("  dusp_limit_apply_kernel (reads and writes the block once)",) + three(apply) +
+                          ("   %.0f GB/s moved; x%.2f of the peak kernel" % (2 * block.numel() * 4 / np.median(apply) / 1e6, np.median(apply) / np.median(peak)),)), flush=True)
+        del source, block, peaks, words
+    # the whole call: stems' piece — eight fader groups, two stateless buses (a gain each), no master — at one channel, and panned into two
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    prog = ctx.build(uni.words)
+    buses = [ctx.build(descriptor.extract(d.Multiply(d.MasterInput(), g)).words) for g in (0.5, 0.25)]
+    track_of = (np.arange(V) % T).astype(np.int32)
+    rs = np.random.RandomState(4)
+    faders, levels = rs.random_sample(T).astype(np.float32), rs.random_sample((B, T)).astype(np.float32)
+
+    def call(**kw):
+        return ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, buses=[(b, None) for b in buses],
+                                      tracks=dict(n_tracks=T, track_of=track_of, programs=[], faders=faders, track_sends=levels), stems=True, **kw)
+
+    def host_clock(run):
+        times = []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = run()
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+        return three(times[1:])
+
+    row = "  render_score_parts with stems, %-66s median %9.2f ms  fastest %9.2f  slowest %9.2f%s"
+    print("  %d notes of %d samples over %d samples, %d signals, into pinned memory, host clock, median, fastest and slowest of %d after a warm-up; library: %s"
+          % (V, nv, nt, S + 1, reps, "another build's, named by DUSP_HIP_LIB" if os.environ.get("DUSP_HIP_LIB") else "this tree's"), flush=True)
+    window = 240.0 / SR
+    for name, kw in (("one channel", {}), ("two channels (pans)", dict(pans=np.linspace(-1, 1, V)))):
+        frames = host_clock(lambda: call(format="s16", normalise=2, **kw))
+        print(row % ((name + ", s16, normalise=2, no new option",) + frames + ("",)), flush=True)
+        loud = host_clock(lambda: call(format="s16", loudness=-16.0, **kw))
+        print(row % ((name + ", s16, loudness=-16",) + loud + ("",)), flush=True)
+        _, got = call(format="s16", loudness=-16.0, **kw)
+        # a target 6 dB above the one at which the largest true peak meets the ceiling: the limiter engages; 12 dB below that: it does not
+        meets = got["lufs"][-1] + 20 * np.log10(10 ** (-1 / 20) / got["true_peak"].max())
+        high, low = float(meets + 6.0), float(meets - 6.0)
+        for target in (low, high):
+            there = host_clock(lambda: call(format="s16", loudness=target, **kw))
+            print(row % ((name + ", s16, loudness=%.2f" % target,) + there + ("",)), flush=True)
+            if has:
+                limited = host_clock(lambda: call(format="s16", loudness=target, limiter=True, limiter_window=window, **kw))
+                _, did = call(format="s16", loudness=target, limiter=True, limiter_window=window, **kw)
+                print(row % ((name + ", s16, loudness=%.2f, limiter=True: %s" % (target, "engaged" if did["limiter"]["engaged"] else "not engaged"),) + limited +
+                             ("   +%.2f ms, x%.3f of the call without" % (limited[0] - there[0], limited[0] / there[0]),)), flush=True)
+                print("    threshold %.4f against a largest true peak of %.4f, reduction %.4f; gain %.4f, the mix leaves at %.2f LUFS, the largest true peak at %.2f dBTP"
+                      % (did["limiter"]["threshold"], did["limiter"]["true_peak_in"], did["limiter"]["reduction"], did["gain"], did["lufs"][-1] + 20 * np.log10(did["gain"]),
+                         20 * np.log10(did["true_peak"].max() * did["gain"])), flush=True)
+    for b in buses:
+        b.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -811,6 +930,7 @@ def main():
     ap.add_argument("--stems", action="store_true", help="the stems leg alone: the stems mix and return kernels beside the kernels they extend, and the piece with and without stems")
     ap.add_argument("--meters", action="store_true", help="the meters leg alone: the meter kernels pass by pass beside the peak kernel, and the piece with stems with and without meters")
     ap.add_argument("--loudness", action="store_true", help="the loudness leg alone: the true-peak kernel beside the peak kernel and the meter passes, and the piece with stems delivered at a loudness target")
+    ap.add_argument("--limiter", action="store_true", help="the limiter leg alone: its two kernels beside the true-peak and peak kernels, and the piece with stems at a loudness target with and without the limiter")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
@@ -826,6 +946,8 @@ def main():
         return meters(a.scale, ctxs, a.reps)
     if a.loudness:
         return loudness(a.scale, ctxs, a.reps)
+    if a.limiter:
+        return limiter(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
