@@ -126,9 +126,12 @@ void dusp_ctx_destroy(dusp_ctx *ctx) {
     if (ctx->d_meter) (void)hipFree(ctx->d_meter);
     if (ctx->d_true_peak) (void)hipFree(ctx->d_true_peak);
     if (ctx->d_limit) (void)hipFree(ctx->d_limit);
+    if (ctx->d_limit_release) (void)hipFree(ctx->d_limit_release);
     for (hipEvent_t ev : ctx->meter_marks)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->limit_marks)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : ctx->limit_release_marks)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->score_uploaded) (void)hipEventDestroy(ctx->score_uploaded);
     if (ctx->score_done) (void)hipEventDestroy(ctx->score_done);

@@ -35,6 +35,7 @@
 #include "fused_plan.hpp"
 #include "jit_codegen.hpp"
 #include "limiter_plan.hpp"
+#include "limiter_release_plan.hpp"
 #include "meter_plan.hpp"
 #include "program.hpp"
 #include "score_plan.hpp"
@@ -88,6 +89,9 @@ hipError_t launch_true_peak(const float *d_planar, uint64_t rows, uint64_t n, ui
 hipError_t launch_limit_envelope(const float *d_planar, uint64_t rows, uint64_t n, uint32_t F, const TruePeakTaps &taps, double T, uint32_t L, int n_cus, uint32_t *d_q,
                                  uint64_t *d_smallest, hipStream_t stream);
 hipError_t launch_limit_apply(float *d_planar, uint64_t rows, uint64_t n, uint32_t L, int n_cus, const uint32_t *d_q, uint64_t *d_smallest, double *d_gain, hipStream_t stream);
+hipError_t launch_limit_hold(uint64_t n, uint32_t L, uint32_t R, int n_cus, const uint32_t *d_q, uint32_t *d_held, uint32_t *d_summary, hipStream_t stream);
+hipError_t launch_limit_release(uint64_t n, uint32_t L, uint32_t R, int n_cus, uint32_t *d_held, const uint32_t *d_summary, hipStream_t stream);
+hipError_t launch_limit_mean_apply(float *d_planar, uint64_t rows, uint64_t n, uint32_t L, int n_cus, const uint32_t *d_held, uint64_t *d_smallest, double *d_gain, hipStream_t stream);
 hipError_t launch_fused(const FusedPlan &plan, const FusedLaunch &L, hipStream_t stream);
 hipError_t launch_wave_engine(WaveArgs A, bool lds_table_ok, int max_waves_cap, hipStream_t stream);
 hipError_t launch_sumchain(const FusedPlan &plan, const FusedLaunch &L, const SumVoice *d_voices, int gb, hipStream_t stream);
@@ -149,6 +153,12 @@ struct dusp_ctx {
     size_t limit_cap = 0;  // samples
     hipEvent_t limit_marks[3] = {nullptr, nullptr, nullptr};  // around the two kernels of the last dusp_limit_device call
     bool limit_timed = false;
+    // the release's scratch (abi_limiter.hip; limiter_release_engine.hip): one 32-bit word a position of the held curve, n + L - 1 of
+    // them, then one summary word a tile, grown on demand
+    uint32_t *d_limit_release = nullptr;
+    size_t limit_release_cap = 0;  // words
+    hipEvent_t limit_release_marks[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // around the four kernels of the last dusp_limit_release_device call
+    bool limit_release_timed = false;
 };
 
 // DUSP_GUARD=1 (tests): every device allocation of the library carries guard bytes behind its end, filled with a pattern and
@@ -474,7 +484,11 @@ int true_peak_values(dusp_ctx *ctx, const char *who, const std::vector<uint64_t>
 // down behind what the stream holds (asynchronously: the caller waits for the stream, then calls limit_reduction, which also checks
 // the scratch's guard).  The caller has checked the shapes, threshold and L (limit_check)
 int limit_check(dusp_ctx *ctx, const char *who, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold, size_t window_samples);
-int limit_launch(dusp_ctx *ctx, float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold, uint32_t L, hipStream_t stream);
+// (R: the release in samples; 0: none — the envelope kernel and the gain / apply kernel, as before there was a release.  Else the
+// envelope kernel, then the hold, release and mean / apply kernels of limiter_release_engine.hip; limit_reduction then checks the
+// release's scratch too)
+int limit_launch(dusp_ctx *ctx, float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold, uint32_t L, hipStream_t stream,
+                 uint32_t R = 0);
 int limit_download(dusp_ctx *ctx, uint64_t *h_smallest, hipStream_t stream);
 int limit_reduction(dusp_ctx *ctx, const char *who, uint64_t smallest, uint32_t L, double *reduction);
 

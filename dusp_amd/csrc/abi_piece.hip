@@ -35,6 +35,7 @@ struct PieceCall {
     const dusp_score_meters *meters = nullptr;  // ..._meters
     const dusp_score_loudness *loud = nullptr;  // ..._loudness: the true peak of every delivered (signal, channel), and with deliver the one gain
     const dusp_score_limiter *limiter = nullptr;  // ..._limiter: the delivered signals limited to the ceiling in front of that gain
+    size_t release = 0;                           // ..._limiter_release: the limiter's release in samples (0: none of its own)
 
     dusp_program *prog0() const { return parts[0].prog; }  // (its buffers hold what belongs to the piece: the timeline, the gains, the encoded frames)
     dusp_ctx *ctx() const { return parts[0].prog->ctx; }
@@ -380,6 +381,7 @@ static int piece_check_limiter(const PieceCall &call) {
     if (!call.loud || !call.loud->deliver) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + dusp::kLimiterNeedsDeliver);
     if (limiter->window_samples < 1 || limiter->window_samples > dusp::kLimiterWindowMax)
         CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + dusp::kLimiterWindowRange + std::to_string(limiter->window_samples));
+    if (call.release > dusp::kLimiterReleaseMax) CTX_FAIL(ctx, DUSP_ERR_ARG, w + ": " + dusp::kLimiterReleaseRange + std::to_string(call.release));
     return DUSP_OK;
 }
 
@@ -581,7 +583,7 @@ static int piece_render(const PieceCall &call, const PieceFacts &F, const PieceT
 // words, smallest: where the true peaks' words and the limiter's smallest sum come down, asynchronously — the CALLER's (deliver_metered),
 // who waits for the stream before they go out of scope where a step in between has failed
 static int deliver_metered_steps(dusp_program *prog, const char *who, const dusp_score_meters *meters, const dusp_score_loudness *loud, const dusp_score_limiter *limiter,
-                                 uint32_t sample_rate, float *d_block, size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise, float *h_peaks, void *h_out,
+                                 uint32_t release, uint32_t sample_rate, float *d_block, size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise, float *h_peaks, void *h_out,
                                  bool common_peak, std::vector<uint64_t> &words, uint64_t &smallest) {
     dusp_ctx *ctx = prog->ctx;
     const bool at_target = loud && loud->deliver;
@@ -609,7 +611,7 @@ static int deliver_metered_steps(dusp_program *prog, const char *who, const dusp
         }
         if (engaged) {
             const uint32_t L = (uint32_t)limiter->window_samples;
-            if (int rc = limit_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, threshold, L, ctx->stream)) return rc;
+            if (int rc = limit_launch(ctx, d_block, n_signals, n_ch, n_total, sample_rate, threshold, L, ctx->stream, release)) return rc;  // (with a release of its own)
             if (int rc = limit_download(ctx, &smallest, ctx->stream)) return rc;
             if (int rc = measure()) return rc;  // (the limited block; its wait is the download's too)
             if (int rc = limit_reduction(ctx, who, smallest, L, &reduction)) return rc;
@@ -644,11 +646,12 @@ static int deliver_metered_steps(dusp_program *prog, const char *who, const dusp
     return DUSP_OK;
 }
 
-static int deliver_metered(dusp_program *prog, const char *who, const dusp_score_meters *meters, const dusp_score_loudness *loud, const dusp_score_limiter *limiter, uint32_t sample_rate,
+static int deliver_metered(dusp_program *prog, const char *who, const dusp_score_meters *meters, const dusp_score_loudness *loud, const dusp_score_limiter *limiter, uint32_t release,
+                           uint32_t sample_rate,
                            float *d_block, size_t n_signals, size_t n_ch, size_t n_total, int format, int normalise, float *h_peaks, void *h_out, bool common_peak) {
     std::vector<uint64_t> words;
     uint64_t smallest = 0;
-    const int rc = deliver_metered_steps(prog, who, meters, loud, limiter, sample_rate, d_block, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak, words, smallest);
+    const int rc = deliver_metered_steps(prog, who, meters, loud, limiter, release, sample_rate, d_block, n_signals, n_ch, n_total, format, normalise, h_peaks, h_out, common_peak, words, smallest);
     if (rc) (void)hipStreamSynchronize(prog->ctx->stream);  // (a copy into `words` or `smallest` may still be on its way)
     return rc;
 }
@@ -667,7 +670,7 @@ static int piece_deliver(const PieceCall &call, const PieceFacts &F, float *d_bl
         if (call.stems)
             HIP_TRY(ctx, hipMemcpyAsync(prog0->d_stems.p + (n_signals - 1) * F.timeline, call.master->prog->d_host_out.p, F.timeline * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    return deliver_metered(prog0, call.who, call.meters, call.loud, call.limiter, F.sample_rate, d_block, n_signals, F.n_out_ch, call.n_total, call.format, call.normalise, call.h_peak, call.h_out, common_peak);
+    return deliver_metered(prog0, call.who, call.meters, call.loud, call.limiter, (uint32_t)call.release, F.sample_rate, d_block, n_signals, F.n_out_ch, call.n_total, call.format, call.normalise, call.h_peak, call.h_out, common_peak);
 }
 
 // guards, behind the delivery: the buffers of the piece that the call used, then every auxiliary program's own
@@ -877,9 +880,9 @@ static int render_host_score_piece_limiter(const char *who, const dusp_score_par
                                            const int64_t *h_lengths, const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks,
                                            const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems, const dusp_score_meters *meters,
                                            const dusp_score_loudness *loudness, const dusp_score_limiter *limiter, size_t n_total_samples, size_t tile_bytes, int format, int normalise,
-                                           void *h_out, float *h_peaks) {
+                                           void *h_out, float *h_peaks, size_t release = 0) {
     PieceCall call = piece_call(who, parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, n_total_samples, tile_bytes, format, normalise, h_out, h_peaks);
-    call.master = master, call.buses = buses, call.tracks = tracks, call.stems = stems, call.meters = meters, call.loud = loudness, call.limiter = limiter;
+    call.master = master, call.buses = buses, call.tracks = tracks, call.stems = stems, call.meters = meters, call.loud = loudness, call.limiter = limiter, call.release = release;
     return render_host_score_piece(call, placement);
 }
 
@@ -897,6 +900,17 @@ int dusp_render_host_score_piece_limiter(const dusp_score_part *parts, size_t n_
                                          const dusp_score_limiter *limiter, size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks) {
     return render_host_score_piece_limiter("dusp_render_host_score_piece_limiter", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, tracks, buses, master, stems,
                                            meters, loudness, limiter, n_total_samples, tile_bytes, format, normalise, h_out, h_peaks);
+}
+
+// ... and with a release of the limiter's own (release_samples = 0, or limiter NULL: the entry above under this entry's name)
+int dusp_render_host_score_piece_limiter_release(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of, const int64_t *h_onsets,
+                                                 const int64_t *h_lengths, const float *h_gains, const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                                 const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems, const dusp_score_meters *meters,
+                                                 const dusp_score_loudness *loudness, const dusp_score_limiter_release *limiter, size_t n_total_samples, size_t tile_bytes, int format,
+                                                 int normalise, void *h_out, float *h_peaks) {
+    return render_host_score_piece_limiter("dusp_render_host_score_piece_limiter_release", parts, n_parts, n_voices, h_part_of, h_onsets, h_lengths, h_gains, placement, tracks, buses, master,
+                                           stems, meters, loudness, limiter ? &limiter->limiter : nullptr, n_total_samples, tile_bytes, format, normalise, h_out, h_peaks,
+                                           limiter ? limiter->release_samples : 0);
 }
 
 }  // extern "C"

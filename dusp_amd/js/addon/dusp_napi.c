@@ -28,6 +28,8 @@
  *         -> Promise<{ ..., limiter: { engaged, threshold, window, reduction, lufsIn, truePeakIn } }>: the same with deliver true, the delivered
  *            signals limited to the ceiling in front of the one gain where the largest true peak lies above it
  *            (dusp_render_host_score_piece_limiter); what the call hands back then describes the limited signals
+ *   renderPieceLimiterRelease(the same thirty-seven, releaseSamples)
+ *         -> the same, the limiter with a release of its own (dusp_render_host_score_piece_limiter_release; 0: renderPieceLimiter); limiter has release
  *   limit(ctx, Float32Array planar, nSignals, nChannels, nSamples, sampleRate, threshold, windowSamples)
  *         -> { data: Float32Array, gain: Float64Array [nSamples], reduction }: signals in host memory limited under ONE look-ahead gain curve
  *            (dusp_limit_host)
@@ -809,6 +811,7 @@ typedef struct {
     float l_level;                /* ... and the level it came from */
     int with_limiter, lim_engaged; /* renderPieceLimiter (dusp_render_host_score_piece_limiter): renderPieceLoudness with a limiter in front of the gain: */
     size_t lim_window;            /* ... its window in samples, */
+    size_t lim_release;           /* ... renderPieceLimiterRelease (dusp_render_host_score_piece_limiter_release): its release in samples, 0 without one, */
     double lim_threshold, lim_reduction, lim_lufs_in, lim_tp_in; /* ... and what it did */
     int format, normalise, rc;
     char err[512];
@@ -903,7 +906,12 @@ static void piece_execute(napi_env env, void *data) {
             dusp_score_meters meters = {j->n_signals, j->n_blocks, j->m_rms, j->m_lufs, j->m_momentary};
             dusp_score_loudness loud = {j->deliver, j->target, j->ceiling, j->m_tp, &j->l_gain, &j->l_level};
             dusp_score_limiter limiter = {j->lim_window, &j->lim_engaged, &j->lim_threshold, &j->lim_reduction, &j->lim_lufs_in, &j->lim_tp_in};
-            if (j->with_limiter)
+            dusp_score_limiter_release released = {limiter, j->lim_release};
+            if (j->with_limiter && j->lim_release)
+                j->rc = dusp_render_host_score_piece_limiter_release(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, j->with_tracks ? &tracks : NULL,
+                                                                     j->n_buses ? &buses : NULL, j->master_pb ? &master : NULL, j->stems_asked ? &stems : NULL, &meters, &loud, &released,
+                                                                     j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->peaks);
+            else if (j->with_limiter)
                 j->rc = dusp_render_host_score_piece_limiter(j->parts, j->n_parts, j->n_voices, j->part_of, j->onsets, j->lengths, j->gains, &place, j->with_tracks ? &tracks : NULL,
                                                              j->n_buses ? &buses : NULL, j->master_pb ? &master : NULL, j->stems_asked ? &stems : NULL, &meters, &loud, &limiter,
                                                              j->n_total, j->tile_bytes, j->format, j->normalise, j->out, j->peaks);
@@ -1003,10 +1011,10 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
             }
             if (j->with_limiter && ok) { /* ... and limiter: what the limiter did */
                 napi_value box, v;
-                const char *names[5] = {"threshold", "window", "reduction", "lufsIn", "truePeakIn"};
-                const double values[5] = {j->lim_threshold, (double)j->lim_window, j->lim_reduction, j->lim_lufs_in, j->lim_tp_in};
+                const char *names[6] = {"threshold", "window", "reduction", "lufsIn", "truePeakIn", "release"};
+                const double values[6] = {j->lim_threshold, (double)j->lim_window, j->lim_reduction, j->lim_lufs_in, j->lim_tp_in, (double)j->lim_release};
                 ok = napi_create_object(env, &box) == napi_ok && napi_get_boolean(env, j->lim_engaged != 0, &v) == napi_ok && napi_set_named_property(env, box, "engaged", v) == napi_ok;
-                for (int m = 0; m < 5 && ok; m++) ok = napi_create_double(env, values[m], &v) == napi_ok && napi_set_named_property(env, box, names[m], v) == napi_ok;
+                for (int m = 0; m < 6 && ok; m++) ok = napi_create_double(env, values[m], &v) == napi_ok && napi_set_named_property(env, box, names[m], v) == napi_ok;
                 ok = ok && napi_set_named_property(env, result, "limiter", box) == napi_ok;
             }
         }
@@ -1077,15 +1085,16 @@ static void piece_complete(napi_env env, napi_status status, void *data) {
  *      1 + nTracks + nBuses + 1 signals one behind the other (a Float32Array of planar f32, or a Buffer of frames under ONE gain), the mix last, peaks a
  *      Float32Array of every signal's own peak */
 static napi_value render_piece_call(napi_env env, napi_callback_info info, int form) { /* form: 0 plain, 1 panned, 2 with fractions, 3 in a space, 4 stereo, 5 any of them, with a master, 6 ... and buses */
-    napi_value argv[37];
+    napi_value argv[38];
     char msg[256];
-    const int with_limiter = form == 11; /* (renderPieceLimiter: renderPieceLoudness' arguments, then the window in samples) */
+    const int with_release = form == 12; /* (renderPieceLimiterRelease: renderPieceLimiter's arguments, then the release in samples) */
+    const int with_limiter = form == 11 || with_release; /* (renderPieceLimiter: renderPieceLoudness' arguments, then the window in samples) */
     const int with_loud = form == 10 || with_limiter; /* (renderPieceLoudness: renderPieceMeters' arguments, then deliver, the target and the ceiling) */
     const int with_meters = form == 9 || with_loud; /* (renderPieceMeters: renderPieceStems' arguments, then whether the stems are asked for and the blocks of the timeline) */
     const int with_stems = form == 8 || with_meters; /* (renderPieceStems: renderPieceTracks' arguments, the tracks among them or not) */
     int with_tracks = form == 7;
     if (with_tracks || with_stems) form = 6;
-    if (!get_args(env, info, with_limiter ? 37 : with_loud ? 36 : with_meters ? 33 : with_tracks || with_stems ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
+    if (!get_args(env, info, with_release ? 38 : with_limiter ? 37 : with_loud ? 36 : with_meters ? 33 : with_tracks || with_stems ? 31 : form == 6 ? 24 : form == 5 ? 21 : form >= 2 ? 15 : form == 1 ? 14 : 12, argv)) return NULL;
     if (with_stems) { /* (nTracks 0: a call without tracks) */
         double n_tracks = 0;
         with_tracks = napi_get_value_double(env, argv[24], &n_tracks) != napi_ok || n_tracks != 0;
@@ -1416,6 +1425,13 @@ static napi_value render_piece_call(napi_env env, napi_callback_info info, int f
         else
             j->lim_window = (size_t)window;
     }
+    if (with_release) { /* (the library refuses a release above 2^22; 0: the call without one) */
+        double release = -1;
+        if (napi_get_value_double(env, argv[37], &release) != napi_ok || !(release >= 0 && release <= 4294967295.0) || release != (double)(size_t)release)
+            bad = bad ? bad : "releaseSamples is a whole number";
+        else
+            j->lim_release = (size_t)release;
+    }
     j->n_signals = j->stems_asked ? 1 + j->n_tracks + j->n_buses + 1 : 1;
     j->n_channels = (size_t)n_channels;
     if (!bad && with_loud && !(j->m_tp = (double *)calloc(j->n_signals * j->n_channels + 1, sizeof(double)))) bad = "out of host memory for the true peaks";
@@ -1532,18 +1548,19 @@ static napi_value fn_meter(napi_env env, napi_callback_info info) {
 }
 
 static napi_value fn_render_piece_limiter(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 11); }
+static napi_value fn_render_piece_limiter_release(napi_env env, napi_callback_info info) { return render_piece_call(env, info, 12); }
 
 /* limit(ctx, planar, nSignals, nChannels, nSamples, sampleRate, threshold, windowSamples) -> { data, gain, reduction }: f32 signals in host memory
  * limited on the device under ONE look-ahead gain curve (dusp_limit_host): data a Float32Array of planar's layout, gain a Float64Array [nSamples],
  * reduction the smallest gain.  Throws the library's message. */
-static napi_value fn_limit(napi_env env, napi_callback_info info) {
-    napi_value argv[8];
-    if (!get_args(env, info, 8, argv)) return NULL;
+static napi_value limit_call(napi_env env, napi_callback_info info, int with_release) {
+    napi_value argv[9];
+    if (!get_args(env, info, with_release ? 9 : 8, argv)) return NULL;
     ctx_box *b = as_ctx(env, argv[0]);
     if (!b) return NULL;
     void *data, *mem, *gain_mem;
     size_t len;
-    double dims[4] = {0, 0, 0, 0}, threshold = 0, window = 0;
+    double dims[4] = {0, 0, 0, 0}, threshold = 0, window = 0, release = 0;
     for (int i = 0; i < 4; i++) napi_get_value_double(env, argv[2 + i], &dims[i]);
     for (int i = 0; i < 4; i++)
         if (!(dims[i] >= 1 && dims[i] <= 4294967295.0) || dims[i] != (double)(size_t)dims[i]) {
@@ -1553,6 +1570,10 @@ static napi_value fn_limit(napi_env env, napi_callback_info info) {
     if (napi_get_value_double(env, argv[6], &threshold) != napi_ok || napi_get_value_double(env, argv[7], &window) != napi_ok || !(window >= 0 && window <= 4294967295.0) ||
         window != (double)(size_t)window) {
         throw_string(env, "dusp-hip: limit: threshold is a number and windowSamples a whole number");
+        return NULL;
+    }
+    if (with_release && (napi_get_value_double(env, argv[8], &release) != napi_ok || !(release >= 0 && release <= 4294967295.0) || release != (double)(size_t)release)) {
+        throw_string(env, "dusp-hip: limit: releaseSamples is a whole number");
         return NULL;
     }
     const size_t n_signals = (size_t)dims[0], n_channels = (size_t)dims[1], n_samples = (size_t)dims[2];
@@ -1567,7 +1588,9 @@ static napi_value fn_limit(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_create_arraybuffer(env, n_samples * sizeof(double), &gain_mem, &gain_ab));
     NAPI_OK(napi_create_typedarray(env, napi_float64_array, n_samples, gain_ab, 0, &gain));
     pthread_mutex_lock(&b->lock);
-    int rc = dusp_limit_host(b->ctx, (const float *)data, n_signals, n_channels, n_samples, (uint32_t)dims[3], threshold, (size_t)window, (float *)mem, (double *)gain_mem, &reduction);
+    int rc = with_release ? dusp_limit_release_host(b->ctx, (const float *)data, n_signals, n_channels, n_samples, (uint32_t)dims[3], threshold, (size_t)window, (size_t)release, (float *)mem,
+                                                    (double *)gain_mem, &reduction)
+                          : dusp_limit_host(b->ctx, (const float *)data, n_signals, n_channels, n_samples, (uint32_t)dims[3], threshold, (size_t)window, (float *)mem, (double *)gain_mem, &reduction);
     char msg[512];
     if (rc != DUSP_OK) snprintf(msg, sizeof msg, "dusp-hip: %s", dusp_last_error(b->ctx));
     pthread_mutex_unlock(&b->lock);
@@ -1582,6 +1605,9 @@ static napi_value fn_limit(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_set_named_property(env, result, "reduction", reduced));
     return result;
 }
+static napi_value fn_limit(napi_env env, napi_callback_info info) { return limit_call(env, info, 0); }
+/* limitRelease(the same eight, releaseSamples): limit with a release of its own, 1 .. 2^22 samples (dusp_limit_release_host) */
+static napi_value fn_limit_release(napi_env env, napi_callback_info info) { return limit_call(env, info, 1); }
 
 /* truePeak(ctx, planar, nSignals, nChannels, nSamples, sampleRate) -> Float64Array [nSignals * nChannels]: the true peaks of f32 signals in
  * host memory, on the device, linear (dusp_true_peak_host).  Throws the library's message. */
@@ -1655,6 +1681,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderPieceBuses", fn_render_piece_buses}, {"renderPieceTracks", fn_render_piece_tracks}, {"renderPieceStems", fn_render_piece_stems},
         {"renderPieceMeters", fn_render_piece_meters}, {"meter", fn_meter}, {"renderPieceLoudness", fn_render_piece_loudness}, {"truePeak", fn_true_peak},
         {"renderPieceLimiter", fn_render_piece_limiter}, {"limit", fn_limit},
+        {"renderPieceLimiterRelease", fn_render_piece_limiter_release}, {"limitRelease", fn_limit_release},
     };
     for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
         napi_value f;

@@ -458,11 +458,11 @@ function wholeSamples(who, name, values, count) {
  * buses, sends: as renderPiece's — per-voice send levels into effect buses beside the mix — through the piece's call too.
  * stems: true — as renderPiece's: the direct mix, every track and every bus return beside the mix — through the piece's call too.
  * meters: true — as renderPiece's: the RMS and the BS.1770 loudness of every signal the call delivers — through the piece's call too.
- * truePeak: true, and on the Pcm / Wav forms loudness, truePeakMax, limiter, limiterWindow — as renderPiece's — through the piece's call too. */
+ * truePeak: true, and on the Pcm / Wav forms loudness, truePeakMax, limiter, limiterWindow, limiterRelease — as renderPiece's — through the piece's call too. */
 const given = (x) => x !== undefined && x !== null
 const asPiece = (opts) => given(opts.pans) || given(opts.fracs) || given(opts.places) || opts.stereo === true || given(opts.master) || given(opts.buses) || given(opts.sends) ||
   given(opts.tracks) || given(opts.trackOf) || given(opts.faders) || given(opts.trackSends) || (opts.stems !== undefined && opts.stems !== false) ||
-  (opts.meters !== undefined && opts.meters !== false) || (opts.truePeak !== undefined && opts.truePeak !== false) || given(opts.loudness) || (opts.limiter !== undefined && opts.limiter !== false)
+  (opts.meters !== undefined && opts.meters !== false) || (opts.truePeak !== undefined && opts.truePeak !== false) || given(opts.loudness) || (opts.limiter !== undefined && opts.limiter !== false) || given(opts.limiterRelease)
 
 function scoreAsPiece(opts) { // renderScore with pans, fracs or places: the piece's call with the score as its one part
   return Object.assign({}, opts, { voiceDurations: opts.voiceDuration === undefined ? 1 : opts.voiceDuration, tileBytes: 0 })
@@ -925,7 +925,12 @@ const LIMITER = {
   windowBad: "dusp-hip: limiter_window is a finite positive number of seconds (default 0.005), the limiter's look-ahead, attack and release",
   windowLong: (samples, sampleRate) => 'dusp-hip: limiter_window is ' + samples + ' samples at ' + sampleRate + " Hz: the limiter's window is at most 4096 samples",
   threshold: "dusp-hip: the limiter's threshold is a finite number above 0, linear",
-  windowSamples: "dusp-hip: the limiter's window is a whole number of samples, 1 .. 4096"
+  windowSamples: "dusp-hip: the limiter's window is a whole number of samples, 1 .. 4096",
+  // (DESIGN.md 6.21: LIMITER_RELEASE_BAD, LIMITER_RELEASE_NEEDS_LIMITER, LIMITER_RELEASE_LONG, LIMITER_RELEASE_SAMPLES; check_limiter_release)
+  releaseBad: "dusp-hip: limiter_release is None or a finite positive number of seconds, the time the limiter's gain takes from 0 back to 1",
+  releaseNeedsLimiter: "dusp-hip: limiter_release without limiter=True: a release is the limiter's",
+  releaseLong: (samples, sampleRate) => 'dusp-hip: limiter_release is ' + samples + ' samples at ' + sampleRate + " Hz: the limiter's release is at most 4194304 samples",
+  releaseSamples: "dusp-hip: the limiter's release is a whole number of samples, 1 .. 4194304"
 }
 function checkLimiterBool(limiter) {
   if (limiter === undefined) return false
@@ -945,6 +950,20 @@ function checkLimiter(limiter, limiterWindow, target, sampleRate) {
   const L = Math.max(1, rounded)
   if (L > 4096) throw LIMITER.windowLong(L, sampleRate)
   return L
+}
+/* limiterRelease: of a call with that limiter (a boolean already) at that sample rate -> the release in samples, 0 without one:
+ * max(1, round(seconds x sampleRate)), halves to the even number as Python's round (twin of mix.py check_limiter_release) */
+function checkLimiterRelease(limiterRelease, limiter, sampleRate) {
+  if (!given(limiterRelease)) return 0
+  const r = limiterRelease
+  if (typeof r !== 'number' || !Number.isFinite(r) || !(r > 0)) throw LIMITER.releaseBad
+  if (!limiter) throw LIMITER.releaseNeedsLimiter
+  const exact = r * sampleRate
+  if (exact > 2 * 4194304) throw LIMITER.releaseLong(BigInt(Math.min(Math.trunc(exact), 2 ** 62)).toString(), sampleRate)
+  const down = Math.floor(exact), rounded = exact - down > 0.5 || (exact - down === 0.5 && down % 2 === 1) ? down + 1 : down
+  const R = Math.max(1, rounded)
+  if (R > 4194304) throw LIMITER.releaseLong(R, sampleRate)
+  return R
 }
 function checkTruePeak(truePeak) {
   if (truePeak === undefined) return false
@@ -1023,20 +1042,23 @@ function truePeak(channelData, sampleRate) {
 /* The linked look-ahead limiter over any signals a user has (twin of render.py limit): channelData as meter takes it, a threshold (linear,
  * finite, above 0) and a window of 1 .. 4096 samples -> { data, gain, reduction }: data shaped as channelData, every row multiplied by ONE
  * gain curve; gain the curve, a Float64Array [samples]; reduction its smallest value, 1 where nothing exceeds the threshold.  On the
- * device (dusp_limit_host). */
-function limit(channelData, sampleRate, threshold, window) {
+ * device (dusp_limit_host).  release: undefined, or the limiter's release of its own, 1 .. 2^22 samples (dusp_limit_release_host;
+ * DESIGN.md 6.21). */
+function limit(channelData, sampleRate, threshold, window, release) {
   const nested = channelData.length && !ArrayBuffer.isView(channelData[0])
   const signals = nested ? Array.from(channelData) : [channelData]
   const nChannels = signals[0].length, nSamples = nChannels ? signals[0][0].length : 0
   if (!(sampleRate > 0)) throw 'dusp-hip: limit: the limiter needs a sample rate: it decides the oversampling'
   if (typeof threshold !== 'number' || !Number.isFinite(threshold) || !(threshold > 0)) throw LIMITER.threshold
   if (!Number.isInteger(window) || window < 1 || window > 4096) throw LIMITER.windowSamples
+  if (given(release) && (!Number.isInteger(release) || release < 1 || release > 4194304)) throw LIMITER.releaseSamples
   if (!nChannels || signals.some((sig) => sig.length !== nChannels || Array.from(sig).some((ch) => !(ch instanceof Float32Array) || ch.length !== nSamples)))
     throw 'dusp-hip: limit: the signals are Float32Arrays of one length, the same number a signal'
   if (nSamples === 0) return { data: nested ? signals.map((sig) => Array.from(sig, () => new Float32Array(0))) : Array.from(signals[0], () => new Float32Array(0)), gain: new Float64Array(0), reduction: 1 }
   const planar = new Float32Array(signals.length * nChannels * nSamples)
   signals.forEach((sig, s) => Array.from(sig).forEach((ch, c) => planar.set(ch, (s * nChannels + c) * nSamples)))
-  const got = native().limit(contextFor(sampleRate), planar, signals.length, nChannels, nSamples, sampleRate, threshold, window)
+  const got = given(release) ? native().limitRelease(contextFor(sampleRate), planar, signals.length, nChannels, nSamples, sampleRate, threshold, window, release)
+    : native().limit(contextFor(sampleRate), planar, signals.length, nChannels, nSamples, sampleRate, threshold, window)
   const rows = signals.map((sig, s) => Array.from(sig, (ch, c) => got.data.subarray((s * nChannels + c) * nSamples, (s * nChannels + c + 1) * nSamples)))
   return { data: nested ? rows : rows[0], gain: got.gain, reduction: got.reduction }
 }
@@ -1122,9 +1144,10 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
   }
   const names = stems ? stemNames(routed ? opts.tracks.length : 0, buses ? buses.length : 0) : null
   const window = checkLimiter(limiterAsked, opts.limiterWindow, loud.target, sampleRate) // (the limiter's window in samples, 0 without one)
+  const release = checkLimiterRelease(opts.limiterRelease, limiterAsked, sampleRate) // (... and its release, 0 without one)
   if (meters && !(sampleRate >= 8000)) throw METER_RATE_LOW(sampleRate)
   const nBlocks = meterBlocks(nSamples, sampleRate)
-  const idle = { engaged: false, threshold: 0, window, reduction: 1, lufsIn: -Infinity, truePeakIn: 0 } // (a timeline of no samples)
+  const idle = { engaged: false, threshold: 0, window, reduction: 1, lufsIn: -Infinity, truePeakIn: 0, release } // (a timeline of no samples)
   const delivered = loud.target !== null ? (got) => Object.assign({ gain: got ? got.gain : 1, level: got ? got.level : 1 }, window ? { limiter: got ? got.limiter : idle } : {}) : () => null
   if (nSamples === 0) return { nSamples, nChannels, sampleRate, result: null, names, metered: meters ? metersOf(names || ['mix'], null, nChannels, 0, sampleRate, truePeaks) : null, loud: delivered(null) }
   const progs = [], busProgs = [], trackProgs = []
@@ -1136,11 +1159,11 @@ async function pieceCall(who, outlets, opts, format, normalise, onePart = false)
     const args = [progs, Float64Array.from(grouped.parts, (part) => part.uni.nInstances), Float64Array.from(grouped.parts, (part) => part.nVoiceSamples),
       grouped.parts.map((part) => (part.uni.nParams ? part.uni.params : null)), grouped.partOf, onsets, lengths, g, nSamples, tileBytes, format, normalise]
     if (groups) for (const group of groups) trackProgs.push(n.programBuild(contextFor(sampleRate), group.uni.words, engine))
-    const result = meters ? await (window ? n.renderPieceLimiter : truePeaks ? n.renderPieceLoudness : n.renderPieceMeters)(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
+    const result = meters ? await (release ? n.renderPieceLimiterRelease : window ? n.renderPieceLimiter : truePeaks ? n.renderPieceLoudness : n.renderPieceMeters)(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
       routed ? trackProgs : null, routed ? groups.map((group) => Uint32Array.from(group.tracks)) : null, routed ? groups.map((group) => (group.uni.nParams ? group.uni.params : null)) : null,
-      routed ? routed.faders : null, routed ? routed.trackSends : null, stems, nBlocks, ...(truePeaks ? [loud.target !== null, loud.target === null ? 0 : loud.target, loud.ceiling] : []), ...(window ? [window] : []))
+      routed ? routed.faders : null, routed ? routed.trackSends : null, stems, nBlocks, ...(truePeaks ? [loud.target !== null, loud.target === null ? 0 : loud.target, loud.ceiling] : []), ...(window ? [window] : []), ...(release ? [release] : []))
       : stems ? await n.renderPieceStems(...args, stereo ? 3 : taps ? 2 : panned ? 1 : 0, fracs, panned ? panned.pans : null, panned ? panned.comp : null,
       taps ? taps.nSpeakers : 0, taps ? taps.delays : null, taps ? taps.gains : null, masterProg, master && master.nParams ? master.params : null,
       buses ? busProgs : null, buses ? buses.map((bus) => (bus.nParams ? bus.params : null)) : null, routed ? null : sends, routed ? opts.tracks.length : 0, routed ? routed.trackOf : null,
@@ -1318,6 +1341,7 @@ module.exports.truePeak = truePeak
 module.exports.limit = limit
 module.exports.LIMITER = LIMITER
 module.exports.checkLimiter = checkLimiter
+module.exports.checkLimiterRelease = checkLimiterRelease
 module.exports.TRUE_PEAK_NOT_BOOL = TRUE_PEAK_NOT_BOOL
 module.exports.LOUDNESS = LOUDNESS
 module.exports.instanceRange = instanceRange

@@ -1218,6 +1218,11 @@ LIMITER_THRESHOLD_BAD = "dusp-hip: the limiter's threshold is a finite number ab
 LIMITER_WINDOW_SAMPLES = "dusp-hip: the limiter's window is a whole number of samples, 1 .. 4096"
 LIMITER_ONE = 1 << 30  # the gain curve's fixed point: 30 fractional bits
 LIMITER_WINDOW_MAX = 4096
+LIMITER_RELEASE_MAX = 1 << 22
+LIMITER_RELEASE_BAD = "dusp-hip: limiter_release is None or a finite positive number of seconds, the time the limiter's gain takes from 0 back to 1"
+LIMITER_RELEASE_NEEDS_LIMITER = "dusp-hip: limiter_release without limiter=True: a release is the limiter's"
+LIMITER_RELEASE_LONG = "dusp-hip: limiter_release is %d samples at %d Hz: the limiter's release is at most 4194304 samples"
+LIMITER_RELEASE_SAMPLES = "dusp-hip: the limiter's release is a whole number of samples, 1 .. 4194304"
 
 
 def check_limiter(limiter, limiter_window, loudness, sample_rate):
@@ -1240,6 +1245,26 @@ def check_limiter(limiter, limiter_window, loudness, sample_rate):
     if L > LIMITER_WINDOW_MAX:
         raise ValueError(LIMITER_WINDOW_LONG % (L, sample_rate))
     return L
+
+
+def check_limiter_release(limiter_release, limiter, sample_rate):
+    """`limiter_release=` of a _pcm or _wav call -> R, the release in samples, max(1, round(seconds x sample_rate)); 0 for None.
+    Refused by string: a release that is no finite positive number (or a bool), one without limiter=True, and one of more than 2^22
+    samples"""
+    r = limiter_release
+    if r is None:
+        return 0
+    if not isinstance(r, (int, float, np.integer, np.floating)) or isinstance(r, (bool, np.bool_)) or not np.isfinite(r) or not r > 0:
+        raise ValueError(LIMITER_RELEASE_BAD)
+    if not (isinstance(limiter, (bool, np.bool_)) and limiter):
+        raise ValueError(LIMITER_RELEASE_NEEDS_LIMITER)
+    exact = float(r) * float(sample_rate)
+    if exact > 2.0 * LIMITER_RELEASE_MAX:
+        raise ValueError(LIMITER_RELEASE_LONG % (int(exact) if exact < 2.0 ** 62 else 2 ** 62, sample_rate))
+    R = max(1, int(round(exact)))
+    if R > LIMITER_RELEASE_MAX:
+        raise ValueError(LIMITER_RELEASE_LONG % (R, sample_rate))
+    return R
 
 
 def limiter_threshold(lufs, target_lufs, ceiling_dbtp):
@@ -1292,13 +1317,8 @@ def limiter_envelope(signals, sample_rate, taps=None):
     return e
 
 
-def limiter_gain(e, threshold, window):
-    """The limiter's gain curve from its envelope -> (g float64 [n], q uint32 [n]).  T = threshold > 0, L = window, 1 .. 4096 samples:
-    r[s] = T / e[s] where e[s] > T, else 1 (one f64 division); q[s] = floor(r[s] x 2^30), ONE = 2^30 outside [0, n);
-    m[j] = min(q[j .. j + L - 1]) for j in [-(L - 1), n); sum[s] = m[s - L + 1] + .. + m[s], an exact integer; g[s] = f64(sum[s]) /
-    f64(L x ONE).  So g[s] <= r[s], exactly — every minimum in the mean holds q[s], and the floor and the integer mean only round down —
-    and g[s] is no lower than the smallest r within L samples of s less 2^-30.  The curve reaches a
-    peak's gain in a linear attack of L samples and leaves it in a release of L samples."""
+def _limiter_minima(e, threshold, window):
+    """-> (q uint32 [n], m int64 [n + L - 1]): limiter_gain's words and their sliding minima, m[j + (L - 1)] = min(q[j .. j + L - 1])"""
     import math
     T, L = float(threshold), int(window)
     if not (T > 0.0 and math.isfinite(T)):
@@ -1316,25 +1336,68 @@ def limiter_gain(e, threshold, window):
     while 2 * step <= L:
         p[:len(p) - step] = np.minimum(p[:len(p) - step], p[step:])
         step *= 2
-    m = np.minimum(p[:n + L - 1], p[L - step:L - step + n + L - 1])  # m[j'] = min(a[j' .. j' + L - 1]), j' = j + (L - 1)
+    return q, np.minimum(p[:n + L - 1], p[L - step:L - step + n + L - 1])  # m[j'] = min(a[j' .. j' + L - 1]), j' = j + (L - 1)
+
+
+def _limiter_mean(m, n, L):
+    """g[s] = f64(m[s] + .. + m[s + L - 1]) / f64(L x ONE) in m's indexing: the integer sum, one division"""
     c = np.concatenate(([0], np.cumsum(m)))
-    total = c[L:L + n] - c[:n]  # sum[s] = m[s] + .. + m[s + L - 1] in that indexing
-    return total.astype(np.float64) / float(L * LIMITER_ONE), q
+    total = c[L:L + n] - c[:n]
+    return total.astype(np.float64) / float(L * LIMITER_ONE)
 
 
-def limit(signals, sample_rate, threshold, window, taps=None):
+def limiter_gain(e, threshold, window):
+    """The limiter's gain curve from its envelope -> (g float64 [n], q uint32 [n]).  T = threshold > 0, L = window, 1 .. 4096 samples:
+    r[s] = T / e[s] where e[s] > T, else 1 (one f64 division); q[s] = floor(r[s] x 2^30), ONE = 2^30 outside [0, n);
+    m[j] = min(q[j .. j + L - 1]) for j in [-(L - 1), n); sum[s] = m[s - L + 1] + .. + m[s], an exact integer; g[s] = f64(sum[s]) /
+    f64(L x ONE).  So g[s] <= r[s], exactly — every minimum in the mean holds q[s], and the floor and the integer mean only round down —
+    and g[s] is no lower than the smallest r within L samples of s less 2^-30.  The curve reaches a
+    peak's gain in a linear attack of L samples and leaves it in a release of L samples."""
+    q, m = _limiter_minima(e, threshold, window)
+    return _limiter_mean(m, len(q), int(window)), q
+
+
+def limiter_release_step(release):
+    """d = ceil(ONE / R), the most the held curve rises a sample: a gain of 0 is back at 1 after at most R samples.  R is a whole
+    number of samples, 1 .. 2^22 (LIMITER_RELEASE_MAX)"""
+    R = int(release)
+    if R != release or isinstance(release, (bool, np.bool_)) or not 1 <= R <= LIMITER_RELEASE_MAX:
+        raise ValueError(LIMITER_RELEASE_SAMPLES)
+    return -(-LIMITER_ONE // R)
+
+
+def limiter_gain_release(e, threshold, window, release):
+    """The gain curve with a release of its own -> (g float64 [n], q uint32 [n], held int64 [n + L - 1]; held[j + (L - 1)] is the held
+    curve at j).  q and m are limiter_gain's.  R = release, 1 .. 2^22 samples, d = limiter_release_step(R) = ceil(ONE / R).
+    held[j] = min(m[j], held[j - 1] + d) for j from -(L - 1) upwards, held[-L] = ONE — in closed form the minimum over i <= j of
+    m[i] + d (j - i), which is how it is formed here: d j + the running minimum of m[i] - d i, all in 64-bit integers (no cap at ONE is
+    needed: m[j] <= ONE is a member).  sum[s] = held[s - L + 1] + .. + held[s], g[s] = f64(sum[s]) / f64(L x ONE).  Exactly:
+      - R = 1: d = ONE, held = m and g is limiter_gain's bit for bit;
+      - held <= m, so g[s] <= limiter_gain's g[s] <= r[s];
+      - held[j] - held[j - 1] <= d and sum[s] - sum[s - 1] <= L d: the curve rises by at most d / ONE a sample;
+      - m[i] + d (j - i) >= ONE once j - i >= ceil(ONE / d): held[j] depends on at most the last ceil(ONE / d) <= R values of m."""
+    d = limiter_release_step(release)
+    q, m = _limiter_minima(e, threshold, window)
+    at = np.arange(len(m), dtype=np.int64) * d  # (below 2^31 x 2^30)
+    held = np.minimum.accumulate(m - at) + at if len(m) else m
+    return _limiter_mean(held, len(q), int(window)), q, held
+
+
+def limit(signals, sample_rate, threshold, window, taps=None, release=None):
     """The linked look-ahead limiter: the contract of dusp_limit_host and of limiter=True, in f64 and integers, needs no GPU.
     signals float32 [S, C, n] -> (limited float32 [S, C, n], g float64 [n], reduction): ONE curve g = limiter_gain(limiter_envelope(
     signals)) for every row, limited = f32(f64(x) x g[s]); reduction = min(g), 1.0 exactly where nothing exceeds the threshold (the
-    output is then the input bit for bit).  A NaN sample stays a NaN."""
+    output is then the input bit for bit).  A NaN sample stays a NaN.  release: None, or R in samples — the curve is then
+    limiter_gain_release's (the contract of dusp_limit_release_host and of limiter_release=)."""
     signals = np.asarray(signals, dtype=np.float32)
-    g, _ = limiter_gain(limiter_envelope(signals, sample_rate, taps), threshold, window)
+    e = limiter_envelope(signals, sample_rate, taps)
+    g = limiter_gain(e, threshold, window)[0] if release is None else limiter_gain_release(e, threshold, window, release)[0]
     with np.errstate(all="ignore"):
         limited = (signals.astype(np.float64) * g).astype(np.float32)
     return limited, g, (float(np.min(g)) if len(g) else 1.0)
 
 
-def deliver_limited(signals, sample_rate, target_lufs, ceiling_dbtp, window, taps=None):
+def deliver_limited(signals, sample_rate, target_lufs, ceiling_dbtp, window, taps=None, release=None):
     """The whole chain of a delivery with limiter=True over the f32 signals the call delivers (the mix LAST), in f64, needs no GPU: the
     contract of dusp_render_host_score_piece_limiter.  -> dict(signals, meters, true_peak, gain, level, limiter): the signals that are
     encoded (wav.encode_at_level(signals, bit_depth, level) has the bytes), their meters and true peaks, the one gain and its level,
@@ -1343,16 +1406,17 @@ def deliver_limited(signals, sample_rate, target_lufs, ceiling_dbtp, window, tap
     First meters, true_peak and loudness_gain as without a limiter.  T = limiter_threshold(lufs of the mix, target, ceiling).  The
     limiter is engaged where that gain is not unity (level != 1), T is finite and above 0, and the largest true peak exceeds T;
     otherwise the delivery is the one without a limiter.  Engaged: limit(signals, T, window), then meters, true_peak and loudness_gain
-    again over the limited signals — the ceiling is held by that gain, and what is returned describes the limited signals."""
+    again over the limited signals — the ceiling is held by that gain, and what is returned describes the limited signals.
+    release: None, or R in samples (limit's); the record then has release=R, else release=0."""
     import math
     signals = np.asarray(signals, dtype=np.float32)
     metered, tps = meters(signals, sample_rate), true_peak(signals, sample_rate, taps)
     gain, level = loudness_gain(metered["lufs"][-1], tps, target_lufs, ceiling_dbtp)
     lufs_in, tp_in = float(metered["lufs"][-1]), (float("nan") if np.any(np.isnan(tps)) else float(np.max(tps)))
-    record = dict(engaged=False, threshold=0.0, window=int(window), reduction=1.0, lufs_in=lufs_in, true_peak_in=tp_in)
+    record = dict(engaged=False, threshold=0.0, window=int(window), reduction=1.0, lufs_in=lufs_in, true_peak_in=tp_in, release=0 if release is None else int(release))
     T = record["threshold"] = limiter_threshold(lufs_in, target_lufs, ceiling_dbtp)
     if level != np.float32(1.0) and T > 0.0 and math.isfinite(T) and tp_in > T:
-        signals, _, reduction = limit(signals, sample_rate, T, window, taps)
+        signals, _, reduction = limit(signals, sample_rate, T, window, taps, release)
         metered, tps = meters(signals, sample_rate), true_peak(signals, sample_rate, taps)
         gain, level = loudness_gain(metered["lufs"][-1], tps, target_lufs, ceiling_dbtp)
         record.update(engaged=True, reduction=reduction)

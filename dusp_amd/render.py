@@ -271,18 +271,21 @@ class Limiter:
     """What the limiter of a call with limiter=True did (mix.deliver_limited is the contract): `engaged`, whether it ran —
     it does where the largest true peak lies above `threshold`, the ceiling seen from the loudness target, linear; `window`, its
     look-ahead, attack and release in samples; `reduction`, the smallest gain of its curve, 1.0 when not engaged; `lufs_in` and
-    `true_peak_in`, the loudness of the mix and the largest true peak of any delivered signal in front of it."""
+    `true_peak_in`, the loudness of the mix and the largest true peak of any delivered signal in front of it; `release`, the release of
+    its own in samples (limiter_release=), 0 when there is none and the curve leaves a peak within `window`."""
 
     def __init__(self, got):
         self.engaged, self.threshold, self.window, self.reduction = bool(got["engaged"]), float(got["threshold"]), int(got["window"]), float(got["reduction"])
         self.lufs_in, self.true_peak_in = float(got["lufs_in"]), float(got["true_peak_in"])
+        self.release = int(got.get("release", 0))
 
 
-def limit(planar, sample_rate, threshold, window, device=-1):
+def limit(planar, sample_rate, threshold, window, release=None, device=-1):
     """The linked look-ahead limiter over any signals a user has: planar float32 [signals, channels, samples] (or [channels, samples]:
     one signal) -> (limited float32 of that shape, g float64 [samples], reduction), ONE gain curve for every row, on the device
-    (Context.limit; mix.limit is the contract).  threshold: linear; window: 1 .. 4096 samples."""
-    return context(sample_rate, device).limit(planar, sample_rate, threshold, window)
+    (Context.limit; mix.limit is the contract).  threshold: linear; window: 1 .. 4096 samples; release: None, or the limiter's release
+    of its own, 1 .. 2^22 samples (mix.limiter_gain_release)."""
+    return context(sample_rate, device).limit(planar, sample_rate, threshold, window, 0 if release is None else release)
 
 
 def _empty_meters(n_signals, channels, sample_rate):
@@ -377,7 +380,7 @@ def _score_voice_duration(voice_duration):
     return voice_duration
 
 
-def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, limiter=False, limiter_window=0.005):
+def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, limiter=False, limiter_window=0.005, limiter_release=None):
     """A piece of N isomorphic circuits, voice k starting at sample onsets[k] of a timeline of `duration` seconds — what
     `renderChannelData(Sum.many(Delay(outlet_k, onsets[k], maxDelay)), duration)` computes (a Delay by whole samples is its input behind
     zeros; the voice with onset 0 bare), with `gains` as in render_mix — rendered as ONE program for `voice_duration` seconds a voice, in
@@ -409,12 +412,12 @@ def render_score(outlets, onsets, voice_duration=1, duration=1, lengths=None, ga
     meters=True, true_peak=True: as render_piece's — the RMS, the loudness and the true peak of every signal the call delivers; the
     piece's call too.  loudness belongs to render_score_pcm and render_score_wav and is refused here."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, -1.0, limiter, limiter_window))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, -1.0, limiter, limiter_window, limiter_release))
 
 
 def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances, placing, pcm=None):
     """render_score (pcm None) and render_score_pcm (pcm = (bit_depth, normalise))"""
-    if placing["stereo"] or placing["stems"] or placing["meters"] or placing["true_peak"] or placing["loudness"] is not None or placing["limiter"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks")):
+    if placing["stereo"] or placing["stems"] or placing["meters"] or placing["true_peak"] or placing["loudness"] is not None or placing["limiter"] or any(placing[k] is not None for k in ("pans", "fracs", "space", "master", "buses", "tracks", "limiter_release")):
         return _render_piece_voices(outlets, onsets, _score_voice_duration(voice_duration), duration, lengths, gains, engine, device, 0, placing, True, pcm)
     if pcm is not None:
         _check_pcm(*pcm)
@@ -427,17 +430,17 @@ def _render_score(outlets, onsets, voice_duration, duration, lengths, gains, eng
 
 
 def render_score_pcm(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005, limiter_release=None):
     """render_score, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_score(outlets, onsets, voice_duration, duration, lengths, gains, engine, device, tile_instances,
-                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max, limiter, limiter_window), (bit_depth, normalise))
+                         _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max, limiter, limiter_window, limiter_release), (bit_depth, normalise))
 
 
 def render_score_wav(outlets, onsets, voice_duration=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005):
+                     tile_instances=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005, limiter_release=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_score_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_score_pcm(outlets, onsets, voice_duration, duration, bit_depth, normalise, lengths, gains, engine, device, tile_instances, pans, fracs, places, speakers,
-                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max, limiter, limiter_window), bit_depth)
+                                 decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max, limiter, limiter_window, limiter_release), bit_depth)
 
 
 class PieceParts:
@@ -481,7 +484,7 @@ def piece_parts(extractions, voice_samples):
     return PieceParts(parts, np.array(part_of, dtype=np.uint32), np.array(instance_of, dtype=np.int64), rates.pop())
 
 
-def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005):
+def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005, limiter_release=None):
     """the placement keywords of a call as one thing: what mix.Placement takes once the voices are counted and their sample rate is
     known.  The Space keywords are one thing too, None without places (the other three alone say nothing).  master: what the mix goes
     through behind the placement (master_program makes it a program once the timeline's channels are known), which travels with it;
@@ -494,7 +497,8 @@ def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per
     takes the true peaks, refused next to meters; loudness, true_peak_max: the target and ceiling of a delivery at a loudness target,
     which travel with it as they are (_render_piece_voices holds them to mix.check_loudness once it knows what the call delivers);
     limiter, limiter_window: whether that delivery is limited first and the limiter's window in seconds, which travel the same way
-    (mix.check_limiter, once the sample rate is known) — a limiter that is no bool is refused here, next to true_peak"""
+    (mix.check_limiter, once the sample rate is known) — a limiter that is no bool is refused here, next to true_peak; limiter_release:
+    the limiter's release in seconds or None, which travels as limiter_window does (mix.check_limiter_release)"""
     stems, meters, true_peak = mix.check_stems(stems), mix.check_meters(meters), mix.check_true_peak(true_peak)
     if not isinstance(limiter, (bool, np.bool_)):
         raise ValueError(mix.LIMITER_NOT_BOOL)
@@ -523,7 +527,7 @@ def _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per
             raise ValueError(mix.BUS_COUNT % (len(buses) if isinstance(buses, (list, tuple)) else 0))
     return dict(pans=pans, fracs=fracs, space=None if places is None else (places, speakers, decibels_per_metre, sample_delay_per_metre), stereo=stereo, master=master,
                 buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters, true_peak=true_peak, loudness=loudness,
-                true_peak_max=true_peak_max, limiter=bool(limiter), limiter_window=limiter_window)
+                true_peak_max=true_peak_max, limiter=bool(limiter), limiter_window=limiter_window, limiter_release=limiter_release)
 
 
 def master_program(master, channels, sample_rate, bus=None):
@@ -604,7 +608,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     tracks, track_of, faders, track_sends = (placing.pop(k, None) for k in ("tracks", "track_of", "faders", "track_sends"))
     stems, meters = placing.pop("stems", False), placing.pop("meters", False)
     true_peak, loudness, true_peak_max = placing.pop("true_peak", False), placing.pop("loudness", None), placing.pop("true_peak_max", -1.0)
-    limiter, limiter_window = placing.pop("limiter", False), placing.pop("limiter_window", 0.005)
+    limiter, limiter_window, limiter_release = placing.pop("limiter", False), placing.pop("limiter_window", 0.005), placing.pop("limiter_release", None)
     mix.Placement.refuse_together(placing["pans"], placing["fracs"], placing["space"], placing["stereo"])
     extractions = [descriptor.extract(o) for o in outlets]
     n = len(extractions)
@@ -631,7 +635,7 @@ def _piece(outlets, onsets, voice_durations, duration, lengths, gains, placing, 
     place.stems = stems  # (... whether the call delivers its stems)
     place.meters = meters  # (... and whether it meters what it delivers)
     place.true_peak, place.loudness, place.true_peak_max = true_peak, loudness, true_peak_max  # (... takes its true peaks, and delivers at a loudness target)
-    place.limiter, place.limiter_window = limiter, limiter_window  # (... limited first)
+    place.limiter, place.limiter_window, place.limiter_release = limiter, limiter_window, limiter_release  # (... limited first, with a release of its own)
     place.tracks = None  # (... and the tracks: (how many, track_of, track_programs' groups, faders, levels [buses, tracks]))
     if tracks is not None:
         track_of, faders, track_sends = mix.check_tracks(n, len(tracks), track_of, faders, track_sends, 0 if buses is None else len(buses), sends)
@@ -671,7 +675,7 @@ def _render_piece(grouped, n_total, onsets, lengths, gains, place, engine, devic
 
 
 def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1, tile_bytes=0, pans=None, _one_part=False,
-                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, limiter=False, limiter_window=0.005):
+                 fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, limiter=False, limiter_window=0.005, limiter_release=None):
     """A piece of several instruments: render_score over voices of ANY circuits, each rendered for its own voice_durations[k] seconds
     (one number: all alike).  The voices are grouped into parts by structure and by samples a voice (piece_parts), every part is ONE
     program, and the device walks the caller's voice list in its own order: bit for bit mix.score_chain_rows over what each program
@@ -754,9 +758,13 @@ def render_piece(outlets, onsets, voice_durations=1, duration=1, lengths=None, g
     target, every delivered signal is first multiplied by ONE look-ahead gain curve made from the largest oversampled magnitude of
     any of them (mix.limit) — so the stems still add up to the mix — then metered again, and the one gain comes from
     that second measurement: the ceiling is still held by the gain.  The result gains `.limiter` (a Limiter), and where it engaged
-    the meters, peaks, gain and level describe the limited signals."""
+    the meters, peaks, gain and level describe the limited signals.
+
+    limiter_release (seconds, with limiter=True; at most 2^22 samples): the limiter's gain then rises by at most 1 / release a second,
+    however short the window — a release of 50 to 500 ms instead of the window's 5 (mix.limiter_gain_release).
+    `.limiter.release` has it in samples, 0 without one."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, -1.0, limiter, limiter_window), _one_part)
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, -1.0, limiter, limiter_window, limiter_release), _one_part)
 
 
 def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes, placing, one_part, pcm=None):
@@ -768,9 +776,12 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
     names = mix.stem_names(place.tracks[0] if place.tracks is not None else 0, len(place.buses) if place.buses is not None else 0) if place.stems else ["mix"]
     loudness, ceiling = mix.check_loudness(place.loudness, place.true_peak_max, pcm[1] if pcm is not None else 0, pcm is not None)
     window = mix.check_limiter(place.limiter, place.limiter_window, loudness, grouped.sample_rate)
+    release = mix.check_limiter_release(place.limiter_release, place.limiter, grouped.sample_rate)
     place.loud = dict(true_peak=True, loudness=loudness, true_peak_max=ceiling) if place.true_peak or loudness is not None else {}
     if window:
         place.loud.update(limiter=True, limiter_window=place.limiter_window)
+    if release:
+        place.loud.update(limiter_release=place.limiter_release)
     if place.meters or place.loud:  # (the run hands back what it does without meters, and the meters beside it)
         got = _empty_meters(len(names), channels, grouped.sample_rate)
         if place.loud:  # (a timeline of no samples: true peaks 0, gain 1)
@@ -778,7 +789,7 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
         if loudness is not None:
             got["gain"], got["level"] = 1.0, np.float32(1.0)
         if window:  # (... and the limiter has nothing to do)
-            got["limiter"] = dict(engaged=False, threshold=0.0, window=window, reduction=1.0, lufs_in=-np.inf, true_peak_in=0.0)
+            got["limiter"] = dict(engaged=False, threshold=0.0, window=window, reduction=1.0, lufs_in=-np.inf, true_peak_in=0.0, release=release)
         render = run
 
         def run(format, normalise):
@@ -803,17 +814,17 @@ def _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, ga
 
 
 def render_piece_pcm(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005):
+                     tile_bytes=0, pans=None, _one_part=False, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005, limiter_release=None):
     """render_piece, delivering what render_pcm delivers: the piece's frames encoded on the device, and its peak -> PcmData (stems=True: a Stems of them, under one gain)."""
     return _render_piece_voices(outlets, onsets, voice_durations, duration, lengths, gains, engine, device, tile_bytes,
-                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max, limiter, limiter_window), _one_part, (bit_depth, normalise))
+                                _placing(pans, fracs, places, speakers, decibels_per_metre, sample_delay_per_metre, stereo, master, buses, sends, tracks, track_of, faders, track_sends, stems, meters, true_peak, loudness, true_peak_max, limiter, limiter_window, limiter_release), _one_part, (bit_depth, normalise))
 
 
 def render_piece_wav(outlets, onsets, voice_durations=1, duration=1, bit_depth=16, normalise=0, lengths=None, gains=None, engine=runtime.ENGINE_AUTO, device=-1,
-                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005):
+                     tile_bytes=0, pans=None, fracs=None, places=None, speakers=None, decibels_per_metre=-3, sample_delay_per_metre=None, stereo=False, master=None, buses=None, sends=None, tracks=None, track_of=None, faders=None, track_sends=None, stems=False, meters=False, true_peak=False, loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005, limiter_release=None):
     """A complete RIFF/WAVE file (bytes) of the piece: render_piece_pcm plus the header (wav.encode_wav); stems=True: a Stems of one file a signal."""
     return _wav(render_piece_pcm(outlets, onsets, voice_durations, duration, bit_depth, normalise, lengths, gains, engine, device, tile_bytes, pans, fracs=fracs, places=places,
-                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters, true_peak=true_peak, loudness=loudness, true_peak_max=true_peak_max, limiter=limiter, limiter_window=limiter_window), bit_depth)
+                                 speakers=speakers, decibels_per_metre=decibels_per_metre, sample_delay_per_metre=sample_delay_per_metre, stereo=stereo, master=master, buses=buses, sends=sends, tracks=tracks, track_of=track_of, faders=faders, track_sends=track_sends, stems=stems, meters=meters, true_peak=true_peak, loudness=loudness, true_peak_max=true_peak_max, limiter=limiter, limiter_window=limiter_window, limiter_release=limiter_release), bit_depth)
 
 
 class PcmData:

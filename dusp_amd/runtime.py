@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .mix import check_limiter, check_loudness, check_meters, check_stems, check_true_peak, meter_blocks, meter_hop, METER_RATE_LOW, METER_RATE_MIN, LIMITER_THRESHOLD_BAD, LIMITER_WINDOW_MAX, LIMITER_WINDOW_SAMPLES, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
+from .mix import check_limiter, check_limiter_release, LIMITER_RELEASE_MAX, LIMITER_RELEASE_SAMPLES, check_loudness, check_meters, check_stems, check_true_peak, meter_blocks, meter_hop, METER_RATE_LOW, METER_RATE_MIN, LIMITER_THRESHOLD_BAD, LIMITER_WINDOW_MAX, LIMITER_WINDOW_SAMPLES, BUSES_WITHOUT_SENDS, SENDS_WITHOUT_BUSES, TRACKS_FADERS_SHAPE, TRACKS_SENDS_SHAPE, check_tracks, SPACE_ALONE, STEREO_NO_PLACES, Placement, check_sends, refuse_sends_placement, _gains_table, _whole, check_stereo_kinds, frac_arrays, pan_arrays, pan_comp, stereo_pan_arrays, tap_arrays  # noqa: F401
 from .wavetables import N_TABLES, make_table
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +40,7 @@ EXPORTS = [
     "dusp_meter_blocks", "dusp_meter_device", "dusp_meter_last_ms", "dusp_meter_host", "dusp_render_host_score_piece_meters",
     "dusp_true_peak_taps", "dusp_true_peak_tile", "dusp_true_peak_device", "dusp_true_peak_host", "dusp_render_host_score_piece_loudness",
     "dusp_limiter_threshold", "dusp_limit_tile", "dusp_limit_device", "dusp_limit_last_ms", "dusp_limit_host", "dusp_render_host_score_piece_limiter",
+    "dusp_limit_release_tile", "dusp_limit_release_device", "dusp_limit_release_last_ms", "dusp_limit_release_host", "dusp_render_host_score_piece_limiter_release",
 ]
 
 PCM_S16, PCM_S24, PCM_F32 = 1, 2, 3  # dusp_pcm_format
@@ -150,6 +151,12 @@ def load():
         L.dusp_limit_last_ms.argtypes = [vp, vp]
         L.dusp_limit_host.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, ctypes.c_double, sz, vp, vp, vp]
         L.dusp_render_host_score_piece_limiter.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, ci, vp, vp]
+    if hasattr(L, "dusp_render_host_score_piece_limiter_release"):  # (... and the limiter's release)
+        L.dusp_limit_release_tile.argtypes, L.dusp_limit_release_tile.restype = [vp, sz, sz, sz], sz
+        L.dusp_limit_release_device.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, ctypes.c_double, sz, sz, vp, vp, vp, vp, vp]
+        L.dusp_limit_release_last_ms.argtypes = [vp, vp]
+        L.dusp_limit_release_host.argtypes = [vp, vp, sz, sz, sz, ctypes.c_uint32, ctypes.c_double, sz, sz, vp, vp, vp]
+        L.dusp_render_host_score_piece_limiter_release.argtypes = L.dusp_render_host_score_piece_limiter.argtypes
     L.dusp_state_download.argtypes = [vp, sz, sz, vp, sz]
     L.dusp_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dusp_fill_device.argtypes = [vp, vp, sz, ctypes.c_float, vp]
@@ -225,6 +232,11 @@ class ScoreLimiter(ctypes.Structure):
     mix's loudness and the largest true peak in front of it"""
     _fields_ = [("window_samples", ctypes.c_size_t), ("h_engaged", ctypes.c_void_p), ("h_threshold", ctypes.c_void_p), ("h_reduction", ctypes.c_void_p),
                 ("h_lufs_in", ctypes.c_void_p), ("h_true_peak_in", ctypes.c_void_p)]
+
+
+class ScoreLimiterRelease(ctypes.Structure):
+    """dusp_score_limiter_release: the limiter's record, and its release in samples (0: none of its own)"""
+    _fields_ = [("limiter", ScoreLimiter), ("release_samples", ctypes.c_size_t)]
 
 
 PINNED_MIN_BYTES = 1 << 20  # results of at least 1 MiB are delivered in pinned memory (dusp_host_alloc): one DMA, no staging
@@ -633,10 +645,30 @@ class Context:
         """-> the samples a workgroup of that limiter call owns on this context's device (dusp_limit_tile)"""
         return int(self._L.dusp_limit_tile(self._h, n_samples, int(window)))
 
-    def limit(self, planar, sample_rate, threshold, window):
+    def limit_release_device(self, d_planar, n_signals, n_channels, n_samples, sample_rate, threshold, window, release, d_q=None, d_held=None, d_gain=None, d_smallest=None,
+                             stream=None):
+        """limit_device with a release of `release` samples, 1 .. 2^22 (dusp_limit_release_device; mix.limit(..., release=) is the
+        contract): the envelope kernel, then the hold, release and mean / apply kernels.  d_held: optional, uint32 [n_samples + window
+        - 1], the held curve.  Timed by score_last_ms; limit_release_last_ms has the four kernels."""
+        self._check(self._L.dusp_limit_release_device(self._h, d_planar, n_signals, n_channels, n_samples, int(sample_rate), float(threshold), int(window), int(release), d_q, d_held,
+                                                      d_gain, d_smallest, stream))
+
+    def limit_release_last_ms(self):
+        """-> the four kernels of the most recent limit_release_device call in ms, by HIP events (dusp_limit_release_last_ms; waits for
+        that call): envelope, hold, release, mean / apply"""
+        ms = (ctypes.c_float * 4)()
+        self._check(self._L.dusp_limit_release_last_ms(self._h, ctypes.addressof(ms)))
+        return tuple(ms)
+
+    def limit_release_tile(self, n_samples, window, release):
+        """-> the positions a workgroup of that call owns on this context's device (dusp_limit_release_tile)"""
+        return int(self._L.dusp_limit_release_tile(self._h, n_samples, int(window), int(release)))
+
+    def limit(self, planar, sample_rate, threshold, window, release=0):
         """planar float32 [signals, channels, samples] (or [channels, samples]: one signal) in host memory -> what mix.limit returns:
         (limited float32 of planar's shape, g float64 [samples], reduction), limited on the device under ONE curve
-        (dusp_limit_host).  threshold: linear, finite, above 0; window: 1 .. 4096 samples."""
+        (dusp_limit_host).  threshold: linear, finite, above 0; window: 1 .. 4096 samples; release: 0, or the limiter's release of its
+        own, 1 .. 2^22 samples (dusp_limit_release_host)."""
         planar = np.ascontiguousarray(planar, dtype=np.float32)
         shape = planar.shape
         if planar.ndim == 2:
@@ -649,16 +681,23 @@ class Context:
             raise ValueError(LIMITER_THRESHOLD_BAD)
         if not (isinstance(window, (int, np.integer)) and 1 <= window <= LIMITER_WINDOW_MAX):
             raise ValueError(LIMITER_WINDOW_SAMPLES)
+        if not (isinstance(release, (int, np.integer)) and not isinstance(release, (bool, np.bool_)) and 0 <= release <= LIMITER_RELEASE_MAX):
+            raise ValueError(LIMITER_RELEASE_SAMPLES)
         S, C, n = planar.shape
         limited, g, reduction = np.empty_like(planar), np.ones(n), ctypes.c_double(1.0)
-        if n and S and C:
+        if n and S and C and release:
+            if not hasattr(self._L, "dusp_limit_release_host"):
+                raise DuspHipError(-3, "dusp-hip: this library's limiter has no release (dusp_limit_release_host is missing)")
+            self._check(self._L.dusp_limit_release_host(self._h, planar.ctypes.data, S, C, n, int(sample_rate), float(threshold), int(window), int(release), limited.ctypes.data,
+                                                        g.ctypes.data, ctypes.addressof(reduction)))
+        elif n and S and C:
             self._check(self._L.dusp_limit_host(self._h, planar.ctypes.data, S, C, n, int(sample_rate), float(threshold), int(window), limited.ctypes.data, g.ctypes.data,
                                                 ctypes.addressof(reduction)))
         return limited.reshape(shape), g, float(reduction.value)
 
     def render_score_parts(self, parts, part_of, onsets, n_total_samples, lengths=None, gains=None, tile_bytes=0, format=None, normalise=NORMALISE_NONE, pinned=None,
                            pans=None, fracs=None, taps=None, stereo=False, master=None, buses=None, sends=None, tracks=None, stems=False, meters=False, true_peak=False,
-                           loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005):
+                           loudness=None, true_peak_max=-1.0, limiter=False, limiter_window=0.005, limiter_release=None):
         """Host round trip that delivers a PIECE of several instruments (dusp_render_host_score_parts).  parts: a list of
         (program, n_voice_samples, n_instances, params) — programs of this context with one number of output channels; voice k of the
         chain is the next unused instance of part part_of[k].  Bit for bit mix.score_chain_rows over what each program's render() gives
@@ -705,10 +744,14 @@ class Context:
         lies above the ceiling seen from the target, every delivered signal is first limited under ONE look-ahead gain curve
         (dusp_render_host_score_piece_limiter; mix.deliver_limited is the contract), and what the call returns — the meters, the
         peaks, gain and level — then describes the limited signals; the dict gains limiter, a dict of engaged, threshold, window (in
-        samples), reduction, lufs_in and true_peak_in."""
+        samples), reduction, lufs_in and true_peak_in.
+        limiter_release (seconds, with limiter=True; at most 2^22 samples): the limiter's release of its own
+        (dusp_render_host_score_piece_limiter_release; mix.deliver_limited(..., release=) is the contract); the limiter's dict then
+        has release, in samples."""
         stems, meters, true_peak = check_stems(stems), check_meters(meters), check_true_peak(true_peak)
         loudness, true_peak_max = check_loudness(loudness, true_peak_max, normalise, format is not None)
         window = check_limiter(limiter, limiter_window, loudness, parts[0][0].sample_rate if parts else 1)
+        release = check_limiter_release(limiter_release, limiter, parts[0][0].sample_rate if parts else 1)
         true_peak = true_peak or loudness is not None
         meters = meters or true_peak
         if tracks is not None:
@@ -791,6 +834,11 @@ class Context:
                     at = ctypes.addressof(did)
                     asked_limiter = ScoreLimiter(window, ctypes.addressof(engaged), at, at + 8, at + 16, at + 24)
                     entry, loud = self._L.dusp_render_host_score_piece_limiter, loud + (ctypes.addressof(asked_limiter),)
+                    if release:  # (... and the same record with a release behind it)
+                        if not hasattr(self._L, "dusp_render_host_score_piece_limiter_release"):
+                            raise DuspHipError(-3, "dusp-hip: this library's limiter has no release (dusp_render_host_score_piece_limiter_release is missing)")
+                        asked_release = ScoreLimiterRelease(asked_limiter, release)
+                        entry, loud = self._L.dusp_render_host_score_piece_limiter_release, loud[:-1] + (ctypes.addressof(asked_release),)
             if stems:
                 if format is None:
                     fmt, normalise, out = 0, 0, self.host_empty((n_signals, n_ch, n_total_samples), pinned)
@@ -805,7 +853,7 @@ class Context:
             if loudness is not None:
                 got["gain"], got["level"] = float(gain.value), np.float32(level.value)
             if window:
-                got["limiter"] = dict(engaged=bool(engaged.value), threshold=float(did[0]), window=window, reduction=float(did[1]), lufs_in=float(did[2]), true_peak_in=float(did[3]))
+                got["limiter"] = dict(engaged=bool(engaged.value), threshold=float(did[0]), window=window, reduction=float(did[1]), lufs_in=float(did[2]), true_peak_in=float(did[3]), release=release)
             return ((out, peak) if stems else out if peak is None else (out, peak[0])), got
         if stems:
             n_signals = 1 + (tracks["n_tracks"] if tracks is not None else 0) + (len(buses) if buses is not None else 0) + 1

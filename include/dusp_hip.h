@@ -884,6 +884,42 @@ int dusp_render_host_score_piece_limiter(const dusp_score_part *parts, size_t n_
                                          const dusp_score_meters *meters, const dusp_score_loudness *loudness, const dusp_score_limiter *limiter,
                                          size_t n_total_samples, size_t tile_bytes, int format, int normalise, void *h_out, float *h_peaks);
 
+/* The limiter's release of its own (additions to ABI v7, detected by symbol; dusp_amd/mix.py limiter_release_step and
+ * limiter_gain_release are the contract).  q, m, L, ONE and T are the limiter's.  R is the release, 1 .. 2^22 samples, and
+ * d = ceil(ONE / R) its step.  Between the minima and the mean stands the held curve, held[j] = min(m[j], held[j - 1] + d) for j from
+ * -(L - 1) upwards with held[-L] = ONE — the minimum over i <= j of m[i] + d (j - i); sum[s] = held[s - L + 1] + .. + held[s];
+ * g[s] = (double)sum[s] / (double)(L x ONE).  So the curve falls as the plain limiter's does and rises by at most d / ONE a sample: a
+ * gain of 0 is back at 1 after at most R samples.  held <= m, so g[s] is at most the plain limiter's g[s], and R = 1 gives that curve
+ * bit for bit.  All integer between the two divisions: a scan over the tiles by three launches, no workgroup waiting for another. */
+/* the positions a workgroup of the release's kernels owns in a call over n_samples with that window and release: dusp_limit_tile's;
+ * 0 for a call that would be refused */
+size_t dusp_limit_release_tile(dusp_ctx *ctx, size_t n_samples, size_t window_samples, size_t release_samples);
+/* dusp_limit_device with a release of release_samples (1 .. 2^22): the envelope kernel, then the hold, release and mean / apply kernels.
+ * d_held: optional, uint32 [n_samples + window_samples - 1], the held curve; position j + (L - 1) holds held[j].  Timed by
+ * dusp_score_last_ms; dusp_limit_release_last_ms has the four kernels. */
+int dusp_limit_release_device(dusp_ctx *ctx, float *d_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold,
+                              size_t window_samples, size_t release_samples, uint32_t *d_q, uint32_t *d_held, double *d_gain, uint64_t *d_smallest, void *stream);
+/* the last dusp_limit_release_device call launch by launch, by events: ms[0] the envelope kernel, ms[1] hold, ms[2] release, ms[3]
+ * mean / apply.  Waits for the call's kernels, then checks the guards behind the context's scratch (DUSP_GUARD). */
+int dusp_limit_release_last_ms(dusp_ctx *ctx, float ms[4]);
+/* dusp_limit_host with a release of release_samples (1 .. 2^22) */
+int dusp_limit_release_host(dusp_ctx *ctx, const float *h_planar, size_t n_signals, size_t n_channels, size_t n_samples, uint32_t sample_rate, double threshold,
+                            size_t window_samples, size_t release_samples, float *h_limited, double *h_gain, double *h_reduction);
+/* dusp_render_host_score_piece_limiter with a release: release_samples = 0 is that entry's call byte for byte (under this entry's
+ * name); 1 .. 2^22, the engaged limiter runs with that release.  Refused behind every refusal of that entry: more than 2^22 samples.
+ * limiter NULL: no limiter and no release.  Scratch on the context: 4 (n + L - 1) bytes and one word a tile beside the limiter's. */
+typedef struct dusp_score_limiter_release {
+    dusp_score_limiter limiter;
+    size_t release_samples; /* R, 1 .. 2^22; 0: no release of its own */
+} dusp_score_limiter_release;
+int dusp_render_host_score_piece_limiter_release(const dusp_score_part *parts, size_t n_parts, size_t n_voices, const uint32_t *h_part_of,
+                                                 const int64_t *h_onsets, const int64_t *h_lengths, const float *h_gains,
+                                                 const dusp_score_placement *placement, const dusp_score_tracks *tracks,
+                                                 const dusp_score_buses *buses, const dusp_score_master *master, const dusp_score_stems *stems,
+                                                 const dusp_score_meters *meters, const dusp_score_loudness *loudness,
+                                                 const dusp_score_limiter_release *limiter, size_t n_total_samples, size_t tile_bytes, int format,
+                                                 int normalise, void *h_out, float *h_peaks);
+
 /* State write-back (SURVEY.md §5 "checkpoint/resume"): after a render, copy the
  * state of `unit` for `instance` into out[] in the layout of the descriptor's
  * state words for that unit's opcode (Osc: phase; Ramp: t, playing; Filter:

@@ -54,6 +54,8 @@
           signals, beside the peak kernel and the meter passes; then the piece with stems as s16 frames with meters=True,
           normalise=2, with true_peak=True and with loudness=-16, and without any new option — the only leg under DUSP_HIP_LIB
           naming the parent's library.  A report: no ratio is fixed in advance.
+  limiter release (--limiter-release; profiles/score_limiter_release.txt) the launches of a limiter call with a release of its own, by HIP
+          events, beside dusp_limit_apply_kernel; the piece with stems at a loudness target with and without limiter_release
   limiter (--limiter; profiles/score_limiter.txt) the limiter's two kernels (dusp_limit_device, kernel by kernel by HIP events:
           dusp_limit_last_ms) over the same twelve signals with a window of 240 samples: the envelope kernel beside
           the true-peak kernel, the gain / apply kernel beside the peak kernel; then the piece with stems as s16 frames at a
@@ -915,6 +917,113 @@ def limiter(scale, ctxs, reps):
     prog.close()
 
 
+def limiter_release(scale, ctxs, reps):
+    """--limiter-release: the launches of a limiter call with a release of its own — envelope, hold, release, mean / apply —
+    by HIP events at a window of 5 ms and releases of 50 ms, 500 ms and 2^22 samples, beside dusp_limit_apply_kernel at the same window in
+    the same run; the call with stems and s16 frames at a loudness target with the limiter engaged, with and without a release; and the
+    calls without the option, the only leg that runs under DUSP_HIP_LIB naming the parent's library."""
+    import torch
+    V, nv, nt = max(64, 8192 // scale), SR // 2, 60 * SR // (1 if scale == 1 else 8)
+    T, B = 8, 2
+    S = 1 + T + B
+    d.configure(SR)
+    ctx = ctxs["default"]
+    has = hasattr(ctx._L, "dusp_limit_release_device")
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    three = lambda xs: (float(np.median(xs)), min(xs), max(xs))
+    line = "  %-78s median %8.3f ms  fastest %8.3f  slowest %8.3f%s"
+    L = 240
+    for C in ((1, 2) if has else ()):
+        source = torch.randn((S + 1, C, nt), dtype=torch.float32, device="cuda") * 0.1
+        block, word = source.clone(), torch.zeros(1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        print("limiter release: %d signals of %d channel(s) of %d samples (%.0f MB) at %d Hz, F = 4, window %d, tiles of %d; launches by HIP events, median, fastest and slowest of %d after a warm-up"
+              % (S + 1, C, nt, block.numel() * 4 / 1e6, SR, L, ctx.limit_release_tile(nt, L, 2400), reps), flush=True)
+        threshold = 0.2  # (two standard deviations of the noise: a few samples in a hundred lie above it)
+        envelope, apply = [], []
+        for r in range(reps + 1):
+            with torch.cuda.stream(stream):
+                block.copy_(source)  # (the limiter works in place: every run limits the same signals)
+            ctx.limit_device(block.data_ptr(), S + 1, C, nt, SR, threshold, L, d_smallest=word.data_ptr(), stream=s)
+            if r:
+                ms = ctx.limit_last_ms()
+                envelope.append(ms[0]), apply.append(ms[1])
+            stream.synchronize()
+        moved = 2 * block.numel() * 4
+        print(line % (("no release: dusp_limit_envelope_kernel<4>",) + three(envelope) + ("",)), flush=True)
+        print(line % (("no release: dusp_limit_apply_kernel, the yardstick (%d bytes a sample of signals)" % (moved // nt),) + three(apply) +
+                      ("   %.0f GB/s moved; reduction %.4f" % (moved / np.median(apply) / 1e6, int(word.item()) / float(L * (1 << 30))),)), flush=True)
+        for R in (2400, 24000, 1 << 22):
+            parts, first = [[], [], [], []], None
+            for r in range(reps + 1):
+                with torch.cuda.stream(stream):
+                    block.copy_(source)
+                ctx.limit_release_device(block.data_ptr(), S + 1, C, nt, SR, threshold, L, R, d_smallest=word.data_ptr(), stream=s)
+                if r:
+                    for k, ms in enumerate(ctx.limit_release_last_ms()):
+                        parts[k].append(ms)
+                if first is None:
+                    with torch.cuda.stream(stream):
+                        first = block.clone()
+                stream.synchronize()
+            print("  release %d samples, d = %d, reduction %.4f, two runs the same bits: %s" % (R, -(-(1 << 30) // R), int(word.item()) / float(L * (1 << 30)), bool(torch.equal(first, block))), flush=True)
+            for k, name in enumerate(("dusp_limit_envelope_kernel<4>", "dusp_limit_hold_kernel (reads q, writes m: 8 bytes a sample)", "dusp_limit_release_kernel (reads m, writes held: 8 bytes a sample)",
+                                      "dusp_limit_mean_apply_kernel (reads and writes the block once)")):
+                extra = "" if k == 0 else "   x%.2f of the apply kernel" % (np.median(parts[k]) / np.median(apply))
+                print(line % (("  " + name,) + three(parts[k]) + (extra,)), flush=True)
+            added = np.median(parts[1]) + np.median(parts[2]) + np.median(parts[3]) - np.median(apply)
+            print("    the three launches cost %.3f ms more than the apply kernel they stand for, x%.2f of it" % (added, added / np.median(apply)), flush=True)
+        del source, block
+    # the whole call: stems' piece — eight fader groups, two stateless buses (a gain each), no master — at one channel, and panned into two
+    note = lambda k: d.Multiply(d.Osc(110.0 + k / 8), d.Ramp(nv, 1, 0).trigger())
+    uni = descriptor.unify([descriptor.extract(note(k)) for k in (0, 1)])
+    params = (110.0 + np.arange(V, dtype=np.float64) / 8).astype(np.float32).reshape(1, V)
+    onsets = np.sort(np.random.RandomState(1).randint(0, nt - nv, V)).astype(np.int64)
+    prog = ctx.build(uni.words)
+    buses = [ctx.build(descriptor.extract(d.Multiply(d.MasterInput(), g)).words) for g in (0.5, 0.25)]
+    track_of = (np.arange(V) % T).astype(np.int32)
+    rs = np.random.RandomState(4)
+    faders, levels = rs.random_sample(T).astype(np.float32), rs.random_sample((B, T)).astype(np.float32)
+
+    def call(**kw):
+        return ctx.render_score_parts([(prog, nv, V, params)], np.zeros(V, dtype=np.uint32), onsets, nt, pinned=True, buses=[(b, None) for b in buses],
+                                      tracks=dict(n_tracks=T, track_of=track_of, programs=[], faders=faders, track_sends=levels), stems=True, **kw)
+
+    def host_clock(run):
+        times = []
+        for r in range(reps + 1):
+            t0 = time.perf_counter()
+            res = run()
+            times.append((time.perf_counter() - t0) * 1e3)
+            del res
+        return three(times[1:])
+
+    row = "  render_score_parts with stems, %-72s median %9.2f ms  fastest %9.2f  slowest %9.2f%s"
+    print("  %d notes of %d samples over %d samples, %d signals, into pinned memory, host clock, median, fastest and slowest of %d after a warm-up; library: %s"
+          % (V, nv, nt, S + 1, reps, "another build's, named by DUSP_HIP_LIB" if os.environ.get("DUSP_HIP_LIB") else "this tree's"), flush=True)
+    window = 240.0 / SR
+    for name, kw in (("one channel", {}), ("two channels (pans)", dict(pans=np.linspace(-1, 1, V)))):
+        frames = host_clock(lambda: call(format="s16", normalise=2, **kw))
+        print(row % ((name + ", s16, normalise=2, no new option",) + frames + ("",)), flush=True)
+        loud = host_clock(lambda: call(format="s16", loudness=-16.0, **kw))
+        print(row % ((name + ", s16, loudness=-16",) + loud + ("",)), flush=True)
+        _, got = call(format="s16", loudness=-16.0, **kw)
+        high = float(got["lufs"][-1] + 20 * np.log10(10 ** (-1 / 20) / got["true_peak"].max()) + 6.0)  # (6 dB above where the largest true peak meets the ceiling: engaged)
+        there = host_clock(lambda: call(format="s16", loudness=high, limiter=True, limiter_window=window, **kw))
+        print(row % ((name + ", s16, loudness=%.2f, limiter=True, engaged" % high,) + there + ("",)), flush=True)
+        for seconds in ((0.05, 0.5) if has else ()):
+            released = host_clock(lambda: call(format="s16", loudness=high, limiter=True, limiter_window=window, limiter_release=seconds, **kw))
+            _, did = call(format="s16", loudness=high, limiter=True, limiter_window=window, limiter_release=seconds, **kw)
+            print(row % ((name + ", ... and limiter_release=%.2f (%d samples)" % (seconds, did["limiter"]["release"]),) + released +
+                         ("   %+.2f ms, x%.3f of the call without a release" % (released[0] - there[0], released[0] / there[0]),)), flush=True)
+            print("    reduction %.4f; gain %.4f, the mix leaves at %.2f LUFS, the largest true peak at %.2f dBTP"
+                  % (did["limiter"]["reduction"], did["gain"], did["lufs"][-1] + 20 * np.log10(did["gain"]), 20 * np.log10(did["true_peak"].max() * did["gain"])), flush=True)
+    for b in buses:
+        b.close()
+    prog.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default="abcd", help="dense cases to run; add p for the piece")
@@ -931,6 +1040,7 @@ def main():
     ap.add_argument("--meters", action="store_true", help="the meters leg alone: the meter kernels pass by pass beside the peak kernel, and the piece with stems with and without meters")
     ap.add_argument("--loudness", action="store_true", help="the loudness leg alone: the true-peak kernel beside the peak kernel and the meter passes, and the piece with stems delivered at a loudness target")
     ap.add_argument("--limiter", action="store_true", help="the limiter leg alone: its two kernels beside the true-peak and peak kernels, and the piece with stems at a loudness target with and without the limiter")
+    ap.add_argument("--limiter-release", action="store_true", help="the limiter's release alone: its launches beside the apply kernel, and the piece with stems at a loudness target with and without a release")
     a = ap.parse_args()
     os.environ["DUSP_WAVE_JIT"] = "2"  # wait for compiled kernels
     ctxs = {"default": context(), "dword8": context(DUSP_MIX_WIDTH=1, DUSP_MIX_DEPTH=8), "one_block": context(DUSP_SCORE_PLAN_KB=1), "log": context(DUSP_JIT_LOG=2)}
@@ -948,6 +1058,8 @@ def main():
         return loudness(a.scale, ctxs, a.reps)
     if a.limiter:
         return limiter(a.scale, ctxs, a.reps)
+    if a.limiter_release:
+        return limiter_release(a.scale, ctxs, a.reps)
     for key in a.cases:
         if key in DENSE:
             (stereo if a.stereo else space if a.space else frac if a.frac else pan if a.pan else dense)(key, a.scale, ctxs, a.reps)
